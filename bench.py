@@ -10,7 +10,7 @@ reference's metric, v6_test.c:60) on N MI355X of one node.
 A step is one factorisation of a freshly generated matrix that is already resident in HBM
 in tile layout; every step is timed in its own synchronised bracket and the K brackets are
 summed, generation happens between them.  The residual of the last step's factor is computed
-(untimed) and printed in the line.
+(untimed) and printed in the line; --dump-outputs DIR writes a fixed sample of it (bench.py: dump_factor).
 The matrix is the same for every GPU count (counter-based generator), so the N-GPU runs
 factor the SAME problem: strong scaling.  Rank 0 prints one JSON line.
 """
@@ -61,7 +61,14 @@ def parse():
     ap.add_argument("--stall-timeout", type=float, default=600.0,
                     help="self-launched ranks (--gpus N without a launcher): seconds without a heartbeat from any rank "
                          "after which the run is declared hung, the ranks are killed and an error line is printed")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the factor the last one computed (a fixed sample of it, at most "
+                         "64 MB) as DIR/<name>.npy; the same arguments give the same inputs, so two builds compare "
+                         "output for output")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 # ---------------------------------------------------------------- heartbeat of a supervised rank
@@ -200,6 +207,52 @@ def load_pmc_traffic():
         return None
 
 
+DUMP_BUDGET = 64 << 20  # bytes, all arrays of --dump-outputs together
+DUMP_TILES = 32         # lower tiles sampled besides the first and the last diagonal tile
+DUMP_PER_TILE = 16384   # entries sampled per tile
+
+
+def dump_factor(d, seed: int, out_dir: str) -> dict:
+    """--dump-outputs: what the timed path hands its caller, the lower factor L in the 1 x 1 descriptor d, as
+    out_dir/<name>.npy in d's precision: L_diag = diag(L) whole, L_sample = DUMP_PER_TILE entries on or below the
+    diagonal of each sampled tile (the first and the last diagonal tile and up to DUMP_TILES more), L_sample_row /
+    L_sample_col = their indices in L (float64).  Tiles and entries are drawn by a generator seeded with `seed` alone,
+    so two runs with the same arguments sample the same places."""
+    import numpy as np
+
+    N, B, nt = d.lm, d.mb, d.mt
+    rng = np.random.default_rng(seed)
+    lower = nt * (nt + 1) // 2  # lower tiles, column by column: index -> (I, J)
+    col_start = np.cumsum([0] + [nt - J for J in range(nt)])
+    picked = {(0, 0), (nt - 1, nt - 1)}
+    for x in rng.choice(lower, size=min(lower, DUMP_TILES), replace=False):
+        J = int(np.searchsorted(col_start, x, side="right")) - 1
+        picked.add((J + int(x - col_start[J]), J))
+    diag = np.empty(N, dtype=d.np_dtype)
+    vals, rows, cols = [], [], []
+    for I, J in sorted(picked | {(I, I) for I in range(nt)}, key=lambda t: (t[1], t[0])):
+        t = d.download_tile(I, J)
+        m, n = min(B, N - I * B), min(B, N - J * B)
+        if I == J:
+            diag[I * B:I * B + m] = np.diagonal(t)[:m]
+        if (I, J) not in picked:
+            continue
+        r, c = rng.integers(0, m, DUMP_PER_TILE), rng.integers(0, n, DUMP_PER_TILE)
+        if I == J:
+            r, c = np.maximum(r, c), np.minimum(r, c)
+        vals.append(t[r, c])
+        rows.append(I * B + r)
+        cols.append(J * B + c)
+    out = {"L_diag": diag, "L_sample": np.concatenate(vals),
+           "L_sample_row": np.concatenate(rows).astype(np.float64), "L_sample_col": np.concatenate(cols).astype(np.float64)}
+    nbytes = sum(v.nbytes for v in out.values())
+    assert nbytes <= DUMP_BUDGET, nbytes
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return {"dir": out_dir, "arrays": sorted(out), "bytes": nbytes, "tiles_sampled": len(picked)}
+
+
 def lib_counters() -> int:
     from dense_linear_app_amd._lib import lib
 
@@ -241,6 +294,7 @@ def run_single(a) -> dict:
         upd_flops += st["update_flops"]
         upd_launches += st["update_launches"]
     ch.set_profiling(False)
+    dump = dump_factor(d, a.seed, a.dump_outputs) if a.dump_outputs else None  # (before the step below overwrites it)
     # one step more, outside the K timed ones, WITHOUT the library's brackets: what the event records and the closing
     # waits of the profiled steps cost (they add no dependency; this puts the number on record)
     ch.CHAMELEON_dplgsy_Tile(float(N), ch.ChamLower, d, a.seed)
@@ -256,7 +310,7 @@ def run_single(a) -> dict:
     return {"elapsed": elapsed, "upd_ms": upd_ms, "upd_flops": upd_flops, "upd_launches": upd_launches,
             "regimes": ch.last_potrf_regimes(),  # of the last (un-bracketed) step: the schedule the timed steps ran too
             "residual": res, "probe": probe, "kernel": kernel, "calibration": ch.calibration(),
-            "counters": bool(lib_counters()), "unprofiled_ms": unprofiled * 1e3}
+            "counters": bool(lib_counters()), "unprofiled_ms": unprofiled * 1e3, "dump": dump}
 
 
 def run_multi(a) -> dict:
@@ -369,6 +423,16 @@ def run_multi(a) -> dict:
     t = torch.tensor([elapsed], dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     stats = dd.dist_last_stats()
+    dump = None
+    if a.dump_outputs:  # the last timed step's factor, gathered on rank 0 before the step below overwrites it
+        full = None
+        if rank == 0:
+            dt = ch.ChamRealDouble if a.dtype == "f64" else ch.ChamRealFloat
+            full = ch.CHAMELEON_Desc_Create(None, dt, a.tile, a.tile, a.tile * a.tile, a.N, a.N, 0, 0, a.N, a.N, 1, 1)
+        dd.gather_lower(eng.desc, full, 0)
+        if rank == 0:
+            dump = dump_factor(full, a.seed, a.dump_outputs)
+            ch.CHAMELEON_Desc_Destroy(full)
     # one more step, untimed, with the library's HIP-event brackets on: every rank's own update-kernel time and the
     # device time of its whole schedule, so that a scaling curve explains itself (update alone vs what the rank waited)
     ch.set_profiling(True)
@@ -411,7 +475,7 @@ def run_multi(a) -> dict:
             res = ch.residual_plgsy(full, float(a.N), a.seed)
             ch.CHAMELEON_Desc_Destroy(full)
     out = {"elapsed": float(t.item()), "rank": rank, "grid": f"{P}x{Q}", "residual": res, "dist": stats,
-           "backend": backend, "fallback": fallback}
+           "backend": backend, "fallback": fallback, "dump": dump}
     dist.barrier()
     dist.destroy_process_group()
     return out
@@ -601,6 +665,8 @@ def main() -> int:
                 line["cpu_baseline"]["extra"] = cpu_baseline(a.cpu_extra_N, a.cpu_tile, a.seed, vendor=False)
     if r.get("residual") is not None:
         line["residual"] = r["residual"]
+    if r.get("dump"):
+        line["outputs"] = r["dump"]
     if r.get("dist"):
         line["config"]["exchange"] = {"backend": r["backend"], "fallback": r.get("fallback"), "host_issue_us_per_wave": round(r["dist"]["issue_us_per_wave"], 1),
                                       "sends_per_rank0": r["dist"]["sends"], "bytes_sent_rank0": r["dist"]["bytes_sent"],

@@ -9,6 +9,8 @@ What is produced, and from what:
       known answers and SHA-256 of the raw bytes of the generated matrix and of
       every lower tile for (N,B) = (12,4), (10,4) [ragged: zero-padded edge],
       (1024,256); load_params / parse_int_str cases; block ids.
+  ref_agreement.json  -- SHA-256 of the reference's input and its column-0 blocks
+      (B=5) for N = 7, 12, 100, 333.
   spd_N12.npy         -- the full 12x12 reference input (C1/C2 default N=12,B=4).
   tileops_B64.npz     -- inputs + outputs of the four tile ops with the worker's
       flag sets (worker_distrib.cpp:238,323,416,511) computed by scipy's bundled
@@ -98,8 +100,24 @@ def reference_vm_rel_error():
     return len(vals)
 
 
+def reference_agreement():
+    """ref_agreement.json: SHA-256 of the reference's input and of its column-0 blocks (B = 5) for the orders
+    test_reference_build_agrees_when_present compares, so that the comparison runs where the reference is absent."""
+    ref = orc.RefClient()
+    B = 5
+    out = {"source": "reference functions compiled by oracle/build_ref.sh", "B": B, "cases": {}}
+    for N in (7, 12, 100, 333):
+        A = ref.reference_input(N)
+        out["cases"][str(N)] = {"sha_A": sha(A),
+                                "col0_blocks_sha": [sha(ref.extract_block(A, B, bi, 0)) for bi in range((N + B - 1) // B)]}
+    with open(os.path.join(HERE, "ref_agreement.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+    return len(out["cases"])
+
+
 def main():
     print("reference_vm_rel_error.json:", reference_vm_rel_error(), "cases")
+    print("ref_agreement.json:", reference_agreement(), "cases")
     ref = orc.RefClient()
     out = {"source": "reference functions compiled by oracle/build_ref.sh", "cases": {}}
     for N, B in ((12, 4), (10, 4), (1024, 256)):

@@ -107,19 +107,33 @@ def test_pxq_rehearsal_ragged_order_and_odd_tiles(P, Q, N, B, cham, orc):
 
 
 def test_one_by_one_through_the_rehearsal_is_the_walker(cham):
-    """p = q = 1 is the same code path as chol_potrf_tile on an ordinary descriptor: bit-identical factors."""
-    from dense_linear_app_amd import distributed as dd
+    """p = q = 1 is the same code path as chol_potrf_tile on an ordinary descriptor: bit-identical factors.
+    In a fresh process with the flow form of the tile POTRF off (CHOLMI_FLOW=0; the switches are read once): that form
+    needs ST_CX and ST_PANEL on hardware queues of their own, which every rank context probes for its own streams, and
+    the rehearsal's contexts, created after the main one, can lose that probe and run the diagonal-block form instead,
+    which rounds differently in the last bits.  The flow form is checked by test_gpu_full.py."""
+    import subprocess
+    import tempfile
 
-    ch = cham
     N, B = 4096, 512
-    info, full, _ = dd.rehearse(N, B, 1, 1)
-    assert info == 0
-    d = ch.CHAMELEON_Desc_Create(None, ch.ChamRealDouble, B, B, B * B, N, N, 0, 0, N, N, 1, 1)
-    ch.CHAMELEON_dplgsy_Tile(float(N), ch.ChamLower, d, 42)
-    assert ch.CHAMELEON_dpotrf_Tile(ch.ChamLower, d) == 0
-    assert np.array_equal(np.tril(full.to_lapack()), np.tril(d.to_lapack()))
-    ch.CHAMELEON_Desc_Destroy(full)
-    ch.CHAMELEON_Desc_Destroy(d)
+    with tempfile.TemporaryDirectory() as tmp:
+        code = (
+            "import sys, numpy as np; sys.path.insert(0, %r)\n"
+            "from dense_linear_app_amd import chameleon as ch\n"
+            "from dense_linear_app_amd import distributed as dd\n"
+            "from dense_linear_app_amd._lib import lib\n"
+            "ch.CHAMELEON_Init(1, 1)\n"
+            "info, full, _ = dd.rehearse(%d, %d, 1, 1)\n"
+            "d = ch.CHAMELEON_Desc_Create(None, ch.ChamRealDouble, %d, %d, %d, %d, %d, 0, 0, %d, %d, 1, 1)\n"
+            "ch.CHAMELEON_dplgsy_Tile(float(%d), ch.ChamLower, d, 42)\n"
+            "info_w = ch.CHAMELEON_dpotrf_Tile(ch.ChamLower, d)\n"
+            "np.save(%r + '/R.npy', np.tril(full.to_lapack())); np.save(%r + '/W.npy', np.tril(d.to_lapack()))\n"
+            "print('info', info, info_w, 'flow_waves', lib().chol_debug_flow_waves())\n"
+        ) % (ROOT, N, B, B, B, B * B, N, N, N, N, N, tmp, tmp)
+        r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, CHOLMI_FLOW="0"), capture_output=True,
+                           text=True, timeout=600)
+        assert r.returncode == 0 and "info 0 0 flow_waves 0" in r.stdout, (r.stdout, r.stderr[-2000:])
+        assert np.array_equal(np.load(tmp + "/R.npy"), np.load(tmp + "/W.npy"))
 
 
 def test_rehearsal_reports_a_bad_pivot_on_every_rank(cham):
