@@ -218,6 +218,24 @@ def CHAMELEON_dposv_Tile(uplo: int, A: Desc, B: Desc) -> int:
     return check("chol_posv_tile", lib().chol_posv_tile(uplo, A.handle, B.handle))
 
 
+def CHAMELEON_dsposv_Tile(uplo: int, A: Desc, B: Desc, X: Desc) -> tuple[int, int]:
+    """Mixed-precision solve (LAPACK DSPOSV): fp32 factor of A, fp64 iterative refinement of X; only the `uplo`
+    triangle of A is read and B is never written.  Returns (info, iter): iter >= 0 is the number of refinement
+    steps (A unchanged); iter < 0 (-2 fp32 overflow, -3 fp32 factor not SPD, -31 no convergence) means X was
+    solved by dposv in fp64, A then holds the fp64 factor and info > 0 says A is not positive definite."""
+    it = C.c_int()
+    info = check("chol_dsposv_tile", lib().chol_dsposv_tile(uplo, A.handle, B.handle, X.handle, C.byref(it)))
+    return info, it.value
+
+
+def last_dsposv_stats() -> dict:
+    """Phases of the last CHAMELEON_dsposv_Tile [ms] (chol_last_dsposv_stats)."""
+    v = (C.c_double * 8)()
+    check("chol_last_dsposv_stats", lib().chol_last_dsposv_stats(v))
+    return {"total_ms": v[0], "convert_ms": v[1], "factor_ms": v[2], "solve_ms": v[3], "residual_ms": v[4],
+            "solves": int(v[5]), "residuals": int(v[6])}
+
+
 CHAMELEON_spotrs_Tile = CHAMELEON_dpotrs_Tile
 CHAMELEON_sposv_Tile = CHAMELEON_dposv_Tile
 CHAMELEON_slacpy_Tile = CHAMELEON_dlacpy_Tile
@@ -294,4 +312,4 @@ def set_profiling(on: bool) -> None:
 
 
 __all__ = [n for n in dir() if n.startswith(("CHAMELEON_", "Cham"))] + [
-    "Desc", "CholmiError", "residual_plgsy", "residual_plgsy_inf", "last_potrf_stats", "set_profiling", "set_device", "set_rank"]
+    "Desc", "CholmiError", "residual_plgsy", "residual_plgsy_inf", "last_potrf_stats", "last_dsposv_stats", "set_profiling", "set_device", "set_rank"]

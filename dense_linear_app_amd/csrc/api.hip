@@ -50,6 +50,12 @@ struct Ctx {
   void *wc_winv = nullptr;
   int *d_binfo = nullptr;  // device info words of asynchronously factored tiles (chol_potrf_batch), a ring
   unsigned binfo_next = 0;
+  // chol_dsposv_tile's scratch, grown on demand and kept (not g.work: potrs_impl and lange grow and reuse that one):
+  // the fp32 factor (n x n tile image), the fp32 right-hand side / correction (n x nrhs), the residual's per-block
+  // partial sums, and the column maxima + overflow flag
+  void *mx[4] = {nullptr, nullptr, nullptr, nullptr};
+  size_t mx_bytes[4] = {0, 0, 0, 0};
+  double mx_stats[8] = {};  // of the last chol_dsposv_tile (chol_last_dsposv_stats)
   std::string last_error;
 };
 
@@ -171,6 +177,18 @@ int ensure_stage(int idx, size_t bytes) {
   g.stage_bytes[idx] = 0;
   HIPCHECK(hipMalloc(&g.stage[idx], bytes));
   g.stage_bytes[idx] = bytes;
+  return 0;
+}
+
+int ensure_mx(int idx, size_t bytes) {
+  if (g.mx_bytes[idx] >= bytes) return 0;
+  if (g.mx[idx]) HIPCHECK(hipFree(g.mx[idx]));
+  g.mx[idx] = nullptr;
+  g.mx_bytes[idx] = 0;
+  bytes = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
+  HIPCHECK(hipMalloc(&g.mx[idx], bytes));
+  HIPCHECK(hipMemset(g.mx[idx], 0, bytes));
+  g.mx_bytes[idx] = bytes;
   return 0;
 }
 
@@ -1024,6 +1042,11 @@ int chol_finalize(void) {
   g.wc_winv = nullptr;
   if (g.d_binfo) (void)hipFree(g.d_binfo);
   g.d_binfo = nullptr;
+  for (int i = 0; i < 4; ++i) {
+    if (g.mx[i]) (void)hipFree(g.mx[i]);
+    g.mx[i] = nullptr;
+    g.mx_bytes[i] = 0;
+  }
   tx_destroy();
   g.wc_ptr = nullptr;
   g.wc_version = 0;
@@ -1850,6 +1873,168 @@ int chol_posv_tile(int uplo, chol_desc_t *A, chol_desc_t *B) {
   const int info = chol_potrf_tile(uplo, A);
   if (info != 0) return info;  // > 0: not positive definite, B untouched (LAPACK dposv)
   return chol_potrs_tile(uplo, A, B);
+}
+
+// ---------------------------------------------------------------- mixed-precision solve (LAPACK DSPOSV)
+// Factor an fp32 copy of A, solve in fp32, refine X in fp64 with residuals R = B - A X read from the stored triangle
+// (mixed.hip) until every column satisfies max|R(:,j)| <= max|X(:,j)| anrm eps sqrt(n); A and B are only read.
+// *iter < 0 (no convergence, an entry that does not fit in fp32, fp32 factor not SPD): X <- B and dposv on A, X.
+namespace {
+constexpr int DSPOSV_ITMAX = 30;
+struct MxTimer {  // the phases of the last call, on ST_MAIN (chol_last_dsposv_stats)
+  hipEvent_t e[2] = {nullptr, nullptr};
+  ~MxTimer() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+  int start() {
+    for (hipEvent_t &x : e)
+      if (!x) HIPCHECK(hipEventCreate(&x));
+    HIPCHECK(hipEventRecord(e[0], g.r.st[ST_MAIN]));
+    return 0;
+  }
+  int stop(double *acc) {  // (the phases end with a stream synchronisation of their own or are followed by one)
+    HIPCHECK(hipEventRecord(e[1], g.r.st[ST_MAIN]));
+    HIPCHECK(hipEventSynchronize(e[1]));
+    float ms = 0;
+    HIPCHECK(hipEventElapsedTime(&ms, e[0], e[1]));
+    *acc += ms;
+    return 0;
+  }
+};
+}  // namespace
+
+// -> *iter (>= 0: refinement steps; or -2 / -3 / -31 for the fallback), or a negative status
+static int dsposv_mixed(int uplo, chol_desc *A, chol_desc *B, chol_desc *X, int *iter) {
+  hipStream_t s = g.r.st[ST_MAIN];
+  const int up = uplo == CHOL_UPPER ? 1 : 0, nrhs = B->ln;
+  const TileGeo ga = geo_of(A), gx = geo_of(B);
+  double *st = g.mx_stats;  // total, conversions + norm, fp32 factor, fp32 solves, residual passes, #solves, #passes, -
+  std::fill(st, st + 8, 0.0);
+  const size_t rf_bytes = (size_t)B->lmt * B->lnt * B->bsizi * sizeof(float);
+  int rc = ensure_mx(0, (size_t)A->lmt * A->lnt * A->bsizi * sizeof(float));
+  if (!rc) rc = ensure_mx(1, rf_bytes);
+  if (!rc) rc = ensure_mx(2, sym_resid_part_bytes(ga, nrhs));
+  if (!rc) rc = ensure_mx(3, (size_t)(2 * nrhs + 2) * sizeof(unsigned long long));
+  if (rc) {
+    (void)hipGetLastError();
+    return fail(CHOL_ERR_OUT_OF_MEMORY, "dsposv_tile: scratch allocation failed");
+  }
+  float *Af = reinterpret_cast<float *>(g.mx[0]), *Rf = reinterpret_cast<float *>(g.mx[1]);
+  double *part = reinterpret_cast<double *>(g.mx[2]);
+  unsigned long long *colmax = reinterpret_cast<unsigned long long *>(g.mx[3]);
+  int *flag = reinterpret_cast<int *>(colmax + 2 * nrhs);
+  std::vector<unsigned long long> hmax(2 * nrhs + 1);
+  // fp32 descriptors over the scratch: A's and B's geometry (and A's work list)
+  chol_desc Ad = *A, Rd = *B;
+  Ad.dtype = Rd.dtype = CHOL_REAL_FLOAT;
+  Ad.esize = Rd.esize = sizeof(float);
+  Ad.mat = Af;
+  Rd.mat = Rf;
+  Ad.owns = Rd.owns = false;
+  Ad.version = Rd.version = 0;
+  Rd.d_list = nullptr;
+  MxTimer tt, tp;
+  if ((rc = tt.start())) return rc;
+  // anrm, then B and A to fp32 (-2 where an entry does not fit)
+  if ((rc = tp.start())) return rc;
+  HIPCHECK(hipMemsetAsync(colmax, 0, (2 * nrhs + 2) * sizeof(unsigned long long), s));
+  HIPCHECK(hipMemsetAsync(Rf, 0, rf_bytes, s));  // (the solve runs on whole tiles: padding must be finite)
+  launch_sym_inf_norm(s, ga, up, (const double *)A->mat, part, colmax);
+  launch_vec_to_f32(s, gx, (const double *)B->mat, Rf, flag);
+  launch_sym_to_f32(s, ga, up, (const double *)A->mat, Af, flag);
+  HIPCHECK(hipGetLastError());
+  unsigned long long anrm_bits = 0;
+  int hflag = 0;
+  HIPCHECK(hipMemcpyAsync(&anrm_bits, colmax, sizeof anrm_bits, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(&hflag, flag, sizeof hflag, hipMemcpyDeviceToHost, s));
+  if ((rc = tp.stop(&st[1]))) return rc;
+  double anrm;
+  memcpy(&anrm, &anrm_bits, sizeof anrm);
+  const double cte = anrm * std::ldexp(1.0, -53) * std::sqrt((double)A->lm);
+  auto finish = [&](int it) {
+    *iter = it;
+    return tt.stop(&st[0]);
+  };
+  if (hflag) return finish(-2);
+  // the fp32 factor: info > 0 -> -3; an error (CHOL_ERR_DEVICE_WAIT, HIP) is returned as it is
+  if ((rc = tp.start())) return rc;
+  rc = potrf_impl<float>(&Ad);
+  if (rc < 0) return rc;
+  if (int r2 = tp.stop(&st[2])) return r2;
+  if (rc > 0) return finish(-3);
+  auto solve = [&]() -> int {  // Rf <- A^{-1} Rf in fp32
+    int r = tp.start();
+    if (!r) r = potrs_impl<float>(&Ad, &Rd);
+    if (!r) r = tp.stop(&st[3]);
+    st[5] += 1;
+    return r;
+  };
+  if ((rc = solve())) return rc;
+  launch_vec_update(s, gx, Rf, (double *)X->mat, /*assign=*/true);
+  for (int it = 0;; ++it) {
+    // R = B - A X in fp64, rounded into Rf; the column maxima of R and X
+    if ((rc = tp.start())) return rc;
+    HIPCHECK(hipMemsetAsync(colmax, 0, (2 * nrhs + 2) * sizeof(unsigned long long), s));
+    launch_sym_resid(s, ga, up, (const double *)A->mat, gx, (const double *)X->mat, (const double *)B->mat, part, Rf,
+                     colmax, flag);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(hmax.data(), colmax, (2 * nrhs + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if ((rc = tp.stop(&st[4]))) return rc;
+    st[6] += 1;
+    bool done = true;
+    for (int j = 0; j < nrhs && done; ++j) {
+      double rn, xn;
+      memcpy(&rn, &hmax[j], sizeof rn);
+      memcpy(&xn, &hmax[nrhs + j], sizeof xn);
+      done = rn <= xn * cte;  // (a NaN residual does not converge)
+    }
+    if (done) return finish(it);
+    if (it == DSPOSV_ITMAX) return finish(-DSPOSV_ITMAX - 1);
+    if (hmax[2 * nrhs] & 0xffffffffull) return finish(-2);  // (the flag: the low word on a little-endian device)
+    if ((rc = solve())) return rc;
+    launch_vec_update(s, gx, Rf, (double *)X->mat, /*assign=*/false);
+  }
+}
+
+int chol_dsposv_tile(int uplo, chol_desc_t *A, chol_desc_t *B, chol_desc_t *X, int *iter) {
+  return with_views({{A, false}, {B, false}, {X, false}}, [&]() -> int {
+  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "dsposv_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "dsposv_tile: uplo");
+  int rc = resident_whole("dsposv_tile", A);
+  if (rc) return rc;
+  if (A->dtype != CHOL_REAL_DOUBLE) return fail(-2, "dsposv_tile: A must be fp64");
+  if (A->mt != A->nt || A->lm != A->ln) return fail(-2, "dsposv_tile: A is not square");
+  if (!B) return fail(-3, "dsposv_tile: B is NULL");
+  if ((rc = resident_whole("dsposv_tile", B))) return rc;
+  if (B->dtype != CHOL_REAL_DOUBLE || B->lm != A->lm || B->mb != A->mb || B->mbi != A->mbi || B->mat == A->mat)
+    return fail(-3, "dsposv_tile: B must be fp64 with A's order and tile size");
+  if (!X) return fail(-4, "dsposv_tile: X is NULL");
+  if ((rc = resident_whole("dsposv_tile", X))) return rc;
+  if (!same_geometry(B, X)) return fail(-4, "dsposv_tile: X must have B's shape, tile size and type");
+  if (X->mat == A->mat || X->mat == B->mat) return fail(-4, "dsposv_tile: X aliases A or B");
+  if (!iter) return fail(-5, "dsposv_tile: iter is NULL");
+  if (A->user_mat || B->user_mat || X->user_mat)
+    return fail(CHOL_ERR_NOT_SUPPORTED, "dsposv_tile: sub-matrix views over a user buffer");
+  if (A->mbi % MACRO) return fail(CHOL_ERR_NOT_SUPPORTED, "dsposv_tile: stored tile edge must be a multiple of 128");
+  CHECK_WINV(A, "dsposv_tile");
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  rc = dsposv_mixed(uplo, A, B, X, iter);
+  if (rc < 0) return rc;
+  if (*iter >= 0) return 0;
+  // fallback (LAPACK dsposv): X <- B, then dposv in fp64 -- A then holds the fp64 factor
+  launch_lacpy<double>(g.r.st[ST_MAIN], geo_of(B), 0, (const double *)B->mat, (double *)X->mat);
+  HIPCHECK(hipStreamSynchronize(g.r.st[ST_MAIN]));
+  const int info = chol_potrf_tile(uplo, A);
+  if (info != 0) return info;
+  return chol_potrs_tile(uplo, A, X);
+  });
+}
+
+int chol_last_dsposv_stats(double *out8) {
+  if (!out8) return fail(-1, "last_dsposv_stats: NULL");
+  std::copy(g.mx_stats, g.mx_stats + 8, out8);
+  return 0;
 }
 
 // valid extent of tile (I,J) inside the matrix (edge tiles are smaller)

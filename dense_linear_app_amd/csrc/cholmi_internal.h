@@ -265,6 +265,24 @@ void launch_lange(hipStream_t s, const TileGeo &g, int kind, const T *A, double 
 template <typename T>
 void launch_lauum_lower(hipStream_t s, const T *L, T *out, int nt, int mbs);
 
+// ---- launchers (mixed.hip): the fp64 side of chol_dsposv_tile on a single-process image (mbs % 128 == 0) ----
+// ga: the n x n matrix (only the Lower / Upper stored triangle is read), gx: the n x nrhs images (same mbs / mbu).
+// part: sym_resid_part_bytes(ga, nrhs) of scratch; colmax: 2 nrhs zeroed words, max |R(:,j)| then max |X(:,j)| as
+// double bit patterns; Rf: R rounded to fp32 at the same positions; *flag |= 1 where an entry does not fit in fp32.
+int sym_resid_width(int nrhs);
+size_t sym_resid_part_bytes(const TileGeo &ga, int nrhs);
+void launch_sym_resid(hipStream_t s, const TileGeo &ga, int upper, const double *A, const TileGeo &gx, const double *X,
+                      const double *B, double *part, float *Rf, unsigned long long *colmax, int *flag);
+// colmax[0] <- bits of the infinity norm of the symmetric matrix (row sums of |A| from the stored triangle)
+void launch_sym_inf_norm(hipStream_t s, const TileGeo &ga, int upper, const double *A, double *part,
+                         unsigned long long *colmax);
+// the stored triangle -> the Lower fp32 tile image (every tile I >= J written; zeros in the unreferenced half of the
+// diagonal tiles, the identity outside the matrix)
+void launch_sym_to_f32(hipStream_t s, const TileGeo &ga, int upper, const double *A, float *Af, int *flag);
+void launch_vec_to_f32(hipStream_t s, const TileGeo &gx, const double *B, float *Bf, int *flag);
+// X := (double) C (assign) or X += (double) C
+void launch_vec_update(hipStream_t s, const TileGeo &gx, const float *C, double *X, bool assign);
+
 // out-of-place transposes of `count` mb x mb tiles (mb % 64 == 0)
 template <typename T>
 void launch_tiles_transpose(hipStream_t s, const T *in, long istride, T *out, long ostride, int mb, int count);

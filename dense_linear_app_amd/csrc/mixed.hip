@@ -1,0 +1,289 @@
+// The fp64 side of the mixed-precision SPD solve (api.hip: chol_dsposv_tile, LAPACK DSPOSV): the symmetric
+// residual R = B - A X read from ONE stored triangle of A, the fp64 -> fp32 conversions with overflow detection,
+// and the fp64 update X += C.  Single-process, device-resident tile images: stored tiles of mbs x mbs elements
+// (mbs a multiple of 128) of which the caller's tile is the leading mbu x mbu part (TileGeo, cholmi_internal.h).
+//
+// The residual works on the 128 x 128 blocks of the stored image.  Block row P of the image is stored rows
+// [128 P, 128 P + 128): tile P / (mbs / 128), so every block lies inside one tile and padding is masked per entry.
+// One workgroup per stored block of the triangle (pair (P, Q), P >= Q, of the symmetric matrix) reads the block
+// once and produces both of its products: A(P,Q) X_Q (goes to R_P) and A(P,Q)^T X_P (goes to R_Q); a diagonal
+// block is made symmetric from its stored half (the diagonal counted once).  The products are written as
+// per-block partial sums and a second pass adds them up in a fixed order -- no floating-point atomics, so the
+// residual is bit-identical from run to run.  The column max-abs values of R and X are by-products of that pass
+// (integer atomicMax on the bit pattern of a non-negative double: order-independent).
+#include <cfloat>
+
+#include "cholmi_internal.h"
+
+namespace cholmi {
+
+namespace {
+
+constexpr int RB = 128;  // residual block edge
+
+__device__ __forceinline__ void atomic_max_abs(unsigned long long *addr, double v) {
+  atomicMax(addr, (unsigned long long)__double_as_longlong(fabs(v)));
+}
+
+// rows of stored block row b that lie inside the matrix (0 ... 128)
+__device__ __forceinline__ int block_valid(const TileGeo &g, int b) {
+  const int bpt = g.mbs / RB, t = b / bpt, r0 = (b % bpt) * RB;
+  const long left = min((long)g.mbu, g.m - (long)t * g.mbu) - r0;
+  return (int)max(0L, min((long)RB, left));
+}
+
+// stored index of entry (stored row s, column j) of an n x ncols image
+__device__ __forceinline__ long vec_index(const TileGeo &g, long s, int j) {
+  const long t = s / g.mbs, rr = s - t * g.mbs;
+  const int tj = j / g.mbu, cj = j - tj * g.mbu;
+  return (t + (long)tj * g.lmt) * g.mbs * g.mbs + rr + (long)cj * g.mbs;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// (P, Q), P >= Q, of pair index P (P + 1) / 2 + Q
+__device__ __forceinline__ void pair_of(long pair, int &P, int &Q) {
+  int p = (int)((sqrt(8.0 * (double)pair + 1.0) - 1.0) * 0.5);
+  while ((long)p * (p + 1) / 2 > pair) --p;
+  while ((long)(p + 1) * (p + 2) / 2 <= pair) ++p;
+  P = p;
+  Q = (int)(pair - (long)p * (p + 1) / 2);
+}
+
+// One stored block of the triangle per workgroup (4 waves, 32 columns each; lane l holds rows 2l, 2l+1).
+// part[((pair * 2 + kind) * NR + j) * 128 + t]: kind 0 -> row t of R_P, kind 1 -> row t of R_Q, rhs column j0 + j.
+// ABS: |A| times a vector of ones (the row sums of |A|: the infinity norm of the symmetric matrix).
+template <int NR, bool ABS>
+__global__ __launch_bounds__(256) void k_sym_resid(TileGeo ga, int upper, const double *__restrict__ A, TileGeo gx,
+                                                   const double *__restrict__ X, int j0, int nr,
+                                                   double *__restrict__ part) {
+  const long pair = blockIdx.x;
+  int P, Q;
+  pair_of(pair, P, Q);
+  // the stored block: Lower at block (P, Q), Upper at (Q, P); its rows are block row br, its columns block column bc
+  const int br = upper ? Q : P, bc = upper ? P : Q;
+  const int bpt = ga.mbs / RB;
+  const double *S = A + ((long)(br / bpt) + (long)(bc / bpt) * ga.lmt) * ga.mbs * ga.mbs + (long)(br % bpt) * RB +
+                    (long)(bc % bpt) * RB * ga.mbs;
+  const int vr = block_valid(ga, br), vc = block_valid(ga, bc);
+  const bool diag = P == Q;
+  __shared__ double sv[NR][RB];        // X rows of the block's columns
+  __shared__ double srow[4][NR][RB];   // per-wave row products
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  for (int e = tid; e < NR * RB; e += 256) {
+    const int j = e / RB, c = e % RB;
+    double v = 0.0;
+    if (c < vc && j < nr) v = ABS ? 1.0 : X[vec_index(gx, (long)bc * RB + c, j0 + j)];
+    sv[j][c] = v;
+  }
+  double u[2][NR];
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      const int r = 2 * lane + k;
+      u[k][j] = (r < vr && j < nr) ? (ABS ? 1.0 : X[vec_index(gx, (long)br * RB + r, j0 + j)]) : 0.0;
+    }
+  __syncthreads();
+  double racc[2][NR], cres[NR];
+#pragma unroll
+  for (int j = 0; j < NR; ++j) racc[0][j] = racc[1][j] = cres[j] = 0.0;
+  const int r = 2 * lane;
+#pragma unroll 8
+  for (int k = 0; k < 32; ++k) {
+    const int c = w * 32 + k;
+    const double2 a = *reinterpret_cast<const double2 *>(S + (long)c * ga.mbs + r);
+    // entries outside the matrix (and, in a diagonal block, the unreferenced half) by selection: they may hold NaN
+    double a0 = (r < vr && c < vc) ? a.x : 0.0, a1 = (r + 1 < vr && c < vc) ? a.y : 0.0;
+    if (ABS) a0 = fabs(a0), a1 = fabs(a1);
+    // the row product takes the stored half with the diagonal, the column product the strict half
+    double ra0 = a0, ra1 = a1, ca0 = a0, ca1 = a1;
+    if (diag) {
+      ra0 = (upper ? r <= c : r >= c) ? a0 : 0.0;
+      ra1 = (upper ? r + 1 <= c : r + 1 >= c) ? a1 : 0.0;
+      ca0 = (upper ? r < c : r > c) ? a0 : 0.0;
+      ca1 = (upper ? r + 1 < c : r + 1 > c) ? a1 : 0.0;
+    }
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      const double v = sv[j][c];
+      racc[0][j] = fma(ra0, v, racc[0][j]);
+      racc[1][j] = fma(ra1, v, racc[1][j]);
+      const double s = wave_sum(fma(ca1, u[1][j], ca0 * u[0][j]));
+      if (lane == k) cres[j] = s;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    srow[w][j][r] = racc[0][j];
+    srow[w][j][r + 1] = racc[1][j];
+  }
+  __syncthreads();
+  // Lower: the row product is A(P,Q) X_Q (-> R_P), the column product A(P,Q)^T X_P (-> R_Q); Upper the other way round
+  const int krow = upper ? 1 : 0, kcol = 1 - krow;
+  double *prow = part + (pair * 2 + krow) * NR * RB, *pcol = part + (pair * 2 + kcol) * NR * RB;
+  for (int e = tid; e < NR * RB; e += 256) {
+    const int j = e / RB, t = e % RB;
+    prow[e] = ((srow[0][j][t] + srow[1][j][t]) + srow[2][j][t]) + srow[3][j][t];
+  }
+  if (lane < 32)
+#pragma unroll
+    for (int j = 0; j < NR; ++j) pcol[j * RB + w * 32 + lane] = cres[j];
+}
+
+// R(s, j0 + j) = B - (sum of the partial products of stored row s), added in a fixed order: the blocks (P, Q), Q <= P,
+// of block row P, then (K, P), K >= P.  Rf (may be null): R rounded to fp32, *flag raised where |R| > FLT_MAX.
+// colmax[j]: max |R(:,j)|, colmax[ncols + j]: max |X(:,j)| (X may be null).
+template <int NR>
+__global__ __launch_bounds__(256) void k_sym_resid_reduce(TileGeo ga, TileGeo gx, const double *__restrict__ part,
+                                                          int j0, const double *__restrict__ B,
+                                                          const double *__restrict__ X, float *__restrict__ Rf,
+                                                          unsigned long long *colmax, int *flag) {
+  const int NB = ga.lmt * (ga.mbs / RB);
+  const long s = (long)blockIdx.x * 256 + threadIdx.x;
+  const int j = blockIdx.y;
+  if (s >= (long)NB * RB) return;
+  const int P = (int)(s / RB), t = (int)(s % RB);
+  if (t >= block_valid(ga, P)) return;
+  double sum = 0.0;
+  for (int q = 0; q <= P; ++q) sum += part[(((long)P * (P + 1) / 2 + q) * 2 + 0) * NR * RB + j * RB + t];
+  for (int k = P; k < NB; ++k) sum += part[(((long)k * (k + 1) / 2 + P) * 2 + 1) * NR * RB + j * RB + t];
+  const long idx = vec_index(gx, s, j0 + j);
+  const double rv = (B ? B[idx] : 0.0) - sum;
+  if (Rf) {
+    if (fabs(rv) > (double)FLT_MAX) atomicOr(flag, 1);
+    Rf[idx] = (float)rv;
+  }
+  atomic_max_abs(colmax + j0 + j, rv);
+  if (X) atomic_max_abs(colmax + gx.n + j0 + j, X[idx]);
+}
+
+// The stored triangle of A -> the Lower fp32 tile image chol_potrf_tile factors: one 64 x 64 block of a lower tile
+// (I >= J) per workgroup, staged through LDS so that Upper is read coalesced and transposed on the fly.  The
+// unreferenced half of a diagonal tile is written as zeros, positions outside the matrix as the identity.
+__global__ __launch_bounds__(256) void k_sym_to_f32(TileGeo ga, int upper, const double *__restrict__ A,
+                                                    float *__restrict__ Af, int *flag) {
+  const long tp = blockIdx.y;  // lower tile pair
+  int I, J;
+  pair_of(tp, I, J);
+  const int bpt = ga.mbs / 64, rb = blockIdx.x % bpt, cb = blockIdx.x / bpt;
+  const long ts = (long)ga.mbs * ga.mbs;
+  __shared__ double sh[64][65];
+  // source block: Lower (I, J) block (rb, cb); Upper (J, I) block (cb, rb), read in its own orientation
+  const int si = upper ? J : I, sj = upper ? I : J, sr = upper ? cb : rb, sc = upper ? rb : cb;
+  const double *src = A + ((long)si + (long)sj * ga.lmt) * ts + (long)sr * 64 + (long)sc * 64 * ga.mbs;
+  for (int e = threadIdx.x; e < 64 * 64; e += 256) {
+    const int rr = e % 64, cc = e / 64;
+    sh[cc][rr] = src[rr + (long)cc * ga.mbs];
+  }
+  __syncthreads();
+  float *dst = Af + ((long)I + (long)J * ga.lmt) * ts + (long)rb * 64 + (long)cb * 64 * ga.mbs;
+  for (int e = threadIdx.x; e < 64 * 64; e += 256) {
+    const int rr = e % 64, cc = e / 64;
+    const int r = rb * 64 + rr, c = cb * 64 + cc;  // in-tile position of the destination entry
+    const bool inside = r < ga.mbu && c < ga.mbu && (long)I * ga.mbu + r < ga.m && (long)J * ga.mbu + c < ga.m;
+    float v;
+    if (I == J && r < c) {
+      v = 0.0f;
+    } else if (!inside) {
+      v = (I == J && r == c) ? 1.0f : 0.0f;
+    } else {
+      const double a = upper ? sh[rr][cc] : sh[cc][rr];
+      if (fabs(a) > (double)FLT_MAX) atomicOr(flag, 1);
+      v = (float)a;
+    }
+    dst[rr + (long)cc * ga.mbs] = v;
+  }
+}
+
+// the n x ncols entries of an fp64 image -> fp32 (same positions), *flag raised where |x| > FLT_MAX
+__global__ __launch_bounds__(256) void k_vec_to_f32(TileGeo gx, const double *__restrict__ B, float *__restrict__ Bf,
+                                                    int *flag) {
+  const long total = gx.m * gx.n;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const long gi = e % gx.m;
+    const int j = (int)(e / gx.m);
+    const long idx = vec_index(gx, gi / gx.mbu * gx.mbs + gi % gx.mbu, j);
+    const double b = B[idx];
+    if (fabs(b) > (double)FLT_MAX) atomicOr(flag, 1);
+    Bf[idx] = (float)b;
+  }
+}
+
+// X := (double) C (assign) or X += (double) C over the n x ncols entries
+__global__ __launch_bounds__(256) void k_vec_update(TileGeo gx, const float *__restrict__ C, double *__restrict__ X,
+                                                    int assign) {
+  const long total = gx.m * gx.n;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const long gi = e % gx.m;
+    const int j = (int)(e / gx.m);
+    const long idx = vec_index(gx, gi / gx.mbu * gx.mbs + gi % gx.mbu, j);
+    const double c = (double)C[idx];
+    X[idx] = assign ? c : X[idx] + c;
+  }
+}
+
+int grid_of(long total) { return (int)std::max(1L, std::min((total + 255) / 256, 8192L)); }
+
+template <int NR>
+void resid_pass(hipStream_t s, const TileGeo &ga, int upper, const double *A, const TileGeo &gx, const double *X,
+                const double *B, int j0, int nr, double *part, float *Rf, unsigned long long *colmax, int *flag,
+                bool abs_mode) {
+  const long NB = (long)ga.lmt * (ga.mbs / RB), pairs = NB * (NB + 1) / 2;
+  if (abs_mode)
+    hipLaunchKernelGGL((k_sym_resid<NR, true>), dim3((unsigned)pairs), dim3(256), 0, s, ga, upper, A, gx, X, j0, nr, part);
+  else
+    hipLaunchKernelGGL((k_sym_resid<NR, false>), dim3((unsigned)pairs), dim3(256), 0, s, ga, upper, A, gx, X, j0, nr, part);
+  hipLaunchKernelGGL(k_sym_resid_reduce<NR>, dim3((unsigned)((NB * RB + 255) / 256), (unsigned)nr), dim3(256), 0, s,
+                     ga, gx, part, j0, B, X, Rf, colmax, flag);
+}
+
+}  // namespace
+
+int sym_resid_width(int nrhs) { return nrhs <= 1 ? 1 : nrhs <= 2 ? 2 : nrhs <= 4 ? 4 : 8; }
+
+size_t sym_resid_part_bytes(const TileGeo &ga, int nrhs) {
+  const long NB = (long)ga.lmt * (ga.mbs / RB);
+  return (size_t)(NB * (NB + 1) / 2) * 2 * RB * sym_resid_width(nrhs) * sizeof(double);
+}
+
+void launch_sym_resid(hipStream_t s, const TileGeo &ga, int upper, const double *A, const TileGeo &gx,
+                      const double *X, const double *B, double *part, float *Rf, unsigned long long *colmax, int *flag) {
+  // column blocks of X of up to 8 right-hand sides, each one pass over the stored triangle
+  for (int j0 = 0; j0 < gx.n; j0 += 8) {
+    const int nr = (int)std::min<long>(8, gx.n - j0);
+    switch (sym_resid_width(nr)) {
+      case 1: resid_pass<1>(s, ga, upper, A, gx, X, B, j0, nr, part, Rf, colmax, flag, false); break;
+      case 2: resid_pass<2>(s, ga, upper, A, gx, X, B, j0, nr, part, Rf, colmax, flag, false); break;
+      case 4: resid_pass<4>(s, ga, upper, A, gx, X, B, j0, nr, part, Rf, colmax, flag, false); break;
+      default: resid_pass<8>(s, ga, upper, A, gx, X, B, j0, nr, part, Rf, colmax, flag, false); break;
+    }
+  }
+}
+
+void launch_sym_inf_norm(hipStream_t s, const TileGeo &ga, int upper, const double *A, double *part,
+                         unsigned long long *colmax) {
+  TileGeo g1 = ga;
+  g1.n = 1;
+  resid_pass<1>(s, ga, upper, A, g1, nullptr, nullptr, 0, 1, part, nullptr, colmax, nullptr, true);
+}
+
+void launch_sym_to_f32(hipStream_t s, const TileGeo &ga, int upper, const double *A, float *Af, int *flag) {
+  const long nt = ga.lmt, bpt = ga.mbs / 64;
+  hipLaunchKernelGGL(k_sym_to_f32, dim3((unsigned)(bpt * bpt), (unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, s, ga,
+                     upper, A, Af, flag);
+}
+
+void launch_vec_to_f32(hipStream_t s, const TileGeo &gx, const double *B, float *Bf, int *flag) {
+  hipLaunchKernelGGL(k_vec_to_f32, dim3(grid_of(gx.m * gx.n)), dim3(256), 0, s, gx, B, Bf, flag);
+}
+
+void launch_vec_update(hipStream_t s, const TileGeo &gx, const float *C, double *X, bool assign) {
+  hipLaunchKernelGGL(k_vec_update, dim3(grid_of(gx.m * gx.n)), dim3(256), 0, s, gx, C, X, assign ? 1 : 0);
+}
+
+}  // namespace cholmi

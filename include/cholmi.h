@@ -202,6 +202,23 @@ int chol_geadd_tile(int trans, double alpha, chol_desc_t *A, double beta, chol_d
 int chol_potrs_tile(int uplo, chol_desc_t *A, chol_desc_t *B);
 int chol_posv_tile(int uplo, chol_desc_t *A, chol_desc_t *B);
 
+/* CHAMELEON_dsposv_Tile(uplo, A, B, X, &iter) -- LAPACK DSPOSV semantics on device-resident single-process
+ * descriptors (the descriptor rules of chol_potrs_tile; A: n x n fp64, B and X: n x nrhs fp64, same tile size).
+ * Factors an fp32 copy of A, solves in fp32 and refines X with fp64 residuals R = B - A X until every column
+ * satisfies max|R(:,j)| <= max|X(:,j)| * anrm * eps * sqrt(n) (anrm = ||A||_inf, eps = 2^-53), at most 30 steps.
+ * Only the `uplo` triangle of A is read; B is never written.  *iter on return:
+ *   >= 0  refinement steps taken; A is unchanged
+ *   -2    an entry of A, B or a residual does not fit in fp32
+ *   -3    the fp32 factorisation reported info > 0
+ *   -31   no convergence in 30 steps
+ * On every negative *iter, X <- B and chol_posv_tile(uplo, A, X) run in fp64: A then holds the fp64 factor and the
+ * return value is that factorisation's info (> 0: A is not SPD, X unspecified).
+ * Argument errors return negative positions (A not fp64, B / X not matching A, X aliasing A or B, iter NULL). */
+int chol_dsposv_tile(int uplo, chol_desc_t *A, chol_desc_t *B, chol_desc_t *X, int *iter);
+/* Phases of the last chol_dsposv_tile [ms]: total, conversions + ||A||_inf, fp32 factor, fp32 solves (all),
+ * residual passes (all), then the number of fp32 solves and of residual passes; out8[7] is 0. */
+int chol_last_dsposv_stats(double *out8);
+
 /* CHAMELEON_Lapack_to_Tile / Tile_to_Lapack equivalents (host LAPACK layout
  * <-> descriptor storage); single-process descriptors only. */
 int chol_lapack_to_tile(const void *A, int lda, chol_desc_t *desc);
