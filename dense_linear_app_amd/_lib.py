@@ -56,6 +56,9 @@ def lib() -> C.CDLL:
         "chol_posv_tile": ([i, vp, vp], i),
         "chol_dsposv_tile": ([i, vp, vp, vp, C.POINTER(i)], i),
         "chol_last_dsposv_stats": ([C.POINTER(d)], i),
+        "chol_trtri_tile": ([i, i, vp], i),
+        "chol_potri_tile": ([i, vp], i),
+        "chol_poinv_tile": ([i, vp], i),
         "chol_lapack_to_tile": ([vp, i, vp], i),
         "chol_tile_to_lapack": ([vp, vp, i], i),
         "chol_tile_upload": ([vp, i, i, vp], i),

@@ -236,12 +236,33 @@ def last_dsposv_stats() -> dict:
             "solves": int(v[5]), "residuals": int(v[6])}
 
 
+def CHAMELEON_dtrtri_Tile(uplo: int, diag: int, A: Desc) -> int:
+    """LAPACK DTRTRI: the `uplo` triangle of A <- its inverse, in place (diag must be ChamNonUnit).  Returns info
+    (> 0: A(info, info) is exactly zero, A unchanged)."""
+    return check("chol_trtri_tile", lib().chol_trtri_tile(uplo, diag, A.handle))
+
+
+def CHAMELEON_dpotri_Tile(uplo: int, A: Desc) -> int:
+    """LAPACK DPOTRI: A holds the Cholesky factor of CHAMELEON_dpotrf_Tile; its `uplo` triangle <- that of inv(A).
+    Returns info (> 0: a zero on the factor's diagonal, A unchanged)."""
+    return check("chol_potri_tile", lib().chol_potri_tile(uplo, A.handle))
+
+
+def CHAMELEON_dpoinv_Tile(uplo: int, A: Desc) -> int:
+    """Chameleon poinv: the `uplo` triangle of A <- that of inv(A) (potrf, then potri).  Returns potrf's info
+    (> 0: A is not positive definite)."""
+    return check("chol_poinv_tile", lib().chol_poinv_tile(uplo, A.handle))
+
+
 CHAMELEON_spotrs_Tile = CHAMELEON_dpotrs_Tile
 CHAMELEON_sposv_Tile = CHAMELEON_dposv_Tile
 CHAMELEON_slacpy_Tile = CHAMELEON_dlacpy_Tile
 CHAMELEON_slange_Tile = CHAMELEON_dlange_Tile
 CHAMELEON_slauum_Tile = CHAMELEON_dlauum_Tile
 CHAMELEON_sgeadd_Tile = CHAMELEON_dgeadd_Tile
+CHAMELEON_strtri_Tile = CHAMELEON_dtrtri_Tile
+CHAMELEON_spotri_Tile = CHAMELEON_dpotri_Tile
+CHAMELEON_spoinv_Tile = CHAMELEON_dpoinv_Tile
 
 
 def residual_plgsy(L: Desc, bump: float, seed: int) -> float:

@@ -56,6 +56,11 @@ struct Ctx {
   void *mx[4] = {nullptr, nullptr, nullptr, nullptr};
   size_t mx_bytes[4] = {0, 0, 0, 0};
   double mx_stats[8] = {};  // of the last chol_dsposv_tile (chol_last_dsposv_stats)
+  // chol_trtri_tile / chol_potri_tile's scratch, grown on demand and kept (not g.work either): the products' Y blocks
+  // (then potri's LAUUM image), the 128 x 128 inverses of every diagonal tile's diagonal blocks, a staged copy of a
+  // single tile whose edge is not a multiple of 128, and the zero-pivot word
+  void *iv[4] = {nullptr, nullptr, nullptr, nullptr};
+  size_t iv_bytes[4] = {0, 0, 0, 0};
   std::string last_error;
 };
 
@@ -189,6 +194,17 @@ int ensure_mx(int idx, size_t bytes) {
   HIPCHECK(hipMalloc(&g.mx[idx], bytes));
   HIPCHECK(hipMemset(g.mx[idx], 0, bytes));
   g.mx_bytes[idx] = bytes;
+  return 0;
+}
+
+int ensure_iv(int idx, size_t bytes) {
+  if (g.iv_bytes[idx] >= bytes) return 0;
+  if (g.iv[idx]) HIPCHECK(hipFree(g.iv[idx]));
+  g.iv[idx] = nullptr;
+  g.iv_bytes[idx] = 0;
+  bytes = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
+  HIPCHECK(hipMalloc(&g.iv[idx], bytes));
+  g.iv_bytes[idx] = bytes;
   return 0;
 }
 
@@ -1046,6 +1062,11 @@ int chol_finalize(void) {
     if (g.mx[i]) (void)hipFree(g.mx[i]);
     g.mx[i] = nullptr;
     g.mx_bytes[i] = 0;
+  }
+  for (int i = 0; i < 4; ++i) {
+    if (g.iv[i]) (void)hipFree(g.iv[i]);
+    g.iv[i] = nullptr;
+    g.iv_bytes[i] = 0;
   }
   tx_destroy();
   g.wc_ptr = nullptr;
@@ -2035,6 +2056,196 @@ int chol_last_dsposv_stats(double *out8) {
   if (!out8) return fail(-1, "last_dsposv_stats: NULL");
   std::copy(g.mx_stats, g.mx_stats + 8, out8);
   return 0;
+}
+
+// ---------------------------------------------------------------- inverse from the factor (LAPACK DTRTRI / DPOTRI)
+// X = L^{-1} in place over the lower tiles (inverse.hip: the 128-blocks of every diagonal tile, then the tiles, each
+// level column by column from the right), then for potri X^T X into the lower triangle (verify_ops.hip's LAUUM).
+// ChamUpper flips the storage around the Lower path, as potrf and potrs do.  A stored image whose padding is the
+// identity (a ragged order, a tile edge that is not a multiple of 128) is inverted as a whole: its padding stays the
+// identity and its matrix part is the inverse of the caller's matrix.
+extern "C++" {
+namespace {
+template <typename T>
+struct InvImg {  // nt x nt tiles of mbs x mbs (mbs % 128 == 0), tile (i,j) at p + (i + j lmt) mbs^2
+  T *p;
+  int nt, lmt, mbs;
+};
+}  // namespace
+
+template <typename T>
+static int trtri_img(const InvImg<T> &A) {
+  hipStream_t s = g.r.st[ST_MAIN];
+  const int nt = A.nt, mb = A.mbs, nbm = mb / MACRO;
+  const long bs = (long)mb * mb, tstride = (long)(A.lmt + 1) * bs, blk = (long)MACRO * MACRO;
+  // Y: nt tiles (tile level) or nt * nbm blocks (inner level); the 128 x 128 inverses of every diagonal tile
+  if (ensure_iv(0, (size_t)nt * bs * sizeof(T)) || ensure_iv(1, (size_t)nt * nbm * blk * sizeof(T))) {
+    (void)hipGetLastError();
+    return fail(CHOL_ERR_OUT_OF_MEMORY, "trtri_tile: scratch allocation failed");
+  }
+  T *Y = reinterpret_cast<T *>(g.iv[0]), *W = reinterpret_cast<T *>(g.iv[1]);
+  launch_invert_diag_batch<T>(s, A.p, tstride, nt, mb, W);
+  // the diagonal tiles, all at once: blocks (i,j) of tile z at p + z tstride + i 128 + j 128 mb
+  const TriLevel<T> in{A.p, MACRO, (long)MACRO * mb, tstride, mb, W, blk, nbm * blk, MACRO, Y, blk, nbm * blk, MACRO};
+  for (int c = nbm - 2; c >= 0; --c) launch_tri_column<T>(s, in, nbm, nt, c);
+  launch_tri_put_diag<T>(s, A.p, tstride, mb, nt, W);
+  // the tiles below the diagonal
+  const TriLevel<T> top{A.p, bs, (long)A.lmt * bs, 0, mb, A.p, tstride, 0, mb, Y, bs, 0, mb};
+  for (int c = nt - 2; c >= 0; --c) launch_tri_column<T>(s, top, nt, 1, c);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// lower triangle of A <- X^T X, X the lower triangle of A (padding included: the identity stays)
+template <typename T>
+static int lauum_img(const InvImg<T> &A) {
+  hipStream_t s = g.r.st[ST_MAIN];
+  if (ensure_iv(0, (size_t)A.nt * A.nt * A.mbs * A.mbs * sizeof(T))) {
+    (void)hipGetLastError();
+    return fail(CHOL_ERR_OUT_OF_MEMORY, "potri_tile: scratch allocation failed");
+  }
+  T *out = reinterpret_cast<T *>(g.iv[0]);
+  launch_lauum_lower<T>(s, A.p, out, A.nt, A.mbs);
+  TileGeo ge;
+  ge.lmt = ge.lnt = A.nt;
+  ge.mbs = ge.mbu = A.mbs;
+  ge.m = ge.n = (long)A.nt * A.mbs;
+  launch_lacpy<T>(s, ge, 1, out, A.p);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// A (Lower orientation, already checked) <- L^{-1}, or inv(L L^T) for potri
+template <typename T>
+static int inverse_impl(chol_desc *A, bool potri) {
+  hipStream_t s = g.r.st[ST_MAIN];
+  forget_winv(A->mat);  // (A is overwritten)
+  // potri: its LAUUM image first (trtri's Y blocks fit in it): no scratch is reallocated between the launches
+  const int ep = roundup(A->mbi, MACRO), nt = A->mbi % MACRO ? 1 : A->nt;
+  if (potri && ensure_iv(0, (size_t)nt * nt * ep * ep * sizeof(T))) {
+    (void)hipGetLastError();
+    return fail(CHOL_ERR_OUT_OF_MEMORY, "potri_tile: scratch allocation failed");
+  }
+  if (A->mbi % MACRO == 0) {
+    const InvImg<T> im{reinterpret_cast<T *>(A->mat), A->nt, A->lmt, A->mbi};
+    int rc = trtri_img<T>(im);
+    if (!rc && potri) rc = lauum_img<T>(im);
+    if (rc) return rc;
+    HIPCHECK(hipStreamSynchronize(s));
+    return 0;
+  }
+  // a single tile whose edge is an odd multiple of 64: staged into a multiple of 128 with the identity beyond it
+  const int e = A->mbi;
+  if (ensure_iv(2, (size_t)ep * ep * sizeof(T))) {
+    (void)hipGetLastError();
+    return fail(CHOL_ERR_OUT_OF_MEMORY, "trtri_tile: staging allocation failed");
+  }
+  T *S = reinterpret_cast<T *>(g.iv[2]);
+  HIPCHECK(hipMemsetAsync(S, 0, (size_t)ep * ep * sizeof(T), s));
+  HIPCHECK(hipMemcpy2DAsync(S, (size_t)ep * sizeof(T), A->mat, (size_t)e * sizeof(T), (size_t)e * sizeof(T), e,
+                            hipMemcpyDeviceToDevice, s));
+  launch_pad_identity<T>(s, S, e, ep);
+  const InvImg<T> im{S, 1, 1, ep};
+  int rc = trtri_img<T>(im);
+  if (!rc && potri) rc = lauum_img<T>(im);
+  if (rc) return rc;
+  // (the strict upper triangle goes back as it came: no kernel writes it)
+  HIPCHECK(hipMemcpy2DAsync(A->mat, (size_t)e * sizeof(T), S, (size_t)ep * sizeof(T), (size_t)e * sizeof(T), e,
+                            hipMemcpyDeviceToDevice, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  return 0;
+}
+
+// the descriptor rules of chol_trtri_tile / chol_potri_tile / chol_poinv_tile (apos: A's argument position)
+static int inverse_check(const char *what, chol_desc *A, int apos) {
+  int rc = resident_whole(what, A);
+  if (rc) return rc;
+  char buf[160];
+  if (A->mt != A->nt || A->lm != A->ln) {
+    snprintf(buf, sizeof buf, "%s: A is not square", what);
+    return fail(-apos, buf);
+  }
+  if (A->mbi % 64) {
+    snprintf(buf, sizeof buf, "%s: stored tile edge must be a multiple of 64", what);
+    return fail(CHOL_ERR_NOT_SUPPORTED, buf);
+  }
+  return 0;
+}
+
+// the first exact zero on the diagonal (1-based), or 0; read before anything is written
+template <typename T>
+static int diag_zero(const chol_desc *A, int *info) {
+  hipStream_t s = g.r.st[ST_MAIN];
+  if (ensure_iv(3, sizeof(int))) {
+    (void)hipGetLastError();
+    return fail(CHOL_ERR_OUT_OF_MEMORY, "trtri_tile: scratch allocation failed");
+  }
+  int *first = reinterpret_cast<int *>(g.iv[3]);
+  launch_diag_zero<T>(s, reinterpret_cast<const T *>(A->mat), (long)(A->lmt + 1) * A->bsizi, A->mbi, A->mb, A->lm, first);
+  HIPCHECK(hipGetLastError());
+  int v = 0;
+  HIPCHECK(hipMemcpyAsync(&v, first, sizeof v, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  *info = v <= A->lm ? v : 0;
+  return 0;
+}
+
+}  // extern "C++"
+
+static int inverse_run(int uplo, chol_desc *A, bool potri) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  const bool dbl = A->dtype == CHOL_REAL_DOUBLE;
+  int info = 0;
+  int rc = dbl ? diag_zero<double>(A, &info) : diag_zero<float>(A, &info);
+  if (rc) return rc;
+  if (info) return info;  // (LAPACK: A is unchanged)
+  // ChamUpper: U = L^T; inv(U) = inv(L)^T and inv(U^T U) = inv(L L^T) -- the Lower path on the transposed storage
+  auto flip = [&]() {
+    if (dbl)
+      launch_transpose_inplace<double>(g.r.st[ST_MAIN], (double *)A->mat, A->nt, A->mbi);
+    else
+      launch_transpose_inplace<float>(g.r.st[ST_MAIN], (float *)A->mat, A->nt, A->mbi);
+  };
+  if (uplo == CHOL_UPPER) flip();
+  rc = dbl ? inverse_impl<double>(A, potri) : inverse_impl<float>(A, potri);
+  if (uplo == CHOL_UPPER) {
+    flip();
+    HIPCHECK(hipStreamSynchronize(g.r.st[ST_MAIN]));
+  }
+  return rc;
+}
+
+int chol_trtri_tile(int uplo, int diag, chol_desc_t *A) {
+  return with_views({{A, true}}, [&]() -> int {
+  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "trtri_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "trtri_tile: uplo");
+  if (diag != CHOL_NONUNIT && diag != CHOL_UNIT) return fail(-2, "trtri_tile: diag");
+  if (diag == CHOL_UNIT)
+    return fail(CHOL_ERR_NOT_SUPPORTED, "trtri_tile: ChamUnit (a Cholesky factor has no unit diagonal)");
+  int rc = inverse_check("trtri_tile", A, 3);
+  if (rc) return rc;
+  return inverse_run(uplo, A, false);
+  });
+}
+
+int chol_potri_tile(int uplo, chol_desc_t *A) {
+  return with_views({{A, true}}, [&]() -> int {
+  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "potri_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "potri_tile: uplo");
+  int rc = inverse_check("potri_tile", A, 2);
+  if (rc) return rc;
+  return inverse_run(uplo, A, true);
+  });
+}
+
+int chol_poinv_tile(int uplo, chol_desc_t *A) {
+  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "poinv_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "poinv_tile: uplo");
+  int rc = inverse_check("poinv_tile", A, 2);  // (before the factorisation writes anything)
+  if (rc) return rc;
+  const int info = chol_potrf_tile(uplo, A);
+  if (info != 0) return info;  // > 0: not positive definite, A as potrf leaves it
+  return chol_potri_tile(uplo, A);
 }
 
 // valid extent of tile (I,J) inside the matrix (edge tiles are smaller)

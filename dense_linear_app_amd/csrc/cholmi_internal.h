@@ -202,6 +202,9 @@ void launch_col_update_small(hipStream_t s, T *C, const T *A, const T *B, int mb
 // winv from an already factored tile
 template <typename T>
 void launch_invert_diag(hipStream_t s, const T *tile, int mb, T *winv);
+// the same for the nt tiles A + t tstride in one launch: the inverses of tile t at winv + t (mb/MACRO) MACRO^2
+template <typename T>
+void launch_invert_diag_batch(hipStream_t s, const T *A, long tstride, int nt, int mb, T *winv);
 
 // tiles[t] := alpha * tiles[t] * L^{-T}, t < ntiles, tiles contiguous (stride bsiz)
 template <typename T>
@@ -282,6 +285,35 @@ void launch_sym_to_f32(hipStream_t s, const TileGeo &ga, int upper, const double
 void launch_vec_to_f32(hipStream_t s, const TileGeo &gx, const double *B, float *Bf, int *flag);
 // X := (double) C (assign) or X += (double) C
 void launch_vec_update(hipStream_t s, const TileGeo &gx, const float *C, double *X, bool assign);
+
+// ---- launchers (inverse.hip): the triangular inverse of chol_trtri_tile / chol_potri_tile ----
+// A lower block-triangular matrix of n blocks of edge E (a multiple of 128), nbatch independent problems:
+// block (i,j) of problem z at base + z sz + i si + j sj (ld), the inverses Xd(i) of its diagonal blocks at
+// dg + z dsz + i dsi (ld dld; read as lower triangular), scratch for n blocks E x E at y + z ysz + m ysi (ld E).
+template <typename T>
+struct TriLevel {
+  T *base;
+  long si, sj, sz;
+  int ld;
+  const T *dg;
+  long dsi, dsz;
+  int dld;
+  T *y;
+  long ysi, ysz;
+  int E;
+};
+// column c of the inverse below the diagonal, every problem: X(i,c) = -sum_{c<m<=i} X(i,m) L(m,c) Xd(c), in place
+// (needs the columns right of c done; two launches)
+template <typename T>
+void launch_tri_column(hipStream_t s, const TriLevel<T> &L, int n, int nbatch, int c);
+// the lower triangles of the nt * mb/128 inverses winv (128 x 128 each, tile by tile) into the diagonal
+// 128-blocks of the diagonal tiles A + t tstride (ld mb)
+template <typename T>
+void launch_tri_put_diag(hipStream_t s, T *A, long tstride, int mb, int nt, const T *winv);
+// *first <- the smallest 1-based i <= n with A(i,i) == 0 (diagonal tile t at A + t tstride, ld mbs, mbu of its rows
+// inside the matrix), or a value above n
+template <typename T>
+void launch_diag_zero(hipStream_t s, const T *A, long tstride, int mbs, int mbu, long n, int *first);
 
 // out-of-place transposes of `count` mb x mb tiles (mb % 64 == 0)
 template <typename T>

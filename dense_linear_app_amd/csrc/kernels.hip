@@ -2764,6 +2764,20 @@ void launch_invert_diag(hipStream_t s, const T *tile, int mb, T *winv) {
                                       winv + (long)st * MACRO * MACRO, nullptr, 0, 0, nullptr, g_ytab);
 }
 
+// the diagonal 128-blocks of nt tiles (A + t tstride, ld mb) at once: workgroup t nbm + s inverts block s of tile t
+template <typename T>
+__global__ __launch_bounds__(256, 2) void k_invert_diag_batch(const T *A, long tstride, int mb, T *__restrict__ winv) {
+  __shared__ DiagLds<T> L;
+  const int nbm = mb / MACRO, t = blockIdx.x / nbm, s = blockIdx.x % nbm;
+  potrf_diag_body<T>(const_cast<T *>(A) + t * tstride + (long)s * MACRO * (mb + 1), mb,
+                     winv + ((long)t * nbm + s) * MACRO * MACRO, nullptr, 0, /*factor=*/0, L);
+}
+
+template <typename T>
+void launch_invert_diag_batch(hipStream_t s, const T *A, long tstride, int nt, int mb, T *winv) {
+  if (nt > 0) k_invert_diag_batch<T><<<(unsigned)(nt * (mb / MACRO)), 256, 0, s>>>(A, tstride, mb, winv);
+}
+
 template <typename T>
 void launch_trsm_panel(hipStream_t s, T *tiles, long bsiz, int ntiles, const T *lkk, const T *winv,
                        int mb, T alpha) {
@@ -2887,6 +2901,7 @@ template void launch_mfma_probe<float>(hipStream_t, float *, int, int);
   template void launch_potrf_tile<T>(hipStream_t, T *, int, T *, int *, int, int *);                \
   template void launch_diag_syrk<T>(hipStream_t, T *, const T *, int);                               \
   template void launch_invert_diag<T>(hipStream_t, const T *, int, T *);                            \
+  template void launch_invert_diag_batch<T>(hipStream_t, const T *, long, int, int, T *);            \
   template void launch_trsm_panel<T>(hipStream_t, T *, long, int, const T *, const T *, int, T);    \
   template void launch_gemm_nt_tile<T>(hipStream_t, const T *, const T *, T *, int, T, T, bool);    \
   template void launch_gemm_nt_batch<T>(hipStream_t, const T *, long, int, const T *, long, int, T *, long, long, \

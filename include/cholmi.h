@@ -219,6 +219,23 @@ int chol_dsposv_tile(int uplo, chol_desc_t *A, chol_desc_t *B, chol_desc_t *X, i
  * residual passes (all), then the number of fp32 solves and of residual passes; out8[7] is 0. */
 int chol_last_dsposv_stats(double *out8);
 
+/* Inverse from the Cholesky factor, on device-resident single-process descriptors (the descriptor rules of
+ * chol_potrs_tile: A square, stored tile edge a multiple of 64, views allowed; a p x q block-cyclic descriptor
+ * returns CHOL_ERR_NOT_SUPPORTED).  fp64 or fp32 by A's dtype; only the `uplo` triangle of A is read or written,
+ * the other strict triangle comes back bit-for-bit as it was.
+ *
+ * CHAMELEON_dtrtri_Tile(uplo, diag, A) -- LAPACK DTRTRI: A <- inv(A), A triangular, in place.  diag must be
+ * CHOL_NONUNIT: a Cholesky factor never has a unit diagonal, so CHOL_UNIT returns CHOL_ERR_NOT_SUPPORTED.
+ * Returns info = i > 0 (1-based) for the first exact zero A(i,i), found before anything is written: A is then
+ * unchanged, as in LAPACK. */
+int chol_trtri_tile(int uplo, int diag, chol_desc_t *A);
+/* CHAMELEON_dpotri_Tile(uplo, A) -- LAPACK DPOTRI: A holds the factor L (or U) of chol_potrf_tile; the `uplo`
+ * triangle of A becomes that of inv(L L^T) (inv(U^T U)).  info = i > 0 as chol_trtri_tile (A unchanged). */
+int chol_potri_tile(int uplo, chol_desc_t *A);
+/* CHAMELEON_dpoinv_Tile(uplo, A) -- Chameleon poinv: chol_potrf_tile followed by chol_potri_tile.  Returns potrf's
+ * info > 0 when A is not positive definite, A then in the state potrf leaves it. */
+int chol_poinv_tile(int uplo, chol_desc_t *A);
+
 /* CHAMELEON_Lapack_to_Tile / Tile_to_Lapack equivalents (host LAPACK layout
  * <-> descriptor storage); single-process descriptors only. */
 int chol_lapack_to_tile(const void *A, int lda, chol_desc_t *desc);
