@@ -59,6 +59,9 @@ def lib() -> C.CDLL:
         "chol_trtri_tile": ([i, i, vp], i),
         "chol_potri_tile": ([i, vp], i),
         "chol_poinv_tile": ([i, vp], i),
+        "chol_lansy_tile": ([i, i, vp, C.POINTER(d)], i),
+        "chol_pocon_tile": ([i, vp, d, C.POINTER(d)], i),
+        "chol_last_pocon_stats": ([C.POINTER(d)], i),
         "chol_lapack_to_tile": ([vp, i, vp], i),
         "chol_tile_to_lapack": ([vp, vp, i], i),
         "chol_tile_upload": ([vp, i, i, vp], i),

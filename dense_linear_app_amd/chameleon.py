@@ -254,6 +254,30 @@ def CHAMELEON_dpoinv_Tile(uplo: int, A: Desc) -> int:
     return check("chol_poinv_tile", lib().chol_poinv_tile(uplo, A.handle))
 
 
+def CHAMELEON_dlansy_Tile(norm: int, uplo: int, A: Desc) -> float:
+    """LAPACK DLANSY: the norm of the symmetric matrix whose `uplo` triangle A stores (ChamMaxNorm, ChamOneNorm,
+    ChamInfNorm, ChamFrobeniusNorm).  Returns the norm, as CHAMELEON_dlange_Tile does."""
+    r = C.c_double()
+    check("chol_lansy_tile", lib().chol_lansy_tile(norm, uplo, A.handle, C.byref(r)))
+    return r.value
+
+
+def CHAMELEON_dpocon_Tile(uplo: int, A: Desc, anorm: float) -> float:
+    """LAPACK DPOCON: A holds the factor of CHAMELEON_dpotrf_Tile(uplo, .), anorm = ||A||_1 of the original matrix
+    (CHAMELEON_dlansy_Tile).  Returns rcond, the reciprocal 1-norm condition estimate (0: a zero on the factor's
+    diagonal, anorm = 0 or +Inf, or a sweep that overflowed)."""
+    r = C.c_double()
+    check("chol_pocon_tile", lib().chol_pocon_tile(uplo, A.handle, float(anorm), C.byref(r)))
+    return r.value
+
+
+def last_pocon_stats() -> dict:
+    """The last CHAMELEON_dpocon_Tile (chol_last_pocon_stats): total and sweep time [ms], applications of A^{-1}."""
+    v = (C.c_double * 4)()
+    check("chol_last_pocon_stats", lib().chol_last_pocon_stats(v))
+    return {"total_ms": v[0], "sweep_ms": v[1], "applications": int(v[2])}
+
+
 CHAMELEON_spotrs_Tile = CHAMELEON_dpotrs_Tile
 CHAMELEON_sposv_Tile = CHAMELEON_dposv_Tile
 CHAMELEON_slacpy_Tile = CHAMELEON_dlacpy_Tile
@@ -263,6 +287,8 @@ CHAMELEON_sgeadd_Tile = CHAMELEON_dgeadd_Tile
 CHAMELEON_strtri_Tile = CHAMELEON_dtrtri_Tile
 CHAMELEON_spotri_Tile = CHAMELEON_dpotri_Tile
 CHAMELEON_spoinv_Tile = CHAMELEON_dpoinv_Tile
+CHAMELEON_slansy_Tile = CHAMELEON_dlansy_Tile
+CHAMELEON_spocon_Tile = CHAMELEON_dpocon_Tile
 
 
 def residual_plgsy(L: Desc, bump: float, seed: int) -> float:

@@ -61,6 +61,12 @@ struct Ctx {
   // single tile whose edge is not a multiple of 128, and the zero-pivot word
   void *iv[4] = {nullptr, nullptr, nullptr, nullptr};
   size_t iv_bytes[4] = {0, 0, 0, 0};
+  // chol_lansy_tile / chol_pocon_tile's scratch, grown on demand and kept (not g.work either): the staged and
+  // inverted diagonal tiles, the 128 x 128 inverses of their diagonal blocks, the products' Y blocks, the sweeps'
+  // vectors and partials, the sign vector, the statistics, lansy's per-block partials
+  void *cn[7] = {};
+  size_t cn_bytes[7] = {};
+  double cn_stats[4] = {};  // of the last chol_pocon_tile (chol_last_pocon_stats)
   std::string last_error;
 };
 
@@ -205,6 +211,17 @@ int ensure_iv(int idx, size_t bytes) {
   bytes = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
   HIPCHECK(hipMalloc(&g.iv[idx], bytes));
   g.iv_bytes[idx] = bytes;
+  return 0;
+}
+
+int ensure_cn(int idx, size_t bytes) {
+  if (g.cn_bytes[idx] >= bytes) return 0;
+  if (g.cn[idx]) HIPCHECK(hipFree(g.cn[idx]));
+  g.cn[idx] = nullptr;
+  g.cn_bytes[idx] = 0;
+  bytes = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
+  HIPCHECK(hipMalloc(&g.cn[idx], bytes));
+  g.cn_bytes[idx] = bytes;
   return 0;
 }
 
@@ -1067,6 +1084,11 @@ int chol_finalize(void) {
     if (g.iv[i]) (void)hipFree(g.iv[i]);
     g.iv[i] = nullptr;
     g.iv_bytes[i] = 0;
+  }
+  for (int i = 0; i < 7; ++i) {
+    if (g.cn[i]) (void)hipFree(g.cn[i]);
+    g.cn[i] = nullptr;
+    g.cn_bytes[i] = 0;
   }
   tx_destroy();
   g.wc_ptr = nullptr;
@@ -2246,6 +2268,192 @@ int chol_poinv_tile(int uplo, chol_desc_t *A) {
   const int info = chol_potrf_tile(uplo, A);
   if (info != 0) return info;  // > 0: not positive definite, A as potrf leaves it
   return chol_potri_tile(uplo, A);
+}
+
+// ---------------------------------------------------------------- condition estimate (LAPACK DLANSY / DPOCON)
+// lansy: one pass over the stored triangle (condest.hip).  pocon: LAPACK DLACN2's state machine on the host, which
+// reads back six scalars after each application of A^{-1}; the applications (two narrow triangular sweeps over the
+// stored triangle) and every operation on an N-vector run on the device (condest.hip).
+static int cn_oom(const char *what) {
+  (void)hipGetLastError();
+  char buf[96];
+  snprintf(buf, sizeof buf, "%s: scratch allocation failed", what);
+  return fail(CHOL_ERR_OUT_OF_MEMORY, buf);
+}
+
+int chol_lansy_tile(int norm, int uplo, chol_desc_t *A, double *value) {
+  return with_views({{A, false}}, [&]() -> int {
+  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "lansy_tile before chol_init");
+  int kind;
+  switch (norm) {
+    case CHOL_MAX_NORM: kind = 0; break;
+    case CHOL_ONE_NORM:
+    case CHOL_INF_NORM: kind = 1; break;  // (symmetric: one value for both)
+    case CHOL_FROBENIUS_NORM: kind = 2; break;
+    default: return fail(-1, "lansy_tile: norm");
+  }
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-2, "lansy_tile: uplo");
+  int rc = inverse_check("lansy_tile", A, 3);
+  if (rc) return rc;
+  if (!value) return fail(-4, "lansy_tile: NULL value");
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  hipStream_t s = g.r.st[ST_MAIN];
+  const TileGeo ge = geo_of(A);
+  const size_t pb = lansy_part_bytes(ge);
+  if (ensure_cn(6, pb + 4 * sizeof(double))) return cn_oom("lansy_tile");
+  double *part = reinterpret_cast<double *>(g.cn[6]), *res = part + pb / sizeof(double);
+  const int up = uplo == CHOL_UPPER;
+  if (A->dtype == CHOL_REAL_DOUBLE)
+    launch_lansy<double>(s, ge, up, (const double *)A->mat, part, res);
+  else
+    launch_lansy<float>(s, ge, up, (const float *)A->mat, part, res);
+  HIPCHECK(hipGetLastError());
+  double v[3] = {0, 0, 0};  // (the max and the row-sum max are the bits of non-negative doubles: read as doubles)
+  HIPCHECK(hipMemcpyAsync(v, res, sizeof v, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  *value = kind == 2 ? std::sqrt(v[2]) : v[kind];
+  return 0;
+  });
+}
+
+extern "C++" {
+namespace {
+struct CnEvents {  // [0, 1]: around the current application, [2, 3]: the whole call
+  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+  ~CnEvents() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+};
+}  // namespace
+
+template <typename T>
+static int pocon_impl(chol_desc *A, int upper, double anorm, double *rcond) {
+  hipStream_t s = g.r.st[ST_MAIN];
+  const TileGeo ge = geo_of(A);
+  const long n = A->lm;
+  for (double &v : g.cn_stats) v = 0;
+  *rcond = 0;
+  if (n == 0) {
+    *rcond = 1;
+    return 0;
+  }
+  if (anorm == 0 || std::isinf(anorm)) return 0;
+  CnEvents ev;
+  for (hipEvent_t &x : ev.e) HIPCHECK(hipEventCreate(&x));
+  HIPCHECK(hipEventRecord(ev.e[2], s));
+  int info = 0;
+  int rc = diag_zero<T>(A, &info);
+  if (rc) return rc;
+  if (info) return 0;  // a zero on the factor's diagonal: rcond = 0, no sweep
+  // scratch: the diagonal tiles, their 128-block inverses, the products' Y blocks, the vectors, the sign vector, the
+  // statistics
+  const int E = condest_edge(ge), nbm = E / MACRO, nt = A->nt, bpt = E / MACRO;
+  const long blk = (long)MACRO * MACRO, NB = (long)nt * bpt;
+  const size_t nv = condest_vec_elems(ge), npg = 2 * (size_t)NB * bpt * MACRO, npd = (size_t)bpt * bpt * MACRO;
+  if (ensure_cn(0, (size_t)nt * E * E * sizeof(T)) || ensure_cn(1, (size_t)nt * nbm * blk * sizeof(T)) ||
+      ensure_cn(2, (size_t)nt * nbm * blk * sizeof(T)) || ensure_cn(3, (2 * nv + npg + npd) * sizeof(T)) ||
+      ensure_cn(4, nv * sizeof(int)) || ensure_cn(5, vec_stats_part_bytes() + 8 * sizeof(double)))
+    return cn_oom("pocon_tile");
+  T *Dv = reinterpret_cast<T *>(g.cn[0]), *W = reinterpret_cast<T *>(g.cn[1]), *Y = reinterpret_cast<T *>(g.cn[2]);
+  T *vx = reinterpret_cast<T *>(g.cn[3]);
+  const SweepBufs<T> bufs{vx, vx + nv, vx + 2 * nv, vx + 2 * nv + npg};
+  int *isgn = reinterpret_cast<int *>(g.cn[4]);
+  double *spart = reinterpret_cast<double *>(g.cn[5]), *sout = spart + vec_stats_part_bytes() / sizeof(double);
+  const T *Am = reinterpret_cast<const T *>(A->mat);
+  // the diagonal tiles of L, inverted once: their 128-blocks (as potrs), then the tiles (trtri's inner level)
+  launch_stage_diag<T>(s, ge, upper, Am, Dv);
+  launch_invert_diag_batch<T>(s, Dv, (long)E * E, nt, E, W);
+  const TriLevel<T> in{Dv, MACRO, (long)MACRO * E, (long)E * E, E, W, blk, nbm * blk, MACRO, Y, blk, nbm * blk, MACRO};
+  for (int c = nbm - 2; c >= 0; --c) launch_tri_column<T>(s, in, nbm, nt, c);
+  launch_tri_put_diag<T>(s, Dv, (long)E * E, E, nt, W);
+  HIPCHECK(hipGetLastError());
+  int apps = 0;
+  double sweep_ms = 0, st[6] = {0, 0, 0, 0, 0, 0};
+  // x <- A^{-1} x, then the statistics of x (DLACN2's kase != 0 round trip); false: a non-finite entry
+  auto apply = [&](int sign, long jlast, bool *finite) -> int {
+    HIPCHECK(hipEventRecord(ev.e[0], s));
+    launch_sweep<T>(s, ge, upper, Am, Dv, bufs);
+    HIPCHECK(hipEventRecord(ev.e[1], s));
+    launch_vec_stats<T>(s, ge, bufs.x, isgn, sign, jlast, spart, sout);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(st, sout, sizeof st, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    float ms = 0;
+    HIPCHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    sweep_ms += ms;
+    ++apps;
+    *finite = st[3] == 0;
+    return 0;
+  };
+  // DLACN2 (Higham's estimator as LAPACK has it); A is symmetric, so kase 1 and kase 2 apply the same A^{-1}
+  constexpr int ITMAX = 5;
+  bool ok = true;
+  double est = 0;
+  launch_vec_fill<T>(s, ge, bufs.x, 0, 0);
+  if ((rc = apply(1, -1, &ok))) return rc;  // (ISAVE 1) est = ||x||_1, x = isgn = sign(x)
+  est = st[0];
+  if (ok && n > 1) {
+    if ((rc = apply(0, -1, &ok))) return rc;  // (ISAVE 2) j = idamax(x)
+    long j = (long)st[2];
+    int iter = 2;
+    while (ok) {
+      launch_vec_fill<T>(s, ge, bufs.x, 1, j);
+      if ((rc = apply(1, -1, &ok))) return rc;  // (ISAVE 3) est = ||x||_1; x = isgn = sign(x), changed?
+      if (!ok) break;
+      const double estold = est;
+      est = st[0];
+      if (st[5] == 0 || est <= estold) break;  // a repeated sign vector, or no increase: converged
+      if ((rc = apply(0, j, &ok))) return rc;  // (ISAVE 4) j = idamax(x), x(jlast) against |x(j)|
+      if (!ok) break;
+      const long jnew = (long)st[2];
+      if (st[4] != st[1] && iter < ITMAX) {
+        ++iter;
+        j = jnew;
+        continue;
+      }
+      break;
+    }
+    if (ok) {
+      launch_vec_fill<T>(s, ge, bufs.x, 2, 0);
+      if ((rc = apply(0, -1, &ok))) return rc;  // (ISAVE 5) the alternating-sign test vector
+      const T temp = T(2) * (T(st[0]) / T(3 * n));
+      if ((double)temp > est) est = (double)temp;
+    }
+  }
+  // (no dlatrs scaling: a sweep that overflows gives rcond = 0)
+  if (ok && est != 0) *rcond = (1.0 / est) / anorm;
+  HIPCHECK(hipEventRecord(ev.e[3], s));
+  HIPCHECK(hipEventSynchronize(ev.e[3]));
+  float total = 0;
+  HIPCHECK(hipEventElapsedTime(&total, ev.e[2], ev.e[3]));
+  g.cn_stats[0] = total;
+  g.cn_stats[1] = sweep_ms;
+  g.cn_stats[2] = apps;
+  return 0;
+}
+}  // extern "C++"
+
+int chol_pocon_tile(int uplo, chol_desc_t *A, double anorm, double *rcond) {
+  return with_views({{A, false}}, [&]() -> int {
+  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "pocon_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "pocon_tile: uplo");
+  int rc = inverse_check("pocon_tile", A, 2);
+  if (rc) return rc;
+  if (!(anorm >= 0)) return fail(-3, "pocon_tile: anorm is negative or NaN");
+  if (!rcond) return fail(-4, "pocon_tile: NULL rcond");
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  const int up = uplo == CHOL_UPPER;
+  return A->dtype == CHOL_REAL_DOUBLE ? pocon_impl<double>(A, up, anorm, rcond) : pocon_impl<float>(A, up, anorm, rcond);
+  });
+}
+
+int chol_last_pocon_stats(double *out4) {
+  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "last_pocon_stats before chol_init");
+  if (!out4) return fail(-1, "last_pocon_stats: NULL");
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  for (int i = 0; i < 4; ++i) out4[i] = g.cn_stats[i];
+  return 0;
 }
 
 // valid extent of tile (I,J) inside the matrix (edge tiles are smaller)

@@ -315,6 +315,39 @@ void launch_tri_put_diag(hipStream_t s, T *A, long tstride, int mb, int nt, cons
 template <typename T>
 void launch_diag_zero(hipStream_t s, const T *A, long tstride, int mbs, int mbu, long n, int *first);
 
+// ---- launchers (condest.hip): chol_lansy_tile and chol_pocon_tile on a single-process image (any mbs) ----
+// The image in 128 x 128 blocks of stored rows (bpt = ceil(mbs / 128) per tile); N-vectors of condest_vec_elems
+// entries in that order, zero outside the matrix.
+int condest_edge(const TileGeo &g);           // bpt 128: the edge of the staged diagonal tiles
+size_t condest_vec_elems(const TileGeo &g);
+// part: lansy_part_bytes(g) of scratch; res[0..2] <- max |a|, the largest row sum of |A|, the sum of squares
+// (off-diagonal entries twice) of the symmetric matrix stored in the `upper` triangle
+size_t lansy_part_bytes(const TileGeo &g);
+template <typename T>
+void launch_lansy(hipStream_t s, const TileGeo &g, int upper, const T *A, double *part, double *res);
+// Dv (lmt tiles of condest_edge^2): the diagonal tiles of the factor as Lower (U^T for Upper), zero above the
+// diagonal, the identity outside the matrix
+template <typename T>
+void launch_stage_diag(hipStream_t s, const TileGeo &g, int upper, const T *A, T *Dv);
+// one application of A^{-1} = L^{-T} L^{-1} (U^{-1} U^{-T}): x <- A^{-1} x; Dv: the inverted diagonal tiles; y, pd
+// (bpt^2 blocks of 128), pg (2 NB bpt blocks of 128): scratch
+template <typename T>
+struct SweepBufs {
+  T *x, *y, *pg, *pd;
+};
+template <typename T>
+void launch_sweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const T *Dv, const SweepBufs<T> &b);
+// x <- 1/n (mode 0), e_j (1; j a vector index), the alternating-sign vector of DLACN2 (2)
+template <typename T>
+void launch_vec_fill(hipStream_t s, const TileGeo &g, T *x, int mode, long j);
+// out[0..5] <- sum |x|, max |x|, its first vector index, a non-finite entry (0 / 1), x[jlast] (jlast >= 0), a sign
+// change; sign != 0: x and isgn <- sign(x) (x >= 0 -> +1), the change flag set where isgn changes.
+// part: vec_stats_part_bytes() of scratch.
+size_t vec_stats_part_bytes();
+template <typename T>
+void launch_vec_stats(hipStream_t s, const TileGeo &g, T *x, int *isgn, int sign, long jlast, double *part,
+                      double *out);
+
 // out-of-place transposes of `count` mb x mb tiles (mb % 64 == 0)
 template <typename T>
 void launch_tiles_transpose(hipStream_t s, const T *in, long istride, T *out, long ostride, int mb, int count);

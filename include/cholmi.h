@@ -236,6 +236,26 @@ int chol_potri_tile(int uplo, chol_desc_t *A);
  * info > 0 when A is not positive definite, A then in the state potrf leaves it. */
 int chol_poinv_tile(int uplo, chol_desc_t *A);
 
+/* Condition estimate from the Cholesky factor, on device-resident single-process descriptors (the descriptor rules
+ * of chol_potrs_tile: A square, stored tile edge a multiple of 64, views allowed; a p x q block-cyclic descriptor
+ * returns CHOL_ERR_NOT_SUPPORTED).  fp64 or fp32 by A's dtype (the fp32 estimate runs in fp32, as LAPACK SPOCON);
+ * A is only read, and only its `uplo` triangle.
+ *
+ * CHAMELEON_dlansy_Tile(norm, uplo, A) -- LAPACK DLANSY: *value <- the norm of the symmetric matrix whose `uplo`
+ * triangle A stores.  CHOL_MAX_NORM, CHOL_ONE_NORM, CHOL_INF_NORM (equal to ONE, bit for bit) or
+ * CHOL_FROBENIUS_NORM (the sum of squares in fp64, off-diagonal entries twice, then its square root, as
+ * chol_lange_tile).  Sums run in a fixed order: a repeated call returns the same bits. */
+int chol_lansy_tile(int norm, int uplo, chol_desc_t *A, double *value);
+/* LAPACK DPOCON: A holds the factor of chol_potrf_tile(uplo, .); anorm = ||A_original||_1 (chol_lansy_tile).
+ * *rcond <- 1 / (anorm * est(||A^{-1}||_1)), est from LAPACK DLACN2 (Higham's estimator, at most 11 applications of
+ * A^{-1} = L^{-T} L^{-1}, each two triangular sweeps on one vector).  Argument errors: -1 uplo, -2 A, -3 anorm < 0
+ * or NaN, -4 rcond NULL.  rcond = 0 for anorm = 0 or +Inf and for an exact zero on the factor's diagonal (found
+ * before any sweep).  Unlike LAPACK, the sweeps do not rescale against overflow (no DLATRS): if a sweep produces a
+ * non-finite value, rcond = 0.  Bit-identical from run to run. */
+int chol_pocon_tile(int uplo, chol_desc_t *A, double anorm, double *rcond);
+/* The last chol_pocon_tile: total ms, sweep ms (the applications alone), the number of applications, 0. */
+int chol_last_pocon_stats(double *out4);
+
 /* CHAMELEON_Lapack_to_Tile / Tile_to_Lapack equivalents (host LAPACK layout
  * <-> descriptor storage); single-process descriptors only. */
 int chol_lapack_to_tile(const void *A, int lda, chol_desc_t *desc);
