@@ -62,6 +62,12 @@ def lib() -> C.CDLL:
         "chol_lansy_tile": ([i, i, vp, C.POINTER(d)], i),
         "chol_pocon_tile": ([i, vp, d, C.POINTER(d)], i),
         "chol_last_pocon_stats": ([C.POINTER(d)], i),
+        "chol_poequ_tile": ([vp, vp, C.POINTER(d), C.POINTER(d)], i),
+        "chol_laqsy_tile": ([i, vp, vp, d, d, C.POINTER(i)], i),
+        "chol_porfs_tile": ([i, vp, vp, vp, vp, C.POINTER(d), C.POINTER(d)], i),
+        "chol_posvx_tile": ([i, i, vp, vp, C.POINTER(i), vp, vp, vp, C.POINTER(d), C.POINTER(d), C.POINTER(d)], i),
+        "chol_last_posvx_stats": ([C.POINTER(d)], i),
+        "chol_bench_refine": ([i, vp, vp, vp, i, i, C.POINTER(d)], i),
         "chol_lapack_to_tile": ([vp, i, vp], i),
         "chol_tile_to_lapack": ([vp, vp, i], i),
         "chol_tile_upload": ([vp, i, i, vp], i),

@@ -278,6 +278,90 @@ def last_pocon_stats() -> dict:
     return {"total_ms": v[0], "sweep_ms": v[1], "applications": int(v[2])}
 
 
+# LAPACK's FACT / EQUED characters <-> the C ABI's codes (CHOL_FACT_*, *equed 0 / 1)
+FACT_CODES = {"N": 0, "E": 1, "F": 2}
+EQUED_CODES = {"N": 0, "Y": 1}
+
+
+def fact_code(fact: str) -> int:
+    """'N' / 'E' / 'F' (any case) -> CHOL_FACT_NONE / _EQUILIBRATE / _FACTORED."""
+    try:
+        return FACT_CODES[str(fact).upper()]
+    except KeyError:
+        raise ValueError(f"fact must be 'N', 'E' or 'F', not {fact!r}") from None
+
+
+def equed_code(equed: str) -> int:
+    """'N' / 'Y' (any case) -> 0 / 1."""
+    try:
+        return EQUED_CODES[str(equed).upper()]
+    except KeyError:
+        raise ValueError(f"equed must be 'N' or 'Y', not {equed!r}") from None
+
+
+def equed_char(code: int) -> str:
+    """0 / 1 -> 'N' / 'Y'."""
+    return {0: "N", 1: "Y"}[int(code)]
+
+
+def CHAMELEON_dpoequ_Tile(A: Desc, S: Desc) -> tuple[int, float, float]:
+    """LAPACK DPOEQU: S (n x 1) <- 1/sqrt(A(i,i)).  Returns (info, scond, amax); info = i > 0 for the first
+    A(i,i) <= 0 (S then unspecified)."""
+    sc, am = C.c_double(), C.c_double()
+    info = check("chol_poequ_tile", lib().chol_poequ_tile(A.handle, S.handle, C.byref(sc), C.byref(am)))
+    return info, sc.value, am.value
+
+
+def CHAMELEON_dlaqsy_Tile(uplo: int, A: Desc, S: Desc, scond: float, amax: float) -> str:
+    """LAPACK DLAQSY: scale the `uplo` triangle of A by S when scond < 0.1 or amax is out of range.  Returns equed,
+    'Y' (A scaled) or 'N' (A untouched)."""
+    e = C.c_int()
+    check("chol_laqsy_tile", lib().chol_laqsy_tile(uplo, A.handle, S.handle, float(scond), float(amax), C.byref(e)))
+    return equed_char(e.value)
+
+
+def CHAMELEON_dporfs_Tile(uplo: int, A: Desc, AF: Desc, B: Desc, X: Desc) -> tuple[int, np.ndarray, np.ndarray]:
+    """LAPACK DPORFS: refine X in place (AF the factor of A).  Returns (info, ferr, berr), one bound per column."""
+    nrhs = B.ln
+    ferr, berr = np.zeros(nrhs), np.zeros(nrhs)
+    dp = C.POINTER(C.c_double)
+    info = check("chol_porfs_tile", lib().chol_porfs_tile(uplo, A.handle, AF.handle, B.handle, X.handle,
+                                                         ferr.ctypes.data_as(dp), berr.ctypes.data_as(dp)))
+    return info, ferr, berr
+
+
+def CHAMELEON_dposvx_Tile(fact: str, uplo: int, A: Desc, AF: Desc, equed: str, S, B: Desc,
+                          X: Desc) -> tuple[int, str, float, np.ndarray, np.ndarray]:
+    """LAPACK DPOSVX with fact / equed as LAPACK's characters ('N', 'E', 'F' / 'N', 'Y'; equed is an input for 'F').
+    S may be None when it is not used.  Returns (info, equed, rcond, ferr, berr); info = n + 1: rcond < eps."""
+    nrhs = B.ln
+    ferr, berr = np.zeros(nrhs), np.zeros(nrhs)
+    e = C.c_int(equed_code(equed))
+    rc = C.c_double()
+    dp = C.POINTER(C.c_double)
+    info = check("chol_posvx_tile", lib().chol_posvx_tile(fact_code(fact), uplo, A.handle, AF.handle, C.byref(e),
+                                                         S.handle if S is not None else None, B.handle, X.handle,
+                                                         C.byref(rc), ferr.ctypes.data_as(dp), berr.ctypes.data_as(dp)))
+    return info, equed_char(e.value), rc.value, ferr, berr
+
+
+def last_posvx_stats() -> dict:
+    """The last CHAMELEON_dposvx_Tile / dporfs_Tile (chol_last_posvx_stats): phases [ms] and the columns to which
+    A^{-1} was applied by the multi-vector sweeps and by potrs."""
+    v = (C.c_double * 8)()
+    check("chol_last_posvx_stats", lib().chol_last_posvx_stats(v))
+    return {"total_ms": v[0], "equilibrate_ms": v[1], "factor_ms": v[2], "rcond_ms": v[3], "solve_ms": v[4],
+            "porfs_ms": v[5], "sweep_columns": int(v[6]), "potrs_columns": int(v[7])}
+
+
+def bench_refine(uplo: int, A: Desc, AF: Desc, X: Desc, path: int, reps: int = 3) -> float:
+    """The parts of CHAMELEON_dporfs_Tile alone on X's columns [ms, fastest of reps]: path 0 the residual pass, 1 one
+    application of A^{-1} by the multi-vector sweeps, 2 the same by potrs (chol_bench_refine)."""
+    r = C.c_double()
+    check("chol_bench_refine", lib().chol_bench_refine(uplo, A.handle, AF.handle, X.handle, path, reps, C.byref(r)))
+    return r.value
+
+
 CHAMELEON_spotrs_Tile = CHAMELEON_dpotrs_Tile
 CHAMELEON_sposv_Tile = CHAMELEON_dposv_Tile
 CHAMELEON_slacpy_Tile = CHAMELEON_dlacpy_Tile
@@ -289,6 +373,10 @@ CHAMELEON_spotri_Tile = CHAMELEON_dpotri_Tile
 CHAMELEON_spoinv_Tile = CHAMELEON_dpoinv_Tile
 CHAMELEON_slansy_Tile = CHAMELEON_dlansy_Tile
 CHAMELEON_spocon_Tile = CHAMELEON_dpocon_Tile
+CHAMELEON_spoequ_Tile = CHAMELEON_dpoequ_Tile
+CHAMELEON_slaqsy_Tile = CHAMELEON_dlaqsy_Tile
+CHAMELEON_sporfs_Tile = CHAMELEON_dporfs_Tile
+CHAMELEON_sposvx_Tile = CHAMELEON_dposvx_Tile
 
 
 def residual_plgsy(L: Desc, bump: float, seed: int) -> float:

@@ -67,6 +67,12 @@ struct Ctx {
   void *cn[7] = {};
   size_t cn_bytes[7] = {};
   double cn_stats[4] = {};  // of the last chol_pocon_tile (chol_last_pocon_stats)
+  // chol_porfs_tile / chol_posvx_tile's scratch, grown on demand and kept (not g.work either): one condest-layout
+  // vector per column for the residuals / estimator, the FERR weights and the signs, the residual partials, the
+  // sweeps' scratch, the backward errors and statistics, potrs's n x k image, poequ's partials
+  void *rf[8] = {};
+  size_t rf_bytes[8] = {};
+  double rf_stats[8] = {};  // of the last chol_posvx_tile / chol_porfs_tile (chol_last_posvx_stats)
   std::string last_error;
 };
 
@@ -1090,6 +1096,11 @@ int chol_finalize(void) {
     g.cn[i] = nullptr;
     g.cn_bytes[i] = 0;
   }
+  for (int i = 0; i < 8; ++i) {
+    if (g.rf[i]) (void)hipFree(g.rf[i]);
+    g.rf[i] = nullptr;
+    g.rf_bytes[i] = 0;
+  }
   tx_destroy();
   g.wc_ptr = nullptr;
   g.wc_version = 0;
@@ -1638,11 +1649,20 @@ int chol_debug_task_check(long long *out5) {
 }
 
 // ---------------------------------------------------------------- POTRF
+static int potrf_run(int uplo, chol_desc *A);
+
 int chol_potrf_tile(int uplo, chol_desc_t *A) {
   return with_views({{A, true}}, [&]() -> int {
   if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "potrf_tile before chol_init");
   if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "potrf_tile: uplo");
   if (!A) return fail(-2, "potrf_tile: NULL descriptor");
+  return potrf_run(uplo, A);
+  });
+}
+
+// chol_potrf_tile after its argument checks, on the descriptor's image as it stands (posvx factors AF inside its own
+// view refresh)
+static int potrf_run(int uplo, chol_desc *A) {
   std::lock_guard<std::recursive_mutex> lk(g_mu);
   if (uplo == CHOL_LOWER)
     return A->dtype == CHOL_REAL_DOUBLE ? potrf_impl<double>(A) : potrf_impl<float>(A);
@@ -1665,7 +1685,6 @@ int chol_potrf_tile(int uplo, chol_desc_t *A) {
   flip();
   HIPCHECK(hipStreamSynchronize(g.r.st[ST_MAIN]));
   return rc;
-  });
 }
 
 int chol_trsm_tile(int side, int uplo, int trans, int diag, double alpha, chol_desc_t *A,
@@ -2327,8 +2346,94 @@ struct CnEvents {  // [0, 1]: around the current application, [2, 3]: the whole 
 };
 }  // namespace
 
+// LAPACK DLACN2's control flow for one vector (Higham's estimator, as LAPACK has it): what the device does before the
+// next application of the operator (fill x: -1 nothing, 0 1/n, 1 e_j, 2 the alternating-sign vector; kase 1 / 2), the
+// statistics after it (condest.hip: launch_vec_stats with `sign`, `jlast`), and the estimate.  pocon applies A^{-1}
+// for both kases; porfs applies diag(W) A^{-1} (kase 1) and A^{-1} diag(W) (kase 2).
+struct Lacn2 {
+  static constexpr int ITMAX = 5;
+  long n = 0;
+  int isave = 0, iter = 0;
+  long j = 0;
+  double est = 0;
+  bool done = false, finite = true;
+  int fill = 0, kase = 1, sign = 1;
+  long fill_j = 0, jlast = -1;
+  void next(int isave_, int fill_, long fill_j_, int kase_, int sign_, long jlast_) {
+    isave = isave_, fill = fill_, fill_j = fill_j_, kase = kase_, sign = sign_, jlast = jlast_;
+  }
+  void start(long n_) {
+    n = n_, iter = 0, j = 0, est = 0, done = false, finite = true;
+    next(1, 0, 0, 1, 1, -1);  // x = 1/n; after it est = ||x||_1, x = isgn = sign(x)
+  }
+  // st: launch_vec_stats' out[0..5] after the application (sum |x|, max |x|, its index, non-finite, x[jlast], changed)
+  template <typename T>
+  void take(const double *st) {
+    if (st[3] != 0) {  // (no dlatrs scaling: a non-finite entry ends the estimate)
+      finite = false;
+      done = true;
+      return;
+    }
+    switch (isave) {
+      case 1:
+        est = st[0];
+        if (n <= 1) {
+          done = true;
+          return;
+        }
+        return next(2, -1, 0, 2, 0, -1);  // then j = idamax(x)
+      case 2:
+        j = (long)st[2];
+        iter = 2;
+        return next(3, 1, j, 1, 1, -1);  // x = e_j; then est = ||x||_1, x = isgn = sign(x), changed?
+      case 3: {
+        const double estold = est;
+        est = st[0];
+        if (st[5] == 0 || est <= estold) break;  // a repeated sign vector, or no increase: converged
+        return next(4, -1, 0, 2, 0, j);          // then j = idamax(x), x(jlast) against |x(j)|
+      }
+      case 4:
+        if (st[4] != st[1] && iter < ITMAX) {
+          ++iter;
+          j = (long)st[2];
+          return next(3, 1, j, 1, 1, -1);
+        }
+        break;
+      default: {  // 5: the alternating-sign test vector
+        const T temp = T(2) * (T(st[0]) / T(3 * n));
+        if ((double)temp > est) est = (double)temp;
+        done = true;
+        return;
+      }
+    }
+    next(5, 2, 0, 1, 0, -1);
+  }
+};
+
+// the diagonal tiles of the factor, inverted once per call: their 128-blocks (as potrs), then the tiles (trtri's inner
+// level), into g.cn[0]
 template <typename T>
-static int pocon_impl(chol_desc *A, int upper, double anorm, double *rcond) {
+static int stage_factor_diag(chol_desc *A, int upper, const char *what) {
+  hipStream_t s = g.r.st[ST_MAIN];
+  const TileGeo ge = geo_of(A);
+  const int E = condest_edge(ge), nbm = E / MACRO, nt = A->nt;
+  const long blk = (long)MACRO * MACRO;
+  if (ensure_cn(0, (size_t)nt * E * E * sizeof(T)) || ensure_cn(1, (size_t)nt * nbm * blk * sizeof(T)) ||
+      ensure_cn(2, (size_t)nt * nbm * blk * sizeof(T)))
+    return cn_oom(what);
+  T *Dv = reinterpret_cast<T *>(g.cn[0]), *W = reinterpret_cast<T *>(g.cn[1]), *Y = reinterpret_cast<T *>(g.cn[2]);
+  launch_stage_diag<T>(s, ge, upper, reinterpret_cast<const T *>(A->mat), Dv);
+  launch_invert_diag_batch<T>(s, Dv, (long)E * E, nt, E, W);
+  const TriLevel<T> in{Dv, MACRO, (long)MACRO * E, (long)E * E, E, W, blk, nbm * blk, MACRO, Y, blk, nbm * blk, MACRO};
+  for (int c = nbm - 2; c >= 0; --c) launch_tri_column<T>(s, in, nbm, nt, c);
+  launch_tri_put_diag<T>(s, Dv, (long)E * E, E, nt, W);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// staged: g.cn[0] already holds the inverted diagonal tiles of this factor (posvx)
+template <typename T>
+static int pocon_impl(chol_desc *A, int upper, double anorm, double *rcond, bool staged = false) {
   hipStream_t s = g.r.st[ST_MAIN];
   const TileGeo ge = geo_of(A);
   const long n = A->lm;
@@ -2346,32 +2451,25 @@ static int pocon_impl(chol_desc *A, int upper, double anorm, double *rcond) {
   int rc = diag_zero<T>(A, &info);
   if (rc) return rc;
   if (info) return 0;  // a zero on the factor's diagonal: rcond = 0, no sweep
-  // scratch: the diagonal tiles, their 128-block inverses, the products' Y blocks, the vectors, the sign vector, the
-  // statistics
-  const int E = condest_edge(ge), nbm = E / MACRO, nt = A->nt, bpt = E / MACRO;
-  const long blk = (long)MACRO * MACRO, NB = (long)nt * bpt;
+  // scratch: the diagonal tiles, their 128-block inverses, the products' Y blocks (stage_factor_diag), the vectors,
+  // the sign vector, the statistics
+  const int E = condest_edge(ge), nt = A->nt, bpt = E / MACRO;
+  const long NB = (long)nt * bpt;
   const size_t nv = condest_vec_elems(ge), npg = 2 * (size_t)NB * bpt * MACRO, npd = (size_t)bpt * bpt * MACRO;
-  if (ensure_cn(0, (size_t)nt * E * E * sizeof(T)) || ensure_cn(1, (size_t)nt * nbm * blk * sizeof(T)) ||
-      ensure_cn(2, (size_t)nt * nbm * blk * sizeof(T)) || ensure_cn(3, (2 * nv + npg + npd) * sizeof(T)) ||
-      ensure_cn(4, nv * sizeof(int)) || ensure_cn(5, vec_stats_part_bytes() + 8 * sizeof(double)))
+  if (!staged && (rc = stage_factor_diag<T>(A, upper, "pocon_tile"))) return rc;
+  if (ensure_cn(3, (2 * nv + npg + npd) * sizeof(T)) || ensure_cn(4, nv * sizeof(int)) ||
+      ensure_cn(5, vec_stats_part_bytes() + 8 * sizeof(double)))
     return cn_oom("pocon_tile");
-  T *Dv = reinterpret_cast<T *>(g.cn[0]), *W = reinterpret_cast<T *>(g.cn[1]), *Y = reinterpret_cast<T *>(g.cn[2]);
+  const T *Dv = reinterpret_cast<const T *>(g.cn[0]);
   T *vx = reinterpret_cast<T *>(g.cn[3]);
   const SweepBufs<T> bufs{vx, vx + nv, vx + 2 * nv, vx + 2 * nv + npg};
   int *isgn = reinterpret_cast<int *>(g.cn[4]);
   double *spart = reinterpret_cast<double *>(g.cn[5]), *sout = spart + vec_stats_part_bytes() / sizeof(double);
   const T *Am = reinterpret_cast<const T *>(A->mat);
-  // the diagonal tiles of L, inverted once: their 128-blocks (as potrs), then the tiles (trtri's inner level)
-  launch_stage_diag<T>(s, ge, upper, Am, Dv);
-  launch_invert_diag_batch<T>(s, Dv, (long)E * E, nt, E, W);
-  const TriLevel<T> in{Dv, MACRO, (long)MACRO * E, (long)E * E, E, W, blk, nbm * blk, MACRO, Y, blk, nbm * blk, MACRO};
-  for (int c = nbm - 2; c >= 0; --c) launch_tri_column<T>(s, in, nbm, nt, c);
-  launch_tri_put_diag<T>(s, Dv, (long)E * E, E, nt, W);
-  HIPCHECK(hipGetLastError());
   int apps = 0;
   double sweep_ms = 0, st[6] = {0, 0, 0, 0, 0, 0};
-  // x <- A^{-1} x, then the statistics of x (DLACN2's kase != 0 round trip); false: a non-finite entry
-  auto apply = [&](int sign, long jlast, bool *finite) -> int {
+  // x <- A^{-1} x, then the statistics of x (DLACN2's kase != 0 round trip)
+  auto apply = [&](int sign, long jlast) -> int {
     HIPCHECK(hipEventRecord(ev.e[0], s));
     launch_sweep<T>(s, ge, upper, Am, Dv, bufs);
     HIPCHECK(hipEventRecord(ev.e[1], s));
@@ -2383,46 +2481,18 @@ static int pocon_impl(chol_desc *A, int upper, double anorm, double *rcond) {
     HIPCHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
     sweep_ms += ms;
     ++apps;
-    *finite = st[3] == 0;
     return 0;
   };
-  // DLACN2 (Higham's estimator as LAPACK has it); A is symmetric, so kase 1 and kase 2 apply the same A^{-1}
-  constexpr int ITMAX = 5;
-  bool ok = true;
-  double est = 0;
-  launch_vec_fill<T>(s, ge, bufs.x, 0, 0);
-  if ((rc = apply(1, -1, &ok))) return rc;  // (ISAVE 1) est = ||x||_1, x = isgn = sign(x)
-  est = st[0];
-  if (ok && n > 1) {
-    if ((rc = apply(0, -1, &ok))) return rc;  // (ISAVE 2) j = idamax(x)
-    long j = (long)st[2];
-    int iter = 2;
-    while (ok) {
-      launch_vec_fill<T>(s, ge, bufs.x, 1, j);
-      if ((rc = apply(1, -1, &ok))) return rc;  // (ISAVE 3) est = ||x||_1; x = isgn = sign(x), changed?
-      if (!ok) break;
-      const double estold = est;
-      est = st[0];
-      if (st[5] == 0 || est <= estold) break;  // a repeated sign vector, or no increase: converged
-      if ((rc = apply(0, j, &ok))) return rc;  // (ISAVE 4) j = idamax(x), x(jlast) against |x(j)|
-      if (!ok) break;
-      const long jnew = (long)st[2];
-      if (st[4] != st[1] && iter < ITMAX) {
-        ++iter;
-        j = jnew;
-        continue;
-      }
-      break;
-    }
-    if (ok) {
-      launch_vec_fill<T>(s, ge, bufs.x, 2, 0);
-      if ((rc = apply(0, -1, &ok))) return rc;  // (ISAVE 5) the alternating-sign test vector
-      const T temp = T(2) * (T(st[0]) / T(3 * n));
-      if ((double)temp > est) est = (double)temp;
-    }
+  // DLACN2; A is symmetric, so kase 1 and kase 2 apply the same A^{-1}
+  Lacn2 est;
+  est.start(n);
+  while (!est.done) {
+    if (est.fill >= 0) launch_vec_fill<T>(s, ge, bufs.x, est.fill, est.fill_j);
+    if ((rc = apply(est.sign, est.jlast))) return rc;
+    est.take<T>(st);
   }
   // (no dlatrs scaling: a sweep that overflows gives rcond = 0)
-  if (ok && est != 0) *rcond = (1.0 / est) / anorm;
+  if (est.finite && est.est != 0) *rcond = (1.0 / est.est) / anorm;
   HIPCHECK(hipEventRecord(ev.e[3], s));
   HIPCHECK(hipEventSynchronize(ev.e[3]));
   float total = 0;
@@ -2453,6 +2523,608 @@ int chol_last_pocon_stats(double *out4) {
   if (!out4) return fail(-1, "last_pocon_stats: NULL");
   std::lock_guard<std::recursive_mutex> lk(g_mu);
   for (int i = 0; i < 4; ++i) out4[i] = g.cn_stats[i];
+  return 0;
+}
+
+// ---------------------------------------------------------------- the SPD expert solve (LAPACK DPOEQU, DLAQSY, DPORFS, DPOSVX)
+// poequ / laqsy: one pass over the diagonal / the stored triangle (refine.hip).  porfs: every column in lockstep, each
+// with its own refinement count, lstres and DLACN2 state; each step applies A^{-1} only to the columns still active,
+// either with the multi-vector sweeps (at most K_X columns: ceil(k / 8) sweeps of up to 8 vectors) or with potrs_impl
+// on a scratch n x k image (wider steps).  posvx composes them in DPOSVX's order.
+extern "C++" {
+namespace {
+// the widest application of A^{-1} that runs as multi-vector sweeps; wider ones go through potrs_impl.  Measured
+// crossover: about 47 columns at N = 65536 / 1024, about 30 at 16384 / 512
+constexpr int POSVX_KX = 40;
+constexpr int PORFS_ITMAX = 5;
+
+template <typename T>
+struct Lam;  // LAPACK xLAMCH: 'E'psilon (rounding), 'S'afe minimum, 'P'recision = eps * base
+template <>
+struct Lam<double> {
+  static constexpr double eps = 0x1p-53, safmin = 0x1p-1022, prec = 0x1p-52;
+};
+template <>
+struct Lam<float> {
+  static constexpr double eps = 0x1p-24, safmin = 0x1p-126, prec = 0x1p-23;
+};
+}  // namespace
+}  // extern "C++"
+
+int ensure_rf(int idx, size_t bytes) {
+  if (g.rf_bytes[idx] >= bytes) return 0;
+  if (g.rf[idx]) HIPCHECK(hipFree(g.rf[idx]));
+  g.rf[idx] = nullptr;
+  g.rf_bytes[idx] = 0;
+  bytes = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
+  HIPCHECK(hipMalloc(&g.rf[idx], bytes));
+  HIPCHECK(hipMemset(g.rf[idx], 0, bytes));
+  g.rf_bytes[idx] = bytes;
+  return 0;
+}
+
+extern "C++" {
+namespace {
+// porfs / posvx's scratch (g.rf): the residual / estimator vectors, the FERR weights, the sign vectors (one
+// condest-layout vector per column each), the residual partials, the sweeps' scratch and padding vectors, the
+// backward errors and statistics, and the n x k image of the potrs path
+template <typename T>
+struct RfBufs {
+  T *R, *F, *part, *sw, *pad;
+  int *isgn;
+  unsigned long long *berr;
+  double *spart, *sout;
+  long nv;
+};
+
+template <typename T>
+static int rf_buffers(const TileGeo &ga, int nrhs, RfBufs<T> *b, const char *what) {
+  const long nv = (long)condest_vec_elems(ga);
+  const size_t vb = (size_t)nrhs * nv * sizeof(T);
+  const size_t sb = vec_stats_part_bytes() + (size_t)(nrhs + 1) * 8 * sizeof(double);
+  if (ensure_rf(0, vb) || ensure_rf(1, vb) || ensure_rf(2, (size_t)nrhs * nv * sizeof(int)) ||
+      ensure_rf(3, porfs_part_elems(ga, refine_width(std::min(nrhs, 8))) * sizeof(T)) ||
+      ensure_rf(4, (msweep_scratch_elems(ga) + 8 * (size_t)nv) * sizeof(T)) ||
+      ensure_rf(5, (size_t)nrhs * sizeof(unsigned long long) + sb))
+    return cn_oom(what);
+  b->nv = nv;
+  b->R = reinterpret_cast<T *>(g.rf[0]);
+  b->F = reinterpret_cast<T *>(g.rf[1]);
+  b->isgn = reinterpret_cast<int *>(g.rf[2]);
+  b->part = reinterpret_cast<T *>(g.rf[3]);
+  b->sw = reinterpret_cast<T *>(g.rf[4]);
+  b->pad = b->sw + msweep_scratch_elems(ga);
+  b->berr = reinterpret_cast<unsigned long long *>(g.rf[5]);
+  b->spart = reinterpret_cast<double *>(b->berr + nrhs);
+  b->sout = b->spart + vec_stats_part_bytes() / sizeof(double);
+  return 0;
+}
+
+// V[c] <- A^{-1} V[c] for the slots c in `cols` (AF: the factor, its diagonal tiles staged in g.cn[0]); st: posvx stats;
+// path: 0 the path rule, 1 the sweeps, 2 potrs (chol_bench_refine)
+template <typename T>
+static int apply_inv(int upper, chol_desc *AF, const RfBufs<T> &b, T *V, const std::vector<int> &cols, double *st,
+                     int path = 0) {
+  hipStream_t s = g.r.st[ST_MAIN];
+  const TileGeo ga = geo_of(AF);
+  const int k = (int)cols.size();
+  if (!k) return 0;
+  if (path == 1 || (path == 0 && k <= POSVX_KX)) {
+    const long NB = (long)ga.lmt * (condest_edge(ga) / MACRO);
+    const long nv = b.nv, pgn = 2 * NB * (condest_edge(ga) / MACRO) * MACRO;
+    const MSweepBufs<T> mb{b.sw, b.sw + 8 * nv, b.sw + 8 * nv + 8 * pgn};
+    for (int c0 = 0; c0 < k; c0 += 8) {
+      const int m = std::min(8, k - c0);
+      T *x[8];
+      for (int j = 0; j < m; ++j) x[j] = V + (long)cols[c0 + j] * nv;
+      launch_msweep<T>(s, ga, upper, reinterpret_cast<const T *>(AF->mat), reinterpret_cast<const T *>(g.cn[0]), x, m,
+                       b.pad, mb);
+      st[6] += m;
+    }
+    HIPCHECK(hipGetLastError());
+    return 0;
+  }
+  // wide: potrs_impl on an n x k scratch image with AF's row tiling (the solve runs on whole tiles: zero padding)
+  chol_desc Td = *AF;
+  Td.ln = Td.n = k;
+  Td.nt = Td.lnt = (k + AF->mb - 1) / AF->mb;
+  Td.owns = false;
+  Td.version = 0;
+  Td.d_list = nullptr;
+  Td.user_mat = nullptr;
+  const size_t tb = (size_t)Td.lmt * Td.lnt * Td.bsizi * sizeof(T);
+  if (ensure_rf(6, tb)) return cn_oom("porfs_tile");
+  Td.mat = g.rf[6];
+  HIPCHECK(hipMemsetAsync(Td.mat, 0, tb, s));
+  const TileGeo gt = geo_of(&Td);
+  for (int c0 = 0; c0 < k; c0 += 8) {
+    VecCols vc{std::min(8, k - c0), {}, {}};
+    for (int j = 0; j < vc.n; ++j) vc.v[j] = cols[c0 + j], vc.d[j] = c0 + j;
+    launch_scatter<T>(s, gt, reinterpret_cast<T *>(Td.mat), vc, V, false);
+  }
+  auto flip = [&]() { launch_transpose_inplace<T>(s, reinterpret_cast<T *>(AF->mat), AF->nt, AF->mbi); };
+  if (upper) flip();
+  int rc = potrs_impl<T>(AF, &Td);
+  if (upper) flip();
+  if (rc) return rc;
+  for (int c0 = 0; c0 < k; c0 += 8) {
+    VecCols vc{std::min(8, k - c0), {}, {}};
+    for (int j = 0; j < vc.n; ++j) vc.v[j] = cols[c0 + j], vc.d[j] = c0 + j;
+    launch_gather<T>(s, gt, reinterpret_cast<const T *>(Td.mat), vc, V);
+  }
+  HIPCHECK(hipGetLastError());
+  st[7] += k;
+  return 0;
+}
+
+template <typename T>
+static std::vector<VecCols> groups_of(const std::vector<int> &cols) {
+  std::vector<VecCols> out;
+  for (size_t c0 = 0; c0 < cols.size(); c0 += 8) {
+    VecCols vc{(int)std::min<size_t>(8, cols.size() - c0), {}, {}};
+    for (int j = 0; j < vc.n; ++j) vc.v[j] = vc.d[j] = cols[c0 + j];
+    out.push_back(vc);
+  }
+  return out;
+}
+
+// LAPACK DPORFS on device images; AF's diagonal tiles staged in g.cn[0]; st: posvx stats ([5] total porfs ms,
+// [6] / [7] columns through the sweeps / through potrs)
+template <typename T>
+static int porfs_impl(int upper, chol_desc *A, chol_desc *AF, chol_desc *B, chol_desc *X, double *ferr, double *berr,
+                      double *st) {
+  hipStream_t s = g.r.st[ST_MAIN];
+  const TileGeo ga = geo_of(A), gx = geo_of(B);
+  const long n = A->lm;
+  const int nrhs = B->ln;
+  if (n == 0 || nrhs == 0) {
+    std::fill(ferr, ferr + nrhs, 0.0);
+    std::fill(berr, berr + nrhs, 0.0);
+    return 0;
+  }
+  MxTimer tt;
+  int rc = tt.start();
+  if (rc) return rc;
+  RfBufs<T> b;
+  if ((rc = rf_buffers<T>(ga, nrhs, &b, "porfs_tile"))) return rc;
+  const double eps = Lam<T>::eps, safe1 = (double)(T(n + 1) * T(Lam<T>::safmin)), safe2 = (double)(T(safe1) / T(eps));
+  const T *Am = reinterpret_cast<const T *>(A->mat);
+  std::vector<int> count(nrhs, 1), active(nrhs);
+  std::vector<double> lstres(nrhs, 3.0);
+  std::vector<unsigned long long> hb(nrhs);
+  for (int j = 0; j < nrhs; ++j) active[j] = j;
+  // refinement: R = B - A X, BERR; X += A^{-1} R for the columns that go on
+  while (!active.empty()) {
+    HIPCHECK(hipMemsetAsync(b.berr, 0, (size_t)nrhs * sizeof(unsigned long long), s));
+    for (const VecCols &vc : groups_of<T>(active))
+      launch_porfs_resid<T>(s, ga, upper, Am, gx, reinterpret_cast<const T *>(X->mat), reinterpret_cast<const T *>(B->mat),
+                            vc, b.part, b.R, b.F, eps, safe1, safe2, b.berr);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(hb.data(), b.berr, (size_t)nrhs * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    std::vector<int> next;
+    for (int j : active) {
+      double bj;
+      memcpy(&bj, &hb[j], sizeof bj);
+      berr[j] = bj;
+      if (bj > eps && 2 * bj <= lstres[j] && count[j] <= PORFS_ITMAX) {
+        next.push_back(j);
+        lstres[j] = bj;
+        ++count[j];
+      }
+    }
+    if ((rc = apply_inv<T>(upper, AF, b, b.R, next, st))) return rc;
+    for (const VecCols &vc : groups_of<T>(next)) launch_scatter<T>(s, gx, reinterpret_cast<T *>(X->mat), vc, b.R, true);
+    active.swap(next);
+  }
+  // FERR: DLACN2 on diag(F) A^{-1} (kase 1) / A^{-1} diag(F) (kase 2), every column in lockstep, x in the R slots
+  std::vector<Lacn2> est(nrhs);
+  for (int j = 0; j < nrhs; ++j) est[j].start(n), active.push_back(j);
+  std::vector<double> hs((size_t)nrhs * 8);
+  while (!active.empty()) {
+    const std::vector<VecCols> gr = groups_of<T>(active);
+    for (int j : active)
+      if (est[j].fill >= 0) launch_vec_fill<T>(s, ga, b.R + (long)j * b.nv, est[j].fill, est[j].fill_j);
+    auto weight = [&](int kase) {
+      for (const VecCols &vc : gr) {
+        unsigned mask = 0;
+        for (int i = 0; i < vc.n; ++i) mask |= (est[vc.v[i]].kase == kase ? 1u : 0u) << i;
+        launch_vec_weight<T>(s, ga, b.R, b.F, vc, mask);
+      }
+    };
+    weight(2);
+    if ((rc = apply_inv<T>(upper, AF, b, b.R, active, st))) return rc;
+    weight(1);
+    for (size_t i = 0; i < active.size(); ++i) {
+      const int j = active[i];
+      launch_vec_stats<T>(s, ga, b.R + (long)j * b.nv, b.isgn + (long)j * b.nv, est[j].sign, est[j].jlast, b.spart,
+                          b.sout + 8 * i);
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(hs.data(), b.sout, active.size() * 8 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    std::vector<int> next;
+    for (size_t i = 0; i < active.size(); ++i) {
+      const int j = active[i];
+      est[j].take<T>(&hs[8 * i]);
+      if (!est[j].done) next.push_back(j);
+    }
+    active.swap(next);
+  }
+  // normalise by max |X(:,j)| (gathered into a padding vector, then launch_vec_stats)
+  for (int j = 0; j < nrhs; ++j) {
+    const VecCols vc{1, {0}, {j}};
+    launch_gather<T>(s, gx, reinterpret_cast<const T *>(X->mat), vc, b.pad);
+    launch_vec_stats<T>(s, ga, b.pad, b.isgn, 0, -1, b.spart, b.sout + 8 * j);
+  }
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpyAsync(hs.data(), b.sout, (size_t)nrhs * 8 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  for (int j = 0; j < nrhs; ++j) {
+    T f = est[j].finite ? T(est[j].est) : T(INFINITY);
+    const T xm = T(hs[8 * j + 1]);
+    if (xm != T(0)) f = f / xm;
+    ferr[j] = (double)f;
+  }
+  return tt.stop(&st[5]);
+}
+}  // namespace
+}  // extern "C++"
+
+// the descriptor rules shared by porfs / posvx: an n x nrhs image d with A's dtype, order and tile size
+static int rhs_check(const char *what, const chol_desc *A, const chol_desc *d, int pos, const char *name) {
+  char buf[160];
+  if (!d) {
+    snprintf(buf, sizeof buf, "%s: %s is NULL", what, name);
+    return fail(-pos, buf);
+  }
+  if (int rc = resident_whole(what, d)) return rc;
+  if (d->dtype != A->dtype || d->lm != A->lm || d->mb != A->mb || d->mbi != A->mbi) {
+    snprintf(buf, sizeof buf, "%s: %s must have A's dtype, order and tile size", what, name);
+    return fail(-pos, buf);
+  }
+  return 0;
+}
+
+static int square_check(const char *what, chol_desc *A, int pos) {
+  if (!A) {
+    char buf[96];
+    snprintf(buf, sizeof buf, "%s: NULL descriptor", what);
+    return fail(-pos, buf);
+  }
+  return inverse_check(what, A, pos);
+}
+
+extern "C++" {
+// LAPACK DPOEQU on the device: S <- 1/sqrt(diag), *scond, *amax; info > 0: the first non-positive diagonal entry
+template <typename T>
+static int poequ_impl(chol_desc *A, chol_desc *S, double *scond, double *amax, int *info) {
+  hipStream_t s = g.r.st[ST_MAIN];
+  const long n = A->lm;
+  *info = 0;
+  if (n == 0) {
+    *scond = 1, *amax = 0;
+    return 0;
+  }
+  if (ensure_rf(7, diag_scan_part_bytes())) return cn_oom("poequ_tile");
+  double *part = reinterpret_cast<double *>(g.rf[7]);
+  launch_diag_scan<T>(s, geo_of(A), reinterpret_cast<const T *>(A->mat), reinterpret_cast<T *>(S->mat), 0, part);
+  HIPCHECK(hipGetLastError());
+  std::vector<double> h(diag_scan_part_bytes() / sizeof(double));
+  HIPCHECK(hipMemcpyAsync(h.data(), part, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  const long per = (n + 255) / 256;
+  T smin = T(INFINITY), smax = T(-INFINITY);
+  long bad = -1;
+  for (long w = 0; w < 256 && w * per < n; ++w) {
+    smin = std::min(smin, T(h[3 * w]));
+    smax = std::max(smax, T(h[3 * w + 1]));
+    if (h[3 * w + 2] >= 0 && bad < 0) bad = (long)h[3 * w + 2];
+  }
+  *amax = (double)smax;
+  if (smin <= T(0)) {
+    *info = (int)(bad + 1);
+    return 0;
+  }
+  *scond = (double)(T(std::sqrt(smin)) / T(std::sqrt(smax)));
+  return 0;
+}
+
+// LAPACK DLAQSY's decision and scaling; *equed <- 1 ('Y') or 0 ('N')
+template <typename T>
+static int laqsy_impl(int upper, chol_desc *A, chol_desc *S, double scond, double amax, int *equed) {
+  const double small = Lam<T>::safmin / Lam<T>::prec, large = 1.0 / small;
+  *equed = 0;
+  if (A->lm == 0) return 0;
+  if (scond >= 0.1 && amax >= small && amax <= large) return 0;
+  launch_laqsy<T>(g.r.st[ST_MAIN], geo_of(A), upper, reinterpret_cast<T *>(A->mat), reinterpret_cast<const T *>(S->mat));
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(g.r.st[ST_MAIN]));
+  *equed = 1;
+  return 0;
+}
+}  // extern "C++"
+
+int chol_poequ_tile(chol_desc_t *A, chol_desc_t *S, double *scond, double *amax) {
+  return with_views({{A, false}, {S, true}}, [&]() -> int {
+  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "poequ_tile before chol_init");
+  int rc = square_check("poequ_tile", A, 1);
+  if (rc) return rc;
+  if ((rc = rhs_check("poequ_tile", A, S, 2, "S"))) return rc;
+  if (S->ln != 1 || S->mat == A->mat) return fail(-2, "poequ_tile: S must be an n x 1 descriptor of its own");
+  if (!scond) return fail(-3, "poequ_tile: NULL scond");
+  if (!amax) return fail(-4, "poequ_tile: NULL amax");
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  int info = 0;
+  rc = A->dtype == CHOL_REAL_DOUBLE ? poequ_impl<double>(A, S, scond, amax, &info)
+                                    : poequ_impl<float>(A, S, scond, amax, &info);
+  return rc ? rc : info;
+  });
+}
+
+int chol_laqsy_tile(int uplo, chol_desc_t *A, chol_desc_t *S, double scond, double amax, int *equed) {
+  return with_views({{A, true}, {S, false}}, [&]() -> int {
+  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "laqsy_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "laqsy_tile: uplo");
+  int rc = square_check("laqsy_tile", A, 2);
+  if (rc) return rc;
+  if ((rc = rhs_check("laqsy_tile", A, S, 3, "S"))) return rc;
+  if (S->ln != 1 || S->mat == A->mat) return fail(-3, "laqsy_tile: S must be an n x 1 descriptor of its own");
+  if (!(scond >= 0)) return fail(-4, "laqsy_tile: scond is negative or NaN");
+  if (!(amax >= 0)) return fail(-5, "laqsy_tile: amax is negative or NaN");
+  if (!equed) return fail(-6, "laqsy_tile: NULL equed");
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  const int up = uplo == CHOL_UPPER;
+  return A->dtype == CHOL_REAL_DOUBLE ? laqsy_impl<double>(up, A, S, scond, amax, equed)
+                                      : laqsy_impl<float>(up, A, S, scond, amax, equed);
+  });
+}
+
+// the checks of porfs (apos: A's position; B, X follow AF)
+static int porfs_args(const char *what, chol_desc *A, chol_desc *AF, chol_desc *B, chol_desc *X, int apos, int bpos,
+                      int xpos) {
+  int rc = square_check(what, A, apos);
+  if (rc) return rc;
+  if ((rc = square_check(what, AF, apos + 1))) return rc;
+  char buf[160];
+  if (!same_geometry(A, AF) || AF->mat == A->mat) {
+    snprintf(buf, sizeof buf, "%s: AF must have A's shape, tile size and type, in storage of its own", what);
+    return fail(-(apos + 1), buf);
+  }
+  if ((rc = rhs_check(what, A, B, bpos, "B"))) return rc;
+  if ((rc = rhs_check(what, A, X, xpos, "X"))) return rc;
+  if (!same_geometry(B, X)) {
+    snprintf(buf, sizeof buf, "%s: X must have B's shape, tile size and type", what);
+    return fail(-xpos, buf);
+  }
+  if (X->mat == A->mat || X->mat == AF->mat || X->mat == B->mat || B->mat == A->mat || B->mat == AF->mat) {
+    snprintf(buf, sizeof buf, "%s: X aliases A, AF or B", what);
+    return fail(-xpos, buf);
+  }
+  if (!winv_fits(AF)) {  // (the wide steps solve with potrs_impl)
+    snprintf(buf, sizeof buf, "%s: tile size above 4096", what);
+    return fail(CHOL_ERR_NOT_SUPPORTED, buf);
+  }
+  return 0;
+}
+
+int chol_porfs_tile(int uplo, chol_desc_t *A, chol_desc_t *AF, chol_desc_t *B, chol_desc_t *X, double *ferr,
+                    double *berr) {
+  return with_views({{A, false}, {AF, false}, {B, false}, {X, true}}, [&]() -> int {
+  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "porfs_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "porfs_tile: uplo");
+  int rc = porfs_args("porfs_tile", A, AF, B, X, 2, 4, 5);
+  if (rc) return rc;
+  if (!ferr) return fail(-6, "porfs_tile: NULL ferr");
+  if (!berr) return fail(-7, "porfs_tile: NULL berr");
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  const int up = uplo == CHOL_UPPER;
+  std::fill(g.rf_stats, g.rf_stats + 8, 0.0);
+  MxTimer tt;
+  if ((rc = tt.start())) return rc;
+  if (A->dtype == CHOL_REAL_DOUBLE) {
+    if (!(rc = stage_factor_diag<double>(AF, up, "porfs_tile")))
+      rc = porfs_impl<double>(up, A, AF, B, X, ferr, berr, g.rf_stats);
+  } else {
+    if (!(rc = stage_factor_diag<float>(AF, up, "porfs_tile")))
+      rc = porfs_impl<float>(up, A, AF, B, X, ferr, berr, g.rf_stats);
+  }
+  if (rc) return rc;
+  return tt.stop(&g.rf_stats[0]);
+  });
+}
+
+extern "C++" {
+template <typename T>
+static int posvx_impl(int fact, int upper, chol_desc *A, chol_desc *AF, int *equed, chol_desc *S, chol_desc *B,
+                      chol_desc *X, double *rcond, double *ferr, double *berr) {
+  hipStream_t s = g.r.st[ST_MAIN];
+  double *st = g.rf_stats;  // total, equilibrate + scale B, factor, lansy + pocon, solve, porfs, #sweep / #potrs columns
+  std::fill(st, st + 8, 0.0);
+  const long n = A->lm;
+  const int nrhs = B->ln, uplo = upper ? CHOL_UPPER : CHOL_LOWER;
+  MxTimer tt, tp;
+  int rc = tt.start();
+  if (rc) return rc;
+  bool rcequ = false;
+  double scond = 1;
+  if ((rc = tp.start())) return rc;
+  if (fact == CHOL_FACT_FACTORED) {
+    rcequ = *equed == 1;
+    if (rcequ && n > 0) {  // DPOSVX: scond from S itself
+      if (ensure_rf(7, diag_scan_part_bytes())) return cn_oom("posvx_tile");
+      double *part = reinterpret_cast<double *>(g.rf[7]);
+      launch_diag_scan<T>(s, geo_of(A), nullptr, reinterpret_cast<T *>(S->mat), 1, part);
+      std::vector<double> h(diag_scan_part_bytes() / sizeof(double));
+      HIPCHECK(hipMemcpyAsync(h.data(), part, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+      HIPCHECK(hipStreamSynchronize(s));
+      const long per = (n + 255) / 256;
+      T smin = T(INFINITY), smax = T(-INFINITY);
+      for (long w = 0; w < 256 && w * per < n; ++w) smin = std::min(smin, T(h[3 * w])), smax = std::max(smax, T(h[3 * w + 1]));
+      if (!(smin > T(0))) return fail(-6, "posvx_tile: S has an entry <= 0");
+      const T smlnum = T(Lam<T>::safmin), bignum = T(1) / smlnum;
+      scond = (double)(std::max(smin, smlnum) / std::min(smax, bignum));
+    }
+  } else {
+    *equed = 0;
+    if (fact == CHOL_FACT_EQUILIBRATE) {
+      int infequ = 0;
+      double amax = 0;
+      if ((rc = poequ_impl<T>(A, S, &scond, &amax, &infequ))) return rc;
+      if (infequ == 0) {
+        if ((rc = laqsy_impl<T>(upper, A, S, scond, amax, equed))) return rc;
+        rcequ = *equed == 1;
+      }
+    }
+  }
+  const TileGeo ga = geo_of(A), gx = geo_of(B);
+  if (rcequ) launch_row_scale<T>(s, gx, reinterpret_cast<T *>(B->mat), reinterpret_cast<const T *>(S->mat));
+  HIPCHECK(hipGetLastError());
+  if ((rc = tp.stop(&st[1]))) return rc;
+  if (fact != CHOL_FACT_FACTORED) {
+    if ((rc = tp.start())) return rc;
+    launch_lacpy<T>(s, ga, upper ? 2 : 1, reinterpret_cast<const T *>(A->mat), reinterpret_cast<T *>(AF->mat));
+    HIPCHECK(hipGetLastError());
+    const int info = potrf_run(uplo, AF);
+    if (info < 0) return info;
+    if ((rc = tp.stop(&st[2]))) return rc;
+    if (info > 0) {
+      *rcond = 0;
+      return tt.stop(&st[0]) ? CHOL_ERR_HIP : info;
+    }
+  }
+  // rcond: anorm = ||A||_1 of the (equilibrated) A, the estimate on AF's sweeps
+  if ((rc = tp.start())) return rc;
+  const size_t pb = lansy_part_bytes(ga);
+  if (ensure_cn(6, pb + 4 * sizeof(double))) return cn_oom("posvx_tile");
+  double *lpart = reinterpret_cast<double *>(g.cn[6]), *lres = lpart + pb / sizeof(double);
+  launch_lansy<T>(s, ga, upper, reinterpret_cast<const T *>(A->mat), lpart, lres);
+  double lv[3] = {0, 0, 0};
+  HIPCHECK(hipMemcpyAsync(lv, lres, sizeof lv, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  if ((rc = stage_factor_diag<T>(AF, upper, "posvx_tile"))) return rc;
+  if ((rc = pocon_impl<T>(AF, upper, lv[1], rcond, /*staged=*/true))) return rc;
+  if ((rc = tp.stop(&st[3]))) return rc;
+  // X <- A^{-1} B: the sweeps on B's columns gathered into the R slots, or lacpy and potrs_impl when wide
+  if ((rc = tp.start())) return rc;
+  if (nrhs > 0 && n > 0) {
+    if (nrhs <= POSVX_KX) {
+      RfBufs<T> b;
+      if ((rc = rf_buffers<T>(ga, nrhs, &b, "posvx_tile"))) return rc;
+      std::vector<int> all(nrhs);
+      for (int j = 0; j < nrhs; ++j) all[j] = j;
+      const std::vector<VecCols> gr = groups_of<T>(all);
+      for (const VecCols &vc : gr) launch_gather<T>(s, gx, reinterpret_cast<const T *>(B->mat), vc, b.R);
+      if ((rc = apply_inv<T>(upper, AF, b, b.R, all, st))) return rc;
+      for (const VecCols &vc : gr) launch_scatter<T>(s, gx, reinterpret_cast<T *>(X->mat), vc, b.R, false);
+    } else {
+      launch_lacpy<T>(s, gx, 0, reinterpret_cast<const T *>(B->mat), reinterpret_cast<T *>(X->mat));
+      auto flip = [&]() { launch_transpose_inplace<T>(s, reinterpret_cast<T *>(AF->mat), AF->nt, AF->mbi); };
+      if (upper) flip();
+      rc = potrs_impl<T>(AF, X);
+      if (upper) flip();
+      if (rc) return rc;
+      st[7] += nrhs;
+    }
+    HIPCHECK(hipGetLastError());
+  }
+  if ((rc = tp.stop(&st[4]))) return rc;
+  if ((rc = porfs_impl<T>(upper, A, AF, B, X, ferr, berr, st))) return rc;
+  // the solution of the original system, its error bound
+  if (rcequ) {
+    launch_row_scale<T>(s, gx, reinterpret_cast<T *>(X->mat), reinterpret_cast<const T *>(S->mat));
+    HIPCHECK(hipGetLastError());
+    for (int j = 0; j < nrhs; ++j) ferr[j] = (double)(T(ferr[j]) / T(scond));
+  }
+  if ((rc = tt.stop(&st[0]))) return rc;
+  return *rcond < Lam<T>::eps ? (int)(n + 1) : 0;
+}
+}  // extern "C++"
+
+int chol_posvx_tile(int fact, int uplo, chol_desc_t *A, chol_desc_t *AF, int *equed, chol_desc_t *S, chol_desc_t *B,
+                    chol_desc_t *X, double *rcond, double *ferr, double *berr) {
+  return with_views({{A, true}, {AF, true}, {S, true}, {B, true}, {X, true}}, [&]() -> int {
+  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "posvx_tile before chol_init");
+  if (fact != CHOL_FACT_NONE && fact != CHOL_FACT_EQUILIBRATE && fact != CHOL_FACT_FACTORED)
+    return fail(-1, "posvx_tile: fact");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-2, "posvx_tile: uplo");
+  int rc = porfs_args("posvx_tile", A, AF, B, X, 3, 7, 8);
+  if (rc) return rc;
+  if (!equed) return fail(-5, "posvx_tile: NULL equed");
+  if (fact == CHOL_FACT_FACTORED && *equed != 0 && *equed != 1) return fail(-5, "posvx_tile: equed must be 0 or 1");
+  const bool need_s = fact == CHOL_FACT_EQUILIBRATE || (fact == CHOL_FACT_FACTORED && *equed == 1);
+  if (need_s || S) {
+    if ((rc = rhs_check("posvx_tile", A, S, 6, "S"))) return rc;
+    if (S->ln != 1 || S->mat == A->mat || S->mat == AF->mat || S->mat == B->mat || S->mat == X->mat)
+      return fail(-6, "posvx_tile: S must be an n x 1 descriptor of its own");
+  }
+  if (!rcond) return fail(-9, "posvx_tile: NULL rcond");
+  if (!ferr) return fail(-10, "posvx_tile: NULL ferr");
+  if (!berr) return fail(-11, "posvx_tile: NULL berr");
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  const int up = uplo == CHOL_UPPER;
+  return A->dtype == CHOL_REAL_DOUBLE ? posvx_impl<double>(fact, up, A, AF, equed, S, B, X, rcond, ferr, berr)
+                                      : posvx_impl<float>(fact, up, A, AF, equed, S, B, X, rcond, ferr, berr);
+  });
+}
+
+// the parts of porfs alone, for scripts/posvx_time.py: path 0 the residual pass over X's columns (B = X), 1 one
+// application of A^{-1} to them by the multi-vector sweeps, 2 the same by potrs_impl; *ms <- the fastest of reps
+extern "C++" {
+template <typename T>
+static int bench_refine_impl(int upper, chol_desc *A, chol_desc *AF, chol_desc *X, int path, int reps, double *ms) {
+  hipStream_t s = g.r.st[ST_MAIN];
+  const TileGeo ga = geo_of(A), gx = geo_of(X);
+  const int k = X->ln;
+  RfBufs<T> b;
+  int rc = rf_buffers<T>(ga, k, &b, "bench_refine");
+  if (rc) return rc;
+  if ((rc = stage_factor_diag<T>(AF, upper, "bench_refine"))) return rc;
+  std::vector<int> all(k);
+  for (int j = 0; j < k; ++j) all[j] = j;
+  for (const VecCols &vc : groups_of<T>(all)) launch_gather<T>(s, gx, reinterpret_cast<const T *>(X->mat), vc, b.R);
+  double st[8] = {};
+  *ms = 1e30;
+  for (int r = 0; r <= reps; ++r) {
+    MxTimer tt;
+    if ((rc = tt.start())) return rc;
+    if (path == 0) {
+      for (const VecCols &vc : groups_of<T>(all))
+        launch_porfs_resid<T>(s, ga, upper, reinterpret_cast<const T *>(A->mat), gx, reinterpret_cast<const T *>(X->mat),
+                              reinterpret_cast<const T *>(X->mat), vc, b.part, b.R, b.F, Lam<T>::eps, 0.0, 0.0, b.berr);
+    } else {
+      if ((rc = apply_inv<T>(upper, AF, b, b.R, all, st, path))) return rc;
+    }
+    HIPCHECK(hipGetLastError());
+    double t = 0;
+    if ((rc = tt.stop(&t))) return rc;
+    if (r > 0) *ms = std::min(*ms, t);
+  }
+  return 0;
+}
+}  // extern "C++"
+
+int chol_bench_refine(int uplo, chol_desc_t *A, chol_desc_t *AF, chol_desc_t *X, int path, int reps, double *ms) {
+  return with_views({{A, false}, {AF, false}, {X, false}}, [&]() -> int {
+  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "bench_refine before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "bench_refine: uplo");
+  int rc = square_check("bench_refine", A, 2);
+  if (rc) return rc;
+  if ((rc = square_check("bench_refine", AF, 3))) return rc;
+  if ((rc = rhs_check("bench_refine", A, X, 4, "X"))) return rc;
+  if (path < 0 || path > 2 || reps < 1 || !ms) return fail(-5, "bench_refine: path, reps or ms");
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  const int up = uplo == CHOL_UPPER;
+  return A->dtype == CHOL_REAL_DOUBLE ? bench_refine_impl<double>(up, A, AF, X, path, reps, ms)
+                                      : bench_refine_impl<float>(up, A, AF, X, path, reps, ms);
+  });
+}
+
+int chol_last_posvx_stats(double *out8) {
+  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "last_posvx_stats before chol_init");
+  if (!out8) return fail(-1, "last_posvx_stats: NULL");
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  for (int i = 0; i < 8; ++i) out8[i] = g.rf_stats[i];
   return 0;
 }
 

@@ -348,6 +348,53 @@ template <typename T>
 void launch_vec_stats(hipStream_t s, const TileGeo &g, T *x, int *isgn, int sign, long jlast, double *part,
                       double *out);
 
+// ---- launchers (refine.hip): chol_poequ_tile, chol_laqsy_tile, chol_porfs_tile, chol_posvx_tile (condest.hip's
+// geometry and vector layout).  An n x ncols image (B, X, S) has the matrix's row tiling (same mbs, mbu, lmt).
+// Up to 8 columns of an image and the condest-layout vector slots they go with: slot v[j] <-> image column d[j].
+struct VecCols {
+  int n;
+  int v[8], d[8];
+};
+int refine_width(int k);  // the group size 1, 2, 4 or 8 that takes k <= 8 columns
+// mode 0: S(i) <- 1/sqrt(A(i,i)) (IEEE) where A(i,i) > 0; mode 1: only scan S.  part (diag_scan_part_bytes): per
+// workgroup min, max, the first 0-based i with a value <= 0 (or -1) of the scanned values
+size_t diag_scan_part_bytes();
+template <typename T>
+void launch_diag_scan(hipStream_t s, const TileGeo &g, const T *A, T *S, int mode, double *part);
+// the stored triangle of A <- (S(j) S(i)) A(i,j) (LAPACK DLAQSY's order); S an n x 1 image
+template <typename T>
+void launch_laqsy(hipStream_t s, const TileGeo &g, int upper, T *A, const T *S);
+// D <- diag(S) D for the n x ncols image D
+template <typename T>
+void launch_row_scale(hipStream_t s, const TileGeo &gx, T *D, const T *S);
+// V[v nv ...] <- image column d (zero outside the matrix); image column d <- (add: += ) V[v nv ...]
+template <typename T>
+void launch_gather(hipStream_t s, const TileGeo &gx, const T *D, const VecCols &cols, T *V);
+template <typename T>
+void launch_scatter(hipStream_t s, const TileGeo &gx, T *D, const VecCols &cols, const T *V, bool add);
+// V[v] <- W[v] .* V[v] for the slots v = cols.v[j] whose bit j of mask is set
+template <typename T>
+void launch_vec_weight(hipStream_t s, const TileGeo &g, T *V, const T *W, const VecCols &cols, unsigned mask);
+// DPORFS's residual pass for the columns d[j] (at most 8) of X and B: R[v] <- B - A X, F[v] <- the FERR weight
+// |R| + (n+1) eps W (+ safe1 where W <= safe2), W = |B| + |A||X|; berr[v] (zeroed) <- bits of the column's
+// componentwise backward error as a double.  part: porfs_part_elems(ga, refine_width(n)) elements of T.
+size_t porfs_part_elems(const TileGeo &ga, int width);
+template <typename T>
+void launch_porfs_resid(hipStream_t s, const TileGeo &ga, int upper, const T *A, const TileGeo &gx, const T *X,
+                        const T *B, const VecCols &cols, T *part, T *R, T *F, double eps, double safe1, double safe2,
+                        unsigned long long *berr);
+// count <= 8 applications of A^{-1} at once (the NV = refine_width(count) form of launch_sweep): x[j] <- A^{-1} x[j],
+// each block of the factor read once per launch for all vectors; pad: 7 vectors of scratch for the unused places;
+// y, pg, pd: msweep_scratch_elems(g) elements of T in all
+template <typename T>
+struct MSweepBufs {
+  T *y, *pg, *pd;
+};
+size_t msweep_scratch_elems(const TileGeo &g);
+template <typename T>
+void launch_msweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const T *Dv, T *const *x, int count,
+                   T *pad, const MSweepBufs<T> &b);
+
 // out-of-place transposes of `count` mb x mb tiles (mb % 64 == 0)
 template <typename T>
 void launch_tiles_transpose(hipStream_t s, const T *in, long istride, T *out, long ostride, int mb, int count);

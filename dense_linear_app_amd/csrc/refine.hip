@@ -1,0 +1,594 @@
+// The SPD expert solve (api.hip: chol_poequ_tile, chol_laqsy_tile, chol_porfs_tile, chol_posvx_tile; LAPACK DPOEQU,
+// DLAQSY, DPORFS, DPOSVX) on a single-process, device-resident tile image, in the geometry of condest.hip: stored
+// tiles of mbs x mbs elements of which the caller's tile is the leading mbu x mbu part, cut into 128 x 128 blocks of
+// stored rows (sweep_blocks.h); entries outside the matrix are masked before they are loaded.  Every kernel is
+// templated on T: the fp32 path is LAPACK's S-routine, in single precision throughout.
+//
+// The residual of porfs: one workgroup per stored block of the triangle (as mixed.hip's k_sym_resid) reads the block
+// once and forms four products for up to 8 columns: A X and A^T X, |A| |X| and |A|^T |X| (a diagonal block made
+// symmetric from its stored half).  A second pass adds the per-block partials in a fixed order, forms R = B - A X and
+// W = |A||X| + |B|, the componentwise backward error of each column (an order-independent max) and the FERR weight
+// vector |R| + nz eps W, both written as condest-layout vectors (v[128 b + t], zero outside the matrix).
+//
+// The multi-vector sweeps: condest.hip's k_sweep_diag / k_sweep_rect for NV = 1, 2, 4, 8 vectors, each 128 x 128 block
+// of the factor read once per launch for all of them.  Partial sums keep their fixed order: bit-identical runs.
+#include <cfloat>
+
+#include "cholmi_internal.h"
+#include "sweep_blocks.h"
+
+namespace cholmi {
+
+namespace {
+
+// storage index of vector entry (block b, t) of column j of an n x ncols image with the matrix's row tiling
+__device__ __forceinline__ long desc_index(const TileGeo &g, long b, int t, int j) {
+  const int bpt = bpt_of(g);
+  return ((b / bpt) + (long)(j / g.mbu) * g.lmt) * (long)g.mbs * g.mbs + (b % bpt) * CB + t + (long)(j % g.mbu) * g.mbs;
+}
+
+// storage index of global row i of column 0 (the S vector) / of the diagonal entry A(i, i)
+__device__ __forceinline__ long col0_index(const TileGeo &g, long i) {
+  return (i / g.mbu) * (long)g.mbs * g.mbs + i % g.mbu;
+}
+__device__ __forceinline__ long diag_index(const TileGeo &g, long i) {
+  const long t = i / g.mbu, r = i % g.mbu;
+  return t * (g.lmt + 1) * (long)g.mbs * g.mbs + r + r * g.mbs;
+}
+
+template <typename T>
+struct Bits;
+template <>
+struct Bits<double> {
+  __device__ static unsigned long long of(double v) { return (unsigned long long)__double_as_longlong(v); }
+};
+template <>
+struct Bits<float> {
+  __device__ static unsigned long long of(float v) { return (unsigned long long)__double_as_longlong((double)v); }
+};
+
+// IEEE 1/sqrt(d), as LAPACK's ONE / SQRT( D ).  fp32: each step in fp64, then rounded to fp32 -- for sqrt and division
+// that is the correctly rounded fp32 result (53 >= 2 * 24 + 2), which the fp32 device instructions do not guarantee
+__device__ __forceinline__ double inv_sqrt_rn(double d) { return __ddiv_rn(1.0, __dsqrt_rn(d)); }
+__device__ __forceinline__ float inv_sqrt_rn(float d) {
+  const float s = (float)__dsqrt_rn((double)d);
+  return (float)__ddiv_rn(1.0, (double)s);
+}
+
+// ---------------------------------------------------------------- poequ / the range of S
+constexpr int SCAN_WG = 256;
+
+// mode 0: d = A(i,i), S(i) <- 1/sqrt(d) where d > 0; mode 1: d = S(i).  part[wg * 3 + ...] <- min d, max d, the first
+// i with d <= 0 (or -1) of the workgroup's range of rows
+template <typename T>
+__global__ __launch_bounds__(256) void k_diag_scan(TileGeo g, const T *__restrict__ A, T *__restrict__ S, int mode,
+                                                   double *__restrict__ part) {
+  const long n = g.m, per = (n + SCAN_WG - 1) / SCAN_WG, lo = blockIdx.x * per, hi = min(n, lo + per);
+  __shared__ T smin[256], smax[256];
+  __shared__ long sbad[256];
+  T mn = T(INFINITY), mx = T(-INFINITY);
+  long bad = -1;
+  for (long i = lo + threadIdx.x; i < hi; i += 256) {
+    const T d = mode == 0 ? A[diag_index(g, i)] : S[col0_index(g, i)];
+    mn = fmin(mn, d);
+    mx = fmax(mx, d);
+    if (d <= T(0) && bad < 0) bad = i;  // (ascending i per thread: its first)
+    if (mode == 0) S[col0_index(g, i)] = d > T(0) ? inv_sqrt_rn(d) : d;
+  }
+  smin[threadIdx.x] = mn;
+  smax[threadIdx.x] = mx;
+  sbad[threadIdx.x] = bad;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    const int t = threadIdx.x;
+    if (t < o) {
+      smin[t] = fmin(smin[t], smin[t + o]);
+      smax[t] = fmax(smax[t], smax[t + o]);
+      const long b2 = sbad[t + o];
+      if (b2 >= 0 && (sbad[t] < 0 || b2 < sbad[t])) sbad[t] = b2;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    part[blockIdx.x * 3 + 0] = (double)smin[0];
+    part[blockIdx.x * 3 + 1] = (double)smax[0];
+    part[blockIdx.x * 3 + 2] = (double)sbad[0];
+  }
+}
+
+// ---------------------------------------------------------------- laqsy and the row scaling
+// the stored triangle of A <- (S(j) S(i)) A(i,j), LAPACK's order; tile pair blockIdx.y (I >= J: Lower tile (I, J),
+// Upper tile (J, I)); nothing outside the matrix or the triangle is read or written
+template <typename T>
+__global__ __launch_bounds__(256) void k_laqsy(TileGeo g, int upper, T *__restrict__ A, const T *__restrict__ S) {
+  int I, J;
+  pair_of(blockIdx.y, I, J);
+  const int ti = upper ? J : I, tj = upper ? I : J;
+  T *tile = A + ((long)ti + (long)tj * g.lmt) * g.mbs * g.mbs;
+  const long total = (long)g.mbu * g.mbu;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const int rr = (int)(e % g.mbu), cc = (int)(e / g.mbu);
+    const long gr = (long)ti * g.mbu + rr, gc = (long)tj * g.mbu + cc;
+    if (gr >= g.m || gc >= g.m || (upper ? gr > gc : gr < gc)) continue;
+    T *p = tile + rr + (long)cc * g.mbs;
+    *p = (S[col0_index(g, gc)] * S[col0_index(g, gr)]) * *p;
+  }
+}
+
+// D(i, j) <- S(i) D(i, j) over the n x ncols entries
+template <typename T>
+__global__ __launch_bounds__(256) void k_row_scale(TileGeo gx, T *__restrict__ D, const T *__restrict__ S) {
+  const long total = gx.m * gx.n;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const long gi = e % gx.m;
+    const int j = (int)(e / gx.m);
+    const long idx = ((gi / gx.mbu) + (long)(j / gx.mbu) * gx.lmt) * (long)gx.mbs * gx.mbs + gi % gx.mbu +
+                     (long)(j % gx.mbu) * gx.mbs;
+    D[idx] = S[col0_index(gx, gi)] * D[idx];
+  }
+}
+
+// ---------------------------------------------------------------- descriptor columns <-> condest-layout vectors
+// V[cols.v[j] nv + e] <- D(row of e, cols.d[j]), zero outside the matrix
+template <typename T>
+__global__ __launch_bounds__(256) void k_gather(TileGeo gx, const T *__restrict__ D, VecCols cols, T *__restrict__ V,
+                                                long nv) {
+  const int j = blockIdx.y;
+  T *v = V + (long)cols.v[j] * nv;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < nv; e += (long)gridDim.x * 256) {
+    const long b = e / CB;
+    const int t = (int)(e % CB);
+    v[e] = t < block_valid(gx, (int)b) ? D[desc_index(gx, b, t, cols.d[j])] : T(0);
+  }
+}
+
+// D(row of e, cols.d[j]) <- (add: D +) V[cols.v[j] nv + e], inside the matrix only
+template <typename T>
+__global__ __launch_bounds__(256) void k_scatter(TileGeo gx, T *__restrict__ D, VecCols cols, const T *__restrict__ V,
+                                                 long nv, int add) {
+  const int j = blockIdx.y;
+  const T *v = V + (long)cols.v[j] * nv;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < nv; e += (long)gridDim.x * 256) {
+    const long b = e / CB;
+    const int t = (int)(e % CB);
+    if (t >= block_valid(gx, (int)b)) continue;
+    T *p = D + desc_index(gx, b, t, cols.d[j]);
+    *p = add ? *p + v[e] : v[e];
+  }
+}
+
+// V[c] <- W[c] .* V[c] for the columns c = cols.v[j] whose bit j of `mask` is set (DPORFS's diag(W))
+template <typename T>
+__global__ __launch_bounds__(256) void k_vec_weight(T *__restrict__ V, const T *__restrict__ W, VecCols cols,
+                                                    unsigned mask, long nv) {
+  const int j = blockIdx.y;
+  if (!((mask >> j) & 1u)) return;
+  const long off = (long)cols.v[j] * nv;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < nv; e += (long)gridDim.x * 256)
+    V[off + e] = W[off + e] * V[off + e];
+}
+
+// ---------------------------------------------------------------- the wave reduction of N values at once
+// v[0..N) of every lane summed over the 64 lanes, N in {1, 2, 4, 8}: the first log2 N exchange steps halve the values a
+// lane holds (at offset 32 the lanes with bit 5 set keep the upper half and send the lower one, and so on), the rest
+// is a plain butterfly.  log2 N + (6 - log2 N) ... = N - 1 + 6 - log2 N exchanges instead of 6 N.  Returns the total of
+// vector *j in every lane (the lanes that share bits 5 .. 6 - log2 N of their index hold the same one); fixed order.
+template <typename T, int N>
+__device__ __forceinline__ T wave_sum_n(const T (&v)[N], int lane, int *j) {
+  T w[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) w[i] = v[i];
+  int jb = 0, off = 32;
+#pragma unroll
+  for (int cnt = N; cnt > 1; cnt >>= 1, off >>= 1) {
+    const bool hi = (lane & off) != 0;
+#pragma unroll
+    for (int i = 0; i < cnt / 2; ++i) {
+      const T keep = hi ? w[i + cnt / 2] : w[i], send = hi ? w[i] : w[i + cnt / 2];
+      w[i] = keep + __shfl_xor(send, off, 64);
+    }
+    if (hi) jb += cnt / 2;
+  }
+#pragma unroll
+  for (; off > 0; off >>= 1) w[0] += __shfl_xor(w[0], off, 64);
+  *j = jb;
+  return w[0];
+}
+
+// ---------------------------------------------------------------- the residual of porfs
+// part[(((pair * 2 + kind) * 2 + q) * NR + j) * 128 + t]: kind 0 -> rows of block row P, 1 -> rows of block row Q;
+// q 0 -> A X, 1 -> |A| |X|; column cols.d[j]
+template <typename T, int NR>
+__global__ __launch_bounds__(256) void k_porfs_resid(TileGeo ga, int upper, const T *__restrict__ A, TileGeo gx,
+                                                     const T *__restrict__ X, VecCols cols, T *__restrict__ part) {
+  const long pair = blockIdx.x;
+  int P, Q;
+  pair_of(pair, P, Q);
+  const int br = upper ? Q : P, bc = upper ? P : Q;  // the stored block's block row and column
+  const T *S = block_at<T>(ga, A, br, bc);
+  const int vr = block_valid(ga, br), vc = block_valid(ga, bc);
+  const bool diag = P == Q;
+  const int nr = cols.n;
+  __shared__ T sv[NR][CB];         // X rows of the block's columns
+  __shared__ T srow[4][NR][CB];    // per-wave row products (A X, then |A| |X|)
+  __shared__ T scol[2][NR][CB];    // the column products (A^T X, |A|^T |X|)
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = 2 * lane;
+  for (int e = tid; e < NR * CB; e += 256) {
+    const int j = e / CB, c = e % CB;
+    sv[j][c] = (c < vc && j < nr) ? X[desc_index(gx, bc, c, cols.d[j])] : T(0);
+  }
+  T u[2][NR];
+#pragma unroll
+  for (int k = 0; k < 2; ++k)
+#pragma unroll
+    for (int j = 0; j < NR; ++j) u[k][j] = (r + k < vr && j < nr) ? X[desc_index(gx, br, r + k, cols.d[j])] : T(0);
+  __syncthreads();
+  T racc[2][NR], aacc[2][NR];
+#pragma unroll
+  for (int j = 0; j < NR; ++j) racc[0][j] = racc[1][j] = aacc[0][j] = aacc[1][j] = T(0);
+  constexpr int GRP = 64 / NR;  // lanes that end with the same column product
+#pragma unroll 4
+  for (int k = 0; k < 32; ++k) {
+    const int c = w * 32 + k;
+    T t0, t1;
+    // (a diagonal block: only its stored half, which is the lower one for Lower and the upper one for Upper)
+    if (diag && upper) {
+      const T *p = S + (long)c * ga.mbs + r;
+      t0 = (c < vc && r < vr && r <= c) ? p[0] : T(0);
+      t1 = (c < vc && r + 1 < vr && r + 1 <= c) ? p[1] : T(0);
+    } else {
+      load_pair<T>(S, ga.mbs, r, c, vr, vc, diag, t0, t1);
+    }
+    // the row products take the stored half with the diagonal, the column products the strict half
+    const T ca0 = (diag && r == c) ? T(0) : t0, ca1 = (diag && r + 1 == c) ? T(0) : t1;
+    T ps[NR], pa[NR];
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      const T v = sv[j][c];
+      racc[0][j] = fma(t0, v, racc[0][j]);
+      racc[1][j] = fma(t1, v, racc[1][j]);
+      aacc[0][j] = fma(fabs(t0), fabs(v), aacc[0][j]);
+      aacc[1][j] = fma(fabs(t1), fabs(v), aacc[1][j]);
+      ps[j] = fma(ca1, u[1][j], ca0 * u[0][j]);
+      pa[j] = fma(fabs(ca1), fabs(u[1][j]), fabs(ca0) * fabs(u[0][j]));
+    }
+    int js, ja;
+    const T s = wave_sum_n<T, NR>(ps, lane, &js), sa = wave_sum_n<T, NR>(pa, lane, &ja);
+    if (lane % GRP == 0) scol[0][js][c] = s, scol[1][ja][c] = sa;
+  }
+  // Lower: the row products go to the rows of P (kind 0), the column products to those of Q; Upper the other way round
+  const int krow = upper ? 1 : 0, kcol = 1 - krow;
+  for (int q = 0; q < 2; ++q) {
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      srow[w][j][r] = q ? aacc[0][j] : racc[0][j];
+      srow[w][j][r + 1] = q ? aacc[1][j] : racc[1][j];
+    }
+    __syncthreads();
+    T *prow = part + ((pair * 2 + krow) * 2 + q) * NR * CB;
+    for (int e = tid; e < NR * CB; e += 256) {
+      const int j = e / CB, t = e % CB;
+      prow[e] = ((srow[0][j][t] + srow[1][j][t]) + srow[2][j][t]) + srow[3][j][t];
+    }
+    __syncthreads();
+  }
+  T *pcol = part + ((pair * 2 + kcol) * 2) * NR * CB;  // (scol is complete: the loop above ends on a barrier)
+  for (int e = tid; e < NR * CB; e += 256) {
+    pcol[e] = scol[0][e / CB][e % CB];
+    pcol[NR * CB + e] = scol[1][e / CB][e % CB];
+  }
+}
+
+// R = B - A X and W = |B| + |A| |X| per stored row, the partials added in a fixed order (the blocks (P, q), q <= P,
+// of block row P, then (k, P), k >= P); R[v nv + s] <- R, F[v nv + s] <- the FERR weight, berr[v] <- max of the
+// componentwise ratio (bits of a non-negative double: order-independent), v = cols.v[j]
+template <typename T, int NR>
+__global__ __launch_bounds__(256) void k_porfs_reduce(TileGeo ga, TileGeo gx, const T *__restrict__ part, VecCols cols,
+                                                      const T *__restrict__ B, T *__restrict__ R, T *__restrict__ F,
+                                                      long nv, T nzeps, T safe1, T safe2,
+                                                      unsigned long long *berr) {
+  const int NB = ga.lmt * bpt_of(ga);
+  const long s = (long)blockIdx.x * 256 + threadIdx.x;
+  const int j = blockIdx.y;
+  if (s >= (long)NB * CB) return;
+  const int P = (int)(s / CB), t = (int)(s % CB);
+  const long vo = (long)cols.v[j] * nv + s;
+  if (t >= block_valid(ga, P)) {
+    R[vo] = T(0);
+    F[vo] = T(0);
+    return;
+  }
+  T sum = 0, asum = 0;
+  for (int q = 0; q <= P; ++q) {
+    const T *p = part + ((((long)P * (P + 1) / 2 + q) * 2 + 0) * 2) * NR * CB + j * CB + t;
+    sum += p[0];
+    asum += p[NR * CB];
+  }
+  for (int k = P; k < NB; ++k) {
+    const T *p = part + ((((long)k * (k + 1) / 2 + P) * 2 + 1) * 2) * NR * CB + j * CB + t;
+    sum += p[0];
+    asum += p[NR * CB];
+  }
+  const T b = B[desc_index(gx, P, t, cols.d[j])];
+  const T rv = b - sum, wv = fabs(b) + asum, ar = fabs(rv);
+  const T ratio = wv > safe2 ? ar / wv : (ar + safe1) / (wv + safe1);
+  atomicMax(berr + cols.v[j], Bits<T>::of(ratio));
+  R[vo] = rv;
+  F[vo] = wv > safe2 ? ar + nzeps * wv : ar + nzeps * wv + safe1;
+}
+
+// ---------------------------------------------------------------- the multi-vector sweeps
+// out[j][t] = sum_c S(t, c) v[j][c] (TRANS: sum_r S(r, t) v[j][r]) for the 128 x 128 block S (ld) and NV vectors, 256
+// threads; v and out in LDS, red: LDS scratch.  The transposed form reduces its NV column products at once
+// (wave_sum_n).  For NV = 1 the arithmetic of block_product.
+template <typename T, bool TRANS, int NV>
+__device__ __forceinline__ void block_product_nv(const T *S, int ld, int vr, int vc, bool lower, const T (*v)[CB],
+                                                 T (*out)[CB], T (*red)[NV][CB]) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = 2 * lane;
+  if (!TRANS) {
+    T acc0[NV], acc1[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) acc0[j] = acc1[j] = T(0);
+#pragma unroll 8
+    for (int k = 0; k < 32; ++k) {
+      const int c = w * 32 + k;
+      T a0, a1;
+      load_pair<T>(S, ld, r, c, vr, vc, lower, a0, a1);
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        acc0[j] = fma(a0, v[j][c], acc0[j]);
+        acc1[j] = fma(a1, v[j][c], acc1[j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      red[w][j][r] = acc0[j];
+      red[w][j][r + 1] = acc1[j];
+    }
+    __syncthreads();
+    for (int e = tid; e < NV * CB; e += 256) {
+      const int j = e / CB, t = e % CB;
+      out[j][t] = ((red[0][j][t] + red[1][j][t]) + red[2][j][t]) + red[3][j][t];
+    }
+  } else {
+    T u0[NV], u1[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) u0[j] = v[j][r], u1[j] = v[j][r + 1];
+#pragma unroll 4
+    for (int k = 0; k < 32; ++k) {
+      const int c = w * 32 + k;
+      T a0, a1, p[NV];
+      load_pair<T>(S, ld, r, c, vr, vc, lower, a0, a1);
+#pragma unroll
+      for (int j = 0; j < NV; ++j) p[j] = fma(a1, u1[j], a0 * u0[j]);
+      int js;
+      const T s = wave_sum_n<T, NV>(p, lane, &js);
+      if (lane % (64 / NV) == 0) out[js][c] = s;
+    }
+  }
+  __syncthreads();
+}
+
+template <typename T>
+struct Vec8 {
+  T *p[8];
+};
+
+// step k, diagonal part, NV vectors (k_sweep_diag): vector j's pending partials at pg + j pgn, its diag partials at
+// pd + j pdn
+template <typename T, bool FWD, int NV>
+__global__ __launch_bounds__(256) void k_msweep_diag(TileGeo g, const T *__restrict__ Dk, int E, int k, Vec8<T> r,
+                                                     const T *__restrict__ pg, long pgn, T *__restrict__ pd, long pdn) {
+  int P, Q;
+  pair_of(blockIdx.x, P, Q);
+  const int bpt = E / CB;
+  const long kb0 = (long)k * bpt;
+  const int rho = FWD ? P : Q, kap = FWD ? Q : P;
+  __shared__ T sv[NV][CB], so[NV][CB];
+  __shared__ T red[4][NV][CB];
+  for (int e = threadIdx.x; e < NV * CB; e += 256) {
+    const int j = e / CB, t = e % CB;
+    // r - the pending partials of the previous rect launch (condest.hip: pending_sub)
+    T v = r.p[j][(kb0 + kap) * CB + t];
+    if (pg) {
+      T sp = 0;
+      for (int c = 0; c < bpt; ++c) sp += pg[j * pgn + ((kb0 + kap) * bpt + c) * CB + t];
+      v -= sp;
+    }
+    sv[j][t] = v;
+  }
+  __syncthreads();
+  const int vr = block_valid(g, (int)kb0 + P), vc = block_valid(g, (int)kb0 + Q);
+  block_product_nv<T, !FWD, NV>(Dk + (long)P * CB + (long)Q * CB * E, E, vr, vc, P == Q, sv, so, red);
+  for (int e = threadIdx.x; e < NV * CB; e += 256) {
+    const int j = e / CB, t = e % CB;
+    pd[j * pdn + ((long)rho * bpt + kap) * CB + t] = so[j][t];
+  }
+}
+
+// step k, the blocks below (forward) / above (backward) tile k, NV vectors (k_sweep_rect)
+template <typename T, bool FWD, int NV>
+__global__ __launch_bounds__(256) void k_msweep_rect(TileGeo g, int upper, const T *__restrict__ A, int k, int row0,
+                                                     int nrows, Vec8<T> r, const T *__restrict__ pg_prev,
+                                                     T *__restrict__ pg, long pgn, const T *__restrict__ pd, long pdn,
+                                                     Vec8<T> yout) {
+  const int bpt = bpt_of(g), i = blockIdx.x / bpt, kap = blockIdx.x % bpt;
+  const long kb0 = (long)k * bpt, rho = row0 + i;
+  __shared__ T sv[NV][CB], so[NV][CB];
+  __shared__ T red[4][NV][CB];
+  for (int e = threadIdx.x; e < NV * CB; e += 256) {
+    const int j = e / CB, t = e % CB;
+    T y = 0;
+    for (int c = FWD ? 0 : kap; c <= (FWD ? kap : bpt - 1); ++c) y += pd[j * pdn + ((long)kap * bpt + c) * CB + t];
+    sv[j][t] = y;
+    if (i == 0) yout.p[j][(kb0 + kap) * CB + t] = y;
+    if (nrows > 0 && kap == 0 && pg_prev) {
+      T s = 0;
+      for (int c = 0; c < bpt; ++c) s += pg_prev[j * pgn + (rho * bpt + c) * CB + t];
+      r.p[j][rho * CB + t] -= s;
+    }
+  }
+  if (nrows == 0) return;
+  __syncthreads();
+  const int kg = (int)(kb0 + kap);
+  const bool trans = FWD ? upper : !upper;
+  const int sr = trans ? kg : (int)rho, sc = trans ? (int)rho : kg;
+  const T *S = block_at<T>(g, A, sr, sc);
+  const int vr = block_valid(g, sr), vc = block_valid(g, sc);
+  if (trans)
+    block_product_nv<T, true, NV>(S, g.mbs, vr, vc, false, sv, so, red);
+  else
+    block_product_nv<T, false, NV>(S, g.mbs, vr, vc, false, sv, so, red);
+  for (int e = threadIdx.x; e < NV * CB; e += 256) {
+    const int j = e / CB, t = e % CB;
+    pg[j * pgn + (rho * bpt + kap) * CB + t] = so[j][t];
+  }
+}
+
+template <typename T, int NV>
+void msweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const T *Dv, const Vec8<T> &x, const MSweepBufs<T> &b) {
+  const int E = condest_edge(g), bpt = E / CB, nt = g.lmt, NB = nt * bpt;
+  const unsigned dwg = (unsigned)(bpt * (bpt + 1) / 2);
+  const long nv = (long)condest_vec_elems(g), pgs = (long)NB * bpt * CB, pgn = 2 * pgs, pdn = (long)bpt * bpt * CB;
+  Vec8<T> y{};
+  for (int j = 0; j < NV; ++j) y.p[j] = b.y + j * nv;
+  for (int pass = 0; pass < 2; ++pass) {
+    const bool fwd = pass == 0;
+    const Vec8<T> r = fwd ? x : y, out = fwd ? y : x;  // forward: b = x -> y; backward: y -> x (r: in place)
+    const T *pg_prev = nullptr;
+    for (int step = 0; step < nt; ++step) {
+      const int k = fwd ? step : nt - 1 - step;
+      T *pg = b.pg + (step % 2) * pgs;
+      const T *Dk = Dv + (long)k * E * E;
+      if (fwd)
+        hipLaunchKernelGGL((k_msweep_diag<T, true, NV>), dim3(dwg), dim3(256), 0, s, g, Dk, E, k, r, pg_prev, pgn, b.pd,
+                           pdn);
+      else
+        hipLaunchKernelGGL((k_msweep_diag<T, false, NV>), dim3(dwg), dim3(256), 0, s, g, Dk, E, k, r, pg_prev, pgn, b.pd,
+                           pdn);
+      const int row0 = fwd ? (k + 1) * bpt : 0, nrows = fwd ? NB - (k + 1) * bpt : k * bpt;
+      const unsigned rwg = (unsigned)(std::max(nrows, 1) * bpt);
+      if (fwd)
+        hipLaunchKernelGGL((k_msweep_rect<T, true, NV>), dim3(rwg), dim3(256), 0, s, g, upper, A, k, row0, nrows, r,
+                           pg_prev, pg, pgn, b.pd, pdn, out);
+      else
+        hipLaunchKernelGGL((k_msweep_rect<T, false, NV>), dim3(rwg), dim3(256), 0, s, g, upper, A, k, row0, nrows, r,
+                           pg_prev, pg, pgn, b.pd, pdn, out);
+      pg_prev = pg;
+    }
+  }
+}
+
+template <typename T, int NR>
+void porfs_pass(hipStream_t s, const TileGeo &ga, int upper, const T *A, const TileGeo &gx, const T *X, const T *B,
+                const VecCols &cols, T *part, T *R, T *F, double eps, double safe1, double safe2,
+                unsigned long long *berr) {
+  const long NB = (long)condest_edge(ga) / CB * ga.lmt, pairs = NB * (NB + 1) / 2;
+  const long nv = (long)condest_vec_elems(ga);
+  if (!pairs) return;
+  hipLaunchKernelGGL((k_porfs_resid<T, NR>), dim3((unsigned)pairs), dim3(256), 0, s, ga, upper, A, gx, X, cols, part);
+  const T nz = T(ga.m + 1);
+  hipLaunchKernelGGL((k_porfs_reduce<T, NR>), dim3((unsigned)((NB * CB + 255) / 256), (unsigned)cols.n), dim3(256), 0, s,
+                     ga, gx, part, cols, B, R, F, nv, T(nz * T(eps)), T(safe1), T(safe2), berr);
+}
+
+unsigned grid_over(long total) { return (unsigned)std::max(1L, std::min((total + 255) / 256, 4096L)); }
+
+}  // namespace
+
+// ---------------------------------------------------------------- launchers
+int refine_width(int k) { return k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 ? 4 : 8; }
+
+size_t porfs_part_elems(const TileGeo &ga, int width) {
+  const long NB = (long)ga.lmt * (condest_edge(ga) / CB);
+  return (size_t)(NB * (NB + 1) / 2) * 4 * CB * width;
+}
+
+size_t diag_scan_part_bytes() { return (size_t)SCAN_WG * 3 * sizeof(double); }
+
+template <typename T>
+void launch_diag_scan(hipStream_t s, const TileGeo &g, const T *A, T *S, int mode, double *part) {
+  hipLaunchKernelGGL(k_diag_scan<T>, dim3(SCAN_WG), dim3(256), 0, s, g, A, S, mode, part);
+}
+
+template <typename T>
+void launch_laqsy(hipStream_t s, const TileGeo &g, int upper, T *A, const T *S) {
+  const long nt = g.lmt, pairs = nt * (nt + 1) / 2;
+  if (!pairs) return;
+  const unsigned gx = grid_over((long)g.mbu * g.mbu) > 64 ? 64 : grid_over((long)g.mbu * g.mbu);
+  hipLaunchKernelGGL(k_laqsy<T>, dim3(gx, (unsigned)pairs), dim3(256), 0, s, g, upper, A, S);
+}
+
+template <typename T>
+void launch_row_scale(hipStream_t s, const TileGeo &gx, T *D, const T *S) {
+  if (gx.m * gx.n > 0) hipLaunchKernelGGL(k_row_scale<T>, dim3(grid_over(gx.m * gx.n)), dim3(256), 0, s, gx, D, S);
+}
+
+template <typename T>
+void launch_gather(hipStream_t s, const TileGeo &gx, const T *D, const VecCols &cols, T *V) {
+  const long nv = (long)condest_vec_elems(gx);
+  if (cols.n > 0) hipLaunchKernelGGL(k_gather<T>, dim3(grid_over(nv), (unsigned)cols.n), dim3(256), 0, s, gx, D, cols, V, nv);
+}
+
+template <typename T>
+void launch_scatter(hipStream_t s, const TileGeo &gx, T *D, const VecCols &cols, const T *V, bool add) {
+  const long nv = (long)condest_vec_elems(gx);
+  if (cols.n > 0)
+    hipLaunchKernelGGL(k_scatter<T>, dim3(grid_over(nv), (unsigned)cols.n), dim3(256), 0, s, gx, D, cols, V, nv, add ? 1 : 0);
+}
+
+template <typename T>
+void launch_vec_weight(hipStream_t s, const TileGeo &g, T *V, const T *W, const VecCols &cols, unsigned mask) {
+  const long nv = (long)condest_vec_elems(g);
+  if (cols.n > 0 && mask)
+    hipLaunchKernelGGL(k_vec_weight<T>, dim3(grid_over(nv), (unsigned)cols.n), dim3(256), 0, s, V, W, cols, mask, nv);
+}
+
+template <typename T>
+void launch_porfs_resid(hipStream_t s, const TileGeo &ga, int upper, const T *A, const TileGeo &gx, const T *X,
+                        const T *B, const VecCols &cols, T *part, T *R, T *F, double eps, double safe1, double safe2,
+                        unsigned long long *berr) {
+  switch (refine_width(cols.n)) {
+    case 1: porfs_pass<T, 1>(s, ga, upper, A, gx, X, B, cols, part, R, F, eps, safe1, safe2, berr); break;
+    case 2: porfs_pass<T, 2>(s, ga, upper, A, gx, X, B, cols, part, R, F, eps, safe1, safe2, berr); break;
+    case 4: porfs_pass<T, 4>(s, ga, upper, A, gx, X, B, cols, part, R, F, eps, safe1, safe2, berr); break;
+    default: porfs_pass<T, 8>(s, ga, upper, A, gx, X, B, cols, part, R, F, eps, safe1, safe2, berr); break;
+  }
+}
+
+size_t msweep_scratch_elems(const TileGeo &g) {
+  const long bpt = (condest_edge(g) / CB), NB = (long)g.lmt * bpt, nv = (long)condest_vec_elems(g);
+  return (size_t)8 * (nv + 2 * NB * bpt * CB + bpt * bpt * CB);
+}
+
+template <typename T>
+void launch_msweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const T *Dv, T *const *x, int count,
+                   T *pad, const MSweepBufs<T> &b) {
+  const long nv = (long)condest_vec_elems(g);
+  Vec8<T> v{};
+  const int w = refine_width(count);
+  for (int j = 0; j < w; ++j) v.p[j] = j < count ? x[j] : pad + (long)(j - count) * nv;  // (padding: results unused)
+  switch (w) {
+    case 1: msweep<T, 1>(s, g, upper, A, Dv, v, b); break;
+    case 2: msweep<T, 2>(s, g, upper, A, Dv, v, b); break;
+    case 4: msweep<T, 4>(s, g, upper, A, Dv, v, b); break;
+    default: msweep<T, 8>(s, g, upper, A, Dv, v, b); break;
+  }
+}
+
+#define INSTANTIATE_REFINE(T)                                                                                        \
+  template void launch_diag_scan<T>(hipStream_t, const TileGeo &, const T *, T *, int, double *);                    \
+  template void launch_laqsy<T>(hipStream_t, const TileGeo &, int, T *, const T *);                                  \
+  template void launch_row_scale<T>(hipStream_t, const TileGeo &, T *, const T *);                                   \
+  template void launch_gather<T>(hipStream_t, const TileGeo &, const T *, const VecCols &, T *);                     \
+  template void launch_scatter<T>(hipStream_t, const TileGeo &, T *, const VecCols &, const T *, bool);              \
+  template void launch_vec_weight<T>(hipStream_t, const TileGeo &, T *, const T *, const VecCols &, unsigned);       \
+  template void launch_porfs_resid<T>(hipStream_t, const TileGeo &, int, const T *, const TileGeo &, const T *,      \
+                                      const T *, const VecCols &, T *, T *, T *, double, double, double,            \
+                                      unsigned long long *);                                                         \
+  template void launch_msweep<T>(hipStream_t, const TileGeo &, int, const T *, const T *, T *const *, int, T *,      \
+                                 const MSweepBufs<T> &);
+INSTANTIATE_REFINE(double)
+INSTANTIATE_REFINE(float)
+
+}  // namespace cholmi

@@ -256,6 +256,48 @@ int chol_pocon_tile(int uplo, chol_desc_t *A, double anorm, double *rcond);
 /* The last chol_pocon_tile: total ms, sweep ms (the applications alone), the number of applications, 0. */
 int chol_last_pocon_stats(double *out4);
 
+/* The SPD expert solve with error bounds (LAPACK DPOEQU, DLAQSY, DPORFS, DPOSVX), on device-resident single-process
+ * descriptors with the rules of chol_pocon_tile (A square, stored tile edge a multiple of 64, views allowed; a p x q
+ * block-cyclic descriptor returns CHOL_ERR_NOT_SUPPORTED).  fp64 or fp32 by A's dtype (fp32 follows LAPACK's
+ * S-routines, in single precision throughout).  Only the `uplo` triangle of A and AF is read or written; the other
+ * strict triangle comes back bit for bit as it was.  S is an n x 1 descriptor, B and X n x nrhs ones, all with A's
+ * dtype and tile size.  No floating-point atomics and fixed summation orders: repeated calls give the same bits.
+ * Argument errors return the negative position of the argument. */
+enum {
+  CHOL_FACT_NONE = 0,        /* 'N': factor A (a copy in AF)                            */
+  CHOL_FACT_EQUILIBRATE = 1, /* 'E': equilibrate A if that helps, then factor it        */
+  CHOL_FACT_FACTORED = 2     /* 'F': AF holds the factor; *equed and S are inputs      */
+};
+/* LAPACK DPOEQU: S <- 1/sqrt(A(i,i)) (IEEE, as LAPACK), *scond = sqrt(min A(i,i)) / sqrt(max A(i,i)),
+ * *amax = max A(i,i).  Reads the diagonal only.  Returns info = i > 0 for the first A(i,i) <= 0 (S then unspecified). */
+int chol_poequ_tile(chol_desc_t *A, chol_desc_t *S, double *scond, double *amax);
+/* LAPACK DLAQSY: if scond < 0.1 or amax outside [small, large] (small = safmin / prec, large = 1 / small), the `uplo`
+ * triangle of A <- (S(j) * S(i)) * A(i,j) in place and *equed = 1 ('Y'); else A untouched and *equed = 0 ('N'). */
+int chol_laqsy_tile(int uplo, chol_desc_t *A, chol_desc_t *S, double scond, double amax, int *equed);
+/* LAPACK DPORFS: A the matrix, AF its factor (chol_potrf_tile(uplo, .)), B the right-hand sides, X the solution,
+ * refined in place (at most 5 steps per column; a column stops when berr <= eps or berr no longer halves).
+ * ferr[nrhs] <- forward error bounds (DLACN2 on diag(W) A^-1, W = |R| + (n+1) eps (|A||X| + |B|)), berr[nrhs] <-
+ * componentwise backward errors; host arrays.  A sweep that overflows (no DLATRS scaling) gives ferr = +Inf. */
+int chol_porfs_tile(int uplo, chol_desc_t *A, chol_desc_t *AF, chol_desc_t *B, chol_desc_t *X, double *ferr,
+                    double *berr);
+/* LAPACK DPOSVX: equilibrate (CHOL_FACT_EQUILIBRATE), factor A into AF (NONE / EQUILIBRATE), rcond from lansy(One)
+ * of the equilibrated A and pocon, X <- A^-1 B, porfs, then X <- diag(S) X and ferr /= scond when *equed = 1.  With
+ * *equed = 1, A comes back equilibrated and B as diag(S) B.  CHOL_FACT_FACTORED takes A as already equilibrated, AF as
+ * its factor and *equed / S as inputs (scond from S as DPOSVX: max(smin, safmin) / min(smax, 1 / safmin)); S may be
+ * NULL when it is not used.  Returns 0; i in 1..n: the leading minor of order i is not positive definite (rcond = 0,
+ * X, ferr, berr untouched); n + 1: rcond < eps (X, ferr and berr still computed).  Argument errors: -1 fact, -2 uplo,
+ * -3 A, -4 AF, -5 equed, -6 S, -7 B, -8 X (or X aliasing A, AF or B), -9 rcond, -10 ferr, -11 berr NULL. */
+int chol_posvx_tile(int fact, int uplo, chol_desc_t *A, chol_desc_t *AF, int *equed, chol_desc_t *S,
+                    chol_desc_t *B, chol_desc_t *X, double *rcond, double *ferr, double *berr);
+/* The last chol_posvx_tile / chol_porfs_tile: [0] total ms, [1] equilibration and the scaling of B, [2] lacpy + potrf,
+ * [3] lansy + pocon, [4] the solve, [5] porfs (ms); [6] columns to which A^-1 was applied by the multi-vector sweeps,
+ * [7] columns to which it was applied by potrs.  Phases a call did not run are 0. */
+int chol_last_posvx_stats(double *out8);
+/* The parts of chol_porfs_tile alone (scripts/posvx_time.py), on X's columns: path 0 the residual pass (B = X), 1 one
+ * application of A^-1 by the multi-vector sweeps (groups of up to 8), 2 the same by potrs on an n x nrhs image.
+ * AF holds the factor of A; X is only read.  *ms <- the fastest of `reps` calls after a warm-up one. */
+int chol_bench_refine(int uplo, chol_desc_t *A, chol_desc_t *AF, chol_desc_t *X, int path, int reps, double *ms);
+
 /* CHAMELEON_Lapack_to_Tile / Tile_to_Lapack equivalents (host LAPACK layout
  * <-> descriptor storage); single-process descriptors only. */
 int chol_lapack_to_tile(const void *A, int lda, chol_desc_t *desc);

@@ -1,0 +1,55 @@
+"""CPU-side checks of the SPD expert solve (chol_poequ_tile / chol_laqsy_tile / chol_porfs_tile / chol_posvx_tile /
+chol_last_posvx_stats): the Python wrappers and ABI symbols exist, every entry point refuses to run before chol_init,
+and LAPACK's FACT / EQUED characters map to the ABI's codes.  The numerics are in test_gpu_posvx.py."""
+import ctypes as C
+
+import pytest
+
+from dense_linear_app_amd import _lib, chameleon as ch
+
+SYMBOLS = ["chol_poequ_tile", "chol_laqsy_tile", "chol_porfs_tile", "chol_posvx_tile", "chol_last_posvx_stats"]
+
+
+def test_wrappers_exist():
+    for name in ("poequ", "laqsy", "porfs", "posvx"):
+        for p in "ds":
+            assert callable(getattr(ch, f"CHAMELEON_{p}{name}_Tile"))
+    assert callable(ch.last_posvx_stats)
+    for s in SYMBOLS:
+        assert s in _lib.abi_symbols()
+
+
+@pytest.mark.parametrize("sym", SYMBOLS)
+def test_before_init_is_refused(sym):
+    L = _lib.lib()
+    d = C.c_double()
+    e = C.c_int(0)
+    args = {"chol_poequ_tile": (None, None, C.byref(d), C.byref(d)),
+            "chol_laqsy_tile": (ch.ChamLower, None, None, 1.0, 1.0, C.byref(e)),
+            "chol_porfs_tile": (ch.ChamLower, None, None, None, None, C.byref(d), C.byref(d)),
+            "chol_posvx_tile": (0, ch.ChamLower, None, None, C.byref(e), None, None, None, C.byref(d), C.byref(d),
+                                C.byref(d)),
+            "chol_last_posvx_stats": ((C.c_double * 8)(),)}[sym]
+    assert getattr(L, sym)(*args) == -101  # CHOL_ERR_NOT_INITIALIZED
+    assert b"before chol_init" in L.chol_last_error()
+
+
+def test_fact_and_equed_characters():
+    assert [ch.fact_code(c) for c in "NEF"] == [0, 1, 2]  # CHOL_FACT_NONE, _EQUILIBRATE, _FACTORED
+    assert [ch.fact_code(c) for c in "nef"] == [0, 1, 2]
+    assert [ch.equed_code(c) for c in "NYny"] == [0, 1, 0, 1]
+    assert [ch.equed_char(i) for i in (0, 1)] == ["N", "Y"]
+    for bad in ("X", "", "NE"):
+        with pytest.raises(ValueError):
+            ch.fact_code(bad)
+    with pytest.raises(ValueError):
+        ch.equed_code("E")
+
+
+def test_header_codes_match():
+    import os
+    import re
+
+    hdr = open(os.path.join(os.path.dirname(_lib.__file__), "..", "include", "cholmi.h")).read()
+    codes = dict((k, int(v)) for k, v in re.findall(r"CHOL_FACT_(\w+)\s*=\s*(\d+)", hdr))
+    assert codes == {"NONE": ch.fact_code("N"), "EQUILIBRATE": ch.fact_code("E"), "FACTORED": ch.fact_code("F")}
