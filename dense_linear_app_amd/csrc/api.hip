@@ -2,7 +2,9 @@
 // descriptors, the synchronous tile operations the reference worker calls
 // (worker_distrib.cpp:238, 323, 416, 511) and the whole-matrix tiled POTRF the
 // reference driver calls (v6_test.c:56), run as the reference client's wave DAG
-// (client_distrib.cpp:506-565) on two HIP streams with one wave of lookahead.
+// (client_distrib.cpp:506-565) on two HIP streams with one wave of lookahead.  The routines that work from a factor
+// (potrs, dsposv, the inverse, the condition estimate, the expert solve) are in spd.hip, on what api_internal.h
+// exports from here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +20,7 @@
 #include <vector>
 
 #include "../../include/cholmi.h"
+#include "api_internal.h"
 #include "cholmi_internal.h"
 
 using namespace cholmi;
@@ -38,10 +41,8 @@ struct Ctx {
   RankCtx r;              // streams, workspaces, counters, events of this process's rank
   int *d_ytab = nullptr;  // per-CU yield requests (kernels.hip: cooperative CU hand-over); one per device
   double *d_acc = nullptr;
-  void *stage[3] = {nullptr, nullptr, nullptr};
-  size_t stage_bytes[3] = {0, 0, 0};
-  void *work = nullptr;   // reusable scratch of lange / potrs / tile batches (grown on demand)
-  size_t work_bytes = 0;
+  ScratchPool<3> stage;   // the staged tiles of the single-tile operations
+  ScratchPool<1> work;    // lange's partial sums
   // block inverses of the last single tile factored or inverted under a version tag (chol_desc_set_version):
   // the TRSM tasks of a wave all use the L(k,k) the POTRF task before them produced
   const void *wc_ptr = nullptr;
@@ -50,29 +51,6 @@ struct Ctx {
   void *wc_winv = nullptr;
   int *d_binfo = nullptr;  // device info words of asynchronously factored tiles (chol_potrf_batch), a ring
   unsigned binfo_next = 0;
-  // chol_dsposv_tile's scratch, grown on demand and kept (not g.work: potrs_impl and lange grow and reuse that one):
-  // the fp32 factor (n x n tile image), the fp32 right-hand side / correction (n x nrhs), the residual's per-block
-  // partial sums, and the column maxima + overflow flag
-  void *mx[4] = {nullptr, nullptr, nullptr, nullptr};
-  size_t mx_bytes[4] = {0, 0, 0, 0};
-  double mx_stats[8] = {};  // of the last chol_dsposv_tile (chol_last_dsposv_stats)
-  // chol_trtri_tile / chol_potri_tile's scratch, grown on demand and kept (not g.work either): the products' Y blocks
-  // (then potri's LAUUM image), the 128 x 128 inverses of every diagonal tile's diagonal blocks, a staged copy of a
-  // single tile whose edge is not a multiple of 128, and the zero-pivot word
-  void *iv[4] = {nullptr, nullptr, nullptr, nullptr};
-  size_t iv_bytes[4] = {0, 0, 0, 0};
-  // chol_lansy_tile / chol_pocon_tile's scratch, grown on demand and kept (not g.work either): the staged and
-  // inverted diagonal tiles, the 128 x 128 inverses of their diagonal blocks, the products' Y blocks, the sweeps'
-  // vectors and partials, the sign vector, the statistics, lansy's per-block partials
-  void *cn[7] = {};
-  size_t cn_bytes[7] = {};
-  double cn_stats[4] = {};  // of the last chol_pocon_tile (chol_last_pocon_stats)
-  // chol_porfs_tile / chol_posvx_tile's scratch, grown on demand and kept (not g.work either): one condest-layout
-  // vector per column for the residuals / estimator, the FERR weights and the signs, the residual partials, the
-  // sweeps' scratch, the backward errors and statistics, potrs's n x k image, poequ's partials
-  void *rf[8] = {};
-  size_t rf_bytes[8] = {};
-  double rf_stats[8] = {};  // of the last chol_posvx_tile / chol_porfs_tile (chol_last_posvx_stats)
   std::string last_error;
 };
 
@@ -162,84 +140,10 @@ void set_error(const char *msg) {
   std::lock_guard<std::mutex> lk(g_err_mu);
   g.last_error = msg;
 }
-int fail_hip(hipError_t e, const char *what, int line) {
-  char buf[256];
-  snprintf(buf, sizeof buf, "%s failed at api.hip:%d: %s", what, line, hipGetErrorString(e));
-  set_error(buf);
-  return CHOL_ERR_HIP;
-}
-#define HIPCHECK(call)                                        \
-  do {                                                        \
-    hipError_t e_ = (call);                                   \
-    if (e_ != hipSuccess) return fail_hip(e_, #call, __LINE__); \
-  } while (0)
-
-int fail(int code, const char *msg) {
-  set_error(msg);
-  return code;
-}
-
-inline int roundup(int x, int m) { return (x + m - 1) / m * m; }
-
 // counters for one single-tile POTRF (launch_potrf_tile): a set of 32, rotating so that consecutive
 // factorisations on different streams never share one
 int *tile_sems() {
   return g.r.d_sem ? g.r.d_sem + (size_t)(SEM_SLOTS + 32 * (g.r.tile_sem_next++ % TILE_SEM_SETS)) * 32 : nullptr;
-}
-
-int ensure_stage(int idx, size_t bytes) {
-  if (g.stage_bytes[idx] >= bytes) return 0;
-  if (g.stage[idx]) HIPCHECK(hipFree(g.stage[idx]));
-  g.stage[idx] = nullptr;
-  g.stage_bytes[idx] = 0;
-  HIPCHECK(hipMalloc(&g.stage[idx], bytes));
-  g.stage_bytes[idx] = bytes;
-  return 0;
-}
-
-int ensure_mx(int idx, size_t bytes) {
-  if (g.mx_bytes[idx] >= bytes) return 0;
-  if (g.mx[idx]) HIPCHECK(hipFree(g.mx[idx]));
-  g.mx[idx] = nullptr;
-  g.mx_bytes[idx] = 0;
-  bytes = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-  HIPCHECK(hipMalloc(&g.mx[idx], bytes));
-  HIPCHECK(hipMemset(g.mx[idx], 0, bytes));
-  g.mx_bytes[idx] = bytes;
-  return 0;
-}
-
-int ensure_iv(int idx, size_t bytes) {
-  if (g.iv_bytes[idx] >= bytes) return 0;
-  if (g.iv[idx]) HIPCHECK(hipFree(g.iv[idx]));
-  g.iv[idx] = nullptr;
-  g.iv_bytes[idx] = 0;
-  bytes = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-  HIPCHECK(hipMalloc(&g.iv[idx], bytes));
-  g.iv_bytes[idx] = bytes;
-  return 0;
-}
-
-int ensure_cn(int idx, size_t bytes) {
-  if (g.cn_bytes[idx] >= bytes) return 0;
-  if (g.cn[idx]) HIPCHECK(hipFree(g.cn[idx]));
-  g.cn[idx] = nullptr;
-  g.cn_bytes[idx] = 0;
-  bytes = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-  HIPCHECK(hipMalloc(&g.cn[idx], bytes));
-  g.cn_bytes[idx] = bytes;
-  return 0;
-}
-
-int ensure_work(size_t bytes) {
-  if (g.work_bytes >= bytes) return 0;
-  if (g.work) HIPCHECK(hipFree(g.work));
-  g.work = nullptr;
-  g.work_bytes = 0;
-  bytes = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-  HIPCHECK(hipMalloc(&g.work, bytes));
-  g.work_bytes = bytes;
-  return 0;
 }
 
 // the cached block inverses for (tile pointer, version), or null
@@ -257,9 +161,6 @@ int remember_winv(const void *ptr, unsigned long long version, int mb, int dtype
   g.wc_mb = mb;
   g.wc_dtype = dtype;
   return 0;
-}
-void forget_winv(const void *ptr) {
-  if (g.wc_ptr == ptr) g.wc_ptr = nullptr, g.wc_version = 0;
 }
 
 // ---- the task executor (TaskExec above) ------------------------------------------------------------------------
@@ -453,14 +354,6 @@ T *local_tile(const chol_desc *d, void *base, int I, int J) {
   return reinterpret_cast<T *>(base) + ((long)(I / d->p) + (long)(J / d->q) * d->lmt) * (long)d->bsizi;
 }
 
-// the context holds the inverses of at most 32 diagonal 128-blocks (tiles up to 4096): every entry
-// that factors, inverts or solves with a tile checks this before any launch writes winv
-bool winv_fits(const chol_desc *d) {
-  return (size_t)(roundup(d->mbi, MACRO) / MACRO) * MACRO * MACRO * d->esize <= g.r.winv_bytes;
-}
-#define CHECK_WINV(d, what) \
-  if (!winv_fits(d)) return fail(CHOL_ERR_NOT_SUPPORTED, what ": tile size above 4096")
-
 bool single_tile_square(const chol_desc *d) {
   return d->mt == 1 && d->nt == 1 && d->m == d->n && d->mb == d->nb && d->m == d->mb &&
          d->p == 1 && d->q == 1 && d->i == 0 && d->j == 0;
@@ -483,9 +376,9 @@ int stage_in(const chol_desc *d, int slot, bool identity_pad, Staged *out) {
     return 0;
   }
   const size_t bytes = (size_t)Bp * Bp * sizeof(T);
-  int rc = ensure_stage(slot, bytes);
+  int rc = g.stage.ensure_bytes(slot, bytes, "tile staging");
   if (rc) return rc;
-  T *dst = reinterpret_cast<T *>(g.stage[slot]);
+  T *dst = g.stage.as<T>(slot);
   if (B != Bp) HIPCHECK(hipMemsetAsync(dst, 0, bytes, g.r.st[ST_MAIN]));
   HIPCHECK(hipMemcpy2DAsync(dst, (size_t)Bp * sizeof(T), d->mat, (size_t)B * sizeof(T),
                             (size_t)B * sizeof(T), B, hipMemcpyDefault, g.r.st[ST_MAIN]));
@@ -550,32 +443,6 @@ int view_sync(chol_desc *d, bool in) {
     }
   return 0;
 }
-// One entry point's body between the refresh of its views' images and their write-back, all under the context
-// lock (recursive: the bodies take it again); a failed refresh returns before the body runs, a failed write-back
-// is reported unless the body already failed.  The write-back also follows a body that returned info > 0
-// (a partly factored matrix, as LAPACK leaves it).
-struct ViewArg {
-  chol_desc *d;
-  bool write_back;
-};
-template <typename F>
-static int with_views(std::initializer_list<ViewArg> views, F &&body) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  if (int rc = tx_quiesce()) return rc;  // (the synchronous calls run on ST_MAIN alone: nothing of the task executor may be in flight)
-  for (const ViewArg &v : views)
-    if (v.d && v.d->user_mat) {
-      const int rc = view_sync(v.d, true);
-      if (rc) return rc;
-    }
-  int rc = body();
-  for (const ViewArg &v : views)
-    if (v.d && v.d->user_mat && v.write_back) {
-      const int r2 = view_sync(v.d, false);
-      if (r2 && rc >= 0) rc = r2;
-    }
-  return rc;
-}
-
 int build_worklist(chol_desc *d) {
   if (d->mt != d->nt) return 0;  // only square tile grids are factored
   std::vector<int2> off, dg;
@@ -644,7 +511,7 @@ static int potrf_impl(chol_desc *A, bool upper_staged = false) {
     if (rc >= 0) e = hipMemcpy(A->mat, dev, bytes, hipMemcpyDeviceToHost);
   }
   (void)hipFree(dev);
-  if (e != hipSuccess) return fail_hip(e, "staged potrf copy", __LINE__);
+  if (e != hipSuccess) return fail_hip(e, "staged potrf copy", __FILE__, __LINE__);
   return rc;
 }
 
@@ -696,61 +563,6 @@ static int gemm_impl(double alpha, chol_desc *A, chol_desc *B, double beta, chol
   rc = stage_out<T>(C, sc);
   if (rc) return rc;
   HIPCHECK(hipStreamSynchronize(g.r.st[ST_MAIN]));
-  return 0;
-}
-
-// ---------------------------------------------------------------- solve with the factor
-// X <- A^{-1} B for A = L L^T already factored (CHAMELEON_dpotrs_Tile(ChamLower, A, B)).
-// The kernels of this library are the right-sided NT forms the factorisation needs
-// (X = A L^{-T}, C -= A B^T), so the solve runs on Z = B^T:
-//   forward   Z(:,k) <- Z(:,k) L(k,k)^{-T};  Z(:,i) -= Z(:,k) L(i,k)^T, i > k      (L Y = B)
-//   backward  Z(:,k) <- Z(:,k) L(k,k)^{-1};  Z(:,i) -= Z(:,k) L(k,i),   i < k      (L^T X = Y)
-// the backward sweep's operands being transposed tiles (L(k,k)^{-T} from a TRSM of the identity,
-// L(k,i)^T from a tile transpose) so that every product is again A B^T.
-template <typename T>
-int potrs_impl(chol_desc *A, chol_desc *B) {
-  const int nt = A->nt, nr = B->nt, mb = A->mbi;
-  const long bs = A->bsizi;
-  const size_t tb = (size_t)bs * sizeof(T);
-  T *La = reinterpret_cast<T *>(A->mat), *Bm = reinterpret_cast<T *>(B->mat);
-  if (ensure_work(((size_t)nr * nt + 2 + (size_t)nr + (size_t)nt) * tb)) {
-    (void)hipGetLastError();
-    return fail(CHOL_ERR_OUT_OF_MEMORY, "potrs_tile: scratch allocation failed");
-  }
-  T *scr = reinterpret_cast<T *>(g.work);
-  T *Z = scr, *Wt = scr + (size_t)nr * nt * bs, *Tt = Wt + bs, *tmp = Tt + (size_t)nt * bs;  // Tt: nt tiles, tmp: nr tiles
-  hipStream_t s = g.r.st[ST_MAIN];
-  T *winv = reinterpret_cast<T *>(g.r.winv);
-  auto Ltile = [&](int i, int j) { return La + ((long)i + (long)j * A->lmt) * bs; };
-  auto Ztile = [&](int r, int i) { return Z + ((long)r + (long)i * nr) * bs; };
-  // Z(r,i) = B(i,r)^T
-  for (int r = 0; r < nr; ++r)
-    launch_tiles_transpose<T>(s, Bm + (long)r * B->lmt * bs, bs, Ztile(r, 0), (long)nr * bs, mb, nt);
-  for (int k = 0; k < nt; ++k) {  // forward
-    launch_invert_diag<T>(s, Ltile(k, k), mb, winv);
-    launch_trsm_panel<T>(s, Ztile(0, k), bs, nr, Ltile(k, k), winv, mb, T(1));
-    // Z(r,i) -= Z(r,k) L(i,k)^T for every r and i > k: one launch
-    launch_gemm_nt_batch<T>(s, Ztile(0, k), bs, nr, Ltile(k + 1, k), bs, nt - 1 - k, Ztile(0, k + 1), bs, (long)nr * bs, mb,
-                            T(-1), T(1));
-  }
-  for (int k = nt - 1; k >= 0; --k) {  // backward
-    HIPCHECK(hipMemsetAsync(Wt, 0, tb, s));
-    launch_pad_identity<T>(s, Wt, 0, mb);
-    launch_invert_diag<T>(s, Ltile(k, k), mb, winv);
-    launch_trsm_panel<T>(s, Wt, bs, 1, Ltile(k, k), winv, mb, T(1));  // Wt = L(k,k)^{-T}
-    // Z(r,k) <- Z(r,k) L(k,k)^{-1} for every r (out of place, then back: the tiles of a column are contiguous)
-    launch_gemm_nt_batch<T>(s, Ztile(0, k), bs, nr, Wt, 0, 1, tmp, bs, 0, mb, T(1), T(0));
-    HIPCHECK(hipMemcpyAsync(Ztile(0, k), tmp, (size_t)nr * tb, hipMemcpyDeviceToDevice, s));
-    // Z(r,i) -= Z(r,k) L(k,i) for every r and i < k: the k tiles L(k,i)^T in one transpose launch, one product launch
-    if (k > 0) {
-      launch_tiles_transpose<T>(s, Ltile(k, 0), (long)A->lmt * bs, Tt, bs, mb, k);
-      launch_gemm_nt_batch<T>(s, Ztile(0, k), bs, nr, Tt, bs, k, Ztile(0, 0), bs, (long)nr * bs, mb, T(-1), T(1));
-    }
-  }
-  for (int r = 0; r < nr; ++r)  // B(i,r) = Z(r,i)^T
-    launch_tiles_transpose<T>(s, Ztile(r, 0), (long)nr * bs, Bm + (long)r * B->lmt * bs, bs, mb, nt);
-  HIPCHECK(hipGetLastError());  // (a refused launch configuration must not come back as a wrong solution)
-  HIPCHECK(hipStreamSynchronize(s));
   return 0;
 }
 
@@ -817,6 +629,104 @@ static int mfma_probe_on(RankCtx *r, int dtype, int waves_per_simd, int iters, d
 }  // namespace
 
 namespace cholmi {
+
+// ---- what spd.hip uses (api_internal.h) ------------------------------------------------------------------------
+bool ctx_inited() { return g.inited; }
+std::recursive_mutex &ctx_mutex() { return g_mu; }
+
+int fail(int code, const char *msg) {
+  set_error(msg);
+  return code;
+}
+int fail_hip(hipError_t e, const char *what, const char *file, int line) {
+  char buf[256];
+  snprintf(buf, sizeof buf, "%s failed at %s:%d: %s", what, file, line, hipGetErrorString(e));
+  set_error(buf);
+  return CHOL_ERR_HIP;
+}
+int scratch_failed(const char *what) {
+  (void)hipGetLastError();
+  char buf[96];
+  snprintf(buf, sizeof buf, "%s: scratch allocation failed", what);
+  return fail(CHOL_ERR_OUT_OF_MEMORY, buf);
+}
+
+int with_views(std::initializer_list<ViewArg> views, const std::function<int()> &body) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  if (int rc = tx_quiesce()) return rc;  // (the synchronous calls run on ST_MAIN alone: nothing of the task executor may be in flight)
+  for (const ViewArg &v : views)
+    if (v.d && v.d->user_mat) {
+      const int rc = view_sync(v.d, true);
+      if (rc) return rc;
+    }
+  int rc = body();
+  for (const ViewArg &v : views)
+    if (v.d && v.d->user_mat && v.write_back) {
+      const int r2 = view_sync(v.d, false);
+      if (r2 && rc >= 0) rc = r2;
+    }
+  return rc;
+}
+
+int resident_whole(const char *what, const chol_desc *d) {
+  char buf[160];
+  const char *why = nullptr;
+  if (!d) why = "NULL descriptor";
+  else if (!d->on_device) why = "descriptor must be device-resident";
+  else if (d->p * d->q != 1) why = "distributed descriptor";
+  else if (d->mb != d->nb) why = "tiles must be square";
+  if (!why) return 0;
+  snprintf(buf, sizeof buf, "%s: %s", what, why);
+  return fail(d ? CHOL_ERR_NOT_SUPPORTED : -2, buf);
+}
+bool same_geometry(const chol_desc *a, const chol_desc *b) {
+  return a->dtype == b->dtype && a->mb == b->mb && a->nb == b->nb && a->lm == b->lm && a->ln == b->ln &&
+         a->mbi == b->mbi && a->lmt == b->lmt && a->lnt == b->lnt;
+}
+TileGeo geo_of(const chol_desc *d) {
+  TileGeo g;
+  g.lmt = d->lmt;
+  g.lnt = d->lnt;
+  g.mbs = d->mbi;
+  g.mbu = d->mb;
+  g.m = d->lm;
+  g.n = d->ln;
+  return g;
+}
+
+bool winv_fits(const chol_desc *d) {
+  return (size_t)(roundup(d->mbi, MACRO) / MACRO) * MACRO * MACRO * d->esize <= g.r.winv_bytes;
+}
+void forget_winv(const void *ptr) {
+  if (g.wc_ptr == ptr) g.wc_ptr = nullptr, g.wc_version = 0;
+}
+
+void transpose_storage(chol_desc *A) {
+  if (A->dtype == CHOL_REAL_DOUBLE)
+    launch_transpose_inplace<double>(g.r.st[ST_MAIN], (double *)A->mat, A->nt, A->mbi);
+  else
+    launch_transpose_inplace<float>(g.r.st[ST_MAIN], (float *)A->mat, A->nt, A->mbi);
+}
+
+// (posvx factors AF inside its own view refresh)
+int potrf_run(int uplo, chol_desc *A) {
+  std::lock_guard<std::recursive_mutex> lk(g_mu);
+  if (uplo == CHOL_LOWER)
+    return A->dtype == CHOL_REAL_DOUBLE ? potrf_impl<double>(A) : potrf_impl<float>(A);
+  // ChamUpper: A = U^T U with U = L^T.  Transpose the stored matrix in place (its upper
+  // triangle becomes the lower one), factor Lower, transpose back: the upper triangle now
+  // holds U and the caller's strict lower triangle is bit-for-bit what it was.
+  const bool one = single_tile_square(A);
+  if (!one && (A->p * A->q != 1 || !A->on_device || A->mt != A->nt))
+    return fail(CHOL_ERR_NOT_SUPPORTED, "potrf_tile(Upper): single-process device-resident square matrices");
+  if (one && !(A->on_device && A->mb % MACRO == 0))
+    return A->dtype == CHOL_REAL_DOUBLE ? potrf_impl<double>(A, true) : potrf_impl<float>(A, true);
+  transpose_storage(A);
+  const int rc = A->dtype == CHOL_REAL_DOUBLE ? potrf_impl<double>(A) : potrf_impl<float>(A);
+  transpose_storage(A);
+  HIPCHECK(hipStreamSynchronize(g.r.st[ST_MAIN]));
+  return rc;
+}
 
 void *DevPool::get(size_t bytes) {
   for (auto &b : blks)
@@ -1069,38 +979,13 @@ int chol_finalize(void) {
   if (!g.inited) return 0;
   (void)hipDeviceSynchronize();
   chol_internal_dist_finalize();
-  for (int i = 0; i < 3; ++i) {
-    if (g.stage[i]) (void)hipFree(g.stage[i]);
-    g.stage[i] = nullptr;
-    g.stage_bytes[i] = 0;
-  }
-  if (g.work) (void)hipFree(g.work);
-  g.work = nullptr;
-  g.work_bytes = 0;
+  g.stage.release();
+  g.work.release();
+  spd_release();
   if (g.wc_winv) (void)hipFree(g.wc_winv);
   g.wc_winv = nullptr;
   if (g.d_binfo) (void)hipFree(g.d_binfo);
   g.d_binfo = nullptr;
-  for (int i = 0; i < 4; ++i) {
-    if (g.mx[i]) (void)hipFree(g.mx[i]);
-    g.mx[i] = nullptr;
-    g.mx_bytes[i] = 0;
-  }
-  for (int i = 0; i < 4; ++i) {
-    if (g.iv[i]) (void)hipFree(g.iv[i]);
-    g.iv[i] = nullptr;
-    g.iv_bytes[i] = 0;
-  }
-  for (int i = 0; i < 7; ++i) {
-    if (g.cn[i]) (void)hipFree(g.cn[i]);
-    g.cn[i] = nullptr;
-    g.cn_bytes[i] = 0;
-  }
-  for (int i = 0; i < 8; ++i) {
-    if (g.rf[i]) (void)hipFree(g.rf[i]);
-    g.rf[i] = nullptr;
-    g.rf_bytes[i] = 0;
-  }
   tx_destroy();
   g.wc_ptr = nullptr;
   g.wc_version = 0;
@@ -1649,8 +1534,6 @@ int chol_debug_task_check(long long *out5) {
 }
 
 // ---------------------------------------------------------------- POTRF
-static int potrf_run(int uplo, chol_desc *A);
-
 int chol_potrf_tile(int uplo, chol_desc_t *A) {
   return with_views({{A, true}}, [&]() -> int {
   if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "potrf_tile before chol_init");
@@ -1658,33 +1541,6 @@ int chol_potrf_tile(int uplo, chol_desc_t *A) {
   if (!A) return fail(-2, "potrf_tile: NULL descriptor");
   return potrf_run(uplo, A);
   });
-}
-
-// chol_potrf_tile after its argument checks, on the descriptor's image as it stands (posvx factors AF inside its own
-// view refresh)
-static int potrf_run(int uplo, chol_desc *A) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  if (uplo == CHOL_LOWER)
-    return A->dtype == CHOL_REAL_DOUBLE ? potrf_impl<double>(A) : potrf_impl<float>(A);
-  // ChamUpper: A = U^T U with U = L^T.  Transpose the stored matrix in place (its upper
-  // triangle becomes the lower one), factor Lower, transpose back: the upper triangle now
-  // holds U and the caller's strict lower triangle is bit-for-bit what it was.
-  const bool one = single_tile_square(A);
-  if (!one && (A->p * A->q != 1 || !A->on_device || A->mt != A->nt))
-    return fail(CHOL_ERR_NOT_SUPPORTED, "potrf_tile(Upper): single-process device-resident square matrices");
-  if (one && !(A->on_device && A->mb % MACRO == 0))
-    return A->dtype == CHOL_REAL_DOUBLE ? potrf_impl<double>(A, true) : potrf_impl<float>(A, true);
-  auto flip = [&]() {
-    if (A->dtype == CHOL_REAL_DOUBLE)
-      launch_transpose_inplace<double>(g.r.st[ST_MAIN], (double *)A->mat, A->nt, A->mbi);
-    else
-      launch_transpose_inplace<float>(g.r.st[ST_MAIN], (float *)A->mat, A->nt, A->mbi);
-  };
-  flip();
-  const int rc = A->dtype == CHOL_REAL_DOUBLE ? potrf_impl<double>(A) : potrf_impl<float>(A);
-  flip();
-  HIPCHECK(hipStreamSynchronize(g.r.st[ST_MAIN]));
-  return rc;
 }
 
 int chol_trsm_tile(int side, int uplo, int trans, int diag, double alpha, chol_desc_t *A,
@@ -1766,32 +1622,6 @@ int chol_plgsy_tile(double bump, int uplo, chol_desc_t *A, unsigned long long se
 }
 
 // ---------------------------------------------------------------- V6 validation block
-static int resident_whole(const char *what, const chol_desc *d) {
-  char buf[160];
-  const char *why = nullptr;
-  if (!d) why = "NULL descriptor";
-  else if (!d->on_device) why = "descriptor must be device-resident";
-  else if (d->p * d->q != 1) why = "distributed descriptor";
-  else if (d->mb != d->nb) why = "tiles must be square";
-  if (!why) return 0;
-  snprintf(buf, sizeof buf, "%s: %s", what, why);
-  return fail(d ? CHOL_ERR_NOT_SUPPORTED : -2, buf);
-}
-static bool same_geometry(const chol_desc *a, const chol_desc *b) {
-  return a->dtype == b->dtype && a->mb == b->mb && a->nb == b->nb && a->lm == b->lm && a->ln == b->ln &&
-         a->mbi == b->mbi && a->lmt == b->lmt && a->lnt == b->lnt;
-}
-static TileGeo geo_of(const chol_desc *d) {
-  TileGeo g;
-  g.lmt = d->lmt;
-  g.lnt = d->lnt;
-  g.mbs = d->mbi;
-  g.mbu = d->mb;
-  g.m = d->lm;
-  g.n = d->ln;
-  return g;
-}
-
 int chol_lacpy_tile(int uplo, chol_desc_t *A, chol_desc_t *B) {
   return with_views({{A, false}, {B, true}}, [&]() -> int {
   if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "lacpy_tile before chol_init");
@@ -1847,9 +1677,9 @@ int chol_lange_tile(int norm, chol_desc_t *A, double *value) {
   if (rc) return rc;
   std::lock_guard<std::recursive_mutex> lk(g_mu);
   const TileGeo ge = geo_of(A);
-  int rcw = ensure_work((size_t)(std::max(ge.m, ge.n) + 2) * sizeof(double));
+  int rcw = g.work.ensure_bytes(0, (size_t)(std::max(ge.m, ge.n) + 2) * sizeof(double), "lange_tile");
   if (rcw) return rcw;
-  double *work = reinterpret_cast<double *>(g.work);
+  double *work = g.work.as<double>(0);
   if (A->dtype == CHOL_REAL_DOUBLE)
     launch_lange<double>(g.r.st[ST_MAIN], ge, kind, (const double *)A->mat, work);
   else
@@ -1857,7 +1687,7 @@ int chol_lange_tile(int norm, chol_desc_t *A, double *value) {
   double v = 0;
   hipError_t e = hipMemcpyAsync(&v, work, sizeof(double), hipMemcpyDeviceToHost, g.r.st[ST_MAIN]);
   if (e == hipSuccess) e = hipStreamSynchronize(g.r.st[ST_MAIN]);
-  if (e != hipSuccess) return fail_hip(e, "lange_tile", __LINE__);
+  if (e != hipSuccess) return fail_hip(e, "lange_tile", __FILE__, __LINE__);
   *value = kind == 3 ? std::sqrt(v) : v;
   return 0;
   });
@@ -1892,1240 +1722,9 @@ int chol_lauum_tile(int uplo, chol_desc_t *A) {
   }
   hipError_t e = hipStreamSynchronize(g.r.st[ST_MAIN]);
   (void)hipFree(tmp);
-  if (e != hipSuccess) return fail_hip(e, "lauum_tile", __LINE__);
+  if (e != hipSuccess) return fail_hip(e, "lauum_tile", __FILE__, __LINE__);
   return 0;
   });
-}
-
-// ---------------------------------------------------------------- solve with the factor
-int chol_potrs_tile(int uplo, chol_desc_t *A, chol_desc_t *B) {
-  return with_views({{A, false}, {B, true}}, [&]() -> int {
-  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "potrs_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "potrs_tile: uplo");
-  int rc = resident_whole("potrs_tile", A);
-  if (rc) return rc;
-  rc = resident_whole("potrs_tile", B);
-  if (rc) return rc;
-  if (A->mt != A->nt || A->lm != A->ln) return fail(-2, "potrs_tile: A is not square");
-  if (B->lm != A->lm || B->mb != A->mb || B->mbi != A->mbi || B->dtype != A->dtype)
-    return fail(-3, "potrs_tile: B must have A's order, tile size and type");
-  if (A->mbi % 64) return fail(CHOL_ERR_NOT_SUPPORTED, "potrs_tile: stored tile edge must be a multiple of 64");
-  CHECK_WINV(A, "potrs_tile");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  // ChamUpper: A = U^T U with U = L^T -- transpose the factor's storage in place around the Lower solve
-  // (as chol_potrf_tile does around the Lower factorisation); the strict lower triangle comes back as it was
-  auto flip = [&]() {
-    if (A->dtype == CHOL_REAL_DOUBLE)
-      launch_transpose_inplace<double>(g.r.st[ST_MAIN], (double *)A->mat, A->nt, A->mbi);
-    else
-      launch_transpose_inplace<float>(g.r.st[ST_MAIN], (float *)A->mat, A->nt, A->mbi);
-  };
-  if (uplo == CHOL_UPPER) flip();
-  rc = A->dtype == CHOL_REAL_DOUBLE ? potrs_impl<double>(A, B) : potrs_impl<float>(A, B);
-  if (uplo == CHOL_UPPER) {
-    flip();
-    HIPCHECK(hipStreamSynchronize(g.r.st[ST_MAIN]));
-  }
-  return rc;
-  });
-}
-
-int chol_posv_tile(int uplo, chol_desc_t *A, chol_desc_t *B) {
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "posv_tile: uplo");
-  const int info = chol_potrf_tile(uplo, A);
-  if (info != 0) return info;  // > 0: not positive definite, B untouched (LAPACK dposv)
-  return chol_potrs_tile(uplo, A, B);
-}
-
-// ---------------------------------------------------------------- mixed-precision solve (LAPACK DSPOSV)
-// Factor an fp32 copy of A, solve in fp32, refine X in fp64 with residuals R = B - A X read from the stored triangle
-// (mixed.hip) until every column satisfies max|R(:,j)| <= max|X(:,j)| anrm eps sqrt(n); A and B are only read.
-// *iter < 0 (no convergence, an entry that does not fit in fp32, fp32 factor not SPD): X <- B and dposv on A, X.
-namespace {
-constexpr int DSPOSV_ITMAX = 30;
-struct MxTimer {  // the phases of the last call, on ST_MAIN (chol_last_dsposv_stats)
-  hipEvent_t e[2] = {nullptr, nullptr};
-  ~MxTimer() {
-    for (hipEvent_t x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-  int start() {
-    for (hipEvent_t &x : e)
-      if (!x) HIPCHECK(hipEventCreate(&x));
-    HIPCHECK(hipEventRecord(e[0], g.r.st[ST_MAIN]));
-    return 0;
-  }
-  int stop(double *acc) {  // (the phases end with a stream synchronisation of their own or are followed by one)
-    HIPCHECK(hipEventRecord(e[1], g.r.st[ST_MAIN]));
-    HIPCHECK(hipEventSynchronize(e[1]));
-    float ms = 0;
-    HIPCHECK(hipEventElapsedTime(&ms, e[0], e[1]));
-    *acc += ms;
-    return 0;
-  }
-};
-}  // namespace
-
-// -> *iter (>= 0: refinement steps; or -2 / -3 / -31 for the fallback), or a negative status
-static int dsposv_mixed(int uplo, chol_desc *A, chol_desc *B, chol_desc *X, int *iter) {
-  hipStream_t s = g.r.st[ST_MAIN];
-  const int up = uplo == CHOL_UPPER ? 1 : 0, nrhs = B->ln;
-  const TileGeo ga = geo_of(A), gx = geo_of(B);
-  double *st = g.mx_stats;  // total, conversions + norm, fp32 factor, fp32 solves, residual passes, #solves, #passes, -
-  std::fill(st, st + 8, 0.0);
-  const size_t rf_bytes = (size_t)B->lmt * B->lnt * B->bsizi * sizeof(float);
-  int rc = ensure_mx(0, (size_t)A->lmt * A->lnt * A->bsizi * sizeof(float));
-  if (!rc) rc = ensure_mx(1, rf_bytes);
-  if (!rc) rc = ensure_mx(2, sym_resid_part_bytes(ga, nrhs));
-  if (!rc) rc = ensure_mx(3, (size_t)(2 * nrhs + 2) * sizeof(unsigned long long));
-  if (rc) {
-    (void)hipGetLastError();
-    return fail(CHOL_ERR_OUT_OF_MEMORY, "dsposv_tile: scratch allocation failed");
-  }
-  float *Af = reinterpret_cast<float *>(g.mx[0]), *Rf = reinterpret_cast<float *>(g.mx[1]);
-  double *part = reinterpret_cast<double *>(g.mx[2]);
-  unsigned long long *colmax = reinterpret_cast<unsigned long long *>(g.mx[3]);
-  int *flag = reinterpret_cast<int *>(colmax + 2 * nrhs);
-  std::vector<unsigned long long> hmax(2 * nrhs + 1);
-  // fp32 descriptors over the scratch: A's and B's geometry (and A's work list)
-  chol_desc Ad = *A, Rd = *B;
-  Ad.dtype = Rd.dtype = CHOL_REAL_FLOAT;
-  Ad.esize = Rd.esize = sizeof(float);
-  Ad.mat = Af;
-  Rd.mat = Rf;
-  Ad.owns = Rd.owns = false;
-  Ad.version = Rd.version = 0;
-  Rd.d_list = nullptr;
-  MxTimer tt, tp;
-  if ((rc = tt.start())) return rc;
-  // anrm, then B and A to fp32 (-2 where an entry does not fit)
-  if ((rc = tp.start())) return rc;
-  HIPCHECK(hipMemsetAsync(colmax, 0, (2 * nrhs + 2) * sizeof(unsigned long long), s));
-  HIPCHECK(hipMemsetAsync(Rf, 0, rf_bytes, s));  // (the solve runs on whole tiles: padding must be finite)
-  launch_sym_inf_norm(s, ga, up, (const double *)A->mat, part, colmax);
-  launch_vec_to_f32(s, gx, (const double *)B->mat, Rf, flag);
-  launch_sym_to_f32(s, ga, up, (const double *)A->mat, Af, flag);
-  HIPCHECK(hipGetLastError());
-  unsigned long long anrm_bits = 0;
-  int hflag = 0;
-  HIPCHECK(hipMemcpyAsync(&anrm_bits, colmax, sizeof anrm_bits, hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipMemcpyAsync(&hflag, flag, sizeof hflag, hipMemcpyDeviceToHost, s));
-  if ((rc = tp.stop(&st[1]))) return rc;
-  double anrm;
-  memcpy(&anrm, &anrm_bits, sizeof anrm);
-  const double cte = anrm * std::ldexp(1.0, -53) * std::sqrt((double)A->lm);
-  auto finish = [&](int it) {
-    *iter = it;
-    return tt.stop(&st[0]);
-  };
-  if (hflag) return finish(-2);
-  // the fp32 factor: info > 0 -> -3; an error (CHOL_ERR_DEVICE_WAIT, HIP) is returned as it is
-  if ((rc = tp.start())) return rc;
-  rc = potrf_impl<float>(&Ad);
-  if (rc < 0) return rc;
-  if (int r2 = tp.stop(&st[2])) return r2;
-  if (rc > 0) return finish(-3);
-  auto solve = [&]() -> int {  // Rf <- A^{-1} Rf in fp32
-    int r = tp.start();
-    if (!r) r = potrs_impl<float>(&Ad, &Rd);
-    if (!r) r = tp.stop(&st[3]);
-    st[5] += 1;
-    return r;
-  };
-  if ((rc = solve())) return rc;
-  launch_vec_update(s, gx, Rf, (double *)X->mat, /*assign=*/true);
-  for (int it = 0;; ++it) {
-    // R = B - A X in fp64, rounded into Rf; the column maxima of R and X
-    if ((rc = tp.start())) return rc;
-    HIPCHECK(hipMemsetAsync(colmax, 0, (2 * nrhs + 2) * sizeof(unsigned long long), s));
-    launch_sym_resid(s, ga, up, (const double *)A->mat, gx, (const double *)X->mat, (const double *)B->mat, part, Rf,
-                     colmax, flag);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpyAsync(hmax.data(), colmax, (2 * nrhs + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    if ((rc = tp.stop(&st[4]))) return rc;
-    st[6] += 1;
-    bool done = true;
-    for (int j = 0; j < nrhs && done; ++j) {
-      double rn, xn;
-      memcpy(&rn, &hmax[j], sizeof rn);
-      memcpy(&xn, &hmax[nrhs + j], sizeof xn);
-      done = rn <= xn * cte;  // (a NaN residual does not converge)
-    }
-    if (done) return finish(it);
-    if (it == DSPOSV_ITMAX) return finish(-DSPOSV_ITMAX - 1);
-    if (hmax[2 * nrhs] & 0xffffffffull) return finish(-2);  // (the flag: the low word on a little-endian device)
-    if ((rc = solve())) return rc;
-    launch_vec_update(s, gx, Rf, (double *)X->mat, /*assign=*/false);
-  }
-}
-
-int chol_dsposv_tile(int uplo, chol_desc_t *A, chol_desc_t *B, chol_desc_t *X, int *iter) {
-  return with_views({{A, false}, {B, false}, {X, false}}, [&]() -> int {
-  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "dsposv_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "dsposv_tile: uplo");
-  int rc = resident_whole("dsposv_tile", A);
-  if (rc) return rc;
-  if (A->dtype != CHOL_REAL_DOUBLE) return fail(-2, "dsposv_tile: A must be fp64");
-  if (A->mt != A->nt || A->lm != A->ln) return fail(-2, "dsposv_tile: A is not square");
-  if (!B) return fail(-3, "dsposv_tile: B is NULL");
-  if ((rc = resident_whole("dsposv_tile", B))) return rc;
-  if (B->dtype != CHOL_REAL_DOUBLE || B->lm != A->lm || B->mb != A->mb || B->mbi != A->mbi || B->mat == A->mat)
-    return fail(-3, "dsposv_tile: B must be fp64 with A's order and tile size");
-  if (!X) return fail(-4, "dsposv_tile: X is NULL");
-  if ((rc = resident_whole("dsposv_tile", X))) return rc;
-  if (!same_geometry(B, X)) return fail(-4, "dsposv_tile: X must have B's shape, tile size and type");
-  if (X->mat == A->mat || X->mat == B->mat) return fail(-4, "dsposv_tile: X aliases A or B");
-  if (!iter) return fail(-5, "dsposv_tile: iter is NULL");
-  if (A->user_mat || B->user_mat || X->user_mat)
-    return fail(CHOL_ERR_NOT_SUPPORTED, "dsposv_tile: sub-matrix views over a user buffer");
-  if (A->mbi % MACRO) return fail(CHOL_ERR_NOT_SUPPORTED, "dsposv_tile: stored tile edge must be a multiple of 128");
-  CHECK_WINV(A, "dsposv_tile");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  rc = dsposv_mixed(uplo, A, B, X, iter);
-  if (rc < 0) return rc;
-  if (*iter >= 0) return 0;
-  // fallback (LAPACK dsposv): X <- B, then dposv in fp64 -- A then holds the fp64 factor
-  launch_lacpy<double>(g.r.st[ST_MAIN], geo_of(B), 0, (const double *)B->mat, (double *)X->mat);
-  HIPCHECK(hipStreamSynchronize(g.r.st[ST_MAIN]));
-  const int info = chol_potrf_tile(uplo, A);
-  if (info != 0) return info;
-  return chol_potrs_tile(uplo, A, X);
-  });
-}
-
-int chol_last_dsposv_stats(double *out8) {
-  if (!out8) return fail(-1, "last_dsposv_stats: NULL");
-  std::copy(g.mx_stats, g.mx_stats + 8, out8);
-  return 0;
-}
-
-// ---------------------------------------------------------------- inverse from the factor (LAPACK DTRTRI / DPOTRI)
-// X = L^{-1} in place over the lower tiles (inverse.hip: the 128-blocks of every diagonal tile, then the tiles, each
-// level column by column from the right), then for potri X^T X into the lower triangle (verify_ops.hip's LAUUM).
-// ChamUpper flips the storage around the Lower path, as potrf and potrs do.  A stored image whose padding is the
-// identity (a ragged order, a tile edge that is not a multiple of 128) is inverted as a whole: its padding stays the
-// identity and its matrix part is the inverse of the caller's matrix.
-extern "C++" {
-namespace {
-template <typename T>
-struct InvImg {  // nt x nt tiles of mbs x mbs (mbs % 128 == 0), tile (i,j) at p + (i + j lmt) mbs^2
-  T *p;
-  int nt, lmt, mbs;
-};
-}  // namespace
-
-template <typename T>
-static int trtri_img(const InvImg<T> &A) {
-  hipStream_t s = g.r.st[ST_MAIN];
-  const int nt = A.nt, mb = A.mbs, nbm = mb / MACRO;
-  const long bs = (long)mb * mb, tstride = (long)(A.lmt + 1) * bs, blk = (long)MACRO * MACRO;
-  // Y: nt tiles (tile level) or nt * nbm blocks (inner level); the 128 x 128 inverses of every diagonal tile
-  if (ensure_iv(0, (size_t)nt * bs * sizeof(T)) || ensure_iv(1, (size_t)nt * nbm * blk * sizeof(T))) {
-    (void)hipGetLastError();
-    return fail(CHOL_ERR_OUT_OF_MEMORY, "trtri_tile: scratch allocation failed");
-  }
-  T *Y = reinterpret_cast<T *>(g.iv[0]), *W = reinterpret_cast<T *>(g.iv[1]);
-  launch_invert_diag_batch<T>(s, A.p, tstride, nt, mb, W);
-  // the diagonal tiles, all at once: blocks (i,j) of tile z at p + z tstride + i 128 + j 128 mb
-  const TriLevel<T> in{A.p, MACRO, (long)MACRO * mb, tstride, mb, W, blk, nbm * blk, MACRO, Y, blk, nbm * blk, MACRO};
-  for (int c = nbm - 2; c >= 0; --c) launch_tri_column<T>(s, in, nbm, nt, c);
-  launch_tri_put_diag<T>(s, A.p, tstride, mb, nt, W);
-  // the tiles below the diagonal
-  const TriLevel<T> top{A.p, bs, (long)A.lmt * bs, 0, mb, A.p, tstride, 0, mb, Y, bs, 0, mb};
-  for (int c = nt - 2; c >= 0; --c) launch_tri_column<T>(s, top, nt, 1, c);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-// lower triangle of A <- X^T X, X the lower triangle of A (padding included: the identity stays)
-template <typename T>
-static int lauum_img(const InvImg<T> &A) {
-  hipStream_t s = g.r.st[ST_MAIN];
-  if (ensure_iv(0, (size_t)A.nt * A.nt * A.mbs * A.mbs * sizeof(T))) {
-    (void)hipGetLastError();
-    return fail(CHOL_ERR_OUT_OF_MEMORY, "potri_tile: scratch allocation failed");
-  }
-  T *out = reinterpret_cast<T *>(g.iv[0]);
-  launch_lauum_lower<T>(s, A.p, out, A.nt, A.mbs);
-  TileGeo ge;
-  ge.lmt = ge.lnt = A.nt;
-  ge.mbs = ge.mbu = A.mbs;
-  ge.m = ge.n = (long)A.nt * A.mbs;
-  launch_lacpy<T>(s, ge, 1, out, A.p);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-// A (Lower orientation, already checked) <- L^{-1}, or inv(L L^T) for potri
-template <typename T>
-static int inverse_impl(chol_desc *A, bool potri) {
-  hipStream_t s = g.r.st[ST_MAIN];
-  forget_winv(A->mat);  // (A is overwritten)
-  // potri: its LAUUM image first (trtri's Y blocks fit in it): no scratch is reallocated between the launches
-  const int ep = roundup(A->mbi, MACRO), nt = A->mbi % MACRO ? 1 : A->nt;
-  if (potri && ensure_iv(0, (size_t)nt * nt * ep * ep * sizeof(T))) {
-    (void)hipGetLastError();
-    return fail(CHOL_ERR_OUT_OF_MEMORY, "potri_tile: scratch allocation failed");
-  }
-  if (A->mbi % MACRO == 0) {
-    const InvImg<T> im{reinterpret_cast<T *>(A->mat), A->nt, A->lmt, A->mbi};
-    int rc = trtri_img<T>(im);
-    if (!rc && potri) rc = lauum_img<T>(im);
-    if (rc) return rc;
-    HIPCHECK(hipStreamSynchronize(s));
-    return 0;
-  }
-  // a single tile whose edge is an odd multiple of 64: staged into a multiple of 128 with the identity beyond it
-  const int e = A->mbi;
-  if (ensure_iv(2, (size_t)ep * ep * sizeof(T))) {
-    (void)hipGetLastError();
-    return fail(CHOL_ERR_OUT_OF_MEMORY, "trtri_tile: staging allocation failed");
-  }
-  T *S = reinterpret_cast<T *>(g.iv[2]);
-  HIPCHECK(hipMemsetAsync(S, 0, (size_t)ep * ep * sizeof(T), s));
-  HIPCHECK(hipMemcpy2DAsync(S, (size_t)ep * sizeof(T), A->mat, (size_t)e * sizeof(T), (size_t)e * sizeof(T), e,
-                            hipMemcpyDeviceToDevice, s));
-  launch_pad_identity<T>(s, S, e, ep);
-  const InvImg<T> im{S, 1, 1, ep};
-  int rc = trtri_img<T>(im);
-  if (!rc && potri) rc = lauum_img<T>(im);
-  if (rc) return rc;
-  // (the strict upper triangle goes back as it came: no kernel writes it)
-  HIPCHECK(hipMemcpy2DAsync(A->mat, (size_t)e * sizeof(T), S, (size_t)ep * sizeof(T), (size_t)e * sizeof(T), e,
-                            hipMemcpyDeviceToDevice, s));
-  HIPCHECK(hipStreamSynchronize(s));
-  return 0;
-}
-
-// the descriptor rules of chol_trtri_tile / chol_potri_tile / chol_poinv_tile (apos: A's argument position)
-static int inverse_check(const char *what, chol_desc *A, int apos) {
-  int rc = resident_whole(what, A);
-  if (rc) return rc;
-  char buf[160];
-  if (A->mt != A->nt || A->lm != A->ln) {
-    snprintf(buf, sizeof buf, "%s: A is not square", what);
-    return fail(-apos, buf);
-  }
-  if (A->mbi % 64) {
-    snprintf(buf, sizeof buf, "%s: stored tile edge must be a multiple of 64", what);
-    return fail(CHOL_ERR_NOT_SUPPORTED, buf);
-  }
-  return 0;
-}
-
-// the first exact zero on the diagonal (1-based), or 0; read before anything is written
-template <typename T>
-static int diag_zero(const chol_desc *A, int *info) {
-  hipStream_t s = g.r.st[ST_MAIN];
-  if (ensure_iv(3, sizeof(int))) {
-    (void)hipGetLastError();
-    return fail(CHOL_ERR_OUT_OF_MEMORY, "trtri_tile: scratch allocation failed");
-  }
-  int *first = reinterpret_cast<int *>(g.iv[3]);
-  launch_diag_zero<T>(s, reinterpret_cast<const T *>(A->mat), (long)(A->lmt + 1) * A->bsizi, A->mbi, A->mb, A->lm, first);
-  HIPCHECK(hipGetLastError());
-  int v = 0;
-  HIPCHECK(hipMemcpyAsync(&v, first, sizeof v, hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipStreamSynchronize(s));
-  *info = v <= A->lm ? v : 0;
-  return 0;
-}
-
-}  // extern "C++"
-
-static int inverse_run(int uplo, chol_desc *A, bool potri) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  const bool dbl = A->dtype == CHOL_REAL_DOUBLE;
-  int info = 0;
-  int rc = dbl ? diag_zero<double>(A, &info) : diag_zero<float>(A, &info);
-  if (rc) return rc;
-  if (info) return info;  // (LAPACK: A is unchanged)
-  // ChamUpper: U = L^T; inv(U) = inv(L)^T and inv(U^T U) = inv(L L^T) -- the Lower path on the transposed storage
-  auto flip = [&]() {
-    if (dbl)
-      launch_transpose_inplace<double>(g.r.st[ST_MAIN], (double *)A->mat, A->nt, A->mbi);
-    else
-      launch_transpose_inplace<float>(g.r.st[ST_MAIN], (float *)A->mat, A->nt, A->mbi);
-  };
-  if (uplo == CHOL_UPPER) flip();
-  rc = dbl ? inverse_impl<double>(A, potri) : inverse_impl<float>(A, potri);
-  if (uplo == CHOL_UPPER) {
-    flip();
-    HIPCHECK(hipStreamSynchronize(g.r.st[ST_MAIN]));
-  }
-  return rc;
-}
-
-int chol_trtri_tile(int uplo, int diag, chol_desc_t *A) {
-  return with_views({{A, true}}, [&]() -> int {
-  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "trtri_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "trtri_tile: uplo");
-  if (diag != CHOL_NONUNIT && diag != CHOL_UNIT) return fail(-2, "trtri_tile: diag");
-  if (diag == CHOL_UNIT)
-    return fail(CHOL_ERR_NOT_SUPPORTED, "trtri_tile: ChamUnit (a Cholesky factor has no unit diagonal)");
-  int rc = inverse_check("trtri_tile", A, 3);
-  if (rc) return rc;
-  return inverse_run(uplo, A, false);
-  });
-}
-
-int chol_potri_tile(int uplo, chol_desc_t *A) {
-  return with_views({{A, true}}, [&]() -> int {
-  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "potri_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "potri_tile: uplo");
-  int rc = inverse_check("potri_tile", A, 2);
-  if (rc) return rc;
-  return inverse_run(uplo, A, true);
-  });
-}
-
-int chol_poinv_tile(int uplo, chol_desc_t *A) {
-  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "poinv_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "poinv_tile: uplo");
-  int rc = inverse_check("poinv_tile", A, 2);  // (before the factorisation writes anything)
-  if (rc) return rc;
-  const int info = chol_potrf_tile(uplo, A);
-  if (info != 0) return info;  // > 0: not positive definite, A as potrf leaves it
-  return chol_potri_tile(uplo, A);
-}
-
-// ---------------------------------------------------------------- condition estimate (LAPACK DLANSY / DPOCON)
-// lansy: one pass over the stored triangle (condest.hip).  pocon: LAPACK DLACN2's state machine on the host, which
-// reads back six scalars after each application of A^{-1}; the applications (two narrow triangular sweeps over the
-// stored triangle) and every operation on an N-vector run on the device (condest.hip).
-static int cn_oom(const char *what) {
-  (void)hipGetLastError();
-  char buf[96];
-  snprintf(buf, sizeof buf, "%s: scratch allocation failed", what);
-  return fail(CHOL_ERR_OUT_OF_MEMORY, buf);
-}
-
-int chol_lansy_tile(int norm, int uplo, chol_desc_t *A, double *value) {
-  return with_views({{A, false}}, [&]() -> int {
-  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "lansy_tile before chol_init");
-  int kind;
-  switch (norm) {
-    case CHOL_MAX_NORM: kind = 0; break;
-    case CHOL_ONE_NORM:
-    case CHOL_INF_NORM: kind = 1; break;  // (symmetric: one value for both)
-    case CHOL_FROBENIUS_NORM: kind = 2; break;
-    default: return fail(-1, "lansy_tile: norm");
-  }
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-2, "lansy_tile: uplo");
-  int rc = inverse_check("lansy_tile", A, 3);
-  if (rc) return rc;
-  if (!value) return fail(-4, "lansy_tile: NULL value");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  hipStream_t s = g.r.st[ST_MAIN];
-  const TileGeo ge = geo_of(A);
-  const size_t pb = lansy_part_bytes(ge);
-  if (ensure_cn(6, pb + 4 * sizeof(double))) return cn_oom("lansy_tile");
-  double *part = reinterpret_cast<double *>(g.cn[6]), *res = part + pb / sizeof(double);
-  const int up = uplo == CHOL_UPPER;
-  if (A->dtype == CHOL_REAL_DOUBLE)
-    launch_lansy<double>(s, ge, up, (const double *)A->mat, part, res);
-  else
-    launch_lansy<float>(s, ge, up, (const float *)A->mat, part, res);
-  HIPCHECK(hipGetLastError());
-  double v[3] = {0, 0, 0};  // (the max and the row-sum max are the bits of non-negative doubles: read as doubles)
-  HIPCHECK(hipMemcpyAsync(v, res, sizeof v, hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipStreamSynchronize(s));
-  *value = kind == 2 ? std::sqrt(v[2]) : v[kind];
-  return 0;
-  });
-}
-
-extern "C++" {
-namespace {
-struct CnEvents {  // [0, 1]: around the current application, [2, 3]: the whole call
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-  ~CnEvents() {
-    for (hipEvent_t x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-};
-}  // namespace
-
-// LAPACK DLACN2's control flow for one vector (Higham's estimator, as LAPACK has it): what the device does before the
-// next application of the operator (fill x: -1 nothing, 0 1/n, 1 e_j, 2 the alternating-sign vector; kase 1 / 2), the
-// statistics after it (condest.hip: launch_vec_stats with `sign`, `jlast`), and the estimate.  pocon applies A^{-1}
-// for both kases; porfs applies diag(W) A^{-1} (kase 1) and A^{-1} diag(W) (kase 2).
-struct Lacn2 {
-  static constexpr int ITMAX = 5;
-  long n = 0;
-  int isave = 0, iter = 0;
-  long j = 0;
-  double est = 0;
-  bool done = false, finite = true;
-  int fill = 0, kase = 1, sign = 1;
-  long fill_j = 0, jlast = -1;
-  void next(int isave_, int fill_, long fill_j_, int kase_, int sign_, long jlast_) {
-    isave = isave_, fill = fill_, fill_j = fill_j_, kase = kase_, sign = sign_, jlast = jlast_;
-  }
-  void start(long n_) {
-    n = n_, iter = 0, j = 0, est = 0, done = false, finite = true;
-    next(1, 0, 0, 1, 1, -1);  // x = 1/n; after it est = ||x||_1, x = isgn = sign(x)
-  }
-  // st: launch_vec_stats' out[0..5] after the application (sum |x|, max |x|, its index, non-finite, x[jlast], changed)
-  template <typename T>
-  void take(const double *st) {
-    if (st[3] != 0) {  // (no dlatrs scaling: a non-finite entry ends the estimate)
-      finite = false;
-      done = true;
-      return;
-    }
-    switch (isave) {
-      case 1:
-        est = st[0];
-        if (n <= 1) {
-          done = true;
-          return;
-        }
-        return next(2, -1, 0, 2, 0, -1);  // then j = idamax(x)
-      case 2:
-        j = (long)st[2];
-        iter = 2;
-        return next(3, 1, j, 1, 1, -1);  // x = e_j; then est = ||x||_1, x = isgn = sign(x), changed?
-      case 3: {
-        const double estold = est;
-        est = st[0];
-        if (st[5] == 0 || est <= estold) break;  // a repeated sign vector, or no increase: converged
-        return next(4, -1, 0, 2, 0, j);          // then j = idamax(x), x(jlast) against |x(j)|
-      }
-      case 4:
-        if (st[4] != st[1] && iter < ITMAX) {
-          ++iter;
-          j = (long)st[2];
-          return next(3, 1, j, 1, 1, -1);
-        }
-        break;
-      default: {  // 5: the alternating-sign test vector
-        const T temp = T(2) * (T(st[0]) / T(3 * n));
-        if ((double)temp > est) est = (double)temp;
-        done = true;
-        return;
-      }
-    }
-    next(5, 2, 0, 1, 0, -1);
-  }
-};
-
-// the diagonal tiles of the factor, inverted once per call: their 128-blocks (as potrs), then the tiles (trtri's inner
-// level), into g.cn[0]
-template <typename T>
-static int stage_factor_diag(chol_desc *A, int upper, const char *what) {
-  hipStream_t s = g.r.st[ST_MAIN];
-  const TileGeo ge = geo_of(A);
-  const int E = condest_edge(ge), nbm = E / MACRO, nt = A->nt;
-  const long blk = (long)MACRO * MACRO;
-  if (ensure_cn(0, (size_t)nt * E * E * sizeof(T)) || ensure_cn(1, (size_t)nt * nbm * blk * sizeof(T)) ||
-      ensure_cn(2, (size_t)nt * nbm * blk * sizeof(T)))
-    return cn_oom(what);
-  T *Dv = reinterpret_cast<T *>(g.cn[0]), *W = reinterpret_cast<T *>(g.cn[1]), *Y = reinterpret_cast<T *>(g.cn[2]);
-  launch_stage_diag<T>(s, ge, upper, reinterpret_cast<const T *>(A->mat), Dv);
-  launch_invert_diag_batch<T>(s, Dv, (long)E * E, nt, E, W);
-  const TriLevel<T> in{Dv, MACRO, (long)MACRO * E, (long)E * E, E, W, blk, nbm * blk, MACRO, Y, blk, nbm * blk, MACRO};
-  for (int c = nbm - 2; c >= 0; --c) launch_tri_column<T>(s, in, nbm, nt, c);
-  launch_tri_put_diag<T>(s, Dv, (long)E * E, E, nt, W);
-  HIPCHECK(hipGetLastError());
-  return 0;
-}
-
-// staged: g.cn[0] already holds the inverted diagonal tiles of this factor (posvx)
-template <typename T>
-static int pocon_impl(chol_desc *A, int upper, double anorm, double *rcond, bool staged = false) {
-  hipStream_t s = g.r.st[ST_MAIN];
-  const TileGeo ge = geo_of(A);
-  const long n = A->lm;
-  for (double &v : g.cn_stats) v = 0;
-  *rcond = 0;
-  if (n == 0) {
-    *rcond = 1;
-    return 0;
-  }
-  if (anorm == 0 || std::isinf(anorm)) return 0;
-  CnEvents ev;
-  for (hipEvent_t &x : ev.e) HIPCHECK(hipEventCreate(&x));
-  HIPCHECK(hipEventRecord(ev.e[2], s));
-  int info = 0;
-  int rc = diag_zero<T>(A, &info);
-  if (rc) return rc;
-  if (info) return 0;  // a zero on the factor's diagonal: rcond = 0, no sweep
-  // scratch: the diagonal tiles, their 128-block inverses, the products' Y blocks (stage_factor_diag), the vectors,
-  // the sign vector, the statistics
-  const int E = condest_edge(ge), nt = A->nt, bpt = E / MACRO;
-  const long NB = (long)nt * bpt;
-  const size_t nv = condest_vec_elems(ge), npg = 2 * (size_t)NB * bpt * MACRO, npd = (size_t)bpt * bpt * MACRO;
-  if (!staged && (rc = stage_factor_diag<T>(A, upper, "pocon_tile"))) return rc;
-  if (ensure_cn(3, (2 * nv + npg + npd) * sizeof(T)) || ensure_cn(4, nv * sizeof(int)) ||
-      ensure_cn(5, vec_stats_part_bytes() + 8 * sizeof(double)))
-    return cn_oom("pocon_tile");
-  const T *Dv = reinterpret_cast<const T *>(g.cn[0]);
-  T *vx = reinterpret_cast<T *>(g.cn[3]);
-  const SweepBufs<T> bufs{vx, vx + nv, vx + 2 * nv, vx + 2 * nv + npg};
-  int *isgn = reinterpret_cast<int *>(g.cn[4]);
-  double *spart = reinterpret_cast<double *>(g.cn[5]), *sout = spart + vec_stats_part_bytes() / sizeof(double);
-  const T *Am = reinterpret_cast<const T *>(A->mat);
-  int apps = 0;
-  double sweep_ms = 0, st[6] = {0, 0, 0, 0, 0, 0};
-  // x <- A^{-1} x, then the statistics of x (DLACN2's kase != 0 round trip)
-  auto apply = [&](int sign, long jlast) -> int {
-    HIPCHECK(hipEventRecord(ev.e[0], s));
-    launch_sweep<T>(s, ge, upper, Am, Dv, bufs);
-    HIPCHECK(hipEventRecord(ev.e[1], s));
-    launch_vec_stats<T>(s, ge, bufs.x, isgn, sign, jlast, spart, sout);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpyAsync(st, sout, sizeof st, hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    float ms = 0;
-    HIPCHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-    sweep_ms += ms;
-    ++apps;
-    return 0;
-  };
-  // DLACN2; A is symmetric, so kase 1 and kase 2 apply the same A^{-1}
-  Lacn2 est;
-  est.start(n);
-  while (!est.done) {
-    if (est.fill >= 0) launch_vec_fill<T>(s, ge, bufs.x, est.fill, est.fill_j);
-    if ((rc = apply(est.sign, est.jlast))) return rc;
-    est.take<T>(st);
-  }
-  // (no dlatrs scaling: a sweep that overflows gives rcond = 0)
-  if (est.finite && est.est != 0) *rcond = (1.0 / est.est) / anorm;
-  HIPCHECK(hipEventRecord(ev.e[3], s));
-  HIPCHECK(hipEventSynchronize(ev.e[3]));
-  float total = 0;
-  HIPCHECK(hipEventElapsedTime(&total, ev.e[2], ev.e[3]));
-  g.cn_stats[0] = total;
-  g.cn_stats[1] = sweep_ms;
-  g.cn_stats[2] = apps;
-  return 0;
-}
-}  // extern "C++"
-
-int chol_pocon_tile(int uplo, chol_desc_t *A, double anorm, double *rcond) {
-  return with_views({{A, false}}, [&]() -> int {
-  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "pocon_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "pocon_tile: uplo");
-  int rc = inverse_check("pocon_tile", A, 2);
-  if (rc) return rc;
-  if (!(anorm >= 0)) return fail(-3, "pocon_tile: anorm is negative or NaN");
-  if (!rcond) return fail(-4, "pocon_tile: NULL rcond");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  const int up = uplo == CHOL_UPPER;
-  return A->dtype == CHOL_REAL_DOUBLE ? pocon_impl<double>(A, up, anorm, rcond) : pocon_impl<float>(A, up, anorm, rcond);
-  });
-}
-
-int chol_last_pocon_stats(double *out4) {
-  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "last_pocon_stats before chol_init");
-  if (!out4) return fail(-1, "last_pocon_stats: NULL");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  for (int i = 0; i < 4; ++i) out4[i] = g.cn_stats[i];
-  return 0;
-}
-
-// ---------------------------------------------------------------- the SPD expert solve (LAPACK DPOEQU, DLAQSY, DPORFS, DPOSVX)
-// poequ / laqsy: one pass over the diagonal / the stored triangle (refine.hip).  porfs: every column in lockstep, each
-// with its own refinement count, lstres and DLACN2 state; each step applies A^{-1} only to the columns still active,
-// either with the multi-vector sweeps (at most K_X columns: ceil(k / 8) sweeps of up to 8 vectors) or with potrs_impl
-// on a scratch n x k image (wider steps).  posvx composes them in DPOSVX's order.
-extern "C++" {
-namespace {
-// the widest application of A^{-1} that runs as multi-vector sweeps; wider ones go through potrs_impl.  Measured
-// crossover: about 47 columns at N = 65536 / 1024, about 30 at 16384 / 512
-constexpr int POSVX_KX = 40;
-constexpr int PORFS_ITMAX = 5;
-
-template <typename T>
-struct Lam;  // LAPACK xLAMCH: 'E'psilon (rounding), 'S'afe minimum, 'P'recision = eps * base
-template <>
-struct Lam<double> {
-  static constexpr double eps = 0x1p-53, safmin = 0x1p-1022, prec = 0x1p-52;
-};
-template <>
-struct Lam<float> {
-  static constexpr double eps = 0x1p-24, safmin = 0x1p-126, prec = 0x1p-23;
-};
-}  // namespace
-}  // extern "C++"
-
-int ensure_rf(int idx, size_t bytes) {
-  if (g.rf_bytes[idx] >= bytes) return 0;
-  if (g.rf[idx]) HIPCHECK(hipFree(g.rf[idx]));
-  g.rf[idx] = nullptr;
-  g.rf_bytes[idx] = 0;
-  bytes = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-  HIPCHECK(hipMalloc(&g.rf[idx], bytes));
-  HIPCHECK(hipMemset(g.rf[idx], 0, bytes));
-  g.rf_bytes[idx] = bytes;
-  return 0;
-}
-
-extern "C++" {
-namespace {
-// porfs / posvx's scratch (g.rf): the residual / estimator vectors, the FERR weights, the sign vectors (one
-// condest-layout vector per column each), the residual partials, the sweeps' scratch and padding vectors, the
-// backward errors and statistics, and the n x k image of the potrs path
-template <typename T>
-struct RfBufs {
-  T *R, *F, *part, *sw, *pad;
-  int *isgn;
-  unsigned long long *berr;
-  double *spart, *sout;
-  long nv;
-};
-
-template <typename T>
-static int rf_buffers(const TileGeo &ga, int nrhs, RfBufs<T> *b, const char *what) {
-  const long nv = (long)condest_vec_elems(ga);
-  const size_t vb = (size_t)nrhs * nv * sizeof(T);
-  const size_t sb = vec_stats_part_bytes() + (size_t)(nrhs + 1) * 8 * sizeof(double);
-  if (ensure_rf(0, vb) || ensure_rf(1, vb) || ensure_rf(2, (size_t)nrhs * nv * sizeof(int)) ||
-      ensure_rf(3, porfs_part_elems(ga, refine_width(std::min(nrhs, 8))) * sizeof(T)) ||
-      ensure_rf(4, (msweep_scratch_elems(ga) + 8 * (size_t)nv) * sizeof(T)) ||
-      ensure_rf(5, (size_t)nrhs * sizeof(unsigned long long) + sb))
-    return cn_oom(what);
-  b->nv = nv;
-  b->R = reinterpret_cast<T *>(g.rf[0]);
-  b->F = reinterpret_cast<T *>(g.rf[1]);
-  b->isgn = reinterpret_cast<int *>(g.rf[2]);
-  b->part = reinterpret_cast<T *>(g.rf[3]);
-  b->sw = reinterpret_cast<T *>(g.rf[4]);
-  b->pad = b->sw + msweep_scratch_elems(ga);
-  b->berr = reinterpret_cast<unsigned long long *>(g.rf[5]);
-  b->spart = reinterpret_cast<double *>(b->berr + nrhs);
-  b->sout = b->spart + vec_stats_part_bytes() / sizeof(double);
-  return 0;
-}
-
-// V[c] <- A^{-1} V[c] for the slots c in `cols` (AF: the factor, its diagonal tiles staged in g.cn[0]); st: posvx stats;
-// path: 0 the path rule, 1 the sweeps, 2 potrs (chol_bench_refine)
-template <typename T>
-static int apply_inv(int upper, chol_desc *AF, const RfBufs<T> &b, T *V, const std::vector<int> &cols, double *st,
-                     int path = 0) {
-  hipStream_t s = g.r.st[ST_MAIN];
-  const TileGeo ga = geo_of(AF);
-  const int k = (int)cols.size();
-  if (!k) return 0;
-  if (path == 1 || (path == 0 && k <= POSVX_KX)) {
-    const long NB = (long)ga.lmt * (condest_edge(ga) / MACRO);
-    const long nv = b.nv, pgn = 2 * NB * (condest_edge(ga) / MACRO) * MACRO;
-    const MSweepBufs<T> mb{b.sw, b.sw + 8 * nv, b.sw + 8 * nv + 8 * pgn};
-    for (int c0 = 0; c0 < k; c0 += 8) {
-      const int m = std::min(8, k - c0);
-      T *x[8];
-      for (int j = 0; j < m; ++j) x[j] = V + (long)cols[c0 + j] * nv;
-      launch_msweep<T>(s, ga, upper, reinterpret_cast<const T *>(AF->mat), reinterpret_cast<const T *>(g.cn[0]), x, m,
-                       b.pad, mb);
-      st[6] += m;
-    }
-    HIPCHECK(hipGetLastError());
-    return 0;
-  }
-  // wide: potrs_impl on an n x k scratch image with AF's row tiling (the solve runs on whole tiles: zero padding)
-  chol_desc Td = *AF;
-  Td.ln = Td.n = k;
-  Td.nt = Td.lnt = (k + AF->mb - 1) / AF->mb;
-  Td.owns = false;
-  Td.version = 0;
-  Td.d_list = nullptr;
-  Td.user_mat = nullptr;
-  const size_t tb = (size_t)Td.lmt * Td.lnt * Td.bsizi * sizeof(T);
-  if (ensure_rf(6, tb)) return cn_oom("porfs_tile");
-  Td.mat = g.rf[6];
-  HIPCHECK(hipMemsetAsync(Td.mat, 0, tb, s));
-  const TileGeo gt = geo_of(&Td);
-  for (int c0 = 0; c0 < k; c0 += 8) {
-    VecCols vc{std::min(8, k - c0), {}, {}};
-    for (int j = 0; j < vc.n; ++j) vc.v[j] = cols[c0 + j], vc.d[j] = c0 + j;
-    launch_scatter<T>(s, gt, reinterpret_cast<T *>(Td.mat), vc, V, false);
-  }
-  auto flip = [&]() { launch_transpose_inplace<T>(s, reinterpret_cast<T *>(AF->mat), AF->nt, AF->mbi); };
-  if (upper) flip();
-  int rc = potrs_impl<T>(AF, &Td);
-  if (upper) flip();
-  if (rc) return rc;
-  for (int c0 = 0; c0 < k; c0 += 8) {
-    VecCols vc{std::min(8, k - c0), {}, {}};
-    for (int j = 0; j < vc.n; ++j) vc.v[j] = cols[c0 + j], vc.d[j] = c0 + j;
-    launch_gather<T>(s, gt, reinterpret_cast<const T *>(Td.mat), vc, V);
-  }
-  HIPCHECK(hipGetLastError());
-  st[7] += k;
-  return 0;
-}
-
-template <typename T>
-static std::vector<VecCols> groups_of(const std::vector<int> &cols) {
-  std::vector<VecCols> out;
-  for (size_t c0 = 0; c0 < cols.size(); c0 += 8) {
-    VecCols vc{(int)std::min<size_t>(8, cols.size() - c0), {}, {}};
-    for (int j = 0; j < vc.n; ++j) vc.v[j] = vc.d[j] = cols[c0 + j];
-    out.push_back(vc);
-  }
-  return out;
-}
-
-// LAPACK DPORFS on device images; AF's diagonal tiles staged in g.cn[0]; st: posvx stats ([5] total porfs ms,
-// [6] / [7] columns through the sweeps / through potrs)
-template <typename T>
-static int porfs_impl(int upper, chol_desc *A, chol_desc *AF, chol_desc *B, chol_desc *X, double *ferr, double *berr,
-                      double *st) {
-  hipStream_t s = g.r.st[ST_MAIN];
-  const TileGeo ga = geo_of(A), gx = geo_of(B);
-  const long n = A->lm;
-  const int nrhs = B->ln;
-  if (n == 0 || nrhs == 0) {
-    std::fill(ferr, ferr + nrhs, 0.0);
-    std::fill(berr, berr + nrhs, 0.0);
-    return 0;
-  }
-  MxTimer tt;
-  int rc = tt.start();
-  if (rc) return rc;
-  RfBufs<T> b;
-  if ((rc = rf_buffers<T>(ga, nrhs, &b, "porfs_tile"))) return rc;
-  const double eps = Lam<T>::eps, safe1 = (double)(T(n + 1) * T(Lam<T>::safmin)), safe2 = (double)(T(safe1) / T(eps));
-  const T *Am = reinterpret_cast<const T *>(A->mat);
-  std::vector<int> count(nrhs, 1), active(nrhs);
-  std::vector<double> lstres(nrhs, 3.0);
-  std::vector<unsigned long long> hb(nrhs);
-  for (int j = 0; j < nrhs; ++j) active[j] = j;
-  // refinement: R = B - A X, BERR; X += A^{-1} R for the columns that go on
-  while (!active.empty()) {
-    HIPCHECK(hipMemsetAsync(b.berr, 0, (size_t)nrhs * sizeof(unsigned long long), s));
-    for (const VecCols &vc : groups_of<T>(active))
-      launch_porfs_resid<T>(s, ga, upper, Am, gx, reinterpret_cast<const T *>(X->mat), reinterpret_cast<const T *>(B->mat),
-                            vc, b.part, b.R, b.F, eps, safe1, safe2, b.berr);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpyAsync(hb.data(), b.berr, (size_t)nrhs * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    std::vector<int> next;
-    for (int j : active) {
-      double bj;
-      memcpy(&bj, &hb[j], sizeof bj);
-      berr[j] = bj;
-      if (bj > eps && 2 * bj <= lstres[j] && count[j] <= PORFS_ITMAX) {
-        next.push_back(j);
-        lstres[j] = bj;
-        ++count[j];
-      }
-    }
-    if ((rc = apply_inv<T>(upper, AF, b, b.R, next, st))) return rc;
-    for (const VecCols &vc : groups_of<T>(next)) launch_scatter<T>(s, gx, reinterpret_cast<T *>(X->mat), vc, b.R, true);
-    active.swap(next);
-  }
-  // FERR: DLACN2 on diag(F) A^{-1} (kase 1) / A^{-1} diag(F) (kase 2), every column in lockstep, x in the R slots
-  std::vector<Lacn2> est(nrhs);
-  for (int j = 0; j < nrhs; ++j) est[j].start(n), active.push_back(j);
-  std::vector<double> hs((size_t)nrhs * 8);
-  while (!active.empty()) {
-    const std::vector<VecCols> gr = groups_of<T>(active);
-    for (int j : active)
-      if (est[j].fill >= 0) launch_vec_fill<T>(s, ga, b.R + (long)j * b.nv, est[j].fill, est[j].fill_j);
-    auto weight = [&](int kase) {
-      for (const VecCols &vc : gr) {
-        unsigned mask = 0;
-        for (int i = 0; i < vc.n; ++i) mask |= (est[vc.v[i]].kase == kase ? 1u : 0u) << i;
-        launch_vec_weight<T>(s, ga, b.R, b.F, vc, mask);
-      }
-    };
-    weight(2);
-    if ((rc = apply_inv<T>(upper, AF, b, b.R, active, st))) return rc;
-    weight(1);
-    for (size_t i = 0; i < active.size(); ++i) {
-      const int j = active[i];
-      launch_vec_stats<T>(s, ga, b.R + (long)j * b.nv, b.isgn + (long)j * b.nv, est[j].sign, est[j].jlast, b.spart,
-                          b.sout + 8 * i);
-    }
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipMemcpyAsync(hs.data(), b.sout, active.size() * 8 * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    std::vector<int> next;
-    for (size_t i = 0; i < active.size(); ++i) {
-      const int j = active[i];
-      est[j].take<T>(&hs[8 * i]);
-      if (!est[j].done) next.push_back(j);
-    }
-    active.swap(next);
-  }
-  // normalise by max |X(:,j)| (gathered into a padding vector, then launch_vec_stats)
-  for (int j = 0; j < nrhs; ++j) {
-    const VecCols vc{1, {0}, {j}};
-    launch_gather<T>(s, gx, reinterpret_cast<const T *>(X->mat), vc, b.pad);
-    launch_vec_stats<T>(s, ga, b.pad, b.isgn, 0, -1, b.spart, b.sout + 8 * j);
-  }
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipMemcpyAsync(hs.data(), b.sout, (size_t)nrhs * 8 * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipStreamSynchronize(s));
-  for (int j = 0; j < nrhs; ++j) {
-    T f = est[j].finite ? T(est[j].est) : T(INFINITY);
-    const T xm = T(hs[8 * j + 1]);
-    if (xm != T(0)) f = f / xm;
-    ferr[j] = (double)f;
-  }
-  return tt.stop(&st[5]);
-}
-}  // namespace
-}  // extern "C++"
-
-// the descriptor rules shared by porfs / posvx: an n x nrhs image d with A's dtype, order and tile size
-static int rhs_check(const char *what, const chol_desc *A, const chol_desc *d, int pos, const char *name) {
-  char buf[160];
-  if (!d) {
-    snprintf(buf, sizeof buf, "%s: %s is NULL", what, name);
-    return fail(-pos, buf);
-  }
-  if (int rc = resident_whole(what, d)) return rc;
-  if (d->dtype != A->dtype || d->lm != A->lm || d->mb != A->mb || d->mbi != A->mbi) {
-    snprintf(buf, sizeof buf, "%s: %s must have A's dtype, order and tile size", what, name);
-    return fail(-pos, buf);
-  }
-  return 0;
-}
-
-static int square_check(const char *what, chol_desc *A, int pos) {
-  if (!A) {
-    char buf[96];
-    snprintf(buf, sizeof buf, "%s: NULL descriptor", what);
-    return fail(-pos, buf);
-  }
-  return inverse_check(what, A, pos);
-}
-
-extern "C++" {
-// LAPACK DPOEQU on the device: S <- 1/sqrt(diag), *scond, *amax; info > 0: the first non-positive diagonal entry
-template <typename T>
-static int poequ_impl(chol_desc *A, chol_desc *S, double *scond, double *amax, int *info) {
-  hipStream_t s = g.r.st[ST_MAIN];
-  const long n = A->lm;
-  *info = 0;
-  if (n == 0) {
-    *scond = 1, *amax = 0;
-    return 0;
-  }
-  if (ensure_rf(7, diag_scan_part_bytes())) return cn_oom("poequ_tile");
-  double *part = reinterpret_cast<double *>(g.rf[7]);
-  launch_diag_scan<T>(s, geo_of(A), reinterpret_cast<const T *>(A->mat), reinterpret_cast<T *>(S->mat), 0, part);
-  HIPCHECK(hipGetLastError());
-  std::vector<double> h(diag_scan_part_bytes() / sizeof(double));
-  HIPCHECK(hipMemcpyAsync(h.data(), part, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipStreamSynchronize(s));
-  const long per = (n + 255) / 256;
-  T smin = T(INFINITY), smax = T(-INFINITY);
-  long bad = -1;
-  for (long w = 0; w < 256 && w * per < n; ++w) {
-    smin = std::min(smin, T(h[3 * w]));
-    smax = std::max(smax, T(h[3 * w + 1]));
-    if (h[3 * w + 2] >= 0 && bad < 0) bad = (long)h[3 * w + 2];
-  }
-  *amax = (double)smax;
-  if (smin <= T(0)) {
-    *info = (int)(bad + 1);
-    return 0;
-  }
-  *scond = (double)(T(std::sqrt(smin)) / T(std::sqrt(smax)));
-  return 0;
-}
-
-// LAPACK DLAQSY's decision and scaling; *equed <- 1 ('Y') or 0 ('N')
-template <typename T>
-static int laqsy_impl(int upper, chol_desc *A, chol_desc *S, double scond, double amax, int *equed) {
-  const double small = Lam<T>::safmin / Lam<T>::prec, large = 1.0 / small;
-  *equed = 0;
-  if (A->lm == 0) return 0;
-  if (scond >= 0.1 && amax >= small && amax <= large) return 0;
-  launch_laqsy<T>(g.r.st[ST_MAIN], geo_of(A), upper, reinterpret_cast<T *>(A->mat), reinterpret_cast<const T *>(S->mat));
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipStreamSynchronize(g.r.st[ST_MAIN]));
-  *equed = 1;
-  return 0;
-}
-}  // extern "C++"
-
-int chol_poequ_tile(chol_desc_t *A, chol_desc_t *S, double *scond, double *amax) {
-  return with_views({{A, false}, {S, true}}, [&]() -> int {
-  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "poequ_tile before chol_init");
-  int rc = square_check("poequ_tile", A, 1);
-  if (rc) return rc;
-  if ((rc = rhs_check("poequ_tile", A, S, 2, "S"))) return rc;
-  if (S->ln != 1 || S->mat == A->mat) return fail(-2, "poequ_tile: S must be an n x 1 descriptor of its own");
-  if (!scond) return fail(-3, "poequ_tile: NULL scond");
-  if (!amax) return fail(-4, "poequ_tile: NULL amax");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  int info = 0;
-  rc = A->dtype == CHOL_REAL_DOUBLE ? poequ_impl<double>(A, S, scond, amax, &info)
-                                    : poequ_impl<float>(A, S, scond, amax, &info);
-  return rc ? rc : info;
-  });
-}
-
-int chol_laqsy_tile(int uplo, chol_desc_t *A, chol_desc_t *S, double scond, double amax, int *equed) {
-  return with_views({{A, true}, {S, false}}, [&]() -> int {
-  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "laqsy_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "laqsy_tile: uplo");
-  int rc = square_check("laqsy_tile", A, 2);
-  if (rc) return rc;
-  if ((rc = rhs_check("laqsy_tile", A, S, 3, "S"))) return rc;
-  if (S->ln != 1 || S->mat == A->mat) return fail(-3, "laqsy_tile: S must be an n x 1 descriptor of its own");
-  if (!(scond >= 0)) return fail(-4, "laqsy_tile: scond is negative or NaN");
-  if (!(amax >= 0)) return fail(-5, "laqsy_tile: amax is negative or NaN");
-  if (!equed) return fail(-6, "laqsy_tile: NULL equed");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  const int up = uplo == CHOL_UPPER;
-  return A->dtype == CHOL_REAL_DOUBLE ? laqsy_impl<double>(up, A, S, scond, amax, equed)
-                                      : laqsy_impl<float>(up, A, S, scond, amax, equed);
-  });
-}
-
-// the checks of porfs (apos: A's position; B, X follow AF)
-static int porfs_args(const char *what, chol_desc *A, chol_desc *AF, chol_desc *B, chol_desc *X, int apos, int bpos,
-                      int xpos) {
-  int rc = square_check(what, A, apos);
-  if (rc) return rc;
-  if ((rc = square_check(what, AF, apos + 1))) return rc;
-  char buf[160];
-  if (!same_geometry(A, AF) || AF->mat == A->mat) {
-    snprintf(buf, sizeof buf, "%s: AF must have A's shape, tile size and type, in storage of its own", what);
-    return fail(-(apos + 1), buf);
-  }
-  if ((rc = rhs_check(what, A, B, bpos, "B"))) return rc;
-  if ((rc = rhs_check(what, A, X, xpos, "X"))) return rc;
-  if (!same_geometry(B, X)) {
-    snprintf(buf, sizeof buf, "%s: X must have B's shape, tile size and type", what);
-    return fail(-xpos, buf);
-  }
-  if (X->mat == A->mat || X->mat == AF->mat || X->mat == B->mat || B->mat == A->mat || B->mat == AF->mat) {
-    snprintf(buf, sizeof buf, "%s: X aliases A, AF or B", what);
-    return fail(-xpos, buf);
-  }
-  if (!winv_fits(AF)) {  // (the wide steps solve with potrs_impl)
-    snprintf(buf, sizeof buf, "%s: tile size above 4096", what);
-    return fail(CHOL_ERR_NOT_SUPPORTED, buf);
-  }
-  return 0;
-}
-
-int chol_porfs_tile(int uplo, chol_desc_t *A, chol_desc_t *AF, chol_desc_t *B, chol_desc_t *X, double *ferr,
-                    double *berr) {
-  return with_views({{A, false}, {AF, false}, {B, false}, {X, true}}, [&]() -> int {
-  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "porfs_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "porfs_tile: uplo");
-  int rc = porfs_args("porfs_tile", A, AF, B, X, 2, 4, 5);
-  if (rc) return rc;
-  if (!ferr) return fail(-6, "porfs_tile: NULL ferr");
-  if (!berr) return fail(-7, "porfs_tile: NULL berr");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  const int up = uplo == CHOL_UPPER;
-  std::fill(g.rf_stats, g.rf_stats + 8, 0.0);
-  MxTimer tt;
-  if ((rc = tt.start())) return rc;
-  if (A->dtype == CHOL_REAL_DOUBLE) {
-    if (!(rc = stage_factor_diag<double>(AF, up, "porfs_tile")))
-      rc = porfs_impl<double>(up, A, AF, B, X, ferr, berr, g.rf_stats);
-  } else {
-    if (!(rc = stage_factor_diag<float>(AF, up, "porfs_tile")))
-      rc = porfs_impl<float>(up, A, AF, B, X, ferr, berr, g.rf_stats);
-  }
-  if (rc) return rc;
-  return tt.stop(&g.rf_stats[0]);
-  });
-}
-
-extern "C++" {
-template <typename T>
-static int posvx_impl(int fact, int upper, chol_desc *A, chol_desc *AF, int *equed, chol_desc *S, chol_desc *B,
-                      chol_desc *X, double *rcond, double *ferr, double *berr) {
-  hipStream_t s = g.r.st[ST_MAIN];
-  double *st = g.rf_stats;  // total, equilibrate + scale B, factor, lansy + pocon, solve, porfs, #sweep / #potrs columns
-  std::fill(st, st + 8, 0.0);
-  const long n = A->lm;
-  const int nrhs = B->ln, uplo = upper ? CHOL_UPPER : CHOL_LOWER;
-  MxTimer tt, tp;
-  int rc = tt.start();
-  if (rc) return rc;
-  bool rcequ = false;
-  double scond = 1;
-  if ((rc = tp.start())) return rc;
-  if (fact == CHOL_FACT_FACTORED) {
-    rcequ = *equed == 1;
-    if (rcequ && n > 0) {  // DPOSVX: scond from S itself
-      if (ensure_rf(7, diag_scan_part_bytes())) return cn_oom("posvx_tile");
-      double *part = reinterpret_cast<double *>(g.rf[7]);
-      launch_diag_scan<T>(s, geo_of(A), nullptr, reinterpret_cast<T *>(S->mat), 1, part);
-      std::vector<double> h(diag_scan_part_bytes() / sizeof(double));
-      HIPCHECK(hipMemcpyAsync(h.data(), part, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-      HIPCHECK(hipStreamSynchronize(s));
-      const long per = (n + 255) / 256;
-      T smin = T(INFINITY), smax = T(-INFINITY);
-      for (long w = 0; w < 256 && w * per < n; ++w) smin = std::min(smin, T(h[3 * w])), smax = std::max(smax, T(h[3 * w + 1]));
-      if (!(smin > T(0))) return fail(-6, "posvx_tile: S has an entry <= 0");
-      const T smlnum = T(Lam<T>::safmin), bignum = T(1) / smlnum;
-      scond = (double)(std::max(smin, smlnum) / std::min(smax, bignum));
-    }
-  } else {
-    *equed = 0;
-    if (fact == CHOL_FACT_EQUILIBRATE) {
-      int infequ = 0;
-      double amax = 0;
-      if ((rc = poequ_impl<T>(A, S, &scond, &amax, &infequ))) return rc;
-      if (infequ == 0) {
-        if ((rc = laqsy_impl<T>(upper, A, S, scond, amax, equed))) return rc;
-        rcequ = *equed == 1;
-      }
-    }
-  }
-  const TileGeo ga = geo_of(A), gx = geo_of(B);
-  if (rcequ) launch_row_scale<T>(s, gx, reinterpret_cast<T *>(B->mat), reinterpret_cast<const T *>(S->mat));
-  HIPCHECK(hipGetLastError());
-  if ((rc = tp.stop(&st[1]))) return rc;
-  if (fact != CHOL_FACT_FACTORED) {
-    if ((rc = tp.start())) return rc;
-    launch_lacpy<T>(s, ga, upper ? 2 : 1, reinterpret_cast<const T *>(A->mat), reinterpret_cast<T *>(AF->mat));
-    HIPCHECK(hipGetLastError());
-    const int info = potrf_run(uplo, AF);
-    if (info < 0) return info;
-    if ((rc = tp.stop(&st[2]))) return rc;
-    if (info > 0) {
-      *rcond = 0;
-      return tt.stop(&st[0]) ? CHOL_ERR_HIP : info;
-    }
-  }
-  // rcond: anorm = ||A||_1 of the (equilibrated) A, the estimate on AF's sweeps
-  if ((rc = tp.start())) return rc;
-  const size_t pb = lansy_part_bytes(ga);
-  if (ensure_cn(6, pb + 4 * sizeof(double))) return cn_oom("posvx_tile");
-  double *lpart = reinterpret_cast<double *>(g.cn[6]), *lres = lpart + pb / sizeof(double);
-  launch_lansy<T>(s, ga, upper, reinterpret_cast<const T *>(A->mat), lpart, lres);
-  double lv[3] = {0, 0, 0};
-  HIPCHECK(hipMemcpyAsync(lv, lres, sizeof lv, hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipStreamSynchronize(s));
-  if ((rc = stage_factor_diag<T>(AF, upper, "posvx_tile"))) return rc;
-  if ((rc = pocon_impl<T>(AF, upper, lv[1], rcond, /*staged=*/true))) return rc;
-  if ((rc = tp.stop(&st[3]))) return rc;
-  // X <- A^{-1} B: the sweeps on B's columns gathered into the R slots, or lacpy and potrs_impl when wide
-  if ((rc = tp.start())) return rc;
-  if (nrhs > 0 && n > 0) {
-    if (nrhs <= POSVX_KX) {
-      RfBufs<T> b;
-      if ((rc = rf_buffers<T>(ga, nrhs, &b, "posvx_tile"))) return rc;
-      std::vector<int> all(nrhs);
-      for (int j = 0; j < nrhs; ++j) all[j] = j;
-      const std::vector<VecCols> gr = groups_of<T>(all);
-      for (const VecCols &vc : gr) launch_gather<T>(s, gx, reinterpret_cast<const T *>(B->mat), vc, b.R);
-      if ((rc = apply_inv<T>(upper, AF, b, b.R, all, st))) return rc;
-      for (const VecCols &vc : gr) launch_scatter<T>(s, gx, reinterpret_cast<T *>(X->mat), vc, b.R, false);
-    } else {
-      launch_lacpy<T>(s, gx, 0, reinterpret_cast<const T *>(B->mat), reinterpret_cast<T *>(X->mat));
-      auto flip = [&]() { launch_transpose_inplace<T>(s, reinterpret_cast<T *>(AF->mat), AF->nt, AF->mbi); };
-      if (upper) flip();
-      rc = potrs_impl<T>(AF, X);
-      if (upper) flip();
-      if (rc) return rc;
-      st[7] += nrhs;
-    }
-    HIPCHECK(hipGetLastError());
-  }
-  if ((rc = tp.stop(&st[4]))) return rc;
-  if ((rc = porfs_impl<T>(upper, A, AF, B, X, ferr, berr, st))) return rc;
-  // the solution of the original system, its error bound
-  if (rcequ) {
-    launch_row_scale<T>(s, gx, reinterpret_cast<T *>(X->mat), reinterpret_cast<const T *>(S->mat));
-    HIPCHECK(hipGetLastError());
-    for (int j = 0; j < nrhs; ++j) ferr[j] = (double)(T(ferr[j]) / T(scond));
-  }
-  if ((rc = tt.stop(&st[0]))) return rc;
-  return *rcond < Lam<T>::eps ? (int)(n + 1) : 0;
-}
-}  // extern "C++"
-
-int chol_posvx_tile(int fact, int uplo, chol_desc_t *A, chol_desc_t *AF, int *equed, chol_desc_t *S, chol_desc_t *B,
-                    chol_desc_t *X, double *rcond, double *ferr, double *berr) {
-  return with_views({{A, true}, {AF, true}, {S, true}, {B, true}, {X, true}}, [&]() -> int {
-  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "posvx_tile before chol_init");
-  if (fact != CHOL_FACT_NONE && fact != CHOL_FACT_EQUILIBRATE && fact != CHOL_FACT_FACTORED)
-    return fail(-1, "posvx_tile: fact");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-2, "posvx_tile: uplo");
-  int rc = porfs_args("posvx_tile", A, AF, B, X, 3, 7, 8);
-  if (rc) return rc;
-  if (!equed) return fail(-5, "posvx_tile: NULL equed");
-  if (fact == CHOL_FACT_FACTORED && *equed != 0 && *equed != 1) return fail(-5, "posvx_tile: equed must be 0 or 1");
-  const bool need_s = fact == CHOL_FACT_EQUILIBRATE || (fact == CHOL_FACT_FACTORED && *equed == 1);
-  if (need_s || S) {
-    if ((rc = rhs_check("posvx_tile", A, S, 6, "S"))) return rc;
-    if (S->ln != 1 || S->mat == A->mat || S->mat == AF->mat || S->mat == B->mat || S->mat == X->mat)
-      return fail(-6, "posvx_tile: S must be an n x 1 descriptor of its own");
-  }
-  if (!rcond) return fail(-9, "posvx_tile: NULL rcond");
-  if (!ferr) return fail(-10, "posvx_tile: NULL ferr");
-  if (!berr) return fail(-11, "posvx_tile: NULL berr");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  const int up = uplo == CHOL_UPPER;
-  return A->dtype == CHOL_REAL_DOUBLE ? posvx_impl<double>(fact, up, A, AF, equed, S, B, X, rcond, ferr, berr)
-                                      : posvx_impl<float>(fact, up, A, AF, equed, S, B, X, rcond, ferr, berr);
-  });
-}
-
-// the parts of porfs alone, for scripts/posvx_time.py: path 0 the residual pass over X's columns (B = X), 1 one
-// application of A^{-1} to them by the multi-vector sweeps, 2 the same by potrs_impl; *ms <- the fastest of reps
-extern "C++" {
-template <typename T>
-static int bench_refine_impl(int upper, chol_desc *A, chol_desc *AF, chol_desc *X, int path, int reps, double *ms) {
-  hipStream_t s = g.r.st[ST_MAIN];
-  const TileGeo ga = geo_of(A), gx = geo_of(X);
-  const int k = X->ln;
-  RfBufs<T> b;
-  int rc = rf_buffers<T>(ga, k, &b, "bench_refine");
-  if (rc) return rc;
-  if ((rc = stage_factor_diag<T>(AF, upper, "bench_refine"))) return rc;
-  std::vector<int> all(k);
-  for (int j = 0; j < k; ++j) all[j] = j;
-  for (const VecCols &vc : groups_of<T>(all)) launch_gather<T>(s, gx, reinterpret_cast<const T *>(X->mat), vc, b.R);
-  double st[8] = {};
-  *ms = 1e30;
-  for (int r = 0; r <= reps; ++r) {
-    MxTimer tt;
-    if ((rc = tt.start())) return rc;
-    if (path == 0) {
-      for (const VecCols &vc : groups_of<T>(all))
-        launch_porfs_resid<T>(s, ga, upper, reinterpret_cast<const T *>(A->mat), gx, reinterpret_cast<const T *>(X->mat),
-                              reinterpret_cast<const T *>(X->mat), vc, b.part, b.R, b.F, Lam<T>::eps, 0.0, 0.0, b.berr);
-    } else {
-      if ((rc = apply_inv<T>(upper, AF, b, b.R, all, st, path))) return rc;
-    }
-    HIPCHECK(hipGetLastError());
-    double t = 0;
-    if ((rc = tt.stop(&t))) return rc;
-    if (r > 0) *ms = std::min(*ms, t);
-  }
-  return 0;
-}
-}  // extern "C++"
-
-int chol_bench_refine(int uplo, chol_desc_t *A, chol_desc_t *AF, chol_desc_t *X, int path, int reps, double *ms) {
-  return with_views({{A, false}, {AF, false}, {X, false}}, [&]() -> int {
-  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "bench_refine before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "bench_refine: uplo");
-  int rc = square_check("bench_refine", A, 2);
-  if (rc) return rc;
-  if ((rc = square_check("bench_refine", AF, 3))) return rc;
-  if ((rc = rhs_check("bench_refine", A, X, 4, "X"))) return rc;
-  if (path < 0 || path > 2 || reps < 1 || !ms) return fail(-5, "bench_refine: path, reps or ms");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  const int up = uplo == CHOL_UPPER;
-  return A->dtype == CHOL_REAL_DOUBLE ? bench_refine_impl<double>(up, A, AF, X, path, reps, ms)
-                                      : bench_refine_impl<float>(up, A, AF, X, path, reps, ms);
-  });
-}
-
-int chol_last_posvx_stats(double *out8) {
-  if (!g.inited) return fail(CHOL_ERR_NOT_INITIALIZED, "last_posvx_stats before chol_init");
-  if (!out8) return fail(-1, "last_posvx_stats: NULL");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  for (int i = 0; i < 8; ++i) out8[i] = g.rf_stats[i];
-  return 0;
 }
 
 // valid extent of tile (I,J) inside the matrix (edge tiles are smaller)
@@ -3221,7 +1820,7 @@ static int residual_common(chol_desc_t *L, double bump, unsigned long long seed,
     std::vector<double> hr(2 * (size_t)n);
     hipError_t e = hipMemcpy(hr.data(), rows, hr.size() * sizeof(double), hipMemcpyDeviceToHost);
     (void)hipFree(rows);
-    if (e != hipSuccess) return fail_hip(e, "residual row sums", __LINE__);
+    if (e != hipSuccess) return fail_hip(e, "residual row sums", __FILE__, __LINE__);
     double rmax = 0, amax = 0;
     for (long r = 0; r < n; ++r) {
       rmax = std::max(rmax, hr[r]);

@@ -1,0 +1,95 @@
+// What api.hip offers the host code of the routines that work from the factor (spd.hip): the context's state, the
+// error reporting, the descriptor rules, the view refresh and the Upper-through-Lower helpers.  Host only: only
+// api.hip and spd.hip include it (the kernel translation units see cholmi_internal.h alone).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <functional>
+#include <initializer_list>
+#include <mutex>
+
+#include "../../include/cholmi.h"
+#include "cholmi_internal.h"
+
+namespace cholmi {
+
+bool ctx_inited();
+std::recursive_mutex &ctx_mutex();  // one ABI call at a time on the context
+
+// record msg as chol_last_error's text and return code
+int fail(int code, const char *msg);
+int fail_hip(hipError_t e, const char *what, const char *file, int line);
+#define HIPCHECK(call)                                                           \
+  do {                                                                           \
+    hipError_t e_ = (call);                                                      \
+    if (e_ != hipSuccess) return cholmi::fail_hip(e_, #call, __FILE__, __LINE__); \
+  } while (0)
+// CHOL_ERR_OUT_OF_MEMORY with "<what>: scratch allocation failed" (the HIP error cleared)
+int scratch_failed(const char *what);
+
+inline int roundup(int x, int m) { return (x + m - 1) / m * m; }
+
+// N device buffers, each grown on demand (in whole MiB) and kept until release(); Zero: a buffer is cleared when it
+// grows.  One pool per set of buffers that are live together: two pools never share memory.
+template <int N, bool Zero = false>
+struct ScratchPool {
+  void *p[N] = {};
+  size_t bytes[N] = {};
+  // buffer i holds at least `need` bytes afterwards, or CHOL_ERR_OUT_OF_MEMORY (scratch_failed(what))
+  int ensure_bytes(int i, size_t need, const char *what) {
+    if (bytes[i] >= need) return 0;
+    if (p[i] && hipFree(p[i]) != hipSuccess) return scratch_failed(what);
+    p[i] = nullptr;
+    bytes[i] = 0;
+    need = (need + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
+    if (hipMalloc(&p[i], need) != hipSuccess || (Zero && hipMemset(p[i], 0, need) != hipSuccess))
+      return scratch_failed(what);
+    bytes[i] = need;
+    return 0;
+  }
+  template <typename T>
+  T *as(int i) const {
+    return reinterpret_cast<T *>(p[i]);
+  }
+  void release() {
+    for (int i = 0; i < N; ++i) {
+      if (p[i]) (void)hipFree(p[i]);
+      p[i] = nullptr;
+      bytes[i] = 0;
+    }
+  }
+};
+
+// One entry point's body between the refresh of its views' images and their write-back, all under the context
+// lock (recursive: the bodies take it again); a failed refresh returns before the body runs, a failed write-back
+// is reported unless the body already failed.  The write-back also follows a body that returned info > 0
+// (a partly factored matrix, as LAPACK leaves it).
+struct ViewArg {
+  chol_desc *d;
+  bool write_back;
+};
+int with_views(std::initializer_list<ViewArg> views, const std::function<int()> &body);
+
+// the descriptor rules of the whole-matrix routines
+int resident_whole(const char *what, const chol_desc *d);
+bool same_geometry(const chol_desc *a, const chol_desc *b);
+TileGeo geo_of(const chol_desc *d);
+
+// the context holds the inverses of at most 32 diagonal 128-blocks (tiles up to 4096): every entry
+// that factors, inverts or solves with a tile checks this before any launch writes winv
+bool winv_fits(const chol_desc *d);
+#define CHECK_WINV(d, what) \
+  if (!winv_fits(d)) return fail(CHOL_ERR_NOT_SUPPORTED, what ": tile size above 4096")
+void forget_winv(const void *ptr);  // (a tile that is overwritten: its cached block inverses are stale)
+
+// chol_potrf_tile after its argument checks, on the descriptor's image as it stands
+int potrf_run(int uplo, chol_desc *A);
+// the stored tiles of a square matrix transposed in place on ST_MAIN, by its dtype: ChamUpper (A = U^T U with
+// U = L^T) runs the Lower path between two of these
+void transpose_storage(chol_desc *A);
+
+// spd.hip: its scratch, freed by chol_finalize
+void spd_release();
+
+}  // namespace cholmi

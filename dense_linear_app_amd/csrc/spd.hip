@@ -1,0 +1,1269 @@
+// The SPD routines of libcholmi.so that work from a Cholesky factor (include/cholmi.h): the solve (potrs / posv), the
+// mixed-precision solve (dsposv), the inverse (trtri / potri / poinv), the condition estimate (lansy / pocon) and the
+// expert solve with error bounds (poequ / laqsy / porfs / posvx).  All run on the main stream of the context that
+// api.hip keeps (api_internal.h); this file owns only its scratch and the statistics of the last call.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <numeric>
+#include <vector>
+
+#include "api_internal.h"
+
+using namespace cholmi;
+
+namespace {
+
+// scratch, grown on demand and kept (one pool per set of buffers that are live together: porfs / posvx hold cn[0]
+// and rf while they call potrs_impl, which grows `work`):
+// potrs_impl's transposed right-hand sides and tiles
+ScratchPool<1> work;
+// chol_dsposv_tile's: the fp32 factor (n x n tile image), the fp32 right-hand side / correction (n x nrhs), the
+// residual's per-block partial sums, and the column maxima + overflow flag
+ScratchPool<4, true> mx;
+// chol_trtri_tile / chol_potri_tile's: the products' Y blocks (then potri's LAUUM image), the 128 x 128 inverses of
+// every diagonal tile's diagonal blocks, a staged copy of a single tile whose edge is not a multiple of 128, and the
+// zero-pivot word
+ScratchPool<4> iv;
+// chol_lansy_tile / chol_pocon_tile's: the staged and inverted diagonal tiles, the 128 x 128 inverses of their
+// diagonal blocks, the products' Y blocks, the sweeps' vectors and partials, the sign vector, the statistics, lansy's
+// per-block partials
+ScratchPool<7> cn;
+// chol_porfs_tile / chol_posvx_tile's: one condest-layout vector per column for the residuals / estimator, the FERR
+// weights and the signs, the residual partials, the sweeps' scratch, the backward errors and statistics, potrs's
+// n x k image, poequ's partials
+ScratchPool<8, true> rf;
+double mx_stats[8] = {};  // of the last chol_dsposv_tile (chol_last_dsposv_stats)
+double cn_stats[4] = {};  // of the last chol_pocon_tile (chol_last_pocon_stats)
+double rf_stats[8] = {};  // of the last chol_posvx_tile / chol_porfs_tile (chol_last_posvx_stats)
+
+hipStream_t main_stream() { return main_rank_ctx()->st[ST_MAIN]; }
+
+// The time between two events on the main stream, added to a statistic; the events are made on first use
+struct EventTimer {
+  hipEvent_t e[2] = {nullptr, nullptr};
+  ~EventTimer() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+  int start() {
+    for (hipEvent_t &x : e)
+      if (!x) HIPCHECK(hipEventCreate(&x));
+    HIPCHECK(hipEventRecord(e[0], main_stream()));
+    return 0;
+  }
+  int mark() {
+    HIPCHECK(hipEventRecord(e[1], main_stream()));
+    return 0;
+  }
+  int add(double *acc) {  // (after the end mark has run)
+    float ms = 0;
+    HIPCHECK(hipEventElapsedTime(&ms, e[0], e[1]));
+    *acc += ms;
+    return 0;
+  }
+  int stop(double *acc) {  // (the phases end with a stream synchronisation of their own or are followed by one)
+    if (int rc = mark()) return rc;
+    HIPCHECK(hipEventSynchronize(e[1]));
+    return add(acc);
+  }
+};
+
+// ---------------------------------------------------------------- solve with the factor
+// X <- A^{-1} B for A = L L^T already factored (CHAMELEON_dpotrs_Tile(ChamLower, A, B)).
+// The kernels of this library are the right-sided NT forms the factorisation needs
+// (X = A L^{-T}, C -= A B^T), so the solve runs on Z = B^T:
+//   forward   Z(:,k) <- Z(:,k) L(k,k)^{-T};  Z(:,i) -= Z(:,k) L(i,k)^T, i > k      (L Y = B)
+//   backward  Z(:,k) <- Z(:,k) L(k,k)^{-1};  Z(:,i) -= Z(:,k) L(k,i),   i < k      (L^T X = Y)
+// the backward sweep's operands being transposed tiles (L(k,k)^{-T} from a TRSM of the identity,
+// L(k,i)^T from a tile transpose) so that every product is again A B^T.
+template <typename T>
+int potrs_impl(chol_desc *A, chol_desc *B) {
+  const int nt = A->nt, nr = B->nt, mb = A->mbi;
+  const long bs = A->bsizi;
+  const size_t tb = (size_t)bs * sizeof(T);
+  T *La = reinterpret_cast<T *>(A->mat), *Bm = reinterpret_cast<T *>(B->mat);
+  if (int rc = work.ensure_bytes(0, ((size_t)nr * nt + 2 + (size_t)nr + (size_t)nt) * tb, "potrs_tile")) return rc;
+  T *scr = work.as<T>(0);
+  T *Z = scr, *Wt = scr + (size_t)nr * nt * bs, *Tt = Wt + bs, *tmp = Tt + (size_t)nt * bs;  // Tt: nt tiles, tmp: nr tiles
+  hipStream_t s = main_stream();
+  T *winv = reinterpret_cast<T *>(main_rank_ctx()->winv);
+  auto Ltile = [&](int i, int j) { return La + ((long)i + (long)j * A->lmt) * bs; };
+  auto Ztile = [&](int r, int i) { return Z + ((long)r + (long)i * nr) * bs; };
+  // Z(r,i) = B(i,r)^T
+  for (int r = 0; r < nr; ++r)
+    launch_tiles_transpose<T>(s, Bm + (long)r * B->lmt * bs, bs, Ztile(r, 0), (long)nr * bs, mb, nt);
+  for (int k = 0; k < nt; ++k) {  // forward
+    launch_invert_diag<T>(s, Ltile(k, k), mb, winv);
+    launch_trsm_panel<T>(s, Ztile(0, k), bs, nr, Ltile(k, k), winv, mb, T(1));
+    // Z(r,i) -= Z(r,k) L(i,k)^T for every r and i > k: one launch
+    launch_gemm_nt_batch<T>(s, Ztile(0, k), bs, nr, Ltile(k + 1, k), bs, nt - 1 - k, Ztile(0, k + 1), bs, (long)nr * bs, mb,
+                            T(-1), T(1));
+  }
+  for (int k = nt - 1; k >= 0; --k) {  // backward
+    HIPCHECK(hipMemsetAsync(Wt, 0, tb, s));
+    launch_pad_identity<T>(s, Wt, 0, mb);
+    launch_invert_diag<T>(s, Ltile(k, k), mb, winv);
+    launch_trsm_panel<T>(s, Wt, bs, 1, Ltile(k, k), winv, mb, T(1));  // Wt = L(k,k)^{-T}
+    // Z(r,k) <- Z(r,k) L(k,k)^{-1} for every r (out of place, then back: the tiles of a column are contiguous)
+    launch_gemm_nt_batch<T>(s, Ztile(0, k), bs, nr, Wt, 0, 1, tmp, bs, 0, mb, T(1), T(0));
+    HIPCHECK(hipMemcpyAsync(Ztile(0, k), tmp, (size_t)nr * tb, hipMemcpyDeviceToDevice, s));
+    // Z(r,i) -= Z(r,k) L(k,i) for every r and i < k: the k tiles L(k,i)^T in one transpose launch, one product launch
+    if (k > 0) {
+      launch_tiles_transpose<T>(s, Ltile(k, 0), (long)A->lmt * bs, Tt, bs, mb, k);
+      launch_gemm_nt_batch<T>(s, Ztile(0, k), bs, nr, Tt, bs, k, Ztile(0, 0), bs, (long)nr * bs, mb, T(-1), T(1));
+    }
+  }
+  for (int r = 0; r < nr; ++r)  // B(i,r) = Z(r,i)^T
+    launch_tiles_transpose<T>(s, Ztile(r, 0), (long)nr * bs, Bm + (long)r * B->lmt * bs, bs, mb, nt);
+  HIPCHECK(hipGetLastError());  // (a refused launch configuration must not come back as a wrong solution)
+  HIPCHECK(hipStreamSynchronize(s));
+  return 0;
+}
+
+// potrs_impl for either orientation of the factor: ChamUpper (A = U^T U with U = L^T) transposes the factor's storage
+// in place around the Lower solve; the strict lower triangle comes back as it was.  No synchronisation after the
+// second transpose: the caller's next work on the stream follows it.
+template <typename T>
+int potrs_uplo(int upper, chol_desc *A, chol_desc *B) {
+  if (upper) transpose_storage(A);
+  const int rc = potrs_impl<T>(A, B);
+  if (upper) transpose_storage(A);
+  return rc;
+}
+
+// ---------------------------------------------------------------- mixed-precision solve (LAPACK DSPOSV)
+// Factor an fp32 copy of A, solve in fp32, refine X in fp64 with residuals R = B - A X read from the stored triangle
+// (mixed.hip) until every column satisfies max|R(:,j)| <= max|X(:,j)| anrm eps sqrt(n); A and B are only read.
+// *iter < 0 (no convergence, an entry that does not fit in fp32, fp32 factor not SPD): X <- B and dposv on A, X.
+constexpr int DSPOSV_ITMAX = 30;
+
+// -> *iter (>= 0: refinement steps; or -2 / -3 / -31 for the fallback), or a negative status
+int dsposv_mixed(int uplo, chol_desc *A, chol_desc *B, chol_desc *X, int *iter) {
+  hipStream_t s = main_stream();
+  const int up = uplo == CHOL_UPPER ? 1 : 0, nrhs = B->ln;
+  const TileGeo ga = geo_of(A), gx = geo_of(B);
+  double *st = mx_stats;  // total, conversions + norm, fp32 factor, fp32 solves, residual passes, #solves, #passes, -
+  std::fill(st, st + 8, 0.0);
+  const size_t rf_bytes = (size_t)B->lmt * B->lnt * B->bsizi * sizeof(float);
+  const char *what = "dsposv_tile";
+  int rc = mx.ensure_bytes(0, (size_t)A->lmt * A->lnt * A->bsizi * sizeof(float), what);
+  if (!rc) rc = mx.ensure_bytes(1, rf_bytes, what);
+  if (!rc) rc = mx.ensure_bytes(2, sym_resid_part_bytes(ga, nrhs), what);
+  if (!rc) rc = mx.ensure_bytes(3, (size_t)(2 * nrhs + 2) * sizeof(unsigned long long), what);
+  if (rc) return rc;
+  float *Af = mx.as<float>(0), *Rf = mx.as<float>(1);
+  double *part = mx.as<double>(2);
+  unsigned long long *colmax = mx.as<unsigned long long>(3);
+  int *flag = reinterpret_cast<int *>(colmax + 2 * nrhs);
+  std::vector<unsigned long long> hmax(2 * nrhs + 1);
+  // fp32 descriptors over the scratch: A's and B's geometry (and A's work list)
+  chol_desc Ad = *A, Rd = *B;
+  Ad.dtype = Rd.dtype = CHOL_REAL_FLOAT;
+  Ad.esize = Rd.esize = sizeof(float);
+  Ad.mat = Af;
+  Rd.mat = Rf;
+  Ad.owns = Rd.owns = false;
+  Ad.version = Rd.version = 0;
+  Rd.d_list = nullptr;
+  EventTimer tt, tp;
+  if ((rc = tt.start())) return rc;
+  // anrm, then B and A to fp32 (-2 where an entry does not fit)
+  if ((rc = tp.start())) return rc;
+  HIPCHECK(hipMemsetAsync(colmax, 0, (2 * nrhs + 2) * sizeof(unsigned long long), s));
+  HIPCHECK(hipMemsetAsync(Rf, 0, rf_bytes, s));  // (the solve runs on whole tiles: padding must be finite)
+  launch_sym_inf_norm(s, ga, up, (const double *)A->mat, part, colmax);
+  launch_vec_to_f32(s, gx, (const double *)B->mat, Rf, flag);
+  launch_sym_to_f32(s, ga, up, (const double *)A->mat, Af, flag);
+  HIPCHECK(hipGetLastError());
+  unsigned long long anrm_bits = 0;
+  int hflag = 0;
+  HIPCHECK(hipMemcpyAsync(&anrm_bits, colmax, sizeof anrm_bits, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(&hflag, flag, sizeof hflag, hipMemcpyDeviceToHost, s));
+  if ((rc = tp.stop(&st[1]))) return rc;
+  double anrm;
+  memcpy(&anrm, &anrm_bits, sizeof anrm);
+  const double cte = anrm * std::ldexp(1.0, -53) * std::sqrt((double)A->lm);
+  auto finish = [&](int it) {
+    *iter = it;
+    return tt.stop(&st[0]);
+  };
+  if (hflag) return finish(-2);
+  // the fp32 factor: info > 0 -> -3; an error (CHOL_ERR_DEVICE_WAIT, HIP) is returned as it is
+  if ((rc = tp.start())) return rc;
+  rc = potrf_run(CHOL_LOWER, &Ad);
+  if (rc < 0) return rc;
+  if (int r2 = tp.stop(&st[2])) return r2;
+  if (rc > 0) return finish(-3);
+  auto solve = [&]() -> int {  // Rf <- A^{-1} Rf in fp32
+    int r = tp.start();
+    if (!r) r = potrs_impl<float>(&Ad, &Rd);
+    if (!r) r = tp.stop(&st[3]);
+    st[5] += 1;
+    return r;
+  };
+  if ((rc = solve())) return rc;
+  launch_vec_update(s, gx, Rf, (double *)X->mat, /*assign=*/true);
+  for (int it = 0;; ++it) {
+    // R = B - A X in fp64, rounded into Rf; the column maxima of R and X
+    if ((rc = tp.start())) return rc;
+    HIPCHECK(hipMemsetAsync(colmax, 0, (2 * nrhs + 2) * sizeof(unsigned long long), s));
+    launch_sym_resid(s, ga, up, (const double *)A->mat, gx, (const double *)X->mat, (const double *)B->mat, part, Rf,
+                     colmax, flag);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(hmax.data(), colmax, (2 * nrhs + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if ((rc = tp.stop(&st[4]))) return rc;
+    st[6] += 1;
+    bool done = true;
+    for (int j = 0; j < nrhs && done; ++j) {
+      double rn, xn;
+      memcpy(&rn, &hmax[j], sizeof rn);
+      memcpy(&xn, &hmax[nrhs + j], sizeof xn);
+      done = rn <= xn * cte;  // (a NaN residual does not converge)
+    }
+    if (done) return finish(it);
+    if (it == DSPOSV_ITMAX) return finish(-DSPOSV_ITMAX - 1);
+    if (hmax[2 * nrhs] & 0xffffffffull) return finish(-2);  // (the flag: the low word on a little-endian device)
+    if ((rc = solve())) return rc;
+    launch_vec_update(s, gx, Rf, (double *)X->mat, /*assign=*/false);
+  }
+}
+
+// ---------------------------------------------------------------- inverse from the factor (LAPACK DTRTRI / DPOTRI)
+// X = L^{-1} in place over the lower tiles (inverse.hip: the 128-blocks of every diagonal tile, then the tiles, each
+// level column by column from the right), then for potri X^T X into the lower triangle (verify_ops.hip's LAUUM).
+// ChamUpper flips the storage around the Lower path, as potrf and potrs do.  A stored image whose padding is the
+// identity (a ragged order, a tile edge that is not a multiple of 128) is inverted as a whole: its padding stays the
+// identity and its matrix part is the inverse of the caller's matrix.
+template <typename T>
+struct InvImg {  // nt x nt tiles of mbs x mbs (mbs % 128 == 0), tile (i,j) at p + (i + j lmt) mbs^2
+  T *p;
+  int nt, lmt, mbs;
+};
+
+template <typename T>
+int trtri_img(const InvImg<T> &A) {
+  hipStream_t s = main_stream();
+  const int nt = A.nt, mb = A.mbs, nbm = mb / MACRO;
+  const long bs = (long)mb * mb, tstride = (long)(A.lmt + 1) * bs, blk = (long)MACRO * MACRO;
+  // Y: nt tiles (tile level) or nt * nbm blocks (inner level); the 128 x 128 inverses of every diagonal tile
+  if (int rc = iv.ensure_bytes(0, (size_t)nt * bs * sizeof(T), "trtri_tile")) return rc;
+  if (int rc = iv.ensure_bytes(1, (size_t)nt * nbm * blk * sizeof(T), "trtri_tile")) return rc;
+  T *Y = iv.as<T>(0), *W = iv.as<T>(1);
+  launch_invert_diag_batch<T>(s, A.p, tstride, nt, mb, W);
+  // the diagonal tiles, all at once: blocks (i,j) of tile z at p + z tstride + i 128 + j 128 mb
+  const TriLevel<T> in{A.p, MACRO, (long)MACRO * mb, tstride, mb, W, blk, nbm * blk, MACRO, Y, blk, nbm * blk, MACRO};
+  for (int c = nbm - 2; c >= 0; --c) launch_tri_column<T>(s, in, nbm, nt, c);
+  launch_tri_put_diag<T>(s, A.p, tstride, mb, nt, W);
+  // the tiles below the diagonal
+  const TriLevel<T> top{A.p, bs, (long)A.lmt * bs, 0, mb, A.p, tstride, 0, mb, Y, bs, 0, mb};
+  for (int c = nt - 2; c >= 0; --c) launch_tri_column<T>(s, top, nt, 1, c);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// lower triangle of A <- X^T X, X the lower triangle of A (padding included: the identity stays)
+template <typename T>
+int lauum_img(const InvImg<T> &A) {
+  hipStream_t s = main_stream();
+  if (int rc = iv.ensure_bytes(0, (size_t)A.nt * A.nt * A.mbs * A.mbs * sizeof(T), "potri_tile")) return rc;
+  T *out = iv.as<T>(0);
+  launch_lauum_lower<T>(s, A.p, out, A.nt, A.mbs);
+  TileGeo ge;
+  ge.lmt = ge.lnt = A.nt;
+  ge.mbs = ge.mbu = A.mbs;
+  ge.m = ge.n = (long)A.nt * A.mbs;
+  launch_lacpy<T>(s, ge, 1, out, A.p);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// A (Lower orientation, already checked) <- L^{-1}, or inv(L L^T) for potri
+template <typename T>
+int inverse_impl(chol_desc *A, bool potri) {
+  hipStream_t s = main_stream();
+  forget_winv(A->mat);  // (A is overwritten)
+  // potri: its LAUUM image first (trtri's Y blocks fit in it): no scratch is reallocated between the launches
+  const int ep = roundup(A->mbi, MACRO), nt = A->mbi % MACRO ? 1 : A->nt;
+  if (potri) {
+    if (int rc = iv.ensure_bytes(0, (size_t)nt * nt * ep * ep * sizeof(T), "potri_tile")) return rc;
+  }
+  if (A->mbi % MACRO == 0) {
+    const InvImg<T> im{reinterpret_cast<T *>(A->mat), A->nt, A->lmt, A->mbi};
+    int rc = trtri_img<T>(im);
+    if (!rc && potri) rc = lauum_img<T>(im);
+    if (rc) return rc;
+    HIPCHECK(hipStreamSynchronize(s));
+    return 0;
+  }
+  // a single tile whose edge is an odd multiple of 64: staged into a multiple of 128 with the identity beyond it
+  const int e = A->mbi;
+  if (int rc = iv.ensure_bytes(2, (size_t)ep * ep * sizeof(T), "trtri_tile")) return rc;
+  T *S = iv.as<T>(2);
+  HIPCHECK(hipMemsetAsync(S, 0, (size_t)ep * ep * sizeof(T), s));
+  HIPCHECK(hipMemcpy2DAsync(S, (size_t)ep * sizeof(T), A->mat, (size_t)e * sizeof(T), (size_t)e * sizeof(T), e,
+                            hipMemcpyDeviceToDevice, s));
+  launch_pad_identity<T>(s, S, e, ep);
+  const InvImg<T> im{S, 1, 1, ep};
+  int rc = trtri_img<T>(im);
+  if (!rc && potri) rc = lauum_img<T>(im);
+  if (rc) return rc;
+  // (the strict upper triangle goes back as it came: no kernel writes it)
+  HIPCHECK(hipMemcpy2DAsync(A->mat, (size_t)e * sizeof(T), S, (size_t)ep * sizeof(T), (size_t)e * sizeof(T), e,
+                            hipMemcpyDeviceToDevice, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  return 0;
+}
+
+// the descriptor rules of chol_trtri_tile / chol_potri_tile / chol_poinv_tile (apos: A's argument position)
+int inverse_check(const char *what, chol_desc *A, int apos) {
+  int rc = resident_whole(what, A);
+  if (rc) return rc;
+  char buf[160];
+  if (A->mt != A->nt || A->lm != A->ln) {
+    snprintf(buf, sizeof buf, "%s: A is not square", what);
+    return fail(-apos, buf);
+  }
+  if (A->mbi % 64) {
+    snprintf(buf, sizeof buf, "%s: stored tile edge must be a multiple of 64", what);
+    return fail(CHOL_ERR_NOT_SUPPORTED, buf);
+  }
+  return 0;
+}
+
+// the first exact zero on the diagonal (1-based), or 0; read before anything is written
+template <typename T>
+int diag_zero(const chol_desc *A, int *info) {
+  hipStream_t s = main_stream();
+  if (int rc = iv.ensure_bytes(3, sizeof(int), "trtri_tile")) return rc;
+  int *first = iv.as<int>(3);
+  launch_diag_zero<T>(s, reinterpret_cast<const T *>(A->mat), (long)(A->lmt + 1) * A->bsizi, A->mbi, A->mb, A->lm, first);
+  HIPCHECK(hipGetLastError());
+  int v = 0;
+  HIPCHECK(hipMemcpyAsync(&v, first, sizeof v, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  *info = v <= A->lm ? v : 0;
+  return 0;
+}
+
+int inverse_run(int uplo, chol_desc *A, bool potri) {
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  const bool dbl = A->dtype == CHOL_REAL_DOUBLE;
+  int info = 0;
+  int rc = dbl ? diag_zero<double>(A, &info) : diag_zero<float>(A, &info);
+  if (rc) return rc;
+  if (info) return info;  // (LAPACK: A is unchanged)
+  // ChamUpper: U = L^T; inv(U) = inv(L)^T and inv(U^T U) = inv(L L^T) -- the Lower path on the transposed storage
+  if (uplo == CHOL_UPPER) transpose_storage(A);
+  rc = dbl ? inverse_impl<double>(A, potri) : inverse_impl<float>(A, potri);
+  if (uplo == CHOL_UPPER) {
+    transpose_storage(A);
+    HIPCHECK(hipStreamSynchronize(main_stream()));
+  }
+  return rc;
+}
+
+// ---------------------------------------------------------------- condition estimate (LAPACK DLANSY / DPOCON)
+// lansy: one pass over the stored triangle (condest.hip).  pocon: LAPACK DLACN2's state machine on the host, which
+// reads back six scalars after each application of A^{-1}; the applications (two narrow triangular sweeps over the
+// stored triangle) and every operation on an N-vector run on the device (condest.hip).
+
+// v <- the max, the one (= inf) norm and the sum of squares of the stored triangle
+template <typename T>
+int lansy_impl(const chol_desc *A, int upper, const char *what, double v[3]) {
+  hipStream_t s = main_stream();
+  const TileGeo ge = geo_of(A);
+  const size_t pb = lansy_part_bytes(ge);
+  if (int rc = cn.ensure_bytes(6, pb + 4 * sizeof(double), what)) return rc;
+  double *part = cn.as<double>(6), *res = part + pb / sizeof(double);
+  launch_lansy<T>(s, ge, upper, reinterpret_cast<const T *>(A->mat), part, res);
+  HIPCHECK(hipGetLastError());
+  v[0] = v[1] = v[2] = 0;  // (the max and the row-sum max are the bits of non-negative doubles: read as doubles)
+  HIPCHECK(hipMemcpyAsync(v, res, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  return 0;
+}
+
+// LAPACK DLACN2's control flow for one vector (Higham's estimator, as LAPACK has it): what the device does before the
+// next application of the operator (fill x: -1 nothing, 0 1/n, 1 e_j, 2 the alternating-sign vector; kase 1 / 2), the
+// statistics after it (condest.hip: launch_vec_stats with `sign`, `jlast`), and the estimate.  pocon applies A^{-1}
+// for both kases; porfs applies diag(W) A^{-1} (kase 1) and A^{-1} diag(W) (kase 2).
+struct Lacn2 {
+  static constexpr int ITMAX = 5;
+  long n = 0;
+  int isave = 0, iter = 0;
+  long j = 0;
+  double est = 0;
+  bool done = false, finite = true;
+  int fill = 0, kase = 1, sign = 1;
+  long fill_j = 0, jlast = -1;
+  void next(int isave_, int fill_, long fill_j_, int kase_, int sign_, long jlast_) {
+    isave = isave_, fill = fill_, fill_j = fill_j_, kase = kase_, sign = sign_, jlast = jlast_;
+  }
+  void start(long n_) {
+    n = n_, iter = 0, j = 0, est = 0, done = false, finite = true;
+    next(1, 0, 0, 1, 1, -1);  // x = 1/n; after it est = ||x||_1, x = isgn = sign(x)
+  }
+  // st: launch_vec_stats' out[0..5] after the application (sum |x|, max |x|, its index, non-finite, x[jlast], changed)
+  template <typename T>
+  void take(const double *st) {
+    if (st[3] != 0) {  // (no dlatrs scaling: a non-finite entry ends the estimate)
+      finite = false;
+      done = true;
+      return;
+    }
+    switch (isave) {
+      case 1:
+        est = st[0];
+        if (n <= 1) {
+          done = true;
+          return;
+        }
+        return next(2, -1, 0, 2, 0, -1);  // then j = idamax(x)
+      case 2:
+        j = (long)st[2];
+        iter = 2;
+        return next(3, 1, j, 1, 1, -1);  // x = e_j; then est = ||x||_1, x = isgn = sign(x), changed?
+      case 3: {
+        const double estold = est;
+        est = st[0];
+        if (st[5] == 0 || est <= estold) break;  // a repeated sign vector, or no increase: converged
+        return next(4, -1, 0, 2, 0, j);          // then j = idamax(x), x(jlast) against |x(j)|
+      }
+      case 4:
+        if (st[4] != st[1] && iter < ITMAX) {
+          ++iter;
+          j = (long)st[2];
+          return next(3, 1, j, 1, 1, -1);
+        }
+        break;
+      default: {  // 5: the alternating-sign test vector
+        const T temp = T(2) * (T(st[0]) / T(3 * n));
+        if ((double)temp > est) est = (double)temp;
+        done = true;
+        return;
+      }
+    }
+    next(5, 2, 0, 1, 0, -1);
+  }
+};
+
+// the diagonal tiles of the factor, inverted once per call: their 128-blocks (as potrs), then the tiles (trtri's inner
+// level), into cn[0]
+template <typename T>
+int stage_factor_diag(chol_desc *A, int upper, const char *what) {
+  hipStream_t s = main_stream();
+  const TileGeo ge = geo_of(A);
+  const int E = condest_edge(ge), nbm = E / MACRO, nt = A->nt;
+  const long blk = (long)MACRO * MACRO;
+  int rc = cn.ensure_bytes(0, (size_t)nt * E * E * sizeof(T), what);
+  if (!rc) rc = cn.ensure_bytes(1, (size_t)nt * nbm * blk * sizeof(T), what);
+  if (!rc) rc = cn.ensure_bytes(2, (size_t)nt * nbm * blk * sizeof(T), what);
+  if (rc) return rc;
+  T *Dv = cn.as<T>(0), *W = cn.as<T>(1), *Y = cn.as<T>(2);
+  launch_stage_diag<T>(s, ge, upper, reinterpret_cast<const T *>(A->mat), Dv);
+  launch_invert_diag_batch<T>(s, Dv, (long)E * E, nt, E, W);
+  const TriLevel<T> in{Dv, MACRO, (long)MACRO * E, (long)E * E, E, W, blk, nbm * blk, MACRO, Y, blk, nbm * blk, MACRO};
+  for (int c = nbm - 2; c >= 0; --c) launch_tri_column<T>(s, in, nbm, nt, c);
+  launch_tri_put_diag<T>(s, Dv, (long)E * E, E, nt, W);
+  HIPCHECK(hipGetLastError());
+  return 0;
+}
+
+// staged: cn[0] already holds the inverted diagonal tiles of this factor (posvx)
+template <typename T>
+int pocon_impl(chol_desc *A, int upper, double anorm, double *rcond, bool staged = false) {
+  hipStream_t s = main_stream();
+  const TileGeo ge = geo_of(A);
+  const long n = A->lm;
+  for (double &v : cn_stats) v = 0;
+  *rcond = 0;
+  if (n == 0) {
+    *rcond = 1;
+    return 0;
+  }
+  if (anorm == 0 || std::isinf(anorm)) return 0;
+  EventTimer tt, tsweep;  // the whole call; each application (read after the synchronisation that follows it)
+  int rc = tt.start();
+  if (rc) return rc;
+  int info = 0;
+  rc = diag_zero<T>(A, &info);
+  if (rc) return rc;
+  if (info) return 0;  // a zero on the factor's diagonal: rcond = 0, no sweep
+  // scratch: the diagonal tiles, their 128-block inverses, the products' Y blocks (stage_factor_diag), the vectors,
+  // the sign vector, the statistics
+  const int E = condest_edge(ge), nt = A->nt, bpt = E / MACRO;
+  const long NB = (long)nt * bpt;
+  const size_t nv = condest_vec_elems(ge), npg = 2 * (size_t)NB * bpt * MACRO, npd = (size_t)bpt * bpt * MACRO;
+  if (!staged && (rc = stage_factor_diag<T>(A, upper, "pocon_tile"))) return rc;
+  rc = cn.ensure_bytes(3, (2 * nv + npg + npd) * sizeof(T), "pocon_tile");
+  if (!rc) rc = cn.ensure_bytes(4, nv * sizeof(int), "pocon_tile");
+  if (!rc) rc = cn.ensure_bytes(5, vec_stats_part_bytes() + 8 * sizeof(double), "pocon_tile");
+  if (rc) return rc;
+  const T *Dv = cn.as<const T>(0);
+  T *vx = cn.as<T>(3);
+  const SweepBufs<T> bufs{vx, vx + nv, vx + 2 * nv, vx + 2 * nv + npg};
+  int *isgn = cn.as<int>(4);
+  double *spart = cn.as<double>(5), *sout = spart + vec_stats_part_bytes() / sizeof(double);
+  const T *Am = reinterpret_cast<const T *>(A->mat);
+  int apps = 0;
+  double sweep_ms = 0, st[6] = {0, 0, 0, 0, 0, 0};
+  // x <- A^{-1} x, then the statistics of x (DLACN2's kase != 0 round trip)
+  auto apply = [&](int sign, long jlast) -> int {
+    if (int r = tsweep.start()) return r;
+    launch_sweep<T>(s, ge, upper, Am, Dv, bufs);
+    if (int r = tsweep.mark()) return r;
+    launch_vec_stats<T>(s, ge, bufs.x, isgn, sign, jlast, spart, sout);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(st, sout, sizeof st, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    if (int r = tsweep.add(&sweep_ms)) return r;
+    ++apps;
+    return 0;
+  };
+  // DLACN2; A is symmetric, so kase 1 and kase 2 apply the same A^{-1}
+  Lacn2 est;
+  est.start(n);
+  while (!est.done) {
+    if (est.fill >= 0) launch_vec_fill<T>(s, ge, bufs.x, est.fill, est.fill_j);
+    if ((rc = apply(est.sign, est.jlast))) return rc;
+    est.take<T>(st);
+  }
+  // (no dlatrs scaling: a sweep that overflows gives rcond = 0)
+  if (est.finite && est.est != 0) *rcond = (1.0 / est.est) / anorm;
+  if ((rc = tt.stop(&cn_stats[0]))) return rc;
+  cn_stats[1] = sweep_ms;
+  cn_stats[2] = apps;
+  return 0;
+}
+
+// ---------------------------------------------------------------- the SPD expert solve (LAPACK DPOEQU, DLAQSY, DPORFS, DPOSVX)
+// poequ / laqsy: one pass over the diagonal / the stored triangle (refine.hip).  porfs: every column in lockstep, each
+// with its own refinement count, lstres and DLACN2 state; each step applies A^{-1} only to the columns still active,
+// either with the multi-vector sweeps (at most K_X columns: ceil(k / 8) sweeps of up to 8 vectors) or with potrs_impl
+// on a scratch n x k image (wider steps).  posvx composes them in DPOSVX's order.
+
+// the widest application of A^{-1} that runs as multi-vector sweeps; wider ones go through potrs_impl.  Measured
+// crossover: about 47 columns at N = 65536 / 1024, about 30 at 16384 / 512
+constexpr int POSVX_KX = 40;
+constexpr int PORFS_ITMAX = 5;
+
+template <typename T>
+struct Lam;  // LAPACK xLAMCH: 'E'psilon (rounding), 'S'afe minimum, 'P'recision = eps * base
+template <>
+struct Lam<double> {
+  static constexpr double eps = 0x1p-53, safmin = 0x1p-1022, prec = 0x1p-52;
+};
+template <>
+struct Lam<float> {
+  static constexpr double eps = 0x1p-24, safmin = 0x1p-126, prec = 0x1p-23;
+};
+
+// porfs / posvx's scratch (rf): the residual / estimator vectors, the FERR weights, the sign vectors (one
+// condest-layout vector per column each), the residual partials, the sweeps' scratch and padding vectors, the
+// backward errors and statistics, and the n x k image of the potrs path
+template <typename T>
+struct RfBufs {
+  T *R, *F, *part, *sw, *pad;
+  int *isgn;
+  unsigned long long *berr;
+  double *spart, *sout;
+  long nv;
+};
+
+template <typename T>
+int rf_buffers(const TileGeo &ga, int nrhs, RfBufs<T> *b, const char *what) {
+  const long nv = (long)condest_vec_elems(ga);
+  const size_t vb = (size_t)nrhs * nv * sizeof(T);
+  const size_t sb = vec_stats_part_bytes() + (size_t)(nrhs + 1) * 8 * sizeof(double);
+  int rc = rf.ensure_bytes(0, vb, what);
+  if (!rc) rc = rf.ensure_bytes(1, vb, what);
+  if (!rc) rc = rf.ensure_bytes(2, (size_t)nrhs * nv * sizeof(int), what);
+  if (!rc) rc = rf.ensure_bytes(3, porfs_part_elems(ga, refine_width(std::min(nrhs, 8))) * sizeof(T), what);
+  if (!rc) rc = rf.ensure_bytes(4, (msweep_scratch_elems(ga) + 8 * (size_t)nv) * sizeof(T), what);
+  if (!rc) rc = rf.ensure_bytes(5, (size_t)nrhs * sizeof(unsigned long long) + sb, what);
+  if (rc) return rc;
+  b->nv = nv;
+  b->R = rf.as<T>(0);
+  b->F = rf.as<T>(1);
+  b->isgn = rf.as<int>(2);
+  b->part = rf.as<T>(3);
+  b->sw = rf.as<T>(4);
+  b->pad = b->sw + msweep_scratch_elems(ga);
+  b->berr = rf.as<unsigned long long>(5);
+  b->spart = reinterpret_cast<double *>(b->berr + nrhs);
+  b->sout = b->spart + vec_stats_part_bytes() / sizeof(double);
+  return 0;
+}
+
+// `cols` in groups of up to 8 (VecCols): vector slot v[j] = column d[j] of the matrix; packed: d[j] is the position
+// in `cols` instead (a compact n x k image)
+std::vector<VecCols> groups_of(const std::vector<int> &cols, bool packed = false) {
+  std::vector<VecCols> out;
+  for (size_t c0 = 0; c0 < cols.size(); c0 += 8) {
+    VecCols vc{(int)std::min<size_t>(8, cols.size() - c0), {}, {}};
+    for (int j = 0; j < vc.n; ++j) vc.v[j] = cols[c0 + j], vc.d[j] = packed ? (int)c0 + j : cols[c0 + j];
+    out.push_back(vc);
+  }
+  return out;
+}
+
+// the columns 0 .. k-1
+std::vector<int> all_cols(int k) {
+  std::vector<int> v(k);
+  std::iota(v.begin(), v.end(), 0);
+  return v;
+}
+
+// V[c] <- A^{-1} V[c] for the slots c in `cols` (AF: the factor, its diagonal tiles staged in cn[0]); st: posvx stats;
+// path: 0 the path rule, 1 the sweeps, 2 potrs (chol_bench_refine)
+template <typename T>
+int apply_inv(int upper, chol_desc *AF, const RfBufs<T> &b, T *V, const std::vector<int> &cols, double *st,
+              int path = 0) {
+  hipStream_t s = main_stream();
+  const TileGeo ga = geo_of(AF);
+  const int k = (int)cols.size();
+  if (!k) return 0;
+  if (path == 1 || (path == 0 && k <= POSVX_KX)) {
+    const long NB = (long)ga.lmt * (condest_edge(ga) / MACRO);
+    const long nv = b.nv, pgn = 2 * NB * (condest_edge(ga) / MACRO) * MACRO;
+    const MSweepBufs<T> mb{b.sw, b.sw + 8 * nv, b.sw + 8 * nv + 8 * pgn};
+    for (int c0 = 0; c0 < k; c0 += 8) {
+      const int m = std::min(8, k - c0);
+      T *x[8];
+      for (int j = 0; j < m; ++j) x[j] = V + (long)cols[c0 + j] * nv;
+      launch_msweep<T>(s, ga, upper, reinterpret_cast<const T *>(AF->mat), cn.as<const T>(0), x, m,
+                       b.pad, mb);
+      st[6] += m;
+    }
+    HIPCHECK(hipGetLastError());
+    return 0;
+  }
+  // wide: potrs_impl on an n x k scratch image with AF's row tiling (the solve runs on whole tiles: zero padding)
+  chol_desc Td = *AF;
+  Td.ln = Td.n = k;
+  Td.nt = Td.lnt = (k + AF->mb - 1) / AF->mb;
+  Td.owns = false;
+  Td.version = 0;
+  Td.d_list = nullptr;
+  Td.user_mat = nullptr;
+  const size_t tb = (size_t)Td.lmt * Td.lnt * Td.bsizi * sizeof(T);
+  if (int rc = rf.ensure_bytes(6, tb, "porfs_tile")) return rc;
+  Td.mat = rf.p[6];
+  HIPCHECK(hipMemsetAsync(Td.mat, 0, tb, s));
+  const TileGeo gt = geo_of(&Td);
+  const std::vector<VecCols> gr = groups_of(cols, /*packed=*/true);
+  for (const VecCols &vc : gr) launch_scatter<T>(s, gt, reinterpret_cast<T *>(Td.mat), vc, V, false);
+  if (int rc = potrs_uplo<T>(upper, AF, &Td)) return rc;
+  for (const VecCols &vc : gr) launch_gather<T>(s, gt, reinterpret_cast<const T *>(Td.mat), vc, V);
+  HIPCHECK(hipGetLastError());
+  st[7] += k;
+  return 0;
+}
+
+// LAPACK DPORFS on device images; AF's diagonal tiles staged in cn[0]; st: posvx stats ([5] total porfs ms,
+// [6] / [7] columns through the sweeps / through potrs)
+template <typename T>
+int porfs_impl(int upper, chol_desc *A, chol_desc *AF, chol_desc *B, chol_desc *X, double *ferr, double *berr,
+               double *st) {
+  hipStream_t s = main_stream();
+  const TileGeo ga = geo_of(A), gx = geo_of(B);
+  const long n = A->lm;
+  const int nrhs = B->ln;
+  if (n == 0 || nrhs == 0) {
+    std::fill(ferr, ferr + nrhs, 0.0);
+    std::fill(berr, berr + nrhs, 0.0);
+    return 0;
+  }
+  EventTimer tt;
+  int rc = tt.start();
+  if (rc) return rc;
+  RfBufs<T> b;
+  if ((rc = rf_buffers<T>(ga, nrhs, &b, "porfs_tile"))) return rc;
+  const double eps = Lam<T>::eps, safe1 = (double)(T(n + 1) * T(Lam<T>::safmin)), safe2 = (double)(T(safe1) / T(eps));
+  const T *Am = reinterpret_cast<const T *>(A->mat);
+  std::vector<int> count(nrhs, 1), active = all_cols(nrhs);
+  std::vector<double> lstres(nrhs, 3.0);
+  std::vector<unsigned long long> hb(nrhs);
+  // refinement: R = B - A X, BERR; X += A^{-1} R for the columns that go on
+  while (!active.empty()) {
+    HIPCHECK(hipMemsetAsync(b.berr, 0, (size_t)nrhs * sizeof(unsigned long long), s));
+    for (const VecCols &vc : groups_of(active))
+      launch_porfs_resid<T>(s, ga, upper, Am, gx, reinterpret_cast<const T *>(X->mat), reinterpret_cast<const T *>(B->mat),
+                            vc, b.part, b.R, b.F, eps, safe1, safe2, b.berr);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(hb.data(), b.berr, (size_t)nrhs * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    std::vector<int> next;
+    for (int j : active) {
+      double bj;
+      memcpy(&bj, &hb[j], sizeof bj);
+      berr[j] = bj;
+      if (bj > eps && 2 * bj <= lstres[j] && count[j] <= PORFS_ITMAX) {
+        next.push_back(j);
+        lstres[j] = bj;
+        ++count[j];
+      }
+    }
+    if ((rc = apply_inv<T>(upper, AF, b, b.R, next, st))) return rc;
+    for (const VecCols &vc : groups_of(next)) launch_scatter<T>(s, gx, reinterpret_cast<T *>(X->mat), vc, b.R, true);
+    active.swap(next);
+  }
+  // FERR: DLACN2 on diag(F) A^{-1} (kase 1) / A^{-1} diag(F) (kase 2), every column in lockstep, x in the R slots
+  std::vector<Lacn2> est(nrhs);
+  for (int j = 0; j < nrhs; ++j) est[j].start(n), active.push_back(j);
+  std::vector<double> hs((size_t)nrhs * 8);
+  while (!active.empty()) {
+    const std::vector<VecCols> gr = groups_of(active);
+    for (int j : active)
+      if (est[j].fill >= 0) launch_vec_fill<T>(s, ga, b.R + (long)j * b.nv, est[j].fill, est[j].fill_j);
+    auto weight = [&](int kase) {
+      for (const VecCols &vc : gr) {
+        unsigned mask = 0;
+        for (int i = 0; i < vc.n; ++i) mask |= (est[vc.v[i]].kase == kase ? 1u : 0u) << i;
+        launch_vec_weight<T>(s, ga, b.R, b.F, vc, mask);
+      }
+    };
+    weight(2);
+    if ((rc = apply_inv<T>(upper, AF, b, b.R, active, st))) return rc;
+    weight(1);
+    for (size_t i = 0; i < active.size(); ++i) {
+      const int j = active[i];
+      launch_vec_stats<T>(s, ga, b.R + (long)j * b.nv, b.isgn + (long)j * b.nv, est[j].sign, est[j].jlast, b.spart,
+                          b.sout + 8 * i);
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(hs.data(), b.sout, active.size() * 8 * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    std::vector<int> next;
+    for (size_t i = 0; i < active.size(); ++i) {
+      const int j = active[i];
+      est[j].take<T>(&hs[8 * i]);
+      if (!est[j].done) next.push_back(j);
+    }
+    active.swap(next);
+  }
+  // normalise by max |X(:,j)| (gathered into a padding vector, then launch_vec_stats)
+  for (int j = 0; j < nrhs; ++j) {
+    const VecCols vc{1, {0}, {j}};
+    launch_gather<T>(s, gx, reinterpret_cast<const T *>(X->mat), vc, b.pad);
+    launch_vec_stats<T>(s, ga, b.pad, b.isgn, 0, -1, b.spart, b.sout + 8 * j);
+  }
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpyAsync(hs.data(), b.sout, (size_t)nrhs * 8 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  for (int j = 0; j < nrhs; ++j) {
+    T f = est[j].finite ? T(est[j].est) : T(INFINITY);
+    const T xm = T(hs[8 * j + 1]);
+    if (xm != T(0)) f = f / xm;
+    ferr[j] = (double)f;
+  }
+  return tt.stop(&st[5]);
+}
+
+// the descriptor rules shared by porfs / posvx: an n x nrhs image d with A's dtype, order and tile size
+int rhs_check(const char *what, const chol_desc *A, const chol_desc *d, int pos, const char *name) {
+  char buf[160];
+  if (!d) {
+    snprintf(buf, sizeof buf, "%s: %s is NULL", what, name);
+    return fail(-pos, buf);
+  }
+  if (int rc = resident_whole(what, d)) return rc;
+  if (d->dtype != A->dtype || d->lm != A->lm || d->mb != A->mb || d->mbi != A->mbi) {
+    snprintf(buf, sizeof buf, "%s: %s must have A's dtype, order and tile size", what, name);
+    return fail(-pos, buf);
+  }
+  return 0;
+}
+
+int square_check(const char *what, chol_desc *A, int pos) {
+  if (!A) {
+    char buf[96];
+    snprintf(buf, sizeof buf, "%s: NULL descriptor", what);
+    return fail(-pos, buf);
+  }
+  return inverse_check(what, A, pos);
+}
+
+// launch_diag_scan (mode 0: S <- 1/sqrt(diag(A)); 1: S alone) reduced on the host: the smallest and the largest
+// value scanned, and the first 0-based index of one <= 0 (or -1)
+template <typename T>
+int diag_scan(const chol_desc *A, chol_desc *S, int mode, const char *what, T *smin, T *smax, long *bad) {
+  hipStream_t s = main_stream();
+  const long n = A->lm;
+  if (int rc = rf.ensure_bytes(7, diag_scan_part_bytes(), what)) return rc;
+  double *part = rf.as<double>(7);
+  launch_diag_scan<T>(s, geo_of(A), mode == 0 ? reinterpret_cast<const T *>(A->mat) : nullptr,
+                      reinterpret_cast<T *>(S->mat), mode, part);
+  HIPCHECK(hipGetLastError());
+  std::vector<double> h(diag_scan_part_bytes() / sizeof(double));
+  HIPCHECK(hipMemcpyAsync(h.data(), part, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  const long per = (n + 255) / 256;
+  *smin = T(INFINITY), *smax = T(-INFINITY), *bad = -1;
+  for (long w = 0; w < 256 && w * per < n; ++w) {
+    *smin = std::min(*smin, T(h[3 * w]));
+    *smax = std::max(*smax, T(h[3 * w + 1]));
+    if (h[3 * w + 2] >= 0 && *bad < 0) *bad = (long)h[3 * w + 2];
+  }
+  return 0;
+}
+
+// LAPACK DPOEQU on the device: S <- 1/sqrt(diag), *scond, *amax; info > 0: the first non-positive diagonal entry
+template <typename T>
+int poequ_impl(chol_desc *A, chol_desc *S, double *scond, double *amax, int *info) {
+  *info = 0;
+  if (A->lm == 0) {
+    *scond = 1, *amax = 0;
+    return 0;
+  }
+  T smin, smax;
+  long bad;
+  if (int rc = diag_scan<T>(A, S, 0, "poequ_tile", &smin, &smax, &bad)) return rc;
+  *amax = (double)smax;
+  if (smin <= T(0)) {
+    *info = (int)(bad + 1);
+    return 0;
+  }
+  *scond = (double)(T(std::sqrt(smin)) / T(std::sqrt(smax)));
+  return 0;
+}
+
+// LAPACK DLAQSY's decision and scaling; *equed <- 1 ('Y') or 0 ('N')
+template <typename T>
+int laqsy_impl(int upper, chol_desc *A, chol_desc *S, double scond, double amax, int *equed) {
+  const double small = Lam<T>::safmin / Lam<T>::prec, large = 1.0 / small;
+  *equed = 0;
+  if (A->lm == 0) return 0;
+  if (scond >= 0.1 && amax >= small && amax <= large) return 0;
+  launch_laqsy<T>(main_stream(), geo_of(A), upper, reinterpret_cast<T *>(A->mat), reinterpret_cast<const T *>(S->mat));
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(main_stream()));
+  *equed = 1;
+  return 0;
+}
+
+// the checks of porfs (apos: A's position; B, X follow AF)
+int porfs_args(const char *what, chol_desc *A, chol_desc *AF, chol_desc *B, chol_desc *X, int apos, int bpos,
+               int xpos) {
+  int rc = square_check(what, A, apos);
+  if (rc) return rc;
+  if ((rc = square_check(what, AF, apos + 1))) return rc;
+  char buf[160];
+  if (!same_geometry(A, AF) || AF->mat == A->mat) {
+    snprintf(buf, sizeof buf, "%s: AF must have A's shape, tile size and type, in storage of its own", what);
+    return fail(-(apos + 1), buf);
+  }
+  if ((rc = rhs_check(what, A, B, bpos, "B"))) return rc;
+  if ((rc = rhs_check(what, A, X, xpos, "X"))) return rc;
+  if (!same_geometry(B, X)) {
+    snprintf(buf, sizeof buf, "%s: X must have B's shape, tile size and type", what);
+    return fail(-xpos, buf);
+  }
+  if (X->mat == A->mat || X->mat == AF->mat || X->mat == B->mat || B->mat == A->mat || B->mat == AF->mat) {
+    snprintf(buf, sizeof buf, "%s: X aliases A, AF or B", what);
+    return fail(-xpos, buf);
+  }
+  if (!winv_fits(AF)) {  // (the wide steps solve with potrs_impl)
+    snprintf(buf, sizeof buf, "%s: tile size above 4096", what);
+    return fail(CHOL_ERR_NOT_SUPPORTED, buf);
+  }
+  return 0;
+}
+
+template <typename T>
+int posvx_impl(int fact, int upper, chol_desc *A, chol_desc *AF, int *equed, chol_desc *S, chol_desc *B,
+               chol_desc *X, double *rcond, double *ferr, double *berr) {
+  hipStream_t s = main_stream();
+  double *st = rf_stats;  // total, equilibrate + scale B, factor, lansy + pocon, solve, porfs, #sweep / #potrs columns
+  std::fill(st, st + 8, 0.0);
+  const long n = A->lm;
+  const int nrhs = B->ln, uplo = upper ? CHOL_UPPER : CHOL_LOWER;
+  EventTimer tt, tp;
+  int rc = tt.start();
+  if (rc) return rc;
+  bool rcequ = false;
+  double scond = 1;
+  if ((rc = tp.start())) return rc;
+  if (fact == CHOL_FACT_FACTORED) {
+    rcequ = *equed == 1;
+    if (rcequ && n > 0) {  // DPOSVX: scond from S itself
+      T smin, smax;
+      long bad;
+      if ((rc = diag_scan<T>(A, S, 1, "posvx_tile", &smin, &smax, &bad))) return rc;
+      if (!(smin > T(0))) return fail(-6, "posvx_tile: S has an entry <= 0");
+      const T smlnum = T(Lam<T>::safmin), bignum = T(1) / smlnum;
+      scond = (double)(std::max(smin, smlnum) / std::min(smax, bignum));
+    }
+  } else {
+    *equed = 0;
+    if (fact == CHOL_FACT_EQUILIBRATE) {
+      int infequ = 0;
+      double amax = 0;
+      if ((rc = poequ_impl<T>(A, S, &scond, &amax, &infequ))) return rc;
+      if (infequ == 0) {
+        if ((rc = laqsy_impl<T>(upper, A, S, scond, amax, equed))) return rc;
+        rcequ = *equed == 1;
+      }
+    }
+  }
+  const TileGeo ga = geo_of(A), gx = geo_of(B);
+  if (rcequ) launch_row_scale<T>(s, gx, reinterpret_cast<T *>(B->mat), reinterpret_cast<const T *>(S->mat));
+  HIPCHECK(hipGetLastError());
+  if ((rc = tp.stop(&st[1]))) return rc;
+  if (fact != CHOL_FACT_FACTORED) {
+    if ((rc = tp.start())) return rc;
+    launch_lacpy<T>(s, ga, upper ? 2 : 1, reinterpret_cast<const T *>(A->mat), reinterpret_cast<T *>(AF->mat));
+    HIPCHECK(hipGetLastError());
+    const int info = potrf_run(uplo, AF);
+    if (info < 0) return info;
+    if ((rc = tp.stop(&st[2]))) return rc;
+    if (info > 0) {
+      *rcond = 0;
+      return tt.stop(&st[0]) ? CHOL_ERR_HIP : info;
+    }
+  }
+  // rcond: anorm = ||A||_1 of the (equilibrated) A, the estimate on AF's sweeps
+  if ((rc = tp.start())) return rc;
+  double lv[3];
+  if ((rc = lansy_impl<T>(A, upper, "posvx_tile", lv))) return rc;
+  if ((rc = stage_factor_diag<T>(AF, upper, "posvx_tile"))) return rc;
+  if ((rc = pocon_impl<T>(AF, upper, lv[1], rcond, /*staged=*/true))) return rc;
+  if ((rc = tp.stop(&st[3]))) return rc;
+  // X <- A^{-1} B: the sweeps on B's columns gathered into the R slots, or lacpy and potrs_impl when wide
+  if ((rc = tp.start())) return rc;
+  if (nrhs > 0 && n > 0) {
+    if (nrhs <= POSVX_KX) {
+      RfBufs<T> b;
+      if ((rc = rf_buffers<T>(ga, nrhs, &b, "posvx_tile"))) return rc;
+      const std::vector<int> all = all_cols(nrhs);
+      const std::vector<VecCols> gr = groups_of(all);
+      for (const VecCols &vc : gr) launch_gather<T>(s, gx, reinterpret_cast<const T *>(B->mat), vc, b.R);
+      if ((rc = apply_inv<T>(upper, AF, b, b.R, all, st))) return rc;
+      for (const VecCols &vc : gr) launch_scatter<T>(s, gx, reinterpret_cast<T *>(X->mat), vc, b.R, false);
+    } else {
+      launch_lacpy<T>(s, gx, 0, reinterpret_cast<const T *>(B->mat), reinterpret_cast<T *>(X->mat));
+      if ((rc = potrs_uplo<T>(upper, AF, X))) return rc;
+      st[7] += nrhs;
+    }
+    HIPCHECK(hipGetLastError());
+  }
+  if ((rc = tp.stop(&st[4]))) return rc;
+  if ((rc = porfs_impl<T>(upper, A, AF, B, X, ferr, berr, st))) return rc;
+  // the solution of the original system, its error bound
+  if (rcequ) {
+    launch_row_scale<T>(s, gx, reinterpret_cast<T *>(X->mat), reinterpret_cast<const T *>(S->mat));
+    HIPCHECK(hipGetLastError());
+    for (int j = 0; j < nrhs; ++j) ferr[j] = (double)(T(ferr[j]) / T(scond));
+  }
+  if ((rc = tt.stop(&st[0]))) return rc;
+  return *rcond < Lam<T>::eps ? (int)(n + 1) : 0;
+}
+
+// the parts of porfs alone, for scripts/posvx_time.py: path 0 the residual pass over X's columns (B = X), 1 one
+// application of A^{-1} to them by the multi-vector sweeps, 2 the same by potrs_impl; *ms <- the fastest of reps
+template <typename T>
+int bench_refine_impl(int upper, chol_desc *A, chol_desc *AF, chol_desc *X, int path, int reps, double *ms) {
+  hipStream_t s = main_stream();
+  const TileGeo ga = geo_of(A), gx = geo_of(X);
+  const int k = X->ln;
+  RfBufs<T> b;
+  int rc = rf_buffers<T>(ga, k, &b, "bench_refine");
+  if (rc) return rc;
+  if ((rc = stage_factor_diag<T>(AF, upper, "bench_refine"))) return rc;
+  const std::vector<int> all = all_cols(k);
+  for (const VecCols &vc : groups_of(all)) launch_gather<T>(s, gx, reinterpret_cast<const T *>(X->mat), vc, b.R);
+  double st[8] = {};
+  *ms = 1e30;
+  for (int r = 0; r <= reps; ++r) {
+    EventTimer tt;
+    if ((rc = tt.start())) return rc;
+    if (path == 0) {
+      for (const VecCols &vc : groups_of(all))
+        launch_porfs_resid<T>(s, ga, upper, reinterpret_cast<const T *>(A->mat), gx, reinterpret_cast<const T *>(X->mat),
+                              reinterpret_cast<const T *>(X->mat), vc, b.part, b.R, b.F, Lam<T>::eps, 0.0, 0.0, b.berr);
+    } else {
+      if ((rc = apply_inv<T>(upper, AF, b, b.R, all, st, path))) return rc;
+    }
+    HIPCHECK(hipGetLastError());
+    double t = 0;
+    if ((rc = tt.stop(&t))) return rc;
+    if (r > 0) *ms = std::min(*ms, t);
+  }
+  return 0;
+}
+
+}  // namespace
+
+void cholmi::spd_release() {
+  work.release();
+  mx.release();
+  iv.release();
+  cn.release();
+  rf.release();
+}
+
+// ---------------------------------------------------------------- the entry points (C linkage: include/cholmi.h)
+int chol_potrs_tile(int uplo, chol_desc_t *A, chol_desc_t *B) {
+  return with_views({{A, false}, {B, true}}, [&]() -> int {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "potrs_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "potrs_tile: uplo");
+  int rc = resident_whole("potrs_tile", A);
+  if (rc) return rc;
+  rc = resident_whole("potrs_tile", B);
+  if (rc) return rc;
+  if (A->mt != A->nt || A->lm != A->ln) return fail(-2, "potrs_tile: A is not square");
+  if (B->lm != A->lm || B->mb != A->mb || B->mbi != A->mbi || B->dtype != A->dtype)
+    return fail(-3, "potrs_tile: B must have A's order, tile size and type");
+  if (A->mbi % 64) return fail(CHOL_ERR_NOT_SUPPORTED, "potrs_tile: stored tile edge must be a multiple of 64");
+  CHECK_WINV(A, "potrs_tile");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  // ChamUpper: the Lower solve on the transposed storage (as chol_potrf_tile does around the Lower factorisation)
+  const int up = uplo == CHOL_UPPER;
+  rc = A->dtype == CHOL_REAL_DOUBLE ? potrs_uplo<double>(up, A, B) : potrs_uplo<float>(up, A, B);
+  if (up) HIPCHECK(hipStreamSynchronize(main_stream()));
+  return rc;
+  });
+}
+
+int chol_posv_tile(int uplo, chol_desc_t *A, chol_desc_t *B) {
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "posv_tile: uplo");
+  const int info = chol_potrf_tile(uplo, A);
+  if (info != 0) return info;  // > 0: not positive definite, B untouched (LAPACK dposv)
+  return chol_potrs_tile(uplo, A, B);
+}
+
+int chol_dsposv_tile(int uplo, chol_desc_t *A, chol_desc_t *B, chol_desc_t *X, int *iter) {
+  return with_views({{A, false}, {B, false}, {X, false}}, [&]() -> int {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "dsposv_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "dsposv_tile: uplo");
+  int rc = resident_whole("dsposv_tile", A);
+  if (rc) return rc;
+  if (A->dtype != CHOL_REAL_DOUBLE) return fail(-2, "dsposv_tile: A must be fp64");
+  if (A->mt != A->nt || A->lm != A->ln) return fail(-2, "dsposv_tile: A is not square");
+  if (!B) return fail(-3, "dsposv_tile: B is NULL");
+  if ((rc = resident_whole("dsposv_tile", B))) return rc;
+  if (B->dtype != CHOL_REAL_DOUBLE || B->lm != A->lm || B->mb != A->mb || B->mbi != A->mbi || B->mat == A->mat)
+    return fail(-3, "dsposv_tile: B must be fp64 with A's order and tile size");
+  if (!X) return fail(-4, "dsposv_tile: X is NULL");
+  if ((rc = resident_whole("dsposv_tile", X))) return rc;
+  if (!same_geometry(B, X)) return fail(-4, "dsposv_tile: X must have B's shape, tile size and type");
+  if (X->mat == A->mat || X->mat == B->mat) return fail(-4, "dsposv_tile: X aliases A or B");
+  if (!iter) return fail(-5, "dsposv_tile: iter is NULL");
+  if (A->user_mat || B->user_mat || X->user_mat)
+    return fail(CHOL_ERR_NOT_SUPPORTED, "dsposv_tile: sub-matrix views over a user buffer");
+  if (A->mbi % MACRO) return fail(CHOL_ERR_NOT_SUPPORTED, "dsposv_tile: stored tile edge must be a multiple of 128");
+  CHECK_WINV(A, "dsposv_tile");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  rc = dsposv_mixed(uplo, A, B, X, iter);
+  if (rc < 0) return rc;
+  if (*iter >= 0) return 0;
+  // fallback (LAPACK dsposv): X <- B, then dposv in fp64 -- A then holds the fp64 factor
+  launch_lacpy<double>(main_stream(), geo_of(B), 0, (const double *)B->mat, (double *)X->mat);
+  HIPCHECK(hipStreamSynchronize(main_stream()));
+  const int info = chol_potrf_tile(uplo, A);
+  if (info != 0) return info;
+  return chol_potrs_tile(uplo, A, X);
+  });
+}
+
+int chol_last_dsposv_stats(double *out8) {
+  if (!out8) return fail(-1, "last_dsposv_stats: NULL");
+  std::copy(mx_stats, mx_stats + 8, out8);
+  return 0;
+}
+
+int chol_trtri_tile(int uplo, int diag, chol_desc_t *A) {
+  return with_views({{A, true}}, [&]() -> int {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "trtri_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "trtri_tile: uplo");
+  if (diag != CHOL_NONUNIT && diag != CHOL_UNIT) return fail(-2, "trtri_tile: diag");
+  if (diag == CHOL_UNIT)
+    return fail(CHOL_ERR_NOT_SUPPORTED, "trtri_tile: ChamUnit (a Cholesky factor has no unit diagonal)");
+  int rc = inverse_check("trtri_tile", A, 3);
+  if (rc) return rc;
+  return inverse_run(uplo, A, false);
+  });
+}
+
+int chol_potri_tile(int uplo, chol_desc_t *A) {
+  return with_views({{A, true}}, [&]() -> int {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "potri_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "potri_tile: uplo");
+  int rc = inverse_check("potri_tile", A, 2);
+  if (rc) return rc;
+  return inverse_run(uplo, A, true);
+  });
+}
+
+int chol_poinv_tile(int uplo, chol_desc_t *A) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "poinv_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "poinv_tile: uplo");
+  int rc = inverse_check("poinv_tile", A, 2);  // (before the factorisation writes anything)
+  if (rc) return rc;
+  const int info = chol_potrf_tile(uplo, A);
+  if (info != 0) return info;  // > 0: not positive definite, A as potrf leaves it
+  return chol_potri_tile(uplo, A);
+}
+
+int chol_lansy_tile(int norm, int uplo, chol_desc_t *A, double *value) {
+  return with_views({{A, false}}, [&]() -> int {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "lansy_tile before chol_init");
+  int kind;
+  switch (norm) {
+    case CHOL_MAX_NORM: kind = 0; break;
+    case CHOL_ONE_NORM:
+    case CHOL_INF_NORM: kind = 1; break;  // (symmetric: one value for both)
+    case CHOL_FROBENIUS_NORM: kind = 2; break;
+    default: return fail(-1, "lansy_tile: norm");
+  }
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-2, "lansy_tile: uplo");
+  int rc = inverse_check("lansy_tile", A, 3);
+  if (rc) return rc;
+  if (!value) return fail(-4, "lansy_tile: NULL value");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  const int up = uplo == CHOL_UPPER;
+  double v[3];
+  rc = A->dtype == CHOL_REAL_DOUBLE ? lansy_impl<double>(A, up, "lansy_tile", v) : lansy_impl<float>(A, up, "lansy_tile", v);
+  if (rc) return rc;
+  *value = kind == 2 ? std::sqrt(v[2]) : v[kind];
+  return 0;
+  });
+}
+
+int chol_pocon_tile(int uplo, chol_desc_t *A, double anorm, double *rcond) {
+  return with_views({{A, false}}, [&]() -> int {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "pocon_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "pocon_tile: uplo");
+  int rc = inverse_check("pocon_tile", A, 2);
+  if (rc) return rc;
+  if (!(anorm >= 0)) return fail(-3, "pocon_tile: anorm is negative or NaN");
+  if (!rcond) return fail(-4, "pocon_tile: NULL rcond");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  const int up = uplo == CHOL_UPPER;
+  return A->dtype == CHOL_REAL_DOUBLE ? pocon_impl<double>(A, up, anorm, rcond) : pocon_impl<float>(A, up, anorm, rcond);
+  });
+}
+
+int chol_last_pocon_stats(double *out4) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "last_pocon_stats before chol_init");
+  if (!out4) return fail(-1, "last_pocon_stats: NULL");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  for (int i = 0; i < 4; ++i) out4[i] = cn_stats[i];
+  return 0;
+}
+
+int chol_poequ_tile(chol_desc_t *A, chol_desc_t *S, double *scond, double *amax) {
+  return with_views({{A, false}, {S, true}}, [&]() -> int {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "poequ_tile before chol_init");
+  int rc = square_check("poequ_tile", A, 1);
+  if (rc) return rc;
+  if ((rc = rhs_check("poequ_tile", A, S, 2, "S"))) return rc;
+  if (S->ln != 1 || S->mat == A->mat) return fail(-2, "poequ_tile: S must be an n x 1 descriptor of its own");
+  if (!scond) return fail(-3, "poequ_tile: NULL scond");
+  if (!amax) return fail(-4, "poequ_tile: NULL amax");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  int info = 0;
+  rc = A->dtype == CHOL_REAL_DOUBLE ? poequ_impl<double>(A, S, scond, amax, &info)
+                                    : poequ_impl<float>(A, S, scond, amax, &info);
+  return rc ? rc : info;
+  });
+}
+
+int chol_laqsy_tile(int uplo, chol_desc_t *A, chol_desc_t *S, double scond, double amax, int *equed) {
+  return with_views({{A, true}, {S, false}}, [&]() -> int {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "laqsy_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "laqsy_tile: uplo");
+  int rc = square_check("laqsy_tile", A, 2);
+  if (rc) return rc;
+  if ((rc = rhs_check("laqsy_tile", A, S, 3, "S"))) return rc;
+  if (S->ln != 1 || S->mat == A->mat) return fail(-3, "laqsy_tile: S must be an n x 1 descriptor of its own");
+  if (!(scond >= 0)) return fail(-4, "laqsy_tile: scond is negative or NaN");
+  if (!(amax >= 0)) return fail(-5, "laqsy_tile: amax is negative or NaN");
+  if (!equed) return fail(-6, "laqsy_tile: NULL equed");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  const int up = uplo == CHOL_UPPER;
+  return A->dtype == CHOL_REAL_DOUBLE ? laqsy_impl<double>(up, A, S, scond, amax, equed)
+                                      : laqsy_impl<float>(up, A, S, scond, amax, equed);
+  });
+}
+
+int chol_porfs_tile(int uplo, chol_desc_t *A, chol_desc_t *AF, chol_desc_t *B, chol_desc_t *X, double *ferr,
+                    double *berr) {
+  return with_views({{A, false}, {AF, false}, {B, false}, {X, true}}, [&]() -> int {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "porfs_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "porfs_tile: uplo");
+  int rc = porfs_args("porfs_tile", A, AF, B, X, 2, 4, 5);
+  if (rc) return rc;
+  if (!ferr) return fail(-6, "porfs_tile: NULL ferr");
+  if (!berr) return fail(-7, "porfs_tile: NULL berr");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  const int up = uplo == CHOL_UPPER;
+  std::fill(rf_stats, rf_stats + 8, 0.0);
+  EventTimer tt;
+  if ((rc = tt.start())) return rc;
+  if (A->dtype == CHOL_REAL_DOUBLE) {
+    if (!(rc = stage_factor_diag<double>(AF, up, "porfs_tile")))
+      rc = porfs_impl<double>(up, A, AF, B, X, ferr, berr, rf_stats);
+  } else {
+    if (!(rc = stage_factor_diag<float>(AF, up, "porfs_tile")))
+      rc = porfs_impl<float>(up, A, AF, B, X, ferr, berr, rf_stats);
+  }
+  if (rc) return rc;
+  return tt.stop(&rf_stats[0]);
+  });
+}
+
+int chol_posvx_tile(int fact, int uplo, chol_desc_t *A, chol_desc_t *AF, int *equed, chol_desc_t *S, chol_desc_t *B,
+                    chol_desc_t *X, double *rcond, double *ferr, double *berr) {
+  return with_views({{A, true}, {AF, true}, {S, true}, {B, true}, {X, true}}, [&]() -> int {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "posvx_tile before chol_init");
+  if (fact != CHOL_FACT_NONE && fact != CHOL_FACT_EQUILIBRATE && fact != CHOL_FACT_FACTORED)
+    return fail(-1, "posvx_tile: fact");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-2, "posvx_tile: uplo");
+  int rc = porfs_args("posvx_tile", A, AF, B, X, 3, 7, 8);
+  if (rc) return rc;
+  if (!equed) return fail(-5, "posvx_tile: NULL equed");
+  if (fact == CHOL_FACT_FACTORED && *equed != 0 && *equed != 1) return fail(-5, "posvx_tile: equed must be 0 or 1");
+  const bool need_s = fact == CHOL_FACT_EQUILIBRATE || (fact == CHOL_FACT_FACTORED && *equed == 1);
+  if (need_s || S) {
+    if ((rc = rhs_check("posvx_tile", A, S, 6, "S"))) return rc;
+    if (S->ln != 1 || S->mat == A->mat || S->mat == AF->mat || S->mat == B->mat || S->mat == X->mat)
+      return fail(-6, "posvx_tile: S must be an n x 1 descriptor of its own");
+  }
+  if (!rcond) return fail(-9, "posvx_tile: NULL rcond");
+  if (!ferr) return fail(-10, "posvx_tile: NULL ferr");
+  if (!berr) return fail(-11, "posvx_tile: NULL berr");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  const int up = uplo == CHOL_UPPER;
+  return A->dtype == CHOL_REAL_DOUBLE ? posvx_impl<double>(fact, up, A, AF, equed, S, B, X, rcond, ferr, berr)
+                                      : posvx_impl<float>(fact, up, A, AF, equed, S, B, X, rcond, ferr, berr);
+  });
+}
+
+int chol_bench_refine(int uplo, chol_desc_t *A, chol_desc_t *AF, chol_desc_t *X, int path, int reps, double *ms) {
+  return with_views({{A, false}, {AF, false}, {X, false}}, [&]() -> int {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "bench_refine before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "bench_refine: uplo");
+  int rc = square_check("bench_refine", A, 2);
+  if (rc) return rc;
+  if ((rc = square_check("bench_refine", AF, 3))) return rc;
+  if ((rc = rhs_check("bench_refine", A, X, 4, "X"))) return rc;
+  if (path < 0 || path > 2 || reps < 1 || !ms) return fail(-5, "bench_refine: path, reps or ms");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  const int up = uplo == CHOL_UPPER;
+  return A->dtype == CHOL_REAL_DOUBLE ? bench_refine_impl<double>(up, A, AF, X, path, reps, ms)
+                                      : bench_refine_impl<float>(up, A, AF, X, path, reps, ms);
+  });
+}
+
+int chol_last_posvx_stats(double *out8) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "last_posvx_stats before chol_init");
+  if (!out8) return fail(-1, "last_posvx_stats: NULL");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  for (int i = 0; i < 8; ++i) out8[i] = rf_stats[i];
+  return 0;
+}

@@ -8,7 +8,7 @@ import scipy.linalg.lapack as lapack
 
 pytestmark = pytest.mark.gpu
 
-KX = 40  # api.hip: POSVX_KX, the widest application of A^{-1} that runs as multi-vector sweeps
+KX = 40  # spd.hip: POSVX_KX, the widest application of A^{-1} that runs as multi-vector sweeps
 NPT = {"d": np.float64, "s": np.float32}
 EPS = {"d": 2.0 ** -53, "s": 2.0 ** -24}
 C_BERR = 2.0  # berr <= (n + 1) eps C_BERR
