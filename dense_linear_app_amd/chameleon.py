@@ -362,6 +362,26 @@ def bench_refine(uplo: int, A: Desc, AF: Desc, X: Desc, path: int, reps: int = 3
     return r.value
 
 
+def CHAMELEON_dpstrf_Tile(uplo: int, A: Desc, tol: float = -1.0) -> tuple[int, np.ndarray, int]:
+    """LAPACK DPSTRF: P^T A P = L L^T (ChamLower) or U^T U (ChamUpper) with complete pivoting, in the `uplo` triangle
+    of A.  tol < 0: n * eps * max(diag(A)).  Returns (info, piv, rank): info 0 (rank = n) or 1 (rank < n), piv the
+    1-based np.int32 pivot vector (as scipy.linalg.lapack.dpstrf), rank the number of pivots taken."""
+    n = int(A.lm)
+    piv = np.zeros(max(n, 1), dtype=np.int32)
+    r = C.c_int()
+    info = check("chol_pstrf_tile", lib().chol_pstrf_tile(uplo, A.handle, piv.ctypes.data_as(C.POINTER(C.c_int)),
+                                                          C.byref(r), float(tol)))
+    return info, piv[:n], r.value
+
+
+def last_pstrf_stats() -> dict:
+    """The last CHAMELEON_dpstrf_Tile (chol_last_pstrf_stats): total, pivot-step, row-interchange and trailing-update
+    time [ms], and the number of pivot steps."""
+    v = (C.c_double * 8)()
+    check("chol_last_pstrf_stats", lib().chol_last_pstrf_stats(v))
+    return {"total_ms": v[0], "steps_ms": v[1], "laswp_ms": v[2], "update_ms": v[3], "steps": int(v[4])}
+
+
 CHAMELEON_spotrs_Tile = CHAMELEON_dpotrs_Tile
 CHAMELEON_sposv_Tile = CHAMELEON_dposv_Tile
 CHAMELEON_slacpy_Tile = CHAMELEON_dlacpy_Tile
@@ -377,6 +397,7 @@ CHAMELEON_spoequ_Tile = CHAMELEON_dpoequ_Tile
 CHAMELEON_slaqsy_Tile = CHAMELEON_dlaqsy_Tile
 CHAMELEON_sporfs_Tile = CHAMELEON_dporfs_Tile
 CHAMELEON_sposvx_Tile = CHAMELEON_dposvx_Tile
+CHAMELEON_spstrf_Tile = CHAMELEON_dpstrf_Tile
 
 
 def residual_plgsy(L: Desc, bump: float, seed: int) -> float:

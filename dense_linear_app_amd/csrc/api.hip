@@ -708,6 +708,12 @@ void transpose_storage(chol_desc *A) {
     launch_transpose_inplace<float>(g.r.st[ST_MAIN], (float *)A->mat, A->nt, A->mbi);
 }
 
+LocalMat whole_local_mat(const chol_desc *d) { return local_mat(d, d->mat); }
+WorkRange whole_col_range(const chol_desc *d, int jlo, int jhi) {
+  const ColRange r = col_range(d, jlo, jhi);
+  return WorkRange{r.off, r.na, r.offb, r.nb};
+}
+
 // (posvx factors AF inside its own view refresh)
 int potrf_run(int uplo, chol_desc *A) {
   std::lock_guard<std::recursive_mutex> lk(g_mu);

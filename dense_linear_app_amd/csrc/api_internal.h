@@ -89,6 +89,14 @@ int potrf_run(int uplo, chol_desc *A);
 // U = L^T) runs the Lower path between two of these
 void transpose_storage(chol_desc *A);
 
+// a whole-matrix descriptor's trailing update from another translation unit (as chol_bench_update calls it): its
+// local tile matrix, and the segments of its work list that hold the tiles of columns [jlo, jhi)
+LocalMat whole_local_mat(const chol_desc *d);
+struct WorkRange {
+  int off, na, offb, nb;
+};
+WorkRange whole_col_range(const chol_desc *d, int jlo, int jhi);
+
 // spd.hip: its scratch, freed by chol_finalize
 void spd_release();
 

@@ -395,6 +395,35 @@ template <typename T>
 void launch_msweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const T *Dv, T *const *x, int count,
                    T *pad, const MSweepBufs<T> &b);
 
+// ---- launchers (pstrf.hip): the pivoted panel of chol_pstrf_tile (LAPACK DPSTRF, Lower) on a single-process image.
+// Entry (r, c) of the n x n matrix at (r / mb + (c / mb) lmt) bsiz + r % mb + (c % mb) mbi; the padding is never
+// touched.  Scratch: dg, w (n each), pval, pidx (pstrf_chunks(n) each: the partial maxima of the candidates
+// d = dg - w per 64-row chunk), ctl (one zeroed int: the step + 1 at which the factorisation stopped), pj (n: the
+// pivot of every step), ajj (one element).
+struct PsGeo {
+  long n;
+  int mb, mbi, lmt;
+  long bsiz;
+};
+long pstrf_chunks(long n);
+// the start of tile column k0 / mb: dg(i) <- A(i,i), w(i) <- 0 for i >= k0, and their partial maxima
+template <typename T>
+void launch_pstrf_init(hipStream_t s, const PsGeo &g, const T *A, long k0, T *dg, T *w, T *pval, int *pidx);
+// *outv, *outi <- the largest partial of the chunks c0 .. (NaN above all, ties to the smaller index)
+template <typename T>
+void launch_pstrf_max(hipStream_t s, const PsGeo &g, long c0, const T *pval, const int *pidx, T *outv, int *outi);
+// pivot step j of the tile column that starts at k0 (two launches): the choice of p (or the stop, for j > 0, when
+// d(p) <= dstop or is NaN), the symmetric interchange j <-> p, then column j of L and the next partial maxima
+template <typename T>
+void launch_pstrf_step(hipStream_t s, const PsGeo &g, T *A, long j, long k0, T dstop, T *dg, T *w, T *pval, int *pidx,
+                       int *ctl, int *pj, T *ajj);
+// rows[t] <- rows[m + t] (t < m) in columns 0 .. ncols-1: the composed interchanges of one tile column (LAPACK laswp)
+template <typename T>
+void launch_pstrf_laswp(hipStream_t s, const PsGeo &g, T *A, long ncols, const int *rows, int m);
+// A(r,c) <-> A(c,r) for r > c, any tile geometry (the Upper path of a single tile whose edge is not a multiple of 64)
+template <typename T>
+void launch_pstrf_transpose(hipStream_t s, const PsGeo &g, T *A);
+
 // out-of-place transposes of `count` mb x mb tiles (mb % 64 == 0)
 template <typename T>
 void launch_tiles_transpose(hipStream_t s, const T *in, long istride, T *out, long ostride, int mb, int count);

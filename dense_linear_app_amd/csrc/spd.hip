@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <numeric>
 #include <vector>
 
@@ -39,6 +40,10 @@ ScratchPool<8, true> rf;
 double mx_stats[8] = {};  // of the last chol_dsposv_tile (chol_last_dsposv_stats)
 double cn_stats[4] = {};  // of the last chol_pocon_tile (chol_last_pocon_stats)
 double rf_stats[8] = {};  // of the last chol_posvx_tile / chol_porfs_tile (chol_last_posvx_stats)
+// chol_pstrf_tile's: the candidates' diagonal and sums of squares, the partial maxima and the step's pivot, their
+// indices with the stop word, the pivots and the interchange list
+ScratchPool<3> ps;
+double ps_stats[8] = {};  // of the last chol_pstrf_tile (chol_last_pstrf_stats)
 
 hipStream_t main_stream() { return main_rank_ctx()->st[ST_MAIN]; }
 
@@ -996,6 +1001,131 @@ int bench_refine_impl(int upper, chol_desc *A, chol_desc *AF, chol_desc *X, int 
   return 0;
 }
 
+// ---------------------------------------------------------------- pivoted Cholesky (LAPACK DPSTRF)
+// Right-looking between tile columns, left-looking inside one (pstrf.hip).  Tile column k (columns k0 .. k1-1) at
+// update level k-1: the candidates d(i) = A(i,i) - (sum of squares of this tile column's finished L(i,:)), then
+// one pivot step per column (two launches); then this tile column's interchanges applied at once to the rows of the
+// earlier tile columns (also after a stop inside the tile column: the rows of L must match piv), then, unless the
+// factorisation stopped, the walker's trailing update of the tiles (i, j >= k+1) by tile column k.  The padded rows
+// of the image are not candidates: the kernels address only rows and columns 0 .. n-1.
+template <typename T>
+int pstrf_impl(chol_desc *A, int *piv, int *rank, double tol) {
+  hipStream_t s = main_stream();
+  const long n = A->lm;
+  const int mb = A->mb;
+  double *st = ps_stats;  // total, pivot steps, row interchanges, trailing updates, #steps
+  std::fill(st, st + 8, 0.0);
+  for (long i = 0; i < n; ++i) piv[i] = (int)(i + 1);
+  *rank = 0;
+  if (n == 0) return 0;
+  const PsGeo g{n, mb, A->mbi, A->lmt, (long)A->bsizi};
+  const long nch = pstrf_chunks(n);
+  const char *what = "pstrf_tile";
+  // ps[0]: dg, w; ps[1]: pval, ajj, the maximum; ps[2]: pidx, ctl, the maximum's index, pj, the interchange list
+  int rc = ps.ensure_bytes(0, 2 * (size_t)n * sizeof(T), what);
+  if (!rc) rc = ps.ensure_bytes(1, ((size_t)nch + 2) * sizeof(T), what);
+  if (!rc) rc = ps.ensure_bytes(2, ((size_t)nch + 2 + (size_t)n + 4 * (size_t)mb) * sizeof(int), what);
+  if (rc) return rc;
+  T *dg = ps.as<T>(0), *w = dg + n, *pval = ps.as<T>(1), *ajj = pval + nch, *mval = ajj + 1;
+  int *pidx = ps.as<int>(2), *ctl = pidx + nch, *midx = ctl + 1, *pj = midx + 1, *rows = pj + n;
+  T *Am = reinterpret_cast<T *>(A->mat);
+  EventTimer tt, tp;
+  if ((rc = tt.start())) return rc;
+  forget_winv(A->mat);  // (A is overwritten)
+  // the largest diagonal entry: <= 0 or NaN -> rank 0, A unchanged; else the stopping value
+  launch_pstrf_init<T>(s, g, Am, 0, dg, w, pval, pidx);
+  launch_pstrf_max<T>(s, g, 0, pval, pidx, mval, midx);
+  HIPCHECK(hipMemsetAsync(ctl, 0, sizeof(int), s));
+  HIPCHECK(hipGetLastError());
+  T amax = T(0);
+  HIPCHECK(hipMemcpyAsync(&amax, mval, sizeof amax, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  if (!(amax > T(0))) {
+    *rank = 0;
+    return tt.stop(&st[0]) ? CHOL_ERR_HIP : 1;
+  }
+  const T dstop = tol < 0 ? T(n) * T(Lam<T>::eps) * amax : T(tol);
+  std::vector<int> hp((size_t)mb), hrows;
+  std::map<long, long> at;  // row -> the row whose content it holds after the interchanges so far
+  long stop = 0;
+  for (int k = 0; k < A->nt && !stop; ++k) {
+    const long k0 = (long)k * mb, k1 = std::min<long>(k0 + mb, n);
+    if ((rc = tp.start())) return rc;
+    if (k > 0) launch_pstrf_init<T>(s, g, Am, k0, dg, w, pval, pidx);
+    for (long j = k0; j < k1; ++j) launch_pstrf_step<T>(s, g, Am, j, k0, dstop, dg, w, pval, pidx, ctl, pj, ajj);
+    HIPCHECK(hipGetLastError());
+    int hctl = 0;
+    HIPCHECK(hipMemcpyAsync(&hctl, ctl, sizeof hctl, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(hp.data(), pj + k0, (size_t)(k1 - k0) * sizeof(int), hipMemcpyDeviceToHost, s));
+    if ((rc = tp.stop(&st[1]))) return rc;
+    stop = hctl;
+    const long jend = stop ? stop - 1 : k1;
+    st[4] += (double)(jend - k0);
+    // piv, and the composed interchanges of this tile column for the earlier ones
+    at.clear();
+    auto cur = [&](long r) {
+      auto it = at.find(r);
+      return it == at.end() ? r : it->second;
+    };
+    for (long j = k0; j < jend; ++j) {
+      const long p = hp[j - k0];
+      std::swap(piv[j], piv[p]);
+      const long a = cur(j), b = cur(p);
+      at[j] = b;
+      at[p] = a;
+    }
+    if (k0 > 0) {
+      hrows.clear();
+      for (const auto &e : at)
+        if (e.first != e.second) hrows.push_back((int)e.first);
+      const int m = (int)hrows.size();
+      for (int t = 0; t < m; ++t) hrows.push_back((int)at[hrows[t]]);
+      if (m > 0) {
+        if ((rc = tp.start())) return rc;
+        HIPCHECK(hipMemcpyAsync(rows, hrows.data(), 2 * (size_t)m * sizeof(int), hipMemcpyHostToDevice, s));
+        launch_pstrf_laswp<T>(s, g, Am, k0, rows, m);
+        HIPCHECK(hipGetLastError());
+        if ((rc = tp.stop(&st[2]))) return rc;
+      }
+    }
+    if (stop || k + 1 >= A->nt) continue;
+    // the trailing update by tile column k (chol_bench_update's call)
+    if ((rc = tp.start())) return rc;
+    PanelRef pan;
+    memset(&pan, 0, sizeof pan);
+    pan.P = 1;
+    pan.base[0] = Am + (size_t)k * A->lmt * A->bsizi;
+    const WorkRange rr = whole_col_range(A, k + 1, A->nt);
+    launch_trail_update<T>(s, whole_local_mat(A), A->d_list, rr.off, rr.na, rr.offb, rr.nb, pan);
+    HIPCHECK(hipGetLastError());
+    if ((rc = tp.stop(&st[3]))) return rc;
+  }
+  *rank = stop ? (int)(stop - 1) : (int)n;
+  if ((rc = tt.stop(&st[0]))) return rc;
+  return *rank < n ? 1 : 0;
+}
+
+// the Lower path, or Upper between two transposes of the storage (transpose_storage; a single tile whose edge is not a
+// multiple of 64 element by element)
+int pstrf_run(int uplo, chol_desc *A, int *piv, int *rank, double tol) {
+  const bool dbl = A->dtype == CHOL_REAL_DOUBLE;
+  const PsGeo g{A->lm, A->mb, A->mbi, A->lmt, (long)A->bsizi};
+  auto flip = [&]() {
+    if (A->mbi % 64 == 0) return transpose_storage(A);
+    if (dbl) launch_pstrf_transpose<double>(main_stream(), g, (double *)A->mat);
+    else launch_pstrf_transpose<float>(main_stream(), g, (float *)A->mat);
+  };
+  const bool up = uplo == CHOL_UPPER;
+  if (up) flip();
+  const int rc = dbl ? pstrf_impl<double>(A, piv, rank, tol) : pstrf_impl<float>(A, piv, rank, tol);
+  if (up) {
+    flip();
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(main_stream()));
+  }
+  return rc;
+}
+
 }  // namespace
 
 void cholmi::spd_release() {
@@ -1004,6 +1134,7 @@ void cholmi::spd_release() {
   iv.release();
   cn.release();
   rf.release();
+  ps.release();
 }
 
 // ---------------------------------------------------------------- the entry points (C linkage: include/cholmi.h)
@@ -1265,5 +1396,29 @@ int chol_last_posvx_stats(double *out8) {
   if (!out8) return fail(-1, "last_posvx_stats: NULL");
   std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
   for (int i = 0; i < 8; ++i) out8[i] = rf_stats[i];
+  return 0;
+}
+
+int chol_pstrf_tile(int uplo, chol_desc_t *A, int *piv, int *rank, double tol) {
+  return with_views({{A, true}}, [&]() -> int {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "pstrf_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "pstrf_tile: uplo");
+  if (!A) return fail(-2, "pstrf_tile: NULL descriptor");
+  int rc = resident_whole("pstrf_tile", A);
+  if (rc) return rc;
+  if (A->mt != A->nt || A->lm != A->ln) return fail(-2, "pstrf_tile: A is not square");
+  if (!piv) return fail(-3, "pstrf_tile: NULL piv");
+  if (!rank) return fail(-4, "pstrf_tile: NULL rank");
+  if (std::isnan(tol)) return fail(-5, "pstrf_tile: tol is NaN");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  return pstrf_run(uplo, A, piv, rank, tol);
+  });
+}
+
+int chol_last_pstrf_stats(double *out8) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "last_pstrf_stats before chol_init");
+  if (!out8) return fail(-1, "last_pstrf_stats: NULL");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  for (int i = 0; i < 8; ++i) out8[i] = ps_stats[i];
   return 0;
 }

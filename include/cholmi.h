@@ -298,6 +298,28 @@ int chol_last_posvx_stats(double *out8);
  * AF holds the factor of A; X is only read.  *ms <- the fastest of `reps` calls after a warm-up one. */
 int chol_bench_refine(int uplo, chol_desc_t *A, chol_desc_t *AF, chol_desc_t *X, int path, int reps, double *ms);
 
+/* LAPACK DPSTRF: P^T A P = L L^T (Lower) or U^T U (Upper) with complete pivoting, stopping when the largest
+ * remaining pivot is <= tol (tol < 0: n * eps * max_i A(i,i), eps = LAPACK's DLAMCH('Epsilon'), 2^-53 / 2^-24).
+ * piv: HOST array of n ints, 1-based (LAPACK's PIV: column j of P is column piv[j] of the identity).
+ * *rank: the number of pivots taken.  Returns 0 (rank = n), 1 (rank < n: semidefinite or rank deficient, as
+ * LAPACK's INFO = 1) or a negative argument position / CHOL_ERR_*.
+ *
+ * Device-resident single-process descriptors that chol_potrf_tile factors (ragged orders, tile edges that are not
+ * multiples of 128, sub-matrix views); a p x q block-cyclic descriptor returns CHOL_ERR_NOT_SUPPORTED.  fp64 or fp32
+ * by A's dtype (fp32 runs in single precision throughout, as SPSTRF).  Only the `uplo` triangle is read or written:
+ * the other strict triangle comes back bit for bit.  On return the first `rank` columns of the triangle hold L (Upper:
+ * the first `rank` rows hold U = L^T), its rows in pivoted order, those of columns finished before a later pivot
+ * included; with info = 1 columns rank+1 .. n are unspecified, as in LAPACK.  The largest diagonal entry <= 0 or NaN:
+ * rank = 0, info = 1, A unchanged and piv the identity.  As in LAPACK the first pivot is taken whatever tol is; a
+ * later step stops when its largest candidate is <= the stopping value or when any candidate is NaN (a NaN ranks
+ * above every number).  Among equal candidates the smallest index wins (LAPACK's MAXLOC).  No floating-point atomics
+ * and fixed reduction orders: a repeated call returns the same bits.  Argument errors: -1 uplo, -2 A, -3 piv NULL,
+ * -4 rank NULL, -5 tol NaN. */
+int chol_pstrf_tile(int uplo, chol_desc_t *A, int *piv, int *rank, double tol);
+/* The last chol_pstrf_tile [ms]: total, pivot steps, row interchanges of the finished columns, trailing updates,
+ * then the number of pivot steps; the rest 0. */
+int chol_last_pstrf_stats(double *out8);
+
 /* CHAMELEON_Lapack_to_Tile / Tile_to_Lapack equivalents (host LAPACK layout
  * <-> descriptor storage); single-process descriptors only. */
 int chol_lapack_to_tile(const void *A, int lda, chol_desc_t *desc);

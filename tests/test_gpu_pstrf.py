@@ -1,0 +1,319 @@
+"""The pivoted Cholesky factorisation CHAMELEON_dpstrf_Tile / CHAMELEON_spstrf_Tile (LAPACK DPSTRF / SPSTRF) against
+scipy's dpstrf / spstrf: pivots, rank, info, the residual of P^T A P = L L^T and the factor itself, full rank and rank
+deficient, Lower and Upper, fp64 and fp32, ragged orders and tiles that are not multiples of 128 -- with the other
+triangle NaN-filled and returned bit for bit, and repeated calls bit-identical."""
+import functools
+
+import numpy as np
+import pytest
+import scipy.linalg.lapack as lapack
+
+pytestmark = pytest.mark.gpu
+
+EPS = {"d": 2.0 ** -53, "s": 2.0 ** -24}
+
+
+def gram(n, r, seed, dtype=np.float64):
+    G = np.random.default_rng(seed).standard_normal((n, r))
+    return np.asfortranarray((G @ G.T).astype(dtype))
+
+
+@functools.lru_cache(maxsize=None)
+def full_rank(n, seed):
+    """a well-conditioned SPD Gram matrix (n x 2n factor) and its 2-norm condition number"""
+    A = gram(n, 2 * n, seed)
+    ev = np.linalg.eigvalsh(A)
+    return A, float(ev[-1] / ev[0])
+
+
+def npdt(dt):
+    return np.float64 if dt == "d" else np.float32
+
+
+def chdt(ch, dt):
+    return ch.ChamRealDouble if dt == "d" else ch.ChamRealFloat
+
+
+def uplo_of(ch, u):
+    return ch.ChamLower if u == "L" else ch.ChamUpper
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
+
+
+def stored(M, u, fill=np.nan):
+    """the lower triangle of the symmetric M stored in the `u` triangle, the other strict triangle = fill"""
+    n = M.shape[0]
+    S = np.array(np.tril(M) if u == "L" else np.triu(M.T), order="F")
+    idx = np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
+    S[idx] = fill
+    return S
+
+
+def desc(ch, N, B, dtype):
+    return ch.CHAMELEON_Desc_Create(None, dtype, B, B, B * B, N, N, 0, 0, N, N, 1, 1)
+
+
+def pstrf(ch, A, B, u="L", dt="d", tol=-1.0):
+    """-> (info, piv, rank, L as Lower, the stored matrix after the call, what was stored)"""
+    S = stored(A.astype(npdt(dt)), u)
+    d = desc(ch, A.shape[0], B, chdt(ch, dt))
+    d.from_lapack(S)
+    info, piv, rank = ch.CHAMELEON_dpstrf_Tile(uplo_of(ch, u), d, tol)
+    F = d.to_lapack()
+    ch.CHAMELEON_Desc_Destroy(d)
+    L = np.tril(F) if u == "L" else np.triu(F).T
+    return info, piv, rank, L, F, S
+
+
+def scipy_pstrf(A, dt="d", tol=-1.0):
+    fn = lapack.dpstrf if dt == "d" else lapack.spstrf
+    c, piv, rank, info = fn(np.asfortranarray(A.astype(npdt(dt))), tol=tol, lower=1)
+    return np.tril(c), piv, rank, info
+
+
+def residual(A, piv, L, rank):
+    """||(P^T A P - L L^T)(:, 1:rank)||_F / ||A||_F on the first rank columns"""
+    A = A.astype(np.float64)
+    P = A[np.ix_(piv - 1, piv - 1)]
+    Lr = L.astype(np.float64)[:, :rank]
+    return np.linalg.norm(P[:, :rank] - Lr @ Lr[:rank].T) / np.linalg.norm(A)
+
+
+def assert_other_triangle(F, S, u):
+    n = S.shape[0]
+    idx = np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
+    assert np.array_equal(bits(F[idx]), bits(S[idx]))
+
+
+# ------------------------------------------------------------------------------------------------------- full rank
+@pytest.mark.parametrize("N,B", [(1024, 256), (1000, 192), (2048, 512), (4096, 1024)])
+@pytest.mark.parametrize("u", ["L", "U"])
+@pytest.mark.parametrize("dt", ["d", "s"])
+def test_full_rank(cham, N, B, u, dt):
+    ch = cham
+    A, kappa = full_rank(N, N + B)
+    info, piv, rank, L, F, S = pstrf(ch, A, B, u, dt)
+    assert info == 0 and rank == N
+    assert sorted(piv) == list(range(1, N + 1))
+    Lref, ref_piv, ref_rank, ref_info = scipy_pstrf(A, dt)
+    assert ref_info == 0 and ref_rank == N
+    if dt == "d":
+        assert np.array_equal(piv, ref_piv)
+    res = residual(A.astype(npdt(dt)), piv, L, rank)
+    assert res <= 30 * N * EPS[dt], res
+    if np.array_equal(piv, ref_piv):
+        err = np.abs(L.astype(np.float64) - Lref).max() / np.abs(Lref).max()
+        assert err <= 10 * kappa * np.sqrt(N) * EPS[dt], (err, kappa)
+    assert_other_triangle(F, S, u)
+    st = ch.last_pstrf_stats()
+    assert st["steps"] == N and st["total_ms"] > 0 and st["steps_ms"] > 0
+
+
+# ------------------------------------------------------------------------------------------------- rank deficient
+@pytest.mark.parametrize("r", [1, 37, 256, 261, 512, 1023])
+@pytest.mark.parametrize("u", ["L", "U"])
+def test_rank_deficient(cham, r, u):
+    ch = cham
+    N, B = 1024, 256
+    A = gram(N, r, r)
+    info, piv, rank, L, F, S = pstrf(ch, A, B, u)
+    _, ref_piv, ref_rank, ref_info = scipy_pstrf(A)
+    assert rank == r == ref_rank and info == 1 == ref_info
+    assert sorted(piv) == list(range(1, N + 1))
+    assert np.array_equal(piv[:rank], ref_piv[:rank])
+    assert residual(A, piv, L, rank) <= 30 * N * EPS["d"]  # (the rows of L match piv)
+    assert_other_triangle(F, S, u)
+    assert ch.last_pstrf_stats()["steps"] == r
+
+
+@pytest.mark.parametrize("r", [5, 300])
+def test_rank_deficient_fp32(cham, r):
+    ch = cham
+    N, B = 1000, 192
+    A = gram(N, r, 3 * r)
+    info, piv, rank, L, F, S = pstrf(ch, A, B, "L", "s")
+    _, _, ref_rank, _ = scipy_pstrf(A, "s")
+    assert info == 1 and rank == ref_rank
+    assert residual(A.astype(np.float32), piv, L, rank) <= 30 * N * EPS["s"]
+
+
+@pytest.mark.parametrize("tol", [1e-2, 1e-6, 1e-10])
+def test_explicit_tol(cham, tol):
+    ch = cham
+    N, B = 1024, 256
+    s = np.logspace(0, -6, N)
+    A = np.asfortranarray(gram(N, N, 9) * np.outer(s, s))
+    info, piv, rank, L, _, _ = pstrf(ch, A, B, tol=tol)
+    _, ref_piv, ref_rank, ref_info = scipy_pstrf(A, tol=tol)
+    assert rank == ref_rank and info == ref_info
+    assert np.array_equal(piv[:rank], ref_piv[:rank])
+
+
+def test_pivots_from_the_last_tile_column(cham):
+    """an increasing diagonal: every pivot comes from far below, the first from the last tile column"""
+    ch = cham
+    N, B = 1024, 256
+    G = gram(N, 2 * N, 10)
+    s = np.linspace(1.0, 4.0, N) / np.sqrt(np.diag(G))
+    A = np.asfortranarray(G * np.outer(s, s))
+    info, piv, rank, L, _, _ = pstrf(ch, A, B)
+    _, ref_piv, _, _ = scipy_pstrf(A)
+    assert info == 0 and piv[0] == N
+    assert np.array_equal(piv, ref_piv)
+    assert residual(A, piv, L, rank) <= 30 * N * EPS["d"]
+
+
+@pytest.mark.parametrize("N,B", [(1000, 192), (700, 320)])
+def test_padding_is_never_chosen(cham, N, B):
+    """a ragged order in tiles that are not multiples of 128: the padded image's identity entries would outrank a
+    diagonal scaled by 1e-3"""
+    ch = cham
+    A = np.asfortranarray(full_rank(N, 11)[0] * 1e-3 / (2 * N))
+    assert np.diag(A).max() < 1
+    info, piv, rank, L, _, _ = pstrf(ch, A, B)
+    _, ref_piv, _, _ = scipy_pstrf(A)
+    assert info == 0 and rank == N
+    assert np.array_equal(piv, ref_piv)
+    assert residual(A, piv, L, rank) <= 30 * N * EPS["d"]
+
+
+@pytest.mark.parametrize("u", ["L", "U"])
+def test_deterministic(cham, u):
+    ch = cham
+    N, B = 2048, 256
+    A = gram(N, 700, 12)
+    a = pstrf(ch, A, B, u)
+    b = pstrf(ch, A, B, u)
+    assert np.array_equal(bits(a[4]), bits(b[4]))
+    assert np.array_equal(a[1], b[1]) and a[2] == b[2] == 700
+
+
+# ------------------------------------------------------------------------------------------------------- edge cases
+@pytest.mark.parametrize("u", ["L", "U"])
+def test_early_exit(cham, u):
+    ch = cham
+    N, B = 512, 128
+    for A in (np.zeros((N, N)), -np.eye(N) + 0.01 * np.ones((N, N))):
+        info, piv, rank, _, F, S = pstrf(ch, A, B, u)
+        assert info == 1 and rank == 0
+        assert np.array_equal(piv, np.arange(1, N + 1))
+        assert np.array_equal(bits(F), bits(S))  # A unchanged
+
+
+def test_nan_stops(cham):
+    ch = cham
+    N, B = 512, 128
+    A = full_rank(N, 13)[0].copy()
+    A[300, 300] = np.nan
+    info, _, rank, _, _, _ = pstrf(ch, A, B)
+    assert info == 1 and rank < N
+    # a NaN that appears during the factorisation: an entry off the diagonal
+    A = full_rank(N, 13)[0].copy()
+    A[400, 200] = A[200, 400] = np.nan
+    info, _, rank, _, _, _ = pstrf(ch, A, B)
+    assert info == 1 and rank < N
+
+
+@pytest.mark.parametrize("B", [1, 64, 128])
+def test_order_one(cham, B):
+    ch = cham
+    info, piv, rank, L, _, _ = pstrf(ch, np.array([[4.0]]), B)
+    assert (info, list(piv), rank, L[0, 0]) == (0, [1], 1, 2.0)
+    info, piv, rank, _, _, _ = pstrf(ch, np.array([[0.0]]), B)
+    assert (info, list(piv), rank) == (1, [1], 0)
+
+
+def test_single_tile_not_a_multiple_of_64(cham):
+    ch = cham
+    N = 100
+    A = gram(N, 60, 14)
+    for u in ("L", "U"):
+        info, piv, rank, L, F, S = pstrf(ch, A, N, u)
+        _, ref_piv, ref_rank, _ = scipy_pstrf(A)
+        assert info == 1 and rank == ref_rank == 60
+        assert np.array_equal(piv[:rank], ref_piv[:rank])
+        assert residual(A, piv, L, rank) <= 30 * N * EPS["d"]
+        assert_other_triangle(F, S, u)
+
+
+def test_argument_errors(cham):
+    from dense_linear_app_amd._lib import lib
+    import ctypes as C
+
+    ch = cham
+    N, B = 256, 128
+    d = desc(ch, N, B, ch.ChamRealDouble)
+    d.from_lapack(full_rank(N, 15)[0])
+    piv = (C.c_int * N)()
+    r = C.c_int()
+    assert lib().chol_pstrf_tile(7, d.handle, piv, C.byref(r), -1.0) == -1
+    assert lib().chol_pstrf_tile(ch.ChamLower, None, piv, C.byref(r), -1.0) == -2
+    assert lib().chol_pstrf_tile(ch.ChamLower, d.handle, None, C.byref(r), -1.0) == -3
+    assert lib().chol_pstrf_tile(ch.ChamLower, d.handle, piv, None, -1.0) == -4
+    assert lib().chol_pstrf_tile(ch.ChamLower, d.handle, piv, C.byref(r), float("nan")) == -5
+    assert lib().chol_last_pstrf_stats(None) == -1
+    with pytest.raises(ch.CholmiError) as e:
+        ch.CHAMELEON_dpstrf_Tile(7, d)
+    assert e.value.code == -1
+    rect = ch.CHAMELEON_Desc_Create(None, ch.ChamRealDouble, B, B, B * B, N, 2 * N, 0, 0, N, 2 * N, 1, 1)
+    with pytest.raises(ch.CholmiError) as e:
+        ch.CHAMELEON_dpstrf_Tile(ch.ChamLower, rect)
+    assert e.value.code == -2
+
+
+def test_pxq_descriptor_is_not_supported(cham):
+    from dense_linear_app_amd._lib import lib
+
+    ch = cham
+    lib().chol_set_transport(None)
+    ch.set_rank(0, 2)
+    try:
+        d = ch.CHAMELEON_Desc_Create(None, ch.ChamRealDouble, 256, 256, 256 * 256, 1024, 1024, 0, 0, 1024, 1024, 1, 2)
+        with pytest.raises(ch.CholmiError) as e:
+            ch.CHAMELEON_dpstrf_Tile(ch.ChamLower, d)
+        assert e.value.code == -104  # CHOL_ERR_NOT_SUPPORTED
+        ch.CHAMELEON_Desc_Destroy(d)
+    finally:
+        ch.set_rank(0, 1)
+
+
+def test_sub_matrix_view(cham):
+    """a tile-aligned view of a device user buffer gives the factor of the whole-matrix descriptor; the user's tiles
+    outside the view stay as they were"""
+    import torch
+
+    ch = cham
+    mb, lt, oi, oj, vt = 256, 5, 1, 2, 3
+    lm, m = lt * mb, vt * mb
+    user = np.random.default_rng(16).standard_normal(lt * lt * mb * mb)
+    buf = torch.from_numpy(user.copy()).cuda()
+    A = gram(m, 500, 16)
+    v = ch.CHAMELEON_Desc_Create(buf, ch.ChamRealDouble, mb, mb, mb * mb, lm, lm, oi * mb, oj * mb, m, m, 1, 1)
+    v.from_lapack(A)
+    info, piv, rank = ch.CHAMELEON_dpstrf_Tile(ch.ChamLower, v)
+    Lv = np.tril(v.to_lapack())
+    ch.CHAMELEON_Desc_Destroy(v)
+    info2, piv2, rank2, L2, _, _ = pstrf(ch, A, mb)
+    assert (info, rank) == (info2, rank2) == (1, 500)
+    assert np.array_equal(piv, piv2)
+    assert np.array_equal(bits(Lv[:, :rank]), bits(L2[:, :rank]))
+    now = buf.cpu().numpy().reshape(lt * lt, mb * mb)
+    before = user.reshape(lt * lt, mb * mb)
+    for J in range(lt):
+        for I in range(lt):
+            if not (oi <= I < oi + vt and oj <= J < oj + vt):
+                assert np.array_equal(now[I + J * lt], before[I + J * lt]), (I, J)
+
+
+def test_large(cham):
+    ch = cham
+    N, B = 8192, 512
+    A = gram(N, N + 512, 17)
+    info, piv, rank, L, _, _ = pstrf(ch, A, B)
+    _, ref_piv, ref_rank, _ = scipy_pstrf(A)
+    assert info == 0 and rank == ref_rank == N
+    assert np.array_equal(piv, ref_piv)
+    assert residual(A, piv, L, rank) <= 30 * N * EPS["d"]
