@@ -534,75 +534,187 @@ __device__ __forceinline__ bool map_update_block(const int2 *__restrict__ list, 
 
 // ------------------------------------------------------------------------------
 // The same trailing update with EIGHT waves per workgroup (fp64): 2 x 4 waves, each 64 rows x 32
-// columns of the 128 x 128 block, two workgroups per CU = four waves per SIMD instead of two.  Every
-// wave still stalls once per K-slice (fragment read after the barrier, the barrier itself, the DMA
-// issue); with four independent MFMA streams per SIMD the matrix pipe finds a ready wave more often.
-// Costs: 3 fragment reads per 8 MFMAs instead of 4 per 16, and <= 128 VGPRs per wave.
+// columns of the 128 x 128 block, two workgroups per CU = four waves per SIMD instead of two.  With
+// four independent MFMA streams per SIMD the matrix pipe finds a ready wave more often.  Costs: 3
+// fragment reads per 8 MFMAs instead of 4 per 16, and <= 120 VGPRs per wave (the guest kernels of
+// the panel chain must fit beside two of these workgroups: tests/test_host_api.py).
+//
+// The operands are fed through a four-stage LDS ring in the 64 KiB a double buffer of 16-deep
+// slices used to take: NST = 4 stages of BKR = 8 k-rows per operand (16 KiB per stage).  One k-row
+// of 128 fp64 is one 1-KiB LDS-DMA piece, so wave w moves k-row w of every stage, one piece per
+// operand: a uniform row address advanced by 8 rows per stage plus lane * 16 B, fixed for the loop.
+// Stage s (two k-groups of 4, 8 MFMAs each per wave):
+//   group 0: MFMA 0 | fragment reads of (s, group 1) | 7 MFMAs
+//   vmcnt(2) -- stage s+1's DMA is done, stage s+2's stays in flight -- and the barrier that
+//   publishes stage s+1 and frees the slot of stage s-1 (every wave has finished its MFMAs)
+//   group 1: MFMA 0 | fragment reads of (s+1, group 0) | [guest poll] | DMA of stage s+3 | 7 MFMAs
+// so the first fragments of a stage are read under the last MFMAs of the stage before it (no LDS
+// round trip behind a barrier), and a stage's DMA has three k-groups of MFMAs to land before the
+// barrier that waits for it (a counted wait: the two stages behind it are never drained).  One
+// barrier per 8 k; the guest slot is polled once per 16 k (issued ahead of the DMA, so that the
+// counted wait covers it, and looked at behind the next stage's wait).  The k order of every
+// accumulator is that of the double-buffered loop (bit-identical results).  The last stage's
+// barrier is also what lets a second call (the paired launch) refill slots 0-2 right away.
+// MODE bit 1: static priority 1 for waves 4-7 (bit 0, the DMA behind the groups' first MFMAs, is
+// what the ring does in any case).
 // ------------------------------------------------------------------------------
-// MODE bit 0: the next slice's DMA is issued behind the first MFMAs of k-groups 0 and 1 instead of
-// in one burst between the barrier and the slice's first MFMA; bit 1: static priority 1 for waves 4-7
+constexpr int BKR = 8, NST = 4;
+template <typename T>
+struct alignas(16) SmemR {
+  T a[NST][BKR][MACRO];
+  T b[NST][BKR][MACRO];
+};
+static_assert(sizeof(SmemR<double>) == sizeof(SmemP<double>), "the ring takes the double buffer's 64 KiB");
+
+#ifdef CHOLMI_KLOOP_STAMPS
+// Diagnostic build only (make ... CXXFLAGS+=-DCHOLMI_KLOOP_STAMPS; never in the shipped library): per-wave
+// s_memtime stamps of the first KST_STAGES stages of the first K-loop of workgroups 0 .. KST_WGS-1, to a
+// buffer of their own (read by chol_debug_kloop_stamps).  Record of a wave: memtime and memrealtime at
+// the loop's start and end, then per stage: start, after the DMA issue, before the counted wait, after
+// the barrier, after the first fragment wait behind it.
+constexpr int KST_WGS = 16, KST_STAGES = 64, KST_REC = 4 + 5 * KST_STAGES;
+__device__ unsigned long long g_kloop_stamps[KST_WGS * 8 * KST_REC];
+#define KST_ON_STAGE(s) (kst_on && (s) < KST_STAGES)
+#define KSTAMP(on, idx)                                                                    \
+  do {                                                                                     \
+    if (on) {                                                                              \
+      __builtin_amdgcn_sched_barrier(0);                                                   \
+      unsigned long long t_;                                                               \
+      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
+      if (lane == 0) kst[idx] = t_;                                                        \
+      __builtin_amdgcn_sched_barrier(0);                                                   \
+    }                                                                                      \
+  } while (0)
+#else
+#define KST_ON_STAGE(s) false
+#define KSTAMP(on, idx) \
+  do {                  \
+  } while (0)
+#endif
+
 template <typename T, int MODE>
 __device__ __forceinline__ void nt_kloop_w8(const T *__restrict__ A, int lda, const T *__restrict__ B, int ldb,
-                                            int K, typename Tr<T>::acc_t (&acc)[4][2], SmemP<T> &sm,
+                                            int K, typename Tr<T>::acc_t (&acc)[4][2], SmemR<T> &sm,
                                             const int *yslot) {
   static_assert(sizeof(T) == 8, "fp64 only");
+  static_assert(BKR * MACRO * (int)sizeof(T) == 8 * 1024, "one 1-KiB piece per operand, wave and stage");
   using vec_t = typename Tr<T>::vec_t;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, wr = w & 1, wc = w >> 1, i = lane & 15, q = lane >> 4;
-  constexpr int PIECES = BK * MACRO * (int)sizeof(T) / 1024, EPP = 1024 / (int)sizeof(T);
-  auto dma_piece = [&](int buf, int k0, int p) {
-    const int piece = p * 8 + w;
-    const int e = piece * EPP + lane * 2;
-    const int kk = e / MACRO, r = e % MACRO;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void *)(A + r + (size_t)(k0 + kk) * lda),
-        (__attribute__((address_space(3))) void *)(&sm.a[buf][0][0] + piece * EPP), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void *)(B + r + (size_t)(k0 + kk) * ldb),
-        (__attribute__((address_space(3))) void *)(&sm.b[buf][0][0] + piece * EPP), 16, 0, 0);
+  const int wu = __builtin_amdgcn_readfirstlane(w);
+  // k-row wu of stage 0; every stage moves both rows on by BKR rows (uniform), each lane by 16 B
+  const char *ga = reinterpret_cast<const char *>(A + (size_t)wu * lda);
+  const char *gb = reinterpret_cast<const char *>(B + (size_t)wu * ldb);
+  const size_t da = (size_t)BKR * lda * sizeof(T), db = (size_t)BKR * ldb * sizeof(T);
+  const unsigned lo = (unsigned)lane * 16u;
+  auto dma = [&](int slot) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(ga + lo),
+                                     (__attribute__((address_space(3))) void *)(&sm.a[slot][wu][0]), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gb + lo),
+                                     (__attribute__((address_space(3))) void *)(&sm.b[slot][wu][0]), 16, 0, 0);
+    ga += da;
+    gb += db;
   };
-  auto dma = [&](int buf, int k0) {
-#pragma unroll
-    for (int p = 0; p < PIECES / 8; ++p) dma_piece(buf, k0, p);
-  };
-  static_assert(PIECES / 8 == 2, "two pieces per operand per wave and slice");
+  // The poll is issued whether or not there is a slot to poll (then it reads the operand, and nobody looks
+  // at the value): a load on one path only leaves the compiler's own wait for it at vmcnt(0).
+  const int *poll = yslot ? yslot : reinterpret_cast<const int *>(A);
   vec_t fa[2][2], fb[2];
   const int arow = wr * 64 + 2 * i, brow = wc * 32 + 2 * i;
   if (MODE & 2) {
     if (w >= 4) __builtin_amdgcn_s_setprio(1);
   }
-  auto fread = [&](int set, int cur, int ks) {
+  auto fread = [&](int set, int slot, int ks) {
 #pragma unroll
-    for (int g = 0; g < 2; ++g) fa[set][g] = *reinterpret_cast<const vec_t *>(&sm.a[cur][ks * 4 + q][arow + 32 * g]);
-    fb[set] = *reinterpret_cast<const vec_t *>(&sm.b[cur][ks * 4 + q][brow]);
+    for (int g = 0; g < 2; ++g) fa[set][g] = *reinterpret_cast<const vec_t *>(&sm.a[slot][ks * 4 + q][arow + 32 * g]);
+    fb[set] = *reinterpret_cast<const vec_t *>(&sm.b[slot][ks * 4 + q][brow]);
   };
-  dma(0, 0);
-  __syncthreads();
-  const int nk = K / BK;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    int guest = 0;
-    if (yslot) guest = __hip_atomic_load(yslot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    fread(0, cur, 0);
-    if (!(MODE & 1) && kt + 1 < nk) dma(cur ^ 1, (kt + 1) * BK);
+  auto mfma_rest = [&](int set) {  // the group's MFMAs after its first
 #pragma unroll
-    for (int ks = 0; ks < BK / 4; ++ks) {
-      __builtin_amdgcn_sched_barrier(0);
-      acc[0][0] = Tr<T>::mfma(fb[ks & 1][0], fa[ks & 1][0][0], acc[0][0]);
-      __builtin_amdgcn_sched_barrier(0);
-      if (ks + 1 < BK / 4) fread((ks + 1) & 1, cur, ks + 1);
-      if ((MODE & 1) && ks < 2 && kt + 1 < nk) dma_piece(cur ^ 1, (kt + 1) * BK, ks);
-      __builtin_amdgcn_sched_barrier(0);
+    for (int a = 0; a < 4; ++a)
 #pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-          if (a + b > 0) acc[a][b] = Tr<T>::mfma(fb[ks & 1][b], fa[ks & 1][a >> 1][a & 1], acc[a][b]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (yslot && __builtin_amdgcn_readfirstlane(guest) != 0) yield_to_guest(yslot);
-    __syncthreads();
+      for (int b = 0; b < 2; ++b)
+        if (a + b > 0) acc[a][b] = Tr<T>::mfma(fb[set][b], fa[set][a >> 1][a & 1], acc[a][b]);
+  };
+#ifdef CHOLMI_KLOOP_STAMPS
+  const bool kst_on = blockIdx.x < KST_WGS;  // (a second call, the paired launch's, stamps over the first)
+  unsigned long long *kst = g_kloop_stamps + ((size_t)blockIdx.x * 8 + wu) * KST_REC;
+  if (kst_on && lane == 0) {
+    kst[0] = __builtin_amdgcn_s_memtime();
+    kst[1] = __builtin_amdgcn_s_memrealtime();
   }
+  __builtin_amdgcn_s_waitcnt(0xC07F);
+#endif
+  // s_waitcnt vmcnt(n) alone (expcnt, lgkmcnt at their maxima): as a builtin, so that the compiler's own wait
+  // insertion knows which LDS-DMA writes are done and adds none in front of the fragment reads
+  constexpr int VMCNT0 = 0x0F70;
+  const int ns = K / BKR;  // a multiple of NST: K is a multiple of MACRO
+  dma(0);
+  dma(1);
+  dma(2);
+  __builtin_amdgcn_s_waitcnt(VMCNT0 + 4);  // stage 0 in
+  asm volatile("s_barrier" ::: "memory");
+  fread(0, 0, 0);
+  // four stages, slots 0 .. 3; MORE: stages s0 + 4 .. exist (false for the last four, a separate copy of
+  // the code, so that the steady state has no branch around its waits and DMA)
+  auto quad = [&](int s0, auto more_c) {
+    constexpr bool MORE = decltype(more_c)::value;
+    int guest;
+    static_for<0, NST>([&](auto jc) {
+      constexpr int j = decltype(jc)::value;  // stage s0 + j, in slot j
+      const int s = s0 + j;
+      const bool st = KST_ON_STAGE(s);
+      (void)st;
+      (void)s;
+      KSTAMP(st, 4 + 5 * s + 0);
+      // group 0
+      __builtin_amdgcn_sched_barrier(0);
+      acc[0][0] = Tr<T>::mfma(fb[0][0], fa[0][0][0], acc[0][0]);
+      __builtin_amdgcn_sched_barrier(0);
+      fread(1, j, 1);
+      __builtin_amdgcn_sched_barrier(0);
+      mfma_rest(0);
+      __builtin_amdgcn_sched_barrier(0);
+      KSTAMP(st, 4 + 5 * s + 2);
+      // stage s+1 in (its DMA was issued in stage s-2); s+2's, if it exists, stays in flight
+      __builtin_amdgcn_s_waitcnt(VMCNT0 + ((j < 2 || MORE) ? 2 : 0));
+      if ((j & 1) && yslot && __builtin_amdgcn_readfirstlane(guest) != 0) yield_to_guest(yslot);
+      asm volatile("s_barrier" ::: "memory");
+      KSTAMP(st, 4 + 5 * s + 3);
+      KSTAMP(st, 4 + 5 * s + 4);
+      // group 1
+      __builtin_amdgcn_sched_barrier(0);
+      acc[0][0] = Tr<T>::mfma(fb[1][0], fa[1][0][0], acc[0][0]);
+      __builtin_amdgcn_sched_barrier(0);
+      if (j < NST - 1 || MORE) fread(0, (j + 1) % NST, 0);
+      if (!(j & 1)) guest = __hip_atomic_load(poll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (j == 0 || MORE) dma((j + 3) % NST);
+      __builtin_amdgcn_sched_barrier(0);
+      KSTAMP(st, 4 + 5 * s + 1);
+      mfma_rest(1);
+      __builtin_amdgcn_sched_barrier(0);
+    });
+  };
+  int s0 = 0;
+  for (; s0 < ns - NST; s0 += NST) quad(s0, std::true_type{});
+  quad(s0, std::false_type{});
+#ifdef CHOLMI_KLOOP_STAMPS
+  if (kst_on && lane == 0) {
+    kst[2] = __builtin_amdgcn_s_memtime();
+    kst[3] = __builtin_amdgcn_s_memrealtime();
+  }
+#endif
 }
+#ifdef CHOLMI_KLOOP_STAMPS
+}  // namespace cholmi
+extern "C" __attribute__((visibility("default"))) int chol_debug_kloop_stamps(unsigned long long *out, int n) {
+  const int all = cholmi::KST_WGS * 8 * cholmi::KST_REC;
+  if (n > all) n = all;
+  if (hipDeviceSynchronize() != hipSuccess ||
+      hipMemcpyFromSymbol(out, HIP_SYMBOL(cholmi::g_kloop_stamps), (size_t)n * sizeof(unsigned long long)) != hipSuccess)
+    return -1;
+  return n;
+}
+namespace cholmi {
+#endif
 
 // Cout = Cin - acc for one 128 x 128 block (eight waves, the accumulator layout of nt_kloop_w8): lane (i, q) holds rows
 // 2i, 2i+1 (+32g) of column 32 wc + 2 (q + 4r) + b.  lower: the block lies on the diagonal of a diagonal tile -- only
@@ -651,7 +763,7 @@ __device__ __forceinline__ void w8_epilogue(const T *Cin, T *Cout, int ld,
 template <typename T, int MODE>
 __device__ __forceinline__ void trail_update_w8_block(const LocalMat &C, const int2 *__restrict__ list, int na, int offb,
                                                       int nb, int blocks_a, const PanelRef &pan, int nbm, int unit,
-                                                      const int *ytab, const PanelRef &pan2, int npan, SmemP<T> &sm, int b) {
+                                                      const int *ytab, const PanelRef &pan2, int npan, SmemR<T> &sm, int b) {
   using vec_t = typename Tr<T>::vec_t;
   BlockMap bm;
   if (!map_update_block(list, na, offb, nb, nbm, blocks_a, unit, bm, b)) return;
@@ -680,7 +792,7 @@ template <typename T, int MODE>
 __global__ __launch_bounds__(512, 4) void k_trail_update_w8(LocalMat C, const int2 *__restrict__ list, int na,
                                                              int offb, int nb, int blocks_a, PanelRef pan, int nbm,
                                                              int unit, const int *ytab, PanelRef pan2, int npan) {
-  __shared__ SmemP<T> sm;
+  __shared__ SmemR<T> sm;
   trail_update_w8_block<T, MODE>(C, list, na, offb, nb, blocks_a, pan, nbm, unit, ytab, pan2, npan, sm, (int)blockIdx.x);
 }
 
@@ -852,7 +964,7 @@ template <typename T, int MODE>
 __global__ __launch_bounds__(512, 4) void k_update_ptrs_w8(const T *const *__restrict__ cin, const T *const *__restrict__ ap,
                                                             const T *const *__restrict__ bp, T *const *__restrict__ cout,
                                                             int n, int mb, int nbm, int unit, const int *ytab) {
-  __shared__ SmemP<T> sm;
+  __shared__ SmemR<T> sm;
   int t, mi, mj;
   if (!map_ptr_block(n, nbm, unit, t, mi, mj)) return;
   const T *A = ap[t], *B = bp[t];
