@@ -2,7 +2,8 @@
 CPU oracle's wave DAG on the same input, plus size-independent properties at scale.
 
 Stated tolerances: fp64 ||tril(L)tril(L)^T - A||_F/||A||_F <= 1e-13 and
-GPU-vs-oracle max|dL|/max|L| <= 1e-12; fp32 residual <= 5e-5, max|dL|/max|L| <= 1e-4.
+GPU-vs-oracle max|dL|/max|L| <= 1e-12; fp32 residual <= 5e-5, max|dL|/max|L| <= 1e-4, and over the strictly lower
+triangle, normalised by its own maximum, <= 3e-5.
 """
 import os
 
@@ -11,6 +12,17 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
+
+
+# plgsy's diagonal (about N) dominates max|L|, so the max-relative bound above barely sees the strictly lower
+# triangle, which the trailing update writes: there the error is also normalised by that triangle's own maximum.
+# Measured on the MI355X against the oracle's fp64 factor: at most 2.5e-6 (N = 2048 ... 4096, default, paired and
+# flow-form schedules); an fp32 update that skips its last K-slice gives 1.7e-3 ... 4.8e-3 and passes the bound above.
+FP32_SL = 3e-5
+
+
+def strictly_lower_error(L, Lref):
+    return np.abs(np.tril(L - Lref, -1)).max() / np.abs(np.tril(Lref, -1)).max()
 
 
 def full_desc(ch, N, B, dtype=None):
@@ -124,6 +136,10 @@ def test_full_potrf_fp32(cham, orc):
     Lref = np.tril(orc.tile_to_lapack(T.astype(np.float64), N, B))
     L = np.tril(d.to_lapack().astype(np.float64))
     assert np.abs(L - Lref).max() / np.abs(Lref).max() <= 1e-4
+    # the oracle's fp32 factor is itself about 2e-5 off in the strictly lower triangle: that check is against its fp64 one
+    T = orc.plgsy_tiles(N // B, B, float(N), 42)
+    assert orc.tiled_potrf(T, N // B, B) == 0
+    assert strictly_lower_error(L, np.tril(orc.tile_to_lapack(T, N, B))) <= FP32_SL
 
 
 @pytest.mark.parametrize("N,B", [(16384, 512), (32768, 512), (32768, 1024)])
@@ -461,6 +477,7 @@ def test_walker_schedule_variants_match_the_oracle(env, orc):
     Lref = np.tril(orc.tile_to_lapack(T, N, B))
     assert np.abs(np.tril(Ld) - Lref).max() / np.abs(Lref).max() <= 1e-12
     assert np.abs(np.tril(Ls).astype(np.float64) - Lref).max() / np.abs(Lref).max() <= 1e-4
+    assert strictly_lower_error(np.tril(Ls).astype(np.float64), Lref) <= FP32_SL
 
 
 FLOW_ALL = {"CHOLMI_FLOW_FACTOR": "100", "CHOLMI_PIPE_FACTOR": "100", "CHOLMI_PAIR_FACTOR": "1000"}
@@ -510,6 +527,7 @@ def test_flow_form_of_the_tile_potrf_matches_the_oracle(N, B, env, orc):
     Lref = np.tril(orc.tile_to_lapack(T, N, B))
     assert np.abs(np.tril(Ld) - Lref).max() / np.abs(Lref).max() <= 1e-12
     assert np.abs(np.tril(Ls).astype(np.float64) - Lref).max() / np.abs(Lref).max() <= 1e-4
+    assert strictly_lower_error(np.tril(Ls).astype(np.float64), Lref) <= FP32_SL
 
 
 def test_flow_form_reports_a_failed_pivot_and_ends(orc):
