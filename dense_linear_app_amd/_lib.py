@@ -70,6 +70,8 @@ def lib() -> C.CDLL:
         "chol_bench_refine": ([i, vp, vp, vp, i, i, C.POINTER(d)], i),
         "chol_pstrf_tile": ([i, vp, C.POINTER(i), C.POINTER(i), d], i),
         "chol_last_pstrf_stats": ([C.POINTER(d)], i),
+        "chol_sygst_tile": ([i, i, vp, vp], i),
+        "chol_last_sygst_stats": ([C.POINTER(d)], i),
         "chol_lapack_to_tile": ([vp, i, vp], i),
         "chol_tile_to_lapack": ([vp, vp, i], i),
         "chol_tile_upload": ([vp, i, i, vp], i),

@@ -382,6 +382,22 @@ def last_pstrf_stats() -> dict:
     return {"total_ms": v[0], "steps_ms": v[1], "laswp_ms": v[2], "update_ms": v[3], "steps": int(v[4])}
 
 
+def CHAMELEON_dsygst_Tile(itype: int, uplo: int, A: Desc, B: Desc) -> int:
+    """LAPACK DSYGST with itype 1: the `uplo` triangle of A <- that of inv(L) A inv(L)^T (ChamLower, B = L L^T) or
+    inv(U^T) A inv(U) (ChamUpper, B = U^T U), B the factor chol_potrf_tile returned.  Returns 0, or info > 0: the
+    1-based index of a zero on B's diagonal (A unchanged).  itype 2 and 3 raise (CHOL_ERR_NOT_SUPPORTED)."""
+    return check("chol_sygst_tile", lib().chol_sygst_tile(itype, uplo, A.handle, B.handle))
+
+
+def last_sygst_stats() -> dict:
+    """The last CHAMELEON_dsygst_Tile (chol_last_sygst_stats): total, diagonal-tile inverses, chain (diagonal tiles,
+    panel TRSM, the two SYMMs), rank-2k updates and deferred-solve time [ms], and the number of steps."""
+    v = (C.c_double * 8)()
+    check("chol_last_sygst_stats", lib().chol_last_sygst_stats(v))
+    return {"total_ms": v[0], "diag_inv_ms": v[1], "chain_ms": v[2], "syr2k_ms": v[3], "solve_ms": v[4],
+            "steps": int(v[5])}
+
+
 CHAMELEON_spotrs_Tile = CHAMELEON_dpotrs_Tile
 CHAMELEON_sposv_Tile = CHAMELEON_dposv_Tile
 CHAMELEON_slacpy_Tile = CHAMELEON_dlacpy_Tile
@@ -398,6 +414,7 @@ CHAMELEON_slaqsy_Tile = CHAMELEON_dlaqsy_Tile
 CHAMELEON_sporfs_Tile = CHAMELEON_dporfs_Tile
 CHAMELEON_sposvx_Tile = CHAMELEON_dposvx_Tile
 CHAMELEON_spstrf_Tile = CHAMELEON_dpstrf_Tile
+CHAMELEON_ssygst_Tile = CHAMELEON_dsygst_Tile
 
 
 def residual_plgsy(L: Desc, bump: float, seed: int) -> float:

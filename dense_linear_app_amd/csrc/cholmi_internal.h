@@ -150,6 +150,12 @@ template <typename T>
 void launch_trail_update(hipStream_t s, const LocalMat &C, const int2 *d_list, int off, int na, int offb,
                          int nb, const PanelRef &pan, bool yield = false, const PanelRef *pan2 = nullptr);
 
+// sygst's rank-2k update (LAPACK DSYR2K, Lower): C(i,j) -= P(i) Q(j)^T + Q(i) P(j)^T for the same (i,j) list and
+// with the same block map as launch_trail_update; P = pan, Q = qan (kernels.hip: k_syr2k_w8, k_syr2k_w8f)
+template <typename T>
+void launch_syr2k_update(hipStream_t s, const LocalMat &C, const int2 *d_list, int off, int na, int offb, int nb,
+                         const PanelRef &pan, const PanelRef &qan);
+
 // In-tile blocked POTRF of one mb x mb tile (device pointer, ld = mb).  Writes the
 // inverses of the MACRO x MACRO diagonal blocks of L to winv (mb/MACRO blocks of
 // MACRO*MACRO elements, ld = MACRO).  info: device int, set to info_base + j (1-based)
@@ -423,6 +429,19 @@ void launch_pstrf_laswp(hipStream_t s, const PsGeo &g, T *A, long ncols, const i
 // A(r,c) <-> A(c,r) for r > c, any tile geometry (the Upper path of a single tile whose edge is not a multiple of 64)
 template <typename T>
 void launch_pstrf_transpose(hipStream_t s, const PsGeo &g, T *A);
+
+// ---- launchers (sygst.hip): chol_sygst_tile (LAPACK DSYGST, itype 1, Lower) on a single-process image ----
+// one diagonal tile D (e x e, ld e) <- the lower triangle of X S X^T on its rows and columns < nv, S the symmetric
+// expansion of D's lower triangle (the identity beyond e), X (E x E, ld E; E >= e, a multiple of 128) lower
+// triangular: L(k,k)^{-1}.  S, W, C: E x E scratch each; afterwards C holds the symmetric X S X^T (its lower
+// triangle mirrored), the A(k,k) of the step's two SYMMs.
+template <typename T>
+void launch_sygst_diag(hipStream_t s, T *D, int e, int nv, const T *X, int E, T *S, T *W, T *C);
+// tile row m of the deferred left solve, two launches: X(m,k) = Xd(m) (A(m,k) - sum_{k<j<m} L(m,j) X(j,k)) in
+// place over A(m,k) for every k < m.  Tile (i,j) of A and L at + (i + j lmt) bs, ld E (E % 128 == 0); the
+// inverted diagonal tile Xd(m) at Xd (ld E); y: m tiles of scratch
+template <typename T>
+void launch_sygst_solve_row(hipStream_t s, T *A, const T *L, long bs, int lmt, int E, int m, const T *Xd, T *y);
 
 // out-of-place transposes of `count` mb x mb tiles (mb % 64 == 0)
 template <typename T>

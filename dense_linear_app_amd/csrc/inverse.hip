@@ -19,97 +19,11 @@
 // sides.  Operands are swapped (B's fragment in the MFMA's A slot), so a lane's accumulator registers hold
 // consecutive ROWS of the output in consecutive lanes: the column-major stores are contiguous per 16 lanes.
 // Every output element is summed by one lane in a fixed order: the result is bit-identical from run to run.
-#include "cholmi_internal.h"
+#include "nn_blocks.h"
 
 namespace cholmi {
 
 namespace {
-
-typedef double vd4_t __attribute__((ext_vector_type(4)));
-typedef float vf4_t __attribute__((ext_vector_type(4)));
-
-template <typename T>
-struct Mf;
-template <>
-struct Mf<double> {
-  using acc_t = vd4_t;
-  using vec4_t = vd4_t;
-  static __device__ __forceinline__ acc_t mfma(double a, double b, acc_t c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int drow(int lane, int reg) { return (lane >> 4) + 4 * reg; }
-};
-template <>
-struct Mf<float> {
-  using acc_t = vf4_t;
-  using vec4_t = vf4_t;
-  static __device__ __forceinline__ acc_t mfma(float a, float b, acc_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int drow(int lane, int reg) { return 4 * (lane >> 4) + reg; }
-};
-
-template <typename T>
-using Acc = typename Mf<T>::acc_t[4][4];
-
-// acc += A(i0 .. i0+63, kb .. ke) B(kb .. ke, j0 .. j0+63); A(r,k) at A[r + k lda], B(k,c) at B[k + c ldb];
-// kb, ke multiples of 16.  TRA: A is lower triangular (A(r,k) = 0 for k > r), TRB: B is (B(k,c) = 0 for k < c):
-// the other triangle is never used, whatever it holds.
-template <typename T, bool TRA, bool TRB>
-__device__ __forceinline__ void nn_acc(const T *__restrict__ A, int lda, const T *__restrict__ B, int ldb, int i0,
-                                       int j0, int kb, int ke, Acc<T> &acc) {
-  using vec4_t = typename Mf<T>::vec4_t;
-  const int lane = threadIdx.x & 63, c = lane & 15, g4 = (lane >> 4) * 4;
-  for (int k0 = kb; k0 < ke; k0 += 16) {
-    T xa[4][4], xb[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const int row = i0 + 16 * a + c;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int k = k0 + g4 + s;
-        xa[a][s] = A[row + (long)k * lda];
-        if (TRA && k > row) xa[a][s] = T(0);
-      }
-    }
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int col = j0 + 16 * b + c;
-      const vec4_t v = *reinterpret_cast<const vec4_t *>(B + (k0 + g4) + (long)col * ldb);
-#pragma unroll
-      for (int s = 0; s < 4; ++s) xb[b][s] = (TRB && k0 + g4 + s < col) ? T(0) : v[s];
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = Mf<T>::mfma(xb[b][s], xa[a][s], acc[a][b]);
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ void acc_zero(Acc<T> &acc) {
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[a][b][r] = T(0);
-}
-
-// C(i0 + 16a + (lane & 15), j0 + 16b + drow(lane, r)) = alpha acc[a][b][r]
-template <typename T>
-__device__ __forceinline__ void acc_store(T *C, int ldc, int i0, int j0, const Acc<T> &acc, T alpha) {
-  const int lane = threadIdx.x & 63, c = lane & 15;
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        C[(i0 + 16 * a + c) + (long)(j0 + 16 * b + Mf<T>::drow(lane, r)) * ldc] = alpha * acc[a][b][r];
-}
 
 // (q, 128-block) of a launch: blockIdx.x = q nb2 + blk, the longest sums (largest q) first
 __device__ __forceinline__ void tri_job(int cnt, int nbe, int &q, int &i0, int &j0) {

@@ -1,6 +1,7 @@
 // The SPD routines of libcholmi.so that work from a Cholesky factor (include/cholmi.h): the solve (potrs / posv), the
 // mixed-precision solve (dsposv), the inverse (trtri / potri / poinv), the condition estimate (lansy / pocon) and the
-// expert solve with error bounds (poequ / laqsy / porfs / posvx).  All run on the main stream of the context that
+// expert solve with error bounds (poequ / laqsy / porfs / posvx), the pivoted factorisation (pstrf) and the
+// reduction of the generalized symmetric-definite eigenproblem (sygst).  All run on the main stream of the context that
 // api.hip keeps (api_internal.h); this file owns only its scratch and the statistics of the last call.
 #include <hip/hip_runtime.h>
 
@@ -44,6 +45,10 @@ double rf_stats[8] = {};  // of the last chol_posvx_tile / chol_porfs_tile (chol
 // indices with the stop word, the pivots and the interchange list
 ScratchPool<3> ps;
 double ps_stats[8] = {};  // of the last chol_pstrf_tile (chol_last_pstrf_stats)
+// chol_sygst_tile's: the inverted diagonal tiles of the factor, their 128-block inverses with the inversion's
+// products, the diagonal step's tiles with one tile row of the deferred solve
+ScratchPool<3> sg;
+double sg_stats[8] = {};  // of the last chol_sygst_tile (chol_last_sygst_stats)
 
 hipStream_t main_stream() { return main_rank_ctx()->st[ST_MAIN]; }
 
@@ -456,11 +461,25 @@ struct Lacn2 {
   }
 };
 
-// the diagonal tiles of the factor, inverted once per call: their 128-blocks (as potrs), then the tiles (trtri's inner
-// level), into cn[0]
+// the diagonal tiles of the factor, inverted once per call: their 128-blocks (as potrs) into W, then the tiles
+// (trtri's inner level) into Dv (nt tiles of E x E, E = condest_edge); Y: the products' scratch.  W and Y hold
+// nt (E / 128) blocks of 128 x 128 each; W keeps the 128-block inverses (potrs's winv, tile t at W + t (E / 128) 128^2).
+template <typename T>
+void stage_factor_diag_into(chol_desc *A, int upper, T *Dv, T *W, T *Y) {
+  hipStream_t s = main_stream();
+  const TileGeo ge = geo_of(A);
+  const int E = condest_edge(ge), nbm = E / MACRO, nt = A->nt;
+  const long blk = (long)MACRO * MACRO;
+  launch_stage_diag<T>(s, ge, upper, reinterpret_cast<const T *>(A->mat), Dv);
+  launch_invert_diag_batch<T>(s, Dv, (long)E * E, nt, E, W);
+  const TriLevel<T> in{Dv, MACRO, (long)MACRO * E, (long)E * E, E, W, blk, nbm * blk, MACRO, Y, blk, nbm * blk, MACRO};
+  for (int c = nbm - 2; c >= 0; --c) launch_tri_column<T>(s, in, nbm, nt, c);
+  launch_tri_put_diag<T>(s, Dv, (long)E * E, E, nt, W);
+}
+
+// ... into cn[0] (cn[1], cn[2]: W, Y)
 template <typename T>
 int stage_factor_diag(chol_desc *A, int upper, const char *what) {
-  hipStream_t s = main_stream();
   const TileGeo ge = geo_of(A);
   const int E = condest_edge(ge), nbm = E / MACRO, nt = A->nt;
   const long blk = (long)MACRO * MACRO;
@@ -468,12 +487,7 @@ int stage_factor_diag(chol_desc *A, int upper, const char *what) {
   if (!rc) rc = cn.ensure_bytes(1, (size_t)nt * nbm * blk * sizeof(T), what);
   if (!rc) rc = cn.ensure_bytes(2, (size_t)nt * nbm * blk * sizeof(T), what);
   if (rc) return rc;
-  T *Dv = cn.as<T>(0), *W = cn.as<T>(1), *Y = cn.as<T>(2);
-  launch_stage_diag<T>(s, ge, upper, reinterpret_cast<const T *>(A->mat), Dv);
-  launch_invert_diag_batch<T>(s, Dv, (long)E * E, nt, E, W);
-  const TriLevel<T> in{Dv, MACRO, (long)MACRO * E, (long)E * E, E, W, blk, nbm * blk, MACRO, Y, blk, nbm * blk, MACRO};
-  for (int c = nbm - 2; c >= 0; --c) launch_tri_column<T>(s, in, nbm, nt, c);
-  launch_tri_put_diag<T>(s, Dv, (long)E * E, E, nt, W);
+  stage_factor_diag_into<T>(A, upper, cn.as<T>(0), cn.as<T>(1), cn.as<T>(2));
   HIPCHECK(hipGetLastError());
   return 0;
 }
@@ -1126,6 +1140,133 @@ int pstrf_run(int uplo, chol_desc *A, int *piv, int *rank, double tol) {
   return rc;
 }
 
+// ---------------------------------------------------------------- generalized eigenproblem reduction (LAPACK DSYGST)
+// itype 1, Lower: A <- inv(L) A inv(L)^T, B = L L^T.  LAPACK's blocked DSYGST with the tile as the block; step k (T: the
+// tiles after k):
+//   1. A(k,k) <- X A(k,k) X^T, X = L(k,k)^{-1} (sygst.hip; the symmetric result stays in scratch for 3 and 5)
+//   2. A(T,k) <- A(T,k) L(k,k)^{-T}                       (the panel TRSM)
+//   3. A(T,k) -= 1/2 L(T,k) A(k,k)                        (the batched NT product against the symmetric copy)
+//   4. A(T,T) -= A(T,k) L(T,k)^T + L(T,k) A(T,k)^T        (the rank-2k update on the walker's work list)
+//   5. step 3 again
+// LAPACK's sixth step, A(T,k) <- inv(L(T,T)) A(T,k), is deferred: no later step reads column k, so after the walk one
+// pass over the tile rows solves every column at once (sygst.hip: launch_sygst_solve_row).  The diagonal tiles of L
+// are inverted once, up front (stage_factor_diag_into); their 128-block inverses are the panel TRSM's.  One stream,
+// in program order; the phases are timed by events recorded between them, read after the last.
+struct PhaseMarks {
+  std::vector<hipEvent_t> ev;
+  std::vector<int> ph;
+  ~PhaseMarks() {
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  }
+  // the end of a stretch of phase `p` (the first mark: the start)
+  int mark(int p) {
+    hipEvent_t e;
+    HIPCHECK(hipEventCreate(&e));
+    ev.push_back(e);
+    ph.push_back(p);
+    HIPCHECK(hipEventRecord(e, main_stream()));
+    return 0;
+  }
+  // st[0] += the whole span, st[ph] += every stretch
+  int sum(double *st) {
+    if (ev.size() < 2) return 0;
+    HIPCHECK(hipEventSynchronize(ev.back()));
+    for (size_t i = 1; i < ev.size(); ++i) {
+      float ms = 0;
+      HIPCHECK(hipEventElapsedTime(&ms, ev[i - 1], ev[i]));
+      st[ph[i]] += ms;
+    }
+    float ms = 0;
+    HIPCHECK(hipEventElapsedTime(&ms, ev.front(), ev.back()));
+    st[0] += ms;
+    return 0;
+  }
+};
+
+template <typename T>
+int sygst_impl(chol_desc *A, chol_desc *B) {
+  hipStream_t s = main_stream();
+  double *st = sg_stats;  // total, diagonal-tile inverses, chain, rank-2k updates, deferred solve, #steps
+  std::fill(st, st + 8, 0.0);
+  const long n = A->lm;
+  if (n == 0) return 0;
+  const int nt = A->nt, mb = A->mb, e = A->mbi, lmt = A->lmt;
+  const int E = condest_edge(geo_of(A)), nbm = E / MACRO;
+  if (nt > 1 && e != E) return fail(CHOL_ERR_NOT_SUPPORTED, "sygst_tile: stored tile edge");  // (not made by desc_create)
+  const long bs = A->bsizi, blk = (long)MACRO * MACRO, EE = (long)E * E;
+  const char *what = "sygst_tile";
+  // sg[0]: the inverted diagonal tiles; sg[1]: their 128-block inverses and the inversion's products; sg[2]: the
+  // diagonal step's three E x E tiles and one tile row of the deferred solve
+  int rc = sg.ensure_bytes(0, (size_t)nt * EE * sizeof(T), what);
+  if (!rc) rc = sg.ensure_bytes(1, 2 * (size_t)nt * nbm * blk * sizeof(T), what);
+  if (!rc) rc = sg.ensure_bytes(2, (3 * (size_t)EE + (size_t)(nt - 1) * bs) * sizeof(T), what);
+  if (rc) return rc;
+  T *Dv = sg.as<T>(0), *W = sg.as<T>(1), *Yi = W + (size_t)nt * nbm * blk;
+  T *S = sg.as<T>(2), *W2 = S + EE, *Cs = W2 + EE, *yrow = Cs + EE;
+  T *Am = reinterpret_cast<T *>(A->mat);
+  const T *Bm = reinterpret_cast<const T *>(B->mat);
+  auto tile = [&](const T *p, int i, int j) { return const_cast<T *>(p) + ((long)i + (long)j * lmt) * bs; };
+  forget_winv(A->mat);  // (A is overwritten)
+  PhaseMarks pm;
+  enum { P_DIAG = 1, P_CHAIN, P_SYR2K, P_SOLVE };
+  if ((rc = pm.mark(0))) return rc;
+  stage_factor_diag_into<T>(B, 0, Dv, W, Yi);
+  if ((rc = pm.mark(P_DIAG))) return rc;
+  const LocalMat lm = whole_local_mat(A);
+  for (int k = 0; k < nt; ++k) {
+    const int nv = (int)std::min<long>(mb, n - (long)k * mb);
+    launch_sygst_diag<T>(s, tile(Am, k, k), e, nv, Dv + k * EE, E, S, W2, Cs);
+    st[5] += 1;
+    if (k + 1 < nt) {
+      const int nr = nt - 1 - k;
+      T *P = tile(Am, k + 1, k);
+      T *Lt = tile(Bm, k + 1, k);
+      launch_trsm_panel<T>(s, P, bs, nr, tile(Bm, k, k), W + (long)k * nbm * blk, e, T(1));
+      launch_gemm_nt_batch<T>(s, Lt, bs, nr, Cs, 0, 1, P, bs, 0, e, T(-0.5), T(1));
+      if ((rc = pm.mark(P_CHAIN))) return rc;
+      PanelRef pan, qan;
+      memset(&pan, 0, sizeof pan);
+      memset(&qan, 0, sizeof qan);
+      pan.P = qan.P = 1;
+      pan.base[0] = tile(Am, 0, k);
+      qan.base[0] = tile(Bm, 0, k);
+      const WorkRange rr = whole_col_range(A, k + 1, nt);
+      launch_syr2k_update<T>(s, lm, A->d_list, rr.off, rr.na, rr.offb, rr.nb, pan, qan);
+      if ((rc = pm.mark(P_SYR2K))) return rc;
+      launch_gemm_nt_batch<T>(s, Lt, bs, nr, Cs, 0, 1, P, bs, 0, e, T(-0.5), T(1));
+    }
+    HIPCHECK(hipGetLastError());
+    if ((rc = pm.mark(P_CHAIN))) return rc;
+  }
+  for (int m = 1; m < nt; ++m) launch_sygst_solve_row<T>(s, Am, Bm, bs, lmt, E, m, Dv + m * EE, yrow);
+  HIPCHECK(hipGetLastError());
+  if ((rc = pm.mark(P_SOLVE))) return rc;
+  return pm.sum(st);
+}
+
+// the Lower path, or Upper between transposes of both storages (U^T U = L L^T with L = U^T, and inv(U^T) A inv(U) is
+// the Lower result); a zero on B's diagonal returns its index before anything is written
+int sygst_run(int uplo, chol_desc *A, chol_desc *B) {
+  const bool dbl = A->dtype == CHOL_REAL_DOUBLE;
+  int info = 0;
+  int rc = dbl ? diag_zero<double>(B, &info) : diag_zero<float>(B, &info);
+  if (rc) return rc;
+  if (info) return info;
+  const bool up = uplo == CHOL_UPPER;
+  if (up) {
+    transpose_storage(A);
+    transpose_storage(B);
+  }
+  rc = dbl ? sygst_impl<double>(A, B) : sygst_impl<float>(A, B);
+  if (up) {
+    transpose_storage(A);
+    transpose_storage(B);
+  }
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(main_stream()));
+  return rc;
+}
+
 }  // namespace
 
 void cholmi::spd_release() {
@@ -1135,6 +1276,7 @@ void cholmi::spd_release() {
   cn.release();
   rf.release();
   ps.release();
+  sg.release();
 }
 
 // ---------------------------------------------------------------- the entry points (C linkage: include/cholmi.h)
@@ -1420,5 +1562,33 @@ int chol_last_pstrf_stats(double *out8) {
   if (!out8) return fail(-1, "last_pstrf_stats: NULL");
   std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
   for (int i = 0; i < 8; ++i) out8[i] = ps_stats[i];
+  return 0;
+}
+
+int chol_sygst_tile(int itype, int uplo, chol_desc_t *A, chol_desc_t *B) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "sygst_tile before chol_init");
+  if (itype < 1 || itype > 3) return fail(-1, "sygst_tile: itype");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-2, "sygst_tile: uplo");
+  if (!A) return fail(-3, "sygst_tile: NULL A");
+  if (!B) return fail(-4, "sygst_tile: NULL B");
+  if (A == B || (A->mat && A->mat == B->mat)) return fail(-4, "sygst_tile: B aliases A");
+  return with_views({{A, true}, {B, false}}, [&]() -> int {
+  int rc = inverse_check("sygst_tile", A, 3);
+  if (rc) return rc;
+  rc = inverse_check("sygst_tile", B, 4);
+  if (rc) return rc;
+  if (!same_geometry(A, B)) return fail(-4, "sygst_tile: B's dtype or geometry differs from A's");
+  if (itype != 1) return fail(CHOL_ERR_NOT_SUPPORTED, "sygst_tile: itype 2 and 3 (C = L^T A L)");
+  CHECK_WINV(A, "sygst_tile");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  return sygst_run(uplo, A, B);
+  });
+}
+
+int chol_last_sygst_stats(double *out8) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "last_sygst_stats before chol_init");
+  if (!out8) return fail(-1, "last_sygst_stats: NULL");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  for (int i = 0; i < 8; ++i) out8[i] = sg_stats[i];
   return 0;
 }

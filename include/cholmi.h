@@ -320,6 +320,25 @@ int chol_pstrf_tile(int uplo, chol_desc_t *A, int *piv, int *rank, double tol);
  * then the number of pivot steps; the rest 0. */
 int chol_last_pstrf_stats(double *out8);
 
+/* LAPACK DSYGST / SSYGST with itype 1: the generalized symmetric-definite eigenproblem A x = lambda B x reduced to
+ * the standard form C y = lambda y.  B holds the Cholesky factor that chol_potrf_tile(uplo, B) returned.  Lower
+ * (B = L L^T): the lower triangle of A becomes that of C = inv(L) A inv(L)^T.  Upper (B = U^T U): the upper triangle
+ * of A becomes that of C = inv(U^T) A inv(U).  Only the `uplo` triangle of A is read or written: the other strict
+ * triangle comes back bit for bit.  Only the `uplo` triangle of B is read, and all of B comes back bit for bit.
+ * itype 2 and 3 (C = L^T A L) return CHOL_ERR_NOT_SUPPORTED.
+ *
+ * The descriptor rules of chol_trtri_tile: device-resident single-process square descriptors (ragged orders and
+ * sub-matrix views included) whose stored tile edge is a multiple of 64, tiles up to 4096; a p x q block-cyclic
+ * descriptor returns CHOL_ERR_NOT_SUPPORTED.  A and B of the same geometry and dtype; fp64 or fp32 by the dtype.
+ * Deviation from LAPACK (which does not check): an exact zero on the diagonal of B returns its 1-based index
+ * (info > 0) before anything is written, A unchanged.  No floating-point atomics and fixed reduction orders: a
+ * repeated call returns the same bits.  Argument errors: -1 itype not in {1, 2, 3}, -2 uplo, -3 A, -4 B (NULL, a
+ * dtype or geometry that differs from A's, or B aliasing A). */
+int chol_sygst_tile(int itype, int uplo, chol_desc_t *A, chol_desc_t *B);
+/* The last chol_sygst_tile [ms]: total, the inverses of B's diagonal tiles, the chain (diagonal tiles, panel TRSM,
+ * the two SYMMs), the rank-2k updates, the deferred left solve; then the number of steps; the rest 0. */
+int chol_last_sygst_stats(double *out8);
+
 /* CHAMELEON_Lapack_to_Tile / Tile_to_Lapack equivalents (host LAPACK layout
  * <-> descriptor storage); single-process descriptors only. */
 int chol_lapack_to_tile(const void *A, int lda, chol_desc_t *desc);
