@@ -72,6 +72,10 @@ def lib() -> C.CDLL:
         "chol_last_pstrf_stats": ([C.POINTER(d)], i),
         "chol_sygst_tile": ([i, i, vp, vp], i),
         "chol_last_sygst_stats": ([C.POINTER(d)], i),
+        "chol_sytrf_nopiv_tile": ([i, vp], i),
+        "chol_sytrs_nopiv_tile": ([i, vp, vp], i),
+        "chol_sysv_nopiv_tile": ([i, vp, vp], i),
+        "chol_last_sytrf_stats": ([C.POINTER(d)], i),
         "chol_lapack_to_tile": ([vp, i, vp], i),
         "chol_tile_to_lapack": ([vp, vp, i], i),
         "chol_tile_upload": ([vp, i, i, vp], i),

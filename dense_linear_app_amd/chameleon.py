@@ -398,6 +398,36 @@ def last_sygst_stats() -> dict:
             "steps": int(v[5])}
 
 
+def CHAMELEON_dsytrf_nopiv_Tile(uplo: int, A: Desc) -> int:
+    """A = L D L^T (ChamLower) or U^T D U (ChamUpper) without pivoting, for symmetric matrices whose factorisation
+    needs none (quasi-definite, diagonally dominant): on return D on the diagonal of A and the unit triangular factor
+    in the strict `uplo` triangle.  Returns 0, or info > 0: the 1-based index of the first pivot that is exactly zero
+    or not finite.  A negative pivot is not an error; last_sytrf_stats() reports the inertia and the growth."""
+    return check("chol_sytrf_nopiv_tile", lib().chol_sytrf_nopiv_tile(uplo, A.handle))
+
+
+def CHAMELEON_dsytrs_nopiv_Tile(uplo: int, A: Desc, B: Desc) -> int:
+    """B <- inv(A) B from the factor CHAMELEON_dsytrf_nopiv_Tile(uplo, A) returned; A is only read.  Returns 0, or
+    info > 0: the 1-based index of a zero on the stored diagonal (B unchanged)."""
+    return check("chol_sytrs_nopiv_tile", lib().chol_sytrs_nopiv_tile(uplo, A.handle, B.handle))
+
+
+def CHAMELEON_dsysv_nopiv_Tile(uplo: int, A: Desc, B: Desc) -> int:
+    """Factor A = L D L^T without pivoting and solve A X = B in place of B.  Returns info (> 0: a zero or non-finite
+    pivot, B untouched)."""
+    return check("chol_sysv_nopiv_tile", lib().chol_sysv_nopiv_tile(uplo, A.handle, B.handle))
+
+
+def last_sytrf_stats() -> dict:
+    """The last CHAMELEON_dsytrf_nopiv_Tile (chol_last_sytrf_stats): total, chain (diagonal tiles, panel TRSM, scaling)
+    and trailing-update time [ms]; the inertia (number of positive, of negative pivots; the padding of a ragged order
+    is not counted); min |d|, max |d| and max |L| over the strict triangle -- what shows an unstable run."""
+    v = (C.c_double * 8)()
+    check("chol_last_sytrf_stats", lib().chol_last_sytrf_stats(v))
+    return {"total_ms": v[0], "chain_ms": v[1], "update_ms": v[2], "inertia": (int(v[3]), int(v[4])),
+            "min_abs_d": v[5], "max_abs_d": v[6], "max_abs_l": v[7]}
+
+
 CHAMELEON_spotrs_Tile = CHAMELEON_dpotrs_Tile
 CHAMELEON_sposv_Tile = CHAMELEON_dposv_Tile
 CHAMELEON_slacpy_Tile = CHAMELEON_dlacpy_Tile
@@ -415,6 +445,9 @@ CHAMELEON_sporfs_Tile = CHAMELEON_dporfs_Tile
 CHAMELEON_sposvx_Tile = CHAMELEON_dposvx_Tile
 CHAMELEON_spstrf_Tile = CHAMELEON_dpstrf_Tile
 CHAMELEON_ssygst_Tile = CHAMELEON_dsygst_Tile
+CHAMELEON_ssytrf_nopiv_Tile = CHAMELEON_dsytrf_nopiv_Tile
+CHAMELEON_ssytrs_nopiv_Tile = CHAMELEON_dsytrs_nopiv_Tile
+CHAMELEON_ssysv_nopiv_Tile = CHAMELEON_dsysv_nopiv_Tile
 
 
 def residual_plgsy(L: Desc, bump: float, seed: int) -> float:

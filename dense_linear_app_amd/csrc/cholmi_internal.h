@@ -156,6 +156,13 @@ template <typename T>
 void launch_syr2k_update(hipStream_t s, const LocalMat &C, const int2 *d_list, int off, int na, int offb, int nb,
                          const PanelRef &pan, const PanelRef &qan);
 
+// sytrf_nopiv's one-pass two-panel update: C(i,j) -= P(i) Q(j)^T for the same (i,j) list and with the same block map
+// as launch_trail_update; P = pan (the unscaled panel W = L D, in scratch: PanelRef::first), Q = qan (L, the matrix's
+// own column) -- kernels.hip: k_ldl_update_w8, k_ldl_update_w8f
+template <typename T>
+void launch_ldl_update(hipStream_t s, const LocalMat &C, const int2 *d_list, int off, int na, int offb, int nb,
+                       const PanelRef &pan, const PanelRef &qan);
+
 // In-tile blocked POTRF of one mb x mb tile (device pointer, ld = mb).  Writes the
 // inverses of the MACRO x MACRO diagonal blocks of L to winv (mb/MACRO blocks of
 // MACRO*MACRO elements, ld = MACRO).  info: device int, set to info_base + j (1-based)
@@ -442,6 +449,33 @@ void launch_sygst_diag(hipStream_t s, T *D, int e, int nv, const T *X, int E, T 
 // inverted diagonal tile Xd(m) at Xd (ld E); y: m tiles of scratch
 template <typename T>
 void launch_sygst_solve_row(hipStream_t s, T *A, const T *L, long bs, int lmt, int E, int m, const T *Xd, T *y);
+
+// ---- launchers (sytrf.hip): chol_sytrf_nopiv_tile / chol_sytrs_nopiv_tile (A = L D L^T, Lower) on a single-process image ----
+// one diagonal tile (e x e, ld e, e % 128 == 0) <- its factor in place, by 128-block steps: D on the diagonal, the unit
+// lower triangular L below it, the strict upper triangle not touched.  Wt: one tile of scratch; Lc, winv: e / 128 blocks
+// of 128 x 128 each (afterwards: the unit lower triangular diagonal blocks of L and their inverses, what
+// launch_trsm_panel takes with the tile itself as lkk); dv, rv (e each) <- d_j and 1 / d_j; *info <- info_base + j
+// (1-based) at the first pivot that is zero or not finite (the first one wins); pm: ldl_partials() doubles, zeroed once
+// per factorisation, that collect the partial maxima of |L|
+int ldl_partials();
+template <typename T>
+void launch_ldl_tile(hipStream_t s, T *tile, int e, T *Wt, T *Lc, T *winv, T *dv, T *rv, int *info, int info_base,
+                     double *pm);
+// the solved panel W (`total` elements in whole tiles of bs, ld e) copied to Wscr and scaled in place to L = W diag(rv),
+// rv = 1 / d: one multiplication by the reciprocal per entry (LAPACK DSYTF2's r1 = 1 / d)
+template <typename T>
+void launch_ldl_scale(hipStream_t s, T *W, T *Wscr, long total, long bs, int e, const T *rv, double *pm);
+// out[0..4] <- the number of positive and of negative pivots, min |d|, max |d| over rows 0 .. n-1 (the padding is not
+// counted), max |L| from the partials
+template <typename T>
+void launch_ldl_stats(hipStream_t s, const T *dv, long n, int mb, int e, const double *pm, double *out);
+// U (nt tiles of bs) <- the diagonal tiles of the factor (tile t at A + t dstride) with unit diagonals and zeros above,
+// rv (nt e) <- 1 / d
+template <typename T>
+void launch_ldl_stage(hipStream_t s, const T *A, long dstride, long bs, int e, int nt, T *U, T *rv);
+// potrs's transposed image Z of the right-hand sides (tile row r of tile column i at (r + i nr) bs) <- Z diag(rv)
+template <typename T>
+void launch_ldl_zscale(hipStream_t s, T *Z, long total, long bs, int e, int nr, const T *rv);
 
 // out-of-place transposes of `count` mb x mb tiles (mb % 64 == 0)
 template <typename T>

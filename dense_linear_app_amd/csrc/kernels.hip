@@ -992,6 +992,60 @@ __global__ __launch_bounds__(512, 4) void k_syr2k_w8f(LocalMat C, const int2 *__
 }
 
 // ------------------------------------------------------------------------------
+// The two-panel update of sytrf_nopiv (A = L D L^T without pivoting), one pass:  C(i,j) -= P(i) Q(j)^T  for the (i,j)
+// tiles of the list, P = `pan` (the unscaled panel W = L D, a scratch tile column addressed through PanelRef::first),
+// Q = `qan` (L, the matrix's own column).  k_syr2k_w8 with its first K-loop only: W L^T = L D L^T is symmetric, so the
+// lower blocks of the diagonal tiles are right as they stand.  Kernels of their own: the update's and the SYR2K's
+// instantiations are not touched.
+// ------------------------------------------------------------------------------
+template <typename T, int MODE>
+__global__ __launch_bounds__(512, 4) void k_ldl_update_w8(LocalMat C, const int2 *__restrict__ list, int na, int offb,
+                                                          int nb, int blocks_a, PanelRef pan, PanelRef qan, int nbm,
+                                                          int unit) {
+  __shared__ SmemR<T> sm;
+  BlockMap bm;
+  if (!map_update_block(list, na, offb, nb, nbm, blocks_a, unit, bm)) return;
+  const int2 ij = bm.ij;
+  const int mi = bm.mi, mj = bm.mj;
+  const bool lower = (ij.x == ij.y) && mi == mj;
+  T *Cp = reinterpret_cast<T *>(C.base) + ((long)(ij.x / C.P) + (long)(ij.y / C.Q) * C.lmt) * C.bsiz + mi * MACRO +
+          (long)mj * MACRO * C.mb;
+  typename Tr<T>::acc_t acc[4][2];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[a][b][r] = T(0);
+  nt_kloop_w8<T, MODE>(panel_tile<T>(pan, ij.x, C.bsiz) + mi * MACRO, C.mb, panel_tile<T>(qan, ij.y, C.bsiz) + mj * MACRO,
+                       C.mb, C.mb, acc, sm, nullptr);
+  w8_epilogue<T, false>(Cp, Cp, C.mb, acc, lower);
+}
+
+__global__ __launch_bounds__(512, 4) void k_ldl_update_w8f(LocalMat C, const int2 *__restrict__ list, int na, int offb,
+                                                           int nb, int blocks_a, PanelRef pan, PanelRef qan, int nbm,
+                                                           int unit) {
+  __shared__ SmemF sm;
+  BlockMap bm;
+  if (!map_update_block(list, na, offb, nb, nbm, blocks_a, unit, bm)) return;
+  const int2 ij = bm.ij;
+  const int mi = bm.mi, mj = bm.mj;
+  const bool lower = (ij.x == ij.y) && mi == mj;
+  float *Cp = reinterpret_cast<float *>(C.base) + ((long)(ij.x / C.P) + (long)(ij.y / C.Q) * C.lmt) * C.bsiz +
+              mi * MACRO + (long)mj * MACRO * C.mb;
+  f4_t acc[4][2];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[a][b][r] = 0.f;
+  nt_kloop_w8f(panel_tile<float>(pan, ij.x, C.bsiz) + mi * MACRO, C.mb,
+               panel_tile<float>(qan, ij.y, C.bsiz) + mj * MACRO, C.mb, C.mb, acc, sm, nullptr);
+  w8f_epilogue<false>(Cp, Cp, C.mb, acc, lower);
+}
+
+// ------------------------------------------------------------------------------
 // The task path's updates (chol_tile_batch: the SYRK / GEMM tasks of a wave, W2:416, 511) on the same eight-wave cores:
 // task t reads its operands through device arrays of tile pointers and writes  cout[t] = cin[t] - a[t] b[t]^T  OUT OF
 // PLACE -- the private copy every task makes of the tile it updates (W2:212-213) is this write, there is no copy pass.
@@ -2762,6 +2816,20 @@ void launch_syr2k_update(hipStream_t s, const LocalMat &C, const int2 *d_list, i
     k_syr2k_w8<T, 3><<<grid, dim3(512), 0, s>>>(C, d_list + off, na, offb, nb, (int)u.blocks_a, pan, qan, nbm, u.unit);
 }
 
+template <typename T>
+void launch_ldl_update(hipStream_t s, const LocalMat &C, const int2 *d_list, int off, int na, int offb, int nb,
+                       const PanelRef &pan, const PanelRef &qan) {
+  if (na + nb <= 0) return;
+  offb -= off;  // the kernels index from d_list + off
+  const int nbm = C.mb / MACRO, MT = nbm * nbm, MTd = nbm * (nbm + 1) / 2;
+  const UpdateGrid u = update_grid((long)na * MT, (long)nb * MTd, na == 0 && nb == 1);
+  const dim3 grid((unsigned)(u.blocks_a + u.blocks_b));
+  if constexpr (sizeof(T) == 4)
+    k_ldl_update_w8f<<<grid, dim3(512), 0, s>>>(C, d_list + off, na, offb, nb, (int)u.blocks_a, pan, qan, nbm, u.unit);
+  else
+    k_ldl_update_w8<T, 3><<<grid, dim3(512), 0, s>>>(C, d_list + off, na, offb, nb, (int)u.blocks_a, pan, qan, nbm, u.unit);
+}
+
 // One 128-column step of the panel TRSM over `ntiles` tiles: X[:, st] = A[:, st] Winv_st^T, then
 // A[:, c] -= X[:, st] L(c, st)^T for the block columns c > st.  Few tiles (the late, chain-bound
 // waves): small-block kernels, latency; many tiles: the 128 x 128 NT core, throughput.
@@ -3085,6 +3153,8 @@ template void launch_mfma_probe<float>(hipStream_t, float *, int, int);
                                        int, const PanelRef &, bool, const PanelRef *);              \
   template void launch_syr2k_update<T>(hipStream_t, const LocalMat &, const int2 *, int, int, int,  \
                                        int, const PanelRef &, const PanelRef &);                    \
+  template void launch_ldl_update<T>(hipStream_t, const LocalMat &, const int2 *, int, int, int,    \
+                                     int, const PanelRef &, const PanelRef &);                      \
   template void launch_potrf_tile<T>(hipStream_t, T *, int, T *, int *, int, int *);                \
   template void launch_diag_syrk<T>(hipStream_t, T *, const T *, int);                               \
   template void launch_invert_diag<T>(hipStream_t, const T *, int, T *);                            \

@@ -1,7 +1,8 @@
 // The SPD routines of libcholmi.so that work from a Cholesky factor (include/cholmi.h): the solve (potrs / posv), the
 // mixed-precision solve (dsposv), the inverse (trtri / potri / poinv), the condition estimate (lansy / pocon) and the
-// expert solve with error bounds (poequ / laqsy / porfs / posvx), the pivoted factorisation (pstrf) and the
-// reduction of the generalized symmetric-definite eigenproblem (sygst).  All run on the main stream of the context that
+// expert solve with error bounds (poequ / laqsy / porfs / posvx), the pivoted factorisation (pstrf), the
+// reduction of the generalized symmetric-definite eigenproblem (sygst) and the L D L^T factorisation without pivoting
+// with its solve (sytrf_nopiv / sytrs_nopiv / sysv_nopiv).  All run on the main stream of the context that
 // api.hip keeps (api_internal.h); this file owns only its scratch and the statistics of the last call.
 #include <hip/hip_runtime.h>
 
@@ -49,6 +50,11 @@ double ps_stats[8] = {};  // of the last chol_pstrf_tile (chol_last_pstrf_stats)
 // products, the diagonal step's tiles with one tile row of the deferred solve
 ScratchPool<3> sg;
 double sg_stats[8] = {};  // of the last chol_sygst_tile (chol_last_sygst_stats)
+// chol_sytrf_nopiv_tile's: the unscaled panel (one tile column); the diagonal tile's scratch tile, its unit 128-blocks
+// with their inverses, d and 1 / d; the partial maxima with the statistics and the info word; chol_sytrs_nopiv_tile's
+// staged diagonal tiles with 1 / d
+ScratchPool<4> sy;
+double sy_stats[8] = {};  // of the last chol_sytrf_nopiv_tile (chol_last_sytrf_stats)
 
 hipStream_t main_stream() { return main_rank_ctx()->st[ST_MAIN]; }
 
@@ -90,8 +96,11 @@ struct EventTimer {
 //   backward  Z(:,k) <- Z(:,k) L(k,k)^{-1};  Z(:,i) -= Z(:,k) L(k,i),   i < k      (L^T X = Y)
 // the backward sweep's operands being transposed tiles (L(k,k)^{-T} from a TRSM of the identity,
 // L(k,i)^T from a tile transpose) so that every product is again A B^T.
+// udiag, rdiag (both or neither): the solve with an L D L^T factor (sytrs_nopiv) -- udiag holds the nt diagonal tiles
+// with unit diagonals (read in place of A's), rdiag the reciprocals 1 / d (tile t at + t mb), by which the right-hand
+// sides are scaled between the two sweeps
 template <typename T>
-int potrs_impl(chol_desc *A, chol_desc *B) {
+int potrs_impl(chol_desc *A, chol_desc *B, const T *udiag = nullptr, const T *rdiag = nullptr) {
   const int nt = A->nt, nr = B->nt, mb = A->mbi;
   const long bs = A->bsizi;
   const size_t tb = (size_t)bs * sizeof(T);
@@ -103,21 +112,23 @@ int potrs_impl(chol_desc *A, chol_desc *B) {
   T *winv = reinterpret_cast<T *>(main_rank_ctx()->winv);
   auto Ltile = [&](int i, int j) { return La + ((long)i + (long)j * A->lmt) * bs; };
   auto Ztile = [&](int r, int i) { return Z + ((long)r + (long)i * nr) * bs; };
+  auto Dtile = [&](int k) { return udiag ? udiag + (long)k * bs : Ltile(k, k); };
   // Z(r,i) = B(i,r)^T
   for (int r = 0; r < nr; ++r)
     launch_tiles_transpose<T>(s, Bm + (long)r * B->lmt * bs, bs, Ztile(r, 0), (long)nr * bs, mb, nt);
   for (int k = 0; k < nt; ++k) {  // forward
-    launch_invert_diag<T>(s, Ltile(k, k), mb, winv);
-    launch_trsm_panel<T>(s, Ztile(0, k), bs, nr, Ltile(k, k), winv, mb, T(1));
+    launch_invert_diag<T>(s, Dtile(k), mb, winv);
+    launch_trsm_panel<T>(s, Ztile(0, k), bs, nr, Dtile(k), winv, mb, T(1));
     // Z(r,i) -= Z(r,k) L(i,k)^T for every r and i > k: one launch
     launch_gemm_nt_batch<T>(s, Ztile(0, k), bs, nr, Ltile(k + 1, k), bs, nt - 1 - k, Ztile(0, k + 1), bs, (long)nr * bs, mb,
                             T(-1), T(1));
   }
+  if (rdiag) launch_ldl_zscale<T>(s, Z, (long)nr * nt * bs, bs, mb, nr, rdiag);  // (D^{-1} between the sweeps)
   for (int k = nt - 1; k >= 0; --k) {  // backward
     HIPCHECK(hipMemsetAsync(Wt, 0, tb, s));
     launch_pad_identity<T>(s, Wt, 0, mb);
-    launch_invert_diag<T>(s, Ltile(k, k), mb, winv);
-    launch_trsm_panel<T>(s, Wt, bs, 1, Ltile(k, k), winv, mb, T(1));  // Wt = L(k,k)^{-T}
+    launch_invert_diag<T>(s, Dtile(k), mb, winv);
+    launch_trsm_panel<T>(s, Wt, bs, 1, Dtile(k), winv, mb, T(1));  // Wt = L(k,k)^{-T}
     // Z(r,k) <- Z(r,k) L(k,k)^{-1} for every r (out of place, then back: the tiles of a column are contiguous)
     launch_gemm_nt_batch<T>(s, Ztile(0, k), bs, nr, Wt, 0, 1, tmp, bs, 0, mb, T(1), T(0));
     HIPCHECK(hipMemcpyAsync(Ztile(0, k), tmp, (size_t)nr * tb, hipMemcpyDeviceToDevice, s));
@@ -1267,6 +1278,118 @@ int sygst_run(int uplo, chol_desc *A, chol_desc *B) {
   return rc;
 }
 
+// ---------------------------------------------------------------- L D L^T without pivoting (MAGMA dsytrf_nopiv)
+// Lower: A = L D L^T, L unit lower triangular, D diagonal; on return D on the diagonal and L below it.  Right-looking
+// with the tile as the block; tile column k (T: the tiles below k):
+//   1. A(k,k) = L_kk D_k L_kk^T in place, by 128-block steps (sytrf.hip), which also leaves the inverses of the unit
+//      diagonal 128-blocks of L_kk and raises the device info word at the first zero or non-finite pivot
+//   2. W(T) = A(T,k) L_kk^{-T}                            (the panel TRSM; L_kk's diagonal blocks enter through the inverses)
+//   3. Wscr(T) <- W(T), A(T,k) <- L(T,k) = W(T) D_k^{-1}  (one pass; a multiplication by the reciprocal 1 / d_j)
+//   4. A(T,T) -= Wscr(T) L(T,k)^T                         (the one-pass two-panel update on the walker's work list)
+// One stream, in program order.  The host reads the info word once per tile column, behind the chain: the update of
+// the column is already queued by then, so the device does not wait for the host.
+template <typename T>
+int sytrf_impl(chol_desc *A, int *info) {
+  hipStream_t s = main_stream();
+  // total, chain, updates [ms]; positive and negative pivots; min |d|, max |d|, max |L|
+  double *st = sy_stats;
+  std::fill(st, st + 8, 0.0);
+  *info = 0;
+  const long n = A->lm;
+  if (n == 0) return 0;
+  const int nt = A->nt, mb = A->mb, e = A->mbi, lmt = A->lmt, nbm = e / MACRO;
+  const long bs = A->bsizi, blk = (long)MACRO * MACRO;
+  const char *what = "sytrf_nopiv_tile";
+  const int npm = ldl_partials();
+  int rc = sy.ensure_bytes(0, (size_t)std::max(1, nt - 1) * bs * sizeof(T), what);
+  if (!rc) rc = sy.ensure_bytes(1, ((size_t)bs + 2 * (size_t)nbm * blk + 2 * (size_t)nt * e) * sizeof(T), what);
+  if (!rc) rc = sy.ensure_bytes(2, ((size_t)npm + 8) * sizeof(double) + sizeof(int), what);
+  if (rc) return rc;
+  T *Wscr = sy.as<T>(0), *Wt = sy.as<T>(1), *Lc = Wt + bs, *winv = Lc + nbm * blk, *dv = winv + nbm * blk, *rv = dv + (long)nt * e;
+  double *pmax = sy.as<double>(2), *out = pmax + npm;
+  int *d_info = reinterpret_cast<int *>(out + 8);
+  T *Am = reinterpret_cast<T *>(A->mat);
+  auto tile = [&](int i, int j) { return Am + ((long)i + (long)j * lmt) * bs; };
+  forget_winv(A->mat);  // (A is overwritten)
+  HIPCHECK(hipMemsetAsync(pmax, 0, ((size_t)npm + 8) * sizeof(double) + sizeof(int), s));
+  PhaseMarks pm;
+  enum { P_CHAIN = 1, P_UPDATE };
+  if ((rc = pm.mark(0))) return rc;
+  const LocalMat lm = whole_local_mat(A);
+  int hinfo = 0;
+  for (int k = 0; k < nt && !hinfo; ++k) {
+    const int nr = nt - 1 - k;
+    launch_ldl_tile<T>(s, tile(k, k), e, Wt, Lc, winv, dv + (long)k * e, rv + (long)k * e, d_info, k * mb, pmax);
+    if (nr > 0) {
+      launch_trsm_panel<T>(s, tile(k + 1, k), bs, nr, tile(k, k), winv, e, T(1));
+      launch_ldl_scale<T>(s, tile(k + 1, k), Wscr, (long)nr * bs, bs, e, rv + (long)k * e, pmax);
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(&hinfo, d_info, sizeof hinfo, hipMemcpyDeviceToHost, s));
+    if ((rc = pm.mark(P_CHAIN))) return rc;
+    const hipEvent_t chain_end = pm.ev.back();
+    if (nr > 0) {
+      PanelRef pan, qan;
+      memset(&pan, 0, sizeof pan);
+      memset(&qan, 0, sizeof qan);
+      pan.P = qan.P = 1;
+      pan.base[0] = Wscr;
+      pan.first[0] = k + 1;
+      qan.base[0] = tile(0, k);
+      const WorkRange rr = whole_col_range(A, k + 1, nt);
+      launch_ldl_update<T>(s, lm, A->d_list, rr.off, rr.na, rr.offb, rr.nb, pan, qan);
+      HIPCHECK(hipGetLastError());
+      if ((rc = pm.mark(P_UPDATE))) return rc;
+    }
+    HIPCHECK(hipEventSynchronize(chain_end));
+  }
+  launch_ldl_stats<T>(s, dv, n, mb, e, pmax, out);
+  HIPCHECK(hipGetLastError());
+  double h[5] = {};
+  HIPCHECK(hipMemcpyAsync(h, out, sizeof h, hipMemcpyDeviceToHost, s));
+  if ((rc = pm.mark(P_CHAIN))) return rc;
+  if ((rc = pm.sum(st))) return rc;
+  HIPCHECK(hipStreamSynchronize(s));
+  for (int i = 0; i < 5; ++i) st[3 + i] = h[i];
+  *info = hinfo;
+  return 0;
+}
+
+// the Lower path, or Upper between two transposes of the storage (U^T D U = L D L^T with L = U^T); -> info
+int sytrf_run(int uplo, chol_desc *A) {
+  if (A->mbi % MACRO) return fail(CHOL_ERR_NOT_SUPPORTED, "sytrf_nopiv_tile: stored tile edge must be a multiple of 128");
+  const bool dbl = A->dtype == CHOL_REAL_DOUBLE, up = uplo == CHOL_UPPER;
+  int info = 0;
+  if (up) transpose_storage(A);
+  const int rc = dbl ? sytrf_impl<double>(A, &info) : sytrf_impl<float>(A, &info);
+  if (up) transpose_storage(A);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(main_stream()));
+  return rc ? rc : info;
+}
+
+// B <- A^{-1} B from that factor: potrs_impl's sweeps over the diagonal tiles staged with unit diagonals, the
+// right-hand sides scaled by 1 / d in between.  A zero on the stored diagonal returns its index before B is written.
+template <typename T>
+int sytrs_impl(int upper, chol_desc *A, chol_desc *B) {
+  int info = 0;
+  int rc = diag_zero<T>(A, &info);
+  if (rc) return rc;
+  if (info) return info;
+  const int nt = A->nt, e = A->mbi;
+  const long bs = A->bsizi;
+  if ((rc = sy.ensure_bytes(3, ((size_t)nt * bs + (size_t)nt * e) * sizeof(T), "sytrs_nopiv_tile"))) return rc;
+  T *U = sy.as<T>(3), *rv = U + (long)nt * bs;
+  if (upper) transpose_storage(A);
+  launch_ldl_stage<T>(main_stream(), reinterpret_cast<const T *>(A->mat), (long)(A->lmt + 1) * bs, bs, e, nt, U, rv);
+  rc = potrs_impl<T>(A, B, U, rv);
+  if (upper) {
+    transpose_storage(A);
+    HIPCHECK(hipStreamSynchronize(main_stream()));
+  }
+  return rc;
+}
+
 }  // namespace
 
 void cholmi::spd_release() {
@@ -1277,6 +1400,7 @@ void cholmi::spd_release() {
   rf.release();
   ps.release();
   sg.release();
+  sy.release();
 }
 
 // ---------------------------------------------------------------- the entry points (C linkage: include/cholmi.h)
@@ -1590,5 +1714,56 @@ int chol_last_sygst_stats(double *out8) {
   if (!out8) return fail(-1, "last_sygst_stats: NULL");
   std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
   for (int i = 0; i < 8; ++i) out8[i] = sg_stats[i];
+  return 0;
+}
+
+int chol_sytrf_nopiv_tile(int uplo, chol_desc_t *A) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "sytrf_nopiv_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "sytrf_nopiv_tile: uplo");
+  if (!A) return fail(-2, "sytrf_nopiv_tile: NULL A");
+  return with_views({{A, true}}, [&]() -> int {
+  int rc = inverse_check("sytrf_nopiv_tile", A, 2);
+  if (rc) return rc;
+  CHECK_WINV(A, "sytrf_nopiv_tile");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  return sytrf_run(uplo, A);
+  });
+}
+
+int chol_sytrs_nopiv_tile(int uplo, chol_desc_t *A, chol_desc_t *B) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "sytrs_nopiv_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "sytrs_nopiv_tile: uplo");
+  if (!A) return fail(-2, "sytrs_nopiv_tile: NULL A");
+  if (!B) return fail(-3, "sytrs_nopiv_tile: NULL B");
+  if (A == B || (A->mat && A->mat == B->mat)) return fail(-3, "sytrs_nopiv_tile: B aliases A");
+  return with_views({{A, false}, {B, true}}, [&]() -> int {
+  int rc = inverse_check("sytrs_nopiv_tile", A, 2);
+  if (rc) return rc;
+  rc = resident_whole("sytrs_nopiv_tile", B);
+  if (rc) return rc;
+  if (B->lm != A->lm || B->mb != A->mb || B->mbi != A->mbi || B->dtype != A->dtype)
+    return fail(-3, "sytrs_nopiv_tile: B must have A's order, tile size and type");
+  CHECK_WINV(A, "sytrs_nopiv_tile");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  const int up = uplo == CHOL_UPPER;
+  return A->dtype == CHOL_REAL_DOUBLE ? sytrs_impl<double>(up, A, B) : sytrs_impl<float>(up, A, B);
+  });
+}
+
+int chol_sysv_nopiv_tile(int uplo, chol_desc_t *A, chol_desc_t *B) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "sysv_nopiv_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "sysv_nopiv_tile: uplo");
+  if (!A) return fail(-2, "sysv_nopiv_tile: NULL A");
+  if (!B) return fail(-3, "sysv_nopiv_tile: NULL B");
+  const int info = chol_sytrf_nopiv_tile(uplo, A);
+  if (info != 0) return info;  // > 0: a zero or non-finite pivot, B untouched
+  return chol_sytrs_nopiv_tile(uplo, A, B);
+}
+
+int chol_last_sytrf_stats(double *out8) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "last_sytrf_stats before chol_init");
+  if (!out8) return fail(-1, "last_sytrf_stats: NULL");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  for (int i = 0; i < 8; ++i) out8[i] = sy_stats[i];
   return 0;
 }

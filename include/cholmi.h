@@ -339,6 +339,42 @@ int chol_sygst_tile(int itype, int uplo, chol_desc_t *A, chol_desc_t *B);
  * the two SYMMs), the rank-2k updates, the deferred left solve; then the number of steps; the rest 0. */
 int chol_last_sygst_stats(double *out8);
 
+/* The L D L^T factorisation WITHOUT pivoting of a symmetric matrix (MAGMA dsytrf_nopiv / ssytrf_nopiv; LAPACK
+ * DSYTF2's storage for 1 x 1 pivots): A = L D L^T (Lower) or U^T D U (Upper, U = L^T), L unit lower triangular, D
+ * diagonal.  On return the diagonal of A holds D and the strict `uplo` triangle holds L (U); the unit diagonal is not
+ * stored.  Only the `uplo` triangle is read or written: the other strict triangle comes back bit for bit.  For
+ * matrices whose factorisation needs no pivoting: symmetric quasi-definite [[H, J^T], [J, -C]] with H and C positive
+ * definite (under any symmetric permutation), symmetric diagonally dominant with diagonal entries of either sign,
+ * shifted matrices C - sigma I whose inertia is wanted.  Nothing bounds the growth of L on other matrices:
+ * chol_last_sytrf_stats reports min |d|, max |d| and max |L| so that a caller can judge the run.
+ *
+ * A column of L is its unscaled column times the reciprocal of the pivot, l(i,j) = w(i,j) * (1 / d_j), the
+ * reciprocal formed once per pivot (DSYTF2's r1 = 1 / d), not a division per entry.
+ *
+ * Returns 0, or j > 0: the 1-based index of the first pivot d_j that is exactly zero or not finite (NaN, +-Inf); then
+ * the tile columns before the one that holds j are final and the rest of the triangle is unspecified (LAPACK leaves a
+ * partly factored matrix in the same way).  A negative pivot is NOT an error.
+ *
+ * The descriptor rules of chol_sygst_tile: device-resident single-process square descriptors (ragged orders and
+ * sub-matrix views included), tiles up to 4096, the stored tile edge a multiple of 128 (what chol_desc_create
+ * allocates; a caller's buffer with another edge returns CHOL_ERR_NOT_SUPPORTED); a p x q block-cyclic descriptor
+ * returns CHOL_ERR_NOT_SUPPORTED.  fp64 or fp32 by the dtype, fp32 in single precision throughout.  No floating-point
+ * atomics and fixed reduction orders: a repeated call returns the same bits.  Argument errors: -1 uplo, -2 A. */
+int chol_sytrf_nopiv_tile(int uplo, chol_desc_t *A);
+/* B <- inv(A) B from the factor chol_sytrf_nopiv_tile(uplo, A) returned: L Y = B, Z = D^{-1} Y (a multiplication by
+ * 1 / d_j), L^T X = Z.  Any number of right-hand sides; B with A's order, row tiling and dtype (the rules of
+ * chol_potrs_tile).  A is only read and comes back bit for bit.  A zero on the stored diagonal returns its 1-based
+ * index (info > 0) before B is written.  Argument errors: -1 uplo, -2 A, -3 B (NULL, another order, tile size or
+ * dtype than A's, or B aliasing A). */
+int chol_sytrs_nopiv_tile(int uplo, chol_desc_t *A, chol_desc_t *B);
+/* chol_sytrf_nopiv_tile then chol_sytrs_nopiv_tile; with info > 0 from the factorisation B is not touched. */
+int chol_sysv_nopiv_tile(int uplo, chol_desc_t *A, chol_desc_t *B);
+/* The last chol_sytrf_nopiv_tile: total, chain (diagonal tiles, panel TRSM, scaling) and trailing-update time [ms];
+ * the number of positive and of negative pivots (the inertia; by Sylvester's law the number of positive and negative
+ * eigenvalues), min |d_j|, max |d_j|, max |L(i,j)| over the strict triangle -- over rows and columns 0 .. n-1 only:
+ * the identity padding of a ragged order is not counted.  From fixed-order reductions. */
+int chol_last_sytrf_stats(double *out8);
+
 /* CHAMELEON_Lapack_to_Tile / Tile_to_Lapack equivalents (host LAPACK layout
  * <-> descriptor storage); single-process descriptors only. */
 int chol_lapack_to_tile(const void *A, int lda, chol_desc_t *desc);
