@@ -76,6 +76,11 @@ def lib() -> C.CDLL:
         "chol_sytrs_nopiv_tile": ([i, vp, vp], i),
         "chol_sysv_nopiv_tile": ([i, vp, vp], i),
         "chol_last_sytrf_stats": ([C.POINTER(d)], i),
+        "chol_rbt_apply_tile": ([i, vp, vp, i], i),
+        "chol_sytrf_rbt_tile": ([i, vp, vp, i, u64], i),
+        "chol_sytrs_rbt_tile": ([i, vp, vp, i, vp], i),
+        "chol_sysv_rbt_tile": ([i, vp, vp, vp, i, u64, vp, vp, C.POINTER(i), C.POINTER(d)], i),
+        "chol_last_rbt_stats": ([C.POINTER(d)], i),
         "chol_lapack_to_tile": ([vp, i, vp], i),
         "chol_tile_to_lapack": ([vp, vp, i], i),
         "chol_tile_upload": ([vp, i, i, vp], i),

@@ -428,6 +428,45 @@ def last_sytrf_stats() -> dict:
             "min_abs_d": v[5], "max_abs_d": v[6], "max_abs_l": v[7]}
 
 
+def CHAMELEON_drbt_apply_Tile(uplo: int, A: Desc, W: Desc, depth: int) -> int:
+    """A <- W^T A W on the `uplo` triangle, W the recursive butterfly of `depth` (1 or 2) levels whose diagonal
+    entries are the columns of the n x depth descriptor W; n a multiple of 2^depth."""
+    return check("chol_rbt_apply_tile", lib().chol_rbt_apply_tile(uplo, A.handle, W.handle, depth))
+
+
+def CHAMELEON_dsytrf_rbt_Tile(uplo: int, A: Desc, W: Desc, depth: int = 2, seed: int = 1) -> int:
+    """The factorisation for general symmetric indefinite matrices: W filled from `seed` (seed = 0: W as given),
+    A <- W^T A W, then A = L D L^T without pivoting.  Returns info as CHAMELEON_dsytrf_nopiv_Tile does (of the
+    transformed matrix); last_sytrf_stats() reports the inertia and the growth, last_rbt_stats() the phases."""
+    return check("chol_sytrf_rbt_tile", lib().chol_sytrf_rbt_tile(uplo, A.handle, W.handle, depth, seed))
+
+
+def CHAMELEON_dsytrs_rbt_Tile(uplo: int, A: Desc, W: Desc, depth: int, B: Desc) -> int:
+    """B <- W inv(L D L^T) W^T B from what CHAMELEON_dsytrf_rbt_Tile left in A and W; both are only read."""
+    return check("chol_sytrs_rbt_tile", lib().chol_sytrs_rbt_tile(uplo, A.handle, W.handle, depth, B.handle))
+
+
+def CHAMELEON_dsysv_rbt_Tile(uplo: int, A: Desc, AF: Desc, W: Desc, depth: int, seed: int, B: Desc, X: Desc):
+    """A X = B for a general symmetric indefinite A (fp64): the butterfly-randomised factorisation of a copy AF, the
+    solve, and refinement against the untouched A.  Returns (info, iter, berr): info 0, the factorisation's info
+    (iter = -3) or n + 1 (iter = -31: no convergence in 10 steps); iter the refinement steps; berr the final
+    max |R(:,j)| / (||A||_inf max |X(:,j)|) of every column."""
+    it = C.c_int(0)
+    berr = (C.c_double * max(1, B.n))()
+    info = check("chol_sysv_rbt_tile", lib().chol_sysv_rbt_tile(uplo, A.handle, AF.handle, W.handle, depth, seed, B.handle,
+                                                                X.handle, C.byref(it), berr))
+    return info, it.value, [berr[j] for j in range(B.n)]
+
+
+def last_rbt_stats() -> dict:
+    """The last butterfly routine (chol_last_rbt_stats) [ms]: total, generation of W, the transformation of A, the
+    factorisation, the solves, the residual passes, the vector butterflies; then the refinement steps."""
+    v = (C.c_double * 8)()
+    check("chol_last_rbt_stats", lib().chol_last_rbt_stats(v))
+    return {"total_ms": v[0], "gen_ms": v[1], "transform_ms": v[2], "factor_ms": v[3], "solve_ms": v[4],
+            "resid_ms": v[5], "vec_ms": v[6], "steps": int(v[7])}
+
+
 CHAMELEON_spotrs_Tile = CHAMELEON_dpotrs_Tile
 CHAMELEON_sposv_Tile = CHAMELEON_dposv_Tile
 CHAMELEON_slacpy_Tile = CHAMELEON_dlacpy_Tile
@@ -448,6 +487,10 @@ CHAMELEON_ssygst_Tile = CHAMELEON_dsygst_Tile
 CHAMELEON_ssytrf_nopiv_Tile = CHAMELEON_dsytrf_nopiv_Tile
 CHAMELEON_ssytrs_nopiv_Tile = CHAMELEON_dsytrs_nopiv_Tile
 CHAMELEON_ssysv_nopiv_Tile = CHAMELEON_dsysv_nopiv_Tile
+CHAMELEON_srbt_apply_Tile = CHAMELEON_drbt_apply_Tile
+CHAMELEON_ssytrf_rbt_Tile = CHAMELEON_dsytrf_rbt_Tile
+CHAMELEON_ssytrs_rbt_Tile = CHAMELEON_dsytrs_rbt_Tile
+CHAMELEON_ssysv_rbt_Tile = CHAMELEON_dsysv_rbt_Tile
 
 
 def residual_plgsy(L: Desc, bump: float, seed: int) -> float:

@@ -289,6 +289,9 @@ int sym_resid_width(int nrhs);
 size_t sym_resid_part_bytes(const TileGeo &ga, int nrhs);
 void launch_sym_resid(hipStream_t s, const TileGeo &ga, int upper, const double *A, const TileGeo &gx, const double *X,
                       const double *B, double *part, float *Rf, unsigned long long *colmax, int *flag);
+// the same pass with the residual kept in fp64: R (an n x nrhs image like X; only the rows of the matrix are written)
+void launch_sym_resid_f64(hipStream_t s, const TileGeo &ga, int upper, const double *A, const TileGeo &gx,
+                          const double *X, const double *B, double *part, double *R, unsigned long long *colmax);
 // colmax[0] <- bits of the infinity norm of the symmetric matrix (row sums of |A| from the stored triangle)
 void launch_sym_inf_norm(hipStream_t s, const TileGeo &ga, int upper, const double *A, double *part,
                          unsigned long long *colmax);
@@ -476,6 +479,19 @@ void launch_ldl_stage(hipStream_t s, const T *A, long dstride, long bs, int e, i
 // potrs's transposed image Z of the right-hand sides (tile row r of tile column i at (r + i nr) bs) <- Z diag(rv)
 template <typename T>
 void launch_ldl_zscale(hipStream_t s, T *Z, long total, long bs, int e, int nr, const T *rv);
+
+// ---- launchers (rbt.hip): the symmetric random butterfly transformation of chol_sytrf_rbt_tile and its solves ----
+// W: an n x depth (or wider) image with A's row tiling whose column k holds the diagonal entries of level k in row
+// order (level k: 2^k butterflies of order n / 2^k; n a multiple of 2^(k+1)).
+// one level of A <- W^T A W on the stored Lower triangle, in place: A <- D_k^T A D_k
+template <typename T>
+void launch_rbt_sym(hipStream_t s, const TileGeo &ga, T *A, const TileGeo &gw, const T *W, int level);
+// one level on the rows of an n x ncols image: X <- D_k^T X (trans) or D_k X
+template <typename T>
+void launch_rbt_vec(hipStream_t s, const TileGeo &gx, T *X, const TileGeo &gw, const T *W, int level, bool trans);
+// W(r, k) <- src[r + k n], k < depth (src: device)
+template <typename T>
+void launch_rbt_put(hipStream_t s, const TileGeo &gw, T *W, const T *src, long n, int depth);
 
 // out-of-place transposes of `count` mb x mb tiles (mb % 64 == 0)
 template <typename T>

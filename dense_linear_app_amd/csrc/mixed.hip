@@ -12,6 +12,7 @@
 // residual is bit-identical from run to run.  The column max-abs values of R and X are by-products of that pass
 // (integer atomicMax on the bit pattern of a non-negative double: order-independent).
 #include <cfloat>
+#include <type_traits>
 
 #include "cholmi_internal.h"
 
@@ -136,12 +137,12 @@ __global__ __launch_bounds__(256) void k_sym_resid(TileGeo ga, int upper, const 
 }
 
 // R(s, j0 + j) = B - (sum of the partial products of stored row s), added in a fixed order: the blocks (P, Q), Q <= P,
-// of block row P, then (K, P), K >= P.  Rf (may be null): R rounded to fp32, *flag raised where |R| > FLT_MAX.
-// colmax[j]: max |R(:,j)|, colmax[ncols + j]: max |X(:,j)| (X may be null).
-template <int NR>
+// of block row P, then (K, P), K >= P.  Rf (may be null): R rounded to fp32, *flag raised where |R| > FLT_MAX
+// -- or, RO = double, R itself.  colmax[j]: max |R(:,j)|, colmax[ncols + j]: max |X(:,j)| (X may be null).
+template <int NR, typename RO>
 __global__ __launch_bounds__(256) void k_sym_resid_reduce(TileGeo ga, TileGeo gx, const double *__restrict__ part,
                                                           int j0, const double *__restrict__ B,
-                                                          const double *__restrict__ X, float *__restrict__ Rf,
+                                                          const double *__restrict__ X, RO *__restrict__ Rf,
                                                           unsigned long long *colmax, int *flag) {
   const int NB = ga.lmt * (ga.mbs / RB);
   const long s = (long)blockIdx.x * 256 + threadIdx.x;
@@ -155,8 +156,8 @@ __global__ __launch_bounds__(256) void k_sym_resid_reduce(TileGeo ga, TileGeo gx
   const long idx = vec_index(gx, s, j0 + j);
   const double rv = (B ? B[idx] : 0.0) - sum;
   if (Rf) {
-    if (fabs(rv) > (double)FLT_MAX) atomicOr(flag, 1);
-    Rf[idx] = (float)rv;
+    if (std::is_same<RO, float>::value && fabs(rv) > (double)FLT_MAX) atomicOr(flag, 1);
+    Rf[idx] = (RO)rv;
   }
   atomic_max_abs(colmax + j0 + j, rv);
   if (X) atomic_max_abs(colmax + gx.n + j0 + j, X[idx]);
@@ -229,16 +230,16 @@ __global__ __launch_bounds__(256) void k_vec_update(TileGeo gx, const float *__r
 
 int grid_of(long total) { return (int)std::max(1L, std::min((total + 255) / 256, 8192L)); }
 
-template <int NR>
+template <int NR, typename RO>
 void resid_pass(hipStream_t s, const TileGeo &ga, int upper, const double *A, const TileGeo &gx, const double *X,
-                const double *B, int j0, int nr, double *part, float *Rf, unsigned long long *colmax, int *flag,
+                const double *B, int j0, int nr, double *part, RO *Rf, unsigned long long *colmax, int *flag,
                 bool abs_mode) {
   const long NB = (long)ga.lmt * (ga.mbs / RB), pairs = NB * (NB + 1) / 2;
   if (abs_mode)
     hipLaunchKernelGGL((k_sym_resid<NR, true>), dim3((unsigned)pairs), dim3(256), 0, s, ga, upper, A, gx, X, j0, nr, part);
   else
     hipLaunchKernelGGL((k_sym_resid<NR, false>), dim3((unsigned)pairs), dim3(256), 0, s, ga, upper, A, gx, X, j0, nr, part);
-  hipLaunchKernelGGL(k_sym_resid_reduce<NR>, dim3((unsigned)((NB * RB + 255) / 256), (unsigned)nr), dim3(256), 0, s,
+  hipLaunchKernelGGL((k_sym_resid_reduce<NR, RO>), dim3((unsigned)((NB * RB + 255) / 256), (unsigned)nr), dim3(256), 0, s,
                      ga, gx, part, j0, B, X, Rf, colmax, flag);
 }
 
@@ -251,25 +252,36 @@ size_t sym_resid_part_bytes(const TileGeo &ga, int nrhs) {
   return (size_t)(NB * (NB + 1) / 2) * 2 * RB * sym_resid_width(nrhs) * sizeof(double);
 }
 
-void launch_sym_resid(hipStream_t s, const TileGeo &ga, int upper, const double *A, const TileGeo &gx,
-                      const double *X, const double *B, double *part, float *Rf, unsigned long long *colmax, int *flag) {
+template <typename RO>
+void sym_resid_blocks(hipStream_t s, const TileGeo &ga, int upper, const double *A, const TileGeo &gx, const double *X,
+                      const double *B, double *part, RO *Rf, unsigned long long *colmax, int *flag) {
   // column blocks of X of up to 8 right-hand sides, each one pass over the stored triangle
   for (int j0 = 0; j0 < gx.n; j0 += 8) {
     const int nr = (int)std::min<long>(8, gx.n - j0);
     switch (sym_resid_width(nr)) {
-      case 1: resid_pass<1>(s, ga, upper, A, gx, X, B, j0, nr, part, Rf, colmax, flag, false); break;
-      case 2: resid_pass<2>(s, ga, upper, A, gx, X, B, j0, nr, part, Rf, colmax, flag, false); break;
-      case 4: resid_pass<4>(s, ga, upper, A, gx, X, B, j0, nr, part, Rf, colmax, flag, false); break;
-      default: resid_pass<8>(s, ga, upper, A, gx, X, B, j0, nr, part, Rf, colmax, flag, false); break;
+      case 1: resid_pass<1, RO>(s, ga, upper, A, gx, X, B, j0, nr, part, Rf, colmax, flag, false); break;
+      case 2: resid_pass<2, RO>(s, ga, upper, A, gx, X, B, j0, nr, part, Rf, colmax, flag, false); break;
+      case 4: resid_pass<4, RO>(s, ga, upper, A, gx, X, B, j0, nr, part, Rf, colmax, flag, false); break;
+      default: resid_pass<8, RO>(s, ga, upper, A, gx, X, B, j0, nr, part, Rf, colmax, flag, false); break;
     }
   }
+}
+
+void launch_sym_resid(hipStream_t s, const TileGeo &ga, int upper, const double *A, const TileGeo &gx,
+                      const double *X, const double *B, double *part, float *Rf, unsigned long long *colmax, int *flag) {
+  sym_resid_blocks<float>(s, ga, upper, A, gx, X, B, part, Rf, colmax, flag);
+}
+
+void launch_sym_resid_f64(hipStream_t s, const TileGeo &ga, int upper, const double *A, const TileGeo &gx,
+                          const double *X, const double *B, double *part, double *R, unsigned long long *colmax) {
+  sym_resid_blocks<double>(s, ga, upper, A, gx, X, B, part, R, colmax, nullptr);
 }
 
 void launch_sym_inf_norm(hipStream_t s, const TileGeo &ga, int upper, const double *A, double *part,
                          unsigned long long *colmax) {
   TileGeo g1 = ga;
   g1.n = 1;
-  resid_pass<1>(s, ga, upper, A, g1, nullptr, nullptr, 0, 1, part, nullptr, colmax, nullptr, true);
+  resid_pass<1, float>(s, ga, upper, A, g1, nullptr, nullptr, 0, 1, part, nullptr, colmax, nullptr, true);
 }
 
 void launch_sym_to_f32(hipStream_t s, const TileGeo &ga, int upper, const double *A, float *Af, int *flag) {

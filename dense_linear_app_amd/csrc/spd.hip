@@ -2,7 +2,8 @@
 // mixed-precision solve (dsposv), the inverse (trtri / potri / poinv), the condition estimate (lansy / pocon) and the
 // expert solve with error bounds (poequ / laqsy / porfs / posvx), the pivoted factorisation (pstrf), the
 // reduction of the generalized symmetric-definite eigenproblem (sygst) and the L D L^T factorisation without pivoting
-// with its solve (sytrf_nopiv / sytrs_nopiv / sysv_nopiv).  All run on the main stream of the context that
+// with its solve (sytrf_nopiv / sytrs_nopiv / sysv_nopiv) and their randomised forms for general symmetric indefinite
+// matrices (sytrf_rbt / sytrs_rbt / sysv_rbt / rbt_apply).  All run on the main stream of the context that
 // api.hip keeps (api_internal.h); this file owns only its scratch and the statistics of the last call.
 #include <hip/hip_runtime.h>
 
@@ -55,6 +56,11 @@ double sg_stats[8] = {};  // of the last chol_sygst_tile (chol_last_sygst_stats)
 // staged diagonal tiles with 1 / d
 ScratchPool<4> sy;
 double sy_stats[8] = {};  // of the last chol_sytrf_nopiv_tile (chol_last_sytrf_stats)
+// chol_sytrf_rbt_tile's generated butterfly entries (n x depth, compact); chol_sysv_rbt_tile's residual image (n x
+// nrhs, B's layout), the residual's per-block partial sums, the column maxima.  Not cleared when it grows (a clear on
+// the null stream would race with the main stream's upload of W): every buffer is written before it is read
+ScratchPool<4> rb;
+double rb_stats[8] = {};  // of the last chol_sytrf_rbt_tile / chol_sytrs_rbt_tile / chol_sysv_rbt_tile (chol_last_rbt_stats)
 
 hipStream_t main_stream() { return main_rank_ctx()->st[ST_MAIN]; }
 
@@ -1371,9 +1377,9 @@ int sytrf_run(int uplo, chol_desc *A) {
 // B <- A^{-1} B from that factor: potrs_impl's sweeps over the diagonal tiles staged with unit diagonals, the
 // right-hand sides scaled by 1 / d in between.  A zero on the stored diagonal returns its index before B is written.
 template <typename T>
-int sytrs_impl(int upper, chol_desc *A, chol_desc *B) {
+int sytrs_impl(int upper, chol_desc *A, chol_desc *B, bool diag_checked = false) {
   int info = 0;
-  int rc = diag_zero<T>(A, &info);
+  int rc = diag_checked ? 0 : diag_zero<T>(A, &info);  // (sytrs_rbt has looked before its butterflies wrote B)
   if (rc) return rc;
   if (info) return info;
   const int nt = A->nt, e = A->mbi;
@@ -1390,6 +1396,199 @@ int sytrs_impl(int upper, chol_desc *A, chol_desc *B) {
   return rc;
 }
 
+// ---------------------------------------------------------------- the symmetric random butterfly transformation
+// (Baboulin, Becker, Dongarra 2012; MAGMA's *_rbt): A_r = W^T A W with the recursive butterfly W = D_(d-1) ... D_0 of
+// depth d (D_0 one butterfly of order n, D_k block diagonal with 2^k butterflies of order n / 2^k), then L D L^T of A_r
+// without pivoting, A^{-1} = W (L D L^T)^{-1} W^T, and for sysv_rbt iterative refinement against the original A.  W is the
+// n x d descriptor of the butterflies' diagonal entries (rbt.hip); W^T A W applies the level of the smallest
+// butterflies first.  rb_stats [ms]: total, generation + upload of W, the transformation, the factorisation, the
+// solves, the residual passes, the vector butterflies; then the refinement steps.
+enum { RB_TOTAL = 0, RB_GEN, RB_XFORM, RB_FACT, RB_SOLVE, RB_RESID, RB_VEC, RB_STEPS };
+constexpr int RBT_ITMAX = 10;
+
+// the entries exp(r / 10), r uniform in [-1/2, 1/2]: the 64-bit LCG of chol_plgsy_tile stepped once per entry from the
+// seed, level by level and row by row, on the host (libm's exp, rounded to T), so that (n, depth, seed, dtype) names W
+template <typename T>
+int rbt_generate(chol_desc *W, long n, int depth, unsigned long long seed) {
+  hipStream_t s = main_stream();
+  std::vector<T> h((size_t)n * depth);
+  unsigned long long ran = seed;
+  for (size_t x = 0; x < h.size(); ++x) {
+    ran = 6364136223846793005ULL * ran + 1ULL;
+    const double r = 0.5 - (double)ran * 5.4210108624275222e-20;
+    h[x] = (T)std::exp(r / 10.0);
+  }
+  if (int rc = rb.ensure_bytes(0, h.size() * sizeof(T), "sytrf_rbt_tile")) return rc;
+  HIPCHECK(hipMemcpyAsync(rb.p[0], h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s));
+  launch_rbt_put<T>(s, geo_of(W), reinterpret_cast<T *>(W->mat), rb.as<T>(0), n, depth);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(s));  // (h goes out of scope)
+  return 0;
+}
+
+// A <- W^T A W on the Lower stored triangle
+template <typename T>
+void rbt_transform(chol_desc *A, const chol_desc *W, int depth) {
+  for (int k = depth - 1; k >= 0; --k)
+    launch_rbt_sym<T>(main_stream(), geo_of(A), reinterpret_cast<T *>(A->mat), geo_of(W), reinterpret_cast<const T *>(W->mat), k);
+}
+
+// X <- W^T X (the smallest butterflies first) or W X (the full-order butterfly first)
+template <typename T>
+int rbt_vectors(chol_desc *X, const chol_desc *W, int depth, bool trans, double *st) {
+  EventTimer tv;
+  if (int rc = tv.start()) return rc;
+  for (int x = 0; x < depth; ++x)
+    launch_rbt_vec<T>(main_stream(), geo_of(X), reinterpret_cast<T *>(X->mat), geo_of(W), reinterpret_cast<const T *>(W->mat),
+                      trans ? depth - 1 - x : x, trans);
+  HIPCHECK(hipGetLastError());
+  return tv.stop(&st[RB_VEC]);
+}
+
+// W filled (seed != 0), A <- W^T A W on the `uplo` triangle, then sytrf_impl on it -> *info.  Upper: one transpose of
+// the storage before the transformation and one after the factorisation.
+template <typename T>
+int sytrf_rbt_impl(int uplo, chol_desc *A, chol_desc *W, int depth, unsigned long long seed, int *info, double *st) {
+  EventTimer tp;
+  int rc;
+  if (seed) {
+    if ((rc = tp.start())) return rc;
+    if ((rc = rbt_generate<T>(W, A->lm, depth, seed))) return rc;
+    if ((rc = tp.stop(&st[RB_GEN]))) return rc;
+  }
+  const bool up = uplo == CHOL_UPPER;
+  if ((rc = tp.start())) return rc;
+  if (up) transpose_storage(A);
+  rbt_transform<T>(A, W, depth);
+  HIPCHECK(hipGetLastError());
+  if ((rc = tp.stop(&st[RB_XFORM]))) return rc;
+  if ((rc = tp.start())) return rc;
+  rc = sytrf_impl<T>(A, info);
+  if (up) transpose_storage(A);
+  HIPCHECK(hipGetLastError());
+  if (int r2 = tp.stop(&st[RB_FACT])) return r2;
+  return rc;
+}
+
+// B <- W (L D L^T)^{-1} W^T B; a zero on the factor's stored diagonal returns its index before B is written
+template <typename T>
+int sytrs_rbt_impl(int upper, chol_desc *A, const chol_desc *W, int depth, chol_desc *B, double *st,
+                   bool diag_checked = false) {
+  int info = 0;
+  int rc = diag_checked ? 0 : diag_zero<T>(A, &info);  // (the refinement steps solve with the factor the first solve saw)
+  if (rc) return rc;
+  if (info) return info;
+  if ((rc = rbt_vectors<T>(B, W, depth, true, st))) return rc;
+  EventTimer tp;
+  if ((rc = tp.start())) return rc;
+  if ((rc = sytrs_impl<T>(upper, A, B, /*diag_checked=*/true))) return rc;
+  if ((rc = tp.stop(&st[RB_SOLVE]))) return rc;
+  return rbt_vectors<T>(B, W, depth, false, st);
+}
+
+// chol_sysv_rbt_tile in fp64 after its argument checks
+int sysv_rbt_impl(int uplo, chol_desc *A, chol_desc *AF, chol_desc *W, int depth, unsigned long long seed, chol_desc *B,
+                  chol_desc *X, int *iter, double *berr) {
+  hipStream_t s = main_stream();
+  double *st = rb_stats;
+  const int up = uplo == CHOL_UPPER ? 1 : 0, nrhs = B->ln;
+  const TileGeo ga = geo_of(A), gx = geo_of(B);
+  const char *what = "sysv_rbt_tile";
+  const size_t img = (size_t)B->lmt * B->lnt * B->bsizi * sizeof(double);
+  int rc = rb.ensure_bytes(1, img, what);
+  if (!rc) rc = rb.ensure_bytes(2, sym_resid_part_bytes(ga, nrhs), what);
+  if (!rc) rc = rb.ensure_bytes(3, (size_t)(2 * nrhs + 2) * sizeof(unsigned long long), what);
+  if (rc) return rc;
+  double *R = rb.as<double>(1), *part = rb.as<double>(2);
+  unsigned long long *colmax = rb.as<unsigned long long>(3);
+  std::vector<unsigned long long> hmax(2 * nrhs);
+  chol_desc Rd = *B;  // the residual / correction: B's geometry over the scratch
+  Rd.mat = R;
+  Rd.user_mat = nullptr;
+  Rd.owns = false;
+  Rd.version = 0;
+  Rd.d_list = nullptr;
+  EventTimer tt, tp;
+  if ((rc = tt.start())) return rc;
+  // anrm (counted with the residual passes: the same kernel), AF <- the triangle of A
+  if ((rc = tp.start())) return rc;
+  HIPCHECK(hipMemsetAsync(colmax, 0, (2 * nrhs + 2) * sizeof(unsigned long long), s));
+  HIPCHECK(hipMemsetAsync(R, 0, img, s));  // (the solve runs on whole tiles: the padding must be finite)
+  launch_sym_inf_norm(s, ga, up, (const double *)A->mat, part, colmax);
+  launch_lacpy<double>(s, ga, up ? 2 : 1, (const double *)A->mat, (double *)AF->mat);
+  HIPCHECK(hipGetLastError());
+  unsigned long long anrm_bits = 0;
+  HIPCHECK(hipMemcpyAsync(&anrm_bits, colmax, sizeof anrm_bits, hipMemcpyDeviceToHost, s));
+  if ((rc = tp.stop(&st[RB_RESID]))) return rc;
+  double anrm;
+  memcpy(&anrm, &anrm_bits, sizeof anrm);
+  const double cte = anrm * std::ldexp(1.0, -53) * std::sqrt((double)A->lm);
+  auto finish = [&](int it, int ret) {
+    *iter = it;
+    const int r = tt.stop(&st[RB_TOTAL]);
+    return r ? r : ret;
+  };
+  int info = 0;
+  rc = sytrf_rbt_impl<double>(uplo, AF, W, depth, seed, &info, st);
+  if (rc) return rc;
+  if (info) return finish(-3, info);  // (X untouched)
+  launch_lacpy<double>(s, gx, 0, (const double *)B->mat, (double *)X->mat);
+  HIPCHECK(hipGetLastError());
+  rc = sytrs_rbt_impl<double>(up, AF, W, depth, X, st);
+  if (rc < 0) return rc;
+  if (rc > 0) return finish(-3, rc);
+  for (int it = 0;; ++it) {
+    // R = B - A X from the stored triangle of the untouched A; the column maxima of R and X
+    if ((rc = tp.start())) return rc;
+    HIPCHECK(hipMemsetAsync(colmax, 0, (2 * nrhs + 2) * sizeof(unsigned long long), s));
+    launch_sym_resid_f64(s, ga, up, (const double *)A->mat, gx, (const double *)X->mat, (const double *)B->mat, part, R,
+                         colmax);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(hmax.data(), colmax, 2 * nrhs * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if ((rc = tp.stop(&st[RB_RESID]))) return rc;
+    bool done = true;
+    for (int j = 0; j < nrhs; ++j) {
+      double rn, xn;
+      memcpy(&rn, &hmax[j], sizeof rn);
+      memcpy(&xn, &hmax[nrhs + j], sizeof xn);
+      if (berr) berr[j] = rn == 0 ? 0.0 : rn / (anrm * xn);
+      if (!(rn <= xn * cte)) done = false;  // (a NaN residual does not converge)
+    }
+    if (done) return finish(it, 0);
+    if (it == RBT_ITMAX) return finish(-31, A->lm + 1);
+    rc = sytrs_rbt_impl<double>(up, AF, W, depth, &Rd, st, /*diag_checked=*/true);
+    if (rc) return rc;
+    launch_geadd<double>(s, gx, 1.0, R, 1.0, (double *)X->mat);
+    HIPCHECK(hipGetLastError());
+    st[RB_STEPS] += 1;
+  }
+}
+
+// the argument rules the butterfly routines share: A square, device-resident, single process, stored tile edge a
+// multiple of 128; depth 1 or 2; the order a multiple of 2^depth; W n x depth or wider with A's dtype and row tiling
+int rbt_args(const char *what, int uplo, chol_desc *A, int apos, chol_desc *W, int wpos, int depth, int dpos) {
+  char buf[160];
+  auto bad = [&](int code, const char *why) {
+    snprintf(buf, sizeof buf, "%s: %s", what, why);
+    return fail(code, buf);
+  };
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return bad(-1, "uplo");
+  if (!A) return bad(-apos, "NULL A");
+  int rc = inverse_check(what, A, apos);
+  if (rc) return rc;
+  if (A->mbi % MACRO) return bad(CHOL_ERR_NOT_SUPPORTED, "stored tile edge must be a multiple of 128");
+  if (!W) return bad(-wpos, "NULL W");
+  if (W->p * W->q != 1 || !W->on_device) return bad(CHOL_ERR_NOT_SUPPORTED, "W must be a device-resident single-process descriptor");
+  if (depth != 1 && depth != 2) return bad(-dpos, "depth must be 1 or 2");
+  if (W->dtype != A->dtype || W->mb != A->mb || W->nb != A->nb || W->mbi != A->mbi || W->lm != A->lm || W->ln < depth ||
+      W == A || W->mat == A->mat)
+    return bad(-wpos, "W must be an n x depth descriptor of its own with A's order, tile size and type");
+  if (A->lm % (1 << depth))
+    return bad(CHOL_ERR_NOT_SUPPORTED, "the order must be a multiple of 2^depth (border A with an identity row)");
+  if (!winv_fits(A)) return bad(CHOL_ERR_NOT_SUPPORTED, "tile size above 4096");
+  return 0;
+}
+
 }  // namespace
 
 void cholmi::spd_release() {
@@ -1401,6 +1600,7 @@ void cholmi::spd_release() {
   ps.release();
   sg.release();
   sy.release();
+  rb.release();
 }
 
 // ---------------------------------------------------------------- the entry points (C linkage: include/cholmi.h)
@@ -1765,5 +1965,111 @@ int chol_last_sytrf_stats(double *out8) {
   if (!out8) return fail(-1, "last_sytrf_stats: NULL");
   std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
   for (int i = 0; i < 8; ++i) out8[i] = sy_stats[i];
+  return 0;
+}
+
+int chol_rbt_apply_tile(int uplo, chol_desc_t *A, chol_desc_t *W, int depth) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "rbt_apply_tile before chol_init");
+  return with_views({{A, true}, {W, false}}, [&]() -> int {
+  int rc = rbt_args("rbt_apply_tile", uplo, A, 2, W, 3, depth, 4);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  if (A->lm == 0) return 0;
+  forget_winv(A->mat);  // (A is overwritten)
+  const bool up = uplo == CHOL_UPPER;
+  if (up) transpose_storage(A);
+  if (A->dtype == CHOL_REAL_DOUBLE)
+    rbt_transform<double>(A, W, depth);
+  else
+    rbt_transform<float>(A, W, depth);
+  if (up) transpose_storage(A);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(main_stream()));
+  return 0;
+  });
+}
+
+int chol_sytrf_rbt_tile(int uplo, chol_desc_t *A, chol_desc_t *W, int depth, unsigned long long seed) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "sytrf_rbt_tile before chol_init");
+  return with_views({{A, true}, {W, true}}, [&]() -> int {
+  int rc = rbt_args("sytrf_rbt_tile", uplo, A, 2, W, 3, depth, 4);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  std::fill(rb_stats, rb_stats + 8, 0.0);
+  if (A->lm == 0) return 0;
+  EventTimer tt;
+  if ((rc = tt.start())) return rc;
+  int info = 0;
+  rc = A->dtype == CHOL_REAL_DOUBLE ? sytrf_rbt_impl<double>(uplo, A, W, depth, seed, &info, rb_stats)
+                                    : sytrf_rbt_impl<float>(uplo, A, W, depth, seed, &info, rb_stats);
+  if (rc) return rc;
+  if ((rc = tt.stop(&rb_stats[RB_TOTAL]))) return rc;
+  return info;
+  });
+}
+
+int chol_sytrs_rbt_tile(int uplo, chol_desc_t *A, chol_desc_t *W, int depth, chol_desc_t *B) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "sytrs_rbt_tile before chol_init");
+  return with_views({{A, false}, {W, false}, {B, true}}, [&]() -> int {
+  int rc = rbt_args("sytrs_rbt_tile", uplo, A, 2, W, 3, depth, 4);
+  if (rc) return rc;
+  if (!B) return fail(-5, "sytrs_rbt_tile: NULL B");
+  if ((rc = resident_whole("sytrs_rbt_tile", B))) return rc;
+  if (B->lm != A->lm || B->mb != A->mb || B->mbi != A->mbi || B->dtype != A->dtype || B == A || B == W ||
+      B->mat == A->mat || B->mat == W->mat)
+    return fail(-5, "sytrs_rbt_tile: B must be a descriptor of its own with A's order, tile size and type");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  std::fill(rb_stats, rb_stats + 8, 0.0);
+  if (A->lm == 0) return 0;
+  EventTimer tt;
+  if ((rc = tt.start())) return rc;
+  const int up = uplo == CHOL_UPPER;
+  rc = A->dtype == CHOL_REAL_DOUBLE ? sytrs_rbt_impl<double>(up, A, W, depth, B, rb_stats)
+                                    : sytrs_rbt_impl<float>(up, A, W, depth, B, rb_stats);
+  if (rc) return rc;
+  return tt.stop(&rb_stats[RB_TOTAL]);
+  });
+}
+
+int chol_sysv_rbt_tile(int uplo, chol_desc_t *A, chol_desc_t *AF, chol_desc_t *W, int depth, unsigned long long seed,
+                       chol_desc_t *B, chol_desc_t *X, int *iter, double *berr) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "sysv_rbt_tile before chol_init");
+  return with_views({{A, false}, {AF, true}, {W, true}, {B, false}, {X, true}}, [&]() -> int {
+  const char *what = "sysv_rbt_tile";
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "sysv_rbt_tile: uplo");
+  if (!A) return fail(-2, "sysv_rbt_tile: NULL A");
+  int rc = inverse_check(what, A, 2);
+  if (rc) return rc;
+  if (!AF) return fail(-3, "sysv_rbt_tile: NULL AF");
+  if ((rc = resident_whole(what, AF))) return rc;
+  if (!same_geometry(A, AF) || AF == A || AF->mat == A->mat)
+    return fail(-3, "sysv_rbt_tile: AF must be a descriptor of its own with A's geometry and type");
+  if ((rc = rbt_args(what, uplo, AF, 3, W, 4, depth, 5))) return rc;
+  if (W->mat == A->mat) return fail(-4, "sysv_rbt_tile: W aliases A");
+  if (!B) return fail(-7, "sysv_rbt_tile: NULL B");
+  if ((rc = resident_whole(what, B))) return rc;
+  if (B->lm != A->lm || B->mb != A->mb || B->mbi != A->mbi || B->dtype != A->dtype || B->mat == A->mat ||
+      B->mat == AF->mat || B->mat == W->mat)
+    return fail(-7, "sysv_rbt_tile: B must be a descriptor of its own with A's order, tile size and type");
+  if (!X) return fail(-8, "sysv_rbt_tile: NULL X");
+  if ((rc = resident_whole(what, X))) return rc;
+  if (!same_geometry(B, X) || X == B || X->mat == B->mat || X->mat == A->mat || X->mat == AF->mat || X->mat == W->mat)
+    return fail(-8, "sysv_rbt_tile: X must be a descriptor of its own with B's shape, tile size and type");
+  if (!iter) return fail(-9, "sysv_rbt_tile: NULL iter");
+  if (A->dtype != CHOL_REAL_DOUBLE)
+    return fail(CHOL_ERR_NOT_SUPPORTED, "sysv_rbt_tile: fp32 (the residual pass is fp64: use sytrf_rbt / sytrs_rbt)");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  std::fill(rb_stats, rb_stats + 8, 0.0);
+  *iter = 0;
+  if (A->lm == 0 || B->ln == 0) return 0;
+  return sysv_rbt_impl(uplo, A, AF, W, depth, seed, B, X, iter, berr);
+  });
+}
+
+int chol_last_rbt_stats(double *out8) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "last_rbt_stats before chol_init");
+  if (!out8) return fail(-1, "last_rbt_stats: NULL");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  for (int i = 0; i < 8; ++i) out8[i] = rb_stats[i];
   return 0;
 }

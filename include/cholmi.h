@@ -375,6 +375,51 @@ int chol_sysv_nopiv_tile(int uplo, chol_desc_t *A, chol_desc_t *B);
  * the identity padding of a ragged order is not counted.  From fixed-order reductions. */
 int chol_last_sytrf_stats(double *out8);
 
+/* The butterfly-randomised solve of a general symmetric INDEFINITE system (Baboulin, Becker, Dongarra, IPDPS 2012;
+ * MAGMA's *_rbt routines): A_r = W^T A W with a random recursive butterfly W, then A_r = L D L^T WITHOUT pivoting (the
+ * routine above), A^{-1} = W (L D L^T)^{-1} W^T, and in chol_sysv_rbt_tile iterative refinement against the original A.
+ * For the matrices on which chol_sytrf_nopiv_tile stops or loses accuracy: a zero diagonal, a saddle point with a
+ * zero block, a shift next to an eigenvalue of a leading block.  The randomisation makes a zero or tiny pivot
+ * improbable; it does not bound the growth, so chol_sysv_rbt_tile refines and returns the backward error it reached.
+ *
+ * A butterfly of order m = 2h is 2^(-1/2) [[R0, R1], [R0, -R1]], R0 and R1 diagonal of order h.  W = D_(depth-1) ...
+ * D_0: D_0 one butterfly of order n, D_k block diagonal with 2^k butterflies of order n / 2^k.  W is an n x depth (or
+ * wider) descriptor with A's dtype and tile size: column k holds the diagonal entries of level k in row order (rows o
+ * .. o+h-1 of a butterfly over the rows o .. o+2h-1 hold R0, the next h hold R1).  seed != 0: the library fills W with
+ * exp(r / 10), r uniform in [-1/2, 1/2] from the 64-bit generator of chol_plgsy_tile run on the host, so that (n,
+ * depth, seed, dtype) gives the same W everywhere.  seed == 0: W is an input.
+ *
+ * depth is 1 or 2.  n MUST be a multiple of 2^depth (CHOL_ERR_NOT_SUPPORTED otherwise): border A with a row and column
+ * of the identity; the library does not pad.  The other descriptor rules are chol_sytrf_nopiv_tile's (device-resident,
+ * single process, sub-matrix views allowed, stored tile edge a multiple of 128; p x q: CHOL_ERR_NOT_SUPPORTED).  Only
+ * the `uplo` triangle is read or written; the other strict triangle and all padding come back bit for bit.  Fixed
+ * formulas and no reductions in the transformation: a repeated call returns the same bits.
+ *
+ * chol_rbt_apply_tile: A <- W^T A W alone (W is read).  Argument errors: -1 uplo, -2 A, -3 W, -4 depth. */
+int chol_rbt_apply_tile(int uplo, chol_desc_t *A, chol_desc_t *W, int depth);
+/* W filled (seed != 0), A <- W^T A W, then the factorisation of chol_sytrf_nopiv_tile.  Returns what that returns: 0,
+ * or the 1-based index of the first zero or non-finite pivot of A_r.  chol_last_sytrf_stats reports the growth and
+ * the inertia (that of A, by Sylvester's law).  Argument errors: -1 uplo, -2 A, -3 W, -4 depth. */
+int chol_sytrf_rbt_tile(int uplo, chol_desc_t *A, chol_desc_t *W, int depth, unsigned long long seed);
+/* B <- W (L D L^T)^{-1} W^T B from what chol_sytrf_rbt_tile left in A and W; both are only read.  A zero on the stored
+ * diagonal returns its index (info > 0) before B is written.  Argument errors: -1 uplo, -2 A, -3 W, -4 depth, -5 B. */
+int chol_sytrs_rbt_tile(int uplo, chol_desc_t *A, chol_desc_t *W, int depth, chol_desc_t *B);
+/* A X = B: AF <- the `uplo` triangle of A, chol_sytrf_rbt_tile on AF, X <- the solve of B, then refinement in fp64
+ * against the untouched A: R = B - A X from the stored triangle, X += W (L D L^T)^{-1} W^T R, until every column has
+ * max |R(:,j)| <= max |X(:,j)| ||A||_inf eps sqrt(n) (LAPACK DSPOSV's criterion, eps = 2^-53), at most 10 steps.  A and
+ * B are only read.  *iter: the steps taken; -3: the factorisation stopped (the return value is its info, X untouched);
+ * -31: no convergence in 10 steps (the return value is n + 1, X holds the last iterate).  berr (nrhs host doubles,
+ * may be NULL): the final max |R(:,j)| / (||A||_inf max |X(:,j)|) of every column; a column of X that is all zeros
+ * gives 0 when its residual is zero too and +Inf otherwise.  fp64 only: an fp32 A returns
+ * CHOL_ERR_NOT_SUPPORTED (chol_sytrf_rbt_tile / chol_sytrs_rbt_tile / chol_rbt_apply_tile serve both dtypes).
+ * Argument errors: -1 uplo, -2 A, -3 AF, -4 W, -5 depth, -7 B, -8 X, -9 iter. */
+int chol_sysv_rbt_tile(int uplo, chol_desc_t *A, chol_desc_t *AF, chol_desc_t *W, int depth, unsigned long long seed,
+                       chol_desc_t *B, chol_desc_t *X, int *iter, double *berr);
+/* The last chol_sytrf_rbt_tile / chol_sytrs_rbt_tile / chol_sysv_rbt_tile [ms]: total, generation and upload of W, the
+ * transformation of A, the factorisation, all solves, all residual passes (with ||A||_inf), all vector butterflies;
+ * then the number of refinement steps. */
+int chol_last_rbt_stats(double *out8);
+
 /* CHAMELEON_Lapack_to_Tile / Tile_to_Lapack equivalents (host LAPACK layout
  * <-> descriptor storage); single-process descriptors only. */
 int chol_lapack_to_tile(const void *A, int lda, chol_desc_t *desc);
