@@ -3,13 +3,13 @@
 // (worker_distrib.cpp:238, 323, 416, 511) and the whole-matrix tiled POTRF the
 // reference driver calls (v6_test.c:56), run as the reference client's wave DAG
 // (client_distrib.cpp:506-565) on two HIP streams with one wave of lookahead.  The routines that work from a factor
-// (potrs, dsposv, the inverse, the condition estimate, the expert solve) are in spd.hip, on what api_internal.h
-// exports from here.
+// are in spd.hip, on what api_internal.h exports from here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -638,11 +638,16 @@ int fail(int code, const char *msg) {
   set_error(msg);
   return code;
 }
-int fail_hip(hipError_t e, const char *what, const char *file, int line) {
+int failf(int code, const char *fmt, ...) {
   char buf[256];
-  snprintf(buf, sizeof buf, "%s failed at %s:%d: %s", what, file, line, hipGetErrorString(e));
-  set_error(buf);
-  return CHOL_ERR_HIP;
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  return fail(code, buf);
+}
+int fail_hip(hipError_t e, const char *what, const char *file, int line) {
+  return failf(CHOL_ERR_HIP, "%s failed at %s:%d: %s", what, file, line, hipGetErrorString(e));
 }
 int scratch_failed(const char *what) {
   (void)hipGetLastError();
@@ -669,19 +674,20 @@ int with_views(std::initializer_list<ViewArg> views, const std::function<int()> 
 }
 
 int resident_whole(const char *what, const chol_desc *d) {
-  char buf[160];
   const char *why = nullptr;
   if (!d) why = "NULL descriptor";
   else if (!d->on_device) why = "descriptor must be device-resident";
   else if (d->p * d->q != 1) why = "distributed descriptor";
   else if (d->mb != d->nb) why = "tiles must be square";
   if (!why) return 0;
-  snprintf(buf, sizeof buf, "%s: %s", what, why);
-  return fail(d ? CHOL_ERR_NOT_SUPPORTED : -2, buf);
+  return failf(d ? CHOL_ERR_NOT_SUPPORTED : -2, "%s: %s", what, why);
 }
 bool same_geometry(const chol_desc *a, const chol_desc *b) {
   return a->dtype == b->dtype && a->mb == b->mb && a->nb == b->nb && a->lm == b->lm && a->ln == b->ln &&
          a->mbi == b->mbi && a->lmt == b->lmt && a->lnt == b->lnt;
+}
+bool same_rows(const chol_desc *a, const chol_desc *b) {
+  return a->lm == b->lm && a->mb == b->mb && a->mbi == b->mbi && a->dtype == b->dtype;
 }
 TileGeo geo_of(const chol_desc *d) {
   TileGeo g;
@@ -708,6 +714,16 @@ void transpose_storage(chol_desc *A) {
     launch_transpose_inplace<float>(g.r.st[ST_MAIN], (float *)A->mat, A->nt, A->mbi);
 }
 
+int through_lower(bool upper, std::initializer_list<chol_desc *> ds, const std::function<int()> &body, bool wait,
+                  void (*flip)(chol_desc *)) {
+  if (!upper) return body();
+  for (chol_desc *d : ds) flip(d);
+  const int rc = body();
+  for (chol_desc *d : ds) flip(d);
+  if (wait) HIPCHECK(hipStreamSynchronize(g.r.st[ST_MAIN]));
+  return rc;
+}
+
 LocalMat whole_local_mat(const chol_desc *d) { return local_mat(d, d->mat); }
 WorkRange whole_col_range(const chol_desc *d, int jlo, int jhi) {
   const ColRange r = col_range(d, jlo, jhi);
@@ -727,11 +743,8 @@ int potrf_run(int uplo, chol_desc *A) {
     return fail(CHOL_ERR_NOT_SUPPORTED, "potrf_tile(Upper): single-process device-resident square matrices");
   if (one && !(A->on_device && A->mb % MACRO == 0))
     return A->dtype == CHOL_REAL_DOUBLE ? potrf_impl<double>(A, true) : potrf_impl<float>(A, true);
-  transpose_storage(A);
-  const int rc = A->dtype == CHOL_REAL_DOUBLE ? potrf_impl<double>(A) : potrf_impl<float>(A);
-  transpose_storage(A);
-  HIPCHECK(hipStreamSynchronize(g.r.st[ST_MAIN]));
-  return rc;
+  return through_lower(true, {A},
+                       [&] { return A->dtype == CHOL_REAL_DOUBLE ? potrf_impl<double>(A) : potrf_impl<float>(A); });
 }
 
 void *DevPool::get(size_t bytes) {
@@ -1869,10 +1882,7 @@ int chol_bench_update(chol_desc_t *d, int k, int ablate, int reps, double *ms, d
   std::lock_guard<std::recursive_mutex> lk(g_mu);
   int rc = ensure_events(2);
   if (rc) return rc;
-  PanelRef pan;
-  memset(&pan, 0, sizeof pan);
-  pan.P = 1;
-  pan.base[0] = (char *)d->mat + (size_t)k * d->nt * d->bsizi * d->esize;
+  const PanelRef pan = one_panel((char *)d->mat + (size_t)k * d->nt * d->bsizi * d->esize);
   const LocalMat C = local_mat(d, d->mat);
   const ColRange rr = col_range(d, k + 1, d->nt);
   float best = 1e30f;

@@ -1,6 +1,7 @@
-// What api.hip offers the host code of the routines that work from the factor (spd.hip): the context's state, the
-// error reporting, the descriptor rules, the view refresh and the Upper-through-Lower helpers.  Host only: only
-// api.hip and spd.hip include it (the kernel translation units see cholmi_internal.h alone).
+// What api.hip shares with the other host translation unit of the ABI (spd.hip, the routines that work from a factor):
+// the context's state, the error reporting, the scratch pools, the view refresh, the descriptor rules, running an Upper
+// call through the Lower path, and a whole-matrix descriptor's trailing update.  Host only: the kernel translation
+// units see cholmi_internal.h alone.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,11 +15,16 @@
 
 namespace cholmi {
 
+// (api.hip and spd.hip are compiled with default visibility for the C ABI; CHOL_LOCAL keeps a helper out of the
+// library's dynamic symbols)
+#define CHOL_LOCAL __attribute__((visibility("hidden")))
+
 bool ctx_inited();
 std::recursive_mutex &ctx_mutex();  // one ABI call at a time on the context
 
-// record msg as chol_last_error's text and return code
+// record msg as chol_last_error's text and return code; failf: the text formatted as printf does
 int fail(int code, const char *msg);
+CHOL_LOCAL int failf(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 int fail_hip(hipError_t e, const char *what, const char *file, int line);
 #define HIPCHECK(call)                                                           \
   do {                                                                           \
@@ -74,6 +80,8 @@ int with_views(std::initializer_list<ViewArg> views, const std::function<int()> 
 // the descriptor rules of the whole-matrix routines
 int resident_whole(const char *what, const chol_desc *d);
 bool same_geometry(const chol_desc *a, const chol_desc *b);
+// b has a's rows: its order, tile size, stored tile edge and dtype (a right-hand side of a, or a vector over its rows)
+CHOL_LOCAL bool same_rows(const chol_desc *a, const chol_desc *b);
 TileGeo geo_of(const chol_desc *d);
 
 // the context holds the inverses of at most 32 diagonal 128-blocks (tiles up to 4096): every entry
@@ -85,17 +93,29 @@ void forget_winv(const void *ptr);  // (a tile that is overwritten: its cached b
 
 // chol_potrf_tile after its argument checks, on the descriptor's image as it stands
 int potrf_run(int uplo, chol_desc *A);
-// the stored tiles of a square matrix transposed in place on ST_MAIN, by its dtype: ChamUpper (A = U^T U with
-// U = L^T) runs the Lower path between two of these
+// the stored tiles of a square matrix transposed in place on ST_MAIN, by its dtype
 void transpose_storage(chol_desc *A);
+// body() on the Lower orientation of the square matrices `ds`.  Lower: the body and nothing else.  Upper (A = U^T U
+// with U = L^T): every storage flipped, in the order given, before the body and again after it -- also after a body
+// that failed: the other triangle comes back as it was -- then ST_MAIN synchronised.  wait = false leaves that
+// synchronisation out, for a caller whose next work on the stream follows.  -> the body's status
+CHOL_LOCAL int through_lower(bool upper, std::initializer_list<chol_desc *> ds, const std::function<int()> &body,
+                        bool wait = true, void (*flip)(chol_desc *) = transpose_storage);
 
-// a whole-matrix descriptor's trailing update from another translation unit (as chol_bench_update calls it): its
-// local tile matrix, and the segments of its work list that hold the tiles of columns [jlo, jhi)
+// a whole-matrix descriptor's trailing update: its local tile matrix, the segments of its work list that hold the
+// tiles of columns [jlo, jhi), and a panel whose tiles lie one after another from `base` (tile `first` at base)
 LocalMat whole_local_mat(const chol_desc *d);
 struct WorkRange {
   int off, na, offb, nb;
 };
 WorkRange whole_col_range(const chol_desc *d, int jlo, int jhi);
+inline PanelRef one_panel(const void *base, int first = 0) {
+  PanelRef pan = {};
+  pan.P = 1;
+  pan.base[0] = base;
+  pan.first[0] = first;
+  return pan;
+}
 
 // spd.hip: its scratch, freed by chol_finalize
 void spd_release();

@@ -1,10 +1,9 @@
-// The SPD routines of libcholmi.so that work from a Cholesky factor (include/cholmi.h): the solve (potrs / posv), the
-// mixed-precision solve (dsposv), the inverse (trtri / potri / poinv), the condition estimate (lansy / pocon) and the
-// expert solve with error bounds (poequ / laqsy / porfs / posvx), the pivoted factorisation (pstrf), the
-// reduction of the generalized symmetric-definite eigenproblem (sygst) and the L D L^T factorisation without pivoting
-// with its solve (sytrf_nopiv / sytrs_nopiv / sysv_nopiv) and their randomised forms for general symmetric indefinite
-// matrices (sytrf_rbt / sytrs_rbt / sysv_rbt / rbt_apply).  All run on the main stream of the context that
-// api.hip keeps (api_internal.h); this file owns only its scratch and the statistics of the last call.
+// The routines of libcholmi.so that work from a factor (include/cholmi.h), one section each below: the SPD solve, the
+// mixed-precision solve, the inverse, the condition estimate, the expert solve with error bounds, the pivoted
+// factorisation, the reduction of the generalized symmetric-definite eigenproblem, the L D L^T factorisation without
+// pivoting with its solve, and their butterfly-randomised forms; the entry points come last.  All run on the main
+// stream of the context that api.hip keeps (api_internal.h); this file owns only its scratch and the statistics of the
+// last call of each family.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,48 +20,45 @@ using namespace cholmi;
 
 namespace {
 
-// scratch, grown on demand and kept (one pool per set of buffers that are live together: porfs / posvx hold cn[0]
-// and rf while they call potrs_impl, which grows `work`):
-// potrs_impl's transposed right-hand sides and tiles
-ScratchPool<1> work;
-// chol_dsposv_tile's: the fp32 factor (n x n tile image), the fp32 right-hand side / correction (n x nrhs), the
-// residual's per-block partial sums, and the column maxima + overflow flag
-ScratchPool<4, true> mx;
-// chol_trtri_tile / chol_potri_tile's: the products' Y blocks (then potri's LAUUM image), the 128 x 128 inverses of
-// every diagonal tile's diagonal blocks, a staged copy of a single tile whose edge is not a multiple of 128, and the
-// zero-pivot word
-ScratchPool<4> iv;
-// chol_lansy_tile / chol_pocon_tile's: the staged and inverted diagonal tiles, the 128 x 128 inverses of their
-// diagonal blocks, the products' Y blocks, the sweeps' vectors and partials, the sign vector, the statistics, lansy's
-// per-block partials
-ScratchPool<7> cn;
-// chol_porfs_tile / chol_posvx_tile's: one condest-layout vector per column for the residuals / estimator, the FERR
-// weights and the signs, the residual partials, the sweeps' scratch, the backward errors and statistics, potrs's
-// n x k image, poequ's partials
-ScratchPool<8, true> rf;
-double mx_stats[8] = {};  // of the last chol_dsposv_tile (chol_last_dsposv_stats)
-double cn_stats[4] = {};  // of the last chol_pocon_tile (chol_last_pocon_stats)
-double rf_stats[8] = {};  // of the last chol_posvx_tile / chol_porfs_tile (chol_last_posvx_stats)
-// chol_pstrf_tile's: the candidates' diagonal and sums of squares, the partial maxima and the step's pivot, their
-// indices with the stop word, the pivots and the interchange list
-ScratchPool<3> ps;
-double ps_stats[8] = {};  // of the last chol_pstrf_tile (chol_last_pstrf_stats)
-// chol_sygst_tile's: the inverted diagonal tiles of the factor, their 128-block inverses with the inversion's
-// products, the diagonal step's tiles with one tile row of the deferred solve
-ScratchPool<3> sg;
-double sg_stats[8] = {};  // of the last chol_sygst_tile (chol_last_sygst_stats)
-// chol_sytrf_nopiv_tile's: the unscaled panel (one tile column); the diagonal tile's scratch tile, its unit 128-blocks
-// with their inverses, d and 1 / d; the partial maxima with the statistics and the info word; chol_sytrs_nopiv_tile's
-// staged diagonal tiles with 1 / d
-ScratchPool<4> sy;
-double sy_stats[8] = {};  // of the last chol_sytrf_nopiv_tile (chol_last_sytrf_stats)
-// chol_sytrf_rbt_tile's generated butterfly entries (n x depth, compact); chol_sysv_rbt_tile's residual image (n x
-// nrhs, B's layout), the residual's per-block partial sums, the column maxima.  Not cleared when it grows (a clear on
-// the null stream would race with the main stream's upload of W): every buffer is written before it is read
+// Scratch, grown on demand and kept until chol_finalize: one pool per family, because a family's buffers are live
+// while it calls into another's (porfs / posvx hold cn[0] and rf while they call potrs_impl, which grows `work`).
+// What each buffer holds is said where it is sized.
+ScratchPool<1> work;      // potrs_impl
+ScratchPool<4, true> mx;  // dsposv
+ScratchPool<4> iv;        // trtri / potri; iv[3]: diag_zero's word, for every family that looks for a zero pivot first
+ScratchPool<7> cn;        // lansy / pocon, and the staged factor diagonal that porfs / posvx share with them
+ScratchPool<8, true> rf;  // poequ / porfs / posvx
+ScratchPool<3> ps;        // pstrf
+ScratchPool<3> sg;        // sygst
+ScratchPool<4> sy;        // sytrf_nopiv / sytrs_nopiv
+// sytrf_rbt / sysv_rbt.  Not cleared when it grows (a clear on the null stream would race with the main stream's upload
+// of W): every buffer is written before it is read
 ScratchPool<4> rb;
-double rb_stats[8] = {};  // of the last chol_sytrf_rbt_tile / chol_sytrs_rbt_tile / chol_sysv_rbt_tile (chol_last_rbt_stats)
+
+// The statistics of a family's last call: written by the routine under the context lock, read by chol_last_*_stats
+struct LastStats {
+  double v[8] = {};
+  void clear() { std::fill(v, v + 8, 0.0); }
+  // the accessor chol_last_<name>_stats: the first n values into out
+  int read(const char *name, double *out, int n = 8) const {
+    if (!ctx_inited()) return failf(CHOL_ERR_NOT_INITIALIZED, "last_%s_stats before chol_init", name);
+    if (!out) return failf(-1, "last_%s_stats: NULL", name);
+    std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+    std::copy(v, v + n, out);
+    return 0;
+  }
+};
+LastStats mx_stats, cn_stats, rf_stats, ps_stats, sg_stats, sy_stats, rb_stats;
 
 hipStream_t main_stream() { return main_rank_ctx()->st[ST_MAIN]; }
+
+// one of the trailing updates (launch_trail_update, launch_syr2k_update, launch_ldl_update) on the tiles of d's columns
+// [jlo, jhi), from the given panels
+template <typename Launch, typename... Panels>
+void update_cols(Launch launch, const chol_desc *d, int jlo, int jhi, const Panels &...pans) {
+  const WorkRange rr = whole_col_range(d, jlo, jhi);
+  launch(main_stream(), whole_local_mat(d), d->d_list, rr.off, rr.na, rr.offb, rr.nb, pans...);
+}
 
 // The time between two events on the main stream, added to a statistic; the events are made on first use
 struct EventTimer {
@@ -151,15 +147,11 @@ int potrs_impl(chol_desc *A, chol_desc *B, const T *udiag = nullptr, const T *rd
   return 0;
 }
 
-// potrs_impl for either orientation of the factor: ChamUpper (A = U^T U with U = L^T) transposes the factor's storage
-// in place around the Lower solve; the strict lower triangle comes back as it was.  No synchronisation after the
-// second transpose: the caller's next work on the stream follows it.
+// potrs_impl for either orientation of the factor.  No synchronisation after the second transpose: the caller's next
+// work on the stream follows it.
 template <typename T>
 int potrs_uplo(int upper, chol_desc *A, chol_desc *B) {
-  if (upper) transpose_storage(A);
-  const int rc = potrs_impl<T>(A, B);
-  if (upper) transpose_storage(A);
-  return rc;
+  return through_lower(upper, {A}, [&] { return potrs_impl<T>(A, B); }, /*wait=*/false);
 }
 
 // ---------------------------------------------------------------- mixed-precision solve (LAPACK DSPOSV)
@@ -168,39 +160,74 @@ int potrs_uplo(int upper, chol_desc *A, chol_desc *B) {
 // *iter < 0 (no convergence, an entry that does not fit in fp32, fp32 factor not SPD): X <- B and dposv on A, X.
 constexpr int DSPOSV_ITMAX = 30;
 
+// What this refinement and sysv_rbt_impl's share.  A descriptor over scratch: d's geometry on `mat`, owning nothing and
+// without a work list
+chol_desc scratch_view(const chol_desc *d, void *mat) {
+  chol_desc v = *d;
+  v.mat = mat;
+  v.user_mat = nullptr;
+  v.owns = false;
+  v.version = 0;
+  v.d_list = nullptr;
+  return v;
+}
+
+// the residual passes' `colmax` (mixed.hip): max |R(:,j)|, then max |X(:,j)|, each the bits of a non-negative double,
+// then the overflow flag's word and a spare; launch_sym_inf_norm leaves anrm in the first word
+size_t colmax_bytes(int nrhs) { return (size_t)(2 * nrhs + 2) * sizeof(unsigned long long); }
+
+// LAPACK DSPOSV's stopping rule: max |R(:,j)| <= max |X(:,j)| cte for every column, cte = anrm eps sqrt(n)
+struct RefineTol {
+  double anrm, cte;
+  RefineTol(unsigned long long anrm_bits, long n) {
+    memcpy(&anrm, &anrm_bits, sizeof anrm);
+    cte = anrm * std::ldexp(1.0, -53) * std::sqrt((double)n);
+  }
+  // hmax: colmax read back; berr (or null)[j] <- max |R(:,j)| / (anrm max |X(:,j)|)
+  bool converged(const unsigned long long *hmax, int nrhs, double *berr = nullptr) const {
+    bool done = true;
+    for (int j = 0; j < nrhs; ++j) {
+      double rn, xn;
+      memcpy(&rn, &hmax[j], sizeof rn);
+      memcpy(&xn, &hmax[nrhs + j], sizeof xn);
+      if (berr) berr[j] = rn == 0 ? 0.0 : rn / (anrm * xn);
+      if (!(rn <= xn * cte)) done = false;  // (a NaN residual does not converge)
+    }
+    return done;
+  }
+};
+
 // -> *iter (>= 0: refinement steps; or -2 / -3 / -31 for the fallback), or a negative status
 int dsposv_mixed(int uplo, chol_desc *A, chol_desc *B, chol_desc *X, int *iter) {
   hipStream_t s = main_stream();
   const int up = uplo == CHOL_UPPER ? 1 : 0, nrhs = B->ln;
   const TileGeo ga = geo_of(A), gx = geo_of(B);
-  double *st = mx_stats;  // total, conversions + norm, fp32 factor, fp32 solves, residual passes, #solves, #passes, -
-  std::fill(st, st + 8, 0.0);
+  mx_stats.clear();
+  double *st = mx_stats.v;  // total, conversions + norm, fp32 factor, fp32 solves, residual passes, #solves, #passes, -
   const size_t rf_bytes = (size_t)B->lmt * B->lnt * B->bsizi * sizeof(float);
   const char *what = "dsposv_tile";
+  // the fp32 factor (A's tile image), the fp32 right-hand side / correction (B's), the residual's per-block partial
+  // sums, colmax
   int rc = mx.ensure_bytes(0, (size_t)A->lmt * A->lnt * A->bsizi * sizeof(float), what);
   if (!rc) rc = mx.ensure_bytes(1, rf_bytes, what);
   if (!rc) rc = mx.ensure_bytes(2, sym_resid_part_bytes(ga, nrhs), what);
-  if (!rc) rc = mx.ensure_bytes(3, (size_t)(2 * nrhs + 2) * sizeof(unsigned long long), what);
+  if (!rc) rc = mx.ensure_bytes(3, colmax_bytes(nrhs), what);
   if (rc) return rc;
   float *Af = mx.as<float>(0), *Rf = mx.as<float>(1);
   double *part = mx.as<double>(2);
   unsigned long long *colmax = mx.as<unsigned long long>(3);
   int *flag = reinterpret_cast<int *>(colmax + 2 * nrhs);
   std::vector<unsigned long long> hmax(2 * nrhs + 1);
-  // fp32 descriptors over the scratch: A's and B's geometry (and A's work list)
-  chol_desc Ad = *A, Rd = *B;
+  // fp32 descriptors over the scratch: A's and B's geometry
+  chol_desc Ad = scratch_view(A, Af), Rd = scratch_view(B, Rf);
   Ad.dtype = Rd.dtype = CHOL_REAL_FLOAT;
   Ad.esize = Rd.esize = sizeof(float);
-  Ad.mat = Af;
-  Rd.mat = Rf;
-  Ad.owns = Rd.owns = false;
-  Ad.version = Rd.version = 0;
-  Rd.d_list = nullptr;
+  Ad.d_list = A->d_list;  // (potrf_run walks A's work list)
   EventTimer tt, tp;
   if ((rc = tt.start())) return rc;
   // anrm, then B and A to fp32 (-2 where an entry does not fit)
   if ((rc = tp.start())) return rc;
-  HIPCHECK(hipMemsetAsync(colmax, 0, (2 * nrhs + 2) * sizeof(unsigned long long), s));
+  HIPCHECK(hipMemsetAsync(colmax, 0, colmax_bytes(nrhs), s));
   HIPCHECK(hipMemsetAsync(Rf, 0, rf_bytes, s));  // (the solve runs on whole tiles: padding must be finite)
   launch_sym_inf_norm(s, ga, up, (const double *)A->mat, part, colmax);
   launch_vec_to_f32(s, gx, (const double *)B->mat, Rf, flag);
@@ -211,9 +238,7 @@ int dsposv_mixed(int uplo, chol_desc *A, chol_desc *B, chol_desc *X, int *iter) 
   HIPCHECK(hipMemcpyAsync(&anrm_bits, colmax, sizeof anrm_bits, hipMemcpyDeviceToHost, s));
   HIPCHECK(hipMemcpyAsync(&hflag, flag, sizeof hflag, hipMemcpyDeviceToHost, s));
   if ((rc = tp.stop(&st[1]))) return rc;
-  double anrm;
-  memcpy(&anrm, &anrm_bits, sizeof anrm);
-  const double cte = anrm * std::ldexp(1.0, -53) * std::sqrt((double)A->lm);
+  const RefineTol tol(anrm_bits, A->lm);
   auto finish = [&](int it) {
     *iter = it;
     return tt.stop(&st[0]);
@@ -237,21 +262,14 @@ int dsposv_mixed(int uplo, chol_desc *A, chol_desc *B, chol_desc *X, int *iter) 
   for (int it = 0;; ++it) {
     // R = B - A X in fp64, rounded into Rf; the column maxima of R and X
     if ((rc = tp.start())) return rc;
-    HIPCHECK(hipMemsetAsync(colmax, 0, (2 * nrhs + 2) * sizeof(unsigned long long), s));
+    HIPCHECK(hipMemsetAsync(colmax, 0, colmax_bytes(nrhs), s));
     launch_sym_resid(s, ga, up, (const double *)A->mat, gx, (const double *)X->mat, (const double *)B->mat, part, Rf,
                      colmax, flag);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpyAsync(hmax.data(), colmax, (2 * nrhs + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     if ((rc = tp.stop(&st[4]))) return rc;
     st[6] += 1;
-    bool done = true;
-    for (int j = 0; j < nrhs && done; ++j) {
-      double rn, xn;
-      memcpy(&rn, &hmax[j], sizeof rn);
-      memcpy(&xn, &hmax[nrhs + j], sizeof xn);
-      done = rn <= xn * cte;  // (a NaN residual does not converge)
-    }
-    if (done) return finish(it);
+    if (tol.converged(hmax.data(), nrhs)) return finish(it);
     if (it == DSPOSV_ITMAX) return finish(-DSPOSV_ITMAX - 1);
     if (hmax[2 * nrhs] & 0xffffffffull) return finish(-2);  // (the flag: the low word on a little-endian device)
     if ((rc = solve())) return rc;
@@ -349,23 +367,16 @@ int inverse_impl(chol_desc *A, bool potri) {
 int inverse_check(const char *what, chol_desc *A, int apos) {
   int rc = resident_whole(what, A);
   if (rc) return rc;
-  char buf[160];
-  if (A->mt != A->nt || A->lm != A->ln) {
-    snprintf(buf, sizeof buf, "%s: A is not square", what);
-    return fail(-apos, buf);
-  }
-  if (A->mbi % 64) {
-    snprintf(buf, sizeof buf, "%s: stored tile edge must be a multiple of 64", what);
-    return fail(CHOL_ERR_NOT_SUPPORTED, buf);
-  }
+  if (A->mt != A->nt || A->lm != A->ln) return failf(-apos, "%s: A is not square", what);
+  if (A->mbi % 64) return failf(CHOL_ERR_NOT_SUPPORTED, "%s: stored tile edge must be a multiple of 64", what);
   return 0;
 }
 
-// the first exact zero on the diagonal (1-based), or 0; read before anything is written
+// the first exact zero on the diagonal (1-based), or 0; read before anything is written (what: the calling routine)
 template <typename T>
-int diag_zero(const chol_desc *A, int *info) {
+int diag_zero(const chol_desc *A, int *info, const char *what) {
   hipStream_t s = main_stream();
-  if (int rc = iv.ensure_bytes(3, sizeof(int), "trtri_tile")) return rc;
+  if (int rc = iv.ensure_bytes(3, sizeof(int), what)) return rc;
   int *first = iv.as<int>(3);
   launch_diag_zero<T>(s, reinterpret_cast<const T *>(A->mat), (long)(A->lmt + 1) * A->bsizi, A->mbi, A->mb, A->lm, first);
   HIPCHECK(hipGetLastError());
@@ -380,17 +391,13 @@ int inverse_run(int uplo, chol_desc *A, bool potri) {
   std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
   const bool dbl = A->dtype == CHOL_REAL_DOUBLE;
   int info = 0;
-  int rc = dbl ? diag_zero<double>(A, &info) : diag_zero<float>(A, &info);
+  const char *what = potri ? "potri_tile" : "trtri_tile";
+  int rc = dbl ? diag_zero<double>(A, &info, what) : diag_zero<float>(A, &info, what);
   if (rc) return rc;
   if (info) return info;  // (LAPACK: A is unchanged)
   // ChamUpper: U = L^T; inv(U) = inv(L)^T and inv(U^T U) = inv(L L^T) -- the Lower path on the transposed storage
-  if (uplo == CHOL_UPPER) transpose_storage(A);
-  rc = dbl ? inverse_impl<double>(A, potri) : inverse_impl<float>(A, potri);
-  if (uplo == CHOL_UPPER) {
-    transpose_storage(A);
-    HIPCHECK(hipStreamSynchronize(main_stream()));
-  }
-  return rc;
+  return through_lower(uplo == CHOL_UPPER, {A},
+                       [&] { return dbl ? inverse_impl<double>(A, potri) : inverse_impl<float>(A, potri); });
 }
 
 // ---------------------------------------------------------------- condition estimate (LAPACK DLANSY / DPOCON)
@@ -515,7 +522,7 @@ int pocon_impl(chol_desc *A, int upper, double anorm, double *rcond, bool staged
   hipStream_t s = main_stream();
   const TileGeo ge = geo_of(A);
   const long n = A->lm;
-  for (double &v : cn_stats) v = 0;
+  cn_stats.clear();
   *rcond = 0;
   if (n == 0) {
     *rcond = 1;
@@ -526,7 +533,7 @@ int pocon_impl(chol_desc *A, int upper, double anorm, double *rcond, bool staged
   int rc = tt.start();
   if (rc) return rc;
   int info = 0;
-  rc = diag_zero<T>(A, &info);
+  rc = diag_zero<T>(A, &info, "pocon_tile");
   if (rc) return rc;
   if (info) return 0;  // a zero on the factor's diagonal: rcond = 0, no sweep
   // scratch: the diagonal tiles, their 128-block inverses, the products' Y blocks (stage_factor_diag), the vectors,
@@ -570,9 +577,9 @@ int pocon_impl(chol_desc *A, int upper, double anorm, double *rcond, bool staged
   }
   // (no dlatrs scaling: a sweep that overflows gives rcond = 0)
   if (est.finite && est.est != 0) *rcond = (1.0 / est.est) / anorm;
-  if ((rc = tt.stop(&cn_stats[0]))) return rc;
-  cn_stats[1] = sweep_ms;
-  cn_stats[2] = apps;
+  if ((rc = tt.stop(&cn_stats.v[0]))) return rc;
+  cn_stats.v[1] = sweep_ms;
+  cn_stats.v[2] = apps;
   return 0;
 }
 
@@ -679,13 +686,9 @@ int apply_inv(int upper, chol_desc *AF, const RfBufs<T> &b, T *V, const std::vec
     return 0;
   }
   // wide: potrs_impl on an n x k scratch image with AF's row tiling (the solve runs on whole tiles: zero padding)
-  chol_desc Td = *AF;
+  chol_desc Td = scratch_view(AF, nullptr);
   Td.ln = Td.n = k;
   Td.nt = Td.lnt = (k + AF->mb - 1) / AF->mb;
-  Td.owns = false;
-  Td.version = 0;
-  Td.d_list = nullptr;
-  Td.user_mat = nullptr;
   const size_t tb = (size_t)Td.lmt * Td.lnt * Td.bsizi * sizeof(T);
   if (int rc = rf.ensure_bytes(6, tb, "porfs_tile")) return rc;
   Td.mat = rf.p[6];
@@ -802,25 +805,14 @@ int porfs_impl(int upper, chol_desc *A, chol_desc *AF, chol_desc *B, chol_desc *
 
 // the descriptor rules shared by porfs / posvx: an n x nrhs image d with A's dtype, order and tile size
 int rhs_check(const char *what, const chol_desc *A, const chol_desc *d, int pos, const char *name) {
-  char buf[160];
-  if (!d) {
-    snprintf(buf, sizeof buf, "%s: %s is NULL", what, name);
-    return fail(-pos, buf);
-  }
+  if (!d) return failf(-pos, "%s: %s is NULL", what, name);
   if (int rc = resident_whole(what, d)) return rc;
-  if (d->dtype != A->dtype || d->lm != A->lm || d->mb != A->mb || d->mbi != A->mbi) {
-    snprintf(buf, sizeof buf, "%s: %s must have A's dtype, order and tile size", what, name);
-    return fail(-pos, buf);
-  }
+  if (!same_rows(A, d)) return failf(-pos, "%s: %s must have A's dtype, order and tile size", what, name);
   return 0;
 }
 
 int square_check(const char *what, chol_desc *A, int pos) {
-  if (!A) {
-    char buf[96];
-    snprintf(buf, sizeof buf, "%s: NULL descriptor", what);
-    return fail(-pos, buf);
-  }
+  if (!A) return failf(-pos, "%s: NULL descriptor", what);
   return inverse_check(what, A, pos);
 }
 
@@ -888,25 +880,15 @@ int porfs_args(const char *what, chol_desc *A, chol_desc *AF, chol_desc *B, chol
   int rc = square_check(what, A, apos);
   if (rc) return rc;
   if ((rc = square_check(what, AF, apos + 1))) return rc;
-  char buf[160];
-  if (!same_geometry(A, AF) || AF->mat == A->mat) {
-    snprintf(buf, sizeof buf, "%s: AF must have A's shape, tile size and type, in storage of its own", what);
-    return fail(-(apos + 1), buf);
-  }
+  if (!same_geometry(A, AF) || AF->mat == A->mat)
+    return failf(-(apos + 1), "%s: AF must have A's shape, tile size and type, in storage of its own", what);
   if ((rc = rhs_check(what, A, B, bpos, "B"))) return rc;
   if ((rc = rhs_check(what, A, X, xpos, "X"))) return rc;
-  if (!same_geometry(B, X)) {
-    snprintf(buf, sizeof buf, "%s: X must have B's shape, tile size and type", what);
-    return fail(-xpos, buf);
-  }
-  if (X->mat == A->mat || X->mat == AF->mat || X->mat == B->mat || B->mat == A->mat || B->mat == AF->mat) {
-    snprintf(buf, sizeof buf, "%s: X aliases A, AF or B", what);
-    return fail(-xpos, buf);
-  }
-  if (!winv_fits(AF)) {  // (the wide steps solve with potrs_impl)
-    snprintf(buf, sizeof buf, "%s: tile size above 4096", what);
-    return fail(CHOL_ERR_NOT_SUPPORTED, buf);
-  }
+  if (!same_geometry(B, X)) return failf(-xpos, "%s: X must have B's shape, tile size and type", what);
+  if (X->mat == A->mat || X->mat == AF->mat || X->mat == B->mat || B->mat == A->mat || B->mat == AF->mat)
+    return failf(-xpos, "%s: X aliases A, AF or B", what);
+  // (the wide steps solve with potrs_impl)
+  if (!winv_fits(AF)) return failf(CHOL_ERR_NOT_SUPPORTED, "%s: tile size above 4096", what);
   return 0;
 }
 
@@ -914,8 +896,8 @@ template <typename T>
 int posvx_impl(int fact, int upper, chol_desc *A, chol_desc *AF, int *equed, chol_desc *S, chol_desc *B,
                chol_desc *X, double *rcond, double *ferr, double *berr) {
   hipStream_t s = main_stream();
-  double *st = rf_stats;  // total, equilibrate + scale B, factor, lansy + pocon, solve, porfs, #sweep / #potrs columns
-  std::fill(st, st + 8, 0.0);
+  rf_stats.clear();
+  double *st = rf_stats.v;  // total, equilibrate + scale B, factor, lansy + pocon, solve, porfs, #sweep / #potrs columns
   const long n = A->lm;
   const int nrhs = B->ln, uplo = upper ? CHOL_UPPER : CHOL_LOWER;
   EventTimer tt, tp;
@@ -1044,8 +1026,8 @@ int pstrf_impl(chol_desc *A, int *piv, int *rank, double tol) {
   hipStream_t s = main_stream();
   const long n = A->lm;
   const int mb = A->mb;
-  double *st = ps_stats;  // total, pivot steps, row interchanges, trailing updates, #steps
-  std::fill(st, st + 8, 0.0);
+  ps_stats.clear();
+  double *st = ps_stats.v;  // total, pivot steps, row interchanges, trailing updates, #steps
   for (long i = 0; i < n; ++i) piv[i] = (int)(i + 1);
   *rank = 0;
   if (n == 0) return 0;
@@ -1122,12 +1104,8 @@ int pstrf_impl(chol_desc *A, int *piv, int *rank, double tol) {
     if (stop || k + 1 >= A->nt) continue;
     // the trailing update by tile column k (chol_bench_update's call)
     if ((rc = tp.start())) return rc;
-    PanelRef pan;
-    memset(&pan, 0, sizeof pan);
-    pan.P = 1;
-    pan.base[0] = Am + (size_t)k * A->lmt * A->bsizi;
-    const WorkRange rr = whole_col_range(A, k + 1, A->nt);
-    launch_trail_update<T>(s, whole_local_mat(A), A->d_list, rr.off, rr.na, rr.offb, rr.nb, pan);
+    update_cols(launch_trail_update<T>, A, k + 1, A->nt, one_panel(Am + (size_t)k * A->lmt * A->bsizi), /*yield=*/false,
+                /*pan2=*/nullptr);
     HIPCHECK(hipGetLastError());
     if ((rc = tp.stop(&st[3]))) return rc;
   }
@@ -1136,24 +1114,20 @@ int pstrf_impl(chol_desc *A, int *piv, int *rank, double tol) {
   return *rank < n ? 1 : 0;
 }
 
-// the Lower path, or Upper between two transposes of the storage (transpose_storage; a single tile whose edge is not a
-// multiple of 64 element by element)
-int pstrf_run(int uplo, chol_desc *A, int *piv, int *rank, double tol) {
-  const bool dbl = A->dtype == CHOL_REAL_DOUBLE;
+// pstrf's transpose of the storage: a single tile whose edge is not a multiple of 64 element by element
+void pstrf_flip(chol_desc *A) {
+  if (A->mbi % 64 == 0) return transpose_storage(A);
   const PsGeo g{A->lm, A->mb, A->mbi, A->lmt, (long)A->bsizi};
-  auto flip = [&]() {
-    if (A->mbi % 64 == 0) return transpose_storage(A);
-    if (dbl) launch_pstrf_transpose<double>(main_stream(), g, (double *)A->mat);
-    else launch_pstrf_transpose<float>(main_stream(), g, (float *)A->mat);
-  };
+  if (A->dtype == CHOL_REAL_DOUBLE) launch_pstrf_transpose<double>(main_stream(), g, (double *)A->mat);
+  else launch_pstrf_transpose<float>(main_stream(), g, (float *)A->mat);
+}
+
+int pstrf_run(int uplo, chol_desc *A, int *piv, int *rank, double tol) {
   const bool up = uplo == CHOL_UPPER;
-  if (up) flip();
-  const int rc = dbl ? pstrf_impl<double>(A, piv, rank, tol) : pstrf_impl<float>(A, piv, rank, tol);
-  if (up) {
-    flip();
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(main_stream()));
-  }
+  const int rc = through_lower(up, {A}, [&] {
+    return A->dtype == CHOL_REAL_DOUBLE ? pstrf_impl<double>(A, piv, rank, tol) : pstrf_impl<float>(A, piv, rank, tol);
+  }, /*wait=*/true, pstrf_flip);
+  if (up) HIPCHECK(hipGetLastError());
   return rc;
 }
 
@@ -1203,8 +1177,8 @@ struct PhaseMarks {
 template <typename T>
 int sygst_impl(chol_desc *A, chol_desc *B) {
   hipStream_t s = main_stream();
-  double *st = sg_stats;  // total, diagonal-tile inverses, chain, rank-2k updates, deferred solve, #steps
-  std::fill(st, st + 8, 0.0);
+  sg_stats.clear();
+  double *st = sg_stats.v;  // total, diagonal-tile inverses, chain, rank-2k updates, deferred solve, #steps
   const long n = A->lm;
   if (n == 0) return 0;
   const int nt = A->nt, mb = A->mb, e = A->mbi, lmt = A->lmt;
@@ -1229,7 +1203,6 @@ int sygst_impl(chol_desc *A, chol_desc *B) {
   if ((rc = pm.mark(0))) return rc;
   stage_factor_diag_into<T>(B, 0, Dv, W, Yi);
   if ((rc = pm.mark(P_DIAG))) return rc;
-  const LocalMat lm = whole_local_mat(A);
   for (int k = 0; k < nt; ++k) {
     const int nv = (int)std::min<long>(mb, n - (long)k * mb);
     launch_sygst_diag<T>(s, tile(Am, k, k), e, nv, Dv + k * EE, E, S, W2, Cs);
@@ -1241,14 +1214,7 @@ int sygst_impl(chol_desc *A, chol_desc *B) {
       launch_trsm_panel<T>(s, P, bs, nr, tile(Bm, k, k), W + (long)k * nbm * blk, e, T(1));
       launch_gemm_nt_batch<T>(s, Lt, bs, nr, Cs, 0, 1, P, bs, 0, e, T(-0.5), T(1));
       if ((rc = pm.mark(P_CHAIN))) return rc;
-      PanelRef pan, qan;
-      memset(&pan, 0, sizeof pan);
-      memset(&qan, 0, sizeof qan);
-      pan.P = qan.P = 1;
-      pan.base[0] = tile(Am, 0, k);
-      qan.base[0] = tile(Bm, 0, k);
-      const WorkRange rr = whole_col_range(A, k + 1, nt);
-      launch_syr2k_update<T>(s, lm, A->d_list, rr.off, rr.na, rr.offb, rr.nb, pan, qan);
+      update_cols(launch_syr2k_update<T>, A, k + 1, nt, one_panel(tile(Am, 0, k)), one_panel(tile(Bm, 0, k)));
       if ((rc = pm.mark(P_SYR2K))) return rc;
       launch_gemm_nt_batch<T>(s, Lt, bs, nr, Cs, 0, 1, P, bs, 0, e, T(-0.5), T(1));
     }
@@ -1266,19 +1232,11 @@ int sygst_impl(chol_desc *A, chol_desc *B) {
 int sygst_run(int uplo, chol_desc *A, chol_desc *B) {
   const bool dbl = A->dtype == CHOL_REAL_DOUBLE;
   int info = 0;
-  int rc = dbl ? diag_zero<double>(B, &info) : diag_zero<float>(B, &info);
+  int rc = dbl ? diag_zero<double>(B, &info, "sygst_tile") : diag_zero<float>(B, &info, "sygst_tile");
   if (rc) return rc;
   if (info) return info;
-  const bool up = uplo == CHOL_UPPER;
-  if (up) {
-    transpose_storage(A);
-    transpose_storage(B);
-  }
-  rc = dbl ? sygst_impl<double>(A, B) : sygst_impl<float>(A, B);
-  if (up) {
-    transpose_storage(A);
-    transpose_storage(B);
-  }
+  rc = through_lower(uplo == CHOL_UPPER, {A, B},
+                     [&] { return dbl ? sygst_impl<double>(A, B) : sygst_impl<float>(A, B); });
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipStreamSynchronize(main_stream()));
   return rc;
@@ -1298,8 +1256,8 @@ template <typename T>
 int sytrf_impl(chol_desc *A, int *info) {
   hipStream_t s = main_stream();
   // total, chain, updates [ms]; positive and negative pivots; min |d|, max |d|, max |L|
-  double *st = sy_stats;
-  std::fill(st, st + 8, 0.0);
+  sy_stats.clear();
+  double *st = sy_stats.v;
   *info = 0;
   const long n = A->lm;
   if (n == 0) return 0;
@@ -1307,6 +1265,8 @@ int sytrf_impl(chol_desc *A, int *info) {
   const long bs = A->bsizi, blk = (long)MACRO * MACRO;
   const char *what = "sytrf_nopiv_tile";
   const int npm = ldl_partials();
+  // sy[0]: the unscaled panel (one tile column); sy[1]: the diagonal tile's scratch tile, its unit 128-blocks with their
+  // inverses, d and 1 / d; sy[2]: the partial maxima with the statistics and the info word
   int rc = sy.ensure_bytes(0, (size_t)std::max(1, nt - 1) * bs * sizeof(T), what);
   if (!rc) rc = sy.ensure_bytes(1, ((size_t)bs + 2 * (size_t)nbm * blk + 2 * (size_t)nt * e) * sizeof(T), what);
   if (!rc) rc = sy.ensure_bytes(2, ((size_t)npm + 8) * sizeof(double) + sizeof(int), what);
@@ -1321,7 +1281,6 @@ int sytrf_impl(chol_desc *A, int *info) {
   PhaseMarks pm;
   enum { P_CHAIN = 1, P_UPDATE };
   if ((rc = pm.mark(0))) return rc;
-  const LocalMat lm = whole_local_mat(A);
   int hinfo = 0;
   for (int k = 0; k < nt && !hinfo; ++k) {
     const int nr = nt - 1 - k;
@@ -1335,15 +1294,7 @@ int sytrf_impl(chol_desc *A, int *info) {
     if ((rc = pm.mark(P_CHAIN))) return rc;
     const hipEvent_t chain_end = pm.ev.back();
     if (nr > 0) {
-      PanelRef pan, qan;
-      memset(&pan, 0, sizeof pan);
-      memset(&qan, 0, sizeof qan);
-      pan.P = qan.P = 1;
-      pan.base[0] = Wscr;
-      pan.first[0] = k + 1;
-      qan.base[0] = tile(0, k);
-      const WorkRange rr = whole_col_range(A, k + 1, nt);
-      launch_ldl_update<T>(s, lm, A->d_list, rr.off, rr.na, rr.offb, rr.nb, pan, qan);
+      update_cols(launch_ldl_update<T>, A, k + 1, nt, one_panel(Wscr, k + 1), one_panel(tile(0, k)));
       HIPCHECK(hipGetLastError());
       if ((rc = pm.mark(P_UPDATE))) return rc;
     }
@@ -1364,11 +1315,10 @@ int sytrf_impl(chol_desc *A, int *info) {
 // the Lower path, or Upper between two transposes of the storage (U^T D U = L D L^T with L = U^T); -> info
 int sytrf_run(int uplo, chol_desc *A) {
   if (A->mbi % MACRO) return fail(CHOL_ERR_NOT_SUPPORTED, "sytrf_nopiv_tile: stored tile edge must be a multiple of 128");
-  const bool dbl = A->dtype == CHOL_REAL_DOUBLE, up = uplo == CHOL_UPPER;
   int info = 0;
-  if (up) transpose_storage(A);
-  const int rc = dbl ? sytrf_impl<double>(A, &info) : sytrf_impl<float>(A, &info);
-  if (up) transpose_storage(A);
+  const int rc = through_lower(uplo == CHOL_UPPER, {A}, [&] {
+    return A->dtype == CHOL_REAL_DOUBLE ? sytrf_impl<double>(A, &info) : sytrf_impl<float>(A, &info);
+  });
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipStreamSynchronize(main_stream()));
   return rc ? rc : info;
@@ -1379,21 +1329,19 @@ int sytrf_run(int uplo, chol_desc *A) {
 template <typename T>
 int sytrs_impl(int upper, chol_desc *A, chol_desc *B, bool diag_checked = false) {
   int info = 0;
-  int rc = diag_checked ? 0 : diag_zero<T>(A, &info);  // (sytrs_rbt has looked before its butterflies wrote B)
+  // (sytrs_rbt has looked before its butterflies wrote B)
+  int rc = diag_checked ? 0 : diag_zero<T>(A, &info, "sytrs_nopiv_tile");
   if (rc) return rc;
   if (info) return info;
   const int nt = A->nt, e = A->mbi;
   const long bs = A->bsizi;
+  // sy[3]: the staged diagonal tiles, then 1 / d
   if ((rc = sy.ensure_bytes(3, ((size_t)nt * bs + (size_t)nt * e) * sizeof(T), "sytrs_nopiv_tile"))) return rc;
   T *U = sy.as<T>(3), *rv = U + (long)nt * bs;
-  if (upper) transpose_storage(A);
-  launch_ldl_stage<T>(main_stream(), reinterpret_cast<const T *>(A->mat), (long)(A->lmt + 1) * bs, bs, e, nt, U, rv);
-  rc = potrs_impl<T>(A, B, U, rv);
-  if (upper) {
-    transpose_storage(A);
-    HIPCHECK(hipStreamSynchronize(main_stream()));
-  }
-  return rc;
+  return through_lower(upper, {A}, [&] {
+    launch_ldl_stage<T>(main_stream(), reinterpret_cast<const T *>(A->mat), (long)(A->lmt + 1) * bs, bs, e, nt, U, rv);
+    return potrs_impl<T>(A, B, U, rv);
+  });
 }
 
 // ---------------------------------------------------------------- the symmetric random butterfly transformation
@@ -1446,7 +1394,7 @@ int rbt_vectors(chol_desc *X, const chol_desc *W, int depth, bool trans, double 
 }
 
 // W filled (seed != 0), A <- W^T A W on the `uplo` triangle, then sytrf_impl on it -> *info.  Upper: one transpose of
-// the storage before the transformation and one after the factorisation.
+// the storage before the transformation and one after the factorisation, inside the two phases' times.
 template <typename T>
 int sytrf_rbt_impl(int uplo, chol_desc *A, chol_desc *W, int depth, unsigned long long seed, int *info, double *st) {
   EventTimer tp;
@@ -1456,15 +1404,14 @@ int sytrf_rbt_impl(int uplo, chol_desc *A, chol_desc *W, int depth, unsigned lon
     if ((rc = rbt_generate<T>(W, A->lm, depth, seed))) return rc;
     if ((rc = tp.stop(&st[RB_GEN]))) return rc;
   }
-  const bool up = uplo == CHOL_UPPER;
   if ((rc = tp.start())) return rc;
-  if (up) transpose_storage(A);
-  rbt_transform<T>(A, W, depth);
-  HIPCHECK(hipGetLastError());
-  if ((rc = tp.stop(&st[RB_XFORM]))) return rc;
-  if ((rc = tp.start())) return rc;
-  rc = sytrf_impl<T>(A, info);
-  if (up) transpose_storage(A);
+  rc = through_lower(uplo == CHOL_UPPER, {A}, [&]() -> int {
+    rbt_transform<T>(A, W, depth);
+    HIPCHECK(hipGetLastError());
+    if (int r = tp.stop(&st[RB_XFORM])) return r;
+    if (int r = tp.start()) return r;
+    return sytrf_impl<T>(A, info);
+  }, /*wait=*/false);
   HIPCHECK(hipGetLastError());
   if (int r2 = tp.stop(&st[RB_FACT])) return r2;
   return rc;
@@ -1475,7 +1422,8 @@ template <typename T>
 int sytrs_rbt_impl(int upper, chol_desc *A, const chol_desc *W, int depth, chol_desc *B, double *st,
                    bool diag_checked = false) {
   int info = 0;
-  int rc = diag_checked ? 0 : diag_zero<T>(A, &info);  // (the refinement steps solve with the factor the first solve saw)
+  // (the refinement steps solve with the factor the first solve saw)
+  int rc = diag_checked ? 0 : diag_zero<T>(A, &info, "sytrs_rbt_tile");
   if (rc) return rc;
   if (info) return info;
   if ((rc = rbt_vectors<T>(B, W, depth, true, st))) return rc;
@@ -1490,29 +1438,25 @@ int sytrs_rbt_impl(int upper, chol_desc *A, const chol_desc *W, int depth, chol_
 int sysv_rbt_impl(int uplo, chol_desc *A, chol_desc *AF, chol_desc *W, int depth, unsigned long long seed, chol_desc *B,
                   chol_desc *X, int *iter, double *berr) {
   hipStream_t s = main_stream();
-  double *st = rb_stats;
+  double *st = rb_stats.v;
   const int up = uplo == CHOL_UPPER ? 1 : 0, nrhs = B->ln;
   const TileGeo ga = geo_of(A), gx = geo_of(B);
   const char *what = "sysv_rbt_tile";
   const size_t img = (size_t)B->lmt * B->lnt * B->bsizi * sizeof(double);
+  // the residual / correction (B's tile image), the residual's per-block partial sums, colmax
   int rc = rb.ensure_bytes(1, img, what);
   if (!rc) rc = rb.ensure_bytes(2, sym_resid_part_bytes(ga, nrhs), what);
-  if (!rc) rc = rb.ensure_bytes(3, (size_t)(2 * nrhs + 2) * sizeof(unsigned long long), what);
+  if (!rc) rc = rb.ensure_bytes(3, colmax_bytes(nrhs), what);
   if (rc) return rc;
   double *R = rb.as<double>(1), *part = rb.as<double>(2);
   unsigned long long *colmax = rb.as<unsigned long long>(3);
   std::vector<unsigned long long> hmax(2 * nrhs);
-  chol_desc Rd = *B;  // the residual / correction: B's geometry over the scratch
-  Rd.mat = R;
-  Rd.user_mat = nullptr;
-  Rd.owns = false;
-  Rd.version = 0;
-  Rd.d_list = nullptr;
+  chol_desc Rd = scratch_view(B, R);
   EventTimer tt, tp;
   if ((rc = tt.start())) return rc;
   // anrm (counted with the residual passes: the same kernel), AF <- the triangle of A
   if ((rc = tp.start())) return rc;
-  HIPCHECK(hipMemsetAsync(colmax, 0, (2 * nrhs + 2) * sizeof(unsigned long long), s));
+  HIPCHECK(hipMemsetAsync(colmax, 0, colmax_bytes(nrhs), s));
   HIPCHECK(hipMemsetAsync(R, 0, img, s));  // (the solve runs on whole tiles: the padding must be finite)
   launch_sym_inf_norm(s, ga, up, (const double *)A->mat, part, colmax);
   launch_lacpy<double>(s, ga, up ? 2 : 1, (const double *)A->mat, (double *)AF->mat);
@@ -1520,9 +1464,7 @@ int sysv_rbt_impl(int uplo, chol_desc *A, chol_desc *AF, chol_desc *W, int depth
   unsigned long long anrm_bits = 0;
   HIPCHECK(hipMemcpyAsync(&anrm_bits, colmax, sizeof anrm_bits, hipMemcpyDeviceToHost, s));
   if ((rc = tp.stop(&st[RB_RESID]))) return rc;
-  double anrm;
-  memcpy(&anrm, &anrm_bits, sizeof anrm);
-  const double cte = anrm * std::ldexp(1.0, -53) * std::sqrt((double)A->lm);
+  const RefineTol tol(anrm_bits, A->lm);
   auto finish = [&](int it, int ret) {
     *iter = it;
     const int r = tt.stop(&st[RB_TOTAL]);
@@ -1540,21 +1482,13 @@ int sysv_rbt_impl(int uplo, chol_desc *A, chol_desc *AF, chol_desc *W, int depth
   for (int it = 0;; ++it) {
     // R = B - A X from the stored triangle of the untouched A; the column maxima of R and X
     if ((rc = tp.start())) return rc;
-    HIPCHECK(hipMemsetAsync(colmax, 0, (2 * nrhs + 2) * sizeof(unsigned long long), s));
+    HIPCHECK(hipMemsetAsync(colmax, 0, colmax_bytes(nrhs), s));
     launch_sym_resid_f64(s, ga, up, (const double *)A->mat, gx, (const double *)X->mat, (const double *)B->mat, part, R,
                          colmax);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpyAsync(hmax.data(), colmax, 2 * nrhs * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     if ((rc = tp.stop(&st[RB_RESID]))) return rc;
-    bool done = true;
-    for (int j = 0; j < nrhs; ++j) {
-      double rn, xn;
-      memcpy(&rn, &hmax[j], sizeof rn);
-      memcpy(&xn, &hmax[nrhs + j], sizeof xn);
-      if (berr) berr[j] = rn == 0 ? 0.0 : rn / (anrm * xn);
-      if (!(rn <= xn * cte)) done = false;  // (a NaN residual does not converge)
-    }
-    if (done) return finish(it, 0);
+    if (tol.converged(hmax.data(), nrhs, berr)) return finish(it, 0);
     if (it == RBT_ITMAX) return finish(-31, A->lm + 1);
     rc = sytrs_rbt_impl<double>(up, AF, W, depth, &Rd, st, /*diag_checked=*/true);
     if (rc) return rc;
@@ -1567,11 +1501,7 @@ int sysv_rbt_impl(int uplo, chol_desc *A, chol_desc *AF, chol_desc *W, int depth
 // the argument rules the butterfly routines share: A square, device-resident, single process, stored tile edge a
 // multiple of 128; depth 1 or 2; the order a multiple of 2^depth; W n x depth or wider with A's dtype and row tiling
 int rbt_args(const char *what, int uplo, chol_desc *A, int apos, chol_desc *W, int wpos, int depth, int dpos) {
-  char buf[160];
-  auto bad = [&](int code, const char *why) {
-    snprintf(buf, sizeof buf, "%s: %s", what, why);
-    return fail(code, buf);
-  };
+  auto bad = [&](int code, const char *why) { return failf(code, "%s: %s", what, why); };
   if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return bad(-1, "uplo");
   if (!A) return bad(-apos, "NULL A");
   int rc = inverse_check(what, A, apos);
@@ -1580,8 +1510,7 @@ int rbt_args(const char *what, int uplo, chol_desc *A, int apos, chol_desc *W, i
   if (!W) return bad(-wpos, "NULL W");
   if (W->p * W->q != 1 || !W->on_device) return bad(CHOL_ERR_NOT_SUPPORTED, "W must be a device-resident single-process descriptor");
   if (depth != 1 && depth != 2) return bad(-dpos, "depth must be 1 or 2");
-  if (W->dtype != A->dtype || W->mb != A->mb || W->nb != A->nb || W->mbi != A->mbi || W->lm != A->lm || W->ln < depth ||
-      W == A || W->mat == A->mat)
+  if (!same_rows(A, W) || W->nb != A->nb || W->ln < depth || W == A || W->mat == A->mat)
     return bad(-wpos, "W must be an n x depth descriptor of its own with A's order, tile size and type");
   if (A->lm % (1 << depth))
     return bad(CHOL_ERR_NOT_SUPPORTED, "the order must be a multiple of 2^depth (border A with an identity row)");
@@ -1613,12 +1542,10 @@ int chol_potrs_tile(int uplo, chol_desc_t *A, chol_desc_t *B) {
   rc = resident_whole("potrs_tile", B);
   if (rc) return rc;
   if (A->mt != A->nt || A->lm != A->ln) return fail(-2, "potrs_tile: A is not square");
-  if (B->lm != A->lm || B->mb != A->mb || B->mbi != A->mbi || B->dtype != A->dtype)
-    return fail(-3, "potrs_tile: B must have A's order, tile size and type");
+  if (!same_rows(A, B)) return fail(-3, "potrs_tile: B must have A's order, tile size and type");
   if (A->mbi % 64) return fail(CHOL_ERR_NOT_SUPPORTED, "potrs_tile: stored tile edge must be a multiple of 64");
   CHECK_WINV(A, "potrs_tile");
   std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
-  // ChamUpper: the Lower solve on the transposed storage (as chol_potrf_tile does around the Lower factorisation)
   const int up = uplo == CHOL_UPPER;
   rc = A->dtype == CHOL_REAL_DOUBLE ? potrs_uplo<double>(up, A, B) : potrs_uplo<float>(up, A, B);
   if (up) HIPCHECK(hipStreamSynchronize(main_stream()));
@@ -1643,7 +1570,7 @@ int chol_dsposv_tile(int uplo, chol_desc_t *A, chol_desc_t *B, chol_desc_t *X, i
   if (A->mt != A->nt || A->lm != A->ln) return fail(-2, "dsposv_tile: A is not square");
   if (!B) return fail(-3, "dsposv_tile: B is NULL");
   if ((rc = resident_whole("dsposv_tile", B))) return rc;
-  if (B->dtype != CHOL_REAL_DOUBLE || B->lm != A->lm || B->mb != A->mb || B->mbi != A->mbi || B->mat == A->mat)
+  if (!same_rows(A, B) || B->mat == A->mat)
     return fail(-3, "dsposv_tile: B must be fp64 with A's order and tile size");
   if (!X) return fail(-4, "dsposv_tile: X is NULL");
   if ((rc = resident_whole("dsposv_tile", X))) return rc;
@@ -1667,11 +1594,7 @@ int chol_dsposv_tile(int uplo, chol_desc_t *A, chol_desc_t *B, chol_desc_t *X, i
   });
 }
 
-int chol_last_dsposv_stats(double *out8) {
-  if (!out8) return fail(-1, "last_dsposv_stats: NULL");
-  std::copy(mx_stats, mx_stats + 8, out8);
-  return 0;
-}
+int chol_last_dsposv_stats(double *out8) { return mx_stats.read("dsposv", out8); }
 
 int chol_trtri_tile(int uplo, int diag, chol_desc_t *A) {
   return with_views({{A, true}}, [&]() -> int {
@@ -1745,13 +1668,7 @@ int chol_pocon_tile(int uplo, chol_desc_t *A, double anorm, double *rcond) {
   });
 }
 
-int chol_last_pocon_stats(double *out4) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "last_pocon_stats before chol_init");
-  if (!out4) return fail(-1, "last_pocon_stats: NULL");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
-  for (int i = 0; i < 4; ++i) out4[i] = cn_stats[i];
-  return 0;
-}
+int chol_last_pocon_stats(double *out4) { return cn_stats.read("pocon", out4, 4); }
 
 int chol_poequ_tile(chol_desc_t *A, chol_desc_t *S, double *scond, double *amax) {
   return with_views({{A, false}, {S, true}}, [&]() -> int {
@@ -1799,18 +1716,18 @@ int chol_porfs_tile(int uplo, chol_desc_t *A, chol_desc_t *AF, chol_desc_t *B, c
   if (!berr) return fail(-7, "porfs_tile: NULL berr");
   std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
   const int up = uplo == CHOL_UPPER;
-  std::fill(rf_stats, rf_stats + 8, 0.0);
+  rf_stats.clear();
   EventTimer tt;
   if ((rc = tt.start())) return rc;
   if (A->dtype == CHOL_REAL_DOUBLE) {
     if (!(rc = stage_factor_diag<double>(AF, up, "porfs_tile")))
-      rc = porfs_impl<double>(up, A, AF, B, X, ferr, berr, rf_stats);
+      rc = porfs_impl<double>(up, A, AF, B, X, ferr, berr, rf_stats.v);
   } else {
     if (!(rc = stage_factor_diag<float>(AF, up, "porfs_tile")))
-      rc = porfs_impl<float>(up, A, AF, B, X, ferr, berr, rf_stats);
+      rc = porfs_impl<float>(up, A, AF, B, X, ferr, berr, rf_stats.v);
   }
   if (rc) return rc;
-  return tt.stop(&rf_stats[0]);
+  return tt.stop(&rf_stats.v[0]);
   });
 }
 
@@ -1857,13 +1774,7 @@ int chol_bench_refine(int uplo, chol_desc_t *A, chol_desc_t *AF, chol_desc_t *X,
   });
 }
 
-int chol_last_posvx_stats(double *out8) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "last_posvx_stats before chol_init");
-  if (!out8) return fail(-1, "last_posvx_stats: NULL");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
-  for (int i = 0; i < 8; ++i) out8[i] = rf_stats[i];
-  return 0;
-}
+int chol_last_posvx_stats(double *out8) { return rf_stats.read("posvx", out8); }
 
 int chol_pstrf_tile(int uplo, chol_desc_t *A, int *piv, int *rank, double tol) {
   return with_views({{A, true}}, [&]() -> int {
@@ -1881,13 +1792,7 @@ int chol_pstrf_tile(int uplo, chol_desc_t *A, int *piv, int *rank, double tol) {
   });
 }
 
-int chol_last_pstrf_stats(double *out8) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "last_pstrf_stats before chol_init");
-  if (!out8) return fail(-1, "last_pstrf_stats: NULL");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
-  for (int i = 0; i < 8; ++i) out8[i] = ps_stats[i];
-  return 0;
-}
+int chol_last_pstrf_stats(double *out8) { return ps_stats.read("pstrf", out8); }
 
 int chol_sygst_tile(int itype, int uplo, chol_desc_t *A, chol_desc_t *B) {
   if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "sygst_tile before chol_init");
@@ -1909,13 +1814,7 @@ int chol_sygst_tile(int itype, int uplo, chol_desc_t *A, chol_desc_t *B) {
   });
 }
 
-int chol_last_sygst_stats(double *out8) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "last_sygst_stats before chol_init");
-  if (!out8) return fail(-1, "last_sygst_stats: NULL");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
-  for (int i = 0; i < 8; ++i) out8[i] = sg_stats[i];
-  return 0;
-}
+int chol_last_sygst_stats(double *out8) { return sg_stats.read("sygst", out8); }
 
 int chol_sytrf_nopiv_tile(int uplo, chol_desc_t *A) {
   if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "sytrf_nopiv_tile before chol_init");
@@ -1941,8 +1840,7 @@ int chol_sytrs_nopiv_tile(int uplo, chol_desc_t *A, chol_desc_t *B) {
   if (rc) return rc;
   rc = resident_whole("sytrs_nopiv_tile", B);
   if (rc) return rc;
-  if (B->lm != A->lm || B->mb != A->mb || B->mbi != A->mbi || B->dtype != A->dtype)
-    return fail(-3, "sytrs_nopiv_tile: B must have A's order, tile size and type");
+  if (!same_rows(A, B)) return fail(-3, "sytrs_nopiv_tile: B must have A's order, tile size and type");
   CHECK_WINV(A, "sytrs_nopiv_tile");
   std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
   const int up = uplo == CHOL_UPPER;
@@ -1960,13 +1858,7 @@ int chol_sysv_nopiv_tile(int uplo, chol_desc_t *A, chol_desc_t *B) {
   return chol_sytrs_nopiv_tile(uplo, A, B);
 }
 
-int chol_last_sytrf_stats(double *out8) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "last_sytrf_stats before chol_init");
-  if (!out8) return fail(-1, "last_sytrf_stats: NULL");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
-  for (int i = 0; i < 8; ++i) out8[i] = sy_stats[i];
-  return 0;
-}
+int chol_last_sytrf_stats(double *out8) { return sy_stats.read("sytrf", out8); }
 
 int chol_rbt_apply_tile(int uplo, chol_desc_t *A, chol_desc_t *W, int depth) {
   if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "rbt_apply_tile before chol_init");
@@ -1976,13 +1868,14 @@ int chol_rbt_apply_tile(int uplo, chol_desc_t *A, chol_desc_t *W, int depth) {
   std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
   if (A->lm == 0) return 0;
   forget_winv(A->mat);  // (A is overwritten)
-  const bool up = uplo == CHOL_UPPER;
-  if (up) transpose_storage(A);
-  if (A->dtype == CHOL_REAL_DOUBLE)
-    rbt_transform<double>(A, W, depth);
-  else
-    rbt_transform<float>(A, W, depth);
-  if (up) transpose_storage(A);
+  rc = through_lower(uplo == CHOL_UPPER, {A}, [&] {
+    if (A->dtype == CHOL_REAL_DOUBLE)
+      rbt_transform<double>(A, W, depth);
+    else
+      rbt_transform<float>(A, W, depth);
+    return 0;
+  });
+  if (rc) return rc;
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipStreamSynchronize(main_stream()));
   return 0;
@@ -1995,15 +1888,15 @@ int chol_sytrf_rbt_tile(int uplo, chol_desc_t *A, chol_desc_t *W, int depth, uns
   int rc = rbt_args("sytrf_rbt_tile", uplo, A, 2, W, 3, depth, 4);
   if (rc) return rc;
   std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
-  std::fill(rb_stats, rb_stats + 8, 0.0);
+  rb_stats.clear();
   if (A->lm == 0) return 0;
   EventTimer tt;
   if ((rc = tt.start())) return rc;
   int info = 0;
-  rc = A->dtype == CHOL_REAL_DOUBLE ? sytrf_rbt_impl<double>(uplo, A, W, depth, seed, &info, rb_stats)
-                                    : sytrf_rbt_impl<float>(uplo, A, W, depth, seed, &info, rb_stats);
+  rc = A->dtype == CHOL_REAL_DOUBLE ? sytrf_rbt_impl<double>(uplo, A, W, depth, seed, &info, rb_stats.v)
+                                    : sytrf_rbt_impl<float>(uplo, A, W, depth, seed, &info, rb_stats.v);
   if (rc) return rc;
-  if ((rc = tt.stop(&rb_stats[RB_TOTAL]))) return rc;
+  if ((rc = tt.stop(&rb_stats.v[RB_TOTAL]))) return rc;
   return info;
   });
 }
@@ -2015,19 +1908,18 @@ int chol_sytrs_rbt_tile(int uplo, chol_desc_t *A, chol_desc_t *W, int depth, cho
   if (rc) return rc;
   if (!B) return fail(-5, "sytrs_rbt_tile: NULL B");
   if ((rc = resident_whole("sytrs_rbt_tile", B))) return rc;
-  if (B->lm != A->lm || B->mb != A->mb || B->mbi != A->mbi || B->dtype != A->dtype || B == A || B == W ||
-      B->mat == A->mat || B->mat == W->mat)
+  if (!same_rows(A, B) || B == A || B == W || B->mat == A->mat || B->mat == W->mat)
     return fail(-5, "sytrs_rbt_tile: B must be a descriptor of its own with A's order, tile size and type");
   std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
-  std::fill(rb_stats, rb_stats + 8, 0.0);
+  rb_stats.clear();
   if (A->lm == 0) return 0;
   EventTimer tt;
   if ((rc = tt.start())) return rc;
   const int up = uplo == CHOL_UPPER;
-  rc = A->dtype == CHOL_REAL_DOUBLE ? sytrs_rbt_impl<double>(up, A, W, depth, B, rb_stats)
-                                    : sytrs_rbt_impl<float>(up, A, W, depth, B, rb_stats);
+  rc = A->dtype == CHOL_REAL_DOUBLE ? sytrs_rbt_impl<double>(up, A, W, depth, B, rb_stats.v)
+                                    : sytrs_rbt_impl<float>(up, A, W, depth, B, rb_stats.v);
   if (rc) return rc;
-  return tt.stop(&rb_stats[RB_TOTAL]);
+  return tt.stop(&rb_stats.v[RB_TOTAL]);
   });
 }
 
@@ -2048,8 +1940,7 @@ int chol_sysv_rbt_tile(int uplo, chol_desc_t *A, chol_desc_t *AF, chol_desc_t *W
   if (W->mat == A->mat) return fail(-4, "sysv_rbt_tile: W aliases A");
   if (!B) return fail(-7, "sysv_rbt_tile: NULL B");
   if ((rc = resident_whole(what, B))) return rc;
-  if (B->lm != A->lm || B->mb != A->mb || B->mbi != A->mbi || B->dtype != A->dtype || B->mat == A->mat ||
-      B->mat == AF->mat || B->mat == W->mat)
+  if (!same_rows(A, B) || B->mat == A->mat || B->mat == AF->mat || B->mat == W->mat)
     return fail(-7, "sysv_rbt_tile: B must be a descriptor of its own with A's order, tile size and type");
   if (!X) return fail(-8, "sysv_rbt_tile: NULL X");
   if ((rc = resident_whole(what, X))) return rc;
@@ -2059,17 +1950,11 @@ int chol_sysv_rbt_tile(int uplo, chol_desc_t *A, chol_desc_t *AF, chol_desc_t *W
   if (A->dtype != CHOL_REAL_DOUBLE)
     return fail(CHOL_ERR_NOT_SUPPORTED, "sysv_rbt_tile: fp32 (the residual pass is fp64: use sytrf_rbt / sytrs_rbt)");
   std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
-  std::fill(rb_stats, rb_stats + 8, 0.0);
+  rb_stats.clear();
   *iter = 0;
   if (A->lm == 0 || B->ln == 0) return 0;
   return sysv_rbt_impl(uplo, A, AF, W, depth, seed, B, X, iter, berr);
   });
 }
 
-int chol_last_rbt_stats(double *out8) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "last_rbt_stats before chol_init");
-  if (!out8) return fail(-1, "last_rbt_stats: NULL");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
-  for (int i = 0; i < 8; ++i) out8[i] = rb_stats[i];
-  return 0;
-}
+int chol_last_rbt_stats(double *out8) { return rb_stats.read("rbt", out8); }

@@ -1,5 +1,5 @@
-"""CPU-side checks of the mixed-precision solve's boundary (chol_dsposv_tile): the Python wrapper exists and the
-entry point refuses to run before chol_init.  The numerics are in test_gpu_dsposv.py."""
+"""CPU-side checks of the mixed-precision solve's boundary (chol_dsposv_tile / chol_last_dsposv_stats): the Python
+wrapper exists and both entry points refuse to run before chol_init.  The numerics are in test_gpu_dsposv.py."""
 import ctypes as C
 
 from dense_linear_app_amd import _lib, chameleon as ch
@@ -17,3 +17,9 @@ def test_dsposv_before_init_is_refused():
     assert L.chol_dsposv_tile(ch.ChamLower, None, None, None, C.byref(it)) == -101  # CHOL_ERR_NOT_INITIALIZED
     assert b"before chol_init" in L.chol_last_error()
     assert it.value == 7
+
+
+def test_last_dsposv_stats_before_init_is_refused():
+    L = _lib.lib()
+    assert L.chol_last_dsposv_stats(None) == -101  # CHOL_ERR_NOT_INITIALIZED
+    assert b"before chol_init" in L.chol_last_error()
