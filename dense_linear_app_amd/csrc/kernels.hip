@@ -4,10 +4,16 @@
 // (v6_test.c:46, 72-87).  Written for 64-wide wavefronts and the fp64 / fp32
 // 16x16x4 MFMA; no other target is supported.
 //
-// Common structure ("NT core"): one 256-thread workgroup (4 waves, 2 x 2) owns a
-// 128 x 128 block of C and computes  acc = A(128 x K) * B(128 x K)^T  with both
-// operands column-major (rows contiguous), staged through LDS in K-slices of 16.
-// Production form (nt_kloop_paired + nt_epilogue_paired_impl):
+// Common structure ("NT core"): one workgroup owns a 128 x 128 block of C and computes
+// acc = A(128 x K) * B(128 x K)^T  with both operands column-major (rows contiguous), staged
+// through LDS in K-slices.  Three cores, by what they serve today:
+//   - eight waves (2 x 4), nt_kloop_w8 (fp64, four-stage LDS ring) / nt_kloop_w8f (fp32, slices of 32) with
+//     w8_epilogue / w8f_epilogue, bound as CoreW8 / CoreW8F: every update that carries the flops -- the trailing
+//     update, sygst's SYR2K, sytrf's two-panel update and the task path's pointer-task update;
+//   - four waves (2 x 2), nt_kloop_paired + nt_epilogue_paired_impl, K-slices of 16: the panel TRSM's solve and
+//     update steps and the tile GEMM (k_panel_solve, k_panel_update, k_gemm_nt_tile);
+//   - nt_kloop (register-staged): the residual kernel only.
+// The four-wave form, which the eight-wave ones were derived from:
 //   - global -> LDS by LDS-DMA (global_load_lds, 16 B per lane): one wave instruction moves a
 //     whole 128-row column of a slice into the [k][128] LDS image, no staging registers;
 //   - LDS -> MFMA fragments by ds_read_b128 with "paired" rows: lane i of a 16-lane group owns
@@ -18,9 +24,9 @@
 //     contiguous per 16 lanes (col-major C);
 //   - double-buffered LDS (64 KiB per workgroup), one barrier per K-slice; 2 workgroups per CU
 //     (<= 232 VGPR) hide the C epilogue behind the other workgroup's MFMA stream.
-// nt_kloop (register-staged, row stride 144) serves the residual kernel only: it carries the operand
-// masks that kernel needs (tril of the diagonal tiles).
+// nt_kloop (row stride 144) carries the operand masks the residual kernel needs (tril of the diagonal tiles).
 #include "cholmi_internal.h"
+#include "mfma_traits.h"
 
 #include <type_traits>
 
@@ -33,34 +39,6 @@
 #endif
 
 namespace cholmi {
-
-typedef double d4_t __attribute__((ext_vector_type(4)));
-typedef double d2_t __attribute__((ext_vector_type(2)));
-typedef float f4_t __attribute__((ext_vector_type(4)));
-
-template <typename T>
-struct Tr;
-template <>
-struct Tr<double> {
-  using acc_t = d4_t;
-  using vec_t = d2_t;
-  static constexpr int EPV = 2;
-  static __device__ __forceinline__ acc_t mfma(double a, double b, acc_t c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  // row of accumulator register `reg` held by `lane` (f64 16x16x4 C/D map)
-  static __device__ __forceinline__ int drow(int lane, int reg) { return (lane >> 4) + 4 * reg; }
-};
-template <>
-struct Tr<float> {
-  using acc_t = f4_t;
-  using vec_t = f4_t;
-  static constexpr int EPV = 4;
-  static __device__ __forceinline__ acc_t mfma(float a, float b, acc_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int drow(int lane, int reg) { return 4 * (lane >> 4) + reg; }
-};
 
 constexpr int BK = 16;
 constexpr int LROW = MACRO + 16;
@@ -80,19 +58,6 @@ struct alignas(16) Smem {
   T a[2][BK][LROW];
   T b[2][BK][LROW];
 };
-
-template <typename T>
-using Acc = typename Tr<T>::acc_t[4][4];
-
-template <typename T>
-__device__ __forceinline__ void acc_zero(Acc<T> &acc) {
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[a][b][r] = T(0);
-}
 
 // acc += A(128 x K) * B(128 x K)^T.  MASKA / MASKB: treat the operand as the lower
 // triangle of a square tile whose row `amask + r` only has columns k <= amask + r
@@ -486,8 +451,8 @@ struct BlockMap {
   int mi, mj;
 };
 __device__ __forceinline__ bool map_update_block(const int2 *__restrict__ list, int na, int offb, int nb,
-                                                 int nbm, int blocks_a, int unit, BlockMap &out, int b = -1) {
-  if (b < 0) b = blockIdx.x;
+                                                 int nbm, int blocks_a, int unit, BlockMap &out) {
+  int b = blockIdx.x;
   if (na == 0 && nb == 1) {
     // one diagonal tile on its own (the SYRK that releases the next POTRF): nothing to share
     // through an L2, so its blocks go round-robin over all XCDs, one workgroup per CU
@@ -760,42 +725,6 @@ __device__ __forceinline__ void w8_epilogue(const T *Cin, T *Cout, int ld,
   }
 }
 
-template <typename T, int MODE>
-__device__ __forceinline__ void trail_update_w8_block(const LocalMat &C, const int2 *__restrict__ list, int na, int offb,
-                                                      int nb, int blocks_a, const PanelRef &pan, int nbm, int unit,
-                                                      const int *ytab, const PanelRef &pan2, int npan, SmemR<T> &sm, int b) {
-  using vec_t = typename Tr<T>::vec_t;
-  BlockMap bm;
-  if (!map_update_block(list, na, offb, nb, nbm, blocks_a, unit, bm, b)) return;
-  const int2 ij = bm.ij;
-  const int mi = bm.mi, mj = bm.mj;
-  const bool lower = (ij.x == ij.y) && mi == mj;
-  T *Cp = reinterpret_cast<T *>(C.base) + ((long)(ij.x / C.P) + (long)(ij.y / C.Q) * C.lmt) * C.bsiz +
-          mi * MACRO + (long)mj * MACRO * C.mb;
-  typename Tr<T>::acc_t acc[4][2];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[a][b][r] = T(0);
-  const int *yslot = ytab ? ytab + cu_slot() : nullptr;
-  nt_kloop_w8<T, MODE>(panel_tile<T>(pan, ij.x, C.bsiz) + mi * MACRO, C.mb, panel_tile<T>(pan, ij.y, C.bsiz) + mj * MACRO,
-                 C.mb, C.mb, acc, sm, yslot);
-  if (npan > 1)
-    nt_kloop_w8<T, MODE>(panel_tile<T>(pan2, ij.x, C.bsiz) + mi * MACRO, C.mb,
-                   panel_tile<T>(pan2, ij.y, C.bsiz) + mj * MACRO, C.mb, C.mb, acc, sm, yslot);
-  w8_epilogue<T, false>(Cp, Cp, C.mb, acc, lower);
-}
-
-template <typename T, int MODE>
-__global__ __launch_bounds__(512, 4) void k_trail_update_w8(LocalMat C, const int2 *__restrict__ list, int na,
-                                                             int offb, int nb, int blocks_a, PanelRef pan, int nbm,
-                                                             int unit, const int *ytab, PanelRef pan2, int npan) {
-  __shared__ SmemR<T> sm;
-  trail_update_w8_block<T, MODE>(C, list, na, offb, nb, blocks_a, pan, nbm, unit, ytab, pan2, npan, sm, (int)blockIdx.x);
-}
-
 // ------------------------------------------------------------------------------
 // fp32 trailing update on eight waves with K-slices of 32.  The fp32 16x16x4 MFMA issues every 32
 // cycles (twice the fp64 rate), so with 16-deep slices a wave meets a barrier after 2048 cycles of
@@ -905,144 +834,131 @@ __device__ __forceinline__ void w8f_epilogue(const float *Cin, float *Cout, int 
     }
 }
 
-__global__ __launch_bounds__(512, 4) void k_trail_update_w8f(LocalMat C, const int2 *__restrict__ list, int na,
-                                                              int offb, int nb, int blocks_a, PanelRef pan, int nbm,
-                                                              int unit, const int *ytab, PanelRef pan2, int npan) {
-  __shared__ SmemF sm;
+// ------------------------------------------------------------------------------
+// The two eight-wave cores under one interface, for the two block bodies below: the LDS image and the accumulator
+// (4 x 2 MFMA tiles per wave) of a workgroup,  kloop (acc += A B^T over K, the guest slot polled if there is one) and
+// epilogue (Cout = Cin - acc, OOP: out of place).  CoreW8: fp64, the four-stage ring (nt_kloop_w8, w8_epilogue);
+// CoreW8F: fp32, double-buffered slices of 32 (nt_kloop_w8f, w8f_epilogue).
+// The block bodies zero the accumulator themselves, in the function that declares it, not through a function of the
+// core: a callee is optimised before it is inlined, the accumulator then arrives as eight whole-vector stores, and the
+// compiler packs the fp32 one into a single 32-wide vector (other registers and schedule for the whole K-loop).
+// ------------------------------------------------------------------------------
+template <typename T_, int MODE>
+struct CoreW8 {
+  using T = T_;
+  using Smem = SmemR<T>;
+  using Acc = typename Tr<T>::acc_t[4][2];
+  static __device__ __forceinline__ void kloop(const T *A, int lda, const T *B, int ldb, int K, Acc &acc, Smem &sm,
+                                               const int *yslot) {
+    nt_kloop_w8<T, MODE>(A, lda, B, ldb, K, acc, sm, yslot);
+  }
+  template <bool OOP>
+  static __device__ __forceinline__ void epilogue(const T *Cin, T *Cout, int ld, Acc &acc, bool lower) {
+    w8_epilogue<T, OOP>(Cin, Cout, ld, acc, lower);
+  }
+};
+struct CoreW8F {
+  using T = float;
+  using Smem = SmemF;
+  using Acc = f4_t[4][2];
+  static __device__ __forceinline__ void kloop(const float *A, int lda, const float *B, int ldb, int K, Acc &acc,
+                                               Smem &sm, const int *yslot) {
+    nt_kloop_w8f(A, lda, B, ldb, K, acc, sm, yslot);
+  }
+  template <bool OOP>
+  static __device__ __forceinline__ void epilogue(const float *Cin, float *Cout, int ld, Acc &acc, bool lower) {
+    w8f_epilogue<OOP>(Cin, Cout, ld, acc, lower);
+  }
+};
+
+// One block of a work-list launch (blockIdx -> block: map_update_block), in place:
+//   C(i,j) block (mi, mj) -= P1(i) Q1(j)^T [+ P2(i) Q2(j)^T if npairs > 1],  one K-loop per pair into one accumulator.
+// ytab: the guest table whose entry for this CU the K-loops poll, or null.  Diagonal blocks of diagonal tiles: lower
+// triangle only.  Every list kernel is its LDS image and one call of this.
+template <typename Core>
+__device__ __forceinline__ void update_list_block(const LocalMat &C, const int2 *list, int na, int offb, int nb,
+                                                  int blocks_a, int nbm, int unit, const int *ytab,
+                                                  typename Core::Smem &sm, const PanelRef &P1, const PanelRef &Q1,
+                                                  const PanelRef &P2, const PanelRef &Q2, int npairs) {
+  using T = typename Core::T;
   BlockMap bm;
   if (!map_update_block(list, na, offb, nb, nbm, blocks_a, unit, bm)) return;
   const int2 ij = bm.ij;
   const int mi = bm.mi, mj = bm.mj;
   const bool lower = (ij.x == ij.y) && mi == mj;
-  float *Cp = reinterpret_cast<float *>(C.base) + ((long)(ij.x / C.P) + (long)(ij.y / C.Q) * C.lmt) * C.bsiz +
-              mi * MACRO + (long)mj * MACRO * C.mb;
-  f4_t acc[4][2];
+  T *Cp = reinterpret_cast<T *>(C.base) + ((long)(ij.x / C.P) + (long)(ij.y / C.Q) * C.lmt) * C.bsiz + mi * MACRO +
+          (long)mj * MACRO * C.mb;
+  typename Core::Acc acc;
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
     for (int b = 0; b < 2; ++b)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) acc[a][b][r] = 0.f;
+      for (int r = 0; r < 4; ++r) acc[a][b][r] = T(0);
   const int *yslot = ytab ? ytab + cu_slot() : nullptr;
-  nt_kloop_w8f(panel_tile<float>(pan, ij.x, C.bsiz) + mi * MACRO, C.mb,
-               panel_tile<float>(pan, ij.y, C.bsiz) + mj * MACRO, C.mb, C.mb, acc, sm, yslot);
-  if (npan > 1)
-    nt_kloop_w8f(panel_tile<float>(pan2, ij.x, C.bsiz) + mi * MACRO, C.mb,
-                 panel_tile<float>(pan2, ij.y, C.bsiz) + mj * MACRO, C.mb, C.mb, acc, sm, yslot);
-  w8f_epilogue<false>(Cp, Cp, C.mb, acc, lower);
+  Core::kloop(panel_tile<T>(P1, ij.x, C.bsiz) + mi * MACRO, C.mb, panel_tile<T>(Q1, ij.y, C.bsiz) + mj * MACRO, C.mb, C.mb,
+              acc, sm, yslot);
+  if (npairs > 1)
+    Core::kloop(panel_tile<T>(P2, ij.x, C.bsiz) + mi * MACRO, C.mb, panel_tile<T>(Q2, ij.y, C.bsiz) + mj * MACRO, C.mb,
+                C.mb, acc, sm, yslot);
+  Core::template epilogue<false>(Cp, Cp, C.mb, acc, lower);
+}
+
+// The trailing update (see above map_update_block): P = Q = pan, then pan2 in a paired launch; polls the guest slot.
+template <typename T, int MODE>
+__global__ __launch_bounds__(512, 4) void k_trail_update_w8(LocalMat C, const int2 *__restrict__ list, int na,
+                                                             int offb, int nb, int blocks_a, PanelRef pan, int nbm,
+                                                             int unit, const int *ytab, PanelRef pan2, int npan) {
+  __shared__ SmemR<T> sm;
+  update_list_block<CoreW8<T, MODE>>(C, list, na, offb, nb, blocks_a, nbm, unit, ytab, sm, pan, pan, pan2, pan2, npan);
+}
+__global__ __launch_bounds__(512, 4) void k_trail_update_w8f(LocalMat C, const int2 *__restrict__ list, int na,
+                                                              int offb, int nb, int blocks_a, PanelRef pan, int nbm,
+                                                              int unit, const int *ytab, PanelRef pan2, int npan) {
+  __shared__ SmemF sm;
+  update_list_block<CoreW8F>(C, list, na, offb, nb, blocks_a, nbm, unit, ytab, sm, pan, pan, pan2, pan2, npan);
 }
 
 // ------------------------------------------------------------------------------
 // The symmetric rank-2k update of sygst (LAPACK DSYR2K, Lower, No transpose) on the trailing update's cores and work
 // list:  C(i,j) -= P(i) Q(j)^T + Q(i) P(j)^T  for the (i,j) tiles of the list, P = `pan` (sygst: A's panel), Q = `qan`
 // (the factor's panel).  The same block map (XCD-aware units, the diagonal tiles' lower blocks last) and epilogue as
-// the update; two K-loops into one accumulator, (P_i, Q_j) then (Q_i, P_j).  Kernels of their own: the update's
-// instantiations are not touched.
+// the update; two K-loops into one accumulator, (P_i, Q_j) then (Q_i, P_j).  No guest slot is polled.
+// (fp32: the first loop's last slice is read by every wave before the second loop's first DMA: nt_kloop_w8f ends on a
+// barrier.)
 // ------------------------------------------------------------------------------
 template <typename T, int MODE>
 __global__ __launch_bounds__(512, 4) void k_syr2k_w8(LocalMat C, const int2 *__restrict__ list, int na, int offb,
                                                      int nb, int blocks_a, PanelRef pan, PanelRef qan, int nbm,
                                                      int unit) {
   __shared__ SmemR<T> sm;
-  BlockMap bm;
-  if (!map_update_block(list, na, offb, nb, nbm, blocks_a, unit, bm)) return;
-  const int2 ij = bm.ij;
-  const int mi = bm.mi, mj = bm.mj;
-  const bool lower = (ij.x == ij.y) && mi == mj;
-  T *Cp = reinterpret_cast<T *>(C.base) + ((long)(ij.x / C.P) + (long)(ij.y / C.Q) * C.lmt) * C.bsiz + mi * MACRO +
-          (long)mj * MACRO * C.mb;
-  typename Tr<T>::acc_t acc[4][2];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[a][b][r] = T(0);
-  nt_kloop_w8<T, MODE>(panel_tile<T>(pan, ij.x, C.bsiz) + mi * MACRO, C.mb, panel_tile<T>(qan, ij.y, C.bsiz) + mj * MACRO,
-                       C.mb, C.mb, acc, sm, nullptr);
-  nt_kloop_w8<T, MODE>(panel_tile<T>(qan, ij.x, C.bsiz) + mi * MACRO, C.mb, panel_tile<T>(pan, ij.y, C.bsiz) + mj * MACRO,
-                       C.mb, C.mb, acc, sm, nullptr);
-  w8_epilogue<T, false>(Cp, Cp, C.mb, acc, lower);
+  update_list_block<CoreW8<T, MODE>>(C, list, na, offb, nb, blocks_a, nbm, unit, nullptr, sm, pan, qan, qan, pan, 2);
 }
-
 __global__ __launch_bounds__(512, 4) void k_syr2k_w8f(LocalMat C, const int2 *__restrict__ list, int na, int offb,
                                                       int nb, int blocks_a, PanelRef pan, PanelRef qan, int nbm,
                                                       int unit) {
   __shared__ SmemF sm;
-  BlockMap bm;
-  if (!map_update_block(list, na, offb, nb, nbm, blocks_a, unit, bm)) return;
-  const int2 ij = bm.ij;
-  const int mi = bm.mi, mj = bm.mj;
-  const bool lower = (ij.x == ij.y) && mi == mj;
-  float *Cp = reinterpret_cast<float *>(C.base) + ((long)(ij.x / C.P) + (long)(ij.y / C.Q) * C.lmt) * C.bsiz +
-              mi * MACRO + (long)mj * MACRO * C.mb;
-  f4_t acc[4][2];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[a][b][r] = 0.f;
-  nt_kloop_w8f(panel_tile<float>(pan, ij.x, C.bsiz) + mi * MACRO, C.mb,
-               panel_tile<float>(qan, ij.y, C.bsiz) + mj * MACRO, C.mb, C.mb, acc, sm, nullptr);
-  // (the first loop's last slice is read by every wave before this loop's first DMA: nt_kloop_w8f ends on a barrier)
-  nt_kloop_w8f(panel_tile<float>(qan, ij.x, C.bsiz) + mi * MACRO, C.mb,
-               panel_tile<float>(pan, ij.y, C.bsiz) + mj * MACRO, C.mb, C.mb, acc, sm, nullptr);
-  w8f_epilogue<false>(Cp, Cp, C.mb, acc, lower);
+  update_list_block<CoreW8F>(C, list, na, offb, nb, blocks_a, nbm, unit, nullptr, sm, pan, qan, qan, pan, 2);
 }
 
 // ------------------------------------------------------------------------------
 // The two-panel update of sytrf_nopiv (A = L D L^T without pivoting), one pass:  C(i,j) -= P(i) Q(j)^T  for the (i,j)
 // tiles of the list, P = `pan` (the unscaled panel W = L D, a scratch tile column addressed through PanelRef::first),
-// Q = `qan` (L, the matrix's own column).  k_syr2k_w8 with its first K-loop only: W L^T = L D L^T is symmetric, so the
-// lower blocks of the diagonal tiles are right as they stand.  Kernels of their own: the update's and the SYR2K's
-// instantiations are not touched.
+// Q = `qan` (L, the matrix's own column).  One K-loop: W L^T = L D L^T is symmetric, so the lower blocks of the
+// diagonal tiles are right as they stand.  No guest slot is polled.
 // ------------------------------------------------------------------------------
 template <typename T, int MODE>
 __global__ __launch_bounds__(512, 4) void k_ldl_update_w8(LocalMat C, const int2 *__restrict__ list, int na, int offb,
                                                           int nb, int blocks_a, PanelRef pan, PanelRef qan, int nbm,
                                                           int unit) {
   __shared__ SmemR<T> sm;
-  BlockMap bm;
-  if (!map_update_block(list, na, offb, nb, nbm, blocks_a, unit, bm)) return;
-  const int2 ij = bm.ij;
-  const int mi = bm.mi, mj = bm.mj;
-  const bool lower = (ij.x == ij.y) && mi == mj;
-  T *Cp = reinterpret_cast<T *>(C.base) + ((long)(ij.x / C.P) + (long)(ij.y / C.Q) * C.lmt) * C.bsiz + mi * MACRO +
-          (long)mj * MACRO * C.mb;
-  typename Tr<T>::acc_t acc[4][2];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[a][b][r] = T(0);
-  nt_kloop_w8<T, MODE>(panel_tile<T>(pan, ij.x, C.bsiz) + mi * MACRO, C.mb, panel_tile<T>(qan, ij.y, C.bsiz) + mj * MACRO,
-                       C.mb, C.mb, acc, sm, nullptr);
-  w8_epilogue<T, false>(Cp, Cp, C.mb, acc, lower);
+  update_list_block<CoreW8<T, MODE>>(C, list, na, offb, nb, blocks_a, nbm, unit, nullptr, sm, pan, qan, pan, qan, 1);
 }
-
 __global__ __launch_bounds__(512, 4) void k_ldl_update_w8f(LocalMat C, const int2 *__restrict__ list, int na, int offb,
                                                            int nb, int blocks_a, PanelRef pan, PanelRef qan, int nbm,
                                                            int unit) {
   __shared__ SmemF sm;
-  BlockMap bm;
-  if (!map_update_block(list, na, offb, nb, nbm, blocks_a, unit, bm)) return;
-  const int2 ij = bm.ij;
-  const int mi = bm.mi, mj = bm.mj;
-  const bool lower = (ij.x == ij.y) && mi == mj;
-  float *Cp = reinterpret_cast<float *>(C.base) + ((long)(ij.x / C.P) + (long)(ij.y / C.Q) * C.lmt) * C.bsiz +
-              mi * MACRO + (long)mj * MACRO * C.mb;
-  f4_t acc[4][2];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[a][b][r] = 0.f;
-  nt_kloop_w8f(panel_tile<float>(pan, ij.x, C.bsiz) + mi * MACRO, C.mb,
-               panel_tile<float>(qan, ij.y, C.bsiz) + mj * MACRO, C.mb, C.mb, acc, sm, nullptr);
-  w8f_epilogue<false>(Cp, Cp, C.mb, acc, lower);
+  update_list_block<CoreW8F>(C, list, na, offb, nb, blocks_a, nbm, unit, nullptr, sm, pan, qan, pan, qan, 1);
 }
 
 // ------------------------------------------------------------------------------
@@ -1073,11 +989,10 @@ __device__ __forceinline__ void copy_block_512(const T *cin, T *cout, int ld) {
     *reinterpret_cast<uint4 *>(cout + r + (long)c * ld) = *reinterpret_cast<const uint4 *>(cin + r + (long)c * ld);
   }
 }
-template <typename T, int MODE>
-__global__ __launch_bounds__(512, 4) void k_update_ptrs_w8(const T *const *__restrict__ cin, const T *const *__restrict__ ap,
-                                                            const T *const *__restrict__ bp, T *const *__restrict__ cout,
-                                                            int n, int mb, int nbm, int unit, const int *ytab) {
-  __shared__ SmemR<T> sm;
+template <typename Core, typename T = typename Core::T>
+__device__ __forceinline__ void update_ptr_block(const T *const *cin, const T *const *ap, const T *const *bp,
+                                                 T *const *cout, int n, int mb, int nbm, int unit, const int *ytab,
+                                                 typename Core::Smem &sm) {
   int t, mi, mj;
   if (!map_ptr_block(n, nbm, unit, t, mi, mj)) return;
   const T *A = ap[t], *B = bp[t];
@@ -1090,7 +1005,7 @@ __global__ __launch_bounds__(512, 4) void k_update_ptrs_w8(const T *const *__res
     return;
   }
   if (syrk) B = A;
-  typename Tr<T>::acc_t acc[4][2];
+  typename Core::Acc acc;
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -1098,35 +1013,21 @@ __global__ __launch_bounds__(512, 4) void k_update_ptrs_w8(const T *const *__res
 #pragma unroll
       for (int r = 0; r < 4; ++r) acc[a][b][r] = T(0);
   const int *yslot = ytab ? ytab + cu_slot() : nullptr;
-  nt_kloop_w8<T, MODE>(A + mi * MACRO, mb, B + mj * MACRO, mb, mb, acc, sm, yslot);
-  w8_epilogue<T, true>(Ci, Co, mb, acc, syrk && mi == mj);
+  Core::kloop(A + mi * MACRO, mb, B + mj * MACRO, mb, mb, acc, sm, yslot);
+  Core::template epilogue<true>(Ci, Co, mb, acc, syrk && mi == mj);
+}
+template <typename T, int MODE>
+__global__ __launch_bounds__(512, 4) void k_update_ptrs_w8(const T *const *__restrict__ cin, const T *const *__restrict__ ap,
+                                                            const T *const *__restrict__ bp, T *const *__restrict__ cout,
+                                                            int n, int mb, int nbm, int unit, const int *ytab) {
+  __shared__ SmemR<T> sm;
+  update_ptr_block<CoreW8<T, MODE>>(cin, ap, bp, cout, n, mb, nbm, unit, ytab, sm);
 }
 __global__ __launch_bounds__(512, 4) void k_update_ptrs_w8f(const float *const *__restrict__ cin, const float *const *__restrict__ ap,
                                                              const float *const *__restrict__ bp, float *const *__restrict__ cout,
                                                              int n, int mb, int nbm, int unit, const int *ytab) {
   __shared__ SmemF sm;
-  int t, mi, mj;
-  if (!map_ptr_block(n, nbm, unit, t, mi, mj)) return;
-  const float *A = ap[t], *B = bp[t];
-  const bool syrk = B == nullptr;
-  const long off = mi * MACRO + (long)mj * MACRO * mb;
-  const float *Ci = cin[t] + off;
-  float *Co = cout[t] + off;
-  if (syrk && mi < mj) {
-    copy_block_512<float>(Ci, Co, mb);
-    return;
-  }
-  if (syrk) B = A;
-  f4_t acc[4][2];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[a][b][r] = 0.f;
-  const int *yslot = ytab ? ytab + cu_slot() : nullptr;
-  nt_kloop_w8f(A + mi * MACRO, mb, B + mj * MACRO, mb, mb, acc, sm, yslot);
-  w8f_epilogue<true>(Ci, Co, mb, acc, syrk && mi == mj);
+  update_ptr_block<CoreW8F>(cin, ap, bp, cout, n, mb, nbm, unit, ytab, sm);
 }
 
 // X[:, s] := alpha * A[:, s] * Winv_s^T, in place, for row blocks r >= r0 of `ntiles`
@@ -2784,50 +2685,53 @@ inline UpdateGrid update_grid(long tot_a, long tot_b, bool single_diag) {
   return u;
 }
 
+// what the three work-list launchers share: the list offset taken out of offb (the kernels index from d_list + off),
+// the blocks per tile, and the grid of the two segments
+struct UpdateLaunch {
+  int offb, nbm, blocks_a, unit;
+  dim3 grid;
+};
+inline UpdateLaunch update_launch(const LocalMat &C, int off, int na, int offb, int nb) {
+  const int nbm = C.mb / MACRO, MT = nbm * nbm, MTd = nbm * (nbm + 1) / 2;
+  const UpdateGrid u = update_grid((long)na * MT, (long)nb * MTd, na == 0 && nb == 1);
+  return {offb - off, nbm, (int)u.blocks_a, u.unit, dim3((unsigned)(u.blocks_a + u.blocks_b))};
+}
+
 template <typename T>
 void launch_trail_update(hipStream_t s, const LocalMat &C, const int2 *d_list, int off, int na, int offb,
                          int nb, const PanelRef &pan, bool yield, const PanelRef *pan2) {
   if (na + nb <= 0) return;
   const int npan = pan2 ? 2 : 1;
   const PanelRef &p2 = pan2 ? *pan2 : pan;
-  offb -= off;  // the kernels index from d_list + off
-  const int nbm = C.mb / MACRO, MT = nbm * nbm, MTd = nbm * (nbm + 1) / 2;
-  const UpdateGrid u = update_grid((long)na * MT, (long)nb * MTd, na == 0 && nb == 1);
-  const dim3 grid((unsigned)(u.blocks_a + u.blocks_b));
+  const UpdateLaunch l = update_launch(C, off, na, offb, nb);
   if constexpr (sizeof(T) == 4)
-    k_trail_update_w8f<<<grid, dim3(512), 0, s>>>(C, d_list + off, na, offb, nb, (int)u.blocks_a, pan, nbm, u.unit,
-                                                 yield ? g_ytab : nullptr, p2, npan);
+    k_trail_update_w8f<<<l.grid, dim3(512), 0, s>>>(C, d_list + off, na, l.offb, nb, l.blocks_a, pan, l.nbm, l.unit,
+                                                   yield ? g_ytab : nullptr, p2, npan);
   else
-    k_trail_update_w8<T, 3><<<grid, dim3(512), 0, s>>>(C, d_list + off, na, offb, nb, (int)u.blocks_a, pan, nbm, u.unit,
-                                                       yield ? g_ytab : nullptr, p2, npan);
+    k_trail_update_w8<T, 3><<<l.grid, dim3(512), 0, s>>>(C, d_list + off, na, l.offb, nb, l.blocks_a, pan, l.nbm, l.unit,
+                                                         yield ? g_ytab : nullptr, p2, npan);
 }
 
 template <typename T>
 void launch_syr2k_update(hipStream_t s, const LocalMat &C, const int2 *d_list, int off, int na, int offb, int nb,
                          const PanelRef &pan, const PanelRef &qan) {
   if (na + nb <= 0) return;
-  offb -= off;  // the kernels index from d_list + off
-  const int nbm = C.mb / MACRO, MT = nbm * nbm, MTd = nbm * (nbm + 1) / 2;
-  const UpdateGrid u = update_grid((long)na * MT, (long)nb * MTd, na == 0 && nb == 1);
-  const dim3 grid((unsigned)(u.blocks_a + u.blocks_b));
+  const UpdateLaunch l = update_launch(C, off, na, offb, nb);
   if constexpr (sizeof(T) == 4)
-    k_syr2k_w8f<<<grid, dim3(512), 0, s>>>(C, d_list + off, na, offb, nb, (int)u.blocks_a, pan, qan, nbm, u.unit);
+    k_syr2k_w8f<<<l.grid, dim3(512), 0, s>>>(C, d_list + off, na, l.offb, nb, l.blocks_a, pan, qan, l.nbm, l.unit);
   else
-    k_syr2k_w8<T, 3><<<grid, dim3(512), 0, s>>>(C, d_list + off, na, offb, nb, (int)u.blocks_a, pan, qan, nbm, u.unit);
+    k_syr2k_w8<T, 3><<<l.grid, dim3(512), 0, s>>>(C, d_list + off, na, l.offb, nb, l.blocks_a, pan, qan, l.nbm, l.unit);
 }
 
 template <typename T>
 void launch_ldl_update(hipStream_t s, const LocalMat &C, const int2 *d_list, int off, int na, int offb, int nb,
                        const PanelRef &pan, const PanelRef &qan) {
   if (na + nb <= 0) return;
-  offb -= off;  // the kernels index from d_list + off
-  const int nbm = C.mb / MACRO, MT = nbm * nbm, MTd = nbm * (nbm + 1) / 2;
-  const UpdateGrid u = update_grid((long)na * MT, (long)nb * MTd, na == 0 && nb == 1);
-  const dim3 grid((unsigned)(u.blocks_a + u.blocks_b));
+  const UpdateLaunch l = update_launch(C, off, na, offb, nb);
   if constexpr (sizeof(T) == 4)
-    k_ldl_update_w8f<<<grid, dim3(512), 0, s>>>(C, d_list + off, na, offb, nb, (int)u.blocks_a, pan, qan, nbm, u.unit);
+    k_ldl_update_w8f<<<l.grid, dim3(512), 0, s>>>(C, d_list + off, na, l.offb, nb, l.blocks_a, pan, qan, l.nbm, l.unit);
   else
-    k_ldl_update_w8<T, 3><<<grid, dim3(512), 0, s>>>(C, d_list + off, na, offb, nb, (int)u.blocks_a, pan, qan, nbm, u.unit);
+    k_ldl_update_w8<T, 3><<<l.grid, dim3(512), 0, s>>>(C, d_list + off, na, l.offb, nb, l.blocks_a, pan, qan, l.nbm, l.unit);
 }
 
 // One 128-column step of the panel TRSM over `ntiles` tiles: X[:, st] = A[:, st] Winv_st^T, then

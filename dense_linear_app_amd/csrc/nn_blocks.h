@@ -4,37 +4,11 @@
 // fragment layout.  Every output element is summed by one lane in a fixed order.
 #pragma once
 #include "cholmi_internal.h"
+#include "mfma_traits.h"
 
 namespace cholmi {
 
 namespace {
-
-typedef double vd4_t __attribute__((ext_vector_type(4)));
-typedef float vf4_t __attribute__((ext_vector_type(4)));
-
-template <typename T>
-struct Mf;
-template <>
-struct Mf<double> {
-  using acc_t = vd4_t;
-  using vec4_t = vd4_t;
-  static __device__ __forceinline__ acc_t mfma(double a, double b, acc_t c) {
-    return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int drow(int lane, int reg) { return (lane >> 4) + 4 * reg; }
-};
-template <>
-struct Mf<float> {
-  using acc_t = vf4_t;
-  using vec4_t = vf4_t;
-  static __device__ __forceinline__ acc_t mfma(float a, float b, acc_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ int drow(int lane, int reg) { return 4 * (lane >> 4) + reg; }
-};
-
-template <typename T>
-using Acc = typename Mf<T>::acc_t[4][4];
 
 // acc += A(i0 .. i0+63, kb .. ke) B(kb .. ke, j0 .. j0+63); A(r,k) at A[r + k lda], B(k,c) at B[k + c ldb];
 // kb, ke multiples of 16.  TRA: A is lower triangular (A(r,k) = 0 for k > r), TRB: B is (B(k,c) = 0 for k < c):
@@ -42,7 +16,7 @@ using Acc = typename Mf<T>::acc_t[4][4];
 template <typename T, bool TRA, bool TRB>
 __device__ __forceinline__ void nn_acc(const T *__restrict__ A, int lda, const T *__restrict__ B, int ldb, int i0,
                                        int j0, int kb, int ke, Acc<T> &acc) {
-  using vec4_t = typename Mf<T>::vec4_t;
+  using vec4_t = typename Tr<T>::acc_t;
   const int lane = threadIdx.x & 63, c = lane & 15, g4 = (lane >> 4) * 4;
   for (int k0 = kb; k0 < ke; k0 += 16) {
     T xa[4][4], xb[4][4];
@@ -68,18 +42,8 @@ __device__ __forceinline__ void nn_acc(const T *__restrict__ A, int lda, const T
 #pragma unroll
       for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = Mf<T>::mfma(xb[b][s], xa[a][s], acc[a][b]);
+        for (int b = 0; b < 4; ++b) acc[a][b] = Tr<T>::mfma(xb[b][s], xa[a][s], acc[a][b]);
   }
-}
-
-template <typename T>
-__device__ __forceinline__ void acc_zero(Acc<T> &acc) {
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[a][b][r] = T(0);
 }
 
 // C(i0 + 16a + (lane & 15), j0 + 16b + drow(lane, r)) = alpha acc[a][b][r]
@@ -92,7 +56,7 @@ __device__ __forceinline__ void acc_store(T *C, int ldc, int i0, int j0, const A
     for (int b = 0; b < 4; ++b)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        C[(i0 + 16 * a + c) + (long)(j0 + 16 * b + Mf<T>::drow(lane, r)) * ldc] = alpha * acc[a][b][r];
+        C[(i0 + 16 * a + c) + (long)(j0 + 16 * b + Tr<T>::drow(lane, r)) * ldc] = alpha * acc[a][b][r];
 }
 
 }  // namespace

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256, 2) void k_sg_row_y(const T *A, const T *L, lon
     for (int b = 0; b < 4; ++b)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const long at = (i0 + 16 * a + c) + (long)(j0 + 16 * b + Mf<T>::drow(lane, r)) * E;
+        const long at = (i0 + 16 * a + c) + (long)(j0 + 16 * b + Tr<T>::drow(lane, r)) * E;
         Y[at] = P[at] - acc[a][b][r];
       }
 }

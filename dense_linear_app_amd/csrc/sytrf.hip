@@ -48,7 +48,7 @@ __device__ __forceinline__ void nt_acc(const T *__restrict__ A, int lda, const T
 #pragma unroll
       for (int a = 0; a < 4; ++a)
 #pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = Mf<T>::mfma(xb[b][s], xa[a][s], acc[a][b]);
+        for (int b = 0; b < 4; ++b) acc[a][b] = Tr<T>::mfma(xb[b][s], xa[a][s], acc[a][b]);
   }
 }
 
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256, 2) void k_ldl_rows(T *tile, int e, int s, cons
     for (int b = 0; b < 4; ++b)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const int col = j0 + 16 * b + Mf<T>::drow(lane, q);
+        const int col = j0 + 16 * b + Tr<T>::drow(lane, q);
         const long at = at0 + (i0 + 16 * a + c) + (long)col * e;
         Wt[at] = acc[a][b][q];
         tile[at] = acc[a][b][q] * rv[col] + T(0);  // (+ 0: the zeros of the padding stay +0)
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void k_ldl_intile(T *tile, int e, int s, co
     for (int b = 0; b < 4; ++b)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const int row = i0 + 16 * a + c, col = j0 + 16 * b + Mf<T>::drow(lane, q);
+        const int row = i0 + 16 * a + c, col = j0 + 16 * b + Tr<T>::drow(lane, q);
         if (r == cc && row < col) continue;
         C[row + (long)col * e] -= acc[a][b][q];
       }
