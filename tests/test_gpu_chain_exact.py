@@ -1,0 +1,250 @@
+"""The panel chain, bit for bit: CHAMELEON_{d,s}potrf_Tile on the dyadic family of dyadic_model.py, whose factor every
+blocked algorithm must return exactly (test_dyadic_host.py proves that for the reference alone), in every form of the
+chain -- event-linked, counter-linked and flow; small-block and throughput TRSM steps; fused and split in-tile steps;
+paired panels; gates and self-polling grids -- each forced through its environment switch in one fresh child process
+(the switches are read once, at chol_init).  Dense diagonal blocks, block inverses, in-tile solves and panel tiles
+throughout: a wrong hand-off, a skipped block column or a sign in the recursive inverse changes integers.
+
+In-process: the probe of the fp64 pivot chain (rsq + two Goldschmidt steps, no sqrt) at powers of four, ChamUpper, the
+single-tile POTRF and TRSM (alpha != 1 takes the throughput form on one tile; B = 200 the staged, padded path) and the
+wave-level task path."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import dyadic_model as dm
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+SHAPES = [(512, 128), (1024, 256), (1536, 384), (2048, 512), (4096, 1024), (1000, 192), (1100, 320)]
+PIPE_ALL = {"CHOLMI_PIPE_FACTOR": "100", "CHOLMI_PAIR_FACTOR": "1000"}
+FLOW_ALL = {"CHOLMI_FLOW_FACTOR": "100", "CHOLMI_PIPE_FACTOR": "100", "CHOLMI_PAIR_FACTOR": "1000"}
+
+
+def npdt(dt):
+    return np.float64 if dt == "d" else np.float32
+
+
+def chdt(ch, dt):
+    return ch.ChamRealDouble if dt == "d" else ch.ChamRealFloat
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
+
+
+def stored_lower(A, dt, fill=np.nan):
+    """the lower triangle of A in dtype dt, the strict upper triangle = fill"""
+    n = A.shape[0]
+    return np.asfortranarray(np.where(np.tri(n, dtype=bool), A, fill).astype(npdt(dt)))
+
+
+def mismatches(got, want, B):
+    """-> (count, the first few as (tile row, tile column, 128-block row, 128-block column) of the tile)"""
+    i, j = np.nonzero(got != want)
+    where = sorted({(int(a // B), int(b // B), int(a % B // 128), int(b % B // 128)) for a, b in zip(i[:4096], j[:4096])})
+    return int(len(i)), where[:6]
+
+
+def factor_case(ch, N, B, dt, S, L):
+    """one whole-matrix factorisation of S (the Cholesky member as stored_lower leaves it) -> the record the child
+    prints"""
+    d = ch.CHAMELEON_Desc_Create(None, chdt(ch, dt), B, B, B * B, N, N, 0, 0, N, N, 1, 1)
+    d.from_lapack(S)
+    info = ch.CHAMELEON_dpotrf_Tile(ch.ChamLower, d)
+    F = d.to_lapack()
+    ch.CHAMELEON_Desc_Destroy(d)
+    low = np.tri(N, dtype=bool)
+    count, where = mismatches(np.where(low, F, 0), L, B)
+    return {"N": N, "B": B, "dt": dt, "info": int(info), "mismatches": count, "first": where,
+            "upper_touched": int(((bits(F) != bits(S)) & ~low).sum()), "regimes": ch.last_potrf_regimes()}
+
+
+def child_main():
+    """every shape in fp64 and fp32 under the switches of this process's environment, one record per case"""
+    import time
+
+    t0 = time.perf_counter()
+    sys.path.insert(0, ROOT)
+    from dense_linear_app_amd import chameleon as ch
+
+    ch.CHAMELEON_Init(1, 1)
+    t1 = time.perf_counter()
+    for N, B in SHAPES:
+        A, L, _ = dm.cholesky_case(N, N)
+        S = stored_lower(A, "s")  # (integers far below 2^24: the fp32 image holds them exactly)
+        Ls = L.astype(np.float32)
+        for dt in ("d", "s"):
+            rec = factor_case(ch, N, B, dt, S.astype(npdt(dt)), Ls.astype(npdt(dt)))
+            print("CASE " + json.dumps(rec), flush=True)
+    print(f"TIME start-up {t1 - t0:.2f} s, cases {time.perf_counter() - t1:.2f} s", flush=True)
+
+
+def nbm_of(c):
+    return -(-c["B"] // 128)
+
+
+def counter_linked(cases):
+    assert all(c["regimes"]["counter_linked"] >= 1 for c in cases), cases
+
+
+def event_linked(cases):
+    assert all(c["regimes"]["counter_linked"] == 0 and c["regimes"]["flow"] == 0 for c in cases), cases
+
+
+def paired(cases):
+    assert all(c["regimes"]["paired"] >= 1 for c in cases), cases
+
+
+def near_off(cases):
+    counter_linked(cases)
+    assert all(c["regimes"]["near_column"] == 0 and c["regimes"]["column_latency_form"] == 0 for c in cases), cases
+
+
+def near_on(cases):
+    counter_linked(cases)
+    assert all(c["regimes"]["near_column"] >= 1 for c in cases), cases
+    assert all(c["regimes"]["column_latency_form"] >= 1 for c in cases if nbm_of(c) <= 4), cases
+
+
+def flow(cases):
+    assert all(c["regimes"]["flow"] >= 1 for c in cases if nbm_of(c) >= 2), cases
+
+
+SETTINGS = [
+    ("default", {}, None),
+    ("trsm-throughput", {"CHOLMI_TRSM_SMALL_MAX": "0"}, None),
+    ("trsm-throughput-counters", dict(PIPE_ALL, CHOLMI_TRSM_SMALL_MAX="0"), counter_linked),
+    ("trsm-small", {"CHOLMI_TRSM_SMALL_MAX": "100000"}, None),
+    ("intile-split", {"CHOLMI_INTILE_FUSED": "0"}, None),
+    ("intile-split-counters", dict(PIPE_ALL, CHOLMI_INTILE_FUSED="0"), counter_linked),
+    ("events-only", {"CHOLMI_DEVICE_FLAGS": "0"}, event_linked),
+    ("counters", PIPE_ALL, counter_linked),
+    ("counters-no-near", dict(PIPE_ALL, CHOLMI_NEAR_FACTOR="0", CHOLMI_U1_SMALL="0"), near_off),
+    ("counters-near", dict(PIPE_ALL, CHOLMI_NEAR_FACTOR="100", CHOLMI_U1_SMALL="64"), near_on),
+    ("paired", {"CHOLMI_PAIR_FACTOR": "0"}, paired),
+    ("gates", {"CHOLMI_POLL_MAX_WGS": "0"}, None),
+    ("self-polling", {"CHOLMI_POLL_MAX_WGS": "100000"}, None),
+    ("flow", dict(FLOW_ALL, CHOLMI_FLOW_NBM="2:8"), flow),
+    ("flow-fences", dict(FLOW_ALL, CHOLMI_FLOW_NBM="2:8", CHOLMI_FLOW_FENCES="1"), flow),
+]
+
+
+@pytest.mark.parametrize("name,env,regime", SETTINGS, ids=[s[0] for s in SETTINGS])
+def test_potrf_is_exact_in_every_form_of_the_chain(name, env, regime):
+    """every shape (nbm = 1, 2, 3, 4, 8 with four tiles per side: a head tile, a far column, room for a pair from wave 1;
+    two ragged orders with odd tiles and identity padding), fp64 and fp32, in one child per setting: info = 0, tril(F) ==
+    L with zero mismatches, the NaN-filled strict upper triangle untouched, and -- where the setting forces a regime --
+    the library's count says that it ran"""
+    try:
+        r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, **env), capture_output=True,
+                           text=True, timeout=300)
+    except subprocess.TimeoutExpired as e:
+        pytest.exit(f"the child of setting {name} hung: nothing more is started on this GPU ({e.stdout})", returncode=3)
+    print(r.stdout)
+    if r.returncode < 0 or r.returncode in (134, 139):  # killed by a signal: a GPU fault or abort, not a wrong number
+        pytest.exit(f"the child of setting {name} died ({r.returncode}): nothing more is started on this GPU\n"
+                    f"{r.stdout}\n{r.stderr[-2000:]}", returncode=3)
+    assert r.returncode == 0, (r.stdout, r.stderr[-2000:])
+    cases = [json.loads(ln[5:]) for ln in r.stdout.splitlines() if ln.startswith("CASE ")]
+    assert [(c["N"], c["B"], c["dt"]) for c in cases] == [(N, B, dt) for N, B in SHAPES for dt in "ds"]
+    bad = [c for c in cases if c["info"] != 0 or c["mismatches"] or c["upper_touched"]]
+    assert not bad, bad
+    if regime:
+        regime(cases)
+
+
+# ---- in-process ---------------------------------------------------------------------------------------------------------
+def potrf_tile(ch, A, dt, fill=np.nan):
+    """single-tile POTRF on a host buffer -> (info, the tile afterwards, the tile as stored)"""
+    S = stored_lower(A, dt, fill)
+    T = S.copy(order="F")
+    B = A.shape[0]
+    d = ch.CHAMELEON_Desc_Create(T, chdt(ch, dt), B, B, B * B, B, B, 0, 0, B, B, 1, 1)
+    info = ch.CHAMELEON_dpotrf_Tile(ch.ChamLower, d)
+    ch.CHAMELEON_Desc_Destroy(d)
+    return info, T, S
+
+
+@pytest.mark.parametrize("dt", ["d", "s"])
+def test_pivot_chain_is_exact_at_powers_of_four(cham, dt):
+    """the fp64 pivot chain takes no square root: v_rsq_f64 and two Goldschmidt steps, rinv = h + h uncorrected.  At
+    d = 4^k the second step lands on 2^k and 2^-k exactly as long as the instruction's result is within about 2^-26 of
+    2^-k -- the fact every fp64 case of this file and of test_gpu_factor_exact.py rests on"""
+    ch = cham
+    d = np.array([1.0, 4.0, 16.0])[np.arange(128) % 3]
+    info, T, _ = potrf_tile(ch, np.diag(d), dt, fill=0.0)
+    got, want = np.diag(T), np.sqrt(d).astype(npdt(dt))
+    print("pivots", dt, [(float(a), hex(int(b))) for a, b in zip(d[:3], bits(got[:3]))])
+    assert info == 0 and np.array_equal(bits(got), bits(want)), [hex(int(b)) for b in bits(got[:3])]
+    assert not np.any(np.tril(T, -1))
+    A, L, _ = dm.cholesky_case(128, 128)
+    info, T, S = potrf_tile(ch, A, dt)
+    assert info == 0
+    assert mismatches(np.tril(T), L.astype(npdt(dt)), 128)[0] == 0
+
+
+@pytest.mark.parametrize("N,B", [(1024, 256), (1000, 192)])
+@pytest.mark.parametrize("dt", ["d", "s"])
+def test_potrf_upper_is_exact(cham, N, B, dt):
+    ch = cham
+    A, L, _ = dm.cholesky_case(N, N)
+    S = np.array(stored_lower(A, dt).T, order="F")
+    d = ch.CHAMELEON_Desc_Create(None, chdt(ch, dt), B, B, B * B, N, N, 0, 0, N, N, 1, 1)
+    d.from_lapack(S)
+    assert ch.CHAMELEON_dpotrf_Tile(ch.ChamUpper, d) == 0
+    F = d.to_lapack()
+    ch.CHAMELEON_Desc_Destroy(d)
+    assert mismatches(np.triu(F).T, L.astype(npdt(dt)), B) == (0, [])
+    il = np.tril_indices(N, -1)
+    assert np.array_equal(bits(F[il]), bits(S[il]))
+
+
+@pytest.mark.parametrize("B", [128, 256, 512, 1024, 200])
+@pytest.mark.parametrize("dt", ["d", "s"])
+def test_single_tile_potrf_and_trsm_are_exact(cham, B, dt):
+    """one tile: POTRF returns L; TRSM (Right, Lower, Trans, NonUnit, alpha) on X L^T returns alpha X -- alpha = 1 in the
+    small-block form, alpha = -2 and 1/2 through k_panel_solve / k_panel_update"""
+    ch = cham
+    A, L, _ = dm.cholesky_case(B, B)
+    info, T, S = potrf_tile(ch, A, dt)
+    assert info == 0
+    assert mismatches(np.tril(T), L.astype(npdt(dt)), B) == (0, [])
+    iu = np.triu_indices(B, 1)
+    assert np.array_equal(bits(T[iu]), bits(S[iu]))
+    X = dm.solution(B, B, B)
+    P = X @ L.T
+    assert np.abs(P).max() * 16 < 2.0 ** 24
+    Lt = np.array(stored_lower(L, dt), order="F")  # (TRSM reads the lower triangle only)
+    dl = ch.CHAMELEON_Desc_Create(Lt, chdt(ch, dt), B, B, B * B, B, B, 0, 0, B, B, 1, 1)
+    for alpha in (1.0, -2.0, 0.5):
+        Pt = np.array(P, dtype=npdt(dt), order="F")
+        dp = ch.CHAMELEON_Desc_Create(Pt, chdt(ch, dt), B, B, B * B, B, B, 0, 0, B, B, 1, 1)
+        assert ch.CHAMELEON_dtrsm_Tile(ch.ChamRight, ch.ChamLower, ch.ChamTrans, ch.ChamNonUnit, alpha, dl, dp) == 0
+        ch.CHAMELEON_Desc_Destroy(dp)
+        assert mismatches(Pt, (alpha * X).astype(npdt(dt)), B) == (0, []), alpha
+    ch.CHAMELEON_Desc_Destroy(dl)
+
+
+@pytest.mark.parametrize("N,B", [(1024, 256), (1536, 512)])
+def test_wave_level_task_path_is_exact(cham, N, B):
+    """the worker / client route (every ready task of a wave in one ExecuteBatch) and the per-task route: exactly L"""
+    from dense_linear_app_amd import client
+    from dense_linear_app_amd.worker import DagCholeskyWorker
+
+    A, L, _ = dm.cholesky_case(N, N)
+    Af = np.array(A, order="F")
+    wave = client.run_cholesky_dag(N, B, A=Af, device_results=True, batched=True, worker=DagCholeskyWorker())
+    assert mismatches(wave.lower_factor(), L, B) == (0, [])
+    per_task = client.run_cholesky_dag(N, B, A=np.array(A, order="F"), device_results=True)
+    assert mismatches(per_task.lower_factor(), L, B) == (0, [])
+
+
+if __name__ == "__main__":
+    child_main()

@@ -1,0 +1,258 @@
+"""What consumes the factor, bit for bit, on the dyadic family of dyadic_model.py (dense diagonal blocks and panels,
+every intermediate a short dyadic number; test_dyadic_host.py proves the reference alone exact in fp32 and fp64 at these
+orders): potrs / posv, trtri, potri / poinv, lansy, porfs / posvx on the exact solution, dsposv, the L D L^T
+factorisation and its solves, and sygst -- fp64 and fp32, Lower and Upper, a tile-multiple order, a ragged one with an
+odd tile, and three tiles of 512.  The factor-consuming routines are fed the exact L directly, so they do not depend on
+potrf; posv, poinv, posvx and dsposv run the factorisation themselves."""
+import numpy as np
+import pytest
+
+import dyadic_model as dm
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(1024, 256), (1000, 192), (1536, 512)]
+
+
+def npdt(dt):
+    return np.float64 if dt == "d" else np.float32
+
+
+def chdt(ch, dt):
+    return ch.ChamRealDouble if dt == "d" else ch.ChamRealFloat
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
+
+
+def uplo(ch, u):
+    return ch.ChamLower if u == "L" else ch.ChamUpper
+
+
+def other(n, u):
+    return np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
+
+
+def stored(M, u, dt, fill=np.nan):
+    """the lower triangle of M (symmetric, or a Lower factor) stored in the `u` triangle, the other strict one = fill"""
+    S = np.array(np.tril(M) if u == "L" else np.tril(M).T, dtype=npdt(dt), order="F")
+    S[other(M.shape[0], u)] = fill
+    return S
+
+
+def lower_of(F, u):
+    return np.tril(F) if u == "L" else np.triu(F).T
+
+
+def desc(ch, N, B, dt, ncols=None, content=None):
+    nc = N if ncols is None else ncols
+    d = ch.CHAMELEON_Desc_Create(None, chdt(ch, dt), B, B, B * B, N, nc, 0, 0, N, nc, 1, 1)
+    if content is not None:
+        d.from_lapack(np.asarray(content, dtype=npdt(dt)))
+    return d
+
+
+def same(got, want, dt):
+    want = np.asarray(want).astype(npdt(dt))
+    assert got.dtype == want.dtype
+    bad = np.argwhere(got != want)
+    assert len(bad) == 0, (len(bad), bad[:6].tolist())
+
+
+def other_kept(F, S, u):
+    idx = other(S.shape[0], u)
+    return np.array_equal(bits(F[idx]), bits(S[idx]))
+
+
+def rhs(N, nrhs):
+    """(X, A X): integers, exact in fp64 and in fp32"""
+    A, _, _ = dm.cholesky_case(N, N)
+    X = dm.solution(N, nrhs, N)
+    return X, A @ X
+
+
+@pytest.mark.parametrize("N,B", SHAPES)
+@pytest.mark.parametrize("nrhs", [1, 5, 300])
+@pytest.mark.parametrize("u", ["L", "U"])
+@pytest.mark.parametrize("dt", ["d", "s"])
+def test_potrs_and_posv(cham, N, B, nrhs, u, dt):
+    """the solution is the integer X; after posv A holds L"""
+    ch = cham
+    A, L, _ = dm.cholesky_case(N, N)
+    X, Bm = rhs(N, nrhs)
+    SL = stored(L, u, dt)
+    dA, dB = desc(ch, N, B, dt, content=SL), desc(ch, N, B, dt, nrhs, Bm)
+    assert ch.CHAMELEON_dpotrs_Tile(uplo(ch, u), dA, dB) == 0
+    same(dB.to_lapack(), X, dt)
+    assert np.array_equal(bits(dA.to_lapack()), bits(SL))  # the factor is only read
+    SA = stored(A, u, dt)
+    dA.from_lapack(SA)
+    dB.from_lapack(Bm.astype(npdt(dt)))
+    assert ch.CHAMELEON_dposv_Tile(uplo(ch, u), dA, dB) == 0
+    same(dB.to_lapack(), X, dt)
+    F = dA.to_lapack()
+    same(lower_of(F, u), L, dt)
+    assert other_kept(F, SA, u)
+    ch.CHAMELEON_Desc_Destroy(dA)
+    ch.CHAMELEON_Desc_Destroy(dB)
+
+
+@pytest.mark.parametrize("N,B", SHAPES)
+@pytest.mark.parametrize("u", ["L", "U"])
+@pytest.mark.parametrize("dt", ["d", "s"])
+def test_trtri(cham, N, B, u, dt):
+    """inv(L) = diag(1/s) (I - Nn); the other triangle untouched"""
+    ch = cham
+    _, L, _ = dm.cholesky_case(N, N)
+    S = stored(L, u, dt)
+    d = desc(ch, N, B, dt, content=S)
+    assert ch.CHAMELEON_dtrtri_Tile(uplo(ch, u), ch.ChamNonUnit, d) == 0
+    F = d.to_lapack()
+    ch.CHAMELEON_Desc_Destroy(d)
+    same(lower_of(F, u), dm.inv_factor(N, N), dt)
+    assert other_kept(F, S, u)
+
+
+@pytest.mark.parametrize("N,B", SHAPES)
+@pytest.mark.parametrize("u", ["L", "U"])
+@pytest.mark.parametrize("dt", ["d", "s"])
+def test_potri_and_poinv(cham, N, B, u, dt):
+    """inv(A) = inv(L)^T inv(L) from the closed form (multiples of 1/4): potri from the exact factor, poinv from A"""
+    ch = cham
+    A, L, _ = dm.cholesky_case(N, N)
+    want = np.tril(dm.inv_spd(N, N))
+    for call, M in ((ch.CHAMELEON_dpotri_Tile, L), (ch.CHAMELEON_dpoinv_Tile, A)):
+        S = stored(M, u, dt)
+        d = desc(ch, N, B, dt, content=S)
+        assert call(uplo(ch, u), d) == 0
+        F = d.to_lapack()
+        ch.CHAMELEON_Desc_Destroy(d)
+        same(lower_of(F, u), want, dt)
+        assert other_kept(F, S, u)
+
+
+@pytest.mark.parametrize("N,B", SHAPES)
+@pytest.mark.parametrize("u", ["L", "U"])
+@pytest.mark.parametrize("dt", ["d", "s"])
+def test_lansy(cham, N, B, u, dt):
+    """sums of integers: the one, infinity and max norms equal numpy's; Frobenius on its tolerance"""
+    ch = cham
+    A, _, _ = dm.cholesky_case(N, N)
+    d = desc(ch, N, B, dt, content=stored(A, u, dt))
+    one = np.abs(A).sum(0).max()
+    assert ch.CHAMELEON_dlansy_Tile(ch.ChamOneNorm, uplo(ch, u), d) == one
+    assert ch.CHAMELEON_dlansy_Tile(ch.ChamInfNorm, uplo(ch, u), d) == one
+    assert ch.CHAMELEON_dlansy_Tile(ch.ChamMaxNorm, uplo(ch, u), d) == np.abs(A).max()
+    fro = np.linalg.norm(A)
+    assert abs(ch.CHAMELEON_dlansy_Tile(ch.ChamFrobeniusNorm, uplo(ch, u), d) - fro) <= (1e-12 if dt == "d" else 1e-5) * fro
+    ch.CHAMELEON_Desc_Destroy(d)
+
+
+@pytest.mark.parametrize("N,B", SHAPES)
+@pytest.mark.parametrize("u", ["L", "U"])
+@pytest.mark.parametrize("dt", ["d", "s"])
+def test_porfs_and_posvx_on_the_exact_solution(cham, N, B, u, dt):
+    """porfs on the exact X: the residual is exactly zero, so berr == 0 and X comes back bit for bit; posvx with
+    fact = N (A needs no equilibration) returns X.  (X without zeros: a row of A with two entries -- the last even row
+    has no more -- times a zero in both places has the weight |b| + |A| |x| = 0, for which LAPACK's rule, and the
+    library's, gives berr = (0 + safe1) / (0 + safe1) = 1.)"""
+    ch = cham
+    A, L, _ = dm.cholesky_case(N, N)
+    nrhs = 5
+    X = dm.solution(N, nrhs, N)
+    X = np.where(X == 0, 1.0, X)
+    Bm = A @ X
+    assert (np.abs(Bm) + np.abs(A) @ np.abs(X)).min() >= 1
+    SA = stored(A, u, dt)
+    dA, dAF = desc(ch, N, B, dt, content=SA), desc(ch, N, B, dt, content=stored(L, u, dt))
+    dB, dX = desc(ch, N, B, dt, nrhs, Bm), desc(ch, N, B, dt, nrhs, X)
+    info, ferr, berr = ch.CHAMELEON_dporfs_Tile(uplo(ch, u), dA, dAF, dB, dX)
+    assert info == 0 and np.array_equal(berr, np.zeros(nrhs)), berr
+    same(dX.to_lapack(), X, dt)
+    dAF.from_lapack(np.full((N, N), np.nan, dtype=npdt(dt)))
+    dX.from_lapack(np.zeros((N, nrhs), dtype=npdt(dt)))
+    info, equed, rcond, ferr, berr = ch.CHAMELEON_dposvx_Tile("N", uplo(ch, u), dA, dAF, "N", None, dB, dX)
+    # (LAPACK's info = n + 1, "rcond below eps", comes with the solution computed; fp32 reaches it at these orders)
+    assert info == (N + 1 if rcond < (2.0 ** -53 if dt == "d" else 2.0 ** -24) else 0) and equed == "N" and rcond > 0
+    same(dX.to_lapack(), X, dt)
+    assert np.array_equal(berr, np.zeros(nrhs)), berr
+    same(lower_of(dAF.to_lapack(), u), L, dt)
+    assert np.array_equal(bits(dA.to_lapack()), bits(SA))
+    for d in (dA, dAF, dB, dX):
+        ch.CHAMELEON_Desc_Destroy(d)
+
+
+@pytest.mark.parametrize("N,B", SHAPES)
+@pytest.mark.parametrize("u", ["L", "U"])
+def test_dsposv(cham, N, B, u):
+    """the fp32 factor is exact, so the first solve is: the residual is zero, iter = 0 (the loop of dsposv_mixed leaves
+    at its first convergence test, after one solve and one residual pass), X bit for bit"""
+    ch = cham
+    A, _, _ = dm.cholesky_case(N, N)
+    nrhs = 5
+    X, Bm = rhs(N, nrhs)
+    SA = stored(A, u, "d")
+    dA, dB, dX = desc(ch, N, B, "d", content=SA), desc(ch, N, B, "d", nrhs, Bm), desc(ch, N, B, "d", nrhs)
+    info, it = ch.CHAMELEON_dsposv_Tile(uplo(ch, u), dA, dB, dX)
+    st = ch.last_dsposv_stats()
+    assert (info, it) == (0, 0) and st["solves"] == 1 and st["residuals"] == 1
+    same(dX.to_lapack(), X, "d")
+    assert np.array_equal(bits(dA.to_lapack()), bits(SA))
+    for d in (dA, dB, dX):
+        ch.CHAMELEON_Desc_Destroy(d)
+
+
+@pytest.mark.parametrize("N,B", SHAPES + [(700, 128)])
+@pytest.mark.parametrize("u", ["L", "U"])
+@pytest.mark.parametrize("dt", ["d", "s"])
+def test_sytrf_sytrs_sysv_nopiv(cham, N, B, u, dt):
+    """the L D L^T member: (L, d), the inertia and the stats exact; both solves return the integer X"""
+    ch = cham
+    A, L, dd = dm.ldl_case(N, N)
+    nrhs = 5
+    X = dm.solution(N, nrhs, N)
+    Bm = A @ X
+    SA = stored(A, u, dt)
+    dA, dB = desc(ch, N, B, dt, content=SA), desc(ch, N, B, dt, nrhs, Bm)
+
+    def check_factor():
+        F = dA.to_lapack()
+        Fl = lower_of(F, u)
+        same(np.tril(Fl, -1), np.tril(L, -1), dt)
+        same(np.diag(Fl).copy(), dd, dt)
+        assert other_kept(F, SA, u)
+        st = ch.last_sytrf_stats()
+        assert st["inertia"] == (int((dd > 0).sum()), int((dd < 0).sum()))
+        assert (st["min_abs_d"], st["max_abs_d"], st["max_abs_l"]) == (1.0, 4.0, 1.0)
+
+    assert ch.CHAMELEON_dsytrf_nopiv_Tile(uplo(ch, u), dA) == 0
+    check_factor()
+    assert ch.CHAMELEON_dsytrs_nopiv_Tile(uplo(ch, u), dA, dB) == 0
+    same(dB.to_lapack(), X, dt)
+    dA.from_lapack(SA)
+    dB.from_lapack(Bm.astype(npdt(dt)))
+    assert ch.CHAMELEON_dsysv_nopiv_Tile(uplo(ch, u), dA, dB) == 0
+    check_factor()
+    same(dB.to_lapack(), X, dt)
+    ch.CHAMELEON_Desc_Destroy(dA)
+    ch.CHAMELEON_Desc_Destroy(dB)
+
+
+@pytest.mark.parametrize("N,B", SHAPES + [(1100, 128)])
+@pytest.mark.parametrize("u", ["L", "U"])
+@pytest.mark.parametrize("dt", ["d", "s"])
+def test_sygst(cham, N, B, u, dt):
+    """inv(L) (L M L^T) inv(L)^T = M, every tile of L and of the panels dense"""
+    ch = cham
+    A, L, M = dm.sygst_case(N, N)
+    SA, SB = stored(A, u, dt), stored(L, u, dt, fill=-7.0)
+    dA, dB = desc(ch, N, B, dt, content=SA), desc(ch, N, B, dt, content=SB)
+    assert ch.CHAMELEON_dsygst_Tile(1, uplo(ch, u), dA, dB) == 0
+    F = dA.to_lapack()
+    same(lower_of(F, u), np.tril(M), dt)
+    assert other_kept(F, SA, u)
+    assert np.array_equal(bits(dB.to_lapack()), bits(SB))
+    ch.CHAMELEON_Desc_Destroy(dA)
+    ch.CHAMELEON_Desc_Destroy(dB)

@@ -131,7 +131,9 @@ def exact_case(n, seed):
 @pytest.mark.parametrize("u", ["L", "U"])
 @pytest.mark.parametrize("dt", ["d", "s"])
 def test_exact_integer(cham, n, B, u, dt):
-    """n / 2 is not tile-aligned: E reaches into a diagonal tile"""
+    """a sparse exact case: n / 2 is not tile-aligned, so E reaches into the one diagonal tile that straddles it; every
+    other diagonal tile of L is the identity and most panel tiles are zero.  The dense exact family, in which every
+    diagonal block, block inverse and panel tile is non-trivial: test_gpu_factor_exact.py::test_sygst"""
     ch = cham
     A, L, M = exact_case(n, n + B)
     info, C, *_ = sygst(ch, A, L, B, u, dt)

@@ -168,6 +168,8 @@ def exact_case(n, seed):
 @pytest.mark.parametrize("u", ["L", "U"])
 @pytest.mark.parametrize("dt", ["d", "s"])
 def test_exact_integer(cham, n, B, u, dt):
+    """a sparse exact case: every diagonal tile of L but the one that straddles n / 2 is the identity.  The dense exact
+    family, with its solves: test_gpu_factor_exact.py::test_sytrf_sytrs_sysv_nopiv"""
     ch = cham
     A, L, d = exact_case(n, n + B)
     info, Fg, _, _, st = sytrf(ch, A, B, u, dt)
