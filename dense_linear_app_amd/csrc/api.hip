@@ -402,19 +402,6 @@ int read_info(int *info) {
   return 0;
 }
 
-// the work-list segments of the tiles in columns [jlo, jhi)
-struct ColRange {
-  int off, na, offb, nb;
-};
-static inline ColRange col_range(const chol_desc *d, int jlo, int jhi) {
-  ColRange r;
-  r.off = d->ge[jhi];
-  r.na = d->ge[jlo] - d->ge[jhi];
-  r.offb = d->n_off + d->gd[jhi];
-  r.nb = d->gd[jlo] - d->gd[jhi];
-  return r;
-}
-
 // ---- sub-matrix views over a user buffer: the library works on a compact image of the view, tiled on its own.
 // The user's matrix holds whole mb x nb tiles of bsiz elements (ld = mb, tile (TI, TJ) at (TI + TJ lmt) bsiz); the
 // image's tiles are mbi x mbi (mb rounded up to 128, identity outside the matrix).  Entry (r, c) of the view is entry
@@ -725,10 +712,6 @@ int through_lower(bool upper, std::initializer_list<chol_desc *> ds, const std::
 }
 
 LocalMat whole_local_mat(const chol_desc *d) { return local_mat(d, d->mat); }
-WorkRange whole_col_range(const chol_desc *d, int jlo, int jhi) {
-  const ColRange r = col_range(d, jlo, jhi);
-  return WorkRange{r.off, r.na, r.offb, r.nb};
-}
 
 // (posvx factors AF inside its own view refresh)
 int potrf_run(int uplo, chol_desc *A) {

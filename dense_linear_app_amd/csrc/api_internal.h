@@ -102,13 +102,10 @@ void transpose_storage(chol_desc *A);
 CHOL_LOCAL int through_lower(bool upper, std::initializer_list<chol_desc *> ds, const std::function<int()> &body,
                         bool wait = true, void (*flip)(chol_desc *) = transpose_storage);
 
-// a whole-matrix descriptor's trailing update: its local tile matrix, the segments of its work list that hold the
-// tiles of columns [jlo, jhi), and a panel whose tiles lie one after another from `base` (tile `first` at base)
+// a whole-matrix descriptor's trailing update: its local tile matrix (the segments of its work list that hold the
+// tiles of columns [jlo, jhi): cholmi_internal.h, col_range), and a panel whose tiles lie one after another from
+// `base` (tile `first` at base)
 LocalMat whole_local_mat(const chol_desc *d);
-struct WorkRange {
-  int off, na, offb, nb;
-};
-WorkRange whole_col_range(const chol_desc *d, int jlo, int jhi);
 inline PanelRef one_panel(const void *base, int first = 0) {
   PanelRef pan = {};
   pan.P = 1;

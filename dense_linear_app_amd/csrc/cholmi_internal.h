@@ -40,6 +40,16 @@ struct chol_desc {
 
 extern "C" int chol_internal_fail(int code, const char *msg);  // api.hip: sets chol_last_error, returns code
 
+// the segments of a descriptor's work list that hold the tiles of columns [jlo, jhi) (clamped to the matrix):
+// `na` off-diagonal entries from `off`, `nb` diagonal ones from `offb`
+struct ColRange {
+  int off, na, offb, nb;
+};
+inline ColRange col_range(const chol_desc *d, int jlo, int jhi) {
+  jlo = std::min(jlo, d->nt), jhi = std::min(jhi, d->nt);
+  return ColRange{d->ge[jhi], d->ge[jlo] - d->ge[jhi], d->n_off + d->gd[jhi], d->gd[jlo] - d->gd[jhi]};
+}
+
 namespace cholmi {
 
 // streams of one rank's factorisation (walker.h)

@@ -62,19 +62,6 @@ int hip_fail(hipError_t e, const char *what) {
     if (e_ != hipSuccess) return hip_fail(e_, #call);    \
   } while (0)
 
-struct ColRange {
-  int off, na, offb, nb;
-};
-inline ColRange col_range(const chol_desc *d, int jlo, int jhi) {
-  jlo = std::min(jlo, d->nt), jhi = std::min(jhi, d->nt);
-  ColRange r;
-  r.off = d->ge[jhi];
-  r.na = d->ge[jlo] - d->ge[jhi];
-  r.offb = d->n_off + d->gd[jhi];
-  r.nb = d->gd[jlo] - d->gd[jhi];
-  return r;
-}
-
 // ---------------------------------------------------------------- product ops: HIP kernels and streams
 template <typename T>
 struct HipOps {

@@ -223,9 +223,6 @@ struct TraceOps {
     cost_of(add(1u << st, "SYRK(" + std::to_string(j) + "," + std::to_string(j) + ") by panel " + std::to_string(k), acc), 'Y', t_round());
     return 0;
   }
-  const char *ptile(const PanelRef &p, int i) const {
-    return (const char *)p.base[i % g.P] + (size_t)(i / g.P - p.first[i % g.P]) * g.tile_bytes;
-  }
   int update(int k1, int k2, int jlo, int jhi, int what, const PanelRef &p1, const PanelRef *p2, bool, int st) {
     const int nt = g.nt;
     jlo = std::min(jlo, nt), jhi = std::min(jhi, nt);
@@ -245,7 +242,7 @@ struct TraceOps {
     const PanelRef *ps[2] = {&p1, (p2 && k2 >= 0) ? p2 : nullptr};
     for (const PanelRef *p : ps)
       if (p)
-        for (int i : rows) touch(acc, ptile(*p, i), g.tile_bytes, false);
+        for (int i : rows) touch(acc, ptile(*p, i, g.tile_bytes), g.tile_bytes, false);
     char b[120];
     snprintf(b, sizeof b, "update columns [%d,%d) %sby panel %d%s", jlo, jhi, what == 3 ? "" : what == 1 ? "(off-diagonal) " : "(diagonal) ", k1,
              ps[1] ? (" and " + std::to_string(k2)).c_str() : "");

@@ -56,7 +56,7 @@ hipStream_t main_stream() { return main_rank_ctx()->st[ST_MAIN]; }
 // [jlo, jhi), from the given panels
 template <typename Launch, typename... Panels>
 void update_cols(Launch launch, const chol_desc *d, int jlo, int jhi, const Panels &...pans) {
-  const WorkRange rr = whole_col_range(d, jlo, jhi);
+  const ColRange rr = col_range(d, jlo, jhi);
   launch(main_stream(), whole_local_mat(d), d->d_list, rr.off, rr.na, rr.offb, rr.nb, pans...);
 }
 

@@ -21,6 +21,9 @@
 // launch on ST_U1 / ST_MAIN in the mid waves; and, once it is shorter than the chain and p = q = 1, the
 // counter-linked form (SyrkPipe: TRSM steps, SYRK slices and the next POTRF launched ahead of time, polling
 // device-side counters, no stream event on the chain).
+// Where things are: WavePlan / Walker::plan decide everything about one wave (ownership, regime, near / far boundary);
+// Walker::Carried is what a wave leaves for the next; Walker::run loops over the steps panel_phase, move_panel,
+// update_paired or update_plain, with start ahead and join_and_finish behind; Walker::update counts launches and flops.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -146,6 +149,30 @@ struct WaveComm {
     if (rc_) return rc_; \
   } while (0)
 
+// tile i of a panel: its address in bytes (cholmi_internal.h: PanelRef)
+inline const char *ptile(const PanelRef &p, int i, size_t tile_bytes) {
+  return (const char *)p.base[i % p.P] + (size_t)(i / p.P - p.first[i % p.P]) * tile_bytes;
+}
+
+// What is decided for wave k.  Walker::plan fills it from the geometry, the calibration, the switches, the Ops'
+// capabilities and what the earlier waves left (Walker::Carried); the steps of the wave only read it.
+struct WavePlan {
+  int k = 0;
+  // grid ownership: (k,k) in my process column / mine, no wave behind this one, (k+1,k+1) mine
+  bool in_col = false, own_diag = false, last = false, next_diag_mine = false;
+  int il0m = 0, cntm = 0;  // this rank's tiles of panel k: first local row and count (0 outside that process column)
+  int local_tiles = 0;     // this rank's tiles of wave k's update
+  // the regime (what each is: Walker::plan)
+  bool paired = false, odd = false;  // panels in pairs; this is the second wave of its pair
+  bool pipe = false, pipe_local = false, flow = false;
+  bool yield = false, split = false, halves = false, near1 = false, u1s = false;
+  // plain waves: the near / far boundary, whether this wave moved it, whether far(k) has to wait for near(k-1)
+  int bnd = -1;
+  bool moved = false, far_behind_near = false;
+  // plain waves: this rank's tiles of column k+1 below / on the diagonal, and of the columns beyond
+  int n_r1o = 0, n_r1d = 0, tiles2 = 0;
+};
+
 // Ops: see HipOps / CbOps in dist.hip.  What the walker asks of it:
 //   bool counters() const                  device-side counters usable (SyrkPipe); pipe_ok(): ... and the kernels' switches allow it
 //   bool profiling() const, can_split_trsm() const
@@ -181,14 +208,34 @@ struct Walker {
   enum { R_PAIRED, R_PLAIN, R_HALVES, R_PIPE, R_NEAR1, R_FLOW, R_YIELD, R_U1SMALL, R_COUNT };
   int regimes[R_COUNT] = {};
   std::vector<int> halves_waves;
+  // fixed for one factorisation (start)
+  std::chrono::steady_clock::time_point t_host0;
+  int sem_per_wave = 0;  // SyrkPipe's counters, the flow's control block
+  bool prof = false, flags = false, flags_local = false, flow_run = false;
+  // What a wave leaves for the waves behind it: who sets it -> who reads it
+  struct Carried {
+    bool paired = false;        // run, from the plan of the first wave of a pair -> plan of the second
+    bool had_pairs = false;     // update_paired -> update_paired: the first pair behind plain waves waits for their far launch
+    bool cols_pending = false;  // update_paired, odd wave -> update_plain: the first plain wave after the paired phase waits
+                                // for F_COLS, since Cb of the last pair wrote column k+2
+    int open_bracket = -1;      // update_paired: the odd wave whose profiling bracket is still open -> whoever closes it:
+                                // update_paired (next even wave), update_plain, join_and_finish
+    int bnd = -1;               // update_plain: the near / far boundary -> plan
+    bool prev_halves = false;   // update_plain: the wave went out as halves (update_paired clears it) -> plan, panel_phase,
+                                // update_paired, update_plain
+    bool prev_flow = false;     // panel_phase: the wave's tile POTRF ran in flow form -> panel_phase (join_flow)
+    // panel_phase -> panel_phase.  The next wave switches to the flow form: its row-slab kernel's stream joins the POTRF
+    // stream's order NOW, a whole wave ahead, so that the event's wake-up (15-30 us) is not on the first flow wave's chain.
+    // (Only behind a counter-linked wave: the row-slab kernel then polls the same counter as the POTRF's first kernel.)
+    bool flow_joined = false;
+    const int *wait_sem = nullptr;  // panel_phase -> panel_phase: what the next wave's first diagonal-block step polls, when
+    int wait_target = 0;            // this wave raised it (counter-linked), and what it counts to
+  } c;
 
-  Walker(O &ops, const WaveGeo &geo, WaveComm *comm, const WaveCalib &c) : o(ops), g(geo), cm(comm), cal(c) {}
+  Walker(O &ops, const WaveGeo &geo, WaveComm *comm, const WaveCalib &cl) : o(ops), g(geo), cm(comm), cal(cl) {}
   int ev(int k, int which) const { return E_PER_WAVE * k + which; }
   int fx(int which) const { return E_PER_WAVE * g.nt + which; }
   bool multi() const { return g.P * g.Q > 1; }
-  const char *ptile(const PanelRef &p, int i) const {
-    return (const char *)p.base[i % g.P] + (size_t)(i / g.P - p.first[i % g.P]) * g.tile_bytes;
-  }
 
   int setup() {
     if (!multi()) return 0;
@@ -339,383 +386,407 @@ struct Walker {
     return o.rec(ev(k, E_PANEL), ST_PX);
   }
 
-  int run(long long *info_out) {
-    const auto t_host0 = std::chrono::steady_clock::now();
-    const int nt = g.nt, mb = g.mb, nbm = g.nbm, P = g.P, Q = g.Q;
-    const bool mr = multi();
-    const int sem_per_wave = 3 * nbm + 1 + flow_ctl_lines(nbm);  // SyrkPipe's counters, the flow's control block
-    WRC(o.begin(E_PER_WAVE * nt + F_FIXED + nbm + 1, nt, sem_per_wave));
-    const int ev_steps = fx(F_FIXED);
+  // ---- one factorisation: start; per wave plan, panel_phase, move_panel, update_paired or update_plain; join_and_finish
+  int start() {
+    t_host0 = std::chrono::steady_clock::now();
+    sem_per_wave = 3 * g.nbm + 1 + flow_ctl_lines(g.nbm);
+    WRC(o.begin(E_PER_WAVE * g.nt + F_FIXED + g.nbm + 1, g.nt, sem_per_wave));
     WRC(o.rec(fx(F_START), ST_MAIN));
-    for (int st = ST_PANEL; st < (mr ? ST_COUNT : ST_CX + 1); ++st) WRC(o.wt(st, fx(F_START)));  // (their kernels may poll counters zeroed on ST_MAIN; ST_CX: the flow's row-slab kernel)
-    bool paired = false, cols_pending = false, had_pairs = false;
-    int open_bracket = -1;  // odd wave whose profiling bracket is still open
-    int bnd = -1;
-    bool prev_halves = false, prev_flow = false, flow_joined = false;
-    const bool flags = !mr && o.counters();
+    for (int st = ST_PANEL; st < (multi() ? ST_COUNT : ST_CX + 1); ++st) WRC(o.wt(st, fx(F_START)));  // (their kernels may poll counters zeroed on ST_MAIN; ST_CX: the flow's row-slab kernel)
+    flags = !multi() && o.counters();
     // On a grid only ONE of the chain's edges is local to a rank: POTRF steps -> its own panel tiles' TRSM steps, on the
     // owner of (k,k).  (The other -- last SYRK slice -> next POTRF -- never is: tile (k+1,k+1) belongs to another rank.)
     // That edge runs on counters too (round 4): the TRSM steps are launched ahead and poll D[s] / I[s] instead of waiting
     // for an event per step; everything that crosses a transport call stays an event.
-    const bool flags_local = mr && o.counters();
+    flags_local = multi() && o.counters();
     // (1.0 panel estimates: N <= ~9000-10000 at tile 512 -- with the near column and the latency-form column update of
     // round 4 the form gains 7 % at N = 8192 and nothing at 12288; at 0.7 the rule flipped at 8192 with the box's calibration)
-    const bool flow_run = (double)g.tiles_in(1, nt) * cal.t_tile < sw.flow_run_fac * cal.t_panel;
-    const int *wait_sem = nullptr;  // what this wave's first diagonal-block step polls, when the last wave raised it
-    int wait_target = 0;
-    const double b3 = (double)mb * mb * mb;
+    flow_run = (double)g.tiles_in(1, g.nt) * cal.t_tile < sw.flow_run_fac * cal.t_panel;
+    prof = o.profiling();
+    c = Carried();
+    return 0;
+  }
+
+  // may the tile POTRF of a wave whose update has `local_tiles` tiles run as a flow (kernels.hip: k_flow_factor)?  When the
+  // WHOLE factorisation is chain-bound (wave 0 already is): measured round 4, the form gains 14-17 % there (tile 512,
+  // N <= 4096) and nothing when only the last waves of a larger matrix use it -- the wave that switches forms pays ~90 us,
+  // the rest gains ~40 us each (CHOLMI_FLOW_FACTOR = f > 0: instead, every wave whose update is shorter than f panel estimates)
+  bool flow_form(int local_tiles) const {
+    return flow_ctl_lines(g.nbm) > 0 && o.flow_ok() && flow_applies(g.nbm) &&
+           (sw.flow_fac > 0 ? (double)local_tiles * cal.t_tile < sw.flow_fac * cal.t_panel : flow_run);
+  }
+
+  WavePlan plan(int k) const {
+    const int nt = g.nt, nbm = g.nbm;
     const double t_tile = cal.t_tile, t_panel = cal.t_panel;
-    const bool prof = o.profiling();
-    for (int k = 0; k < nt; ++k) {
-      const int dr = k % P, dc = k % Q, par = k & 1;
-      const bool in_col = g.pc == dc, own_diag = in_col && g.pr == dr, last = k + 1 >= nt;
-      int il0m = 0, cntm = 0;
-      g.part(k, g.pr, &il0m, &cntm);
-      if (!in_col) cntm = 0;
-      // ---- panel k: POTRF on the owner of (k,k), the TRSM steps of its own panel tiles pipelined behind it;
-      // the other ranks of the process column solve theirs once L(k,k) has arrived  (C2:510-535)
-      // (ST_TRSM needs no event for the start of the wave: its first step waits for the event recorded on
-      // ST_PANEL behind the first diagonal-block step, and a record on ST_PANEL costs the chain ~7 us)
-      const int local_tiles = g.tiles_in(k + 1, nt);  // this rank's tiles of wave k's update
-      const bool pair_first = k >= PAIR_START && ((k - PAIR_START) & 1) == 0;
-      if (pair_first)
-        paired = mb <= PAIR_MAX_MB && k + 2 < nt && (double)local_tiles * t_tile >= sw.pair_fac * t_panel;
-      // Plain (unpaired) wave whose panel chain is (nearly) critical: the SYRK on tile (k+1,k+1) follows the
-      // head tile's TRSM steps slice by slice and the chain's cross-stream edges are device-side counters
-      // (only while the update is shorter than about a panel chain: the polling workgroups hold CU slots the
-      // update would otherwise use -- measured +10 ... +20 % on the waves between pipe_fac and the yield threshold)
-      const bool plain_yield = (double)local_tiles * t_tile < sw.yfac * t_panel;
-      const bool chain_bound = (double)local_tiles * t_tile < sw.pipe_fac * t_panel;
-      const bool pipe = flags && !paired && !last && o.pipe_ok() && plain_yield && chain_bound;
-      const bool pipe_local = flags_local && !paired && o.pipe_ok() && plain_yield && chain_bound && own_diag && cntm > 0;
-      // ... with its tile POTRF as a flow (kernels.hip: k_flow_factor) when the WHOLE factorisation is chain-bound (wave 0
-      // already is): measured round 4, the form gains 14-17 % there (tile 512, N <= 4096) and nothing when only the last
-      // waves of a larger matrix use it -- the wave that switches forms pays ~90 us, the rest gains ~40 us each
-      // (CHOLMI_FLOW_FACTOR = f > 0: instead, every wave whose update is shorter than f panel estimates)
-      const bool flow = pipe && own_diag && cntm > 0 && flow_ctl_lines(nbm) > 0 && o.flow_ok() && flow_applies(nbm) &&
-                        (sw.flow_fac > 0 ? (double)local_tiles * t_tile < sw.flow_fac * t_panel : flow_run);
-      if (k > 0 && in_col) WRC(o.wt(ST_TRSM, ev(k - 1, E_U1R)));
-      // block inverses of L(k,k): two workspaces alternating by wave, so that POTRF(k+1) may overwrite its
-      // set while TRSM(k) still reads the other
-      const char *head = nullptr;
-      if (own_diag) {
-        char *lkk = o.tile(k / P, k / Q);
-        SyrkPipe sy;
-        if (pipe_local) {
-          sy.c = nullptr;  // (no SYRK slices: the next diagonal tile is another rank's)
-          sy.su = nullptr;
-          sy.sem = o.sem(k, 0, sem_per_wave);
-        }
-        if (pipe) {
-          // the tile's earlier writers: U2(k-1), whose range includes column k+1 (or, behind the paired
-          // phase, the column launches of the last pair, which precede this on ST_U1)
-          // (... or near(k-1): column k+1 alone, on this very stream)
-          if (k > 0 && !prev_halves) WRC(o.wt(ST_U1, ev(k - 1, E_U2)));
-          sy.c = o.tile((k + 1) / P, (k + 1) / Q);
-          sy.su = (hipStream_t)o.stream(ST_U1);
-          sy.sem = o.sem(k, 0, sem_per_wave);
-          if (flow) {
-            sy.fc = o.sem(k, 3 * nbm + 1, sem_per_wave);
-            sy.sflow = (hipStream_t)o.stream(ST_CX);
-            sy.ev_flow = (hipEvent_t)o.flow_event();
-            // The row-slab kernel (ST_CX) reads its rows of tile (k,k).  Behind another flow wave it follows that wave's
-            // row-slab kernel in stream order and polls the counter the POTRF's first kernel polls (the last SYRK slice
-            // of wave k-1, the tile's last writer).  Otherwise its stream joins the POTRF stream's order by an event --
-            // unless that happened a wave ahead (flow_joined, below) AND this wave polls that counter: without a counter
-            // to poll (the wave before was not counter-linked) the event is the only thing that orders it.
-            sy.join_flow = !prev_flow && (wait_sem == nullptr || !flow_joined);
-          }
-        }
-        // the head tile is this rank's first panel tile only when there is one process row
-        const bool head_mine = !last && P == 1;
-        WRC(o.panel(k, lkk, o.winv(par), lkk + g.tile_bytes, cntm, ev_steps, head_mine ? ev(k, E_HEAD) : -1,
-                    pipe || pipe_local ? &sy : nullptr, wait_sem, wait_target));
-        if (mr && P > 1 && !last) {
-          WRC(o.rec(ev(k, E_LKK), ST_PANEL));
-          WRC(diag_send(k, lkk, (const char *)o.winv(par)));
-        }
-        // the next wave switches to the flow form: its row-slab kernel's stream joins the POTRF stream's order NOW, a
-        // whole wave ahead, so that the event's wake-up (15-30 us) is not on the first flow wave's chain.  (Only behind
-        // a counter-linked wave: the row-slab kernel then polls the same counter as the POTRF's first kernel.)
-        if (pipe && !flow && !flow_joined && !mr && k + 2 < nt && flow_ctl_lines(nbm) > 0 && o.flow_ok() && flow_applies(nbm) &&
-            (sw.flow_fac > 0 ? (double)g.tiles_in(k + 2, nt) * t_tile < sw.flow_fac * t_panel : flow_run)) {
-          WRC(o.rec(fx(F_FLOWJ), ST_PANEL));
-          WRC(o.wt(ST_CX, fx(F_FLOWJ)));
-          flow_joined = true;
-        }
-      } else if (in_col && cntm > 0) {
-        WRC(diag_recv(k));
-        WRC(o.wt(ST_TRSM, ev(k, E_LKKR)));
-        char *tiles = o.tile(il0m, k / Q);
-        const char *lkk = lkk_buf[par], *wv = lkk_buf[par] + g.tile_bytes;
-        const bool head_mine = !last && g.pr == (k + 1) % P;  // my first tile is L(k+1,k)
-        if (head_mine && cntm > 1 && o.can_split_trsm()) {
-          WRC(o.trsm(k, tiles, 1, lkk, wv, ST_TRSM));
-          WRC(o.rec(ev(k, E_HEAD), ST_TRSM));
-          WRC(o.trsm(k, tiles + g.tile_bytes, cntm - 1, lkk, wv, ST_TRSM));
-        } else {
-          WRC(o.trsm(k, tiles, cntm, lkk, wv, ST_TRSM));
-          if (head_mine) WRC(o.rec(ev(k, E_HEAD), ST_TRSM));
+    WavePlan pl;
+    pl.k = k;
+    pl.in_col = g.pc == k % g.Q, pl.own_diag = pl.in_col && g.pr == k % g.P, pl.last = k + 1 >= nt;
+    g.part(k, g.pr, &pl.il0m, &pl.cntm);
+    if (!pl.in_col) pl.cntm = 0;
+    pl.next_diag_mine = g.rank_of((k + 1) % g.P, (k + 1) % g.Q) == g.rank;
+    pl.local_tiles = g.tiles_in(k + 1, nt);
+    const bool pair_first = k >= PAIR_START && ((k - PAIR_START) & 1) == 0;
+    pl.paired = pair_first ? g.mb <= PAIR_MAX_MB && k + 2 < nt && (double)pl.local_tiles * t_tile >= sw.pair_fac * t_panel : c.paired;
+    pl.odd = !pair_first;
+    // Plain (unpaired) wave whose panel chain is (nearly) critical: the SYRK on tile (k+1,k+1) follows the
+    // head tile's TRSM steps slice by slice and the chain's cross-stream edges are device-side counters
+    // (only while the update is shorter than about a panel chain: the polling workgroups hold CU slots the
+    // update would otherwise use -- measured +10 ... +20 % on the waves between pipe_fac and the yield threshold)
+    const bool plain_yield = (double)pl.local_tiles * t_tile < sw.yfac * t_panel;
+    const bool chain_bound = (double)pl.local_tiles * t_tile < sw.pipe_fac * t_panel;
+    pl.pipe = flags && !pl.paired && !pl.last && o.pipe_ok() && plain_yield && chain_bound;
+    pl.pipe_local = flags_local && !pl.paired && o.pipe_ok() && plain_yield && chain_bound && pl.own_diag && pl.cntm > 0;
+    // ... with its tile POTRF as a flow
+    pl.flow = pl.pipe && pl.own_diag && pl.cntm > 0 && flow_form(pl.local_tiles);
+    if (pl.last) return pl;
+    if (pl.paired) {
+      const int wave_tiles = g.tiles_in(k + 1, k + 2) + (pl.odd ? g.tiles_in(k + 2, nt) : 0);
+      pl.yield = (double)wave_tiles * t_tile * (pl.odd ? 2 : 1) < sw.yfac * t_panel * (pl.odd ? 2 : 1);
+      return pl;
+    }
+    pl.n_r1o = g.off_in(k + 1, k + 2), pl.n_r1d = g.diag_in(k + 1, k + 2);
+    pl.tiles2 = g.tiles_in(k + 2, nt);
+    // Give CUs to the next panel's guest workgroups only when that panel is on the critical path, i.e. when
+    // this wave's update is not much longer than a panel; otherwise the polling is pure cost.
+    pl.yield = (double)(pl.n_r1o + pl.n_r1d + pl.tiles2) * t_tile < sw.yfac * t_panel;
+    pl.split = pl.yield;
+    // Plain waves of a few rounds of workgroups: the columns beyond k+1 go out as TWO launches, the near
+    // columns [k+2, bnd) on ST_U1 behind the column-(k+1) launch and the far ones [bnd, nt) on ST_MAIN.
+    // With a boundary that stays put for several waves each half depends on its own predecessor only
+    // (far(k+1) is a subset of far(k), near(k+1) of near(k)), so the last, partly filled round of one launch
+    // runs beside full rounds of the other chain's next launch instead of beside nothing; and column k+1 --
+    // the next panel -- waits for near(k-1) only.  The boundary moves (then near(k) also waits for far(k-1))
+    // when the near part has shrunk under 30 % of the wave.
+    pl.halves = sw.halves_max_rounds > 0 && !pl.pipe && pl.split && nt - 1 - k >= 6 &&
+                (double)pl.tiles2 * nbm * nbm / 512.0 < sw.halves_max_rounds;
+    // Counter-linked waves (CHOLMI_PIPE_NEAR): the near half is column k+2 alone, every wave.  The SYRK slices of the
+    // NEXT wave (tile (k+2,k+2), on ST_U1) then follow near(k) in stream order instead of waiting for the whole far
+    // update of this wave, which started only when this panel was complete: the chain looks two columns ahead.
+    pl.near1 = pl.pipe && pl.split && k + 3 < nt && (double)pl.local_tiles * t_tile < sw.near_fac * t_panel;
+    pl.bnd = c.bnd;
+    if (pl.near1) {
+      pl.halves = true;
+      pl.far_behind_near = c.prev_halves && c.bnd > k + 3;  // (from the wider halves of the waves before)
+      pl.bnd = k + 3;
+      pl.moved = true;
+    } else if (pl.halves) {
+      if (!c.prev_halves || c.bnd <= k + 2 || g.tiles_in(k + 2, c.bnd) * 10 < pl.tiles2 * 3) {
+        int b = k + 3;
+        while (b < nt - 1 && g.tiles_in(k + 2, b) * 2 < pl.tiles2) ++b;
+        // (the boundary only ever moves right, far(k) stays a subset of far(k-1); should it not, far(k)
+        // waits for near(k-1) as well)
+        pl.far_behind_near = c.prev_halves && b < c.bnd;
+        pl.bnd = b;
+        pl.moved = true;
+      }
+      if (pl.bnd >= nt) pl.halves = false;
+    }
+    if (c.prev_halves && !pl.halves) pl.far_behind_near = true;  // U2(k) covers near(k-1)'s columns
+    // (... of tiles up to 512: with 1024 tiles the form lost 2-4 % -- 256 workgroups per tile, K = 1024 each)
+    pl.u1s = pl.pipe && !multi() && nbm <= 4 && pl.n_r1o > 0 && pl.n_r1o <= sw.u1_small_max;
+    return pl;
+  }
+
+  // o.update with its accounting: one k_trail_update launch when this rank has tiles of the kinds `what` names in the
+  // range, and their algorithmic flops per panel applied: GEMM 2 B^3 per off-diagonal tile, SYRK B^3 per diagonal tile
+  // (SURVEY 8d).  (The one-tile SYRKs of diag_syrk and the latency form of column k+1 are not k_trail_update launches.)
+  int update(int k1, int k2, int jlo, int jhi, int what, const PanelRef &p1, const PanelRef *p2, bool yield, int st) {
+    WRC(o.update(k1, k2, jlo, jhi, what, p1, p2, yield, st));
+    const int n_off = (what & 1) ? g.off_in(jlo, jhi) : 0, n_diag = (what & 2) ? g.diag_in(jlo, jhi) : 0;
+    if (n_off + n_diag > 0) {
+      ++upd_launches;
+      upd_flops += (2.0 * n_off + n_diag) * (p2 ? 2 : 1) * ((double)g.mb * g.mb * g.mb);
+    }
+    return 0;
+  }
+
+  // ---- panel k: POTRF on the owner of (k,k), the TRSM steps of its own panel tiles pipelined behind it;
+  // the other ranks of the process column solve theirs once L(k,k) has arrived  (C2:510-535)
+  // (ST_TRSM needs no event for the start of the wave: its first step waits for the event recorded on
+  // ST_PANEL behind the first diagonal-block step, and a record on ST_PANEL costs the chain ~7 us)
+  int panel_phase(const WavePlan &pl) {
+    const int k = pl.k, P = g.P, Q = g.Q, nbm = g.nbm, par = k & 1;
+    if (k > 0 && pl.in_col) WRC(o.wt(ST_TRSM, ev(k - 1, E_U1R)));
+    // block inverses of L(k,k): two workspaces alternating by wave, so that POTRF(k+1) may overwrite its
+    // set while TRSM(k) still reads the other
+    if (pl.own_diag) {
+      char *lkk = o.tile(k / P, k / Q);
+      SyrkPipe sy;
+      if (pl.pipe_local) {
+        sy.c = nullptr;  // (no SYRK slices: the next diagonal tile is another rank's)
+        sy.su = nullptr;
+        sy.sem = o.sem(k, 0, sem_per_wave);
+      }
+      if (pl.pipe) {
+        // the tile's earlier writers: U2(k-1), whose range includes column k+1 (or, behind the paired
+        // phase, the column launches of the last pair, which precede this on ST_U1)
+        // (... or near(k-1): column k+1 alone, on this very stream)
+        if (k > 0 && !c.prev_halves) WRC(o.wt(ST_U1, ev(k - 1, E_U2)));
+        sy.c = o.tile((k + 1) / P, (k + 1) / Q);
+        sy.su = (hipStream_t)o.stream(ST_U1);
+        sy.sem = o.sem(k, 0, sem_per_wave);
+        if (pl.flow) {
+          sy.fc = o.sem(k, 3 * nbm + 1, sem_per_wave);
+          sy.sflow = (hipStream_t)o.stream(ST_CX);
+          sy.ev_flow = (hipEvent_t)o.flow_event();
+          // The row-slab kernel (ST_CX) reads its rows of tile (k,k).  Behind another flow wave it follows that wave's
+          // row-slab kernel in stream order and polls the counter the POTRF's first kernel polls (the last SYRK slice
+          // of wave k-1, the tile's last writer).  Otherwise its stream joins the POTRF stream's order by an event --
+          // unless that happened a wave ahead (flow_joined, below) AND this wave polls that counter: without a counter
+          // to poll (the wave before was not counter-linked) the event is the only thing that orders it.
+          sy.join_flow = !c.prev_flow && (c.wait_sem == nullptr || !c.flow_joined);
         }
       }
-      // with device-side edges ST_PANEL waits for no event between waves: POTRF(k+1)'s first step polls the
-      // last slice's counter, which also stands behind TRSM(k) (same stream, earlier), so POTRF(k+2) may
-      // reuse TRSM(k)'s workspace
-      const bool by_flags = pipe;
-      prev_flow = flow;
-      if (flow) ++flow_waves, ++regimes[R_FLOW];
-      if (pipe || pipe_local) ++regimes[R_PIPE];
-      wait_sem = by_flags ? o.sem(k, 3 * nbm, sem_per_wave) : nullptr;
-      wait_target = (mb / 64) * (mb / 64 + 1) / 2;
-      // TRSM(k) complete on this rank
-      if (in_col) WRC(o.rec(ev(k, mr ? E_TRSM : E_PANEL), ST_TRSM));
-      if (own_diag && !by_flags) {
-        WRC(o.wt(ST_PANEL, ev(k, mr ? E_TRSM : E_PANEL)));  // POTRF(k+2) overwrites this wave's block inverses
-        if (mr && P > 1 && !last) WRC(o.wt(ST_PANEL, ev(k, E_CXS)));  // ... which also travel
+      // the head tile is this rank's first panel tile only when there is one process row
+      const bool head_mine = !pl.last && P == 1;
+      WRC(o.panel(k, lkk, o.winv(par), lkk + g.tile_bytes, pl.cntm, fx(F_FIXED), head_mine ? ev(k, E_HEAD) : -1,
+                  pl.pipe || pl.pipe_local ? &sy : nullptr, c.wait_sem, c.wait_target));
+      if (multi() && P > 1 && !pl.last) {
+        WRC(o.rec(ev(k, E_LKK), ST_PANEL));
+        WRC(diag_send(k, lkk, (const char *)o.winv(par)));
       }
-      if (last) break;
-      if (mr) {
-        WRC(head_move(k, &head));
-        WRC(exchange(k));
+      // the wave after next switches to the flow form: join its stream now (Carried::flow_joined)
+      if (pl.pipe && !pl.flow && !c.flow_joined && !multi() && k + 2 < g.nt && flow_form(g.tiles_in(k + 2, g.nt))) {
+        WRC(o.rec(fx(F_FLOWJ), ST_PANEL));
+        WRC(o.wt(ST_CX, fx(F_FLOWJ)));
+        c.flow_joined = true;
+      }
+    } else if (pl.in_col && pl.cntm > 0) {
+      WRC(diag_recv(k));
+      WRC(o.wt(ST_TRSM, ev(k, E_LKKR)));
+      char *tiles = o.tile(pl.il0m, k / Q);
+      const char *lkk = lkk_buf[par], *wv = lkk_buf[par] + g.tile_bytes;
+      const bool head_mine = !pl.last && g.pr == (k + 1) % P;  // my first tile is L(k+1,k)
+      if (head_mine && pl.cntm > 1 && o.can_split_trsm()) {
+        WRC(o.trsm(k, tiles, 1, lkk, wv, ST_TRSM));
+        WRC(o.rec(ev(k, E_HEAD), ST_TRSM));
+        WRC(o.trsm(k, tiles + g.tile_bytes, pl.cntm - 1, lkk, wv, ST_TRSM));
       } else {
-        PanelRef &p = pan[k % NBUF];
-        memset(&p, 0, sizeof p);
-        p.P = 1;
-        p.base[0] = o.tile(0, k);
-        head = o.tile(k + 1, k);
+        WRC(o.trsm(k, tiles, pl.cntm, lkk, wv, ST_TRSM));
+        if (head_mine) WRC(o.rec(ev(k, E_HEAD), ST_TRSM));
       }
-      const PanelRef &pk = pan[k % NBUF];
-      const bool next_diag_mine = g.rank_of((k + 1) % P, (k + 1) % Q) == g.rank;
-      char *ckk = next_diag_mine ? o.tile((k + 1) / P, (k + 1) / Q) : nullptr;
-      // ---- trailing update (C2:540-560)
-      if (paired) {
-        // Panels in pairs (k-1, k), k odd: the far columns' update by the even panel is deferred and applied
-        // together with the odd one in ONE pass of twice the K (k_trail_update, npan = 2).
-        //   even k:  U1(k)  = column k+1 by panel k                                       (ST_U1)
-        //   odd  k:  U1'(k) = column k+1, Ca = column k+2, Cb = column k+3 by panels k-1, k  (ST_U1, in this order)
-        //            big(k) = the columns from k+4 on by panels k-1, k                      (ST_MAIN, beside them)
-        // Every column is written by launches of ST_U1 in program order, except by big(); the first launches
-        // of ST_U1 on a column big(k) covers are Ca / Cb of wave k+2, which wait for it.  POTRF(k+1) waits
-        // for the SYRKs on (k+1,k+1) only, TRSM(k+1) for the rest of column k+1.
-        const bool odd = !pair_first;
-        // the first pair behind plain waves: their far launch (ST_MAIN) wrote the columns ST_U1 is about to touch
-        if (!odd && k > 0 && !had_pairs) WRC(o.wt(ST_U1, ev(k - 1, E_U2)));
-        if (prev_halves) {  // ... and their near launch (ST_U1) the columns ST_MAIN is about to touch
-          WRC(o.wt(ST_MAIN, ev(k - 1, E_NEAR)));
-          prev_halves = false;
-        }
-        const PanelRef &prev = pan[(odd ? k - 1 : k) % NBUF];
-        const PanelRef *p2 = odd ? &pk : nullptr;  // launches: first `prev`, then `pk` when odd
-        const PanelRef &p1 = odd ? prev : pk;
-        const int k1 = odd ? k - 1 : k, k2 = odd ? k : -1;
-        const int n_c1 = g.tiles_in(k + 1, k + 2), n_ca = g.tiles_in(k + 2, k + 3), n_cb = g.tiles_in(k + 3, k + 4),
-                  n_big = g.tiles_in(k + 4, nt);
-        const int wave_tiles = n_c1 + (odd ? n_ca + n_cb + n_big : 0);
-        const bool yield = (double)wave_tiles * t_tile * (odd ? 2 : 1) < sw.yfac * t_panel * (odd ? 2 : 1);
-        if (next_diag_mine) {
-          if (odd) WRC(o.diag_syrk(k - 1, k + 1, ckk, ptile(prev, k + 1), ST_U1));
-          WRC(o.wt(ST_U1, ev(k, E_HEAD)));  // the head tile L(k+1,k) is all the last SYRK needs
-          WRC(o.diag_syrk(k, k + 1, ckk, head, ST_U1));
-          WRC(o.rec(ev(k, E_U1D), ST_U1));
-          WRC(o.wt(ST_PANEL, ev(k, E_U1D)));
-        }
-        WRC(o.wt(ST_U1, ev(k, E_PANEL)));
-        if (!odd && open_bracket < 0 && prof) WRC(o.rec(ev(k, E_P0), ST_U1));
-        WRC(o.update(k1, k2, k + 1, k + 2, 1, p1, p2, yield, ST_U1));
-        WRC(o.rec(ev(k, E_U1R), ST_U1));
-        int timed = 0;
-        double fl = 0;
-        const int o_c1 = g.off_in(k + 1, k + 2);
-        if (odd) {
-          if (o_c1 > 0) ++timed, fl += 2.0 * o_c1;
-          if (k >= 2) WRC(o.wt(ST_U1, ev(k - 2, E_U2)));  // big(k-2) covered these columns
-          WRC(o.update(k1, k2, k + 2, k + 3, 3, p1, p2, yield, ST_U1));
-          WRC(o.update(k1, k2, k + 3, k + 4, 3, p1, p2, yield, ST_U1));
-          if (n_ca > 0) ++timed, fl += 2.0 * g.off_in(k + 2, k + 3) + g.diag_in(k + 2, k + 3);
-          if (n_cb > 0) ++timed, fl += 2.0 * g.off_in(k + 3, k + 4) + g.diag_in(k + 3, k + 4);
-          WRC(o.rec(fx(F_COLS), ST_U1));
-          cols_pending = true;
-          WRC(o.wt(ST_MAIN, ev(k, E_PANEL)));
-          if (prof) WRC(o.rec(ev(k, E_P0), ST_MAIN));
-          WRC(o.update(k1, k2, k + 4, nt, 3, p1, p2, yield, ST_MAIN));
-          if (n_big > 0) ++timed, fl += 2.0 * g.off_in(k + 4, nt) + g.diag_in(k + 4, nt);
-          WRC(o.rec(ev(k, E_U2), ST_MAIN));
-          // the bracket [P0(k), P1(k)] covers every k_trail_update launch of the pair's update: the
-          // two-panel launches of this wave, which start together, and U1(k+1), which runs beside
-          // big(k); it is closed at the next wave
-          open_bracket = k;
-          upd_launches += timed;
-          upd_flops += 2.0 * fl * b3;  // two panels per pass
-        } else {
-          WRC(o.rec(ev(k, E_U2), ST_MAIN));
-          if (prof) {
-            if (open_bracket >= 0) {
-              // waiting for the column launches and for U1(k) on ST_MAIN constrains nothing: big(k+1)
-              // needs panel k+1, which comes after all of them
-              WRC(o.wt(ST_MAIN, fx(F_COLS)));
-              WRC(o.wt(ST_MAIN, ev(k, E_U1R)));
-              WRC(o.rec(ev(open_bracket, E_P1), ST_MAIN));
-              WRC(o.rec(ev(k, E_P0), ST_MAIN));
-              WRC(o.rec(ev(k, E_P1), ST_MAIN));
-            } else {
-              WRC(o.rec(ev(k, E_P1), ST_U1));  // the very first wave: U1(0) alone, bracketed on its stream
-            }
-          }
-          open_bracket = -1;
-          if (o_c1 > 0) ++upd_launches, upd_flops += 2.0 * o_c1 * b3;
-        }
-        had_pairs = true;
-        ++regimes[R_PAIRED];
-        if (yield) ++regimes[R_YIELD];
-        if (mr) WRC(o.rec(ev(k, E_SU), ST_U1));
-        continue;
-      }
-      if (open_bracket >= 0) {  // the paired phase ended on an odd wave: close its bracket
-        if (prof) {
-          WRC(o.wt(ST_MAIN, fx(F_COLS)));
-          WRC(o.rec(ev(open_bracket, E_P1), ST_MAIN));
-        }
-        open_bracket = -1;
-      }
-      const int n_r1o = g.off_in(k + 1, k + 2), n_r1d = g.diag_in(k + 1, k + 2);
-      const int n_r2o = g.off_in(k + 2, nt), n_r2d = g.diag_in(k + 2, nt);
-      // Give CUs to the next panel's guest workgroups only when that panel is on the critical path, i.e. when
-      // this wave's update is not much longer than a panel; otherwise the polling is pure cost.
-      const bool yield = (double)(n_r1o + n_r1d + n_r2o + n_r2d) * t_tile < sw.yfac * t_panel;
-      const bool split = yield;
-      // the SYRK on (k+1,k+1) needs the head tile L(k+1,k) only; everything else the whole panel
-      if (!pipe) {
-        if (!split) WRC(o.wt(ST_U1, ev(k, E_PANEL)));
-        else if (next_diag_mine) WRC(o.wt(ST_U1, ev(k, E_HEAD)));
-      }
-      if (cols_pending) {  // first plain wave after the paired phase: Cb of the last pair wrote column k+2
-        WRC(o.wt(ST_MAIN, fx(F_COLS)));
-        cols_pending = false;
-      }
-      // Plain waves of a few rounds of workgroups: the columns beyond k+1 go out as TWO launches, the near
-      // columns [k+2, bnd) on ST_U1 behind the column-(k+1) launch and the far ones [bnd, nt) on ST_MAIN.
-      // With a boundary that stays put for several waves each half depends on its own predecessor only
-      // (far(k+1) is a subset of far(k), near(k+1) of near(k)), so the last, partly filled round of one launch
-      // runs beside full rounds of the other chain's next launch instead of beside nothing; and column k+1 --
-      // the next panel -- waits for near(k-1) only.  The boundary moves (then near(k) also waits for far(k-1))
-      // when the near part has shrunk under 30 % of the wave.
-      const int tiles2 = n_r2o + n_r2d;
-      bool halves = sw.halves_max_rounds > 0 && !pipe && split && nt - 1 - k >= 6 &&
-                    (double)tiles2 * nbm * nbm / 512.0 < sw.halves_max_rounds;
-      // Counter-linked waves (CHOLMI_PIPE_NEAR): the near half is column k+2 alone, every wave.  The SYRK slices of the
-      // NEXT wave (tile (k+2,k+2), on ST_U1) then follow near(k) in stream order instead of waiting for the whole far
-      // update of this wave, which started only when this panel was complete: the chain looks two columns ahead.
-      const bool near1 = pipe && split && k + 3 < nt && (double)local_tiles * t_tile < sw.near_fac * t_panel;
-      bool moved = false;
-      if (near1) {
-        halves = true;
-        if (prev_halves && bnd > k + 3) WRC(o.wt(ST_MAIN, ev(k - 1, E_NEAR)));  // (from the wider halves of the waves before)
-        bnd = k + 3;
-        moved = true;
-      } else if (halves) {
-        if (!prev_halves || bnd <= k + 2 || g.tiles_in(k + 2, bnd) * 10 < tiles2 * 3) {
-          int b = k + 3;
-          while (b < nt - 1 && g.tiles_in(k + 2, b) * 2 < tiles2) ++b;
-          // (the boundary only ever moves right, far(k) stays a subset of far(k-1); should it not, far(k)
-          // waits for near(k-1) as well)
-          if (prev_halves && b < bnd) WRC(o.wt(ST_MAIN, ev(k - 1, E_NEAR)));
-          bnd = b;
-          moved = true;
-        }
-        if (bnd >= nt) halves = false;
-      }
-      if (prev_halves && !halves) WRC(o.wt(ST_MAIN, ev(k - 1, E_NEAR)));  // U2(k) covers near(k-1)'s columns
-      // column k+1 was in U2(k-1)'s range -- or in near(k-1)'s, which precedes this on ST_U1
-      if (k > 0 && !prev_halves) WRC(o.wt(ST_U1, ev(k - 1, E_U2)));
+    }
+    c.prev_flow = pl.flow;
+    if (pl.flow) ++flow_waves, ++regimes[R_FLOW];
+    if (pl.pipe || pl.pipe_local) ++regimes[R_PIPE];
+    // with device-side edges ST_PANEL waits for no event between waves: POTRF(k+1)'s first step polls the
+    // last slice's counter, which also stands behind TRSM(k) (same stream, earlier), so POTRF(k+2) may
+    // reuse TRSM(k)'s workspace
+    c.wait_sem = pl.pipe ? o.sem(k, 3 * nbm, sem_per_wave) : nullptr;
+    c.wait_target = (g.mb / 64) * (g.mb / 64 + 1) / 2;
+    // TRSM(k) complete on this rank
+    if (pl.in_col) WRC(o.rec(ev(k, multi() ? E_TRSM : E_PANEL), ST_TRSM));
+    if (pl.own_diag && !pl.pipe) {
+      WRC(o.wt(ST_PANEL, ev(k, multi() ? E_TRSM : E_PANEL)));  // POTRF(k+2) overwrites this wave's block inverses
+      if (multi() && P > 1 && !pl.last) WRC(o.wt(ST_PANEL, ev(k, E_CXS)));  // ... which also travel
+    }
+    return 0;
+  }
+
+  // panel k to where this rank's update reads it: pan[k % NBUF]; -> the head tile L(k+1,k) (null where nobody uses it)
+  int move_panel(const WavePlan &pl, const char **head) {
+    const int k = pl.k;
+    if (multi()) {
+      WRC(head_move(k, head));
+      return exchange(k);
+    }
+    PanelRef &p = pan[k % NBUF];
+    memset(&p, 0, sizeof p);
+    p.P = 1;
+    p.base[0] = o.tile(0, k);
+    *head = o.tile(k + 1, k);
+    return 0;
+  }
+  char *next_diag(const WavePlan &pl) { return pl.next_diag_mine ? o.tile((pl.k + 1) / g.P, (pl.k + 1) / g.Q) : nullptr; }
+
+  // ---- trailing update (C2:540-560), panels in pairs (k-1, k), k odd: the far columns' update by the even panel is
+  // deferred and applied together with the odd one in ONE pass of twice the K (k_trail_update, npan = 2).
+  //   even k:  U1(k)  = column k+1 by panel k                                       (ST_U1)
+  //   odd  k:  U1'(k) = column k+1, Ca = column k+2, Cb = column k+3 by panels k-1, k  (ST_U1, in this order)
+  //            big(k) = the columns from k+4 on by panels k-1, k                      (ST_MAIN, beside them)
+  // Every column is written by launches of ST_U1 in program order, except by big(); the first launches
+  // of ST_U1 on a column big(k) covers are Ca / Cb of wave k+2, which wait for it.  POTRF(k+1) waits
+  // for the SYRKs on (k+1,k+1) only, TRSM(k+1) for the rest of column k+1.
+  int update_paired(const WavePlan &pl, const char *head) {
+    const int k = pl.k, nt = g.nt;
+    const bool odd = pl.odd, yield = pl.yield;
+    const PanelRef &pk = pan[k % NBUF];
+    char *ckk = next_diag(pl);
+    // the first pair behind plain waves: their far launch (ST_MAIN) wrote the columns ST_U1 is about to touch
+    if (!odd && k > 0 && !c.had_pairs) WRC(o.wt(ST_U1, ev(k - 1, E_U2)));
+    if (c.prev_halves) {  // ... and their near launch (ST_U1) the columns ST_MAIN is about to touch
+      WRC(o.wt(ST_MAIN, ev(k - 1, E_NEAR)));
+      c.prev_halves = false;
+    }
+    const PanelRef &prev = pan[(odd ? k - 1 : k) % NBUF];
+    const PanelRef *p2 = odd ? &pk : nullptr;  // launches: first `prev`, then `pk` when odd
+    const PanelRef &p1 = odd ? prev : pk;
+    const int k1 = odd ? k - 1 : k, k2 = odd ? k : -1;
+    if (pl.next_diag_mine) {
+      if (odd) WRC(o.diag_syrk(k - 1, k + 1, ckk, ptile(prev, k + 1, g.tile_bytes), ST_U1));
+      WRC(o.wt(ST_U1, ev(k, E_HEAD)));  // the head tile L(k+1,k) is all the last SYRK needs
+      WRC(o.diag_syrk(k, k + 1, ckk, head, ST_U1));
+      WRC(o.rec(ev(k, E_U1D), ST_U1));
+      WRC(o.wt(ST_PANEL, ev(k, E_U1D)));
+    }
+    WRC(o.wt(ST_U1, ev(k, E_PANEL)));
+    if (!odd && c.open_bracket < 0 && prof) WRC(o.rec(ev(k, E_P0), ST_U1));
+    WRC(update(k1, k2, k + 1, k + 2, 1, p1, p2, yield, ST_U1));
+    WRC(o.rec(ev(k, E_U1R), ST_U1));
+    if (odd) {
+      if (k >= 2) WRC(o.wt(ST_U1, ev(k - 2, E_U2)));  // big(k-2) covered these columns
+      WRC(update(k1, k2, k + 2, k + 3, 3, p1, p2, yield, ST_U1));
+      WRC(update(k1, k2, k + 3, k + 4, 3, p1, p2, yield, ST_U1));
+      WRC(o.rec(fx(F_COLS), ST_U1));
+      c.cols_pending = true;
       WRC(o.wt(ST_MAIN, ev(k, E_PANEL)));
-      int timed = 0;  // k_trail_update launches inside this wave's profiling bracket
-      // (... of tiles up to 512: with 1024 tiles the form lost 2-4 % -- 256 workgroups per tile, K = 1024 each)
-      const bool u1s = pipe && !mr && nbm <= 4 && n_r1o > 0 && n_r1o <= sw.u1_small_max;
-      if (split) {
-        // the panel chain is (nearly) critical: the diagonal tile (k+1,k+1) alone first, POTRF(k+1)
-        // needs nothing else; then the rest of column k+1, which TRSM(k+1) needs
-        if (!pipe && next_diag_mine) {
-          WRC(o.diag_syrk(k, k + 1, ckk, head, ST_U1));
-          WRC(o.rec(ev(k, E_U1D), ST_U1));
-        }
-        WRC(o.wt(ST_U1, ev(k, E_PANEL)));
-        if (halves && prof) WRC(o.rec(ev(k, E_PN0), ST_U1));
-        if (u1s) {
-          WRC(o.update_col_small(k, ST_U1));
-        } else {
-          WRC(o.update(k, -1, k + 1, k + 2, 1, pk, nullptr, yield, ST_U1));
-          if (n_r1o > 0) ++timed;
-        }
-        WRC(o.rec(ev(k, E_U1R), ST_U1));
-        if (halves) {
-          if (moved && prev_halves) WRC(o.wt(ST_U1, ev(k - 1, E_U2)));  // columns taken over from far(k-1)
-          WRC(o.update(k, -1, k + 2, bnd, 3, pk, nullptr, yield, ST_U1));
-          if (g.tiles_in(k + 2, bnd) > 0) ++timed;
-          WRC(o.rec(ev(k, E_NEAR), ST_U1));
-          if (prof) WRC(o.rec(ev(k, E_PN1), ST_U1));
-        }
-      } else {
-        // the update dwarfs the panel: one launch for the whole column (one tail less per wave)
-        WRC(o.update(k, -1, k + 1, k + 2, 3, pk, nullptr, yield, ST_U1));
-        if (n_r1o + n_r1d > 0) ++timed;
-        WRC(o.rec(ev(k, E_U1D), ST_U1));
-        WRC(o.rec(ev(k, E_U1R), ST_U1));
-      }
-      if (!by_flags && next_diag_mine) WRC(o.wt(ST_PANEL, ev(k, E_U1D)));
       if (prof) WRC(o.rec(ev(k, E_P0), ST_MAIN));
-      if (halves) {
-        WRC(o.update(k, -1, bnd, nt, 3, pk, nullptr, yield, ST_MAIN));
-        if (g.tiles_in(bnd, nt) > 0) ++timed;
-        halves_waves.push_back(k);
-      } else if (tiles2 > 0) {
-        WRC(o.update(k, -1, k + 2, nt, 3, pk, nullptr, yield, ST_MAIN));
-        ++timed;
-      }
+      WRC(update(k1, k2, k + 4, nt, 3, p1, p2, yield, ST_MAIN));
+      WRC(o.rec(ev(k, E_U2), ST_MAIN));
+      // the bracket [P0(k), P1(k)] covers every k_trail_update launch of the pair's update: the
+      // two-panel launches of this wave, which start together, and U1(k+1), which runs beside
+      // big(k); it is closed at the next wave
+      c.open_bracket = k;
+    } else {
       WRC(o.rec(ev(k, E_U2), ST_MAIN));
       if (prof) {
-        // the bracket [P0, P1] on ST_MAIN covers every k_trail_update launch of the wave: U1(k) started
-        // with U2(k); waiting for its end here constrains nothing (U2(k+1) needs panel k+1, which needs it).
-        // (halves: far(k+1) does NOT need near(k) -- two brackets, [PN0, PN1] on ST_U1 for column k+1 and the
-        // near half, and the host takes the union)
-        if (!halves) WRC(o.wt(ST_MAIN, ev(k, E_U1R)));
-        WRC(o.rec(ev(k, E_P1), ST_MAIN));
+        if (c.open_bracket >= 0) {
+          // waiting for the column launches and for U1(k) on ST_MAIN constrains nothing: big(k+1)
+          // needs panel k+1, which comes after all of them
+          WRC(o.wt(ST_MAIN, fx(F_COLS)));
+          WRC(o.wt(ST_MAIN, ev(k, E_U1R)));
+          WRC(o.rec(ev(c.open_bracket, E_P1), ST_MAIN));
+          WRC(o.rec(ev(k, E_P0), ST_MAIN));
+          WRC(o.rec(ev(k, E_P1), ST_MAIN));
+        } else {
+          WRC(o.rec(ev(k, E_P1), ST_U1));  // the very first wave: U1(0) alone, bracketed on its stream
+        }
       }
-      if (mr) WRC(o.rec(ev(k, E_SU), ST_U1));
-      prev_halves = halves;
-      ++regimes[near1 ? R_NEAR1 : halves ? R_HALVES : R_PLAIN];
-      if (yield) ++regimes[R_YIELD];
-      if (u1s) ++regimes[R_U1SMALL];
-      upd_launches += timed;
-      // algorithmic flops of the launches inside the bracket: GEMM 2 B^3 per off-diagonal tile, SYRK B^3
-      // per diagonal tile; the diagonal-tile SYRK of the split form is not a k_trail_update
-      upd_flops += (2.0 * n_r2o + n_r2d) * b3;
-      if (!u1s) upd_flops += (2.0 * n_r1o + (split ? 0 : n_r1d)) * b3;
+      c.open_bracket = -1;
     }
-    if (open_bracket >= 0 && prof) {
+    c.had_pairs = true;
+    ++regimes[R_PAIRED];
+    if (yield) ++regimes[R_YIELD];
+    if (multi()) WRC(o.rec(ev(k, E_SU), ST_U1));
+    return 0;
+  }
+
+  // ---- trailing update (C2:540-560) of a plain wave: column k+1 on ST_U1, the columns beyond on ST_MAIN or as halves
+  int update_plain(const WavePlan &pl, const char *head) {
+    const int k = pl.k, nt = g.nt;
+    const bool yield = pl.yield, halves = pl.halves;
+    const PanelRef &pk = pan[k % NBUF];
+    char *ckk = next_diag(pl);
+    if (c.open_bracket >= 0) {  // the paired phase ended on an odd wave: close its bracket
+      if (prof) {
+        WRC(o.wt(ST_MAIN, fx(F_COLS)));
+        WRC(o.rec(ev(c.open_bracket, E_P1), ST_MAIN));
+      }
+      c.open_bracket = -1;
+    }
+    // the SYRK on (k+1,k+1) needs the head tile L(k+1,k) only; everything else the whole panel
+    if (!pl.pipe) {
+      if (!pl.split) WRC(o.wt(ST_U1, ev(k, E_PANEL)));
+      else if (pl.next_diag_mine) WRC(o.wt(ST_U1, ev(k, E_HEAD)));
+    }
+    if (c.cols_pending) {
       WRC(o.wt(ST_MAIN, fx(F_COLS)));
-      WRC(o.rec(ev(open_bracket, E_P1), ST_MAIN));
+      c.cols_pending = false;
     }
-    (void)had_pairs;
+    if (pl.far_behind_near) WRC(o.wt(ST_MAIN, ev(k - 1, E_NEAR)));
+    // column k+1 was in U2(k-1)'s range -- or in near(k-1)'s, which precedes this on ST_U1
+    if (k > 0 && !c.prev_halves) WRC(o.wt(ST_U1, ev(k - 1, E_U2)));
+    WRC(o.wt(ST_MAIN, ev(k, E_PANEL)));
+    if (pl.split) {
+      // the panel chain is (nearly) critical: the diagonal tile (k+1,k+1) alone first, POTRF(k+1)
+      // needs nothing else; then the rest of column k+1, which TRSM(k+1) needs
+      if (!pl.pipe && pl.next_diag_mine) {
+        WRC(o.diag_syrk(k, k + 1, ckk, head, ST_U1));
+        WRC(o.rec(ev(k, E_U1D), ST_U1));
+      }
+      WRC(o.wt(ST_U1, ev(k, E_PANEL)));
+      if (halves && prof) WRC(o.rec(ev(k, E_PN0), ST_U1));
+      if (pl.u1s) WRC(o.update_col_small(k, ST_U1));
+      else WRC(update(k, -1, k + 1, k + 2, 1, pk, nullptr, yield, ST_U1));
+      WRC(o.rec(ev(k, E_U1R), ST_U1));
+      if (halves) {
+        if (pl.moved && c.prev_halves) WRC(o.wt(ST_U1, ev(k - 1, E_U2)));  // columns taken over from far(k-1)
+        WRC(update(k, -1, k + 2, pl.bnd, 3, pk, nullptr, yield, ST_U1));
+        WRC(o.rec(ev(k, E_NEAR), ST_U1));
+        if (prof) WRC(o.rec(ev(k, E_PN1), ST_U1));
+      }
+    } else {
+      // the update dwarfs the panel: one launch for the whole column (one tail less per wave)
+      WRC(update(k, -1, k + 1, k + 2, 3, pk, nullptr, yield, ST_U1));
+      WRC(o.rec(ev(k, E_U1D), ST_U1));
+      WRC(o.rec(ev(k, E_U1R), ST_U1));
+    }
+    if (!pl.pipe && pl.next_diag_mine) WRC(o.wt(ST_PANEL, ev(k, E_U1D)));
+    if (prof) WRC(o.rec(ev(k, E_P0), ST_MAIN));
+    if (halves) {
+      WRC(update(k, -1, pl.bnd, nt, 3, pk, nullptr, yield, ST_MAIN));
+      halves_waves.push_back(k);
+    } else if (pl.tiles2 > 0) {
+      WRC(update(k, -1, k + 2, nt, 3, pk, nullptr, yield, ST_MAIN));
+    }
+    WRC(o.rec(ev(k, E_U2), ST_MAIN));
+    if (prof) {
+      // the bracket [P0, P1] on ST_MAIN covers every k_trail_update launch of the wave: U1(k) started
+      // with U2(k); waiting for its end here constrains nothing (U2(k+1) needs panel k+1, which needs it).
+      // (halves: far(k+1) does NOT need near(k) -- two brackets, [PN0, PN1] on ST_U1 for column k+1 and the
+      // near half, and the host takes the union)
+      if (!halves) WRC(o.wt(ST_MAIN, ev(k, E_U1R)));
+      WRC(o.rec(ev(k, E_P1), ST_MAIN));
+    }
+    if (multi()) WRC(o.rec(ev(k, E_SU), ST_U1));
+    c.prev_halves = halves;
+    c.bnd = pl.bnd;
+    ++regimes[pl.near1 ? R_NEAR1 : halves ? R_HALVES : R_PLAIN];
+    if (yield) ++regimes[R_YIELD];
+    if (pl.u1s) ++regimes[R_U1SMALL];
+    return 0;
+  }
+
+  int join_and_finish(long long *info_out) {
+    if (c.open_bracket >= 0 && prof) {
+      WRC(o.wt(ST_MAIN, fx(F_COLS)));
+      WRC(o.rec(ev(c.open_bracket, E_P1), ST_MAIN));
+    }
     issue_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_host0).count();
     // join every stream into ST_MAIN
     const int joins[5][2] = {{F_JOIN, ST_PANEL}, {F_TRSM, ST_TRSM}, {F_U1END, ST_U1}, {F_CX, ST_CX}, {F_PX, ST_PX}};
-    for (int i = 0; i < (mr ? 5 : 4); ++i) {  // (one GPU: ST_CX carries the flow's row-slab kernel)
+    for (int i = 0; i < (multi() ? 5 : 4); ++i) {  // (one GPU: ST_CX carries the flow's row-slab kernel)
       WRC(o.rec(fx(joins[i][0]), joins[i][1]));
       WRC(o.wt(ST_MAIN, fx(joins[i][0])));
     }
     WRC(o.rec(fx(F_STOP), ST_MAIN));
     std::vector<std::pair<int, int>> brackets;
     if (prof) {
-      for (int k = 0; k + 1 < nt; ++k) brackets.emplace_back(ev(k, E_P0), ev(k, E_P1));
+      for (int k = 0; k + 1 < g.nt; ++k) brackets.emplace_back(ev(k, E_P0), ev(k, E_P1));
       for (int k : halves_waves) brackets.emplace_back(ev(k, E_PN0), ev(k, E_PN1));
     }
     int info = 0;
     WRC(o.finish(fx(F_START), fx(F_STOP), brackets, &info));
     // the smallest positive info wins: MAX-reduce (2^40 - info), 0 = success
     long long v = info > 0 ? (1LL << 40) - info : 0;
-    if (mr) WRC(cm->ch[0].allreduce_max(cm->ch[0].ctx, &v));
+    if (multi()) WRC(cm->ch[0].allreduce_max(cm->ch[0].ctx, &v));
     *info_out = v == 0 ? 0 : (1LL << 40) - v;
     return 0;
+  }
+
+  int run(long long *info_out) {
+    WRC(start());
+    for (int k = 0; k < g.nt; ++k) {
+      const WavePlan pl = plan(k);
+      c.paired = pl.paired;
+      WRC(panel_phase(pl));
+      if (pl.last) break;
+      const char *head = nullptr;
+      WRC(move_panel(pl, &head));
+      WRC(pl.paired ? update_paired(pl, head) : update_plain(pl, head));
+    }
+    return join_and_finish(info_out);
   }
 };
 
