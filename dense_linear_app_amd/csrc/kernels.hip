@@ -1030,10 +1030,10 @@ __global__ __launch_bounds__(512, 4) void k_update_ptrs_w8f(const float *const *
   update_ptr_block<CoreW8F>(cin, ap, bp, cout, n, mb, nbm, unit, ytab, sm);
 }
 
-// X[:, s] := alpha * A[:, s] * Winv_s^T, in place, for row blocks r >= r0 of `ntiles`
+// X[:, s] := alpha * A[:, s] * Winv_s^T, in place, for every row block of `ntiles`
 // contiguous tiles.  (TRSM by multiplication with the inverted 128x128 diagonal block.)
 template <typename T>
-__global__ __launch_bounds__(256, 2) void k_panel_solve(T *tiles, long bsiz, int mb, int nbm, int r0,
+__global__ __launch_bounds__(256, 2) void k_panel_solve(T *tiles, long bsiz, int mb, int nbm,
                                                         int s, const T *__restrict__ winv, T alpha,
                                                         int *ytab, const int *wait_sem = nullptr,
                                                         int wait_target = 0, int *fail = nullptr,
@@ -1042,8 +1042,7 @@ __global__ __launch_bounds__(256, 2) void k_panel_solve(T *tiles, long bsiz, int
   sem_wait(wait_sem, wait_target, fail);
   GuestOnCu guest(ytab);
   __builtin_amdgcn_s_setprio(2);  // panel chain: ahead of co-resident trailing-update waves
-  const int nr = nbm - r0;
-  const int tix = blockIdx.x / nr, r = r0 + blockIdx.x % nr;
+  const int tix = blockIdx.x / nbm, r = blockIdx.x % nbm;
   T *Ap = tiles + (long)tix * bsiz + r * MACRO + (long)s * MACRO * mb;
   const T *Bp = winv + (long)s * MACRO * MACRO;
   Acc<T> acc;
@@ -1051,7 +1050,7 @@ __global__ __launch_bounds__(256, 2) void k_panel_solve(T *tiles, long bsiz, int
   nt_kloop_paired<T>(Ap, mb, Bp, MACRO, MACRO, acc, sm);
   nt_epilogue_paired<T>(Ap, mb, acc, alpha, T(0), false);
   guest.leave();
-  if (tix == 0) sem_signal(head_sem);  // (the first tile's workgroups: nr counts)
+  if (tix == 0) sem_signal(head_sem);  // (the first tile's workgroups: nbm counts)
 }
 
 // A[:, c] := beta*A[:, c] - X[:, s] * L[c, s]^T for c > s (right-looking TRSM step)
@@ -1086,10 +1085,12 @@ __global__ __launch_bounds__(256, 2) void k_panel_update(T *tiles, long bsiz, in
 // block); in the 128 x 128 NT core one such block is 8 K-slices of a DMA pipeline that never
 // fills: 19-22 us, 3x its MFMA time.  Here a workgroup takes a quarter of the work (solve: a
 // 32-row slab of the block row, all 128 columns, so that it can run in place; update: a 64 x 64
-// block), K in four phases of 32 staged global -> registers -> LDS with the next phase's loads
+// block), K in phases of 32 staged global -> registers -> LDS with the next phase's loads
 // in flight under the current phase's MFMAs, one wave = 32 x 32 of the output = 2 x 2 MFMA
 // tiles.  LDS image [k][rows + 16]: the row stride puts the four 16-lane k-groups of a fragment
 // read on alternating bank halves (conflict-free for 8-byte reads).
+// Two bodies, small_solve_block and small_update_block, serve the three kernels: k_solve_small and
+// k_small_update add their block index, counters and guest bracket, k_intile_step is both behind one branch.
 // ------------------------------------------------------------------------------
 constexpr int SK = 32;
 template <typename T, int ROWS>
@@ -1133,23 +1134,11 @@ __device__ __forceinline__ void small_mma(const SmallImg<T, RA> &ia, const Small
   }
 }
 
-// X[slab, 0..127] = alpha * A[slab, 0..127] * Winv_s^T, in place: one workgroup per 32-row slab of
-// the block rows r0.. of each of the tiles at tiles + q*bsiz (it reads only its own rows, all of
-// them before it writes).  In-tile step: one tile, r0 = s+1; panel TRSM step: all panel tiles, r0 = 0.
+// One 32-row slab of the small solve: Ap[0..31, 0..127] = Ap * Bp^T, in place (the slab reads only its own
+// rows, all of them before it writes).
 template <typename T>
-__global__ __launch_bounds__(256, 2) void k_solve_small(T *tiles, long bsiz, int mb, int nbm, int r0, int s,
-                                                        const T *__restrict__ winv, T alpha, int *ytab,
-                                                        const int *wait_sem = nullptr, int wait_target = 0,
-                                                        int *fail = nullptr, int *head_sem = nullptr) {
-  __shared__ SmallImg<T, 32> ia;
-  __shared__ SmallImg<T, MACRO> ib;
-  sem_wait(wait_sem, wait_target, fail);
-  GuestOnCu guest(ytab);
-  __builtin_amdgcn_s_setprio(2);
-  const int per_tile = 4 * (nbm - r0);
-  const int tix = blockIdx.x / per_tile, slab = blockIdx.x % per_tile;
-  T *Ap = tiles + (long)tix * bsiz + (long)r0 * MACRO + 32 * slab + (long)s * MACRO * mb;
-  const T *Bp = winv + (long)s * MACRO * MACRO;
+__device__ __forceinline__ void small_solve_block(T *Ap, int mb, const T *Bp,
+                                                  SmallImg<T, 32> &ia, SmallImg<T, MACRO> &ib) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, lo = lane & 15;
   T ra[32 * SK / 256], rb[MACRO * SK / 256];
   typename Tr<T>::acc_t acc[2][2];
@@ -1178,7 +1167,91 @@ __global__ __launch_bounds__(256, 2) void k_solve_small(T *tiles, long bsiz, int
     for (int b = 0; b < 2; ++b)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        Ap[16 * a + lo + (long)(32 * w + 16 * b + Tr<T>::drow(lane, r)) * mb] = alpha * acc[a][b][r];
+        Ap[16 * a + lo + (long)(32 * w + 16 * b + Tr<T>::drow(lane, r)) * mb] = acc[a][b][r];
+}
+
+// One 64 x 64 block of the small update: C -= A B^T over K columns, behind a poll of the producer of A / B;
+// dg: a diagonal block, which writes i >= j only.
+template <typename T>
+__device__ __forceinline__ void small_update_block(T *Cp, long ldc, const T *Ap,
+                                                   const T *Bp, int ldab, int K, bool dg, int *ytab,
+                                                   const int *wait_sem, int wait_target, int *fail,
+                                                   SmallImg<T, 64> &ia, SmallImg<T, 64> &ib) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, lo = lane & 15;
+  const int i0 = 32 * (w & 1), j0 = 32 * (w >> 1);
+  T ra[64 * SK / 256], rb[64 * SK / 256];
+  typename Tr<T>::acc_t acc[2][2];
+  // C up front (nobody else writes this block meanwhile): its load latency -- a cold miss, the block was last
+  // written a step or a wave ago -- is then hidden behind the polls and the K loop instead of ending the kernel
+  T cv[2][2][4];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        acc[a][b][r] = T(0);
+        cv[a][b][r] = Cp[(i0 + 16 * a + lo) + (long)(j0 + 16 * b + Tr<T>::drow(lane, r)) * ldc];
+      }
+  // (what is polled for is the producer of A / B; the block of C was last written by an earlier launch of
+  // this stream, or before the launch that raised an earlier counter of the chain)
+  sem_wait(wait_sem, wait_target, fail);
+  GuestOnCu guest(ytab);
+  __builtin_amdgcn_s_setprio(2);
+  small_gload<T, 64>(Ap, ldab, 0, ra);
+  small_gload<T, 64>(Bp, ldab, 0, rb);
+  const int nph = K / SK;
+  for (int ph = 0; ph < nph; ++ph) {
+    small_lstore<T, 64>(ia, ra);
+    small_lstore<T, 64>(ib, rb);
+    __syncthreads();
+    if (ph + 1 < nph) {
+      small_gload<T, 64>(Ap, ldab, (ph + 1) * SK, ra);
+      small_gload<T, 64>(Bp, ldab, (ph + 1) * SK, rb);
+    }
+    small_mma<T, 64, 64>(ia, ib, i0, j0, acc);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = i0 + 16 * a + lo, j = j0 + 16 * b + Tr<T>::drow(lane, r);
+        if (!dg || i >= j) Cp[i + (long)j * ldc] = cv[a][b][r] - acc[a][b][r];
+      }
+  guest.leave();
+}
+
+// (row, col) of the idx-th block on or below the diagonal of an n x n block grid, column by column
+struct BlkRC {
+  int r, c;
+};
+__host__ __device__ constexpr BlkRC lower_blk(int idx, int n) {
+  int c = 0;
+  for (; idx >= n - c; ++c) idx -= n - c;
+  return {c + idx, c};
+}
+
+// X[slab, 0..127] = A[slab, 0..127] * Winv_s^T, in place: one workgroup per 32-row slab of the block rows r0..
+// of each of the tiles at tiles + q*bsiz.  In-tile step: one tile, r0 = s+1; panel TRSM step: all panel tiles,
+// r0 = 0.
+template <typename T>
+__global__ __launch_bounds__(256, 2) void k_solve_small(T *tiles, long bsiz, int mb, int nbm, int r0, int s,
+                                                        const T *__restrict__ winv, int *ytab,
+                                                        const int *wait_sem = nullptr, int wait_target = 0,
+                                                        int *fail = nullptr, int *head_sem = nullptr) {
+  __shared__ SmallImg<T, 32> ia;
+  __shared__ SmallImg<T, MACRO> ib;
+  sem_wait(wait_sem, wait_target, fail);
+  GuestOnCu guest(ytab);
+  __builtin_amdgcn_s_setprio(2);
+  const int per_tile = 4 * (nbm - r0);
+  const int tix = blockIdx.x / per_tile, slab = blockIdx.x % per_tile;
+  T *Ap = tiles + (long)tix * bsiz + (long)r0 * MACRO + 32 * slab + (long)s * MACRO * mb;
+  const T *Bp = winv + (long)s * MACRO * MACRO;
+  small_solve_block<T>(Ap, mb, Bp, ia, ib);
   guest.leave();
   if (tix == 0) sem_signal(head_sem);  // (the first tile's workgroups: per_tile counts)
 }
@@ -1204,52 +1277,8 @@ __global__ __launch_bounds__(256, 2) void k_small_update(T *C, long ldc, const T
   const T *Ap = A + 64 * r64;
   const T *Bp = B + 64 * c64;
   T *Cp = C + 64 * r64 + 64 * c64 * ldc;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, lo = lane & 15;
-  const int i0 = 32 * (w & 1), j0 = 32 * (w >> 1);
-  T ra[64 * SK / 256], rb[64 * SK / 256];
-  typename Tr<T>::acc_t acc[2][2];
-  // C up front (nobody else writes this block meanwhile): its load latency -- a cold miss, the block was last
-  // written a step or a wave ago -- is then hidden behind the polls and the K loop instead of ending the kernel
-  T cv[2][2][4];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        acc[a][b][r] = T(0);
-        cv[a][b][r] = Cp[(i0 + 16 * a + lo) + (long)(j0 + 16 * b + Tr<T>::drow(lane, r)) * ldc];
-      }
-  // (what is polled for is the producer of A / B; the block of C was last written by an earlier launch of
-  // this stream, or before the launch that raised an earlier counter of the chain)
-  sem_wait(wait_sem, wait_target, fail);
-  GuestOnCu guest(ytab);
-  __builtin_amdgcn_s_setprio(2);
-  small_gload<T, 64>(Ap, (int)ldab, 0, ra);
-  small_gload<T, 64>(Bp, (int)ldab, 0, rb);
-  const int nph = K / SK;
-  for (int ph = 0; ph < nph; ++ph) {
-    small_lstore<T, 64>(ia, ra);
-    small_lstore<T, 64>(ib, rb);
-    __syncthreads();
-    if (ph + 1 < nph) {
-      small_gload<T, 64>(Ap, (int)ldab, (ph + 1) * SK, ra);
-      small_gload<T, 64>(Bp, (int)ldab, (ph + 1) * SK, rb);
-    }
-    small_mma<T, 64, 64>(ia, ib, i0, j0, acc);
-    __syncthreads();
-  }
-  const bool dg = !full && (r64 == c64);
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = i0 + 16 * a + lo, j = j0 + 16 * b + Tr<T>::drow(lane, r);
-        if (!dg || i >= j) Cp[i + (long)j * ldc] = cv[a][b][r] - acc[a][b][r];
-      }
-  guest.leave();
+  small_update_block<T>(Cp, ldc, Ap, Bp, (int)ldab, K, !full && r64 == c64, ytab, wait_sem, wait_target, fail, ia,
+                        ib);
   sem_signal(signal_sem);  // (one count per workgroup that has a block: n (n + 1) / 2 of the n x n grid when !full)
 }
 
@@ -1276,93 +1305,22 @@ __global__ __launch_bounds__(256, 2) void k_intile_step(T *tile, int mb, int nbm
                                                         int *ytab, int *cnt, int *fail) {
   __shared__ IntileLds<T> L;
   const int nr = nbm - 1 - s, nsolve = 4 * nr;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, lo = lane & 15;
-  typename Tr<T>::acc_t acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[a][b][r] = T(0);
   if ((int)blockIdx.x < nsolve) {
     GuestOnCu guest(ytab);
     __builtin_amdgcn_s_setprio(2);
     T *Ap = tile + (long)(s + 1) * MACRO + 32 * (int)blockIdx.x + (long)s * MACRO * mb;
     const T *Bp = winv + (long)s * MACRO * MACRO;
-    T ra[32 * SK / 256], rb[MACRO * SK / 256];
-    small_gload<T, 32>(Ap, mb, 0, ra);
-    small_gload<T, MACRO>(Bp, MACRO, 0, rb);
-    for (int ph = 0; ph < MACRO / SK; ++ph) {
-      small_lstore<T, 32>(L.sv.a, ra);
-      small_lstore<T, MACRO>(L.sv.b, rb);
-      __syncthreads();
-      if (ph + 1 < MACRO / SK) {
-        small_gload<T, 32>(Ap, mb, (ph + 1) * SK, ra);
-        small_gload<T, MACRO>(Bp, MACRO, (ph + 1) * SK, rb);
-      }
-      small_mma<T, 32, MACRO>(L.sv.a, L.sv.b, 0, 32 * w, acc);
-      __syncthreads();
-    }
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          Ap[16 * a + lo + (long)(32 * w + 16 * b + Tr<T>::drow(lane, r)) * mb] = acc[a][b][r];
+    small_solve_block<T>(Ap, mb, Bp, L.sv.a, L.sv.b);
     guest.leave();
     sem_signal(cnt);
     return;
   }
-  // the idx-th lower block, column by column
-  int c64 = 0, left = (int)blockIdx.x - nsolve, len = 2 * nr;
-  while (left >= len) {
-    left -= len;
-    --len;
-    ++c64;
-  }
-  const int r64 = c64 + left;
+  const BlkRC blk = lower_blk((int)blockIdx.x - nsolve, 2 * nr);
   T *tr = tile + (long)(s + 1) * MACRO * (mb + 1);                        // trailing part of the tile
   const T *xs = tile + (long)(s + 1) * MACRO + (long)s * MACRO * mb;      // block column s below the diagonal
-  const T *Ap = xs + 64 * r64, *Bp = xs + 64 * c64;
-  T *Cp = tr + 64 * r64 + (long)64 * c64 * mb;
-  const int i0 = 32 * (w & 1), j0 = 32 * (w >> 1);
-  T cv[2][2][4];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        cv[a][b][r] = Cp[(i0 + 16 * a + lo) + (long)(j0 + 16 * b + Tr<T>::drow(lane, r)) * mb];
-  sem_wait(cnt, nsolve, fail);
-  GuestOnCu guest(ytab);
-  __builtin_amdgcn_s_setprio(2);
-  T ra[64 * SK / 256], rb[64 * SK / 256];
-  small_gload<T, 64>(Ap, mb, 0, ra);
-  small_gload<T, 64>(Bp, mb, 0, rb);
-  for (int ph = 0; ph < MACRO / SK; ++ph) {
-    small_lstore<T, 64>(L.up.a, ra);
-    small_lstore<T, 64>(L.up.b, rb);
-    __syncthreads();
-    if (ph + 1 < MACRO / SK) {
-      small_gload<T, 64>(Ap, mb, (ph + 1) * SK, ra);
-      small_gload<T, 64>(Bp, mb, (ph + 1) * SK, rb);
-    }
-    small_mma<T, 64, 64>(L.up.a, L.up.b, i0, j0, acc);
-    __syncthreads();
-  }
-  const bool dg = r64 == c64;
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = i0 + 16 * a + lo, j = j0 + 16 * b + Tr<T>::drow(lane, r);
-        if (!dg || i >= j) Cp[i + (long)j * mb] = cv[a][b][r] - acc[a][b][r];
-      }
-  guest.leave();
+  const T *Ap = xs + 64 * blk.r, *Bp = xs + 64 * blk.c;
+  T *Cp = tr + 64 * blk.r + (long)64 * blk.c * mb;
+  small_update_block<T>(Cp, mb, Ap, Bp, mb, MACRO, blk.r == blk.c, ytab, cnt, nsolve, fail, L.up.a, L.up.b);
 }
 
 // generic one-tile C := alpha*A*B^T + beta*C (GEMM NoTrans/Trans, or SYRK Lower)
@@ -1654,10 +1612,6 @@ __device__ __forceinline__ void potrf_diag_body(T *A, int ld, T *__restrict__ wi
   int &failed = L.failed;
   const int t = threadIdx.x, lane = t & 63, lo = lane & 15;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);  // wave-uniform by construction: scalar branches
-  // Global <-> LDS: thread t owns row (t & 127) and block columns 4 (t >> 7) .. +3; per 16x16
-  // block the 16 elements of its row are one base address + constant strides on both sides
-  // (no per-element index arithmetic), 16 independent accesses in flight, rows of consecutive
-  // threads contiguous in global memory.
   // Global <-> LDS, two ROWS per lane (16 bytes on the global side: one wave instruction moves a whole 128-row column):
   // lane rp of wave w4 owns rows 2 rp, 2 rp + 1 of the block columns w4 and 7 - w4 (nine of the 36 lower blocks per
   // wave); per block the pair's 16 columns are one base address + constant strides on both sides.
@@ -2168,30 +2122,11 @@ __device__ __forceinline__ void flow_drain(int fences) {
   }
 }
 
-// idx-th lower 16 x 16 block of the 8 x 8 block grid, column by column
-__host__ __device__ constexpr int flow_blk_c(int idx) {
-  int c = 0, len = DB_NP;
-  while (idx >= len) {
-    idx -= len;
-    --len;
-    ++c;
-  }
-  return c;
-}
-__host__ __device__ constexpr int flow_blk_r(int idx) {
-  int c = 0, len = DB_NP;
-  while (idx >= len) {
-    idx -= len;
-    --len;
-    ++c;
-  }
-  return c + idx;
-}
-
+// accumulator q of wave W is lower 16 x 16 block W + 4 q of the 8 x 8 block grid, column by column (lower_blk)
 template <typename T, int W>
 __device__ __forceinline__ void flow_rank16(typename Tr<T>::acc_t (&acc)[9], const T (&xf)[8][4], const T (&nxf)[8][4]) {
   static_for<0, 9>([&](auto Q) {
-    constexpr int q = decltype(Q)::value, idx = W + 4 * q, bi = flow_blk_r(idx), bj = flow_blk_c(idx);
+    constexpr int q = decltype(Q)::value, bi = lower_blk(W + 4 * q, DB_NP).r, bj = lower_blk(W + 4 * q, DB_NP).c;
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc[q] = Tr<T>::mfma(nxf[bi][r], xf[bj][r], acc[q]);
   });
@@ -2200,7 +2135,7 @@ template <typename T, int W>
 __device__ __forceinline__ void flow_fold(const typename Tr<T>::acc_t (&acc)[9], T *S) {
   const int lane = threadIdx.x & 63, lo = lane & 15;
   static_for<0, 9>([&](auto Q) {
-    constexpr int q = decltype(Q)::value, idx = W + 4 * q, bi = flow_blk_r(idx), bj = flow_blk_c(idx);
+    constexpr int q = decltype(Q)::value, bi = lower_blk(W + 4 * q, DB_NP).r, bj = lower_blk(W + 4 * q, DB_NP).c;
     T *Cb = S + db_off(bi, bj);
 #pragma unroll
     for (int reg = 0; reg < 4; ++reg) Cb[Tr<T>::drow(lane, reg) + lo * DB_LD] += acc[q][reg];
@@ -2754,7 +2689,7 @@ int trsm_step(hipStream_t s, T *tiles, long bsiz, int ntiles, const T *lkk, cons
   const int nbm = mb / MACRO, nc = nbm - 1 - st;
   if (alpha == T(1) && ntiles * nbm <= g_trsm_small_max) {
     const bool p1 = poll_in_kernel(s, sm.diag, 1, sm.fail, (long)ntiles * nbm * 4);
-    k_solve_small<T><<<ntiles * nbm * 4, 256, 0, s>>>(tiles, bsiz, mb, nbm, 0, st, winv, T(1), g_ytab,
+    k_solve_small<T><<<ntiles * nbm * 4, 256, 0, s>>>(tiles, bsiz, mb, nbm, 0, st, winv, g_ytab,
                                                       p1 ? sm.diag : nullptr, 1, sm.fail, sm.head);
     if (nc > 0) {
       const bool p2 = poll_in_kernel(s, sm.intile, sm.intile_target, sm.fail, 4L * nbm * nc * ntiles);
@@ -2768,7 +2703,7 @@ int trsm_step(hipStream_t s, T *tiles, long bsiz, int ntiles, const T *lkk, cons
   // alpha is applied once to every column block: in the solve of block 0 and as the beta of the
   // first update of blocks > 0
   const bool p1 = poll_in_kernel(s, sm.diag, 1, sm.fail, (long)ntiles * nbm);
-  k_panel_solve<T><<<ntiles * nbm, 256, 0, s>>>(tiles, bsiz, mb, nbm, 0, st, winv, st == 0 ? alpha : T(1), g_ytab,
+  k_panel_solve<T><<<ntiles * nbm, 256, 0, s>>>(tiles, bsiz, mb, nbm, st, winv, st == 0 ? alpha : T(1), g_ytab,
                                                 p1 ? sm.diag : nullptr, 1, sm.fail, sm.head);
   if (nc > 0) {
     const bool p2 = poll_in_kernel(s, sm.intile, sm.intile_target, sm.fail, (long)ntiles * nbm * nc);
@@ -2795,6 +2730,28 @@ void launch_diag_syrk(hipStream_t s, T *C, const T *A, int mb) {
   k_small_update<T><<<dim3(mb / 64, mb / 64), 256, 0, s>>>(C, mb, A, A, mb, mb, g_ytab, 0, 0, 0);
 }
 
+// In-tile step s of the tile POTRF (nbm - 1 - s > 0 block rows below the diagonal block): a handful of workgroups
+// on the critical path, guests.  cnt != null and the step small enough: solve and update in one launch, the
+// update's workgroups polling the solves' counter cnt; otherwise two launches, the solve raising solve_signal
+// (may be null).
+template <typename T>
+void launch_intile_step(hipStream_t stream, T *tile, int mb, int nbm, int s, const T *winv, int *cnt,
+                        int *solve_signal, int *d_info) {
+  const int nr = nbm - 1 - s;
+  if (cnt && nr * (2 * nr + 1) <= INTILE_FUSED_MAX) {
+    k_intile_step<T><<<4 * nr + nr * (2 * nr + 1), 256, 0, stream>>>(tile, mb, nbm, s, winv, g_ytab, cnt, d_info);
+    return;
+  }
+  k_solve_small<T><<<4 * nr, 256, 0, stream>>>(tile, 0, mb, nbm, s + 1, s, winv, g_ytab, nullptr, 0, nullptr,
+                                               solve_signal);
+  T *tr = tile + (long)(s + 1) * MACRO * (mb + 1);                    // trailing part of the tile
+  const T *xs = tile + (long)(s + 1) * MACRO + (long)s * MACRO * mb;  // block column s below the diagonal
+  // (launching the update ahead of time on another stream, polling the in-tile solve's counter, the
+  // next diagonal-block step polling its own: -1 ... -5 % on st, -10 ... -20 % on su -- it queues
+  // behind that stream's own launches)
+  k_small_update<T><<<dim3(2 * nr, 2 * nr), 256, 0, stream>>>(tr, mb, xs, xs, mb, MACRO, g_ytab, 0, 0, 0);
+}
+
 // sem (may be null): mb / 128 counters, 32 ints apart, for the fused in-tile steps (k_intile_step); zeroed here
 template <typename T>
 void launch_potrf_tile(hipStream_t s, T *tile, int mb, T *winv, int *d_info, int info_base, int *sem) {
@@ -2804,18 +2761,8 @@ void launch_potrf_tile(hipStream_t s, T *tile, int mb, T *winv, int *d_info, int
   for (int st = 0; st < nbm; ++st) {
     k_potrf_diag<T><<<1, 256, 0, s>>>(tile + (long)st * MACRO * (mb + 1), mb,
                                       winv + (long)st * MACRO * MACRO, d_info, info_base + st * MACRO, 1, g_dbg, g_ytab);
-    const int nr = nbm - 1 - st;
-    if (nr > 0) {
-      // the in-tile POTRF steps are a handful of workgroups on the critical path: guests
-      if (fused_steps && nr * (2 * nr + 1) <= INTILE_FUSED_MAX) {
-        k_intile_step<T><<<4 * nr + nr * (2 * nr + 1), 256, 0, s>>>(tile, mb, nbm, st, winv, g_ytab, sem + 32 * st, d_info);
-      } else {
-        k_solve_small<T><<<4 * nr, 256, 0, s>>>(tile, 0, mb, nbm, st + 1, st, winv, T(1), g_ytab);
-        T *tr = tile + (long)(st + 1) * MACRO * (mb + 1);  // trailing part of the tile
-        const T *xs = tile + (long)(st + 1) * MACRO + (long)st * MACRO * mb;  // block column st below the diagonal
-        k_small_update<T><<<dim3(2 * nr, 2 * nr), 256, 0, s>>>(tr, mb, xs, xs, mb, MACRO, g_ytab, 0, 0, 0);
-      }
-    }
+    if (st < nbm - 1)
+      launch_intile_step<T>(s, tile, mb, nbm, st, winv, fused_steps ? sem + 32 * st : nullptr, nullptr, d_info);
   }
 }
 
@@ -2863,21 +2810,10 @@ void launch_panel_pipelined(hipStream_t sp, hipStream_t st, hipEvent_t *ev, T *l
                                          d_info, info_base + s * MACRO, 1, g_dbg, g_ytab, s == 0 ? wait_sem : nullptr,
                                          wait_target, pipe ? slot(s) : nullptr);
     if (nr > 0 && !flow) {
-      if ((pipe || fused_plain) && g_intile_fused && nr * (2 * nr + 1) <= INTILE_FUSED_MAX) {
-        // solve and update of the step in one launch, the update's workgroups polling the solves' counter
-        // (which the TRSM step's update on st polls too)
-        k_intile_step<T><<<4 * nr + nr * (2 * nr + 1), 256, 0, sp>>>(lkk, mb, nbm, s, winv, g_ytab,
-                                                                     pipe ? slot(nbm + s) : tile_sem + 32 * s, d_info);
-      } else {
-        k_solve_small<T><<<4 * nr, 256, 0, sp>>>(lkk, 0, mb, nbm, s + 1, s, winv, T(1), g_ytab, nullptr, 0, nullptr,
-                                                 pipe ? slot(nbm + s) : nullptr);
-        T *tr = lkk + (long)(s + 1) * MACRO * (mb + 1);
-        const T *xs = lkk + (long)(s + 1) * MACRO + (long)s * MACRO * mb;
-        // (launching the update ahead of time on another stream, polling the in-tile solve's counter, the
-        // next diagonal-block step polling its own: -1 ... -5 % on st, -10 ... -20 % on su -- it queues
-        // behind that stream's own launches)
-        k_small_update<T><<<dim3(2 * nr, 2 * nr), 256, 0, sp>>>(tr, mb, xs, xs, mb, MACRO, g_ytab, 0, 0, 0);
-      }
+      int *const is = pipe ? slot(nbm + s) : nullptr;  // I[s] of a counter-linked wave: the TRSM step's update on st polls it
+      // cnt: what the update of a fused step polls -- I[s], or the tile's own counter in the event-linked form
+      int *const cnt = pipe && g_intile_fused ? is : fused_plain ? tile_sem + 32 * s : nullptr;
+      launch_intile_step<T>(sp, lkk, mb, nbm, s, winv, cnt, is, d_info);
     }
     if (ntiles <= 0) continue;
     if (pipe) {

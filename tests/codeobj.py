@@ -1,5 +1,5 @@
 """Reads the gfx950 code object embedded in libcholmi.so (clang offload bundle in .hip_fatbin)
-and returns, per kernel, what the hardware will allocate: VGPRs (granulated, arch + acc) and LDS.
+and returns, per kernel, what the hardware will allocate: VGPRs (granulated, arch + acc), LDS and scratch.
 Test infrastructure: lets the CPU suite check the co-residency budget the design relies on."""
 import struct
 
@@ -37,7 +37,7 @@ def device_elf(so_path: str, arch: str = "gfx950") -> bytes:
 
 
 def kernel_resources(so_path: str) -> dict:
-    """{mangled kernel name: {"vgprs": allocated VGPRs per lane (arch+acc), "lds": bytes}}"""
+    """{mangled kernel name: {"vgprs": allocated VGPRs per lane (arch+acc), "lds": bytes, "scratch": bytes per lane}}"""
     elf = device_elf(so_path)
     secs = _sections(elf)
     out = {}
@@ -51,9 +51,9 @@ def kernel_resources(so_path: str) -> dict:
                 continue
             sec = secs[shndx]
             kd = elf[sec["off"] + value - sec["addr"]:][:64]
-            lds, = struct.unpack_from("<I", kd, 0)
+            lds, scratch = struct.unpack_from("<II", kd, 0)
             rsrc1, = struct.unpack_from("<I", kd, 48)
-            out[name[:-3]] = {"vgprs": ((rsrc1 & 0x3F) + 1) * 8, "lds": lds}
+            out[name[:-3]] = {"vgprs": ((rsrc1 & 0x3F) + 1) * 8, "lds": lds, "scratch": scratch}
     return out
 
 

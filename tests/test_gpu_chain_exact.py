@@ -160,6 +160,44 @@ def test_potrf_is_exact_in_every_form_of_the_chain(name, env, regime):
         regime(cases)
 
 
+def fill_child_main():
+    """single-tile POTRF with a FINITE strict upper triangle, under this process's in-tile switch"""
+    sys.path.insert(0, ROOT)
+    from dense_linear_app_amd import chameleon as ch
+
+    ch.CHAMELEON_Init(1, 1)
+    for B in (256, 512):
+        A, L, _ = dm.cholesky_case(B, B)
+        for dt in ("d", "s"):
+            info, T, S = potrf_tile(ch, A, dt, fill=-7.0)
+            iu = np.triu_indices(B, 1)
+            rec = {"B": B, "dt": dt, "info": int(info), "mismatches": mismatches(np.tril(T), L.astype(npdt(dt)), B)[0],
+                   "upper_touched": int((bits(T[iu]) != bits(S[iu])).sum())}
+            print("CASE " + json.dumps(rec), flush=True)
+
+
+@pytest.mark.parametrize("fused", ["1", "0"], ids=["fused", "split"])
+def test_intile_update_leaves_a_finite_upper_triangle_alone(fused):
+    """the diagonal 64 x 64 blocks of the in-tile update write i >= j only.  Above the diagonal the other cases hold NaN,
+    and NaN - x stores the same NaN back: an update that lost its mask would pass them.  Here the strict upper triangle
+    is -7, one tile of 2 and of 4 blocks (one and three in-tile steps), fp64 and fp32, the solve and the update of a step
+    in one launch and in two: L exact, and not one bit above the diagonal changed"""
+    try:
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "finite-fill"],
+                           env=dict(os.environ, CHOLMI_INTILE_FUSED=fused), capture_output=True, text=True, timeout=120)
+    except subprocess.TimeoutExpired as e:
+        pytest.exit(f"the finite-fill child hung: nothing more is started on this GPU ({e.stdout})", returncode=3)
+    print(r.stdout)
+    if r.returncode < 0 or r.returncode in (134, 139):
+        pytest.exit(f"the finite-fill child died ({r.returncode}): nothing more is started on this GPU\n"
+                    f"{r.stdout}\n{r.stderr[-2000:]}", returncode=3)
+    assert r.returncode == 0, (r.stdout, r.stderr[-2000:])
+    cases = [json.loads(ln[5:]) for ln in r.stdout.splitlines() if ln.startswith("CASE ")]
+    assert [(c["B"], c["dt"]) for c in cases] == [(B, dt) for B in (256, 512) for dt in "ds"]
+    bad = [c for c in cases if c["info"] != 0 or c["mismatches"] or c["upper_touched"]]
+    assert not bad, bad
+
+
 # ---- in-process ---------------------------------------------------------------------------------------------------------
 def potrf_tile(ch, A, dt, fill=np.nan):
     """single-tile POTRF on a host buffer -> (info, the tile afterwards, the tile as stored)"""
@@ -247,4 +285,4 @@ def test_wave_level_task_path_is_exact(cham, N, B):
 
 
 if __name__ == "__main__":
-    child_main()
+    fill_child_main() if sys.argv[1:] == ["finite-fill"] else child_main()
