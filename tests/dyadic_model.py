@@ -14,7 +14,22 @@ the known answer bit for bit as long as no partial sum leaves the range in which
 emulations below run the right-looking algorithms in 128-blocks (explicit recursive inverse of every diagonal block,
 the panel times that inverse, the trailing update; sygst with its two half updates and the deferred solve) in a given
 dtype and record, for every product they form, the largest entry of |X| |Y|: a bound on every partial sum of every
-summation order.  tests/test_dyadic_host.py asserts that 16 times that peak (four fractional bits) is below 2^24."""
+summation order.  tests/test_dyadic_host.py asserts that 16 times that peak (four fractional bits) is below 2^24.
+
+That family ("parity") is thin: half the rows and half the columns of the factor carry nothing below the diagonal, and
+every product of two off-diagonal pieces of it is zero.  Three more families take the same draws through another mask
+(FAMILIES, family_mask):
+    mirror   row even, column odd: Nn Nn = 0 again, the other half of the rows and columns carries the entries
+    mod3     row % 3 > column % 3: Nn^3 = 0, inv(I + Nn) = I - Nn + Nn^2 -- a second-order term in every inverse
+    panel    (of a tile size B, a multiple of 128) the mod3 rule inside the diagonal 128-blocks of the tiles, no mask
+             outside them: every panel tile and every trailing update dense
+For A = L L^T with L an integer lower triangle whose diagonal is a power of two, unblocked Cholesky is exact whatever the
+sparsity of L; only the inverses a blocked algorithm forms constrain the family.  The factorisations (potrf, sytrf) and
+the forward sweep of the solves invert nothing larger than a 128-block, as potrf_blocked and ldl_blocked do.  sygst and
+the backward sweep of the solves multiply by the inverse of a whole diagonal tile (inv_tile; sygst_blocked with nb = the
+tile size follows the library): on a panel member that inverse has magnitude 5e2 for a tile of 256 and 2e6 for one of
+512, which is where the host proofs send some of its cases to fp64 alone.  The global inverse of a panel member is huge
+(1e13 at n = 1024), so inv_factor and inv_spd refuse that family."""
 import functools
 
 import numpy as np
@@ -22,13 +37,35 @@ import numpy as np
 NB = 128
 
 
+FAMILIES = ("parity", "mirror", "mod3", "panel")
+
+
+def family_mask(n, family="parity", B=None):
+    """where a member of the family may have an entry of Nn (boolean n x n, strictly lower)"""
+    i = np.arange(n)
+    r, c = i[:, None], i[None, :]
+    if family == "parity":
+        extra = (r % 2 == 1) & (c % 2 == 0)
+    elif family == "mirror":
+        extra = (r % 2 == 0) & (c % 2 == 1)
+    elif family == "mod3":
+        extra = r % 3 > c % 3
+    elif family == "panel":
+        if B is None or B <= 0 or B % NB:
+            raise ValueError(f"the panel family needs a tile size that is a multiple of {NB}, not {B}")
+        same_block = (r // B == c // B) & (r % B // NB == c % B // NB)  # a diagonal 128-block of a tile
+        extra = ~same_block | (r % 3 > c % 3)
+    else:
+        raise ValueError(f"unknown family {family!r}")
+    return extra & (r > c)
+
+
 @functools.lru_cache(maxsize=None)
-def nn(n, seed):
-    """Nn of order n (read-only)"""
+def nn(n, seed, family="parity", B=None):
+    """Nn of order n (read-only); B: the tile size, for the panel family only"""
     r = np.random.default_rng(seed)
     N = r.integers(-1, 2, (n, n)).astype(np.float64) * (r.random((n, n)) < 0.75)  # P(nonzero) = 2/3 * 3/4 = 1/2
-    i = np.arange(n)
-    N *= (i[:, None] % 2 == 1) & (i[None, :] % 2 == 0) & (i[:, None] > i[None, :])
+    N *= family_mask(n, family, B)
     N.setflags(write=False)
     return N
 
@@ -40,28 +77,28 @@ def _frozen(*arrays):
 
 
 @functools.lru_cache(maxsize=None)
-def cholesky_case(n, seed, smax=2):
+def cholesky_case(n, seed, smax=2, family="parity", B=None):
     """-> (A, L, s): A = L L^T, L = (I + Nn) diag(s), s_j a power of two <= smax (smax = 1: s = 1)"""
     r = np.random.default_rng(seed + 1000003)
     s = r.choice([1.0, 2.0, 4.0][:int(np.log2(smax)) + 1], n)
-    L = (np.eye(n) + nn(n, seed)) * s[None, :]
+    L = (np.eye(n) + nn(n, seed, family, B)) * s[None, :]
     return _frozen(L @ L.T, L, s)
 
 
 @functools.lru_cache(maxsize=None)
-def ldl_case(n, seed):
+def ldl_case(n, seed, family="parity", B=None):
     """-> (A, L, d): A = L diag(d) L^T, L = I + Nn, d_j = +-{1, 2, 4}"""
     r = np.random.default_rng(seed + 2000003)
     d = r.choice([1.0, 2.0, 4.0], n) * r.choice([-1.0, 1.0], n)
-    L = np.eye(n) + nn(n, seed)
+    L = np.eye(n) + nn(n, seed, family, B)
     return _frozen((L * d) @ L.T, L, d)
 
 
 @functools.lru_cache(maxsize=None)
-def sygst_case(n, seed):
+def sygst_case(n, seed, family="parity", B=None):
     """-> (A, L, M): A = L M L^T, L the Cholesky member's factor, M symmetric with integer entries in [-3, 3]"""
     r = np.random.default_rng(seed + 3000003)
-    _, L, _ = cholesky_case(n, seed)
+    _, L, _ = cholesky_case(n, seed, 2, family, B)
     M = r.integers(-3, 4, (n, n)).astype(np.float64)
     M = np.tril(M) + np.tril(M, -1).T
     return _frozen(L @ M @ L.T, L, M)
@@ -74,15 +111,22 @@ def solution(n, nrhs, seed):
     return _frozen(X)[0]
 
 
-def inv_factor(n, seed, smax=2):
-    """inv(L) of the Cholesky member, from the closed form diag(1/s) (I - Nn): multiples of 1/smax"""
-    _, _, s = cholesky_case(n, seed, smax)
-    return (np.eye(n) - nn(n, seed)) / s[:, None]
+def inv_factor(n, seed, smax=2, family="parity"):
+    """inv(L) of the Cholesky member, from the closed form diag(1/s) (I - Nn) -- mod3: diag(1/s) (I - Nn + Nn Nn), the
+    product in fp64 (integers far below 2^53): multiples of 1/smax.  Not for the panel family, whose inverse is huge"""
+    if family == "panel":
+        raise ValueError("the global inverse of a panel member is not a short dyadic number")
+    _, _, s = cholesky_case(n, seed, smax, family)
+    N = nn(n, seed, family)
+    X = np.eye(n) - N
+    if family == "mod3":
+        X += N @ N
+    return X / s[:, None]
 
 
-def inv_spd(n, seed, smax=2):
+def inv_spd(n, seed, smax=2, family="parity"):
     """inv(A) = inv(L)^T inv(L) of the Cholesky member in fp64 (exact: multiples of 1/smax^2, far below 2^53)"""
-    X = inv_factor(n, seed, smax)
+    X = inv_factor(n, seed, smax, family)
     return X.T @ X
 
 
@@ -131,6 +175,29 @@ def inv_lower(T, peak, unit=False):
     W[h:, :h] = -peak.mm(W[h:, h:], peak.mm(T[h:, :h], W[:h, :h]))
     peak.see(W)
     return W
+
+
+def inv_tile(T, peak):
+    """the inverse of a lower triangular tile as the library forms it for sygst, pocon and the tile level of trtri
+    (stage_factor_diag_into): the tile in an image of whole 128-blocks, the identity beyond it; the diagonal 128-blocks
+    by inv_lower; then block column c = n - 2 .. 0 of the inverse from the columns to its right, Y(m) = L(m,c) Xd(c) and
+    X(i,c) = - sum_{c < m <= i} X(i,m) Y(m) (each X(i,c) one sum in one accumulator: one product here).  One 128-block:
+    inv_lower itself"""
+    n = T.shape[0]
+    if n <= NB:
+        return inv_lower(T, peak)
+    P = padded(T, T.dtype)
+    nbk = P.shape[0] // NB
+    blk = lambda i: slice(i * NB, (i + 1) * NB)
+    for i in range(nbk):
+        P[blk(i), blk(i)] = inv_lower(P[blk(i), blk(i)], peak)
+    for c in range(nbk - 2, -1, -1):
+        below = slice((c + 1) * NB, nbk * NB)
+        Y = peak.mm(P[below, blk(c)], P[blk(c), blk(c)])
+        for i in range(c + 1, nbk):
+            P[blk(i), blk(c)] = -peak.mm(P[blk(i), (c + 1) * NB:(i + 1) * NB], Y[:(i - c) * NB])
+    peak.see(P)
+    return np.tril(P[:n, :n])
 
 
 def padded(A, dtype, nb=NB):
@@ -209,7 +276,8 @@ def ldl_blocked(A, dtype, nb=NB):
 
 def sygst_blocked(A, L, dtype, nb=NB):
     """-> (C, peak): the lower triangle of inv(L) A inv(L)^T by LAPACK's blocked DSYGST (itype 1, Lower) in nb-blocks
-    with the left solve of every block column deferred into one pass over the block rows (sygst_model.py)"""
+    with the left solve of every block column deferred into one pass over the block rows (sygst_model.py).  The
+    library's block is the tile, and it inverts the whole diagonal tile of L (inv_tile): nb = the tile size follows it"""
     dtype = np.dtype(dtype)
     n = A.shape[0]
     M = padded(A, dtype, nb)
@@ -218,7 +286,7 @@ def sygst_blocked(A, L, dtype, nb=NB):
     half = dtype.type(0.5)
     peak = Peak()
     peak.see(M, F)
-    Xd = [inv_lower(F[k:k + nb, k:k + nb], peak) for k in range(0, N, nb)]
+    Xd = [inv_tile(F[k:k + nb, k:k + nb], peak) for k in range(0, N, nb)]
     for b, k in enumerate(range(0, N, nb)):
         d, t = slice(k, k + nb), slice(k + nb, N)
         lo = np.tril(M[d, d])

@@ -1,9 +1,17 @@
-"""The panel chain, bit for bit: CHAMELEON_{d,s}potrf_Tile on the dyadic family of dyadic_model.py, whose factor every
-blocked algorithm must return exactly (test_dyadic_host.py proves that for the reference alone), in every form of the
-chain -- event-linked, counter-linked and flow; small-block and throughput TRSM steps; fused and split in-tile steps;
+"""The panel chain, bit for bit: CHAMELEON_{d,s}potrf_Tile on the dyadic families of dyadic_model.py, whose factor every
+blocked algorithm must return exactly (test_dyadic_host.py proves that for the reference alone, at every (family, order)
+of CASES and of the in-process tests), in every form of the chain -- event-linked, counter-linked and flow;
+small-block and throughput TRSM steps; fused and split in-tile steps;
 paired panels; gates and self-polling grids -- each forced through its environment switch in one fresh child process
 (the switches are read once, at chol_init).  Dense diagonal blocks, block inverses, in-tile solves and panel tiles
 throughout: a wrong hand-off, a skipped block column or a sign in the recursive inverse changes integers.
+
+Four families.  "parity" (entries at odd row, even column only) leaves half the rows and columns of the factor empty and
+makes every product of two off-diagonal pieces zero: the rank-1 update of every odd column of a diagonal block adds
+zeros, and the recursive inverse is right with or without the strictly lower part of W11.  "mirror" fills the other
+half; "mod3" (Nn^3 = 0) gives every inverse a second-order term; "panel" (tiles of whole 128-blocks only) is dense
+everywhere outside the diagonal 128-blocks, which follow mod3: every row and column of every panel tile and of every
+trailing update carries entries, and every K-loop of 128 sums dozens of non-zero products.
 
 In-process: the probe of the fp64 pivot chain (rsq + two Goldschmidt steps, no sqrt) at powers of four, ChamUpper, the
 single-tile POTRF and TRSM (alpha != 1 takes the throughput form on one tile; B = 200 the staged, padded path) and the
@@ -22,6 +30,12 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 SHAPES = [(512, 128), (1024, 256), (1536, 384), (2048, 512), (4096, 1024), (1000, 192), (1100, 320)]
+PANEL_SHAPES = [(N, B) for N, B in SHAPES if B % 128 == 0] + [(1000, 256), (1100, 384)]  # (two ragged orders on such tiles)
+THIN_SHAPES = [(1024, 256), (2048, 512), (1000, 192), (1100, 320)]
+CASES = ([("parity", N, B) for N, B in SHAPES] + [("panel", N, B) for N, B in PANEL_SHAPES]
+         + [(fam, N, B) for fam in ("mirror", "mod3") for N, B in THIN_SHAPES])
+FILL_CASES = [(fam, B) for fam in ("parity", "panel") for B in (256, 512)]
+NEW_FAMILIES = ("mirror", "mod3", "panel")
 PIPE_ALL = {"CHOLMI_PIPE_FACTOR": "100", "CHOLMI_PAIR_FACTOR": "1000"}
 FLOW_ALL = {"CHOLMI_FLOW_FACTOR": "100", "CHOLMI_PIPE_FACTOR": "100", "CHOLMI_PAIR_FACTOR": "1000"}
 
@@ -32,6 +46,22 @@ def npdt(dt):
 
 def chdt(ch, dt):
     return ch.ChamRealDouble if dt == "d" else ch.ChamRealFloat
+
+
+def member(fam, N, B):
+    """(A, L, s) of the Cholesky member of a family at order N (seed N); B, the tile size, shapes the panel family only"""
+    if fam == "parity":
+        return dm.cholesky_case(N, N)
+    return dm.cholesky_case(N, N, 2, fam, B if fam == "panel" else None)
+
+
+def with_families(shapes, one=lambda s: s):
+    """the (family, shape) parameters of an in-process test and their ids: today's ids for parity, the family in front
+    for the others, panel on tiles of whole 128-blocks only (one(shape): its tile size)"""
+    params = [("parity", s) for s in shapes] + [(fam, s) for fam in NEW_FAMILIES for s in shapes
+                                                 if fam != "panel" or one(s) % 128 == 0]
+    flat = [(fam,) + (s if isinstance(s, tuple) else (s,)) for fam, s in params]
+    return flat, ["-".join(str(x) for x in (f[1:] if f[0] == "parity" else f)) for f in flat]
 
 
 def bits(a):
@@ -52,7 +82,7 @@ def mismatches(got, want, B):
     return int(len(i)), where[:6]
 
 
-def factor_case(ch, N, B, dt, S, L):
+def factor_case(ch, fam, N, B, dt, S, L):
     """one whole-matrix factorisation of S (the Cholesky member as stored_lower leaves it) -> the record the child
     prints"""
     d = ch.CHAMELEON_Desc_Create(None, chdt(ch, dt), B, B, B * B, N, N, 0, 0, N, N, 1, 1)
@@ -62,12 +92,44 @@ def factor_case(ch, N, B, dt, S, L):
     ch.CHAMELEON_Desc_Destroy(d)
     low = np.tri(N, dtype=bool)
     count, where = mismatches(np.where(low, F, 0), L, B)
-    return {"N": N, "B": B, "dt": dt, "info": int(info), "mismatches": count, "first": where,
+    return {"family": fam, "N": N, "B": B, "dt": dt, "info": int(info), "mismatches": count, "first": where,
             "upper_touched": int(((bits(F) != bits(S)) & ~low).sum()), "regimes": ch.last_potrf_regimes()}
 
 
-def child_main():
-    """every shape in fp64 and fp32 under the switches of this process's environment, one record per case"""
+def chain_inputs(fam, N, B):
+    """-> (S, L) in fp32: A as stored_lower leaves it and the factor (integers far below 2^24: the fp32 image holds them
+    exactly, and the fp64 inputs are its widening)"""
+    A, L, _ = member(fam, N, B)
+    return stored_lower(A, "s"), L.astype(np.float32)
+
+
+_inputs_file = None
+
+
+def inputs_file():
+    """the inputs of every case, built once per session and handed to the children: each of the fifteen would
+    otherwise spend its first seconds on the same random draws and L L^T products"""
+    global _inputs_file
+    if _inputs_file is None:
+        import atexit
+        import tempfile
+
+        fd, path = tempfile.mkstemp(prefix="chain_exact_", suffix=".npz")
+        os.close(fd)
+        atexit.register(lambda: os.path.exists(path) and os.remove(path))
+        arrays = {}
+        for fam, N, B in CASES:  # (small integers: A as int16 and L as int8 keep the file at a tenth of the fp32 images)
+            A, L, _ = member(fam, N, B)
+            assert np.abs(A).max() < 2 ** 15 and np.abs(L).max() < 2 ** 7
+            arrays[f"A_{fam}_{N}_{B}"], arrays[f"L_{fam}_{N}_{B}"] = np.tril(A).astype(np.int16), L.astype(np.int8)
+        np.savez(path, **arrays)
+        _inputs_file = path
+    return _inputs_file
+
+
+def child_main(inputs=None):
+    """every case in fp64 and fp32 under the switches of this process's environment, one record per case; inputs: the
+    parent's file of inputs (without one the child builds them itself)"""
     import time
 
     t0 = time.perf_counter()
@@ -76,18 +138,26 @@ def child_main():
 
     ch.CHAMELEON_Init(1, 1)
     t1 = time.perf_counter()
-    for N, B in SHAPES:
-        A, L, _ = dm.cholesky_case(N, N)
-        S = stored_lower(A, "s")  # (integers far below 2^24: the fp32 image holds them exactly)
-        Ls = L.astype(np.float32)
+    held = np.load(inputs) if inputs else None
+    for fam, N, B in CASES:
+        if held is not None:
+            S, Ls = stored_lower(held[f"A_{fam}_{N}_{B}"], "s"), held[f"L_{fam}_{N}_{B}"].astype(np.float32)
+        else:
+            S, Ls = chain_inputs(fam, N, B)
         for dt in ("d", "s"):
-            rec = factor_case(ch, N, B, dt, S.astype(npdt(dt)), Ls.astype(npdt(dt)))
+            rec = factor_case(ch, fam, N, B, dt, S.astype(npdt(dt)), Ls.astype(npdt(dt)))
             print("CASE " + json.dumps(rec), flush=True)
     print(f"TIME start-up {t1 - t0:.2f} s, cases {time.perf_counter() - t1:.2f} s", flush=True)
 
 
 def nbm_of(c):
     return -(-c["B"] // 128)
+
+
+def four_tiles(cases):
+    """the cases with at least four tiles per side: a head tile, a far column, room for a pair from wave 1 (every shape
+    but the ragged (1100, 384) of the panel family, which has three)"""
+    return [c for c in cases if -(-c["N"] // c["B"]) >= 4]
 
 
 def counter_linked(cases):
@@ -99,7 +169,7 @@ def event_linked(cases):
 
 
 def paired(cases):
-    assert all(c["regimes"]["paired"] >= 1 for c in cases), cases
+    assert all(c["regimes"]["paired"] >= 1 for c in four_tiles(cases)), cases
 
 
 def near_off(cases):
@@ -109,7 +179,7 @@ def near_off(cases):
 
 def near_on(cases):
     counter_linked(cases)
-    assert all(c["regimes"]["near_column"] >= 1 for c in cases), cases
+    assert all(c["regimes"]["near_column"] >= 1 for c in four_tiles(cases)), cases
     assert all(c["regimes"]["column_latency_form"] >= 1 for c in cases if nbm_of(c) <= 4), cases
 
 
@@ -139,12 +209,13 @@ SETTINGS = [
 @pytest.mark.parametrize("name,env,regime", SETTINGS, ids=[s[0] for s in SETTINGS])
 def test_potrf_is_exact_in_every_form_of_the_chain(name, env, regime):
     """every shape (nbm = 1, 2, 3, 4, 8 with four tiles per side: a head tile, a far column, room for a pair from wave 1;
-    two ragged orders with odd tiles and identity padding), fp64 and fp32, in one child per setting: info = 0, tril(F) ==
-    L with zero mismatches, the NaN-filled strict upper triangle untouched, and -- where the setting forces a regime --
-    the library's count says that it ran"""
+    two ragged orders with odd tiles and identity padding) on the parity family, the panel family on the tiles of whole
+    128-blocks (and two ragged orders on such tiles), mirror and mod3 on nbm = 2, 4 and the two ragged orders (CASES),
+    fp64 and fp32, in one child per setting: info = 0, tril(F) == L with zero mismatches, the NaN-filled strict upper
+    triangle untouched, and -- where the setting forces a regime -- the library's count says that it ran"""
     try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, **env), capture_output=True,
-                           text=True, timeout=300)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "cases", inputs_file()], env=dict(os.environ, **env),
+                           capture_output=True, text=True, timeout=300)
     except subprocess.TimeoutExpired as e:
         pytest.exit(f"the child of setting {name} hung: nothing more is started on this GPU ({e.stdout})", returncode=3)
     print(r.stdout)
@@ -153,7 +224,7 @@ def test_potrf_is_exact_in_every_form_of_the_chain(name, env, regime):
                     f"{r.stdout}\n{r.stderr[-2000:]}", returncode=3)
     assert r.returncode == 0, (r.stdout, r.stderr[-2000:])
     cases = [json.loads(ln[5:]) for ln in r.stdout.splitlines() if ln.startswith("CASE ")]
-    assert [(c["N"], c["B"], c["dt"]) for c in cases] == [(N, B, dt) for N, B in SHAPES for dt in "ds"]
+    assert [(c["family"], c["N"], c["B"], c["dt"]) for c in cases] == [(fam, N, B, dt) for fam, N, B in CASES for dt in "ds"]
     bad = [c for c in cases if c["info"] != 0 or c["mismatches"] or c["upper_touched"]]
     assert not bad, bad
     if regime:
@@ -166,12 +237,13 @@ def fill_child_main():
     from dense_linear_app_amd import chameleon as ch
 
     ch.CHAMELEON_Init(1, 1)
-    for B in (256, 512):
-        A, L, _ = dm.cholesky_case(B, B)
+    for fam, B in FILL_CASES:
+        A, L, _ = member(fam, B, B)
         for dt in ("d", "s"):
             info, T, S = potrf_tile(ch, A, dt, fill=-7.0)
             iu = np.triu_indices(B, 1)
-            rec = {"B": B, "dt": dt, "info": int(info), "mismatches": mismatches(np.tril(T), L.astype(npdt(dt)), B)[0],
+            rec = {"family": fam, "B": B, "dt": dt, "info": int(info),
+                   "mismatches": mismatches(np.tril(T), L.astype(npdt(dt)), B)[0],
                    "upper_touched": int((bits(T[iu]) != bits(S[iu])).sum())}
             print("CASE " + json.dumps(rec), flush=True)
 
@@ -180,7 +252,8 @@ def fill_child_main():
 def test_intile_update_leaves_a_finite_upper_triangle_alone(fused):
     """the diagonal 64 x 64 blocks of the in-tile update write i >= j only.  Above the diagonal the other cases hold NaN,
     and NaN - x stores the same NaN back: an update that lost its mask would pass them.  Here the strict upper triangle
-    is -7, one tile of 2 and of 4 blocks (one and three in-tile steps), fp64 and fp32, the solve and the update of a step
+    is -7, one tile of 2 and of 4 blocks (one and three in-tile steps), the parity and the panel family (whose in-tile
+    update touches every entry of the diagonal blocks' lower triangles), fp64 and fp32, the solve and the update of a step
     in one launch and in two: L exact, and not one bit above the diagonal changed"""
     try:
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "finite-fill"],
@@ -193,7 +266,7 @@ def test_intile_update_leaves_a_finite_upper_triangle_alone(fused):
                     f"{r.stdout}\n{r.stderr[-2000:]}", returncode=3)
     assert r.returncode == 0, (r.stdout, r.stderr[-2000:])
     cases = [json.loads(ln[5:]) for ln in r.stdout.splitlines() if ln.startswith("CASE ")]
-    assert [(c["B"], c["dt"]) for c in cases] == [(B, dt) for B in (256, 512) for dt in "ds"]
+    assert [(c["family"], c["B"], c["dt"]) for c in cases] == [(fam, B, dt) for fam, B in FILL_CASES for dt in "ds"]
     bad = [c for c in cases if c["info"] != 0 or c["mismatches"] or c["upper_touched"]]
     assert not bad, bad
 
@@ -228,11 +301,16 @@ def test_pivot_chain_is_exact_at_powers_of_four(cham, dt):
     assert mismatches(np.tril(T), L.astype(npdt(dt)), 128)[0] == 0
 
 
-@pytest.mark.parametrize("N,B", [(1024, 256), (1000, 192)])
+UPPER = with_families([(1024, 256), (1000, 192)], lambda s: s[1])
+ONE_TILE = with_families([128, 256, 512, 1024, 200])
+WAVE = with_families([(1024, 256), (1536, 512)], lambda s: s[1])
+
+
+@pytest.mark.parametrize("fam,N,B", UPPER[0], ids=UPPER[1])
 @pytest.mark.parametrize("dt", ["d", "s"])
-def test_potrf_upper_is_exact(cham, N, B, dt):
+def test_potrf_upper_is_exact(cham, fam, N, B, dt):
     ch = cham
-    A, L, _ = dm.cholesky_case(N, N)
+    A, L, _ = member(fam, N, B)
     S = np.array(stored_lower(A, dt).T, order="F")
     d = ch.CHAMELEON_Desc_Create(None, chdt(ch, dt), B, B, B * B, N, N, 0, 0, N, N, 1, 1)
     d.from_lapack(S)
@@ -244,13 +322,13 @@ def test_potrf_upper_is_exact(cham, N, B, dt):
     assert np.array_equal(bits(F[il]), bits(S[il]))
 
 
-@pytest.mark.parametrize("B", [128, 256, 512, 1024, 200])
+@pytest.mark.parametrize("fam,B", ONE_TILE[0], ids=ONE_TILE[1])
 @pytest.mark.parametrize("dt", ["d", "s"])
-def test_single_tile_potrf_and_trsm_are_exact(cham, B, dt):
+def test_single_tile_potrf_and_trsm_are_exact(cham, fam, B, dt):
     """one tile: POTRF returns L; TRSM (Right, Lower, Trans, NonUnit, alpha) on X L^T returns alpha X -- alpha = 1 in the
     small-block form, alpha = -2 and 1/2 through k_panel_solve / k_panel_update"""
     ch = cham
-    A, L, _ = dm.cholesky_case(B, B)
+    A, L, _ = member(fam, B, B)
     info, T, S = potrf_tile(ch, A, dt)
     assert info == 0
     assert mismatches(np.tril(T), L.astype(npdt(dt)), B) == (0, [])
@@ -270,13 +348,13 @@ def test_single_tile_potrf_and_trsm_are_exact(cham, B, dt):
     ch.CHAMELEON_Desc_Destroy(dl)
 
 
-@pytest.mark.parametrize("N,B", [(1024, 256), (1536, 512)])
-def test_wave_level_task_path_is_exact(cham, N, B):
+@pytest.mark.parametrize("fam,N,B", WAVE[0], ids=WAVE[1])
+def test_wave_level_task_path_is_exact(cham, fam, N, B):
     """the worker / client route (every ready task of a wave in one ExecuteBatch) and the per-task route: exactly L"""
     from dense_linear_app_amd import client
     from dense_linear_app_amd.worker import DagCholeskyWorker
 
-    A, L, _ = dm.cholesky_case(N, N)
+    A, L, _ = member(fam, N, B)
     Af = np.array(A, order="F")
     wave = client.run_cholesky_dag(N, B, A=Af, device_results=True, batched=True, worker=DagCholeskyWorker())
     assert mismatches(wave.lower_factor(), L, B) == (0, [])
@@ -285,4 +363,4 @@ def test_wave_level_task_path_is_exact(cham, N, B):
 
 
 if __name__ == "__main__":
-    fill_child_main() if sys.argv[1:] == ["finite-fill"] else child_main()
+    fill_child_main() if sys.argv[1:] == ["finite-fill"] else child_main(sys.argv[2] if sys.argv[1:2] == ["cases"] else None)

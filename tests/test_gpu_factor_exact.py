@@ -1,9 +1,16 @@
-"""What consumes the factor, bit for bit, on the dyadic family of dyadic_model.py (dense diagonal blocks and panels,
-every intermediate a short dyadic number; test_dyadic_host.py proves the reference alone exact in fp32 and fp64 at these
-orders): potrs / posv, trtri, potri / poinv, lansy, porfs / posvx on the exact solution, dsposv, the L D L^T
+"""What consumes the factor, bit for bit, on the dyadic families of dyadic_model.py (dense diagonal blocks and panels,
+every intermediate a short dyadic number; test_dyadic_host.py proves the reference alone exact in fp32 and fp64 at every
+(routine, family, order) used here): potrs / posv, trtri, potri / poinv, lansy, porfs / posvx on the exact solution,
+dsposv, the L D L^T
 factorisation and its solves, and sygst -- fp64 and fp32, Lower and Upper, a tile-multiple order, a ragged one with an
 odd tile, and three tiles of 512.  The factor-consuming routines are fed the exact L directly, so they do not depend on
-potrf; posv, poinv, posvx and dsposv run the factorisation themselves."""
+potrf; posv, poinv, posvx and dsposv run the factorisation themselves.
+
+The families: "parity" (half the rows and columns of the factor empty, every product of two off-diagonal pieces zero),
+"mirror" (the other half), "mod3" (Nn^3 = 0: a second-order term in every inverse) and "panel" (dense outside the
+diagonal 128-blocks, on tiles of whole 128-blocks only).  The global inverse of a panel member reaches 1e13 at order
+1024 and 5e19 at 1536 -- no short dyadic number -- so whatever forms inv(L) or inv(A), or measures them, runs on mirror
+and mod3 only: trtri, potri / poinv and porfs / posvx (whose rcond is an estimate of |inv(A)|)."""
 import numpy as np
 import pytest
 
@@ -12,6 +19,41 @@ import dyadic_model as dm
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1024, 256), (1000, 192), (1536, 512)]
+
+
+def cases(shapes, families):
+    """-> (parameters (family, N, B), ids): parity under the ids the shapes alone had, the family in front for the
+    others; panel on tiles of whole 128-blocks only"""
+    ps = [(fam, N, B) for fam in ("parity",) + families for N, B in shapes if fam != "panel" or B % 128 == 0]
+    return {"argvalues": ps, "ids": ["-".join(str(x) for x in (p[1:] if p[0] == "parity" else p)) for p in ps]}
+
+
+SOLVES = cases(SHAPES, ("mirror", "mod3", "panel"))
+INVERSES = cases(SHAPES, ("mirror", "mod3"))
+LDL = cases(SHAPES + [(700, 128)], ("mirror", "mod3", "panel"))
+SYGST = cases(SHAPES + [(1100, 128)], ("mirror", "mod3", "panel"))
+
+
+def split(cs, fp64_only):
+    """-> (the cases that run in both types, those of fp64_only with their ids)"""
+    keep = [(p, i) for p, i in zip(cs["argvalues"], cs["ids"]) if p not in fp64_only]
+    assert all(p in cs["argvalues"] for p in fp64_only)
+    return ({"argvalues": [p for p, _ in keep], "ids": [i for _, i in keep]},
+            {"argvalues": fp64_only, "ids": ["-".join(str(x) for x in p) for p in fp64_only]})
+
+
+# Not everything the library inverts is a 128-block: sygst multiplies by the inverse of the whole diagonal tile of L, and
+# the backward sweep of potrs (so posv, dsposv, sytrs, sysv) by the transposed inverse of the whole diagonal tile.  On
+# the panel family such an inverse is large -- magnitude 5e2 for a tile of 256, 2e6 for one of 512 -- and the host
+# proofs (test_dyadic_host.py, which follow the library there) leave the range of fp32: for sygst on both tile sizes,
+# for the solves on 512.  Those shapes run in fp64 only; dsposv, whose solves are fp32, does not run there at all.
+SYGST, SYGST_FP64_ONLY = split(SYGST, [("panel", 1024, 256), ("panel", 1536, 512)])
+SOLVES, SOLVES_FP64_ONLY = split(SOLVES, [("panel", 1536, 512)])
+LDL, LDL_FP64_ONLY = split(LDL, [("panel", 1536, 512)])
+
+
+def fam_kw(fam, B):
+    return {} if fam == "parity" else {"family": fam, "B": B} if fam == "panel" else {"family": fam}
 
 
 def npdt(dt):
@@ -66,22 +108,34 @@ def other_kept(F, S, u):
     return np.array_equal(bits(F[idx]), bits(S[idx]))
 
 
-def rhs(N, nrhs):
+def rhs(fam, N, B, nrhs):
     """(X, A X): integers, exact in fp64 and in fp32"""
-    A, _, _ = dm.cholesky_case(N, N)
+    A, _, _ = dm.cholesky_case(N, N, **fam_kw(fam, B))
     X = dm.solution(N, nrhs, N)
     return X, A @ X
 
 
-@pytest.mark.parametrize("N,B", SHAPES)
+@pytest.mark.parametrize("fam,N,B", **SOLVES)
 @pytest.mark.parametrize("nrhs", [1, 5, 300])
 @pytest.mark.parametrize("u", ["L", "U"])
 @pytest.mark.parametrize("dt", ["d", "s"])
-def test_potrs_and_posv(cham, N, B, nrhs, u, dt):
+def test_potrs_and_posv(cham, fam, N, B, nrhs, u, dt):
     """the solution is the integer X; after posv A holds L"""
-    ch = cham
-    A, L, _ = dm.cholesky_case(N, N)
-    X, Bm = rhs(N, nrhs)
+    potrs_and_posv_are_exact(cham, fam, N, B, nrhs, u, dt)
+
+
+@pytest.mark.parametrize("fam,N,B", **SOLVES_FP64_ONLY)
+@pytest.mark.parametrize("nrhs", [1, 5, 300])
+@pytest.mark.parametrize("u", ["L", "U"])
+def test_potrs_and_posv_on_wide_panel_tiles_in_fp64(cham, fam, N, B, nrhs, u):
+    """the panel family on tiles of 512: the backward sweep multiplies by the inverse of a whole diagonal tile, of
+    magnitude 2e6 there -- exact in fp64, out of the range of fp32 (the host proof says so; no fp32 case)"""
+    potrs_and_posv_are_exact(cham, fam, N, B, nrhs, u, "d")
+
+
+def potrs_and_posv_are_exact(ch, fam, N, B, nrhs, u, dt):
+    A, L, _ = dm.cholesky_case(N, N, **fam_kw(fam, B))
+    X, Bm = rhs(fam, N, B, nrhs)
     SL = stored(L, u, dt)
     dA, dB = desc(ch, N, B, dt, content=SL), desc(ch, N, B, dt, nrhs, Bm)
     assert ch.CHAMELEON_dpotrs_Tile(uplo(ch, u), dA, dB) == 0
@@ -99,30 +153,32 @@ def test_potrs_and_posv(cham, N, B, nrhs, u, dt):
     ch.CHAMELEON_Desc_Destroy(dB)
 
 
-@pytest.mark.parametrize("N,B", SHAPES)
+@pytest.mark.parametrize("fam,N,B", **INVERSES)
 @pytest.mark.parametrize("u", ["L", "U"])
 @pytest.mark.parametrize("dt", ["d", "s"])
-def test_trtri(cham, N, B, u, dt):
-    """inv(L) = diag(1/s) (I - Nn); the other triangle untouched"""
+def test_trtri(cham, fam, N, B, u, dt):
+    """inv(L) = diag(1/s) (I - Nn), mod3: diag(1/s) (I - Nn + Nn Nn); the other triangle untouched.  (Not panel: its
+    inverse is no short dyadic number)"""
     ch = cham
-    _, L, _ = dm.cholesky_case(N, N)
+    _, L, _ = dm.cholesky_case(N, N, **fam_kw(fam, B))
     S = stored(L, u, dt)
     d = desc(ch, N, B, dt, content=S)
     assert ch.CHAMELEON_dtrtri_Tile(uplo(ch, u), ch.ChamNonUnit, d) == 0
     F = d.to_lapack()
     ch.CHAMELEON_Desc_Destroy(d)
-    same(lower_of(F, u), dm.inv_factor(N, N), dt)
+    same(lower_of(F, u), dm.inv_factor(N, N, family=fam), dt)
     assert other_kept(F, S, u)
 
 
-@pytest.mark.parametrize("N,B", SHAPES)
+@pytest.mark.parametrize("fam,N,B", **INVERSES)
 @pytest.mark.parametrize("u", ["L", "U"])
 @pytest.mark.parametrize("dt", ["d", "s"])
-def test_potri_and_poinv(cham, N, B, u, dt):
-    """inv(A) = inv(L)^T inv(L) from the closed form (multiples of 1/4): potri from the exact factor, poinv from A"""
+def test_potri_and_poinv(cham, fam, N, B, u, dt):
+    """inv(A) = inv(L)^T inv(L) from the closed form (multiples of 1/4): potri from the exact factor, poinv from A.
+    (Not panel: its inverse is no short dyadic number)"""
     ch = cham
-    A, L, _ = dm.cholesky_case(N, N)
-    want = np.tril(dm.inv_spd(N, N))
+    A, L, _ = dm.cholesky_case(N, N, **fam_kw(fam, B))
+    want = np.tril(dm.inv_spd(N, N, family=fam))
     for call, M in ((ch.CHAMELEON_dpotri_Tile, L), (ch.CHAMELEON_dpoinv_Tile, A)):
         S = stored(M, u, dt)
         d = desc(ch, N, B, dt, content=S)
@@ -150,16 +206,17 @@ def test_lansy(cham, N, B, u, dt):
     ch.CHAMELEON_Desc_Destroy(d)
 
 
-@pytest.mark.parametrize("N,B", SHAPES)
+@pytest.mark.parametrize("fam,N,B", **INVERSES)
 @pytest.mark.parametrize("u", ["L", "U"])
 @pytest.mark.parametrize("dt", ["d", "s"])
-def test_porfs_and_posvx_on_the_exact_solution(cham, N, B, u, dt):
+def test_porfs_and_posvx_on_the_exact_solution(cham, fam, N, B, u, dt):
     """porfs on the exact X: the residual is exactly zero, so berr == 0 and X comes back bit for bit; posvx with
     fact = N (A needs no equilibration) returns X.  (X without zeros: a row of A with two entries -- the last even row
     has no more -- times a zero in both places has the weight |b| + |A| |x| = 0, for which LAPACK's rule, and the
-    library's, gives berr = (0 + safe1) / (0 + safe1) = 1.)"""
+    library's, gives berr = (0 + safe1) / (0 + safe1) = 1.)  Not panel: the error bound and the condition estimate
+    sweep with inv(A), which is no short dyadic number there"""
     ch = cham
-    A, L, _ = dm.cholesky_case(N, N)
+    A, L, _ = dm.cholesky_case(N, N, **fam_kw(fam, B))
     nrhs = 5
     X = dm.solution(N, nrhs, N)
     X = np.where(X == 0, 1.0, X)
@@ -184,15 +241,15 @@ def test_porfs_and_posvx_on_the_exact_solution(cham, N, B, u, dt):
         ch.CHAMELEON_Desc_Destroy(d)
 
 
-@pytest.mark.parametrize("N,B", SHAPES)
+@pytest.mark.parametrize("fam,N,B", **SOLVES)
 @pytest.mark.parametrize("u", ["L", "U"])
-def test_dsposv(cham, N, B, u):
+def test_dsposv(cham, fam, N, B, u):
     """the fp32 factor is exact, so the first solve is: the residual is zero, iter = 0 (the loop of dsposv_mixed leaves
     at its first convergence test, after one solve and one residual pass), X bit for bit"""
     ch = cham
-    A, _, _ = dm.cholesky_case(N, N)
+    A, _, _ = dm.cholesky_case(N, N, **fam_kw(fam, B))
     nrhs = 5
-    X, Bm = rhs(N, nrhs)
+    X, Bm = rhs(fam, N, B, nrhs)
     SA = stored(A, u, "d")
     dA, dB, dX = desc(ch, N, B, "d", content=SA), desc(ch, N, B, "d", nrhs, Bm), desc(ch, N, B, "d", nrhs)
     info, it = ch.CHAMELEON_dsposv_Tile(uplo(ch, u), dA, dB, dX)
@@ -204,13 +261,25 @@ def test_dsposv(cham, N, B, u):
         ch.CHAMELEON_Desc_Destroy(d)
 
 
-@pytest.mark.parametrize("N,B", SHAPES + [(700, 128)])
+@pytest.mark.parametrize("fam,N,B", **LDL)
 @pytest.mark.parametrize("u", ["L", "U"])
 @pytest.mark.parametrize("dt", ["d", "s"])
-def test_sytrf_sytrs_sysv_nopiv(cham, N, B, u, dt):
+def test_sytrf_sytrs_sysv_nopiv(cham, fam, N, B, u, dt):
     """the L D L^T member: (L, d), the inertia and the stats exact; both solves return the integer X"""
-    ch = cham
-    A, L, dd = dm.ldl_case(N, N)
+    ldl_is_exact(cham, fam, N, B, u, dt)
+
+
+@pytest.mark.parametrize("fam,N,B", **LDL_FP64_ONLY)
+@pytest.mark.parametrize("u", ["L", "U"])
+@pytest.mark.parametrize("dt", ["d", "s"])
+def test_sytrf_sytrs_sysv_nopiv_on_wide_panel_tiles(cham, fam, N, B, u, dt):
+    """the panel family on tiles of 512: the factorisation in both types (it inverts 128-blocks only); the solves, whose
+    backward sweep multiplies by the inverse of a whole diagonal tile, in fp64 alone"""
+    ldl_is_exact(cham, fam, N, B, u, dt, solves=dt == "d")
+
+
+def ldl_is_exact(ch, fam, N, B, u, dt, solves=True):
+    A, L, dd = dm.ldl_case(N, N, **fam_kw(fam, B))
     nrhs = 5
     X = dm.solution(N, nrhs, N)
     Bm = A @ X
@@ -230,23 +299,36 @@ def test_sytrf_sytrs_sysv_nopiv(cham, N, B, u, dt):
     assert ch.CHAMELEON_dsytrf_nopiv_Tile(uplo(ch, u), dA) == 0
     check_factor()
     assert ch.CHAMELEON_dsytrs_nopiv_Tile(uplo(ch, u), dA, dB) == 0
-    same(dB.to_lapack(), X, dt)
+    if solves:
+        same(dB.to_lapack(), X, dt)
     dA.from_lapack(SA)
     dB.from_lapack(Bm.astype(npdt(dt)))
     assert ch.CHAMELEON_dsysv_nopiv_Tile(uplo(ch, u), dA, dB) == 0
     check_factor()
-    same(dB.to_lapack(), X, dt)
+    if solves:
+        same(dB.to_lapack(), X, dt)
     ch.CHAMELEON_Desc_Destroy(dA)
     ch.CHAMELEON_Desc_Destroy(dB)
 
 
-@pytest.mark.parametrize("N,B", SHAPES + [(1100, 128)])
+@pytest.mark.parametrize("fam,N,B", **SYGST)
 @pytest.mark.parametrize("u", ["L", "U"])
 @pytest.mark.parametrize("dt", ["d", "s"])
-def test_sygst(cham, N, B, u, dt):
+def test_sygst(cham, fam, N, B, u, dt):
     """inv(L) (L M L^T) inv(L)^T = M, every tile of L and of the panels dense"""
-    ch = cham
-    A, L, M = dm.sygst_case(N, N)
+    sygst_is_exact(cham, fam, N, B, u, dt)
+
+
+@pytest.mark.parametrize("fam,N,B", **SYGST_FP64_ONLY)
+@pytest.mark.parametrize("u", ["L", "U"])
+def test_sygst_on_wide_panel_tiles_in_fp64(cham, fam, N, B, u):
+    """the panel family on tiles of 256 and 512: the inverse of a whole diagonal tile (second- to sixth-order terms)
+    enters every product.  fp64 only: the host emulation proves these two exact there and not in fp32"""
+    sygst_is_exact(cham, fam, N, B, u, "d")
+
+
+def sygst_is_exact(ch, fam, N, B, u, dt):
+    A, L, M = dm.sygst_case(N, N, **fam_kw(fam, B))
     SA, SB = stored(A, u, dt), stored(L, u, dt, fill=-7.0)
     dA, dB = desc(ch, N, B, dt, content=SA), desc(ch, N, B, dt, content=SB)
     assert ch.CHAMELEON_dsygst_Tile(1, uplo(ch, u), dA, dB) == 0
