@@ -72,6 +72,9 @@ def lib() -> C.CDLL:
         "chol_last_pstrf_stats": ([C.POINTER(d)], i),
         "chol_sygst_tile": ([i, i, vp, vp], i),
         "chol_last_sygst_stats": ([C.POINTER(d)], i),
+        "chol_chud_tile": ([i, vp, vp], i),
+        "chol_chdd_tile": ([i, vp, vp], i),
+        "chol_last_chud_stats": ([C.POINTER(d)], i),
         "chol_sytrf_nopiv_tile": ([i, vp], i),
         "chol_sytrs_nopiv_tile": ([i, vp, vp], i),
         "chol_sysv_nopiv_tile": ([i, vp, vp], i),

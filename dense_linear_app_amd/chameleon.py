@@ -398,6 +398,30 @@ def last_sygst_stats() -> dict:
             "steps": int(v[5])}
 
 
+def CHAMELEON_dchud_Tile(uplo: int, A: Desc, V: Desc) -> int:
+    """LINPACK DCHUD for r vectors (MATLAB cholupdate): A, the factor chol_potrf_tile(uplo, .) returned, <- the factor
+    of L L^T + V V^T in O(n^2 r) operations; V (n x r) is workspace and is overwritten.  Returns 0, or info > 0: the
+    1-based index of a zero on the factor's diagonal (A and V unchanged)."""
+    return check("chol_chud_tile", lib().chol_chud_tile(uplo, A.handle, V.handle))
+
+
+def CHAMELEON_dchdd_Tile(uplo: int, A: Desc, V: Desc) -> int:
+    """LINPACK DCHDD for r vectors: A <- the factor of L L^T - V V^T; V (n x r) is workspace.  Returns 0, or info > 0:
+    a zero at L(info, info) (A and V unchanged), or the leading minor of order info of L L^T - V V^T is not positive
+    definite (A and V unspecified: keep a copy of the factor if it is needed)."""
+    return check("chol_chdd_tile", lib().chol_chdd_tile(uplo, A.handle, V.handle))
+
+
+def last_chud_stats() -> dict:
+    """The last CHAMELEON_dchud_Tile / dchdd_Tile (chol_last_chud_stats): total, chain (generators and in-tile
+    appliers) and bulk applier time [ms], r, the passes over the matrix, and the vector at which a downdate stopped
+    (-1: none)."""
+    v = (C.c_double * 8)()
+    check("chol_last_chud_stats", lib().chol_last_chud_stats(v))
+    return {"total_ms": v[0], "chain_ms": v[1], "bulk_ms": v[2], "r": int(v[3]), "passes": int(v[4]),
+            "stop_vector": int(v[5])}
+
+
 def CHAMELEON_dsytrf_nopiv_Tile(uplo: int, A: Desc) -> int:
     """A = L D L^T (ChamLower) or U^T D U (ChamUpper) without pivoting, for symmetric matrices whose factorisation
     needs none (quasi-definite, diagonally dominant): on return D on the diagonal of A and the unit triangular factor
@@ -484,6 +508,8 @@ CHAMELEON_sporfs_Tile = CHAMELEON_dporfs_Tile
 CHAMELEON_sposvx_Tile = CHAMELEON_dposvx_Tile
 CHAMELEON_spstrf_Tile = CHAMELEON_dpstrf_Tile
 CHAMELEON_ssygst_Tile = CHAMELEON_dsygst_Tile
+CHAMELEON_schud_Tile = CHAMELEON_dchud_Tile
+CHAMELEON_schdd_Tile = CHAMELEON_dchdd_Tile
 CHAMELEON_ssytrf_nopiv_Tile = CHAMELEON_dsytrf_nopiv_Tile
 CHAMELEON_ssytrs_nopiv_Tile = CHAMELEON_dsytrs_nopiv_Tile
 CHAMELEON_ssysv_nopiv_Tile = CHAMELEON_dsysv_nopiv_Tile

@@ -463,6 +463,30 @@ void launch_sygst_diag(hipStream_t s, T *D, int e, int nv, const T *X, int E, T 
 template <typename T>
 void launch_sygst_solve_row(hipStream_t s, T *A, const T *L, long bs, int lmt, int E, int m, const T *Xd, T *y);
 
+// ---- launchers (chud.hip): chol_chud_tile / chol_chdd_tile (LINPACK DCHUD / DCHDD, Lower) on a single-process image ----
+constexpr int CHUD_GROUP = 16;  // the vectors of one pass: a lane of the appliers keeps that many entries of V in registers
+// the vectors g0 .. of an n x r image with the factor's row tiling: vector t, stored row r of tile row I at
+// p + ((t / mb) lmt + I) bs + (t % mb) ld + r
+template <typename T>
+struct ChudVecs {
+  T *p;
+  long bs;
+  int ld, lmt, mb, g0;
+};
+// columns c0 .. c0+nc-1 (nc <= 128) of the diagonal tile D (ld e; tile row I of V) against rg <= CHUD_GROUP vectors:
+// the nc x nc diagonal block and its rows of V rotated in place, tab[((c0 + j) rg + t) 4 ..] <- (c, s, ci, sigma s) of
+// column c0 + j and vector g0 + t (chud_rot.h).  info[0..1] <- (col1 + j, g0 + t) at a rotation whose rr^2 is not
+// positive, when that column comes before the one already recorded (0: none)
+template <typename T>
+void launch_chud_gen(hipStream_t s, T *D, int e, int c0, int nc, const ChudVecs<T> &V, int I, int rg, T sigma, T *tab,
+                     int *info, int col1);
+// the rotations of columns c0 .. c0+nc-1 of tile column k applied to the stored rows [r0, r1) counted from the top of
+// the diagonal tile (tile (k + i, k) at Acol + i bs, ld e); rows outside the matrix (beyond mb in a tile, beyond n)
+// are neither read nor written
+template <typename T>
+void launch_chud_apply(hipStream_t s, T *Acol, long bs, int e, int mb, long n, int k, long r0, long r1, int c0, int nc,
+                       const T *tab, const ChudVecs<T> &V, int rg);
+
 // ---- launchers (sytrf.hip): chol_sytrf_nopiv_tile / chol_sytrs_nopiv_tile (A = L D L^T, Lower) on a single-process image ----
 // one diagonal tile (e x e, ld e, e % 128 == 0) <- its factor in place, by 128-block steps: D on the diagonal, the unit
 // lower triangular L below it, the strict upper triangle not touched.  Wt: one tile of scratch; Lc, winv: e / 128 blocks

@@ -1,7 +1,8 @@
 // The routines of libcholmi.so that work from a factor (include/cholmi.h), one section each below: the SPD solve, the
 // mixed-precision solve, the inverse, the condition estimate, the expert solve with error bounds, the pivoted
 // factorisation, the reduction of the generalized symmetric-definite eigenproblem, the L D L^T factorisation without
-// pivoting with its solve, and their butterfly-randomised forms; the entry points come last.  All run on the main
+// pivoting with its solve, their butterfly-randomised forms, and the rank-r update and downdate of a factor; the entry
+// points come last.  All run on the main
 // stream of the context that api.hip keeps (api_internal.h); this file owns only its scratch and the statistics of the
 // last call of each family.
 #include <hip/hip_runtime.h>
@@ -30,6 +31,7 @@ ScratchPool<7> cn;        // lansy / pocon, and the staged factor diagonal that 
 ScratchPool<8, true> rf;  // poequ / porfs / posvx
 ScratchPool<3> ps;        // pstrf
 ScratchPool<3> sg;        // sygst
+ScratchPool<2> cu;        // chud / chdd
 ScratchPool<4> sy;        // sytrf_nopiv / sytrs_nopiv
 // sytrf_rbt / sysv_rbt.  Not cleared when it grows (a clear on the null stream would race with the main stream's upload
 // of W): every buffer is written before it is read
@@ -48,7 +50,7 @@ struct LastStats {
     return 0;
   }
 };
-LastStats mx_stats, cn_stats, rf_stats, ps_stats, sg_stats, sy_stats, rb_stats;
+LastStats mx_stats, cn_stats, rf_stats, ps_stats, sg_stats, cu_stats, sy_stats, rb_stats;
 
 hipStream_t main_stream() { return main_rank_ctx()->st[ST_MAIN]; }
 
@@ -1242,6 +1244,103 @@ int sygst_run(int uplo, chol_desc *A, chol_desc *B) {
   return rc;
 }
 
+// ---------------------------------------------------------------- rank-r update / downdate (LINPACK DCHUD / DCHDD)
+// Lower: L <- the factor of L L^T + sigma V V^T, sigma = +1 (chud) or -1 (chdd).  Column j of L is rotated against
+// every vector in turn (chud_rot.h), columns outer, vectors inner; a vector sees the columns in order and a column
+// sees the vectors in order, and any schedule that keeps those two orders gives the same values.  This one walks the
+// tile columns; in tile column k, for each block of 128 columns of the diagonal tile: the generator (chud.hip) on the
+// diagonal block, which also leaves the rotations in a table, then the applier on the rows of the diagonal tile below
+// the block; then one applier launch on every row below the diagonal tile for all the columns of k.  More than
+// CHUD_GROUP vectors run as several such passes over the matrix, CHUD_GROUP vectors each.  One stream, in program
+// order; the phases are timed as sygst's are.
+// *info <- 0, or the 1-based column of the first rotation in that order whose rr^2 is not positive (or is NaN)
+template <typename T>
+int chud_impl(chol_desc *A, chol_desc *V, T sigma, int *info) {
+  hipStream_t s = main_stream();
+  cu_stats.clear();
+  double *st = cu_stats.v;  // total, chain (generators, in-tile appliers), bulk appliers, r, #passes, stop vector
+  const long n = A->lm;
+  const int r = V->ln, nt = A->nt, mb = A->mb, e = A->mbi;
+  const long bs = A->bsizi;
+  *info = 0;
+  st[3] = r;
+  st[5] = -1;
+  if (n == 0 || r == 0) return 0;
+  // cu[0]: the rotations of one tile column (mb columns x CHUD_GROUP vectors x 4 values); cu[1]: the stop word
+  int rc = cu.ensure_bytes(0, (size_t)mb * CHUD_GROUP * 4 * sizeof(T), "chud_tile");
+  if (!rc) rc = cu.ensure_bytes(1, 2 * sizeof(int), "chud_tile");
+  if (rc) return rc;
+  T *tab = cu.as<T>(0);
+  int *stop = cu.as<int>(1);
+  T *Am = reinterpret_cast<T *>(A->mat);
+  forget_winv(A->mat);  // (A is overwritten)
+  HIPCHECK(hipMemsetAsync(stop, 0, 2 * sizeof(int), s));
+  PhaseMarks pm;
+  enum { P_CHAIN = 1, P_BULK };
+  if ((rc = pm.mark(0))) return rc;
+  for (int g0 = 0; g0 < r; g0 += CHUD_GROUP) {
+    const int rg = std::min(CHUD_GROUP, r - g0);
+    const ChudVecs<T> vec{reinterpret_cast<T *>(V->mat), (long)V->bsizi, V->mbi, V->lmt, V->mb, g0};
+    st[4] += 1;
+    for (int k = 0; k < nt; ++k) {
+      const int nv = (int)std::min<long>(mb, n - (long)k * mb);  // (the columns of the tile beyond nv are padding)
+      T *Acol = Am + ((long)k + (long)k * A->lmt) * bs;
+      for (int c0 = 0; c0 < nv; c0 += MACRO) {
+        const int nc = std::min(MACRO, nv - c0);
+        launch_chud_gen<T>(s, Acol, e, c0, nc, vec, k, rg, sigma, tab, stop, k * mb + c0 + 1);
+        launch_chud_apply<T>(s, Acol, bs, e, mb, n, k, c0 + nc, nv, c0, nc, tab, vec, rg);
+      }
+      if ((rc = pm.mark(P_CHAIN))) return rc;
+      if (k + 1 < nt) {
+        launch_chud_apply<T>(s, Acol, bs, e, mb, n, k, e, (long)(nt - k) * e, 0, nv, tab, vec, rg);
+        if ((rc = pm.mark(P_BULK))) return rc;
+      }
+    }
+    HIPCHECK(hipGetLastError());
+  }
+  int hstop[2] = {0, 0};
+  HIPCHECK(hipMemcpyAsync(hstop, stop, sizeof hstop, hipMemcpyDeviceToHost, s));
+  if ((rc = pm.sum(st))) return rc;
+  HIPCHECK(hipStreamSynchronize(s));
+  if (hstop[0]) *info = hstop[0], st[5] = hstop[1];
+  return 0;
+}
+
+// the Lower path, or Upper between two transposes of A's storage (U^T U + sigma V V^T = L L^T + sigma V V^T with
+// L = U^T); a zero on the factor's diagonal returns its index before anything is written
+int chud_run(int uplo, chol_desc *A, chol_desc *V, double sigma, const char *what) {
+  const bool dbl = A->dtype == CHOL_REAL_DOUBLE;
+  int info = 0;
+  int rc = dbl ? diag_zero<double>(A, &info, what) : diag_zero<float>(A, &info, what);
+  if (rc) return rc;
+  if (info) return info;
+  rc = through_lower(uplo == CHOL_UPPER, {A}, [&] {
+    return dbl ? chud_impl<double>(A, V, sigma, &info) : chud_impl<float>(A, V, (float)sigma, &info);
+  });
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(main_stream()));
+  return rc ? rc : info;
+}
+
+// chol_chud_tile / chol_chdd_tile after the initialisation check
+int chud_entry(const char *what, int uplo, chol_desc *A, chol_desc *V, double sigma) {
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return failf(-1, "%s: uplo", what);
+  if (!A) return failf(-2, "%s: NULL A", what);
+  if (!V) return failf(-3, "%s: NULL V", what);
+  if (A == V || (A->mat && A->mat == V->mat)) return failf(-3, "%s: V aliases A", what);
+  // (V is workspace: the image of a view of V is not written back)
+  return with_views({{A, true}, {V, false}}, [&]() -> int {
+    int rc = inverse_check(what, A, 2);
+    if (rc) return rc;
+    if ((rc = resident_whole(what, V))) return rc;
+    // (A's rows, not same_rows: a one-tile A of order mb keeps its tile edge, an n x r image of it is padded to 128)
+    if (V->lm != A->lm || V->mb != A->mb || V->dtype != A->dtype)
+      return failf(-3, "%s: V must have A's dtype, order and tile size", what);
+    std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+    return chud_run(uplo, A, V, sigma, what);
+  });
+}
+
 // ---------------------------------------------------------------- L D L^T without pivoting (MAGMA dsytrf_nopiv)
 // Lower: A = L D L^T, L unit lower triangular, D diagonal; on return D on the diagonal and L below it.  Right-looking
 // with the tile as the block; tile column k (T: the tiles below k):
@@ -1528,6 +1627,7 @@ void cholmi::spd_release() {
   rf.release();
   ps.release();
   sg.release();
+  cu.release();
   sy.release();
   rb.release();
 }
@@ -1815,6 +1915,18 @@ int chol_sygst_tile(int itype, int uplo, chol_desc_t *A, chol_desc_t *B) {
 }
 
 int chol_last_sygst_stats(double *out8) { return sg_stats.read("sygst", out8); }
+
+int chol_chud_tile(int uplo, chol_desc_t *A, chol_desc_t *V) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "chud_tile before chol_init");
+  return chud_entry("chud_tile", uplo, A, V, 1.0);
+}
+
+int chol_chdd_tile(int uplo, chol_desc_t *A, chol_desc_t *V) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "chdd_tile before chol_init");
+  return chud_entry("chdd_tile", uplo, A, V, -1.0);
+}
+
+int chol_last_chud_stats(double *out8) { return cu_stats.read("chud", out8); }
 
 int chol_sytrf_nopiv_tile(int uplo, chol_desc_t *A) {
   if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "sytrf_nopiv_tile before chol_init");

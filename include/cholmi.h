@@ -339,6 +339,38 @@ int chol_sygst_tile(int itype, int uplo, chol_desc_t *A, chol_desc_t *B);
  * the two SYMMs), the rank-2k updates, the deferred left solve; then the number of steps; the rest 0. */
 int chol_last_sygst_stats(double *out8);
 
+/* LINPACK DCHUD / DCHDD (MATLAB cholupdate) for r vectors at once: A holds the Cholesky factor that
+ * chol_potrf_tile(uplo, A) returned, A = L L^T (Lower) or U^T U (Upper); on return it holds the factor of
+ * L L^T + V V^T (chol_chud_tile) or of L L^T - V V^T (chol_chdd_tile), V an n x r descriptor, any r >= 0.  O(n^2 r)
+ * operations and one read and one write of the stored triangle per 16 vectors, against the O(n^3) of a new
+ * factorisation.  Only the `uplo` triangle of A is read or written: the other strict triangle (and the padding of a
+ * ragged order) comes back bit for bit.  V IS WORKSPACE: it is overwritten and its content on return is unspecified.
+ *
+ * The arithmetic is fixed (sigma = +1 update, -1 downdate; columns j outer, vectors v inner):
+ *     d2 = L_jj L_jj + sigma v_j v_j;   rr = sqrt(d2);   c = rr / L_jj;   s = v_j / L_jj;   ci = L_jj / rr;   L_jj = rr
+ *     i > j:   L_ij = (L_ij + sigma s v_i) ci;   v_i = c v_i - s L_ij  (the new L_ij)
+ * each sum of a product and a term one fused multiply-add.  No floating-point atomics and no reductions: a repeated
+ * call returns the same bits, and the result does not depend on the tile size.
+ *
+ * The descriptor rules of chol_potrs_tile: device-resident single-process square A (ragged orders and sub-matrix
+ * views included) whose stored tile edge is a multiple of 64; V with A's dtype, order and tile size; a p x q
+ * block-cyclic descriptor returns CHOL_ERR_NOT_SUPPORTED.  fp64 or fp32 by the dtype, fp32 in single precision
+ * throughout.  Cached block inverses of the old factor (chol_desc_set_version) are dropped.
+ *
+ * Returns 0, or j > 0 (1-based):
+ *   - an exact zero at L_jj, found before anything is written: A and V unchanged;
+ *   - the first column j, in the order above, at which some vector gives d2 <= 0 or NaN (for finite data only
+ *     chol_chdd_tile can): the leading minor of order j of A - V V^T is not positive definite, chol_potrf_tile's
+ *     meaning of info.  A and V are then unspecified, as A is after a failed chol_potrf_tile: a caller who needs the
+ *     old factor keeps a copy (chol_lacpy_tile).
+ * Argument errors: -1 uplo, -2 A, -3 V (NULL, another dtype, order or tile size, or V aliasing A). */
+int chol_chud_tile(int uplo, chol_desc_t *A, chol_desc_t *V);
+int chol_chdd_tile(int uplo, chol_desc_t *A, chol_desc_t *V);
+/* The last chol_chud_tile / chol_chdd_tile: total, chain (the diagonal blocks' generators and the appliers inside
+ * the diagonal tiles) and bulk applier time [ms]; r; the number of passes over the matrix (16 vectors each); the
+ * 0-based index of the vector at which a downdate stopped (-1: none); the rest 0. */
+int chol_last_chud_stats(double *out8);
+
 /* The L D L^T factorisation WITHOUT pivoting of a symmetric matrix (MAGMA dsytrf_nopiv / ssytrf_nopiv; LAPACK
  * DSYTF2's storage for 1 x 1 pivots): A = L D L^T (Lower) or U^T D U (Upper, U = L^T), L unit lower triangular, D
  * diagonal.  On return the diagonal of A holds D and the strict `uplo` triangle holds L (U); the unit diagonal is not

@@ -1,0 +1,392 @@
+"""The rank-r update / downdate of a Cholesky factor, CHAMELEON_dchud_Tile / dchdd_Tile (and the s forms), on the
+device: against the numpy model of the arithmetic (chud_model.py) and against LAPACK's factor of A +- V V^T; Lower and
+Upper, fp64 and fp32, tiles from 128 to 512, ragged orders, a single tile, a rank above the per-pass group; the other
+triangle and the padding bit for bit; tile-size independence and repeatability bit for bit; a sub-matrix view; the
+stale-cache checks; the failing downdates; the argument errors.
+
+Inputs as in test_chud_host.py: A a Gram matrix with an n x 2n factor, V standard normal times sqrt(n); the downdate
+starts from the factor of A + V V^T.  Errors are max |dL| / max |L| in eps (2^-52, 2^-23).
+
+Against LAPACK: test_chud_host.py's bounds (the model itself measures, on this file's shapes, at most 44 / 274 eps in
+fp64 and 3.9 / 133 eps in fp32 for update / downdate).
+
+Against the model: the device forms each a + b c with one fused multiply-add, the model rounds the product first, and
+nothing else differs (the order of the rotations is the model's for every row).  What that contraction can change was
+measured with the model itself, fp32 with the product and the sum in fp64 (chud_model(..., fused=True)) against plain
+fp32, on this file's shapes: at most 3.0 eps for the update and 113 eps for the downdate (the downdate's starting
+matrix has kappa up to about 7000).  The bounds are 10 x that, in units of eps for both precisions."""
+import functools
+
+import numpy as np
+import pytest
+
+from chud_model import chud_model
+
+pytestmark = pytest.mark.gpu
+
+LAPACK_BOUND = {"d": (360.0, 1400.0), "s": (31.0, 560.0)}  # [update, downdate], test_chud_host.py
+MODEL_BOUND = (30.0, 1130.0)
+SHAPES = [(1000, 128, 1), (1100, 192, 5), (1536, 256, 16), (2100, 512, 3), (300, 512, 2), (192, 192, 1), (600, 128, 40)]
+GROUP = 16  # vectors per pass
+
+
+def npdt(dt):
+    return np.float64 if dt == "d" else np.float32
+
+
+def chdt(ch, dt):
+    return ch.ChamRealDouble if dt == "d" else ch.ChamRealFloat
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
+
+
+@functools.lru_cache(maxsize=None)
+def problem(n, r, seed):
+    """A, V, the factor of A, the factor of A + V V^T"""
+    g = np.random.default_rng(seed)
+    G = g.standard_normal((n, 2 * n))
+    A = G @ G.T
+    V = g.standard_normal((n, r)) * np.sqrt(n)
+    return A, V, np.linalg.cholesky(A), np.linalg.cholesky(A + V @ V.T)
+
+
+@functools.lru_cache(maxsize=None)
+def case(n, r, seed, sigma, dt):
+    """-> (the factor to start from and V, both rounded to dt; the model's result; LAPACK's factor)"""
+    _, V, L0, L1 = problem(n, r, seed)
+    start, ref = (L0, L1) if sigma > 0 else (L1, L0)
+    start, V = start.astype(npdt(dt)), V.astype(npdt(dt))
+    info, Lm, _ = chud_model(start, V, sigma, npdt(dt))
+    assert info == 0
+    return start, V, Lm, ref
+
+
+def err_eps(L, ref, dt):
+    return np.abs(L.astype(np.float64) - ref.astype(np.float64)).max() / np.abs(ref).max() / np.finfo(npdt(dt)).eps
+
+
+def stored(M, u, fill=np.nan):
+    """the Lower factor M stored in the `u` triangle, the other strict one = fill"""
+    n = M.shape[0]
+    S = np.array(np.tril(M) if u == "L" else np.tril(M).T, order="F")
+    idx = np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
+    S[idx] = fill
+    return S
+
+
+def desc(ch, n, B, dt, r=None):
+    r = n if r is None else r
+    return ch.CHAMELEON_Desc_Create(None, chdt(ch, dt), B, B, B * B, n, r, 0, 0, n, r, 1, 1)
+
+
+def uplo(ch, u):
+    return ch.ChamLower if u == "L" else ch.ChamUpper
+
+
+def run(ch, sigma, L, V, B, u="L", dt="d"):
+    """-> (info, the result as Lower, A after the call, A as stored, V after the call)"""
+    n, r = V.shape
+    S = stored(L.astype(npdt(dt)), u)
+    da, dv = desc(ch, n, B, dt), desc(ch, n, B, dt, r)
+    da.from_lapack(S)
+    dv.from_lapack(V.astype(npdt(dt)))
+    fn = ch.CHAMELEON_dchud_Tile if sigma > 0 else ch.CHAMELEON_dchdd_Tile
+    info = fn(uplo(ch, u), da, dv)
+    F, W = da.to_lapack(), dv.to_lapack()
+    ch.CHAMELEON_Desc_Destroy(da)
+    ch.CHAMELEON_Desc_Destroy(dv)
+    return info, (np.tril(F) if u == "L" else np.triu(F).T), F, S, W
+
+
+def other_triangle_kept(F, S, u):
+    n = S.shape[0]
+    idx = np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
+    return np.array_equal(bits(F[idx]), bits(S[idx]))
+
+
+@pytest.mark.parametrize("n,B,r", SHAPES)
+@pytest.mark.parametrize("sigma", [1, -1])
+@pytest.mark.parametrize("u", ["L", "U"])
+@pytest.mark.parametrize("dt", ["d", "s"])
+def test_against_model_and_lapack(cham, n, B, r, sigma, u, dt):
+    ch = cham
+    start, V, Lm, ref = case(n, r, n + B + r, sigma, dt)
+    info, L, F, S, _ = run(ch, sigma, start, V, B, u, dt)
+    assert info == 0
+    k = 0 if sigma > 0 else 1
+    em, el = err_eps(L, Lm, dt), err_eps(L, ref, dt)
+    print(f"n={n} B={B} r={r} sigma={sigma} {u} {dt}: {em:.2f} eps from the model, {el:.1f} eps from LAPACK")
+    assert em <= MODEL_BOUND[k], em
+    assert el <= LAPACK_BOUND[dt][k], el
+    assert other_triangle_kept(F, S, u)  # (NaN fill: nothing of it was read either)
+    st = ch.last_chud_stats()
+    assert st["r"] == r and st["passes"] == -(-r // GROUP) and st["total_ms"] > 0 and st["stop_vector"] == -1
+    assert st["chain_ms"] > 0
+    if n > B:
+        assert st["bulk_ms"] > 0
+
+
+@pytest.mark.parametrize("dt", ["d", "s"])
+def test_tile_size_independence(cham, dt):
+    """every row takes the same operations whichever kernel and tile handles it: the bits do not depend on the tile"""
+    ch = cham
+    n, r = 1000, 3
+    start, V, Lm, _ = case(n, r, 21, 1, dt)
+    outs = [run(ch, 1, start, V, B, "L", dt)[1] for B in (128, 256, 512)]
+    assert np.array_equal(bits(outs[0]), bits(outs[1])) and np.array_equal(bits(outs[0]), bits(outs[2]))
+    assert err_eps(outs[0], Lm, dt) <= MODEL_BOUND[0]
+
+
+def raw_image(d):
+    """the descriptor's stored fp64 tile image, padding included (through the HIP runtime this process has loaded)"""
+    import ctypes
+
+    ptr, nbytes = d.local_ptr()
+    path = next(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln)
+    hip = ctypes.CDLL(path)
+    out = np.empty(nbytes // 8, dtype=np.float64)
+    assert hip.hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), ctypes.c_size_t(nbytes), 2) == 0
+    return out
+
+
+@pytest.mark.parametrize("sigma", [1, -1])
+def test_repeatable_and_padding(cham, sigma):
+    """two calls on fresh descriptors give the same bits; a ragged order keeps the padding of A's image (the identity
+    on the diagonal, zeros elsewhere) bit for bit"""
+    ch = cham
+    n, B, nt, r = 1000, 256, 4, 5
+    k = n - (nt - 1) * B  # rows / columns k .. B-1 of the last tile row / column are padding
+    pad = np.zeros((nt * B, nt * B), dtype=bool)
+    pad[(nt - 1) * B + k:, :] = pad[:, (nt - 1) * B + k:] = True
+    start, V, _, _ = case(n, r, 5, sigma, "d")
+    fn = ch.CHAMELEON_dchud_Tile if sigma > 0 else ch.CHAMELEON_dchdd_Tile
+    outs = []
+
+    def image(d):  # as one (nt B) x (nt B) matrix
+        return raw_image(d)[: nt * nt * B * B].reshape(nt, nt, B, B).transpose(1, 3, 0, 2).reshape(nt * B, nt * B)
+
+    for _ in range(2):
+        da, dv = desc(ch, n, B, "d"), desc(ch, n, B, "d", r)
+        da.from_lapack(stored(start, "L", 0.0))
+        dv.from_lapack(V)
+        before = image(da)
+        assert fn(ch.ChamLower, da, dv) == 0
+        outs.append(da.to_lapack())
+        after = image(da)
+        ch.CHAMELEON_Desc_Destroy(da)
+        ch.CHAMELEON_Desc_Destroy(dv)
+        assert np.array_equal(bits(after[pad]), bits(before[pad]))
+        assert np.array_equal(after[n:, n:], np.eye(nt * B - n)) and not np.any(after[n:, :n])
+    assert np.array_equal(bits(outs[0]), bits(outs[1]))
+
+
+@pytest.mark.parametrize("dt", ["d", "s"])
+def test_round_trip(cham, dt):
+    """chud then chdd with the same V returns L within the downdate bound"""
+    ch = cham
+    n, B, r = 1100, 256, 4
+    _, V, L0, _ = problem(n, r, 9)
+    da, dv = desc(ch, n, B, dt), desc(ch, n, B, dt, r)
+    da.from_lapack(stored(L0.astype(npdt(dt)), "L", 0.0))
+    dv.from_lapack(V.astype(npdt(dt)))
+    assert ch.CHAMELEON_dchud_Tile(ch.ChamLower, da, dv) == 0
+    dv.from_lapack(V.astype(npdt(dt)))  # (V is workspace)
+    assert ch.CHAMELEON_dchdd_Tile(ch.ChamLower, da, dv) == 0
+    L = np.tril(da.to_lapack())
+    ch.CHAMELEON_Desc_Destroy(da)
+    ch.CHAMELEON_Desc_Destroy(dv)
+    e = err_eps(L, L0, dt)
+    print(f"round trip {dt}: {e:.1f} eps")
+    assert e <= LAPACK_BOUND[dt][1], e
+
+
+def test_sub_matrix_view(cham):
+    """a tile-aligned view of a device user buffer gives the whole-matrix descriptor's result bit for bit; the user's
+    tiles outside the view stay as they were"""
+    import torch
+
+    ch = cham
+    mb, lt, oi, oj, vt, r = 256, 5, 1, 2, 3, 3
+    lm, m = lt * mb, vt * mb
+    user = np.random.default_rng(16).standard_normal(lt * lt * mb * mb)
+    buf = torch.from_numpy(user.copy()).cuda()
+    start, V, _, _ = case(m, r, 6, 1, "d")
+    v = ch.CHAMELEON_Desc_Create(buf, ch.ChamRealDouble, mb, mb, mb * mb, lm, lm, oi * mb, oj * mb, m, m, 1, 1)
+    v.from_lapack(stored(start, "L"))
+    dv = desc(ch, m, mb, "d", r)
+    dv.from_lapack(V)
+    assert ch.CHAMELEON_dchud_Tile(ch.ChamLower, v, dv) == 0
+    Lv = np.tril(v.to_lapack())
+    ch.CHAMELEON_Desc_Destroy(v)
+    ch.CHAMELEON_Desc_Destroy(dv)
+    _, L, *_ = run(ch, 1, start, V, mb)
+    assert np.array_equal(bits(Lv), bits(L))
+    now = buf.cpu().numpy().reshape(lt * lt, mb * mb)
+    before = user.reshape(lt * lt, mb * mb)
+    for J in range(lt):
+        for I in range(lt):
+            if not (oi <= I < oi + vt and oj <= J < oj + vt):
+                assert np.array_equal(now[I + J * lt], before[I + J * lt]), (I, J)
+
+
+# potrs's usual normwise residual (test_gpu_full.py) plus the backward error the update itself may add (LAPACK_BOUND)
+SOLVE_BOUND = 1e-15 + LAPACK_BOUND["d"][0] * 2.0 ** -52
+
+
+def test_potrs_after_chud_solves_the_updated_system(cham):
+    """potrf, potrs on one right-hand side, chud, potrs again: the second solution solves (A + V V^T) x = b"""
+    ch = cham
+    n, B, r = 1000, 256, 2
+    A, V, _, _ = problem(n, r, 31)
+    b = np.random.default_rng(32).standard_normal((n, 1))
+    da, dv, db = desc(ch, n, B, "d"), desc(ch, n, B, "d", r), desc(ch, n, B, "d", 1)
+    da.from_lapack(A)
+    dv.from_lapack(V)
+    db.from_lapack(b)
+    assert ch.CHAMELEON_dpotrf_Tile(ch.ChamLower, da) == 0
+    assert ch.CHAMELEON_dpotrs_Tile(ch.ChamLower, da, db) == 0
+    x0 = db.to_lapack()
+    assert np.linalg.norm(A @ x0 - b) / (np.linalg.norm(A) * np.linalg.norm(x0)) <= 1e-15
+    assert ch.CHAMELEON_dchud_Tile(ch.ChamLower, da, dv) == 0
+    db.from_lapack(b)
+    assert ch.CHAMELEON_dpotrs_Tile(ch.ChamLower, da, db) == 0
+    x = db.to_lapack()
+    for d in (da, dv, db):
+        ch.CHAMELEON_Desc_Destroy(d)
+    M = A + V @ V.T
+    res = np.linalg.norm(M @ x - b) / (np.linalg.norm(M) * np.linalg.norm(x))
+    assert res <= SOLVE_BOUND, res
+
+
+def test_tagged_tile_drops_its_block_inverses(cham):
+    """the path that really caches block inverses: a tagged one-tile descriptor over a device buffer, factored (its
+    block inverses kept under the tag), updated, then chol_trsm_tile with the same buffer and tag: X L^T = X0 with the
+    NEW factor"""
+    import torch
+
+    ch = cham
+    B, r = 512, 2
+    A, V, _, L1 = problem(B, r, 41)
+    X0 = np.asfortranarray(np.random.default_rng(42).standard_normal((B, B)))
+    dl = torch.from_numpy(A.ravel(order="F").copy()).cuda()
+    dL = ch.CHAMELEON_Desc_Create(dl, ch.ChamRealDouble, B, B, B * B, B, B, 0, 0, B, B, 1, 1)
+    dL.set_version(0x51ab)
+    assert ch.CHAMELEON_dpotrf_Tile(ch.ChamLower, dL) == 0
+    dv = desc(ch, B, B, "d", r)
+    dv.from_lapack(V)
+    assert ch.CHAMELEON_dchud_Tile(ch.ChamLower, dL, dv) == 0
+    dx = torch.from_numpy(X0.ravel(order="F").copy()).cuda()
+    dX = ch.CHAMELEON_Desc_Create(dx, ch.ChamRealDouble, B, B, B * B, B, B, 0, 0, B, B, 1, 1)
+    assert ch.CHAMELEON_dtrsm_Tile(ch.ChamRight, ch.ChamLower, ch.ChamTrans, ch.ChamNonUnit, 1.0, dL, dX) == 0
+    X = dx.cpu().numpy().reshape((B, B), order="F").copy()
+    L = np.tril(dl.cpu().numpy().reshape((B, B), order="F"))
+    for d in (dL, dv, dX):
+        ch.CHAMELEON_Desc_Destroy(d)
+    assert err_eps(L, L1, "d") <= LAPACK_BOUND["d"][0]
+    # (test_gpu_abi.py's bound for this solve, as a residual)
+    assert np.abs(X @ L.T - X0).max() <= 16 * B * 2.0 ** -52 * np.abs(X).max() * np.abs(L).max()
+
+
+@pytest.mark.parametrize("u", ["L", "U"])
+@pytest.mark.parametrize("dt", ["d", "s"])
+def test_failing_downdate_reports_the_minor(cham, u, dt):
+    """v = 1.001 L[:, 137]: the leading minor of order 138 of L L^T - v v^T is not positive definite; 0.999: it is"""
+    ch = cham
+    n, B = 600, 128
+    _, _, L, _ = problem(n, 1, 77)
+    L = L.astype(npdt(dt))
+    v = L[:, 137:138].astype(np.float64)
+    info, *_ = run(ch, -1, L, 1.001 * v, B, u, dt)
+    assert info == 138
+    assert ch.last_chud_stats()["stop_vector"] == 0
+    info, *_ = run(ch, -1, L, 0.999 * v, B, u, dt)
+    assert info == 0
+    assert ch.last_chud_stats()["stop_vector"] == -1
+
+
+def test_failing_downdate_is_column_outer(cham):
+    """the vector that fails at the earlier column is reported, wherever it stands; also across two passes"""
+    ch = cham
+    n, B = 600, 128
+    _, _, L, _ = problem(n, 1, 77)
+    V = np.stack([1.001 * L[:, 300], 1.001 * L[:, 137]], axis=1)
+    info, *_ = run(ch, -1, L, V, B)
+    assert info == 138 and ch.last_chud_stats()["stop_vector"] == 1
+    W = np.zeros((n, GROUP + 2))
+    W[:, 0], W[:, GROUP + 1] = V[:, 0], V[:, 1]  # (the second pass fails first)
+    info, *_ = run(ch, -1, L, W, B)
+    assert info == 138 and ch.last_chud_stats()["stop_vector"] == GROUP + 1
+
+
+@pytest.mark.parametrize("u", ["L", "U"])
+def test_zero_on_the_diagonal(cham, u):
+    ch = cham
+    n, B, r = 600, 128, 2
+    _, V, L, _ = problem(n, r, 8)
+    L = L.copy()
+    L[300, 300] = 0.0
+    for sigma in (1, -1):
+        info, _, F, S, W = run(ch, sigma, L, V, B, u)
+        assert info == 301
+        assert np.array_equal(bits(F), bits(S))  # A unchanged
+        assert np.array_equal(bits(W), bits(V))  # V unchanged
+
+
+def test_nan_in_v_reports_its_row(cham):
+    ch = cham
+    n, B, r = 600, 128, 3
+    _, V, L, _ = problem(n, r, 8)
+    V = V.copy()
+    V[211, 1] = np.nan
+    for sigma in (1, -1):
+        start = L if sigma > 0 else np.linalg.cholesky(L @ L.T + np.nan_to_num(V) @ np.nan_to_num(V).T)
+        # (the NaN spreads along row 211 of L and to the later vectors' entries of that row, nowhere else)
+        assert chud_model(start, V, sigma)[0::2] == (212, 1)
+        info, *_ = run(ch, sigma, start, V, B)
+        assert info == 212
+        assert ch.last_chud_stats()["stop_vector"] == 1
+
+
+def test_argument_errors(cham):
+    from dense_linear_app_amd._lib import lib
+
+    ch = cham
+    n, B, r = 512, 128, 3
+    da, dv = desc(ch, n, B, "d"), desc(ch, n, B, "d", r)
+    L = lib()
+    for fn in (L.chol_chud_tile, L.chol_chdd_tile):
+        assert fn(7, da.handle, dv.handle) == -1
+        assert fn(ch.ChamLower, None, dv.handle) == -2
+        assert fn(ch.ChamLower, da.handle, None) == -3
+        assert fn(ch.ChamLower, da.handle, da.handle) == -3  # V aliasing A
+        for other in (desc(ch, n, B, "s", r), desc(ch, n, 256, "d", r), desc(ch, 640, B, "d", r)):
+            assert fn(ch.ChamLower, da.handle, other.handle) == -3
+            ch.CHAMELEON_Desc_Destroy(other)
+        rect = desc(ch, n, B, "d", 2 * n)
+        assert fn(ch.ChamLower, rect.handle, dv.handle) == -2
+        ch.CHAMELEON_Desc_Destroy(rect)
+    assert L.chol_last_chud_stats(None) == -1
+    ch.CHAMELEON_Desc_Destroy(da)
+    ch.CHAMELEON_Desc_Destroy(dv)
+
+
+def test_pxq_descriptor_is_not_supported(cham):
+    from dense_linear_app_amd._lib import lib
+
+    ch = cham
+    lib().chol_set_transport(None)
+    ch.set_rank(0, 2)
+    try:
+        da = ch.CHAMELEON_Desc_Create(None, ch.ChamRealDouble, 256, 256, 256 * 256, 1024, 1024, 0, 0, 1024, 1024, 1, 2)
+        dv = ch.CHAMELEON_Desc_Create(None, ch.ChamRealDouble, 256, 256, 256 * 256, 1024, 1024, 0, 0, 1024, 1024, 1, 2)
+        for fn in (ch.CHAMELEON_dchud_Tile, ch.CHAMELEON_dchdd_Tile):
+            with pytest.raises(ch.CholmiError) as e:
+                fn(ch.ChamLower, da, dv)
+            assert e.value.code == -104  # CHOL_ERR_NOT_SUPPORTED
+        ch.CHAMELEON_Desc_Destroy(da)
+        ch.CHAMELEON_Desc_Destroy(dv)
+    finally:
+        ch.set_rank(0, 1)
