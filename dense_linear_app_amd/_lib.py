@@ -75,6 +75,11 @@ def lib() -> C.CDLL:
         "chol_chud_tile": ([i, vp, vp], i),
         "chol_chdd_tile": ([i, vp, vp], i),
         "chol_last_chud_stats": ([C.POINTER(d)], i),
+        "chol_trtrs_tile": ([i, i, i, vp, vp], i),
+        "chol_trmm_tile": ([i, i, i, i, d, vp, vp], i),
+        "chol_logdet_tile": ([vp, C.POINTER(d)], i),
+        "chol_last_trtrs_stats": ([C.POINTER(d)], i),
+        "chol_debug_half_limits": ([i, i], i),
         "chol_sytrf_nopiv_tile": ([i, vp], i),
         "chol_sytrs_nopiv_tile": ([i, vp, vp], i),
         "chol_sysv_nopiv_tile": ([i, vp, vp], i),

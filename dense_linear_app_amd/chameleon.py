@@ -422,6 +422,40 @@ def last_chud_stats() -> dict:
             "stop_vector": int(v[5])}
 
 
+def CHAMELEON_dtrtrs_Tile(uplo: int, trans: int, diag: int, A: Desc, B: Desc) -> int:
+    """LAPACK DTRTRS: B <- inv(op(T)) B, T the `uplo` triangle of A (the factor chol_potrf_tile(uplo, .) returned), op
+    the transpose for ChamTrans; A is only read.  Returns 0, or info > 0: the 1-based index of a zero on the diagonal
+    (B unchanged).  ChamUnit raises (CHOL_ERR_NOT_SUPPORTED)."""
+    return check("chol_trtrs_tile", lib().chol_trtrs_tile(uplo, trans, diag, A.handle, B.handle))
+
+
+def CHAMELEON_dtrmm_Tile(side: int, uplo: int, trans: int, diag: int, alpha: float, A: Desc, B: Desc) -> int:
+    """BLAS DTRMM, side ChamLeft: B <- alpha op(T) B in place, T the `uplo` triangle of A; A is only read.  ChamRight
+    and ChamUnit raise (CHOL_ERR_NOT_SUPPORTED)."""
+    return check("chol_trmm_tile", lib().chol_trmm_tile(side, uplo, trans, diag, float(alpha), A.handle, B.handle))
+
+
+def CHAMELEON_dlogdet_Tile(A: Desc) -> tuple[int, float]:
+    """(info, 2 sum_j log A(j,j)): log det(L L^T) from the diagonal of the factor A, summed in fp64 in a fixed order.
+    info > 0: the 1-based index of the first diagonal entry that is <= 0 or NaN (the value is then unspecified)."""
+    v = C.c_double(0.0)
+    info = check("chol_logdet_tile", lib().chol_logdet_tile(A.handle, C.byref(v)))
+    return info, v.value
+
+
+def last_trtrs_stats() -> dict:
+    """The last CHAMELEON_dtrtrs_Tile / dtrmm_Tile (chol_last_trtrs_stats): total, diagonal-tile staging and sweep or
+    product time [ms], and the columns that took the narrow and the wide path."""
+    v = (C.c_double * 8)()
+    check("chol_last_trtrs_stats", lib().chol_last_trtrs_stats(v))
+    return {"total_ms": v[0], "stage_ms": v[1], "work_ms": v[2], "narrow_cols": int(v[3]), "wide_cols": int(v[4])}
+
+
+def half_limits(trtrs_cols: int = -1, trmm_cols: int = -1) -> None:
+    """Diagnostic: the widest trtrs / trmm call that takes the narrow path (negative: the built-in limit)."""
+    check("chol_debug_half_limits", lib().chol_debug_half_limits(trtrs_cols, trmm_cols))
+
+
 def CHAMELEON_dsytrf_nopiv_Tile(uplo: int, A: Desc) -> int:
     """A = L D L^T (ChamLower) or U^T D U (ChamUpper) without pivoting, for symmetric matrices whose factorisation
     needs none (quasi-definite, diagonally dominant): on return D on the diagonal of A and the unit triangular factor
@@ -510,6 +544,9 @@ CHAMELEON_spstrf_Tile = CHAMELEON_dpstrf_Tile
 CHAMELEON_ssygst_Tile = CHAMELEON_dsygst_Tile
 CHAMELEON_schud_Tile = CHAMELEON_dchud_Tile
 CHAMELEON_schdd_Tile = CHAMELEON_dchdd_Tile
+CHAMELEON_strtrs_Tile = CHAMELEON_dtrtrs_Tile
+CHAMELEON_strmm_Tile = CHAMELEON_dtrmm_Tile
+CHAMELEON_slogdet_Tile = CHAMELEON_dlogdet_Tile
 CHAMELEON_ssytrf_nopiv_Tile = CHAMELEON_dsytrf_nopiv_Tile
 CHAMELEON_ssytrs_nopiv_Tile = CHAMELEON_dsytrs_nopiv_Tile
 CHAMELEON_ssysv_nopiv_Tile = CHAMELEON_dsysv_nopiv_Tile

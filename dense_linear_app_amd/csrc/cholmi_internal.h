@@ -411,7 +411,10 @@ void launch_porfs_resid(hipStream_t s, const TileGeo &ga, int upper, const T *A,
                         unsigned long long *berr);
 // count <= 8 applications of A^{-1} at once (the NV = refine_width(count) form of launch_sweep): x[j] <- A^{-1} x[j],
 // each block of the factor read once per launch for all vectors; pad: 7 vectors of scratch for the unused places;
-// y, pg, pd: msweep_scratch_elems(g) elements of T in all
+// y, pg, pd: msweep_scratch_elems(g) elements of T in all.
+// which = SWEEP_FORWARD / SWEEP_BACKWARD: one half alone, L y = x (U^T y = x) / L^T y = x (U y = x): vector j's
+// result is left at b.y + j condest_vec_elems(g) and x[j] is used up
+enum { SWEEP_BOTH = 0, SWEEP_FORWARD = 1, SWEEP_BACKWARD = 2 };
 template <typename T>
 struct MSweepBufs {
   T *y, *pg, *pd;
@@ -419,7 +422,29 @@ struct MSweepBufs {
 size_t msweep_scratch_elems(const TileGeo &g);
 template <typename T>
 void launch_msweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const T *Dv, T *const *x, int count,
-                   T *pad, const MSweepBufs<T> &b);
+                   T *pad, const MSweepBufs<T> &b, int which = SWEEP_BOTH);
+
+// ---- launchers (trmm.hip): chol_trmm_tile's narrow path and chol_logdet_tile (condest.hip's geometry) ----
+// B(:, cols.d[j]) <- alpha op(T) B(:, cols.d[j]) for at most 8 columns of the n x ncols image B (gx), T the `upper`
+// triangle of the n x n image A (ga; the other strict triangle is not read), op the transpose when trans.  x: 8
+// vectors (condest_vec_elems each) that take the gathered columns; part: trmm_part_elems(ga, refine_width(cols.n))
+// elements, the per-block products that a second kernel adds in a fixed order
+size_t trmm_part_elems(const TileGeo &ga, int width);
+template <typename T>
+void launch_trmm_narrow(hipStream_t s, const TileGeo &ga, int upper, int trans, const T *A, const TileGeo &gx, T *B,
+                        const VecCols &cols, T alpha, T *x, T *part);
+// out (nt tiles of mb x mb) <- the lower triangles of the diagonal tiles A + t tstride (ld mb), zero above the
+// diagonal; transposed: each written as its transpose
+template <typename T>
+void launch_tri_tiles(hipStream_t s, const T *A, long tstride, int mb, int nt, bool transposed, T *out);
+// v <- alpha v, `total` entries
+template <typename T>
+void launch_scale(hipStream_t s, T *v, long total, T alpha);
+// out[0] <- 2 sum_i log A(i,i) (logs and sum in fp64, fixed order), out[1] <- the first 0-based i whose A(i,i) is
+// <= 0 or NaN, or -1; part: logdet_part_bytes() of scratch
+size_t logdet_part_bytes();
+template <typename T>
+void launch_logdet(hipStream_t s, const TileGeo &g, const T *A, double *part, double *out);
 
 // ---- launchers (pstrf.hip): the pivoted panel of chol_pstrf_tile (LAPACK DPSTRF, Lower) on a single-process image.
 // Entry (r, c) of the n x n matrix at (r / mb + (c / mb) lmt) bsiz + r % mb + (c % mb) mbi; the padding is never

@@ -21,21 +21,6 @@ namespace cholmi {
 
 namespace {
 
-// storage index of vector entry (block b, t) of column j of an n x ncols image with the matrix's row tiling
-__device__ __forceinline__ long desc_index(const TileGeo &g, long b, int t, int j) {
-  const int bpt = bpt_of(g);
-  return ((b / bpt) + (long)(j / g.mbu) * g.lmt) * (long)g.mbs * g.mbs + (b % bpt) * CB + t + (long)(j % g.mbu) * g.mbs;
-}
-
-// storage index of global row i of column 0 (the S vector) / of the diagonal entry A(i, i)
-__device__ __forceinline__ long col0_index(const TileGeo &g, long i) {
-  return (i / g.mbu) * (long)g.mbs * g.mbs + i % g.mbu;
-}
-__device__ __forceinline__ long diag_index(const TileGeo &g, long i) {
-  const long t = i / g.mbu, r = i % g.mbu;
-  return t * (g.lmt + 1) * (long)g.mbs * g.mbs + r + r * g.mbs;
-}
-
 template <typename T>
 struct Bits;
 template <>
@@ -166,33 +151,6 @@ __global__ __launch_bounds__(256) void k_vec_weight(T *__restrict__ V, const T *
   const long off = (long)cols.v[j] * nv;
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < nv; e += (long)gridDim.x * 256)
     V[off + e] = W[off + e] * V[off + e];
-}
-
-// ---------------------------------------------------------------- the wave reduction of N values at once
-// v[0..N) of every lane summed over the 64 lanes, N in {1, 2, 4, 8}: the first log2 N exchange steps halve the values a
-// lane holds (at offset 32 the lanes with bit 5 set keep the upper half and send the lower one, and so on), the rest
-// is a plain butterfly.  log2 N + (6 - log2 N) ... = N - 1 + 6 - log2 N exchanges instead of 6 N.  Returns the total of
-// vector *j in every lane (the lanes that share bits 5 .. 6 - log2 N of their index hold the same one); fixed order.
-template <typename T, int N>
-__device__ __forceinline__ T wave_sum_n(const T (&v)[N], int lane, int *j) {
-  T w[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) w[i] = v[i];
-  int jb = 0, off = 32;
-#pragma unroll
-  for (int cnt = N; cnt > 1; cnt >>= 1, off >>= 1) {
-    const bool hi = (lane & off) != 0;
-#pragma unroll
-    for (int i = 0; i < cnt / 2; ++i) {
-      const T keep = hi ? w[i + cnt / 2] : w[i], send = hi ? w[i] : w[i + cnt / 2];
-      w[i] = keep + __shfl_xor(send, off, 64);
-    }
-    if (hi) jb += cnt / 2;
-  }
-#pragma unroll
-  for (; off > 0; off >>= 1) w[0] += __shfl_xor(w[0], off, 64);
-  *j = jb;
-  return w[0];
 }
 
 // ---------------------------------------------------------------- the residual of porfs
@@ -445,16 +403,21 @@ __global__ __launch_bounds__(256) void k_msweep_rect(TileGeo g, int upper, const
   }
 }
 
+// which: SWEEP_BOTH x <- A^{-1} x; SWEEP_FORWARD / SWEEP_BACKWARD that half alone, its result left in the y vectors
+// (b.y + j nv) and x used up
 template <typename T, int NV>
-void msweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const T *Dv, const Vec8<T> &x, const MSweepBufs<T> &b) {
+void msweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const T *Dv, const Vec8<T> &x, const MSweepBufs<T> &b,
+            int which) {
   const int E = condest_edge(g), bpt = E / CB, nt = g.lmt, NB = nt * bpt;
   const unsigned dwg = (unsigned)(bpt * (bpt + 1) / 2);
   const long nv = (long)condest_vec_elems(g), pgs = (long)NB * bpt * CB, pgn = 2 * pgs, pdn = (long)bpt * bpt * CB;
   Vec8<T> y{};
   for (int j = 0; j < NV; ++j) y.p[j] = b.y + j * nv;
-  for (int pass = 0; pass < 2; ++pass) {
+  const bool half = which != SWEEP_BOTH;
+  for (int pass = which == SWEEP_BACKWARD ? 1 : 0; pass < (which == SWEEP_FORWARD ? 1 : 2); ++pass) {
     const bool fwd = pass == 0;
-    const Vec8<T> r = fwd ? x : y, out = fwd ? y : x;  // forward: b = x -> y; backward: y -> x (r: in place)
+    // forward: b = x -> y; backward: y -> x (r: in place); one half alone: x -> y
+    const Vec8<T> r = fwd || half ? x : y, out = fwd || half ? y : x;
     const T *pg_prev = nullptr;
     for (int step = 0; step < nt; ++step) {
       const int k = fwd ? step : nt - 1 - step;
@@ -563,16 +526,16 @@ size_t msweep_scratch_elems(const TileGeo &g) {
 
 template <typename T>
 void launch_msweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const T *Dv, T *const *x, int count,
-                   T *pad, const MSweepBufs<T> &b) {
+                   T *pad, const MSweepBufs<T> &b, int which) {
   const long nv = (long)condest_vec_elems(g);
   Vec8<T> v{};
   const int w = refine_width(count);
   for (int j = 0; j < w; ++j) v.p[j] = j < count ? x[j] : pad + (long)(j - count) * nv;  // (padding: results unused)
   switch (w) {
-    case 1: msweep<T, 1>(s, g, upper, A, Dv, v, b); break;
-    case 2: msweep<T, 2>(s, g, upper, A, Dv, v, b); break;
-    case 4: msweep<T, 4>(s, g, upper, A, Dv, v, b); break;
-    default: msweep<T, 8>(s, g, upper, A, Dv, v, b); break;
+    case 1: msweep<T, 1>(s, g, upper, A, Dv, v, b, which); break;
+    case 2: msweep<T, 2>(s, g, upper, A, Dv, v, b, which); break;
+    case 4: msweep<T, 4>(s, g, upper, A, Dv, v, b, which); break;
+    default: msweep<T, 8>(s, g, upper, A, Dv, v, b, which); break;
   }
 }
 
@@ -587,7 +550,7 @@ void launch_msweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const
                                       const T *, const VecCols &, T *, T *, T *, double, double, double,            \
                                       unsigned long long *);                                                         \
   template void launch_msweep<T>(hipStream_t, const TileGeo &, int, const T *, const T *, T *const *, int, T *,      \
-                                 const MSweepBufs<T> &);
+                                 const MSweepBufs<T> &, int);
 INSTANTIATE_REFINE(double)
 INSTANTIATE_REFINE(float)
 

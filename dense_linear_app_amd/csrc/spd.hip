@@ -36,6 +36,10 @@ ScratchPool<4> sy;        // sytrf_nopiv / sytrs_nopiv
 // sytrf_rbt / sysv_rbt.  Not cleared when it grows (a clear on the null stream would race with the main stream's upload
 // of W): every buffer is written before it is read
 ScratchPool<4> rb;
+// trtrs / trmm / logdet: [0] the narrow paths' vectors and partials, [1] the wide product's clean diagonal tiles (in
+// `work`, see ZSweeps), [2] the padded copy of a one-tile factor, [3] logdet's partials and result.  Cleared when it
+// grows: the sweeps' unused vector slots then hold numbers
+ScratchPool<4, true> tr;
 
 // The statistics of a family's last call: written by the routine under the context lock, read by chol_last_*_stats
 struct LastStats {
@@ -50,7 +54,7 @@ struct LastStats {
     return 0;
   }
 };
-LastStats mx_stats, cn_stats, rf_stats, ps_stats, sg_stats, cu_stats, sy_stats, rb_stats;
+LastStats mx_stats, cn_stats, rf_stats, ps_stats, sg_stats, cu_stats, sy_stats, rb_stats, tr_stats;
 
 hipStream_t main_stream() { return main_rank_ctx()->st[ST_MAIN]; }
 
@@ -103,50 +107,108 @@ struct EventTimer {
 // udiag, rdiag (both or neither): the solve with an L D L^T factor (sytrs_nopiv) -- udiag holds the nt diagonal tiles
 // with unit diagonals (read in place of A's), rdiag the reciprocals 1 / d (tile t at + t mb), by which the right-hand
 // sides are scaled between the two sweeps
+// The two sweeps apart (chol_trtrs_tile runs one of them), on the image Z that `load` makes and `store` writes back
 template <typename T>
-int potrs_impl(chol_desc *A, chol_desc *B, const T *udiag = nullptr, const T *rdiag = nullptr) {
-  const int nt = A->nt, nr = B->nt, mb = A->mbi;
-  const long bs = A->bsizi;
-  const size_t tb = (size_t)bs * sizeof(T);
-  T *La = reinterpret_cast<T *>(A->mat), *Bm = reinterpret_cast<T *>(B->mat);
-  if (int rc = work.ensure_bytes(0, ((size_t)nr * nt + 2 + (size_t)nr + (size_t)nt) * tb, "potrs_tile")) return rc;
-  T *scr = work.as<T>(0);
-  T *Z = scr, *Wt = scr + (size_t)nr * nt * bs, *Tt = Wt + bs, *tmp = Tt + (size_t)nt * bs;  // Tt: nt tiles, tmp: nr tiles
-  hipStream_t s = main_stream();
-  T *winv = reinterpret_cast<T *>(main_rank_ctx()->winv);
-  auto Ltile = [&](int i, int j) { return La + ((long)i + (long)j * A->lmt) * bs; };
-  auto Ztile = [&](int r, int i) { return Z + ((long)r + (long)i * nr) * bs; };
-  auto Dtile = [&](int k) { return udiag ? udiag + (long)k * bs : Ltile(k, k); };
-  // Z(r,i) = B(i,r)^T
-  for (int r = 0; r < nr; ++r)
-    launch_tiles_transpose<T>(s, Bm + (long)r * B->lmt * bs, bs, Ztile(r, 0), (long)nr * bs, mb, nt);
-  for (int k = 0; k < nt; ++k) {  // forward
-    launch_invert_diag<T>(s, Dtile(k), mb, winv);
-    launch_trsm_panel<T>(s, Ztile(0, k), bs, nr, Dtile(k), winv, mb, T(1));
-    // Z(r,i) -= Z(r,k) L(i,k)^T for every r and i > k: one launch
-    launch_gemm_nt_batch<T>(s, Ztile(0, k), bs, nr, Ltile(k + 1, k), bs, nt - 1 - k, Ztile(0, k + 1), bs, (long)nr * bs, mb,
-                            T(-1), T(1));
+struct ZSweeps {
+  chol_desc *A, *B;
+  const T *udiag;
+  int nt, nr, mb;
+  long bs;
+  size_t tb;
+  T *La, *Bm, *Z, *Wt, *Tt, *tmp, *winv;  // Tt: nt tiles, tmp: nr tiles
+  hipStream_t s;
+  // extra: tiles of scratch beyond the sweeps' own, at `more` (chol_trmm_tile's clean diagonal tiles)
+  T *more;
+  int init(chol_desc *A_, chol_desc *B_, const T *udiag_, const char *what, size_t extra = 0) {
+    A = A_, B = B_, udiag = udiag_;
+    nt = A->nt, nr = B->nt, mb = A->mbi;
+    bs = A->bsizi;
+    tb = (size_t)bs * sizeof(T);
+    La = reinterpret_cast<T *>(A->mat), Bm = reinterpret_cast<T *>(B->mat);
+    if (int rc = work.ensure_bytes(0, ((size_t)nr * nt + 2 + (size_t)nr + (size_t)nt + extra) * tb, what)) return rc;
+    T *scr = work.as<T>(0);
+    Z = scr, Wt = scr + (size_t)nr * nt * bs, Tt = Wt + bs, tmp = Tt + (size_t)nt * bs, more = tmp + (size_t)nr * bs;
+    s = main_stream();
+    winv = reinterpret_cast<T *>(main_rank_ctx()->winv);
+    return 0;
   }
-  if (rdiag) launch_ldl_zscale<T>(s, Z, (long)nr * nt * bs, bs, mb, nr, rdiag);  // (D^{-1} between the sweeps)
-  for (int k = nt - 1; k >= 0; --k) {  // backward
-    HIPCHECK(hipMemsetAsync(Wt, 0, tb, s));
-    launch_pad_identity<T>(s, Wt, 0, mb);
-    launch_invert_diag<T>(s, Dtile(k), mb, winv);
-    launch_trsm_panel<T>(s, Wt, bs, 1, Dtile(k), winv, mb, T(1));  // Wt = L(k,k)^{-T}
-    // Z(r,k) <- Z(r,k) L(k,k)^{-1} for every r (out of place, then back: the tiles of a column are contiguous)
-    launch_gemm_nt_batch<T>(s, Ztile(0, k), bs, nr, Wt, 0, 1, tmp, bs, 0, mb, T(1), T(0));
-    HIPCHECK(hipMemcpyAsync(Ztile(0, k), tmp, (size_t)nr * tb, hipMemcpyDeviceToDevice, s));
-    // Z(r,i) -= Z(r,k) L(k,i) for every r and i < k: the k tiles L(k,i)^T in one transpose launch, one product launch
-    if (k > 0) {
-      launch_tiles_transpose<T>(s, Ltile(k, 0), (long)A->lmt * bs, Tt, bs, mb, k);
-      launch_gemm_nt_batch<T>(s, Ztile(0, k), bs, nr, Tt, bs, k, Ztile(0, 0), bs, (long)nr * bs, mb, T(-1), T(1));
+  T *Ltile(int i, int j) const { return La + ((long)i + (long)j * A->lmt) * bs; }
+  T *Ztile(int r, int i) const { return Z + ((long)r + (long)i * nr) * bs; }
+  const T *Dtile(int k) const { return udiag ? udiag + (long)k * bs : Ltile(k, k); }
+  void load() const {  // Z(r,i) = B(i,r)^T
+    for (int r = 0; r < nr; ++r)
+      launch_tiles_transpose<T>(s, Bm + (long)r * B->lmt * bs, bs, Ztile(r, 0), (long)nr * bs, mb, nt);
+  }
+  void store() const {  // B(i,r) = Z(r,i)^T
+    for (int r = 0; r < nr; ++r)
+      launch_tiles_transpose<T>(s, Ztile(r, 0), (long)nr * bs, Bm + (long)r * B->lmt * bs, bs, mb, nt);
+  }
+  void forward() const {
+    for (int k = 0; k < nt; ++k) {
+      launch_invert_diag<T>(s, Dtile(k), mb, winv);
+      launch_trsm_panel<T>(s, Ztile(0, k), bs, nr, Dtile(k), winv, mb, T(1));
+      // Z(r,i) -= Z(r,k) L(i,k)^T for every r and i > k: one launch
+      launch_gemm_nt_batch<T>(s, Ztile(0, k), bs, nr, Ltile(k + 1, k), bs, nt - 1 - k, Ztile(0, k + 1), bs, (long)nr * bs,
+                              mb, T(-1), T(1));
     }
   }
-  for (int r = 0; r < nr; ++r)  // B(i,r) = Z(r,i)^T
-    launch_tiles_transpose<T>(s, Ztile(r, 0), (long)nr * bs, Bm + (long)r * B->lmt * bs, bs, mb, nt);
-  HIPCHECK(hipGetLastError());  // (a refused launch configuration must not come back as a wrong solution)
-  HIPCHECK(hipStreamSynchronize(s));
-  return 0;
+  int backward() const {
+    for (int k = nt - 1; k >= 0; --k) {
+      HIPCHECK(hipMemsetAsync(Wt, 0, tb, s));
+      launch_pad_identity<T>(s, Wt, 0, mb);
+      launch_invert_diag<T>(s, Dtile(k), mb, winv);
+      launch_trsm_panel<T>(s, Wt, bs, 1, Dtile(k), winv, mb, T(1));  // Wt = L(k,k)^{-T}
+      // Z(r,k) <- Z(r,k) L(k,k)^{-1} for every r (out of place, then back: the tiles of a column are contiguous)
+      launch_gemm_nt_batch<T>(s, Ztile(0, k), bs, nr, Wt, 0, 1, tmp, bs, 0, mb, T(1), T(0));
+      HIPCHECK(hipMemcpyAsync(Ztile(0, k), tmp, (size_t)nr * tb, hipMemcpyDeviceToDevice, s));
+      // Z(r,i) -= Z(r,k) L(k,i) for every r and i < k: the k tiles L(k,i)^T in one transpose launch, one product launch
+      if (k > 0) {
+        launch_tiles_transpose<T>(s, Ltile(k, 0), (long)A->lmt * bs, Tt, bs, mb, k);
+        launch_gemm_nt_batch<T>(s, Ztile(0, k), bs, nr, Tt, bs, k, Ztile(0, 0), bs, (long)nr * bs, mb, T(-1), T(1));
+      }
+    }
+    return 0;
+  }
+  // Z <- alpha Z L^T (B <- alpha L B), or with trans Z <- alpha Z L (B <- alpha L^T B); Dc: the diagonal tiles with
+  // zeros above the diagonal (trans: transposed), nt tiles of bs.  Tile column k of Z is multiplied into the columns
+  // that are already final before it is overwritten, so the order is from the last column down (trans: from the first
+  // up); alpha multiplies the finished sums
+  int product(bool trans, T alpha, const T *Dc) const {
+    for (int step = 0; step < nt; ++step) {
+      const int k = trans ? step : nt - 1 - step;
+      if (!trans) {
+        // Z(r,i) += Z(r,k) L(i,k)^T for every r and i > k
+        launch_gemm_nt_batch<T>(s, Ztile(0, k), bs, nr, Ltile(k + 1, k), bs, nt - 1 - k, Ztile(0, k + 1), bs,
+                                (long)nr * bs, mb, T(1), T(1));
+      } else if (k > 0) {
+        // Z(r,i) += Z(r,k) L(k,i) for every r and i < k, on the transposed tiles as the backward sweep
+        launch_tiles_transpose<T>(s, Ltile(k, 0), (long)A->lmt * bs, Tt, bs, mb, k);
+        launch_gemm_nt_batch<T>(s, Ztile(0, k), bs, nr, Tt, bs, k, Ztile(0, 0), bs, (long)nr * bs, mb, T(1), T(1));
+      }
+      // Z(r,k) <- Z(r,k) D_k^T (trans: D_k), out of place and back
+      launch_gemm_nt_batch<T>(s, Ztile(0, k), bs, nr, Dc + (long)k * bs, 0, 1, tmp, bs, 0, mb, T(1), T(0));
+      HIPCHECK(hipMemcpyAsync(Ztile(0, k), tmp, (size_t)nr * tb, hipMemcpyDeviceToDevice, s));
+    }
+    if (alpha != T(1)) launch_scale<T>(s, Z, (long)nr * nt * bs, alpha);
+    return 0;
+  }
+  int finish() const {
+    HIPCHECK(hipGetLastError());  // (a refused launch configuration must not come back as a wrong solution)
+    HIPCHECK(hipStreamSynchronize(s));
+    return 0;
+  }
+};
+
+template <typename T>
+int potrs_impl(chol_desc *A, chol_desc *B, const T *udiag = nullptr, const T *rdiag = nullptr) {
+  ZSweeps<T> z;
+  if (int rc = z.init(A, B, udiag, "potrs_tile")) return rc;
+  z.load();
+  z.forward();
+  if (rdiag) launch_ldl_zscale<T>(z.s, z.Z, (long)z.nr * z.nt * z.bs, z.bs, z.mb, z.nr, rdiag);  // (D^{-1} between the sweeps)
+  if (int rc = z.backward()) return rc;
+  z.store();
+  return z.finish();
 }
 
 // potrs_impl for either orientation of the factor.  No synchronisation after the second transpose: the caller's next
@@ -1597,6 +1659,177 @@ int sysv_rbt_impl(int uplo, chol_desc *A, chol_desc *AF, chol_desc *W, int depth
   }
 }
 
+// ---------------------------------------------------------------- one half of the factor alone (LAPACK DTRTRS, BLAS DTRMM, log det)
+// trtrs: B <- inv(op(T)) B, T the `uplo` triangle.  (Lower, NoTrans) and (Upper, Trans) are potrs's forward half,
+// L Y = B; the other two its backward half, L^T X = Y.  Up to TRTRS_KX columns run as one pass of the multi-vector
+// sweeps (refine.hip) in groups of 8 on the gathered columns, the diagonal tiles staged and inverted once per call;
+// more columns run as one sweep of potrs_impl's on Z = B^T (Upper between two transposes of the storage, as potrs).
+// trmm: B <- alpha op(T) B.  Up to TRMM_KX columns in groups of 8 by trmm.hip's block products; more columns as
+// products of whole tiles on Z = B^T (ZSweeps::product), with the diagonal tiles staged as clean triangles.
+// The limits: apply_inv's rule (POSVX_KX).  Measured: the forward solve crosses at about 72 columns at
+// N = 65536 / 1024 and 43 at 16384 / 512, the backward solve at about 36 and 24, the product beyond 70 in every case
+constexpr int TRTRS_KX = POSVX_KX, TRMM_KX = POSVX_KX;
+int trtrs_kx = TRTRS_KX, trmm_kx = TRMM_KX;  // (chol_debug_half_limits moves them for scripts/trtrs_time.py)
+
+// the factor the wide paths work on: A's own image, or, for a one-tile A whose edge is not a multiple of 128 (its
+// n x nrhs image has that tile padded to one), a copy with B's tile edge and the identity beyond A's (tr[2])
+template <typename T>
+int wide_factor(chol_desc *A, const chol_desc *B, chol_desc *Aw, const char *what) {
+  *Aw = scratch_view(A, A->mat);
+  if (A->mbi == B->mbi) return 0;
+  hipStream_t s = main_stream();
+  const int e = A->mbi, ep = B->mbi;
+  if (int rc = tr.ensure_bytes(2, (size_t)ep * ep * sizeof(T), what)) return rc;
+  T *S = tr.as<T>(2);
+  HIPCHECK(hipMemsetAsync(S, 0, (size_t)ep * ep * sizeof(T), s));
+  HIPCHECK(hipMemcpy2DAsync(S, (size_t)ep * sizeof(T), A->mat, (size_t)e * sizeof(T), (size_t)e * sizeof(T), e,
+                            hipMemcpyDeviceToDevice, s));
+  launch_pad_identity<T>(s, S, e, ep);
+  Aw->mat = S;
+  Aw->mbi = ep;
+  Aw->bsizi = ep * ep;
+  return 0;
+}
+
+// st: total, staging of the diagonal tiles, sweeps or products [ms]; columns through the narrow / the wide path
+template <typename T>
+int trtrs_impl(int upper, int trans, chol_desc *A, chol_desc *B, double *st) {
+  hipStream_t s = main_stream();
+  const char *what = "trtrs_tile";
+  const int nrhs = B->ln;
+  if (A->lm == 0 || nrhs == 0) return 0;
+  const bool fwd = (upper != 0) == (trans != 0);
+  EventTimer tp;
+  int rc = 0;
+  if (nrhs <= trtrs_kx) {
+    const TileGeo ga = geo_of(A), gx = geo_of(B);
+    const int bpt = condest_edge(ga) / MACRO;
+    const long nv = (long)condest_vec_elems(ga), pgn = 2 * (long)ga.lmt * bpt * bpt * MACRO;
+    if ((rc = tp.start())) return rc;
+    if ((rc = stage_factor_diag<T>(A, upper, what))) return rc;
+    if ((rc = tp.stop(&st[1]))) return rc;
+    // the gathered columns, the padding vectors, the sweeps' scratch (whose first 8 vectors take the results)
+    if ((rc = tr.ensure_bytes(0, (16 * (size_t)nv + msweep_scratch_elems(ga)) * sizeof(T), what))) return rc;
+    T *x = tr.as<T>(0), *pad = x + 8 * nv, *sw = pad + 8 * nv;
+    const MSweepBufs<T> mb{sw, sw + 8 * nv, sw + 8 * nv + 8 * pgn};
+    if ((rc = tp.start())) return rc;
+    for (const VecCols &vc : groups_of(all_cols(nrhs))) {
+      VecCols in = vc;  // (slot j of the group <- column d[j])
+      T *xs[8];
+      for (int j = 0; j < vc.n; ++j) in.v[j] = j, xs[j] = x + (long)j * nv;
+      launch_gather<T>(s, gx, reinterpret_cast<const T *>(B->mat), in, x);
+      launch_msweep<T>(s, ga, upper, reinterpret_cast<const T *>(A->mat), cn.as<const T>(0), xs, vc.n, pad, mb,
+                       fwd ? SWEEP_FORWARD : SWEEP_BACKWARD);
+      launch_scatter<T>(s, gx, reinterpret_cast<T *>(B->mat), in, mb.y, false);
+    }
+    HIPCHECK(hipGetLastError());
+    if ((rc = tp.stop(&st[2]))) return rc;
+    st[3] = nrhs;
+    return 0;
+  }
+  chol_desc Aw;
+  if ((rc = wide_factor<T>(A, B, &Aw, what))) return rc;
+  if ((rc = tp.start())) return rc;
+  rc = through_lower(upper, {&Aw}, [&]() -> int {
+    ZSweeps<T> z;
+    if (int r = z.init(&Aw, B, nullptr, what)) return r;
+    z.load();
+    if (fwd)
+      z.forward();
+    else if (int r = z.backward())
+      return r;
+    z.store();
+    return z.finish();
+  });
+  if (rc) return rc;
+  if ((rc = tp.stop(&st[2]))) return rc;
+  st[4] = nrhs;
+  return 0;
+}
+
+template <typename T>
+int trmm_impl(int upper, int trans, double alpha, chol_desc *A, chol_desc *B, double *st) {
+  hipStream_t s = main_stream();
+  const char *what = "trmm_tile";
+  const int nrhs = B->ln;
+  if (A->lm == 0 || nrhs == 0) return 0;
+  EventTimer tp;
+  int rc = 0;
+  if (nrhs <= trmm_kx) {
+    const TileGeo ga = geo_of(A), gx = geo_of(B);
+    const long nv = (long)condest_vec_elems(ga);
+    const size_t pe = trmm_part_elems(ga, refine_width(std::min(nrhs, 8)));
+    if ((rc = tr.ensure_bytes(0, (8 * (size_t)nv + pe) * sizeof(T), what))) return rc;
+    T *x = tr.as<T>(0), *part = x + 8 * nv;
+    if ((rc = tp.start())) return rc;
+    for (const VecCols &vc : groups_of(all_cols(nrhs))) {
+      VecCols in = vc;
+      for (int j = 0; j < vc.n; ++j) in.v[j] = j;
+      launch_trmm_narrow<T>(s, ga, upper, trans, reinterpret_cast<const T *>(A->mat), gx, reinterpret_cast<T *>(B->mat),
+                            in, T(alpha), x, part);
+    }
+    HIPCHECK(hipGetLastError());
+    if ((rc = tp.stop(&st[2]))) return rc;
+    st[3] = nrhs;
+    return 0;
+  }
+  chol_desc Aw;
+  if ((rc = wide_factor<T>(A, B, &Aw, what))) return rc;
+  // on the Lower orientation: Upper NoTrans is L^T B, Upper Trans is L B
+  const bool ltrans = (upper != 0) != (trans != 0);
+  rc = through_lower(upper, {&Aw}, [&]() -> int {
+    ZSweeps<T> z;
+    if (int r = z.init(&Aw, B, nullptr, what, (size_t)Aw.nt)) return r;
+    if (int r = tp.start()) return r;
+    launch_tri_tiles<T>(s, z.La, (long)(Aw.lmt + 1) * z.bs, z.mb, z.nt, ltrans, z.more);
+    if (int r = tp.stop(&st[1])) return r;
+    if (int r = tp.start()) return r;
+    z.load();
+    if (int r = z.product(ltrans, T(alpha), z.more)) return r;
+    z.store();
+    if (int r = z.finish()) return r;
+    return tp.stop(&st[2]);
+  });
+  if (rc) return rc;
+  st[4] = nrhs;
+  return 0;
+}
+
+// *logdet <- 2 sum log A(j,j); -> info: the first j (1-based) with A(j,j) <= 0 or NaN
+template <typename T>
+int logdet_impl(const chol_desc *A, double *logdet, int *info) {
+  hipStream_t s = main_stream();
+  *info = 0;
+  *logdet = 0;
+  if (A->lm == 0) return 0;
+  if (int rc = tr.ensure_bytes(3, logdet_part_bytes() + 2 * sizeof(double), "logdet_tile")) return rc;
+  double *part = tr.as<double>(3), *out = part + logdet_part_bytes() / sizeof(double);
+  launch_logdet<T>(s, geo_of(A), reinterpret_cast<const T *>(A->mat), part, out);
+  HIPCHECK(hipGetLastError());
+  double h[2] = {0, -1};
+  HIPCHECK(hipMemcpyAsync(h, out, sizeof h, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  *logdet = h[0];
+  if (h[1] >= 0) *info = (int)h[1] + 1;
+  return 0;
+}
+
+// the argument rules chol_trtrs_tile and chol_trmm_tile share (apos, bpos: the positions of A and B)
+int half_args(const char *what, chol_desc *A, int apos, chol_desc *B, int bpos) {
+  if (!A) return failf(-apos, "%s: NULL A", what);
+  if (!B) return failf(-bpos, "%s: NULL B", what);
+  if (A == B || (A->mat && A->mat == B->mat)) return failf(-bpos, "%s: B aliases A", what);
+  int rc = inverse_check(what, A, apos);
+  if (rc) return rc;
+  if ((rc = resident_whole(what, B))) return rc;
+  // (A's rows, but not same_rows: a one-tile A of order mb keeps its tile edge, an n x nrhs image of it is padded to 128)
+  if (B->lm != A->lm || B->mb != A->mb || B->dtype != A->dtype ||
+      (B->mbi != A->mbi && !(A->nt == 1 && B->mbi == roundup(A->mbi, MACRO))))
+    return failf(-bpos, "%s: B must have A's dtype, order and tile size", what);
+  if (!winv_fits(B)) return failf(CHOL_ERR_NOT_SUPPORTED, "%s: tile size above 4096", what);
+  return 0;
+}
+
 // the argument rules the butterfly routines share: A square, device-resident, single process, stored tile edge a
 // multiple of 128; depth 1 or 2; the order a multiple of 2^depth; W n x depth or wider with A's dtype and row tiling
 int rbt_args(const char *what, int uplo, chol_desc *A, int apos, chol_desc *W, int wpos, int depth, int dpos) {
@@ -1630,6 +1863,7 @@ void cholmi::spd_release() {
   cu.release();
   sy.release();
   rb.release();
+  tr.release();
 }
 
 // ---------------------------------------------------------------- the entry points (C linkage: include/cholmi.h)
@@ -1927,6 +2161,85 @@ int chol_chdd_tile(int uplo, chol_desc_t *A, chol_desc_t *V) {
 }
 
 int chol_last_chud_stats(double *out8) { return cu_stats.read("chud", out8); }
+
+int chol_trtrs_tile(int uplo, int trans, int diag, chol_desc_t *A, chol_desc_t *B) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "trtrs_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "trtrs_tile: uplo");
+  if (trans != CHOL_NOTRANS && trans != CHOL_TRANS) return fail(-2, "trtrs_tile: trans");
+  if (diag != CHOL_NONUNIT && diag != CHOL_UNIT) return fail(-3, "trtrs_tile: diag");
+  if (!A) return fail(-4, "trtrs_tile: NULL A");
+  if (!B) return fail(-5, "trtrs_tile: NULL B");
+  if (A == B || (A->mat && A->mat == B->mat)) return fail(-5, "trtrs_tile: B aliases A");
+  return with_views({{A, false}, {B, true}}, [&]() -> int {
+  int rc = half_args("trtrs_tile", A, 4, B, 5);
+  if (rc) return rc;
+  if (diag == CHOL_UNIT)
+    return fail(CHOL_ERR_NOT_SUPPORTED, "trtrs_tile: ChamUnit (a Cholesky factor has no unit diagonal)");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  const bool dbl = A->dtype == CHOL_REAL_DOUBLE;
+  const int up = uplo == CHOL_UPPER, tr_ = trans == CHOL_TRANS;
+  tr_stats.clear();
+  EventTimer tt;
+  if ((rc = tt.start())) return rc;
+  int info = 0;
+  rc = dbl ? diag_zero<double>(A, &info, "trtrs_tile") : diag_zero<float>(A, &info, "trtrs_tile");
+  if (rc) return rc;
+  if (info) return info;  // (LAPACK: B is unchanged)
+  rc = dbl ? trtrs_impl<double>(up, tr_, A, B, tr_stats.v) : trtrs_impl<float>(up, tr_, A, B, tr_stats.v);
+  if (rc) return rc;
+  return tt.stop(&tr_stats.v[0]);
+  });
+}
+
+int chol_trmm_tile(int side, int uplo, int trans, int diag, double alpha, chol_desc_t *A, chol_desc_t *B) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "trmm_tile before chol_init");
+  if (side != CHOL_LEFT && side != CHOL_RIGHT) return fail(-1, "trmm_tile: side");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-2, "trmm_tile: uplo");
+  if (trans != CHOL_NOTRANS && trans != CHOL_TRANS) return fail(-3, "trmm_tile: trans");
+  if (diag != CHOL_NONUNIT && diag != CHOL_UNIT) return fail(-4, "trmm_tile: diag");
+  if (!A) return fail(-6, "trmm_tile: NULL A");
+  if (!B) return fail(-7, "trmm_tile: NULL B");
+  if (A == B || (A->mat && A->mat == B->mat)) return fail(-7, "trmm_tile: B aliases A");
+  return with_views({{A, false}, {B, true}}, [&]() -> int {
+  int rc = half_args("trmm_tile", A, 6, B, 7);
+  if (rc) return rc;
+  if (side == CHOL_RIGHT) return fail(CHOL_ERR_NOT_SUPPORTED, "trmm_tile: ChamRight");
+  if (diag == CHOL_UNIT)
+    return fail(CHOL_ERR_NOT_SUPPORTED, "trmm_tile: ChamUnit (a Cholesky factor has no unit diagonal)");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  const int up = uplo == CHOL_UPPER, tr_ = trans == CHOL_TRANS;
+  tr_stats.clear();
+  EventTimer tt;
+  if ((rc = tt.start())) return rc;
+  rc = A->dtype == CHOL_REAL_DOUBLE ? trmm_impl<double>(up, tr_, alpha, A, B, tr_stats.v)
+                                    : trmm_impl<float>(up, tr_, alpha, A, B, tr_stats.v);
+  if (rc) return rc;
+  return tt.stop(&tr_stats.v[0]);
+  });
+}
+
+int chol_logdet_tile(chol_desc_t *A, double *logdet) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "logdet_tile before chol_init");
+  if (!A) return fail(-1, "logdet_tile: NULL A");
+  return with_views({{A, false}}, [&]() -> int {
+  int rc = inverse_check("logdet_tile", A, 1);
+  if (rc) return rc;
+  if (!logdet) return fail(-2, "logdet_tile: NULL logdet");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  int info = 0;
+  rc = A->dtype == CHOL_REAL_DOUBLE ? logdet_impl<double>(A, logdet, &info) : logdet_impl<float>(A, logdet, &info);
+  return rc ? rc : info;
+  });
+}
+
+int chol_last_trtrs_stats(double *out8) { return tr_stats.read("trtrs", out8); }
+
+int chol_debug_half_limits(int trtrs_cols, int trmm_cols) {
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  trtrs_kx = trtrs_cols < 0 ? TRTRS_KX : trtrs_cols;
+  trmm_kx = trmm_cols < 0 ? TRMM_KX : trmm_cols;
+  return 0;
+}
 
 int chol_sytrf_nopiv_tile(int uplo, chol_desc_t *A) {
   if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "sytrf_nopiv_tile before chol_init");

@@ -1,6 +1,7 @@
-// Device helpers shared by condest.hip (the one-vector sweeps of pocon) and refine.hip (the multi-vector sweeps and
-// the residual of porfs): the cut of a single-process tile image into 128 x 128 blocks of stored rows, and the
-// one-block product.  See condest.hip for the geometry.
+// Device helpers shared by condest.hip (the one-vector sweeps of pocon), refine.hip (the multi-vector sweeps and the
+// residual of porfs) and trmm.hip (the products with a triangle): the cut of a single-process tile image into
+// 128 x 128 blocks of stored rows, where a vector entry lies in an image, the wave reductions, and the one-block
+// product.  See condest.hip for the geometry.
 #pragma once
 #include "cholmi_internal.h"
 
@@ -44,11 +45,52 @@ __device__ __forceinline__ const T *block_at(const TileGeo &g, const T *A, int P
          (long)(Q % bpt) * CB * g.mbs;
 }
 
+// storage index of vector entry (block b, t) of column j of an n x ncols image with the matrix's row tiling
+__device__ __forceinline__ long desc_index(const TileGeo &g, long b, int t, int j) {
+  const int bpt = bpt_of(g);
+  return ((b / bpt) + (long)(j / g.mbu) * g.lmt) * (long)g.mbs * g.mbs + (b % bpt) * CB + t + (long)(j % g.mbu) * g.mbs;
+}
+
+// storage index of global row i of column 0 (the S vector) / of the diagonal entry A(i, i)
+__device__ __forceinline__ long col0_index(const TileGeo &g, long i) {
+  return (i / g.mbu) * (long)g.mbs * g.mbs + i % g.mbu;
+}
+__device__ __forceinline__ long diag_index(const TileGeo &g, long i) {
+  const long t = i / g.mbu, r = i % g.mbu;
+  return t * (g.lmt + 1) * (long)g.mbs * g.mbs + r + r * g.mbs;
+}
+
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// v[0..N) of every lane summed over the 64 lanes, N in {1, 2, 4, 8}: the first log2 N exchange steps halve the values a
+// lane holds (at offset 32 the lanes with bit 5 set keep the upper half and send the lower one, and so on), the rest
+// is a plain butterfly.  log2 N + (6 - log2 N) ... = N - 1 + 6 - log2 N exchanges instead of 6 N.  Returns the total of
+// vector *j in every lane (the lanes that share bits 5 .. 6 - log2 N of their index hold the same one); fixed order.
+template <typename T, int N>
+__device__ __forceinline__ T wave_sum_n(const T (&v)[N], int lane, int *j) {
+  T w[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) w[i] = v[i];
+  int jb = 0, off = 32;
+#pragma unroll
+  for (int cnt = N; cnt > 1; cnt >>= 1, off >>= 1) {
+    const bool hi = (lane & off) != 0;
+#pragma unroll
+    for (int i = 0; i < cnt / 2; ++i) {
+      const T keep = hi ? w[i + cnt / 2] : w[i], send = hi ? w[i] : w[i + cnt / 2];
+      w[i] = keep + __shfl_xor(send, off, 64);
+    }
+    if (hi) jb += cnt / 2;
+  }
+#pragma unroll
+  for (; off > 0; off >>= 1) w[0] += __shfl_xor(w[0], off, 64);
+  *j = jb;
+  return w[0];
 }
 
 // (P, Q), P >= Q, of pair index P (P + 1) / 2 + Q
@@ -75,6 +117,34 @@ __device__ __forceinline__ void load_pair(const T *S, int ld, int r, int c, int 
   const bool in = c < vc;
   a0 = (in && r < vr && (!lower || r >= c)) ? p[0] : T(0);
   a1 = (in && r + 1 < vr && (!lower || r + 1 >= c)) ? p[1] : T(0);
+}
+
+// load_pair for a block whose entries are used once (the products of trmm.hip): nontemporal loads; tri: 0 the whole
+// block, 1 its entries on or below the diagonal, 2 those on or above; nothing masked is loaded
+template <typename T>
+struct V2N;
+template <>
+struct V2N<double> {
+  typedef double t __attribute__((ext_vector_type(2)));
+};
+template <>
+struct V2N<float> {
+  typedef float t __attribute__((ext_vector_type(2)));
+};
+template <typename T>
+__device__ __forceinline__ void load_pair_nt(const T *S, int ld, int r, int c, int vr, int vc, int tri, T &a0, T &a1) {
+  const T *p = S + (long)c * ld + r;
+  if (vr == CB && vc == CB && tri == 0) {
+    const typename V2N<T>::t a = __builtin_nontemporal_load(reinterpret_cast<const typename V2N<T>::t *>(p));
+    a0 = a.x;
+    a1 = a.y;
+    return;
+  }
+  const bool in = c < vc;
+  const bool k0 = in && r < vr && (tri == 0 || (tri == 1 ? r >= c : r <= c));
+  const bool k1 = in && r + 1 < vr && (tri == 0 || (tri == 1 ? r + 1 >= c : r + 1 <= c));
+  a0 = k0 ? __builtin_nontemporal_load(p) : T(0);
+  a1 = k1 ? __builtin_nontemporal_load(p + 1) : T(0);
 }
 
 // out[t] = sum_c S(t, c) v[c] (TRANS: sum_r S(r, t) v[r]) for the 128 x 128 block S (ld), 256 threads; v and out in

@@ -371,6 +371,42 @@ int chol_chdd_tile(int uplo, chol_desc_t *A, chol_desc_t *V);
  * 0-based index of the vector at which a downdate stopped (-1: none); the rest 0. */
 int chol_last_chud_stats(double *out8);
 
+/* One half of a Cholesky factor alone: the triangular solve, the triangular product and the log-determinant, on
+ * device-resident single-process descriptors with the rules of chol_potrs_tile: A square (ragged orders and
+ * sub-matrix views included), stored tile edge a multiple of 64; B n x nrhs with A's dtype, order and tile size, any
+ * nrhs >= 0; a p x q block-cyclic descriptor returns CHOL_ERR_NOT_SUPPORTED.  fp64 or fp32 by the dtype, fp32 in
+ * single precision throughout.  T is the `uplo` triangle of A (what chol_potrf_tile(uplo, .) returned), op(T) = T
+ * (CHOL_NOTRANS) or T^T (CHOL_TRANS): all four combinations.  diag must be CHOL_NONUNIT: CHOL_UNIT returns
+ * CHOL_ERR_NOT_SUPPORTED, as chol_trtri_tile.  A IS ONLY READ and comes back bit for bit, all of it; the other strict
+ * triangle may hold anything, NaN included, and does not reach B.  No floating-point atomics and fixed summation
+ * orders: a repeated call returns the same bits.
+ *
+ * CHAMELEON_dtrtrs_Tile(uplo, trans, diag, A, B) -- LAPACK DTRTRS: B <- inv(op(T)) B.  (Lower, NoTrans) and (Upper,
+ * Trans) are the forward half of chol_potrs_tile, (Lower, Trans) and (Upper, NoTrans) its backward half: x = L^-T y
+ * takes the eigenvectors of chol_sygst_tile's standard problem back to the generalized one, |L^-1 y|^2 is the
+ * quadratic form of a Gaussian likelihood, L^-1 B whitens.  Up to 40 columns run as one pass of the narrow sweeps of
+ * chol_pocon_tile / chol_porfs_tile over the stored triangle, 8 columns at a time (a column's result does not depend
+ * on which columns share its pass); more columns run as one sweep of chol_potrs_tile's.  Returns info = i > 0
+ * (1-based) for the first exact zero T(i,i), found before B is written (B unchanged), as LAPACK.
+ * Argument errors: -1 uplo, -2 trans, -3 diag, -4 A, -5 B (NULL, another dtype, order or tile size, or B aliasing A). */
+int chol_trtrs_tile(int uplo, int trans, int diag, chol_desc_t *A, chol_desc_t *B);
+/* CHAMELEON_dtrmm_Tile(side, uplo, trans, diag, alpha, A, B) -- BLAS DTRMM: B <- alpha op(T) B, in place (x = L z is
+ * a sample with covariance L L^T).  side must be CHOL_LEFT: CHOL_RIGHT returns CHOL_ERR_NOT_SUPPORTED.  Up to 40
+ * columns run 8 at a time, each pass reading the stored triangle once; more columns run as products of whole tiles.
+ * Argument errors (chol_trsm_tile's positions): -1 side, -2 uplo, -3 trans, -4 diag, -6 A, -7 B (as above). */
+int chol_trmm_tile(int side, int uplo, int trans, int diag, double alpha, chol_desc_t *A, chol_desc_t *B);
+/* *logdet <- 2 sum_j log A(j,j): log det(L L^T) from the diagonal of the factor, which alone is read (either uplo).
+ * Logs and the sum in fp64 for both dtypes, as chol_lansy_tile's Frobenius sum, in a fixed order.  n = 0 gives 0.
+ * Returns info = j > 0 for the first A(j,j) that is <= 0 or NaN (*logdet is unspecified then).
+ * Argument errors: -1 A, -2 logdet NULL. */
+int chol_logdet_tile(chol_desc_t *A, double *logdet);
+/* The last chol_trtrs_tile / chol_trmm_tile: total, staging of the diagonal tiles, sweeps or products [ms]; the
+ * columns that went through the narrow path, those that went through the wide path; the rest 0. */
+int chol_last_trtrs_stats(double *out8);
+/* Diagnostic (scripts/trtrs_time.py measures the crossovers with it): the widest chol_trtrs_tile / chol_trmm_tile call
+ * that takes the narrow path; a negative value restores the built-in limit (40). */
+int chol_debug_half_limits(int trtrs_cols, int trmm_cols);
+
 /* The L D L^T factorisation WITHOUT pivoting of a symmetric matrix (MAGMA dsytrf_nopiv / ssytrf_nopiv; LAPACK
  * DSYTF2's storage for 1 x 1 pivots): A = L D L^T (Lower) or U^T D U (Upper, U = L^T), L unit lower triangular, D
  * diagonal.  On return the diagonal of A holds D and the strict `uplo` triangle holds L (U); the unit diagonal is not

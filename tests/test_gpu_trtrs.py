@@ -1,0 +1,429 @@
+"""The half solve, the half product and the log-determinant with a Cholesky factor on the device:
+CHAMELEON_dtrtrs_Tile, CHAMELEON_dtrmm_Tile, CHAMELEON_dlogdet_Tile (and the s forms); all four (uplo, trans), fp64 and
+fp32, the narrow paths (1, 3, 8 and 9 columns: one group, and a second group of one vector) and the wide ones (41), on
+a ragged last tile, a tile edge that is no multiple of 128, one tile larger than the matrix and a single tile.  A is
+stored as test_gpu_chud.py stores it: the other strict triangle is NaN, and the whole stored image of A, that triangle
+and the padding included, must come back bit for bit.
+
+Exact: on the dyadic cases that test_trtrs_host.py proves (trtrs_model.EXACT), trtrs returns the integer X from
+B = op(L) X bit for bit and trmm returns alpha op(L) X bit for bit (alpha = 1 and -2): sharp against a wrong mask, a
+wrong block, a padding read, or an order that depends on uninitialised scratch.
+
+Random family (A = G G^T, G n x 2n standard normal, L its LAPACK factor rounded to the dtype, B standard normal;
+kappa(L) about 6), with u = 2^-53 / 2^-24 and gamma_k = k u / (1 - k u):
+  trtrs   the componentwise backward error of every column, max_i |B - op(T) X|_i / (|op(T)| |X| + |B|)_i in fp64, is
+          at most n u: substitution in any order (Higham, Accuracy and Stability, Thm 8.5).  On these inputs the CPU
+          model with whole-tile inverses reaches 9.6 u and LAPACK 7.1 u (test_trtrs_host.py), so a failure is a bug
+  trmm    |C - alpha op(T) B| <= gamma_{n+2} |alpha| |op(T)| |B| entry by entry, the reference formed from the rounded
+          inputs in fp64 (np.longdouble for fp64): the product bound for any order, with or without fma
+  logdet  |value - ref| <= gamma_{n+4} 2 sum |log L_jj|, ref from the stored diagonal in np.longdouble: a log within
+          1 ulp and n - 1 additions."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+
+import trtrs_model as tm
+
+pytestmark = pytest.mark.gpu
+
+U = {"d": 2.0 ** -53, "s": 2.0 ** -24}
+
+
+def gamma(k, dt):
+    return k * U[dt] / (1 - k * U[dt])
+
+
+def npdt(dt):
+    return np.float64 if dt == "d" else np.float32
+
+
+def chdt(ch, dt):
+    return ch.ChamRealDouble if dt == "d" else ch.ChamRealFloat
+
+
+def bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
+
+
+def stored(M, u, fill=np.nan):
+    """the Lower factor M stored in the `u` triangle, the other strict one = fill"""
+    n = M.shape[0]
+    S = np.array(np.tril(M) if u == "L" else np.tril(M).T, order="F")
+    idx = np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
+    S[idx] = fill
+    return S
+
+
+def desc(ch, n, B, dt, r=None):
+    r = n if r is None else r
+    return ch.CHAMELEON_Desc_Create(None, chdt(ch, dt), B, B, B * B, n, r, 0, 0, n, r, 1, 1)
+
+
+def codes(ch, u, t):
+    return (ch.ChamLower if u == "L" else ch.ChamUpper), (ch.ChamNoTrans if t == "N" else ch.ChamTrans)
+
+
+def raw_image(d):
+    """the descriptor's stored tile image, padding included (through the HIP runtime this process has loaded)"""
+    ptr, nbytes = d.local_ptr()
+    path = next(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln)
+    hip = ctypes.CDLL(path)
+    out = np.empty(nbytes, dtype=np.uint8)
+    assert hip.hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), ctypes.c_size_t(nbytes), 2) == 0
+    return out
+
+
+class Factor:
+    """L (rounded to dt) on the device in the `u` triangle, NaN in the other; leaving the block checks that the whole
+    stored image is what it was, bit for bit, and destroys the descriptor"""
+
+    def __init__(self, ch, L, B, u, dt):
+        self.ch, self.u, self.dt, self.B, self.n = ch, u, dt, B, L.shape[0]
+        self.d = desc(ch, self.n, B, dt)
+        self.d.from_lapack(stored(L.astype(npdt(dt)), u))
+        self.before = raw_image(self.d)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        same = np.array_equal(raw_image(self.d), self.before)
+        self.ch.CHAMELEON_Desc_Destroy(self.d)
+        if exc[0] is None:
+            assert same, "A's stored image changed"
+
+    def _call(self, fn, M):
+        M = np.asarray(M, dtype=npdt(self.dt))
+        db = desc(self.ch, self.n, self.B, self.dt, M.shape[1])
+        db.from_lapack(np.asfortranarray(M))
+        info = fn(db)
+        out = db.to_lapack()
+        self.ch.CHAMELEON_Desc_Destroy(db)
+        return info, out
+
+    def trtrs(self, t, M):
+        ch = self.ch
+        uc, tc = codes(ch, self.u, t)
+        return self._call(lambda db: ch.CHAMELEON_dtrtrs_Tile(uc, tc, ch.ChamNonUnit, self.d, db), M)
+
+    def trmm(self, t, alpha, M):
+        ch = self.ch
+        uc, tc = codes(ch, self.u, t)
+        return self._call(lambda db: ch.CHAMELEON_dtrmm_Tile(ch.ChamLeft, uc, tc, ch.ChamNonUnit, alpha, self.d, db), M)
+
+
+def op_of(L, u, t):
+    """op(T) as a dense matrix, T the `u` triangle that stores the Lower factor L (U = L^T)"""
+    return np.tril(L) if tm.is_forward(u, t) else np.tril(L).T
+
+
+# ---------------------------------------------------------------- exact
+@pytest.mark.parametrize("fam,n,B,dt", tm.EXACT, ids=tm.EXACT_IDS)
+def test_exact(cham, fam, n, B, dt):
+    """trtrs returns X and trmm returns alpha op(L) X, bit for bit, on both paths"""
+    L, X = tm.factor(fam, n, B), tm.solution(n)
+    prod = {f: tm.half_product(L, X, f)[0] for f in (True, False)}
+    for u in "LU":
+        with Factor(cham, L, B, u, dt) as F:
+            for t in "NT":
+                P = prod[tm.is_forward(u, t)]
+                for nrhs in tm.NRHS:
+                    info, got = F.trtrs(t, P[:, :nrhs])
+                    assert info == 0
+                    assert np.array_equal(bits(got), bits(X[:, :nrhs].astype(npdt(dt)))), (u, t, nrhs, "trtrs")
+                    st = cham.last_trtrs_stats()
+                    assert (st["narrow_cols"], st["wide_cols"]) == ((nrhs, 0) if nrhs <= tm.NARROW else (0, nrhs))
+                    for alpha in (1.0, -2.0):
+                        info, got = F.trmm(t, alpha, X[:, :nrhs])
+                        assert info == 0
+                        assert np.array_equal(bits(got), bits((alpha * P[:, :nrhs]).astype(npdt(dt)))), (u, t, nrhs, alpha)
+                    st = cham.last_trtrs_stats()
+                    assert (st["narrow_cols"], st["wide_cols"]) == ((nrhs, 0) if nrhs <= tm.NARROW else (0, nrhs))
+
+
+# ---------------------------------------------------------------- the random family
+@functools.lru_cache(maxsize=None)
+def rounded(n, dt):
+    """-> (L, B) of trtrs_model.random_problem rounded to dt (read-only)"""
+    L, B = (a.astype(npdt(dt)) for a in tm.random_problem(n))
+    L.setflags(write=False)
+    B.setflags(write=False)
+    return L, B
+
+
+@functools.lru_cache(maxsize=None)
+def product_reference(n, dt, forward):
+    """op(L) B and |op(L)| |B| from the rounded inputs, in fp64 (np.longdouble for fp64)"""
+    L, B = rounded(n, dt)
+    hi = np.longdouble if dt == "d" else np.float64
+    M = np.tril(L) if forward else np.tril(L).T
+    return M.astype(hi) @ B.astype(hi), np.abs(M).astype(np.float64) @ np.abs(B).astype(np.float64)
+
+
+@pytest.mark.parametrize("dt", ["d", "s"])
+@pytest.mark.parametrize("n,B", tm.SHAPES)
+def test_random_family(cham, n, B, dt):
+    """trtrs within n u of componentwise backward error, trmm within gamma_{n+2}, the round trip within both; repeated
+    calls and another grouping of the columns give the same bits"""
+    L, R = rounded(n, dt)
+    worst = 0.0
+    for u in "LU":
+        with Factor(cham, L, B, u, dt) as F:
+            for t in "NT":
+                M = op_of(L, u, t)
+                ref, aref = product_reference(n, dt, tm.is_forward(u, t))
+                first = {}
+                for nrhs in tm.NRHS:
+                    info, X = F.trtrs(t, R[:, :nrhs])
+                    assert info == 0
+                    w = tm.solve_backward_error(M, X, R[:, :nrhs]).max()
+                    worst = max(worst, w / U[dt])
+                    assert w <= n * U[dt], (u, t, nrhs, w / U[dt])
+                    first[nrhs] = X
+                    for alpha in (1.0, -0.75):
+                        info, C = F.trmm(t, alpha, R[:, :nrhs])
+                        assert info == 0
+                        err = np.abs(C.astype(ref.dtype) - alpha * ref[:, :nrhs])
+                        assert np.all(err <= gamma(n + 2, dt) * abs(alpha) * aref[:, :nrhs]), (u, t, nrhs, alpha)
+                    # the round trip: trmm then trtrs returns B within the two bounds combined
+                    info, C = F.trmm(t, 1.0, R[:, :nrhs])
+                    info2, Y = F.trtrs(t, C)
+                    assert info == 0 and info2 == 0
+                    Y64, C64, M64 = (a.astype(np.float64) for a in (Y, C, M))
+                    # |op(T) (Y - B)| <= |op(T) Y - C| + |C - op(T) B| (Y - B is small: the product in fp64 is accurate)
+                    resid = np.abs(M64 @ (Y64 - R[:, :nrhs].astype(np.float64)))
+                    bound = n * U[dt] * (np.abs(M64) @ np.abs(Y64) + np.abs(C64)) + gamma(n + 2, dt) * aref[:, :nrhs]
+                    assert np.all(resid <= bound), (u, t, nrhs)
+                # repeated calls give identical bits (narrow and wide)
+                for nrhs in (8, tm.NARROW + 1):
+                    assert np.array_equal(bits(F.trtrs(t, R[:, :nrhs])[1]), bits(first[nrhs]))
+                    assert np.array_equal(bits(F.trmm(t, 1.0, R[:, :nrhs])[1]), bits(F.trmm(t, 1.0, R[:, :nrhs])[1]))
+                # the narrow result does not depend on which columns share a group
+                assert np.array_equal(bits(first[8][:, :1]), bits(first[1]))
+                assert np.array_equal(bits(first[9][:, :8]), bits(first[8]))
+                assert np.array_equal(bits(F.trmm(t, 1.0, R[:, :8])[1][:, :1]), bits(F.trmm(t, 1.0, R[:, :1])[1]))
+    print(f"n={n} B={B} {dt}: trtrs componentwise backward error at most {worst:.2f} u (bound {n} u)")
+
+
+# ---------------------------------------------------------------- logdet
+def logdet_check(ch, L, B, dt, u="L"):
+    n = L.shape[0]
+    Ld = L.astype(npdt(dt))
+    with Factor(ch, L, B, u, dt) as F:
+        info, v = ch.CHAMELEON_dlogdet_Tile(F.d)
+        again = ch.CHAMELEON_dlogdet_Tile(F.d)
+    logs = np.log(np.diag(Ld).astype(np.longdouble))
+    ref, scale = 2 * logs.sum(), 2 * np.abs(logs).sum()
+    assert info == 0 and again == (info, v)  # (the same bits)
+    assert abs(np.longdouble(v) - ref) <= gamma(n + 4, "d") * scale, (v, ref)
+
+
+@pytest.mark.parametrize("dt", ["d", "s"])
+@pytest.mark.parametrize("n,B", tm.SHAPES)
+def test_logdet(cham, n, B, dt):
+    logdet_check(cham, tm.random_problem(n)[0], B, dt, "L")
+    logdet_check(cham, tm.random_problem(n)[0], B, dt, "U")
+    logdet_check(cham, tm.factor("mod3", n, B), B, dt)
+
+
+def test_logdet_info(cham):
+    """info = j for a zero, a negative and a NaN diagonal entry; the first one wins.  (n = 0 cannot be asked for:
+    chol_desc_create refuses an empty descriptor)"""
+    ch = cham
+    n, B = 1000, 256
+    L = tm.random_problem(1000)[0]
+    for planted in ([(700, 0.0)], [(513, -1.0)], [(999, np.nan)], [(0, 0.0)], [(300, np.nan), (200, -2.0), (900, 0.0)]):
+        M = L.copy()
+        for j, v in planted:
+            M[j, j] = v
+        d = desc(ch, n, B, "d")
+        d.from_lapack(stored(M, "L"))
+        info, _ = ch.CHAMELEON_dlogdet_Tile(d)
+        ch.CHAMELEON_Desc_Destroy(d)
+        assert info == min(j for j, _ in planted) + 1
+
+
+# ---------------------------------------------------------------- against the existing routines
+@pytest.mark.parametrize("dt", ["d", "s"])
+@pytest.mark.parametrize("n,B", [(1100, 192), (1536, 256)])
+def test_both_halves_against_potrs(cham, n, B, dt):
+    """trtrs(Lower, NoTrans) then trtrs(Lower, Trans) is potrs: bit for bit on the wide path (the same launches), within
+    2 n u of componentwise backward error for A = L L^T on the narrow one"""
+    ch = cham
+    L, R = rounded(n, dt)
+    for u in "LU":
+        fwd, bwd = ("N", "T") if u == "L" else ("T", "N")
+        with Factor(ch, L, B, u, dt) as F:
+            for nrhs in (3, tm.NARROW + 1):
+                _, Y = F.trtrs(fwd, R[:, :nrhs])
+                _, X = F.trtrs(bwd, Y)
+                _, P = F._call(lambda db: ch.CHAMELEON_dpotrs_Tile(codes(ch, u, "N")[0], F.d, db), R[:, :nrhs])
+                if nrhs > tm.NARROW:
+                    assert np.array_equal(bits(X), bits(P)), (u, nrhs)
+                else:
+                    # |B - L (L^T X)| <= n u (|L| |Y| + |B|) + |L| n u (|L^T| |X| + |Y|): both halves' bounds composed
+                    L64, X64, Y64, R64 = (a.astype(np.float64) for a in (np.tril(L), X, Y, R[:, :nrhs]))
+                    resid = np.abs(R64 - L64 @ (L64.T @ X64))
+                    aL = np.abs(L64)
+                    bound = n * U[dt] * (aL @ np.abs(Y64) + np.abs(R64) + aL @ (aL.T @ np.abs(X64) + np.abs(Y64)))
+                    assert np.all(resid <= bound), (u, nrhs)
+
+
+def test_eigenvectors_of_the_generalized_problem(cham):
+    """what the feature exists for: after sygst and an eigensolver for C, x = inv(L)^T y solves A x = lambda B x"""
+    ch = cham
+    n, B, u = 300, 128, 2.0 ** -53
+    r = np.random.default_rng(300)
+    G = r.standard_normal((n, 2 * n))
+    Bm = G @ G.T
+    H = r.standard_normal((n, n))
+    A = H + H.T
+    L = np.linalg.cholesky(Bm)
+    da, db = desc(ch, n, B, "d"), desc(ch, n, B, "d")
+    da.from_lapack(stored(A, "L", 0.0))
+    db.from_lapack(stored(L, "L"))
+    assert ch.CHAMELEON_dsygst_Tile(1, ch.ChamLower, da, db) == 0
+    C = np.tril(da.to_lapack())
+    lam, Yv = np.linalg.eigh(C + np.tril(C, -1).T)
+    dy = desc(ch, n, B, "d")
+    dy.from_lapack(np.asfortranarray(Yv))
+    assert ch.CHAMELEON_dtrtrs_Tile(ch.ChamLower, ch.ChamTrans, ch.ChamNonUnit, db, dy) == 0
+    X = dy.to_lapack()
+    for d in (da, db, dy):
+        ch.CHAMELEON_Desc_Destroy(d)
+    inf = lambda M: np.abs(M).sum(axis=1).max()
+    kappa = inf(L) * inf(np.linalg.inv(L))
+    res = np.abs(A @ X - (Bm @ X) * lam[None, :]).max(axis=0)
+    bound = n * u * (inf(A) + np.abs(lam) * inf(Bm)) * np.abs(X).max(axis=0) * kappa
+    print(f"generalized eigenvectors: residual / bound at most {(res / bound).max():.3g}")
+    assert np.all(res <= bound)
+
+
+# ---------------------------------------------------------------- edge cases
+def test_sub_matrix_view(cham):
+    """a tile-aligned view of a device user buffer as A gives the whole-matrix descriptor's results bit for bit; the
+    user's buffer stays as it was, all of it"""
+    import torch
+
+    ch = cham
+    mb, lt, oi, oj, vt = 256, 5, 1, 2, 3
+    lm, m = lt * mb, vt * mb
+    user = np.random.default_rng(16).standard_normal(lt * lt * mb * mb)
+    buf = torch.from_numpy(user.copy()).cuda()
+    L, R = rounded(m, "d")
+    v = ch.CHAMELEON_Desc_Create(buf, ch.ChamRealDouble, mb, mb, mb * mb, lm, lm, oi * mb, oj * mb, m, m, 1, 1)
+    v.from_lapack(stored(L, "L"))
+    held = buf.cpu().numpy().copy()
+    with Factor(ch, L, mb, "L", "d") as F:
+        for nrhs in (3, tm.NARROW + 1):
+            for t in "NT":
+                tc = codes(ch, "L", t)[1]
+                db = desc(ch, m, mb, "d", nrhs)
+                db.from_lapack(np.asfortranarray(R[:, :nrhs]))
+                assert ch.CHAMELEON_dtrtrs_Tile(ch.ChamLower, tc, ch.ChamNonUnit, v, db) == 0
+                assert np.array_equal(bits(db.to_lapack()), bits(F.trtrs(t, R[:, :nrhs])[1]))
+                db.from_lapack(np.asfortranarray(R[:, :nrhs]))
+                assert ch.CHAMELEON_dtrmm_Tile(ch.ChamLeft, ch.ChamLower, tc, ch.ChamNonUnit, 0.5, v, db) == 0
+                assert np.array_equal(bits(db.to_lapack()), bits(F.trmm(t, 0.5, R[:, :nrhs])[1]))
+                ch.CHAMELEON_Desc_Destroy(db)
+        assert ch.CHAMELEON_dlogdet_Tile(v) == ch.CHAMELEON_dlogdet_Tile(F.d)
+    ch.CHAMELEON_Desc_Destroy(v)
+    assert np.array_equal(bits(buf.cpu().numpy()), bits(held))
+
+
+@pytest.mark.parametrize("dt", ["d", "s"])
+def test_no_columns_and_a_zero_pivot(cham, dt):
+    ch = cham
+    n, B = 1000, 256
+    L, R = rounded(n, dt)
+    # nrhs = 0 cannot be asked for: chol_desc_create refuses a descriptor without columns
+    with pytest.raises(ch.CholmiError) as e:
+        desc(ch, n, B, dt, 0)
+    assert e.value.code == -8
+    M = np.array(L)
+    M[600, 600] = 0.0
+    M[800, 800] = 0.0
+    for u in "LU":
+        with Factor(ch, M, B, u, dt) as F:
+            for t in "NT":
+                for nrhs in (3, tm.NARROW + 1):
+                    info, out = F.trtrs(t, R[:, :nrhs])
+                    assert info == 601
+                    assert np.array_equal(bits(out), bits(R[:, :nrhs]))  # (found before B is written)
+
+
+def test_argument_errors(cham):
+    ch = cham
+    from dense_linear_app_amd._lib import CholmiError, lib
+
+    n, B = 512, 256
+    NS, L_, U_, N_, T_, NU, UN, LE, RI = (-104, ch.ChamLower, ch.ChamUpper, ch.ChamNoTrans, ch.ChamTrans, ch.ChamNonUnit,
+                                          ch.ChamUnit, ch.ChamLeft, ch.ChamRight)
+    a, b = desc(ch, n, B, "d"), desc(ch, n, B, "d", 4)
+    a.from_lapack(np.asfortranarray(np.eye(n)))
+    b.from_lapack(np.asfortranarray(np.ones((n, 4))))
+    others = {"dtype": desc(ch, n, B, "s", 4), "order": desc(ch, n - B, B, "d", 4), "tile": desc(ch, n, 128, "d", 4),
+              "rect": desc(ch, n, B, "d", 2 * n)}
+    raw = lib()
+
+    def code(fn, *args):
+        with pytest.raises(CholmiError) as e:
+            fn(*args)
+        return e.value.code
+
+    trtrs, trmm = ch.CHAMELEON_dtrtrs_Tile, ch.CHAMELEON_dtrmm_Tile
+    assert code(trtrs, 7, N_, NU, a, b) == -1
+    assert code(trtrs, L_, 7, NU, a, b) == -2
+    assert code(trtrs, L_, N_, 7, a, b) == -3
+    assert code(trtrs, L_, N_, UN, a, b) == NS
+    assert raw.chol_trtrs_tile(L_, N_, NU, None, b.handle) == -4
+    assert raw.chol_trtrs_tile(L_, N_, NU, a.handle, None) == -5
+    assert code(trtrs, L_, N_, NU, others["rect"], b) == -4  # (A is not square)
+    assert code(trtrs, L_, N_, NU, a, a) == -5
+    for k in ("dtype", "order", "tile"):
+        assert code(trtrs, L_, N_, NU, a, others[k]) == -5, k
+    assert code(trmm, 7, L_, N_, NU, 1.0, a, b) == -1
+    assert code(trmm, RI, L_, N_, NU, 1.0, a, b) == NS
+    assert code(trmm, LE, 7, N_, NU, 1.0, a, b) == -2
+    assert code(trmm, LE, U_, 7, NU, 1.0, a, b) == -3
+    assert code(trmm, LE, U_, T_, 7, 1.0, a, b) == -4
+    assert code(trmm, LE, U_, T_, UN, 1.0, a, b) == NS
+    assert raw.chol_trmm_tile(LE, L_, N_, NU, 1.0, None, b.handle) == -6
+    assert raw.chol_trmm_tile(LE, L_, N_, NU, 1.0, a.handle, None) == -7
+    assert code(trmm, LE, L_, N_, NU, 1.0, others["rect"], b) == -6
+    assert code(trmm, LE, L_, N_, NU, 1.0, a, a) == -7
+    for k in ("dtype", "order", "tile"):
+        assert code(trmm, LE, L_, N_, NU, 1.0, a, others[k]) == -7, k
+    assert raw.chol_logdet_tile(None, None) == -1
+    assert raw.chol_logdet_tile(a.handle, None) == -2
+    assert code(ch.CHAMELEON_dlogdet_Tile, others["rect"]) == -1
+    # nothing above touched B; the good call still works
+    assert np.array_equal(b.to_lapack(), np.ones((n, 4)))
+    assert trtrs(L_, N_, NU, a, b) == 0 and trmm(LE, L_, N_, NU, 1.0, a, b) == 0
+    for d in [a, b] + list(others.values()):
+        ch.CHAMELEON_Desc_Destroy(d)
+
+
+def test_pxq_descriptor_is_not_supported(cham):
+    from dense_linear_app_amd._lib import lib
+
+    ch = cham
+    lib().chol_set_transport(None)
+    ch.set_rank(0, 2)
+    try:
+        mk = lambda: ch.CHAMELEON_Desc_Create(None, ch.ChamRealDouble, 256, 256, 256 * 256, 1024, 1024, 0, 0, 1024, 1024, 1, 2)
+        da, db = mk(), mk()
+        calls = [lambda: ch.CHAMELEON_dtrtrs_Tile(ch.ChamLower, ch.ChamNoTrans, ch.ChamNonUnit, da, db),
+                 lambda: ch.CHAMELEON_dtrmm_Tile(ch.ChamLeft, ch.ChamLower, ch.ChamNoTrans, ch.ChamNonUnit, 1.0, da, db),
+                 lambda: ch.CHAMELEON_dlogdet_Tile(da)]
+        for fn in calls:
+            with pytest.raises(ch.CholmiError) as e:
+                fn()
+            assert e.value.code == -104  # CHOL_ERR_NOT_SUPPORTED
+        ch.CHAMELEON_Desc_Destroy(da)
+        ch.CHAMELEON_Desc_Destroy(db)
+    finally:
+        ch.set_rank(0, 1)

@@ -1,0 +1,91 @@
+"""chol_trtrs_tile / chol_trmm_tile / chol_logdet_tile without a GPU: the symbols and wrappers, the numpy model of the
+narrow half solve (trtrs_model.py) beside LAPACK on the random family of the GPU test, and the proof that the dyadic
+cases of the GPU test are exact: the emulation with a Peak on every product returns X bit for bit, and 16 times the
+peak stays inside the dtype's integer range.
+
+Measured here on the random family (componentwise backward error of the half solve, in u = 2^-53 / 2^-24, the largest
+over both halves, every shape and 41 columns): the model with whole-tile inverses at most 9.6 u, LAPACK (scipy's
+solve_triangular) at most 7.1 u; the required bound is n u."""
+import numpy as np
+import pytest
+import scipy.linalg
+
+import dyadic_model as dm
+import trtrs_model as tm
+from dense_linear_app_amd import _lib
+from dense_linear_app_amd import chameleon as ch
+
+SYMBOLS = ["chol_trtrs_tile", "chol_trmm_tile", "chol_logdet_tile", "chol_last_trtrs_stats"]
+
+
+def test_wrappers_exist():
+    for p in "ds":
+        for r in ("trtrs", "trmm", "logdet"):
+            assert callable(getattr(ch, f"CHAMELEON_{p}{r}_Tile"))
+    assert callable(ch.last_trtrs_stats)
+    for s in SYMBOLS:
+        assert s in _lib.abi_symbols()
+        assert hasattr(_lib.lib(), s)
+
+
+@pytest.mark.parametrize("sym", SYMBOLS)
+def test_before_init_is_refused(sym):
+    L = _lib.lib()
+    args = {"chol_trtrs_tile": (ch.ChamLower, ch.ChamNoTrans, ch.ChamNonUnit, None, None),
+            "chol_trmm_tile": (ch.ChamLeft, ch.ChamLower, ch.ChamNoTrans, ch.ChamNonUnit, 1.0, None, None),
+            "chol_logdet_tile": (None, None), "chol_last_trtrs_stats": (None,)}[sym]
+    assert getattr(L, sym)(*args) == -101  # CHOL_ERR_NOT_INITIALIZED
+    assert b"before chol_init" in L.chol_last_error()
+
+
+@pytest.mark.parametrize("dt", ["d", "s"])
+@pytest.mark.parametrize("n,B", tm.SHAPES)
+def test_model_beside_lapack_on_the_random_family(n, B, dt):
+    """both reach a componentwise backward error far inside n u (Higham, Accuracy and Stability, Thm 8.5)"""
+    L64, B64 = tm.random_problem(n)
+    L, R = L64.astype(tm.npdt(dt)), B64.astype(tm.npdt(dt))
+    u = 2.0 ** -53 if dt == "d" else 2.0 ** -24
+    for forward in (True, False):
+        M = L if forward else L.T
+        wm = tm.solve_backward_error(M, tm.half_solve(L, R, B, forward, tm.npdt(dt)), R).max() / u
+        wl = tm.solve_backward_error(M, scipy.linalg.solve_triangular(L, R, lower=True, trans=0 if forward else 1), R).max() / u
+        print(f"n={n} B={B} {dt} {'forward' if forward else 'backward'}: model {wm:.2f} u, LAPACK {wl:.2f} u")
+        assert wm <= n and wl <= n
+
+
+@pytest.mark.parametrize("fam,n,B,dt", tm.EXACT, ids=tm.EXACT_IDS)
+def test_the_emulation_is_exact(fam, n, B, dt):
+    """every (family, shape, dtype) of the GPU test, both halves, all 41 columns at once"""
+    L, X = tm.factor(fam, n, B), tm.solution(n)
+    peak = dm.Peak()
+    for forward in (True, False):
+        Bm, pk = tm.half_product(L, X, forward)
+        # the product alpha op(L) X is exact in either dtype for |alpha| <= 2, whatever the order of its sums.  (The
+        # peak is at most 2.8e3 on every case but panel (2100, 512), where it is 2.94e3 forward and 3.84e3 backward.)
+        print(f"{fam} n={n} B={B} {'forward' if forward else 'backward'}: product peak {pk:.4g}")
+        assert pk <= (3.9e3 if (fam, n) == ("panel", 2100) else 2.8e3) and 16 * 2 * pk < tm.limit("s"), pk
+        Bd = Bm.astype(tm.npdt(dt))
+        assert np.array_equal(Bd.astype(np.float64), Bm)
+        got = tm.half_solve(L, Bd, B, forward, tm.npdt(dt), peak)
+        assert got.dtype == tm.npdt(dt) and np.array_equal(got.astype(np.float64), X)
+    print(f"{fam} n={n} B={B} {dt}: peak {peak.value:.3g}")
+    assert 16 * peak.value < tm.limit(dt), peak.value
+
+
+def test_the_case_list():
+    """the three thin families on all six shapes in both dtypes; panel where the tile is a multiple of 128, and at
+    (2100, 512) in fp64 only: there the whole-tile inverses leave the range of fp32"""
+    assert len(tm.SHAPES) == 6
+    for fam in ("parity", "mirror", "mod3"):
+        for n, B in tm.SHAPES:
+            assert (fam, n, B, "d") in tm.EXACT and (fam, n, B, "s") in tm.EXACT
+    panel = [c for c in tm.EXACT if c[0] == "panel"]
+    assert sorted(panel) == sorted([("panel", n, B, dt) for n, B in tm.SHAPES if B % 128 == 0 for dt in "ds"
+                                    if (n, B, dt) != (2100, 512, "s")])
+    # (2100, 512) in fp32: the same emulation in fp64 shows a peak that fp32 cannot hold
+    L, X = tm.factor("panel", 2100, 512), tm.solution(2100)
+    peak = dm.Peak()
+    for forward in (True, False):
+        tm.half_solve(L, tm.half_product(L, X, forward)[0], 512, forward, np.float64, peak)
+    print(f"panel n=2100 B=512: peak {peak.value:.3g}")
+    assert tm.limit("s") <= 16 * peak.value < tm.limit("d")
