@@ -80,6 +80,8 @@ def lib() -> C.CDLL:
         "chol_logdet_tile": ([vp, C.POINTER(d)], i),
         "chol_last_trtrs_stats": ([C.POINTER(d)], i),
         "chol_debug_half_limits": ([i, i], i),
+        "chol_symm_tile": ([i, i, d, vp, vp, d, vp], i),
+        "chol_last_symm_stats": ([C.POINTER(d)], i),
         "chol_sytrf_nopiv_tile": ([i, vp], i),
         "chol_sytrs_nopiv_tile": ([i, vp, vp], i),
         "chol_sysv_nopiv_tile": ([i, vp, vp], i),

@@ -456,6 +456,23 @@ def half_limits(trtrs_cols: int = -1, trmm_cols: int = -1) -> None:
     check("chol_debug_half_limits", lib().chol_debug_half_limits(trtrs_cols, trmm_cols))
 
 
+def CHAMELEON_dsymm_Tile(side: int, uplo: int, alpha: float, A: Desc, B: Desc, beta: float, C: Desc) -> int:
+    """BLAS DSYMM, side ChamLeft: C <- alpha A B + beta C for the symmetric A of which only the `uplo` triangle is read
+    (the other strict triangle may hold anything); B and C n x nrhs, any nrhs.  A and B are only read, B may be A, C
+    must not alias either.  beta == 0: C is not read; alpha == 0: A and B are not read.  ChamRight raises
+    (CHOL_ERR_NOT_SUPPORTED)."""
+    return check("chol_symm_tile", lib().chol_symm_tile(side, uplo, float(alpha), A.handle, B.handle, float(beta), C.handle))
+
+
+def last_symm_stats() -> dict:
+    """The last CHAMELEON_dsymm_Tile (chol_last_symm_stats): total and kernel time [ms], nrhs, the column width of a
+    workgroup's block of C (0: alpha == 0), the number of workgroups and the flop count 2 n^2 nrhs."""
+    v = (C.c_double * 8)()
+    check("chol_last_symm_stats", lib().chol_last_symm_stats(v))
+    return {"total_ms": v[0], "kernel_ms": v[1], "nrhs": int(v[2]), "block_cols": int(v[3]), "workgroups": int(v[4]),
+            "flops": v[5]}
+
+
 def CHAMELEON_dsytrf_nopiv_Tile(uplo: int, A: Desc) -> int:
     """A = L D L^T (ChamLower) or U^T D U (ChamUpper) without pivoting, for symmetric matrices whose factorisation
     needs none (quasi-definite, diagonally dominant): on return D on the diagonal of A and the unit triangular factor
@@ -547,6 +564,7 @@ CHAMELEON_schdd_Tile = CHAMELEON_dchdd_Tile
 CHAMELEON_strtrs_Tile = CHAMELEON_dtrtrs_Tile
 CHAMELEON_strmm_Tile = CHAMELEON_dtrmm_Tile
 CHAMELEON_slogdet_Tile = CHAMELEON_dlogdet_Tile
+CHAMELEON_ssymm_Tile = CHAMELEON_dsymm_Tile
 CHAMELEON_ssytrf_nopiv_Tile = CHAMELEON_dsytrf_nopiv_Tile
 CHAMELEON_ssytrs_nopiv_Tile = CHAMELEON_dsytrs_nopiv_Tile
 CHAMELEON_ssysv_nopiv_Tile = CHAMELEON_dsysv_nopiv_Tile

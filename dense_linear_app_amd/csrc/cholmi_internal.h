@@ -446,6 +446,16 @@ size_t logdet_part_bytes();
 template <typename T>
 void launch_logdet(hipStream_t s, const TileGeo &g, const T *A, double *part, double *out);
 
+// ---- launcher (symm.hip): chol_symm_tile (condest.hip's geometry) ----
+// C <- alpha A B + beta C: A the n x n image ga of which only the `upper` / lower triangle is read, B (gb) and C (gc)
+// n x nrhs images with A's row tiling (their stored tile edge may be A's rounded up to 128); one MFMA kernel for every
+// nrhs, a workgroup owning 128 rows x symm_width(nrhs) columns of C; alpha == 0: A and B are not read.  -> the number
+// of workgroups launched
+int symm_width(long nrhs);
+template <typename T>
+long launch_symm(hipStream_t s, const TileGeo &ga, int upper, const T *A, const TileGeo &gb, const T *B,
+                 const TileGeo &gc, T *C, T alpha, T beta);
+
 // ---- launchers (pstrf.hip): the pivoted panel of chol_pstrf_tile (LAPACK DPSTRF, Lower) on a single-process image.
 // Entry (r, c) of the n x n matrix at (r / mb + (c / mb) lmt) bsiz + r % mb + (c % mb) mbi; the padding is never
 // touched.  Scratch: dg, w (n each), pval, pidx (pstrf_chunks(n) each: the partial maxima of the candidates

@@ -1,7 +1,8 @@
 // The routines of libcholmi.so that work from a factor (include/cholmi.h), one section each below: the SPD solve, the
 // mixed-precision solve, the inverse, the condition estimate, the expert solve with error bounds, the pivoted
 // factorisation, the reduction of the generalized symmetric-definite eigenproblem, the L D L^T factorisation without
-// pivoting with its solve, their butterfly-randomised forms, and the rank-r update and downdate of a factor; the entry
+// pivoting with its solve, their butterfly-randomised forms, the rank-r update and downdate of a factor, the halves of a
+// factor alone, and the symmetric product from one stored triangle; the entry
 // points come last.  All run on the main
 // stream of the context that api.hip keeps (api_internal.h); this file owns only its scratch and the statistics of the
 // last call of each family.
@@ -54,7 +55,7 @@ struct LastStats {
     return 0;
   }
 };
-LastStats mx_stats, cn_stats, rf_stats, ps_stats, sg_stats, cu_stats, sy_stats, rb_stats, tr_stats;
+LastStats mx_stats, cn_stats, rf_stats, ps_stats, sg_stats, cu_stats, sy_stats, rb_stats, tr_stats, sm_stats;
 
 hipStream_t main_stream() { return main_rank_ctx()->st[ST_MAIN]; }
 
@@ -1795,6 +1796,36 @@ int trmm_impl(int upper, int trans, double alpha, chol_desc *A, chol_desc *B, do
   return 0;
 }
 
+// ---------------------------------------------------------------- the symmetric product (BLAS DSYMM, side Left)
+// C <- alpha A B + beta C from the `upper` / lower triangle of A, by symm.hip's one kernel for every nrhs; no scratch.
+// st: total, kernel [ms], nrhs, the column width of a workgroup's block (0: alpha == 0, A and B are not read), the
+// workgroups launched, 2 n^2 nrhs
+template <typename T>
+int symm_impl(int upper, double alpha, const chol_desc *A, const chol_desc *B, double beta, chol_desc *C, double *st) {
+  const int nrhs = B->ln;
+  st[2] = nrhs;
+  st[5] = 2.0 * (double)A->lm * (double)A->lm * nrhs;
+  if (A->lm == 0 || nrhs == 0) return 0;
+  EventTimer tp;
+  if (int rc = tp.start()) return rc;
+  const long wgs = launch_symm<T>(main_stream(), geo_of(A), upper, reinterpret_cast<const T *>(A->mat), geo_of(B),
+                                  reinterpret_cast<const T *>(B->mat), geo_of(C), reinterpret_cast<T *>(C->mat), T(alpha),
+                                  T(beta));
+  HIPCHECK(hipGetLastError());
+  st[3] = T(alpha) == T(0) ? 0 : symm_width(nrhs);
+  st[4] = (double)wgs;
+  return tp.stop(&st[1]);
+}
+
+// the rule for an n x nrhs operand X of chol_symm_tile (pos: its argument position): chol_trmm_tile's rule for its B
+int symm_operand(const chol_desc *A, const chol_desc *X, int pos, const char *name) {
+  if (int rc = resident_whole("symm_tile", X)) return rc;
+  if (X->lm != A->lm || X->mb != A->mb || X->dtype != A->dtype ||
+      (X->mbi != A->mbi && !(A->nt == 1 && X->mbi == roundup(A->mbi, MACRO))))
+    return failf(-pos, "symm_tile: %s must have A's dtype, order and tile size", name);
+  return 0;
+}
+
 // *logdet <- 2 sum log A(j,j); -> info: the first j (1-based) with A(j,j) <= 0 or NaN
 template <typename T>
 int logdet_impl(const chol_desc *A, double *logdet, int *info) {
@@ -2217,6 +2248,36 @@ int chol_trmm_tile(int side, int uplo, int trans, int diag, double alpha, chol_d
   return tt.stop(&tr_stats.v[0]);
   });
 }
+
+int chol_symm_tile(int side, int uplo, double alpha, chol_desc_t *A, chol_desc_t *B, double beta, chol_desc_t *C) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "symm_tile before chol_init");
+  if (side != CHOL_LEFT && side != CHOL_RIGHT) return fail(-1, "symm_tile: side");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-2, "symm_tile: uplo");
+  if (!A) return fail(-4, "symm_tile: NULL A");
+  if (!B) return fail(-5, "symm_tile: NULL B");
+  if (!C) return fail(-7, "symm_tile: NULL C");
+  if (C == A || C == B || (C->mat && (C->mat == A->mat || C->mat == B->mat)))
+    return fail(-7, "symm_tile: C aliases A or B");
+  return with_views({{A, false}, {B, false}, {C, true}}, [&]() -> int {
+  int rc = inverse_check("symm_tile", A, 4);
+  if (rc) return rc;
+  if ((rc = symm_operand(A, B, 5, "B"))) return rc;
+  if ((rc = symm_operand(A, C, 7, "C"))) return rc;
+  if (C->ln != B->ln || C->mbi != B->mbi) return fail(-7, "symm_tile: C must have B's width");
+  if (side == CHOL_RIGHT) return fail(CHOL_ERR_NOT_SUPPORTED, "symm_tile: ChamRight");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  sm_stats.clear();
+  EventTimer tt;
+  if ((rc = tt.start())) return rc;
+  const int up = uplo == CHOL_UPPER;
+  rc = A->dtype == CHOL_REAL_DOUBLE ? symm_impl<double>(up, alpha, A, B, beta, C, sm_stats.v)
+                                    : symm_impl<float>(up, alpha, A, B, beta, C, sm_stats.v);
+  if (rc) return rc;
+  return tt.stop(&sm_stats.v[0]);
+  });
+}
+
+int chol_last_symm_stats(double *out8) { return sm_stats.read("symm", out8); }
 
 int chol_logdet_tile(chol_desc_t *A, double *logdet) {
   if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "logdet_tile before chol_init");

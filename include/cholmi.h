@@ -407,6 +407,37 @@ int chol_last_trtrs_stats(double *out8);
  * that takes the narrow path; a negative value restores the built-in limit (40). */
 int chol_debug_half_limits(int trtrs_cols, int trmm_cols);
 
+/* The symmetric matrix product from one stored triangle: CHAMELEON_dsymm_Tile(side, uplo, alpha, A, B, beta, C) --
+ * BLAS DSYMM / SSYMM: C <- alpha A B + beta C.  A is n x n symmetric and only its `uplo` triangle is read: the other
+ * strict triangle may hold anything, NaN included, and does not reach C.  B and C are n x nrhs with A's dtype, order
+ * and tile size (chol_trmm_tile's rule for its B), any nrhs >= 1, also across several tile columns.  Device-resident
+ * single-process descriptors; ragged orders, tile edges that are no multiple of 128 and sub-matrix views (C writable)
+ * are served; a p x q block-cyclic descriptor returns CHOL_ERR_NOT_SUPPORTED.  side must be CHOL_LEFT: CHOL_RIGHT
+ * returns CHOL_ERR_NOT_SUPPORTED.  fp64 or fp32 by the dtype; fp32 runs in single precision throughout, alpha and beta
+ * rounded to float.
+ * A and B ARE ONLY READ: their stored images come back bit for bit, padding and the unreferenced triangle included.  B
+ * may be A itself; C must not alias A or B.  Of C only the entries of the matrix are written, its padding comes back
+ * bit for bit.
+ * The scalars follow BLAS: with beta == 0 C is not read (a NaN in C does not survive); with alpha == 0 A and B are not
+ * read and C <- beta C (C <- 0 when beta == 0 too).
+ * Arithmetic: one lane forms s = sum_k A(i,k) B(k,j) over k = 0 .. n-1 in ascending steps of four on the 16x16x4 MFMA,
+ * in the same order whatever nrhs is and whichever columns share its workgroup, then stores
+ *     C(i,j) <- fma(alpha, s, beta * C(i,j))      (beta != 0)        C(i,j) <- alpha * s      (beta == 0)
+ * and, with alpha == 0, C(i,j) <- beta * C(i,j) or 0.  No floating-point atomics, no partial sums: a repeated call
+ * returns the same bits, and a column's result depends neither on nrhs nor on its neighbours.
+ * One kernel serves every nrhs: a workgroup owns 128 rows of C and 16, 32, 64 or 128 columns (the smallest of these
+ * that holds nrhs, else 128) and reads its block row of A once, so the whole of A is read once per block of columns:
+ * twice the stored triangle, where the residual pass inside chol_dsposv_tile / chol_porfs_tile reads the triangle once
+ * per 8 columns.  Measured at N=65536 / 1024 and 16384 / 512, fp64: that pass is faster at one column (0.81 /
+ * 0.35 of this routine's time), this routine from 8 columns on (4.5 x / 1.7 x at 8, 12 x at 128 and 1024): the crossover
+ * lies between 1 and 8 columns.
+ * Argument errors (Chameleon's positions): -1 side, -2 uplo, -4 A (NULL or not square), -5 B (NULL, another dtype,
+ * order or tile size), -7 C (as B, a width that differs from B's, or C aliasing A or B). */
+int chol_symm_tile(int side, int uplo, double alpha, chol_desc_t *A, chol_desc_t *B, double beta, chol_desc_t *C);
+/* The last chol_symm_tile: total, kernel [ms] (the library's own events), nrhs, the column width of a workgroup's
+ * block (0 when alpha == 0), the number of workgroups, 2 n^2 nrhs; the rest 0. */
+int chol_last_symm_stats(double *out8);
+
 /* The L D L^T factorisation WITHOUT pivoting of a symmetric matrix (MAGMA dsytrf_nopiv / ssytrf_nopiv; LAPACK
  * DSYTF2's storage for 1 x 1 pivots): A = L D L^T (Lower) or U^T D U (Upper, U = L^T), L unit lower triangular, D
  * diagonal.  On return the diagonal of A holds D and the strict `uplo` triangle holds L (U); the unit diagonal is not
