@@ -49,7 +49,11 @@ struct ScratchPool {
     p[i] = nullptr;
     bytes[i] = 0;
     need = (need + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-    if (hipMalloc(&p[i], need) != hipSuccess || (Zero && hipMemset(p[i], 0, need) != hipSuccess))
+    // (the clearing runs on the null stream, which the library's non-blocking streams do not wait for, and hipMemset
+    // of device memory may return before it is done: without the synchronisation it can overtake and wipe what the
+    // caller's first kernels write into the new buffer)
+    if (hipMalloc(&p[i], need) != hipSuccess ||
+        (Zero && (hipMemset(p[i], 0, need) != hipSuccess || hipDeviceSynchronize() != hipSuccess)))
       return scratch_failed(what);
     bytes[i] = need;
     return 0;

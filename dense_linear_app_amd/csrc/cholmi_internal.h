@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/cholmi.h"
@@ -279,6 +280,22 @@ struct TileGeo {
   int lmt, lnt, mbs, mbu;
   long m, n;
 };
+// The image cut into 128 x 128 blocks of stored rows (condest.hip): its block rows, and the blocks (P, Q), P >= Q, of
+// one triangle
+inline long block_rows(const TileGeo &g) { return (long)g.lmt * ((g.mbs + MACRO - 1) / MACRO); }
+inline long tri_pairs(const TileGeo &g) { return block_rows(g) * (block_rows(g) + 1) / 2; }
+// The group size 1, 2, 4 or 8 that takes k <= 8 columns (more: 8), and f called with it as a
+// std::integral_constant: the kernels of a column group are instantiated for these four widths
+int refine_width(int k);
+template <typename F>
+void with_width(int k, F f) {
+  switch (refine_width(k)) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+  }
+}
 // side: 0 all, 1 on or below the diagonal, 2 on or above
 template <typename T>
 void launch_lacpy(hipStream_t s, const TileGeo &g, int side, const T *A, T *B);
@@ -295,7 +312,6 @@ void launch_lauum_lower(hipStream_t s, const T *L, T *out, int nt, int mbs);
 // ga: the n x n matrix (only the Lower / Upper stored triangle is read), gx: the n x nrhs images (same mbs / mbu).
 // part: sym_resid_part_bytes(ga, nrhs) of scratch; colmax: 2 nrhs zeroed words, max |R(:,j)| then max |X(:,j)| as
 // double bit patterns; Rf: R rounded to fp32 at the same positions; *flag |= 1 where an entry does not fit in fp32.
-int sym_resid_width(int nrhs);
 size_t sym_resid_part_bytes(const TileGeo &ga, int nrhs);
 void launch_sym_resid(hipStream_t s, const TileGeo &ga, int upper, const double *A, const TileGeo &gx, const double *X,
                       const double *B, double *part, float *Rf, unsigned long long *colmax, int *flag);
@@ -342,6 +358,7 @@ template <typename T>
 void launch_diag_zero(hipStream_t s, const T *A, long tstride, int mbs, int mbu, long n, int *first);
 
 // ---- launchers (condest.hip): chol_lansy_tile and chol_pocon_tile on a single-process image (any mbs) ----
+// and the triangular sweeps that chol_pocon_tile, chol_porfs_tile, chol_posvx_tile and chol_trtrs_tile share.
 // The image in 128 x 128 blocks of stored rows (bpt = ceil(mbs / 128) per tile); N-vectors of condest_vec_elems
 // entries in that order, zero outside the matrix.
 int condest_edge(const TileGeo &g);           // bpt 128: the edge of the staged diagonal tiles
@@ -355,14 +372,30 @@ void launch_lansy(hipStream_t s, const TileGeo &g, int upper, const T *A, double
 // diagonal, the identity outside the matrix
 template <typename T>
 void launch_stage_diag(hipStream_t s, const TileGeo &g, int upper, const T *A, T *Dv);
-// one application of A^{-1} = L^{-T} L^{-1} (U^{-1} U^{-T}): x <- A^{-1} x; Dv: the inverted diagonal tiles; y, pd
-// (bpt^2 blocks of 128), pg (2 NB bpt blocks of 128): scratch
+// pocon's own one-vector form: one application of A^{-1} = L^{-T} L^{-1} (U^{-1} U^{-T}): x <- A^{-1} x; Dv: the
+// inverted diagonal tiles; y, pd (bpt^2 blocks of 128), pg (2 NB bpt blocks of 128): scratch
 template <typename T>
 struct SweepBufs {
   T *x, *y, *pg, *pd;
 };
 template <typename T>
 void launch_sweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const T *Dv, const SweepBufs<T> &b);
+// count <= 8 applications of A^{-1} = L^{-T} L^{-1} (U^{-1} U^{-T}) at once, in the NV = refine_width(count) form:
+// x[j] <- A^{-1} x[j], each block of the factor read once per launch for all vectors; Dv: the inverted diagonal tiles;
+// pad: NV - count vectors of scratch for the unused places (none for count = 1, 2, 4, 8); scratch per vector: y, pd
+// (bpt^2 blocks of 128), pg (2 NB bpt blocks of 128), vector j's at y + j nv, pg + j 2 NB bpt 128, pd + j bpt^2 128:
+// msweep_scratch_elems(g) elements of T hold them for 8 vectors.
+// which = SWEEP_FORWARD / SWEEP_BACKWARD: one half alone, L y = x (U^T y = x) / L^T y = x (U y = x): vector j's
+// result is left at b.y + j condest_vec_elems(g) and x[j] is used up
+enum { SWEEP_BOTH = 0, SWEEP_FORWARD = 1, SWEEP_BACKWARD = 2 };
+template <typename T>
+struct MSweepBufs {
+  T *y, *pg, *pd;
+};
+size_t msweep_scratch_elems(const TileGeo &g);
+template <typename T>
+void launch_msweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const T *Dv, T *const *x, int count,
+                   T *pad, const MSweepBufs<T> &b, int which = SWEEP_BOTH);
 // x <- 1/n (mode 0), e_j (1; j a vector index), the alternating-sign vector of DLACN2 (2)
 template <typename T>
 void launch_vec_fill(hipStream_t s, const TileGeo &g, T *x, int mode, long j);
@@ -381,7 +414,6 @@ struct VecCols {
   int n;
   int v[8], d[8];
 };
-int refine_width(int k);  // the group size 1, 2, 4 or 8 that takes k <= 8 columns
 // mode 0: S(i) <- 1/sqrt(A(i,i)) (IEEE) where A(i,i) > 0; mode 1: only scan S.  part (diag_scan_part_bytes): per
 // workgroup min, max, the first 0-based i with a value <= 0 (or -1) of the scanned values
 size_t diag_scan_part_bytes();
@@ -409,20 +441,6 @@ template <typename T>
 void launch_porfs_resid(hipStream_t s, const TileGeo &ga, int upper, const T *A, const TileGeo &gx, const T *X,
                         const T *B, const VecCols &cols, T *part, T *R, T *F, double eps, double safe1, double safe2,
                         unsigned long long *berr);
-// count <= 8 applications of A^{-1} at once (the NV = refine_width(count) form of launch_sweep): x[j] <- A^{-1} x[j],
-// each block of the factor read once per launch for all vectors; pad: 7 vectors of scratch for the unused places;
-// y, pg, pd: msweep_scratch_elems(g) elements of T in all.
-// which = SWEEP_FORWARD / SWEEP_BACKWARD: one half alone, L y = x (U^T y = x) / L^T y = x (U y = x): vector j's
-// result is left at b.y + j condest_vec_elems(g) and x[j] is used up
-enum { SWEEP_BOTH = 0, SWEEP_FORWARD = 1, SWEEP_BACKWARD = 2 };
-template <typename T>
-struct MSweepBufs {
-  T *y, *pg, *pd;
-};
-size_t msweep_scratch_elems(const TileGeo &g);
-template <typename T>
-void launch_msweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const T *Dv, T *const *x, int count,
-                   T *pad, const MSweepBufs<T> &b, int which = SWEEP_BOTH);
 
 // ---- launchers (trmm.hip): chol_trmm_tile's narrow path and chol_logdet_tile (condest.hip's geometry) ----
 // B(:, cols.d[j]) <- alpha op(T) B(:, cols.d[j]) for at most 8 columns of the n x ncols image B (gx), T the `upper`

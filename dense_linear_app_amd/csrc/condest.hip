@@ -14,7 +14,10 @@
 // pass adds up per row in a fixed order; the max and the weighted sum of squares of each block are reduced
 // order-independently (integer max on the bits of a non-negative double) or in a fixed order.
 //
-// The sweeps (the hot path of pocon): L y = b and then L^T x = y, one vector each, one tile column per step.
+// The sweeps: L y = b and then L^T x = y, one tile column per step.  Two forms of one scheme live here: pocon's own
+// one-vector kernels (k_sweep_*) and the multi-vector kernels (k_msweep_*) of porfs, posvx and trtrs for NV = 1, 2, 4
+// or 8 vectors, each 128 x 128 block of the factor read once per launch for all of them.  pocon does not run the
+// NV = 1 instantiation: its application measured about 1 % slower so in fp64 (profiles/fold_blocks_ab.txt).
 // The diagonal tiles are inverted once per call (their 128-blocks by kernels.hip's diagonal-block kernel, then
 // the tile by inverse.hip's inner level), so that the step's serial part is a product, not a chain of solves.
 // Step k is two launches, each spread over 128 x 128 blocks, one workgroup per block:
@@ -43,12 +46,8 @@ __global__ __launch_bounds__(256) void k_lansy_blocks(TileGeo g, int upper, cons
                                                       double *__restrict__ part, double *__restrict__ ssq,
                                                       unsigned long long *res) {
   const long pair = blockIdx.x;
-  int P, Q;
-  pair_of(pair, P, Q);
-  const int br = upper ? Q : P, bc = upper ? P : Q;  // the stored block's block row and column
-  const T *S = block_at<T>(g, A, br, bc);
-  const int vr = block_valid(g, br), vc = block_valid(g, bc);
-  const bool diag = P == Q;
+  const TriBlock<T> b = tri_block<T>(g, A, upper, pair);
+  const bool diag = b.tri != 0;
   __shared__ double srow[4][CB];
   __shared__ double sred[2][4];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = 2 * lane;
@@ -57,14 +56,7 @@ __global__ __launch_bounds__(256) void k_lansy_blocks(TileGeo g, int upper, cons
   for (int k = 0; k < 32; ++k) {
     const int c = w * 32 + k;
     T t0, t1;
-    // (a diagonal block: only its stored half, which is the lower one for Lower and the upper one for Upper)
-    if (diag && upper) {
-      const T *p = S + (long)c * g.mbs + r;
-      t0 = (c < vc && r < vr && r <= c) ? p[0] : T(0);
-      t1 = (c < vc && r + 1 < vr && r + 1 <= c) ? p[1] : T(0);
-    } else {
-      load_pair<T>(S, g.mbs, r, c, vr, vc, diag, t0, t1);
-    }
+    load_pair<T>(b.S, g.mbs, r, c, b.vr, b.vc, b.tri, t0, t1);
     const double a0 = fabs((double)t0), a1 = fabs((double)t1);
     // the row sums take the stored half with the diagonal, the column sums the strict half
     const double ca0 = (diag && r == c) ? 0.0 : a0, ca1 = (diag && r + 1 == c) ? 0.0 : a1;
@@ -99,8 +91,7 @@ __global__ __launch_bounds__(256) void k_lansy_blocks(TileGeo g, int upper, cons
   }
 }
 
-// the row sums, added in a fixed order (the blocks (P, q), q <= P, of block row P, then (k, P), k >= P); res[1]: bits
-// of their max
+// the row sums, added in the fixed order of for_row_partials; res[1]: bits of their max
 __global__ __launch_bounds__(256) void k_lansy_rows(TileGeo g, const double *__restrict__ part,
                                                     unsigned long long *res) {
   const int NB = g.lmt * bpt_of(g);
@@ -109,8 +100,7 @@ __global__ __launch_bounds__(256) void k_lansy_rows(TileGeo g, const double *__r
   const int P = (int)(s / CB), t = (int)(s % CB);
   if (t >= block_valid(g, P)) return;
   double sum = 0.0;
-  for (int q = 0; q <= P; ++q) sum += part[(((long)P * (P + 1) / 2 + q) * 2 + 0) * CB + t];
-  for (int k = P; k < NB; ++k) sum += part[(((long)k * (k + 1) / 2 + P) * 2 + 1) * CB + t];
+  for_row_partials(P, NB, [&](long pair, int kind) { sum += part[(pair * 2 + kind) * CB + t]; });
   atomicMax(res + 1, (unsigned long long)__double_as_longlong(sum));
 }
 
@@ -231,6 +221,130 @@ __global__ __launch_bounds__(256) void k_sweep_rect(TileGeo g, int upper, const 
   if (t < CB) pg[(rho * bpt + kap) * CB + t] = so[t];
 }
 
+// ---------------------------------------------------------------- the multi-vector sweeps (porfs, posvx, trtrs)
+template <typename T>
+struct Vec8 {
+  T *p[8];
+};
+
+// step k, diagonal part, NV vectors: workgroup (P, Q), P >= Q, of Dinv_k; forward partial (P, Q) = Dinv(P,Q) v_Q,
+// backward partial (Q, P) = Dinv(P,Q)^T v_P; vector j's pending partials at pg + j pgn, its diag partials at
+// pd + j pdn + (rho * bpt + kappa) * 128 + t
+template <typename T, bool FWD, int NV>
+__global__ __launch_bounds__(256) void k_msweep_diag(TileGeo g, const T *__restrict__ Dk, int E, int k, Vec8<T> r,
+                                                     const T *__restrict__ pg, long pgn, T *__restrict__ pd, long pdn) {
+  int P, Q;
+  pair_of(blockIdx.x, P, Q);
+  const int bpt = E / CB;
+  const long kb0 = (long)k * bpt;
+  const int rho = FWD ? P : Q, kap = FWD ? Q : P;
+  __shared__ T sv[NV][CB], so[NV][CB];
+  __shared__ T red[4][NV][CB];
+  for (int e = threadIdx.x; e < NV * CB; e += 256) {
+    const int j = e / CB, t = e % CB;
+    // the input block kappa (local to tile k): r - the pending partials of the previous rect launch
+    T v = r.p[j][(kb0 + kap) * CB + t];
+    if (pg) {
+      T sp = 0;
+      for (int c = 0; c < bpt; ++c) sp += pg[j * pgn + ((kb0 + kap) * bpt + c) * CB + t];
+      v -= sp;
+    }
+    sv[j][t] = v;
+  }
+  __syncthreads();
+  const int vr = block_valid(g, (int)kb0 + P), vc = block_valid(g, (int)kb0 + Q);
+  // (the staged tiles are Lower: a diagonal block's half on or below the diagonal, never the upper one)
+  const T *S = Dk + (long)P * CB + (long)Q * CB * E;
+  block_product_nv<T, !FWD, NV, false>(S, E, vr, vc, P == Q ? 1 : 0, sv, so, red);
+  for (int e = threadIdx.x; e < NV * CB; e += 256) {
+    const int j = e / CB, t = e % CB;
+    pd[j * pdn + ((long)rho * bpt + kap) * CB + t] = so[j][t];
+  }
+}
+
+// step k, the blocks below (forward) / above (backward) tile k, NV vectors: workgroup (i, kappa) of block row
+// rho = row0 + i and block column kb0 + kappa.  y_k(kappa) from the diag partials; nrows == 0: only y_k is stored.
+template <typename T, bool FWD, int NV>
+__global__ __launch_bounds__(256) void k_msweep_rect(TileGeo g, int upper, const T *__restrict__ A, int k, int row0,
+                                                     int nrows, Vec8<T> r, const T *__restrict__ pg_prev,
+                                                     T *__restrict__ pg, long pgn, const T *__restrict__ pd, long pdn,
+                                                     Vec8<T> yout) {
+  const int bpt = bpt_of(g), i = blockIdx.x / bpt, kap = blockIdx.x % bpt;
+  const long kb0 = (long)k * bpt, rho = row0 + i;
+  __shared__ T sv[NV][CB], so[NV][CB];
+  __shared__ T red[4][NV][CB];
+  for (int e = threadIdx.x; e < NV * CB; e += 256) {
+    const int j = e / CB, t = e % CB;
+    // y_k(kappa): forward the partials (kappa, c), c <= kappa; backward (kappa, c), c >= kappa
+    T y = 0;
+    for (int c = FWD ? 0 : kap; c <= (FWD ? kap : bpt - 1); ++c) y += pd[j * pdn + ((long)kap * bpt + c) * CB + t];
+    sv[j][t] = y;
+    if (i == 0) yout.p[j][(kb0 + kap) * CB + t] = y;
+    // the previous rect launch's partials of this row (every row of this launch was one of its rows)
+    if (nrows > 0 && kap == 0 && pg_prev) {
+      T s = 0;
+      for (int c = 0; c < bpt; ++c) s += pg_prev[j * pgn + (rho * bpt + c) * CB + t];
+      r.p[j][rho * CB + t] -= s;
+    }
+  }
+  if (nrows == 0) return;
+  __syncthreads();
+  // forward L(rho, kappa) y: Lower the stored block (rho, kappa), Upper U(kappa, rho)^T; backward L(kappa, rho)^T y:
+  // Lower the stored block (kappa, rho) transposed, Upper U(rho, kappa)
+  const int kg = (int)(kb0 + kap);
+  const bool trans = FWD ? upper : !upper;
+  const int sr = trans ? kg : (int)rho, sc = trans ? (int)rho : kg;
+  const T *S = block_at<T>(g, A, sr, sc);
+  const int vr = block_valid(g, sr), vc = block_valid(g, sc);
+  if (trans)
+    block_product_nv<T, true, NV, false>(S, g.mbs, vr, vc, 0, sv, so, red);
+  else
+    block_product_nv<T, false, NV, false>(S, g.mbs, vr, vc, 0, sv, so, red);
+  for (int e = threadIdx.x; e < NV * CB; e += 256) {
+    const int j = e / CB, t = e % CB;
+    pg[j * pgn + (rho * bpt + kap) * CB + t] = so[j][t];
+  }
+}
+
+// which: SWEEP_BOTH x <- A^{-1} x; SWEEP_FORWARD / SWEEP_BACKWARD that half alone, its result left in the y vectors
+// (b.y + j nv) and x used up
+template <typename T, int NV>
+void msweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const T *Dv, const Vec8<T> &x, const MSweepBufs<T> &b,
+            int which) {
+  const int E = condest_edge(g), bpt = E / CB, nt = g.lmt, NB = nt * bpt;
+  const unsigned dwg = (unsigned)(bpt * (bpt + 1) / 2);
+  const long nv = (long)condest_vec_elems(g), pgs = (long)NB * bpt * CB, pgn = 2 * pgs, pdn = (long)bpt * bpt * CB;
+  Vec8<T> y{};
+  for (int j = 0; j < NV; ++j) y.p[j] = b.y + j * nv;
+  const bool half = which != SWEEP_BOTH;
+  for (int pass = which == SWEEP_BACKWARD ? 1 : 0; pass < (which == SWEEP_FORWARD ? 1 : 2); ++pass) {
+    const bool fwd = pass == 0;
+    // forward: b = x -> y; backward: y -> x (r: in place); one half alone: x -> y
+    const Vec8<T> r = fwd || half ? x : y, out = fwd || half ? y : x;
+    const T *pg_prev = nullptr;
+    for (int step = 0; step < nt; ++step) {
+      const int k = fwd ? step : nt - 1 - step;
+      T *pg = b.pg + (step % 2) * pgs;
+      const T *Dk = Dv + (long)k * E * E;
+      if (fwd)
+        hipLaunchKernelGGL((k_msweep_diag<T, true, NV>), dim3(dwg), dim3(256), 0, s, g, Dk, E, k, r, pg_prev, pgn, b.pd,
+                           pdn);
+      else
+        hipLaunchKernelGGL((k_msweep_diag<T, false, NV>), dim3(dwg), dim3(256), 0, s, g, Dk, E, k, r, pg_prev, pgn, b.pd,
+                           pdn);
+      const int row0 = fwd ? (k + 1) * bpt : 0, nrows = fwd ? NB - (k + 1) * bpt : k * bpt;
+      const unsigned rwg = (unsigned)(std::max(nrows, 1) * bpt);
+      if (fwd)
+        hipLaunchKernelGGL((k_msweep_rect<T, true, NV>), dim3(rwg), dim3(256), 0, s, g, upper, A, k, row0, nrows, r,
+                           pg_prev, pg, pgn, b.pd, pdn, out);
+      else
+        hipLaunchKernelGGL((k_msweep_rect<T, false, NV>), dim3(rwg), dim3(256), 0, s, g, upper, A, k, row0, nrows, r,
+                           pg_prev, pg, pgn, b.pd, pdn, out);
+      pg_prev = pg;
+    }
+  }
+}
+
 // ---------------------------------------------------------------- the estimator's vector operations
 // x over the NB * 128 entries: mode 0 -> 1/n, 1 -> e_j (j a storage index), 2 -> the alternating-sign vector
 // (-1)^i (1 + i / (n - 1)) of DLACN2's last step (i the 0-based global row); zero outside the matrix
@@ -330,14 +444,11 @@ __global__ __launch_bounds__(64) void k_vec_final(const double *__restrict__ par
 }  // namespace
 
 // ---------------------------------------------------------------- launchers
-size_t lansy_part_bytes(const TileGeo &g) {
-  const long NB = (long)g.lmt * ((g.mbs + CB - 1) / CB), pairs = NB * (NB + 1) / 2;
-  return (size_t)pairs * (2 * CB + 1) * sizeof(double);
-}
+size_t lansy_part_bytes(const TileGeo &g) { return (size_t)tri_pairs(g) * (2 * CB + 1) * sizeof(double); }
 
 template <typename T>
 void launch_lansy(hipStream_t s, const TileGeo &g, int upper, const T *A, double *part, double *res) {
-  const long NB = (long)g.lmt * ((g.mbs + CB - 1) / CB), pairs = NB * (NB + 1) / 2;
+  const long NB = block_rows(g), pairs = tri_pairs(g);
   double *ssq = part + pairs * 2 * CB;
   auto *bits = reinterpret_cast<unsigned long long *>(res);
   (void)hipMemsetAsync(res, 0, 3 * sizeof(double), s);
@@ -349,7 +460,7 @@ void launch_lansy(hipStream_t s, const TileGeo &g, int upper, const T *A, double
 
 int condest_edge(const TileGeo &g) { return (g.mbs + CB - 1) / CB * CB; }
 
-size_t condest_vec_elems(const TileGeo &g) { return (size_t)g.lmt * ((g.mbs + CB - 1) / CB) * CB; }
+size_t condest_vec_elems(const TileGeo &g) { return (size_t)block_rows(g) * CB; }
 
 template <typename T>
 void launch_stage_diag(hipStream_t s, const TileGeo &g, int upper, const T *A, T *Dv) {
@@ -388,6 +499,23 @@ void launch_sweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const 
   }
 }
 
+size_t msweep_scratch_elems(const TileGeo &g) {
+  const long bpt = (condest_edge(g) / CB), NB = block_rows(g), nv = (long)condest_vec_elems(g);
+  return (size_t)8 * (nv + 2 * NB * bpt * CB + bpt * bpt * CB);
+}
+
+template <typename T>
+void launch_msweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const T *Dv, T *const *x, int count,
+                   T *pad, const MSweepBufs<T> &b, int which) {
+  const long nv = (long)condest_vec_elems(g);
+  with_width(count, [&](auto width) {
+    constexpr int NV = decltype(width)::value;
+    Vec8<T> v{};
+    for (int j = 0; j < NV; ++j) v.p[j] = j < count ? x[j] : pad + (long)(j - count) * nv;  // (padding: results unused)
+    msweep<T, NV>(s, g, upper, A, Dv, v, b, which);
+  });
+}
+
 template <typename T>
 void launch_vec_fill(hipStream_t s, const TileGeo &g, T *x, int mode, long j) {
   const long total = (long)condest_vec_elems(g);
@@ -410,6 +538,8 @@ void launch_vec_stats(hipStream_t s, const TileGeo &g, T *x, int *isgn, int sign
   template void launch_lansy<T>(hipStream_t, const TileGeo &, int, const T *, double *, double *);           \
   template void launch_stage_diag<T>(hipStream_t, const TileGeo &, int, const T *, T *);                     \
   template void launch_sweep<T>(hipStream_t, const TileGeo &, int, const T *, const T *, const SweepBufs<T> &); \
+  template void launch_msweep<T>(hipStream_t, const TileGeo &, int, const T *, const T *, T *const *, int, T *, \
+                                 const MSweepBufs<T> &, int);                                                \
   template void launch_vec_fill<T>(hipStream_t, const TileGeo &, T *, int, long);                            \
   template void launch_vec_stats<T>(hipStream_t, const TileGeo &, T *, int *, int, long, double *, double *);
 INSTANTIATE_CONDEST(double)

@@ -3,8 +3,8 @@
 // and the fp64 update X += C.  Single-process, device-resident tile images: stored tiles of mbs x mbs elements
 // (mbs a multiple of 128) of which the caller's tile is the leading mbu x mbu part (TileGeo, cholmi_internal.h).
 //
-// The residual works on the 128 x 128 blocks of the stored image.  Block row P of the image is stored rows
-// [128 P, 128 P + 128): tile P / (mbs / 128), so every block lies inside one tile and padding is masked per entry.
+// The residual works on the 128 x 128 blocks of the stored image (sweep_blocks.h; see condest.hip for the geometry):
+// every block lies inside one tile and padding is masked per entry.
 // One workgroup per stored block of the triangle (pair (P, Q), P >= Q, of the symmetric matrix) reads the block
 // once and produces both of its products: A(P,Q) X_Q (goes to R_P) and A(P,Q)^T X_P (goes to R_Q); a diagonal
 // block is made symmetric from its stored half (the diagonal counted once).  The products are written as
@@ -15,44 +15,14 @@
 #include <type_traits>
 
 #include "cholmi_internal.h"
+#include "sweep_blocks.h"
 
 namespace cholmi {
 
 namespace {
 
-constexpr int RB = 128;  // residual block edge
-
 __device__ __forceinline__ void atomic_max_abs(unsigned long long *addr, double v) {
   atomicMax(addr, (unsigned long long)__double_as_longlong(fabs(v)));
-}
-
-// rows of stored block row b that lie inside the matrix (0 ... 128)
-__device__ __forceinline__ int block_valid(const TileGeo &g, int b) {
-  const int bpt = g.mbs / RB, t = b / bpt, r0 = (b % bpt) * RB;
-  const long left = min((long)g.mbu, g.m - (long)t * g.mbu) - r0;
-  return (int)max(0L, min((long)RB, left));
-}
-
-// stored index of entry (stored row s, column j) of an n x ncols image
-__device__ __forceinline__ long vec_index(const TileGeo &g, long s, int j) {
-  const long t = s / g.mbs, rr = s - t * g.mbs;
-  const int tj = j / g.mbu, cj = j - tj * g.mbu;
-  return (t + (long)tj * g.lmt) * g.mbs * g.mbs + rr + (long)cj * g.mbs;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// (P, Q), P >= Q, of pair index P (P + 1) / 2 + Q
-__device__ __forceinline__ void pair_of(long pair, int &P, int &Q) {
-  int p = (int)((sqrt(8.0 * (double)pair + 1.0) - 1.0) * 0.5);
-  while ((long)p * (p + 1) / 2 > pair) --p;
-  while ((long)(p + 1) * (p + 2) / 2 <= pair) ++p;
-  P = p;
-  Q = (int)(pair - (long)p * (p + 1) / 2);
 }
 
 // One stored block of the triangle per workgroup (4 waves, 32 columns each; lane l holds rows 2l, 2l+1).
@@ -63,22 +33,17 @@ __global__ __launch_bounds__(256) void k_sym_resid(TileGeo ga, int upper, const 
                                                    const double *__restrict__ X, int j0, int nr,
                                                    double *__restrict__ part) {
   const long pair = blockIdx.x;
-  int P, Q;
-  pair_of(pair, P, Q);
-  // the stored block: Lower at block (P, Q), Upper at (Q, P); its rows are block row br, its columns block column bc
-  const int br = upper ? Q : P, bc = upper ? P : Q;
-  const int bpt = ga.mbs / RB;
-  const double *S = A + ((long)(br / bpt) + (long)(bc / bpt) * ga.lmt) * ga.mbs * ga.mbs + (long)(br % bpt) * RB +
-                    (long)(bc % bpt) * RB * ga.mbs;
-  const int vr = block_valid(ga, br), vc = block_valid(ga, bc);
-  const bool diag = P == Q;
-  __shared__ double sv[NR][RB];        // X rows of the block's columns
-  __shared__ double srow[4][NR][RB];   // per-wave row products
+  const TriBlock<double> b = tri_block<double>(ga, A, upper, pair);
+  const double *S = b.S;
+  const int br = b.br, bc = b.bc, vr = b.vr, vc = b.vc;
+  const bool diag = b.tri != 0;
+  __shared__ double sv[NR][CB];        // X rows of the block's columns
+  __shared__ double srow[4][NR][CB];   // per-wave row products
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  for (int e = tid; e < NR * RB; e += 256) {
-    const int j = e / RB, c = e % RB;
+  for (int e = tid; e < NR * CB; e += 256) {
+    const int j = e / CB, c = e % CB;
     double v = 0.0;
-    if (c < vc && j < nr) v = ABS ? 1.0 : X[vec_index(gx, (long)bc * RB + c, j0 + j)];
+    if (c < vc && j < nr) v = ABS ? 1.0 : X[desc_index(gx, bc, c, j0 + j)];
     sv[j][c] = v;
   }
   double u[2][NR];
@@ -87,7 +52,7 @@ __global__ __launch_bounds__(256) void k_sym_resid(TileGeo ga, int upper, const 
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
       const int r = 2 * lane + k;
-      u[k][j] = (r < vr && j < nr) ? (ABS ? 1.0 : X[vec_index(gx, (long)br * RB + r, j0 + j)]) : 0.0;
+      u[k][j] = (r < vr && j < nr) ? (ABS ? 1.0 : X[desc_index(gx, br, r, j0 + j)]) : 0.0;
     }
   __syncthreads();
   double racc[2][NR], cres[NR];
@@ -114,7 +79,7 @@ __global__ __launch_bounds__(256) void k_sym_resid(TileGeo ga, int upper, const 
       const double v = sv[j][c];
       racc[0][j] = fma(ra0, v, racc[0][j]);
       racc[1][j] = fma(ra1, v, racc[1][j]);
-      const double s = wave_sum(fma(ca1, u[1][j], ca0 * u[0][j]));
+      const double s = wave_sum<double>(fma(ca1, u[1][j], ca0 * u[0][j]));
       if (lane == k) cres[j] = s;
     }
   }
@@ -126,34 +91,33 @@ __global__ __launch_bounds__(256) void k_sym_resid(TileGeo ga, int upper, const 
   __syncthreads();
   // Lower: the row product is A(P,Q) X_Q (-> R_P), the column product A(P,Q)^T X_P (-> R_Q); Upper the other way round
   const int krow = upper ? 1 : 0, kcol = 1 - krow;
-  double *prow = part + (pair * 2 + krow) * NR * RB, *pcol = part + (pair * 2 + kcol) * NR * RB;
-  for (int e = tid; e < NR * RB; e += 256) {
-    const int j = e / RB, t = e % RB;
+  double *prow = part + (pair * 2 + krow) * NR * CB, *pcol = part + (pair * 2 + kcol) * NR * CB;
+  for (int e = tid; e < NR * CB; e += 256) {
+    const int j = e / CB, t = e % CB;
     prow[e] = ((srow[0][j][t] + srow[1][j][t]) + srow[2][j][t]) + srow[3][j][t];
   }
   if (lane < 32)
 #pragma unroll
-    for (int j = 0; j < NR; ++j) pcol[j * RB + w * 32 + lane] = cres[j];
+    for (int j = 0; j < NR; ++j) pcol[j * CB + w * 32 + lane] = cres[j];
 }
 
-// R(s, j0 + j) = B - (sum of the partial products of stored row s), added in a fixed order: the blocks (P, Q), Q <= P,
-// of block row P, then (K, P), K >= P.  Rf (may be null): R rounded to fp32, *flag raised where |R| > FLT_MAX
+// R(s, j0 + j) = B - (sum of the partial products of stored row s), added in the fixed order of for_row_partials.
+// Rf (may be null): R rounded to fp32, *flag raised where |R| > FLT_MAX
 // -- or, RO = double, R itself.  colmax[j]: max |R(:,j)|, colmax[ncols + j]: max |X(:,j)| (X may be null).
 template <int NR, typename RO>
 __global__ __launch_bounds__(256) void k_sym_resid_reduce(TileGeo ga, TileGeo gx, const double *__restrict__ part,
                                                           int j0, const double *__restrict__ B,
                                                           const double *__restrict__ X, RO *__restrict__ Rf,
                                                           unsigned long long *colmax, int *flag) {
-  const int NB = ga.lmt * (ga.mbs / RB);
+  const int NB = ga.lmt * bpt_of(ga);
   const long s = (long)blockIdx.x * 256 + threadIdx.x;
   const int j = blockIdx.y;
-  if (s >= (long)NB * RB) return;
-  const int P = (int)(s / RB), t = (int)(s % RB);
+  if (s >= (long)NB * CB) return;
+  const int P = (int)(s / CB), t = (int)(s % CB);
   if (t >= block_valid(ga, P)) return;
   double sum = 0.0;
-  for (int q = 0; q <= P; ++q) sum += part[(((long)P * (P + 1) / 2 + q) * 2 + 0) * NR * RB + j * RB + t];
-  for (int k = P; k < NB; ++k) sum += part[(((long)k * (k + 1) / 2 + P) * 2 + 1) * NR * RB + j * RB + t];
-  const long idx = vec_index(gx, s, j0 + j);
+  for_row_partials(P, NB, [&](long pair, int kind) { sum += part[(pair * 2 + kind) * NR * CB + j * CB + t]; });
+  const long idx = desc_index(gx, P, t, j0 + j);
   const double rv = (B ? B[idx] : 0.0) - sum;
   if (Rf) {
     if (std::is_same<RO, float>::value && fabs(rv) > (double)FLT_MAX) atomicOr(flag, 1);
@@ -208,7 +172,7 @@ __global__ __launch_bounds__(256) void k_vec_to_f32(TileGeo gx, const double *__
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
     const long gi = e % gx.m;
     const int j = (int)(e / gx.m);
-    const long idx = vec_index(gx, gi / gx.mbu * gx.mbs + gi % gx.mbu, j);
+    const long idx = image_index(gx, gi, j);
     const double b = B[idx];
     if (fabs(b) > (double)FLT_MAX) atomicOr(flag, 1);
     Bf[idx] = (float)b;
@@ -222,7 +186,7 @@ __global__ __launch_bounds__(256) void k_vec_update(TileGeo gx, const float *__r
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
     const long gi = e % gx.m;
     const int j = (int)(e / gx.m);
-    const long idx = vec_index(gx, gi / gx.mbu * gx.mbs + gi % gx.mbu, j);
+    const long idx = image_index(gx, gi, j);
     const double c = (double)C[idx];
     X[idx] = assign ? c : X[idx] + c;
   }
@@ -234,22 +198,19 @@ template <int NR, typename RO>
 void resid_pass(hipStream_t s, const TileGeo &ga, int upper, const double *A, const TileGeo &gx, const double *X,
                 const double *B, int j0, int nr, double *part, RO *Rf, unsigned long long *colmax, int *flag,
                 bool abs_mode) {
-  const long NB = (long)ga.lmt * (ga.mbs / RB), pairs = NB * (NB + 1) / 2;
+  const long NB = block_rows(ga), pairs = tri_pairs(ga);
   if (abs_mode)
     hipLaunchKernelGGL((k_sym_resid<NR, true>), dim3((unsigned)pairs), dim3(256), 0, s, ga, upper, A, gx, X, j0, nr, part);
   else
     hipLaunchKernelGGL((k_sym_resid<NR, false>), dim3((unsigned)pairs), dim3(256), 0, s, ga, upper, A, gx, X, j0, nr, part);
-  hipLaunchKernelGGL((k_sym_resid_reduce<NR, RO>), dim3((unsigned)((NB * RB + 255) / 256), (unsigned)nr), dim3(256), 0, s,
+  hipLaunchKernelGGL((k_sym_resid_reduce<NR, RO>), dim3((unsigned)((NB * CB + 255) / 256), (unsigned)nr), dim3(256), 0, s,
                      ga, gx, part, j0, B, X, Rf, colmax, flag);
 }
 
 }  // namespace
 
-int sym_resid_width(int nrhs) { return nrhs <= 1 ? 1 : nrhs <= 2 ? 2 : nrhs <= 4 ? 4 : 8; }
-
 size_t sym_resid_part_bytes(const TileGeo &ga, int nrhs) {
-  const long NB = (long)ga.lmt * (ga.mbs / RB);
-  return (size_t)(NB * (NB + 1) / 2) * 2 * RB * sym_resid_width(nrhs) * sizeof(double);
+  return (size_t)tri_pairs(ga) * 2 * CB * refine_width(nrhs) * sizeof(double);
 }
 
 template <typename RO>
@@ -258,12 +219,9 @@ void sym_resid_blocks(hipStream_t s, const TileGeo &ga, int upper, const double 
   // column blocks of X of up to 8 right-hand sides, each one pass over the stored triangle
   for (int j0 = 0; j0 < gx.n; j0 += 8) {
     const int nr = (int)std::min<long>(8, gx.n - j0);
-    switch (sym_resid_width(nr)) {
-      case 1: resid_pass<1, RO>(s, ga, upper, A, gx, X, B, j0, nr, part, Rf, colmax, flag, false); break;
-      case 2: resid_pass<2, RO>(s, ga, upper, A, gx, X, B, j0, nr, part, Rf, colmax, flag, false); break;
-      case 4: resid_pass<4, RO>(s, ga, upper, A, gx, X, B, j0, nr, part, Rf, colmax, flag, false); break;
-      default: resid_pass<8, RO>(s, ga, upper, A, gx, X, B, j0, nr, part, Rf, colmax, flag, false); break;
-    }
+    with_width(nr, [&](auto w) {
+      resid_pass<decltype(w)::value, RO>(s, ga, upper, A, gx, X, B, j0, nr, part, Rf, colmax, flag, false);
+    });
   }
 }
 

@@ -8,10 +8,8 @@
 // once and forms four products for up to 8 columns: A X and A^T X, |A| |X| and |A|^T |X| (a diagonal block made
 // symmetric from its stored half).  A second pass adds the per-block partials in a fixed order, forms R = B - A X and
 // W = |A||X| + |B|, the componentwise backward error of each column (an order-independent max) and the FERR weight
-// vector |R| + nz eps W, both written as condest-layout vectors (v[128 b + t], zero outside the matrix).
-//
-// The multi-vector sweeps: condest.hip's k_sweep_diag / k_sweep_rect for NV = 1, 2, 4, 8 vectors, each 128 x 128 block
-// of the factor read once per launch for all of them.  Partial sums keep their fixed order: bit-identical runs.
+// vector |R| + nz eps W, both written as condest-layout vectors (v[128 b + t], zero outside the matrix).  The
+// applications of A^{-1} between two residuals are condest.hip's sweeps.
 #include <cfloat>
 
 #include "cholmi_internal.h"
@@ -107,8 +105,7 @@ __global__ __launch_bounds__(256) void k_row_scale(TileGeo gx, T *__restrict__ D
   for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
     const long gi = e % gx.m;
     const int j = (int)(e / gx.m);
-    const long idx = ((gi / gx.mbu) + (long)(j / gx.mbu) * gx.lmt) * (long)gx.mbs * gx.mbs + gi % gx.mbu +
-                     (long)(j % gx.mbu) * gx.mbs;
+    const long idx = image_index(gx, gi, j);
     D[idx] = S[col0_index(gx, gi)] * D[idx];
   }
 }
@@ -160,12 +157,9 @@ template <typename T, int NR>
 __global__ __launch_bounds__(256) void k_porfs_resid(TileGeo ga, int upper, const T *__restrict__ A, TileGeo gx,
                                                      const T *__restrict__ X, VecCols cols, T *__restrict__ part) {
   const long pair = blockIdx.x;
-  int P, Q;
-  pair_of(pair, P, Q);
-  const int br = upper ? Q : P, bc = upper ? P : Q;  // the stored block's block row and column
-  const T *S = block_at<T>(ga, A, br, bc);
-  const int vr = block_valid(ga, br), vc = block_valid(ga, bc);
-  const bool diag = P == Q;
+  const TriBlock<T> b = tri_block<T>(ga, A, upper, pair);
+  const int br = b.br, bc = b.bc, vr = b.vr, vc = b.vc;
+  const bool diag = b.tri != 0;
   const int nr = cols.n;
   __shared__ T sv[NR][CB];         // X rows of the block's columns
   __shared__ T srow[4][NR][CB];    // per-wave row products (A X, then |A| |X|)
@@ -189,14 +183,7 @@ __global__ __launch_bounds__(256) void k_porfs_resid(TileGeo ga, int upper, cons
   for (int k = 0; k < 32; ++k) {
     const int c = w * 32 + k;
     T t0, t1;
-    // (a diagonal block: only its stored half, which is the lower one for Lower and the upper one for Upper)
-    if (diag && upper) {
-      const T *p = S + (long)c * ga.mbs + r;
-      t0 = (c < vc && r < vr && r <= c) ? p[0] : T(0);
-      t1 = (c < vc && r + 1 < vr && r + 1 <= c) ? p[1] : T(0);
-    } else {
-      load_pair<T>(S, ga.mbs, r, c, vr, vc, diag, t0, t1);
-    }
+    load_pair<T>(b.S, ga.mbs, r, c, vr, vc, b.tri, t0, t1);
     // the row products take the stored half with the diagonal, the column products the strict half
     const T ca0 = (diag && r == c) ? T(0) : t0, ca1 = (diag && r + 1 == c) ? T(0) : t1;
     T ps[NR], pa[NR];
@@ -237,8 +224,8 @@ __global__ __launch_bounds__(256) void k_porfs_resid(TileGeo ga, int upper, cons
   }
 }
 
-// R = B - A X and W = |B| + |A| |X| per stored row, the partials added in a fixed order (the blocks (P, q), q <= P,
-// of block row P, then (k, P), k >= P); R[v nv + s] <- R, F[v nv + s] <- the FERR weight, berr[v] <- max of the
+// R = B - A X and W = |B| + |A| |X| per stored row, the partials added in the fixed order of for_row_partials;
+// R[v nv + s] <- R, F[v nv + s] <- the FERR weight, berr[v] <- max of the
 // componentwise ratio (bits of a non-negative double: order-independent), v = cols.v[j]
 template <typename T, int NR>
 __global__ __launch_bounds__(256) void k_porfs_reduce(TileGeo ga, TileGeo gx, const T *__restrict__ part, VecCols cols,
@@ -257,16 +244,11 @@ __global__ __launch_bounds__(256) void k_porfs_reduce(TileGeo ga, TileGeo gx, co
     return;
   }
   T sum = 0, asum = 0;
-  for (int q = 0; q <= P; ++q) {
-    const T *p = part + ((((long)P * (P + 1) / 2 + q) * 2 + 0) * 2) * NR * CB + j * CB + t;
+  for_row_partials(P, NB, [&](long pair, int kind) {
+    const T *p = part + ((pair * 2 + kind) * 2) * NR * CB + j * CB + t;
     sum += p[0];
     asum += p[NR * CB];
-  }
-  for (int k = P; k < NB; ++k) {
-    const T *p = part + ((((long)k * (k + 1) / 2 + P) * 2 + 1) * 2) * NR * CB + j * CB + t;
-    sum += p[0];
-    asum += p[NR * CB];
-  }
+  });
   const T b = B[desc_index(gx, P, t, cols.d[j])];
   const T rv = b - sum, wv = fabs(b) + asum, ar = fabs(rv);
   const T ratio = wv > safe2 ? ar / wv : (ar + safe1) / (wv + safe1);
@@ -275,178 +257,11 @@ __global__ __launch_bounds__(256) void k_porfs_reduce(TileGeo ga, TileGeo gx, co
   F[vo] = wv > safe2 ? ar + nzeps * wv : ar + nzeps * wv + safe1;
 }
 
-// ---------------------------------------------------------------- the multi-vector sweeps
-// out[j][t] = sum_c S(t, c) v[j][c] (TRANS: sum_r S(r, t) v[j][r]) for the 128 x 128 block S (ld) and NV vectors, 256
-// threads; v and out in LDS, red: LDS scratch.  The transposed form reduces its NV column products at once
-// (wave_sum_n).  For NV = 1 the arithmetic of block_product.
-template <typename T, bool TRANS, int NV>
-__device__ __forceinline__ void block_product_nv(const T *S, int ld, int vr, int vc, bool lower, const T (*v)[CB],
-                                                 T (*out)[CB], T (*red)[NV][CB]) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = 2 * lane;
-  if (!TRANS) {
-    T acc0[NV], acc1[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) acc0[j] = acc1[j] = T(0);
-#pragma unroll 8
-    for (int k = 0; k < 32; ++k) {
-      const int c = w * 32 + k;
-      T a0, a1;
-      load_pair<T>(S, ld, r, c, vr, vc, lower, a0, a1);
-#pragma unroll
-      for (int j = 0; j < NV; ++j) {
-        acc0[j] = fma(a0, v[j][c], acc0[j]);
-        acc1[j] = fma(a1, v[j][c], acc1[j]);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      red[w][j][r] = acc0[j];
-      red[w][j][r + 1] = acc1[j];
-    }
-    __syncthreads();
-    for (int e = tid; e < NV * CB; e += 256) {
-      const int j = e / CB, t = e % CB;
-      out[j][t] = ((red[0][j][t] + red[1][j][t]) + red[2][j][t]) + red[3][j][t];
-    }
-  } else {
-    T u0[NV], u1[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) u0[j] = v[j][r], u1[j] = v[j][r + 1];
-#pragma unroll 4
-    for (int k = 0; k < 32; ++k) {
-      const int c = w * 32 + k;
-      T a0, a1, p[NV];
-      load_pair<T>(S, ld, r, c, vr, vc, lower, a0, a1);
-#pragma unroll
-      for (int j = 0; j < NV; ++j) p[j] = fma(a1, u1[j], a0 * u0[j]);
-      int js;
-      const T s = wave_sum_n<T, NV>(p, lane, &js);
-      if (lane % (64 / NV) == 0) out[js][c] = s;
-    }
-  }
-  __syncthreads();
-}
-
-template <typename T>
-struct Vec8 {
-  T *p[8];
-};
-
-// step k, diagonal part, NV vectors (k_sweep_diag): vector j's pending partials at pg + j pgn, its diag partials at
-// pd + j pdn
-template <typename T, bool FWD, int NV>
-__global__ __launch_bounds__(256) void k_msweep_diag(TileGeo g, const T *__restrict__ Dk, int E, int k, Vec8<T> r,
-                                                     const T *__restrict__ pg, long pgn, T *__restrict__ pd, long pdn) {
-  int P, Q;
-  pair_of(blockIdx.x, P, Q);
-  const int bpt = E / CB;
-  const long kb0 = (long)k * bpt;
-  const int rho = FWD ? P : Q, kap = FWD ? Q : P;
-  __shared__ T sv[NV][CB], so[NV][CB];
-  __shared__ T red[4][NV][CB];
-  for (int e = threadIdx.x; e < NV * CB; e += 256) {
-    const int j = e / CB, t = e % CB;
-    // r - the pending partials of the previous rect launch (condest.hip: pending_sub)
-    T v = r.p[j][(kb0 + kap) * CB + t];
-    if (pg) {
-      T sp = 0;
-      for (int c = 0; c < bpt; ++c) sp += pg[j * pgn + ((kb0 + kap) * bpt + c) * CB + t];
-      v -= sp;
-    }
-    sv[j][t] = v;
-  }
-  __syncthreads();
-  const int vr = block_valid(g, (int)kb0 + P), vc = block_valid(g, (int)kb0 + Q);
-  block_product_nv<T, !FWD, NV>(Dk + (long)P * CB + (long)Q * CB * E, E, vr, vc, P == Q, sv, so, red);
-  for (int e = threadIdx.x; e < NV * CB; e += 256) {
-    const int j = e / CB, t = e % CB;
-    pd[j * pdn + ((long)rho * bpt + kap) * CB + t] = so[j][t];
-  }
-}
-
-// step k, the blocks below (forward) / above (backward) tile k, NV vectors (k_sweep_rect)
-template <typename T, bool FWD, int NV>
-__global__ __launch_bounds__(256) void k_msweep_rect(TileGeo g, int upper, const T *__restrict__ A, int k, int row0,
-                                                     int nrows, Vec8<T> r, const T *__restrict__ pg_prev,
-                                                     T *__restrict__ pg, long pgn, const T *__restrict__ pd, long pdn,
-                                                     Vec8<T> yout) {
-  const int bpt = bpt_of(g), i = blockIdx.x / bpt, kap = blockIdx.x % bpt;
-  const long kb0 = (long)k * bpt, rho = row0 + i;
-  __shared__ T sv[NV][CB], so[NV][CB];
-  __shared__ T red[4][NV][CB];
-  for (int e = threadIdx.x; e < NV * CB; e += 256) {
-    const int j = e / CB, t = e % CB;
-    T y = 0;
-    for (int c = FWD ? 0 : kap; c <= (FWD ? kap : bpt - 1); ++c) y += pd[j * pdn + ((long)kap * bpt + c) * CB + t];
-    sv[j][t] = y;
-    if (i == 0) yout.p[j][(kb0 + kap) * CB + t] = y;
-    if (nrows > 0 && kap == 0 && pg_prev) {
-      T s = 0;
-      for (int c = 0; c < bpt; ++c) s += pg_prev[j * pgn + (rho * bpt + c) * CB + t];
-      r.p[j][rho * CB + t] -= s;
-    }
-  }
-  if (nrows == 0) return;
-  __syncthreads();
-  const int kg = (int)(kb0 + kap);
-  const bool trans = FWD ? upper : !upper;
-  const int sr = trans ? kg : (int)rho, sc = trans ? (int)rho : kg;
-  const T *S = block_at<T>(g, A, sr, sc);
-  const int vr = block_valid(g, sr), vc = block_valid(g, sc);
-  if (trans)
-    block_product_nv<T, true, NV>(S, g.mbs, vr, vc, false, sv, so, red);
-  else
-    block_product_nv<T, false, NV>(S, g.mbs, vr, vc, false, sv, so, red);
-  for (int e = threadIdx.x; e < NV * CB; e += 256) {
-    const int j = e / CB, t = e % CB;
-    pg[j * pgn + (rho * bpt + kap) * CB + t] = so[j][t];
-  }
-}
-
-// which: SWEEP_BOTH x <- A^{-1} x; SWEEP_FORWARD / SWEEP_BACKWARD that half alone, its result left in the y vectors
-// (b.y + j nv) and x used up
-template <typename T, int NV>
-void msweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const T *Dv, const Vec8<T> &x, const MSweepBufs<T> &b,
-            int which) {
-  const int E = condest_edge(g), bpt = E / CB, nt = g.lmt, NB = nt * bpt;
-  const unsigned dwg = (unsigned)(bpt * (bpt + 1) / 2);
-  const long nv = (long)condest_vec_elems(g), pgs = (long)NB * bpt * CB, pgn = 2 * pgs, pdn = (long)bpt * bpt * CB;
-  Vec8<T> y{};
-  for (int j = 0; j < NV; ++j) y.p[j] = b.y + j * nv;
-  const bool half = which != SWEEP_BOTH;
-  for (int pass = which == SWEEP_BACKWARD ? 1 : 0; pass < (which == SWEEP_FORWARD ? 1 : 2); ++pass) {
-    const bool fwd = pass == 0;
-    // forward: b = x -> y; backward: y -> x (r: in place); one half alone: x -> y
-    const Vec8<T> r = fwd || half ? x : y, out = fwd || half ? y : x;
-    const T *pg_prev = nullptr;
-    for (int step = 0; step < nt; ++step) {
-      const int k = fwd ? step : nt - 1 - step;
-      T *pg = b.pg + (step % 2) * pgs;
-      const T *Dk = Dv + (long)k * E * E;
-      if (fwd)
-        hipLaunchKernelGGL((k_msweep_diag<T, true, NV>), dim3(dwg), dim3(256), 0, s, g, Dk, E, k, r, pg_prev, pgn, b.pd,
-                           pdn);
-      else
-        hipLaunchKernelGGL((k_msweep_diag<T, false, NV>), dim3(dwg), dim3(256), 0, s, g, Dk, E, k, r, pg_prev, pgn, b.pd,
-                           pdn);
-      const int row0 = fwd ? (k + 1) * bpt : 0, nrows = fwd ? NB - (k + 1) * bpt : k * bpt;
-      const unsigned rwg = (unsigned)(std::max(nrows, 1) * bpt);
-      if (fwd)
-        hipLaunchKernelGGL((k_msweep_rect<T, true, NV>), dim3(rwg), dim3(256), 0, s, g, upper, A, k, row0, nrows, r,
-                           pg_prev, pg, pgn, b.pd, pdn, out);
-      else
-        hipLaunchKernelGGL((k_msweep_rect<T, false, NV>), dim3(rwg), dim3(256), 0, s, g, upper, A, k, row0, nrows, r,
-                           pg_prev, pg, pgn, b.pd, pdn, out);
-      pg_prev = pg;
-    }
-  }
-}
-
 template <typename T, int NR>
 void porfs_pass(hipStream_t s, const TileGeo &ga, int upper, const T *A, const TileGeo &gx, const T *X, const T *B,
                 const VecCols &cols, T *part, T *R, T *F, double eps, double safe1, double safe2,
                 unsigned long long *berr) {
-  const long NB = (long)condest_edge(ga) / CB * ga.lmt, pairs = NB * (NB + 1) / 2;
+  const long NB = block_rows(ga), pairs = tri_pairs(ga);
   const long nv = (long)condest_vec_elems(ga);
   if (!pairs) return;
   hipLaunchKernelGGL((k_porfs_resid<T, NR>), dim3((unsigned)pairs), dim3(256), 0, s, ga, upper, A, gx, X, cols, part);
@@ -462,10 +277,7 @@ unsigned grid_over(long total) { return (unsigned)std::max(1L, std::min((total +
 // ---------------------------------------------------------------- launchers
 int refine_width(int k) { return k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 ? 4 : 8; }
 
-size_t porfs_part_elems(const TileGeo &ga, int width) {
-  const long NB = (long)ga.lmt * (condest_edge(ga) / CB);
-  return (size_t)(NB * (NB + 1) / 2) * 4 * CB * width;
-}
+size_t porfs_part_elems(const TileGeo &ga, int width) { return (size_t)tri_pairs(ga) * 4 * CB * width; }
 
 size_t diag_scan_part_bytes() { return (size_t)SCAN_WG * 3 * sizeof(double); }
 
@@ -511,32 +323,9 @@ template <typename T>
 void launch_porfs_resid(hipStream_t s, const TileGeo &ga, int upper, const T *A, const TileGeo &gx, const T *X,
                         const T *B, const VecCols &cols, T *part, T *R, T *F, double eps, double safe1, double safe2,
                         unsigned long long *berr) {
-  switch (refine_width(cols.n)) {
-    case 1: porfs_pass<T, 1>(s, ga, upper, A, gx, X, B, cols, part, R, F, eps, safe1, safe2, berr); break;
-    case 2: porfs_pass<T, 2>(s, ga, upper, A, gx, X, B, cols, part, R, F, eps, safe1, safe2, berr); break;
-    case 4: porfs_pass<T, 4>(s, ga, upper, A, gx, X, B, cols, part, R, F, eps, safe1, safe2, berr); break;
-    default: porfs_pass<T, 8>(s, ga, upper, A, gx, X, B, cols, part, R, F, eps, safe1, safe2, berr); break;
-  }
-}
-
-size_t msweep_scratch_elems(const TileGeo &g) {
-  const long bpt = (condest_edge(g) / CB), NB = (long)g.lmt * bpt, nv = (long)condest_vec_elems(g);
-  return (size_t)8 * (nv + 2 * NB * bpt * CB + bpt * bpt * CB);
-}
-
-template <typename T>
-void launch_msweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const T *Dv, T *const *x, int count,
-                   T *pad, const MSweepBufs<T> &b, int which) {
-  const long nv = (long)condest_vec_elems(g);
-  Vec8<T> v{};
-  const int w = refine_width(count);
-  for (int j = 0; j < w; ++j) v.p[j] = j < count ? x[j] : pad + (long)(j - count) * nv;  // (padding: results unused)
-  switch (w) {
-    case 1: msweep<T, 1>(s, g, upper, A, Dv, v, b, which); break;
-    case 2: msweep<T, 2>(s, g, upper, A, Dv, v, b, which); break;
-    case 4: msweep<T, 4>(s, g, upper, A, Dv, v, b, which); break;
-    default: msweep<T, 8>(s, g, upper, A, Dv, v, b, which); break;
-  }
+  with_width(cols.n, [&](auto w) {
+    porfs_pass<T, decltype(w)::value>(s, ga, upper, A, gx, X, B, cols, part, R, F, eps, safe1, safe2, berr);
+  });
 }
 
 #define INSTANTIATE_REFINE(T)                                                                                        \
@@ -548,9 +337,7 @@ void launch_msweep(hipStream_t s, const TileGeo &g, int upper, const T *A, const
   template void launch_vec_weight<T>(hipStream_t, const TileGeo &, T *, const T *, const VecCols &, unsigned);       \
   template void launch_porfs_resid<T>(hipStream_t, const TileGeo &, int, const T *, const TileGeo &, const T *,      \
                                       const T *, const VecCols &, T *, T *, T *, double, double, double,            \
-                                      unsigned long long *);                                                         \
-  template void launch_msweep<T>(hipStream_t, const TileGeo &, int, const T *, const T *, T *const *, int, T *,      \
-                                 const MSweepBufs<T> &, int);
+                                      unsigned long long *);
 INSTANTIATE_REFINE(double)
 INSTANTIATE_REFINE(float)
 

@@ -1663,7 +1663,7 @@ int sysv_rbt_impl(int uplo, chol_desc *A, chol_desc *AF, chol_desc *W, int depth
 // ---------------------------------------------------------------- one half of the factor alone (LAPACK DTRTRS, BLAS DTRMM, log det)
 // trtrs: B <- inv(op(T)) B, T the `uplo` triangle.  (Lower, NoTrans) and (Upper, Trans) are potrs's forward half,
 // L Y = B; the other two its backward half, L^T X = Y.  Up to TRTRS_KX columns run as one pass of the multi-vector
-// sweeps (refine.hip) in groups of 8 on the gathered columns, the diagonal tiles staged and inverted once per call;
+// sweeps (condest.hip) in groups of 8 on the gathered columns, the diagonal tiles staged and inverted once per call;
 // more columns run as one sweep of potrs_impl's on Z = B^T (Upper between two transposes of the storage, as potrs).
 // trmm: B <- alpha op(T) B.  Up to TRMM_KX columns in groups of 8 by trmm.hip's block products; more columns as
 // products of whole tiles on Z = B^T (ZSweeps::product), with the diagonal tiles staged as clean triangles.

@@ -19,6 +19,8 @@ namespace cholmi {
 
 namespace {
 
+// (The block product is block_product_nv of sweep_blocks.h with nontemporal loads, spelled out here: through the shared
+// body three instantiations were allocated 8 VGPRs more, one wave per SIMD less.)
 // part[(pair NV + j) 128 + t] <- row / column t of the product of stored block `pair` with vector j (x + j nv).
 // TRANS: the block's transpose times the vector's entries of the block's rows; else the block times those of its columns
 template <typename T, bool TRANS, int NV>
@@ -108,7 +110,7 @@ __global__ __launch_bounds__(256) void k_trmm_reduce(TileGeo ga, TileGeo gx, con
 template <typename T, int NV>
 void trmm_pass(hipStream_t s, const TileGeo &ga, int upper, int trans, const T *A, const TileGeo &gx, T *B,
                const VecCols &cols, T alpha, const T *x, T *part) {
-  const long NB = (long)condest_edge(ga) / CB * ga.lmt, pairs = NB * (NB + 1) / 2, nv = (long)condest_vec_elems(ga);
+  const long NB = block_rows(ga), pairs = tri_pairs(ga), nv = (long)condest_vec_elems(ga);
   if (!pairs) return;
   if (trans)
     hipLaunchKernelGGL((k_trmm_block<T, true, NV>), dim3((unsigned)pairs), dim3(256), 0, s, ga, upper, A, x, nv, part);
@@ -193,22 +195,14 @@ __global__ void k_logdet_sum(const double *__restrict__ part, double *__restrict
 }  // namespace
 
 // ---------------------------------------------------------------- launchers
-size_t trmm_part_elems(const TileGeo &ga, int width) {
-  const long NB = (long)ga.lmt * (condest_edge(ga) / CB);
-  return (size_t)(NB * (NB + 1) / 2) * CB * width;
-}
+size_t trmm_part_elems(const TileGeo &ga, int width) { return (size_t)tri_pairs(ga) * CB * width; }
 
 template <typename T>
 void launch_trmm_narrow(hipStream_t s, const TileGeo &ga, int upper, int trans, const T *A, const TileGeo &gx, T *B,
                         const VecCols &cols, T alpha, T *x, T *part) {
   if (cols.n <= 0) return;
   launch_gather<T>(s, gx, B, cols, x);
-  switch (refine_width(cols.n)) {
-    case 1: trmm_pass<T, 1>(s, ga, upper, trans, A, gx, B, cols, alpha, x, part); break;
-    case 2: trmm_pass<T, 2>(s, ga, upper, trans, A, gx, B, cols, alpha, x, part); break;
-    case 4: trmm_pass<T, 4>(s, ga, upper, trans, A, gx, B, cols, alpha, x, part); break;
-    default: trmm_pass<T, 8>(s, ga, upper, trans, A, gx, B, cols, alpha, x, part); break;
-  }
+  with_width(cols.n, [&](auto w) { trmm_pass<T, decltype(w)::value>(s, ga, upper, trans, A, gx, B, cols, alpha, x, part); });
 }
 
 template <typename T>

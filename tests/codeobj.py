@@ -19,26 +19,37 @@ def _sections(elf: bytes):
     return raw
 
 
-def device_elf(so_path: str, arch: str = "gfx950") -> bytes:
+def device_elfs(so_path: str, arch: str = "gfx950"):
+    """Every code object for `arch` in the library, in link order (one per translation unit with device code)."""
     host = open(so_path, "rb").read()
     fat = next(s for s in _sections(host) if s["name"] == ".hip_fatbin")
     blob = host[fat["off"]:fat["off"] + fat["size"]]
     magic = b"__CLANG_OFFLOAD_BUNDLE__"
     assert blob.startswith(magic)
-    n, = struct.unpack_from("<Q", blob, len(magic))
-    p = len(magic) + 8
-    for _ in range(n):
-        off, size, tlen = struct.unpack_from("<QQQ", blob, p)
-        triple = blob[p + 24:p + 24 + tlen].decode()
-        p += 24 + tlen
-        if arch in triple:
-            return blob[off:off + size]
+    at = 0
+    while at >= 0:  # the bundles lie one after another, each aligned; its offsets count from its own start
+        n, = struct.unpack_from("<Q", blob, at + len(magic))
+        p = at + len(magic) + 8
+        for _ in range(n):
+            off, size, tlen = struct.unpack_from("<QQQ", blob, p)
+            triple = blob[p + 24:p + 24 + tlen].decode()
+            p += 24 + tlen
+            if arch in triple:
+                yield blob[at + off:at + off + size]
+        at = blob.find(magic, at + len(magic))
+
+
+def device_elf(so_path: str, arch: str = "gfx950") -> bytes:
+    """The first of them: kernels.hip's."""
+    for elf in device_elfs(so_path, arch):
+        return elf
     raise KeyError(arch)
 
 
-def kernel_resources(so_path: str) -> dict:
-    """{mangled kernel name: {"vgprs": allocated VGPRs per lane (arch+acc), "lds": bytes, "scratch": bytes per lane}}"""
-    elf = device_elf(so_path)
+def kernel_resources(so_path: str, elf: bytes = None) -> dict:
+    """{mangled kernel name: {"vgprs": allocated VGPRs per lane (arch+acc), "lds": bytes, "scratch": bytes per lane}}
+    of the code object `elf` (default: the library's first)"""
+    elf = elf or device_elf(so_path)
     secs = _sections(elf)
     out = {}
     for symtab in (s for s in secs if s["type"] in (2, 11)):  # SYMTAB, DYNSYM
@@ -57,8 +68,9 @@ def kernel_resources(so_path: str) -> dict:
     return out
 
 
-def disassemble(so_path: str, arch: str = "gfx950") -> dict:
-    """{mangled kernel name: [instruction text, ...]} from llvm-objdump of the embedded code object."""
+def disassemble(so_path: str, arch: str = "gfx950", elf: bytes = None) -> dict:
+    """{mangled kernel name: [instruction text, ...]} from llvm-objdump of the embedded code object `elf` (default: the
+    library's first)."""
     import os
     import re
     import subprocess
@@ -66,7 +78,7 @@ def disassemble(so_path: str, arch: str = "gfx950") -> dict:
 
     objdump = "/opt/rocm/lib/llvm/bin/llvm-objdump"
     with tempfile.NamedTemporaryFile(suffix=".co", delete=False) as f:
-        f.write(device_elf(so_path, arch))
+        f.write(elf or device_elf(so_path, arch))
         path = f.name
     try:
         text = subprocess.run([objdump, "-d", f"--mcpu={arch}", "--no-show-raw-insn", path], check=True, capture_output=True, text=True).stdout
