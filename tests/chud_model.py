@@ -7,7 +7,11 @@ the library's arithmetic.  Columns outer, vectors inner; column j, vector t, sig
 
 vectorised over the rows i.  Every operation is rounded to `dtype`.  The device forms each `a + b c` with one fused
 multiply-add; `fused=True` imitates that for float32 (the product and the sum in float64, rounded once), which is how
-the tests measure what the contraction can change."""
+the tests measure what the contraction can change.
+
+problem: the inputs that test_chud_host.py and test_gpu_chud.py share."""
+import functools
+
 import numpy as np
 
 
@@ -40,3 +44,13 @@ def chud_model(L, V, sigma, dtype=np.float64, fused=False):
             col[:] = muladd(sg * s, v, col) * ci
             v[:] = muladd(-s, col, c * v)
     return 0, L, -1
+
+
+@functools.lru_cache(maxsize=None)
+def problem(n, r, seed):
+    """A, V, the factor of A, the factor of A + V V^T"""
+    g = np.random.default_rng(seed)
+    G = g.standard_normal((n, 2 * n))
+    A = G @ G.T
+    V = g.standard_normal((n, r)) * np.sqrt(n)
+    return A, V, np.linalg.cholesky(A), np.linalg.cholesky(A + V @ V.T)

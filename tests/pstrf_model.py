@@ -67,3 +67,9 @@ def pstrf_model(A, B, tol=-1.0, exclude_padding=True):
     rank = stop if stop is not None else min(n, real)
     L = np.tril(M)[:n, :n]
     return piv[:n] + 1, rank, int(rank < n), L
+
+
+def gram(n, r, seed, dtype=np.float64):
+    """G G^T, G n x r standard normal: rank min(n, r); what test_pstrf_host.py and test_gpu_pstrf.py factor"""
+    G = np.random.default_rng(seed).standard_normal((n, r))
+    return np.asfortranarray((G @ G.T).astype(dtype))

@@ -20,10 +20,6 @@ SCALARS = ((1.0, 0.0), (-2.0, 1.0), (0.5, -1.0))
 RANDOM_SCALARS = (-1.5, 0.75)
 
 
-def npdt(dt):
-    return np.float64 if dt == "d" else np.float32
-
-
 def _frozen(*arrays):
     for a in arrays:
         a.setflags(write=False)
@@ -48,14 +44,6 @@ def random_problem(n):
     G = r.standard_normal((n, n))
     A = np.tril(G) + np.tril(G, -1).T
     return _frozen(A, r.standard_normal((n, max(NRHS))), r.standard_normal((n, max(NRHS))))
-
-
-def stored(A, u, fill=np.nan):
-    """the symmetric A as chol_symm_tile reads it: its `u` triangle, the other strict triangle = fill (Fortran order)"""
-    n = A.shape[0]
-    S = np.array(A, order="F")
-    S[np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)] = fill
-    return S
 
 
 def symm(S, u, alpha, B, beta, C):

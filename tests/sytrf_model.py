@@ -93,3 +93,19 @@ def growth_scale(F):
 def inertia(F):
     d = np.diag(F)
     return int((d > 0).sum()), int((d < 0).sum())
+
+
+def quasi_definite(n, m, seed, perm=False):
+    """[[H, J^T], [J, -C]], H = G G^T / 2n with G n x 2n standard normal, C likewise of order m, J = randn / sqrt(n):
+    what test_sytrf_host.py and test_gpu_sytrf.py factor (a fresh array per call)"""
+    r = np.random.default_rng(seed)
+    G = r.standard_normal((n, 2 * n))
+    H = G @ G.T / (2 * n)
+    G = r.standard_normal((m, 2 * m))
+    C = G @ G.T / (2 * m)
+    J = r.standard_normal((m, n)) / np.sqrt(n)
+    K = np.block([[H, J.T], [J, -C]])
+    if perm:
+        p = r.permutation(n + m)
+        K = K[np.ix_(p, p)]
+    return K

@@ -12,13 +12,12 @@ Measured with this model on this file's inputs, (n, r) = (600, 1), (600, 5), (10
     downdate  fp64 <= 140 eps    fp32 <= 56 eps
 
 The bounds below are about 10 x that."""
-import functools
-
 import numpy as np
 import pytest
 
-from dense_linear_app_amd import _lib, chameleon as ch
-from chud_model import chud_model
+from dense_linear_app_amd import chameleon as ch
+from chol_testkit import assert_before_init_refused, assert_symbols_exported
+from chud_model import chud_model, problem
 
 SYMBOLS = ["chol_chud_tile", "chol_chdd_tile", "chol_last_chud_stats"]
 # [update, downdate] in eps
@@ -31,27 +30,12 @@ def test_wrappers_exist():
         assert callable(getattr(ch, f"CHAMELEON_{p}chud_Tile"))
         assert callable(getattr(ch, f"CHAMELEON_{p}chdd_Tile"))
     assert callable(ch.last_chud_stats)
-    for s in SYMBOLS:
-        assert s in _lib.abi_symbols()
-        assert hasattr(_lib.lib(), s)
+    assert_symbols_exported(SYMBOLS)
 
 
 @pytest.mark.parametrize("sym", SYMBOLS)
 def test_before_init_is_refused(sym):
-    L = _lib.lib()
-    args = (None,) if sym == "chol_last_chud_stats" else (ch.ChamLower, None, None)
-    assert getattr(L, sym)(*args) == -101  # CHOL_ERR_NOT_INITIALIZED
-    assert b"before chol_init" in L.chol_last_error()
-
-
-@functools.lru_cache(maxsize=None)
-def problem(n, r, seed):
-    """A, V, the factor of A, the factor of A + V V^T"""
-    g = np.random.default_rng(seed)
-    G = g.standard_normal((n, 2 * n))
-    A = G @ G.T
-    V = g.standard_normal((n, r)) * np.sqrt(n)
-    return A, V, np.linalg.cholesky(A), np.linalg.cholesky(A + V @ V.T)
+    assert_before_init_refused(sym, (None,) if sym == "chol_last_chud_stats" else (ch.ChamLower, None, None))
 
 
 def err_eps(L, ref, dt):

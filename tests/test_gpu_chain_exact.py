@@ -25,6 +25,7 @@ import numpy as np
 import pytest
 
 import dyadic_model as dm
+from chol_testkit import bits, chdt, desc, npdt, stored_lower
 
 pytestmark = pytest.mark.gpu
 
@@ -38,14 +39,6 @@ FILL_CASES = [(fam, B) for fam in ("parity", "panel") for B in (256, 512)]
 NEW_FAMILIES = ("mirror", "mod3", "panel")
 PIPE_ALL = {"CHOLMI_PIPE_FACTOR": "100", "CHOLMI_PAIR_FACTOR": "1000"}
 FLOW_ALL = {"CHOLMI_FLOW_FACTOR": "100", "CHOLMI_PIPE_FACTOR": "100", "CHOLMI_PAIR_FACTOR": "1000"}
-
-
-def npdt(dt):
-    return np.float64 if dt == "d" else np.float32
-
-
-def chdt(ch, dt):
-    return ch.ChamRealDouble if dt == "d" else ch.ChamRealFloat
 
 
 def member(fam, N, B):
@@ -64,15 +57,9 @@ def with_families(shapes, one=lambda s: s):
     return flat, ["-".join(str(x) for x in (f[1:] if f[0] == "parity" else f)) for f in flat]
 
 
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
-
-
-def stored_lower(A, dt, fill=np.nan):
+def lower_as(A, dt, fill=np.nan):
     """the lower triangle of A in dtype dt, the strict upper triangle = fill"""
-    n = A.shape[0]
-    return np.asfortranarray(np.where(np.tri(n, dtype=bool), A, fill).astype(npdt(dt)))
+    return stored_lower(A.astype(npdt(dt)), "L", fill)
 
 
 def mismatches(got, want, B):
@@ -83,9 +70,9 @@ def mismatches(got, want, B):
 
 
 def factor_case(ch, fam, N, B, dt, S, L):
-    """one whole-matrix factorisation of S (the Cholesky member as stored_lower leaves it) -> the record the child
+    """one whole-matrix factorisation of S (the Cholesky member as lower_as leaves it) -> the record the child
     prints"""
-    d = ch.CHAMELEON_Desc_Create(None, chdt(ch, dt), B, B, B * B, N, N, 0, 0, N, N, 1, 1)
+    d = desc(ch, N, B, dt)
     d.from_lapack(S)
     info = ch.CHAMELEON_dpotrf_Tile(ch.ChamLower, d)
     F = d.to_lapack()
@@ -97,10 +84,10 @@ def factor_case(ch, fam, N, B, dt, S, L):
 
 
 def chain_inputs(fam, N, B):
-    """-> (S, L) in fp32: A as stored_lower leaves it and the factor (integers far below 2^24: the fp32 image holds them
+    """-> (S, L) in fp32: A as lower_as leaves it and the factor (integers far below 2^24: the fp32 image holds them
     exactly, and the fp64 inputs are its widening)"""
     A, L, _ = member(fam, N, B)
-    return stored_lower(A, "s"), L.astype(np.float32)
+    return lower_as(A, "s"), L.astype(np.float32)
 
 
 _inputs_file = None
@@ -141,7 +128,7 @@ def child_main(inputs=None):
     held = np.load(inputs) if inputs else None
     for fam, N, B in CASES:
         if held is not None:
-            S, Ls = stored_lower(held[f"A_{fam}_{N}_{B}"], "s"), held[f"L_{fam}_{N}_{B}"].astype(np.float32)
+            S, Ls = lower_as(held[f"A_{fam}_{N}_{B}"], "s"), held[f"L_{fam}_{N}_{B}"].astype(np.float32)
         else:
             S, Ls = chain_inputs(fam, N, B)
         for dt in ("d", "s"):
@@ -274,7 +261,7 @@ def test_intile_update_leaves_a_finite_upper_triangle_alone(fused):
 # ---- in-process ---------------------------------------------------------------------------------------------------------
 def potrf_tile(ch, A, dt, fill=np.nan):
     """single-tile POTRF on a host buffer -> (info, the tile afterwards, the tile as stored)"""
-    S = stored_lower(A, dt, fill)
+    S = lower_as(A, dt, fill)
     T = S.copy(order="F")
     B = A.shape[0]
     d = ch.CHAMELEON_Desc_Create(T, chdt(ch, dt), B, B, B * B, B, B, 0, 0, B, B, 1, 1)
@@ -311,8 +298,8 @@ WAVE = with_families([(1024, 256), (1536, 512)], lambda s: s[1])
 def test_potrf_upper_is_exact(cham, fam, N, B, dt):
     ch = cham
     A, L, _ = member(fam, N, B)
-    S = np.array(stored_lower(A, dt).T, order="F")
-    d = ch.CHAMELEON_Desc_Create(None, chdt(ch, dt), B, B, B * B, N, N, 0, 0, N, N, 1, 1)
+    S = np.array(lower_as(A, dt).T, order="F")
+    d = desc(ch, N, B, dt)
     d.from_lapack(S)
     assert ch.CHAMELEON_dpotrf_Tile(ch.ChamUpper, d) == 0
     F = d.to_lapack()
@@ -337,7 +324,7 @@ def test_single_tile_potrf_and_trsm_are_exact(cham, fam, B, dt):
     X = dm.solution(B, B, B)
     P = X @ L.T
     assert np.abs(P).max() * 16 < 2.0 ** 24
-    Lt = np.array(stored_lower(L, dt), order="F")  # (TRSM reads the lower triangle only)
+    Lt = np.array(lower_as(L, dt), order="F")  # (TRSM reads the lower triangle only)
     dl = ch.CHAMELEON_Desc_Create(Lt, chdt(ch, dt), B, B, B * B, B, B, 0, 0, B, B, 1, 1)
     for alpha in (1.0, -2.0, 0.5):
         Pt = np.array(P, dtype=npdt(dt), order="F")

@@ -20,7 +20,9 @@ import functools
 import numpy as np
 import pytest
 
-from chud_model import chud_model
+from chol_testkit import (UserView, bits, desc, image_matrix, npdt, other_triangle_kept, pxq_refused,
+                          ragged_padding_mask, stored_lower, uplo_code)
+from chud_model import chud_model, problem
 
 pytestmark = pytest.mark.gpu
 
@@ -28,29 +30,6 @@ LAPACK_BOUND = {"d": (360.0, 1400.0), "s": (31.0, 560.0)}  # [update, downdate],
 MODEL_BOUND = (30.0, 1130.0)
 SHAPES = [(1000, 128, 1), (1100, 192, 5), (1536, 256, 16), (2100, 512, 3), (300, 512, 2), (192, 192, 1), (600, 128, 40)]
 GROUP = 16  # vectors per pass
-
-
-def npdt(dt):
-    return np.float64 if dt == "d" else np.float32
-
-
-def chdt(ch, dt):
-    return ch.ChamRealDouble if dt == "d" else ch.ChamRealFloat
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
-
-
-@functools.lru_cache(maxsize=None)
-def problem(n, r, seed):
-    """A, V, the factor of A, the factor of A + V V^T"""
-    g = np.random.default_rng(seed)
-    G = g.standard_normal((n, 2 * n))
-    A = G @ G.T
-    V = g.standard_normal((n, r)) * np.sqrt(n)
-    return A, V, np.linalg.cholesky(A), np.linalg.cholesky(A + V @ V.T)
 
 
 @functools.lru_cache(maxsize=None)
@@ -68,43 +47,19 @@ def err_eps(L, ref, dt):
     return np.abs(L.astype(np.float64) - ref.astype(np.float64)).max() / np.abs(ref).max() / np.finfo(npdt(dt)).eps
 
 
-def stored(M, u, fill=np.nan):
-    """the Lower factor M stored in the `u` triangle, the other strict one = fill"""
-    n = M.shape[0]
-    S = np.array(np.tril(M) if u == "L" else np.tril(M).T, order="F")
-    idx = np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
-    S[idx] = fill
-    return S
-
-
-def desc(ch, n, B, dt, r=None):
-    r = n if r is None else r
-    return ch.CHAMELEON_Desc_Create(None, chdt(ch, dt), B, B, B * B, n, r, 0, 0, n, r, 1, 1)
-
-
-def uplo(ch, u):
-    return ch.ChamLower if u == "L" else ch.ChamUpper
-
-
 def run(ch, sigma, L, V, B, u="L", dt="d"):
     """-> (info, the result as Lower, A after the call, A as stored, V after the call)"""
     n, r = V.shape
-    S = stored(L.astype(npdt(dt)), u)
+    S = stored_lower(L.astype(npdt(dt)), u)
     da, dv = desc(ch, n, B, dt), desc(ch, n, B, dt, r)
     da.from_lapack(S)
     dv.from_lapack(V.astype(npdt(dt)))
     fn = ch.CHAMELEON_dchud_Tile if sigma > 0 else ch.CHAMELEON_dchdd_Tile
-    info = fn(uplo(ch, u), da, dv)
+    info = fn(uplo_code(ch, u), da, dv)
     F, W = da.to_lapack(), dv.to_lapack()
     ch.CHAMELEON_Desc_Destroy(da)
     ch.CHAMELEON_Desc_Destroy(dv)
     return info, (np.tril(F) if u == "L" else np.triu(F).T), F, S, W
-
-
-def other_triangle_kept(F, S, u):
-    n = S.shape[0]
-    idx = np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
-    return np.array_equal(bits(F[idx]), bits(S[idx]))
 
 
 @pytest.mark.parametrize("n,B,r", SHAPES)
@@ -140,42 +95,24 @@ def test_tile_size_independence(cham, dt):
     assert err_eps(outs[0], Lm, dt) <= MODEL_BOUND[0]
 
 
-def raw_image(d):
-    """the descriptor's stored fp64 tile image, padding included (through the HIP runtime this process has loaded)"""
-    import ctypes
-
-    ptr, nbytes = d.local_ptr()
-    path = next(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln)
-    hip = ctypes.CDLL(path)
-    out = np.empty(nbytes // 8, dtype=np.float64)
-    assert hip.hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), ctypes.c_size_t(nbytes), 2) == 0
-    return out
-
-
 @pytest.mark.parametrize("sigma", [1, -1])
 def test_repeatable_and_padding(cham, sigma):
     """two calls on fresh descriptors give the same bits; a ragged order keeps the padding of A's image (the identity
     on the diagonal, zeros elsewhere) bit for bit"""
     ch = cham
     n, B, nt, r = 1000, 256, 4, 5
-    k = n - (nt - 1) * B  # rows / columns k .. B-1 of the last tile row / column are padding
-    pad = np.zeros((nt * B, nt * B), dtype=bool)
-    pad[(nt - 1) * B + k:, :] = pad[:, (nt - 1) * B + k:] = True
+    pad = ragged_padding_mask(n, B, nt)
     start, V, _, _ = case(n, r, 5, sigma, "d")
     fn = ch.CHAMELEON_dchud_Tile if sigma > 0 else ch.CHAMELEON_dchdd_Tile
     outs = []
-
-    def image(d):  # as one (nt B) x (nt B) matrix
-        return raw_image(d)[: nt * nt * B * B].reshape(nt, nt, B, B).transpose(1, 3, 0, 2).reshape(nt * B, nt * B)
-
     for _ in range(2):
         da, dv = desc(ch, n, B, "d"), desc(ch, n, B, "d", r)
-        da.from_lapack(stored(start, "L", 0.0))
+        da.from_lapack(stored_lower(start, "L", 0.0))
         dv.from_lapack(V)
-        before = image(da)
+        before = image_matrix(da, nt, B, np.float64)
         assert fn(ch.ChamLower, da, dv) == 0
         outs.append(da.to_lapack())
-        after = image(da)
+        after = image_matrix(da, nt, B, np.float64)
         ch.CHAMELEON_Desc_Destroy(da)
         ch.CHAMELEON_Desc_Destroy(dv)
         assert np.array_equal(bits(after[pad]), bits(before[pad]))
@@ -190,7 +127,7 @@ def test_round_trip(cham, dt):
     n, B, r = 1100, 256, 4
     _, V, L0, _ = problem(n, r, 9)
     da, dv = desc(ch, n, B, dt), desc(ch, n, B, dt, r)
-    da.from_lapack(stored(L0.astype(npdt(dt)), "L", 0.0))
+    da.from_lapack(stored_lower(L0.astype(npdt(dt)), "L", 0.0))
     dv.from_lapack(V.astype(npdt(dt)))
     assert ch.CHAMELEON_dchud_Tile(ch.ChamLower, da, dv) == 0
     dv.from_lapack(V.astype(npdt(dt)))  # (V is workspace)
@@ -206,16 +143,12 @@ def test_round_trip(cham, dt):
 def test_sub_matrix_view(cham):
     """a tile-aligned view of a device user buffer gives the whole-matrix descriptor's result bit for bit; the user's
     tiles outside the view stay as they were"""
-    import torch
-
     ch = cham
-    mb, lt, oi, oj, vt, r = 256, 5, 1, 2, 3, 3
-    lm, m = lt * mb, vt * mb
-    user = np.random.default_rng(16).standard_normal(lt * lt * mb * mb)
-    buf = torch.from_numpy(user.copy()).cuda()
+    uv, r = UserView(ch), 3
+    mb, m = uv.mb, uv.m
     start, V, _, _ = case(m, r, 6, 1, "d")
-    v = ch.CHAMELEON_Desc_Create(buf, ch.ChamRealDouble, mb, mb, mb * mb, lm, lm, oi * mb, oj * mb, m, m, 1, 1)
-    v.from_lapack(stored(start, "L"))
+    v = uv.view_desc()
+    v.from_lapack(stored_lower(start, "L"))
     dv = desc(ch, m, mb, "d", r)
     dv.from_lapack(V)
     assert ch.CHAMELEON_dchud_Tile(ch.ChamLower, v, dv) == 0
@@ -224,12 +157,7 @@ def test_sub_matrix_view(cham):
     ch.CHAMELEON_Desc_Destroy(dv)
     _, L, *_ = run(ch, 1, start, V, mb)
     assert np.array_equal(bits(Lv), bits(L))
-    now = buf.cpu().numpy().reshape(lt * lt, mb * mb)
-    before = user.reshape(lt * lt, mb * mb)
-    for J in range(lt):
-        for I in range(lt):
-            if not (oi <= I < oi + vt and oj <= J < oj + vt):
-                assert np.array_equal(now[I + J * lt], before[I + J * lt]), (I, J)
+    uv.outside_unchanged()
 
 
 # potrs's usual normwise residual (test_gpu_full.py) plus the backward error the update itself may add (LAPACK_BOUND)
@@ -374,19 +302,6 @@ def test_argument_errors(cham):
 
 
 def test_pxq_descriptor_is_not_supported(cham):
-    from dense_linear_app_amd._lib import lib
-
     ch = cham
-    lib().chol_set_transport(None)
-    ch.set_rank(0, 2)
-    try:
-        da = ch.CHAMELEON_Desc_Create(None, ch.ChamRealDouble, 256, 256, 256 * 256, 1024, 1024, 0, 0, 1024, 1024, 1, 2)
-        dv = ch.CHAMELEON_Desc_Create(None, ch.ChamRealDouble, 256, 256, 256 * 256, 1024, 1024, 0, 0, 1024, 1024, 1, 2)
-        for fn in (ch.CHAMELEON_dchud_Tile, ch.CHAMELEON_dchdd_Tile):
-            with pytest.raises(ch.CholmiError) as e:
-                fn(ch.ChamLower, da, dv)
-            assert e.value.code == -104  # CHOL_ERR_NOT_SUPPORTED
-        ch.CHAMELEON_Desc_Destroy(da)
-        ch.CHAMELEON_Desc_Destroy(dv)
-    finally:
-        ch.set_rank(0, 1)
+    pxq_refused(ch, 2, lambda da, dv: ch.CHAMELEON_dchud_Tile(ch.ChamLower, da, dv),
+                lambda da, dv: ch.CHAMELEON_dchdd_Tile(ch.ChamLower, da, dv))

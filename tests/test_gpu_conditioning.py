@@ -20,6 +20,8 @@ that buys, as a function of kappa (DESIGN.md section 6 carries the same table):
 import numpy as np
 import pytest
 
+from chol_testkit import spd_spectral  # (scripts/cond_table.py takes it from here too)
+
 pytestmark = pytest.mark.gpu
 EPS = np.finfo(np.float64).eps
 
@@ -27,15 +29,6 @@ EPS = np.finfo(np.float64).eps
 def desc1(ch, a):
     B = a.shape[0]
     return ch.CHAMELEON_Desc_Create(a, ch.ChamRealDouble, B, B, B * B, B, B, 0, 0, B, B, 1, 1)
-
-
-def spd_spectral(n, kappa, seed):
-    """Q diag(logspace(0, -log10 kappa)) Q^T: kappa_2 = kappa exactly (up to rounding)."""
-    rng = np.random.default_rng(seed)
-    Q, _ = np.linalg.qr(rng.standard_normal((n, n)))
-    lam = np.logspace(0.0, -np.log10(kappa), n)
-    A = (Q * lam) @ Q.T
-    return np.asfortranarray((A + A.T) * 0.5)
 
 
 def spd_graded(n, decades, seed):

@@ -7,20 +7,13 @@ import functools
 import numpy as np
 import pytest
 
+from chol_testkit import bits, desc, other, spd_spectral, uplo_code
+
 pytestmark = pytest.mark.gpu
 
 EPS = 2.0 ** -53
 SHAPES = [(1024, 256, 1), (1000, 192, 7), (2048, 128, 128), (1536, 512, 1024), (16384, 512, 16)]
 CASES = [(N, B, r, u) for N, B, r in SHAPES for u in "LU" if u == "L" or N % B == 0]  # Upper as the potrs test
-
-
-def spd_spectral(n, kappa, seed):
-    """Q diag(logspace(0, -log10 kappa)) Q^T: kappa_2 = kappa exactly (up to rounding)  (as test_gpu_conditioning.py)."""
-    rng = np.random.default_rng(seed)
-    Q, _ = np.linalg.qr(rng.standard_normal((n, n)))
-    lam = np.logspace(0.0, -np.log10(kappa), n)
-    A = (Q * lam) @ Q.T
-    return np.asfortranarray((A + A.T) * 0.5)
 
 
 @functools.lru_cache(maxsize=2)
@@ -32,22 +25,10 @@ def plgsy_problem(N, nrhs):
     return A, Bm, np.linalg.solve(A, Bm)
 
 
-def desc(ch, N, B, ncols, dtype=None):
-    return ch.CHAMELEON_Desc_Create(None, dtype or ch.ChamRealDouble, B, B, B * B, N, ncols, 0, 0, N, ncols, 1, 1)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64)
-
-
-def uplo_of(ch, u):
-    return ch.ChamLower if u == "L" else ch.ChamUpper
-
-
 def solve(ch, A, Bm, B, uplo):
     """-> (info, iter, X, A after, B after)"""
     N, nrhs = Bm.shape
-    dA, dB, dX = desc(ch, N, B, N), desc(ch, N, B, nrhs), desc(ch, N, B, nrhs)
+    dA, dB, dX = desc(ch, N, B), desc(ch, N, B, cols=nrhs), desc(ch, N, B, cols=nrhs)
     dA.from_lapack(A)
     dB.from_lapack(Bm)
     info, it = ch.CHAMELEON_dsposv_Tile(uplo, dA, dB, dX)
@@ -74,7 +55,7 @@ def stopping_test_holds(A, Bm, X):
 def test_dsposv_against_numpy(cham, N, B, nrhs, u):
     ch = cham
     A, Bm, Xref = plgsy_problem(N, nrhs)
-    info, it, X, Aafter, Bafter = solve(ch, A, Bm, B, uplo_of(ch, u))
+    info, it, X, Aafter, Bafter = solve(ch, A, Bm, B, uplo_code(ch, u))
     assert info == 0 and 0 <= it <= 30, (info, it)
     ok, _ = stopping_test_holds(A, Bm, X)
     assert ok
@@ -83,7 +64,7 @@ def test_dsposv_against_numpy(cham, N, B, nrhs, u):
     st = ch.last_dsposv_stats()
     assert st["residuals"] == it + 1 and st["solves"] == it + 1
     # deterministic: a second call gives the same X and iter, bit for bit
-    info2, it2, X2, _, _ = solve(ch, A, Bm, B, uplo_of(ch, u))
+    info2, it2, X2, _, _ = solve(ch, A, Bm, B, uplo_code(ch, u))
     assert (info2, it2) == (info, it) and np.array_equal(bits(X2), bits(X))
 
 
@@ -92,10 +73,10 @@ def test_only_the_uplo_triangle_is_read(cham, N, B, nrhs, u):
     """The other triangle -- the other halves of the diagonal tiles included -- full of NaN: same X and iter."""
     ch = cham
     A, Bm, _ = plgsy_problem(N, nrhs)
-    info, it, X, _, _ = solve(ch, A, Bm, B, uplo_of(ch, u))
+    info, it, X, _, _ = solve(ch, A, Bm, B, uplo_code(ch, u))
     M = A.copy(order="F")
-    M[np.triu_indices(N, 1) if u == "L" else np.tril_indices(N, -1)] = np.nan
-    info2, it2, X2, Mafter, _ = solve(ch, M, Bm, B, uplo_of(ch, u))
+    M[other(N, u)] = np.nan
+    info2, it2, X2, Mafter, _ = solve(ch, M, Bm, B, uplo_code(ch, u))
     assert info == info2 == 0 and it2 == it >= 0
     assert np.array_equal(bits(X2), bits(X))
     assert np.array_equal(bits(Mafter), bits(M))
@@ -120,13 +101,13 @@ def test_harder_conditioning_still_converges(cham):
 def fallback_matches_dposv(ch, A, Bm, B, uplo, want_iter):
     """dsposv falls back (iter in want_iter) and leaves X and A bit-identical to lacpy(B -> X) + posv(A, X) on copies."""
     N, nrhs = Bm.shape
-    dA, dB, dX = desc(ch, N, B, N), desc(ch, N, B, nrhs), desc(ch, N, B, nrhs)
+    dA, dB, dX = desc(ch, N, B), desc(ch, N, B, cols=nrhs), desc(ch, N, B, cols=nrhs)
     dA.from_lapack(A)
     dB.from_lapack(Bm)
     info, it = ch.CHAMELEON_dsposv_Tile(uplo, dA, dB, dX)
     assert it in want_iter, it
     assert np.array_equal(bits(dB.to_lapack()), bits(Bm))
-    cA, cB, cX = desc(ch, N, B, N), desc(ch, N, B, nrhs), desc(ch, N, B, nrhs)
+    cA, cB, cX = desc(ch, N, B), desc(ch, N, B, cols=nrhs), desc(ch, N, B, cols=nrhs)
     cA.from_lapack(A)
     cB.from_lapack(Bm)
     ch.CHAMELEON_dlacpy_Tile(ch.ChamUpperLower, cB, cX)
@@ -144,7 +125,7 @@ def test_fallback_ill_conditioned(cham, u):
     N, B = 1024, 256
     A = spd_spectral(N, 1e10, 7)
     Bm = np.asfortranarray(np.random.default_rng(9).standard_normal((N, 3)))
-    info, _ = fallback_matches_dposv(ch, A, Bm, B, uplo_of(ch, u), (-3, -31))
+    info, _ = fallback_matches_dposv(ch, A, Bm, B, uplo_code(ch, u), (-3, -31))
     assert info == 0
 
 
@@ -176,10 +157,10 @@ def test_argument_errors(cham):
     ch = cham
     N, B = 512, 128
     A, Bm, _ = plgsy_problem(N, 2)
-    dA, dB, dX = desc(ch, N, B, N), desc(ch, N, B, 2), desc(ch, N, B, 2)
+    dA, dB, dX = desc(ch, N, B), desc(ch, N, B, cols=2), desc(ch, N, B, cols=2)
     dA.from_lapack(A)
     dB.from_lapack(Bm)
-    fA = desc(ch, N, B, N, ch.ChamRealFloat)
+    fA = desc(ch, N, B, "s")
     with pytest.raises(ch.CholmiError) as e:
         ch.CHAMELEON_dsposv_Tile(ch.ChamLower, fA, dB, dX)  # fp32 A
     assert e.value.code == -2
@@ -187,7 +168,7 @@ def test_argument_errors(cham):
         ch.CHAMELEON_dsposv_Tile(ch.ChamLower, dA, dB, dB)  # X aliases B
     assert e.value.code == -4
     with pytest.raises(ch.CholmiError) as e:
-        ch.CHAMELEON_dsposv_Tile(ch.ChamLower, dA, desc(ch, N, 256, 2), dX)  # tile size differs
+        ch.CHAMELEON_dsposv_Tile(ch.ChamLower, dA, desc(ch, N, 256, cols=2), dX)  # tile size differs
     assert e.value.code == -3
     assert ch.lib().chol_dsposv_tile(ch.ChamLower, dA.handle, dB.handle, dX.handle, None) == -5  # iter NULL
     it = C.c_int()

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import dyadic_model as dm
+from chol_testkit import bits, desc, lower_of, npdt, other_triangle_kept, stored_lower, uplo_code
 
 pytestmark = pytest.mark.gpu
 
@@ -56,44 +57,9 @@ def fam_kw(fam, B):
     return {} if fam == "parity" else {"family": fam, "B": B} if fam == "panel" else {"family": fam}
 
 
-def npdt(dt):
-    return np.float64 if dt == "d" else np.float32
-
-
-def chdt(ch, dt):
-    return ch.ChamRealDouble if dt == "d" else ch.ChamRealFloat
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
-
-
-def uplo(ch, u):
-    return ch.ChamLower if u == "L" else ch.ChamUpper
-
-
-def other(n, u):
-    return np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
-
-
-def stored(M, u, dt, fill=np.nan):
-    """the lower triangle of M (symmetric, or a Lower factor) stored in the `u` triangle, the other strict one = fill"""
-    S = np.array(np.tril(M) if u == "L" else np.tril(M).T, dtype=npdt(dt), order="F")
-    S[other(M.shape[0], u)] = fill
-    return S
-
-
-def lower_of(F, u):
-    return np.tril(F) if u == "L" else np.triu(F).T
-
-
-def desc(ch, N, B, dt, ncols=None, content=None):
-    nc = N if ncols is None else ncols
-    d = ch.CHAMELEON_Desc_Create(None, chdt(ch, dt), B, B, B * B, N, nc, 0, 0, N, nc, 1, 1)
-    if content is not None:
-        d.from_lapack(np.asarray(content, dtype=npdt(dt)))
-    return d
+def stored_as(M, u, dt, fill=np.nan):
+    """stored_lower of M rounded to dt"""
+    return stored_lower(M.astype(npdt(dt)), u, fill)
 
 
 def same(got, want, dt):
@@ -101,11 +67,6 @@ def same(got, want, dt):
     assert got.dtype == want.dtype
     bad = np.argwhere(got != want)
     assert len(bad) == 0, (len(bad), bad[:6].tolist())
-
-
-def other_kept(F, S, u):
-    idx = other(S.shape[0], u)
-    return np.array_equal(bits(F[idx]), bits(S[idx]))
 
 
 def rhs(fam, N, B, nrhs):
@@ -136,19 +97,19 @@ def test_potrs_and_posv_on_wide_panel_tiles_in_fp64(cham, fam, N, B, nrhs, u):
 def potrs_and_posv_are_exact(ch, fam, N, B, nrhs, u, dt):
     A, L, _ = dm.cholesky_case(N, N, **fam_kw(fam, B))
     X, Bm = rhs(fam, N, B, nrhs)
-    SL = stored(L, u, dt)
+    SL = stored_as(L, u, dt)
     dA, dB = desc(ch, N, B, dt, content=SL), desc(ch, N, B, dt, nrhs, Bm)
-    assert ch.CHAMELEON_dpotrs_Tile(uplo(ch, u), dA, dB) == 0
+    assert ch.CHAMELEON_dpotrs_Tile(uplo_code(ch, u), dA, dB) == 0
     same(dB.to_lapack(), X, dt)
     assert np.array_equal(bits(dA.to_lapack()), bits(SL))  # the factor is only read
-    SA = stored(A, u, dt)
+    SA = stored_as(A, u, dt)
     dA.from_lapack(SA)
     dB.from_lapack(Bm.astype(npdt(dt)))
-    assert ch.CHAMELEON_dposv_Tile(uplo(ch, u), dA, dB) == 0
+    assert ch.CHAMELEON_dposv_Tile(uplo_code(ch, u), dA, dB) == 0
     same(dB.to_lapack(), X, dt)
     F = dA.to_lapack()
     same(lower_of(F, u), L, dt)
-    assert other_kept(F, SA, u)
+    assert other_triangle_kept(F, SA, u)
     ch.CHAMELEON_Desc_Destroy(dA)
     ch.CHAMELEON_Desc_Destroy(dB)
 
@@ -161,13 +122,13 @@ def test_trtri(cham, fam, N, B, u, dt):
     inverse is no short dyadic number)"""
     ch = cham
     _, L, _ = dm.cholesky_case(N, N, **fam_kw(fam, B))
-    S = stored(L, u, dt)
+    S = stored_as(L, u, dt)
     d = desc(ch, N, B, dt, content=S)
-    assert ch.CHAMELEON_dtrtri_Tile(uplo(ch, u), ch.ChamNonUnit, d) == 0
+    assert ch.CHAMELEON_dtrtri_Tile(uplo_code(ch, u), ch.ChamNonUnit, d) == 0
     F = d.to_lapack()
     ch.CHAMELEON_Desc_Destroy(d)
     same(lower_of(F, u), dm.inv_factor(N, N, family=fam), dt)
-    assert other_kept(F, S, u)
+    assert other_triangle_kept(F, S, u)
 
 
 @pytest.mark.parametrize("fam,N,B", **INVERSES)
@@ -180,13 +141,13 @@ def test_potri_and_poinv(cham, fam, N, B, u, dt):
     A, L, _ = dm.cholesky_case(N, N, **fam_kw(fam, B))
     want = np.tril(dm.inv_spd(N, N, family=fam))
     for call, M in ((ch.CHAMELEON_dpotri_Tile, L), (ch.CHAMELEON_dpoinv_Tile, A)):
-        S = stored(M, u, dt)
+        S = stored_as(M, u, dt)
         d = desc(ch, N, B, dt, content=S)
-        assert call(uplo(ch, u), d) == 0
+        assert call(uplo_code(ch, u), d) == 0
         F = d.to_lapack()
         ch.CHAMELEON_Desc_Destroy(d)
         same(lower_of(F, u), want, dt)
-        assert other_kept(F, S, u)
+        assert other_triangle_kept(F, S, u)
 
 
 @pytest.mark.parametrize("N,B", SHAPES)
@@ -196,13 +157,13 @@ def test_lansy(cham, N, B, u, dt):
     """sums of integers: the one, infinity and max norms equal numpy's; Frobenius on its tolerance"""
     ch = cham
     A, _, _ = dm.cholesky_case(N, N)
-    d = desc(ch, N, B, dt, content=stored(A, u, dt))
+    d = desc(ch, N, B, dt, content=stored_as(A, u, dt))
     one = np.abs(A).sum(0).max()
-    assert ch.CHAMELEON_dlansy_Tile(ch.ChamOneNorm, uplo(ch, u), d) == one
-    assert ch.CHAMELEON_dlansy_Tile(ch.ChamInfNorm, uplo(ch, u), d) == one
-    assert ch.CHAMELEON_dlansy_Tile(ch.ChamMaxNorm, uplo(ch, u), d) == np.abs(A).max()
+    assert ch.CHAMELEON_dlansy_Tile(ch.ChamOneNorm, uplo_code(ch, u), d) == one
+    assert ch.CHAMELEON_dlansy_Tile(ch.ChamInfNorm, uplo_code(ch, u), d) == one
+    assert ch.CHAMELEON_dlansy_Tile(ch.ChamMaxNorm, uplo_code(ch, u), d) == np.abs(A).max()
     fro = np.linalg.norm(A)
-    assert abs(ch.CHAMELEON_dlansy_Tile(ch.ChamFrobeniusNorm, uplo(ch, u), d) - fro) <= (1e-12 if dt == "d" else 1e-5) * fro
+    assert abs(ch.CHAMELEON_dlansy_Tile(ch.ChamFrobeniusNorm, uplo_code(ch, u), d) - fro) <= (1e-12 if dt == "d" else 1e-5) * fro
     ch.CHAMELEON_Desc_Destroy(d)
 
 
@@ -222,15 +183,15 @@ def test_porfs_and_posvx_on_the_exact_solution(cham, fam, N, B, u, dt):
     X = np.where(X == 0, 1.0, X)
     Bm = A @ X
     assert (np.abs(Bm) + np.abs(A) @ np.abs(X)).min() >= 1
-    SA = stored(A, u, dt)
-    dA, dAF = desc(ch, N, B, dt, content=SA), desc(ch, N, B, dt, content=stored(L, u, dt))
+    SA = stored_as(A, u, dt)
+    dA, dAF = desc(ch, N, B, dt, content=SA), desc(ch, N, B, dt, content=stored_as(L, u, dt))
     dB, dX = desc(ch, N, B, dt, nrhs, Bm), desc(ch, N, B, dt, nrhs, X)
-    info, ferr, berr = ch.CHAMELEON_dporfs_Tile(uplo(ch, u), dA, dAF, dB, dX)
+    info, ferr, berr = ch.CHAMELEON_dporfs_Tile(uplo_code(ch, u), dA, dAF, dB, dX)
     assert info == 0 and np.array_equal(berr, np.zeros(nrhs)), berr
     same(dX.to_lapack(), X, dt)
     dAF.from_lapack(np.full((N, N), np.nan, dtype=npdt(dt)))
     dX.from_lapack(np.zeros((N, nrhs), dtype=npdt(dt)))
-    info, equed, rcond, ferr, berr = ch.CHAMELEON_dposvx_Tile("N", uplo(ch, u), dA, dAF, "N", None, dB, dX)
+    info, equed, rcond, ferr, berr = ch.CHAMELEON_dposvx_Tile("N", uplo_code(ch, u), dA, dAF, "N", None, dB, dX)
     # (LAPACK's info = n + 1, "rcond below eps", comes with the solution computed; fp32 reaches it at these orders)
     assert info == (N + 1 if rcond < (2.0 ** -53 if dt == "d" else 2.0 ** -24) else 0) and equed == "N" and rcond > 0
     same(dX.to_lapack(), X, dt)
@@ -250,9 +211,9 @@ def test_dsposv(cham, fam, N, B, u):
     A, _, _ = dm.cholesky_case(N, N, **fam_kw(fam, B))
     nrhs = 5
     X, Bm = rhs(fam, N, B, nrhs)
-    SA = stored(A, u, "d")
+    SA = stored_as(A, u, "d")
     dA, dB, dX = desc(ch, N, B, "d", content=SA), desc(ch, N, B, "d", nrhs, Bm), desc(ch, N, B, "d", nrhs)
-    info, it = ch.CHAMELEON_dsposv_Tile(uplo(ch, u), dA, dB, dX)
+    info, it = ch.CHAMELEON_dsposv_Tile(uplo_code(ch, u), dA, dB, dX)
     st = ch.last_dsposv_stats()
     assert (info, it) == (0, 0) and st["solves"] == 1 and st["residuals"] == 1
     same(dX.to_lapack(), X, "d")
@@ -283,7 +244,7 @@ def ldl_is_exact(ch, fam, N, B, u, dt, solves=True):
     nrhs = 5
     X = dm.solution(N, nrhs, N)
     Bm = A @ X
-    SA = stored(A, u, dt)
+    SA = stored_as(A, u, dt)
     dA, dB = desc(ch, N, B, dt, content=SA), desc(ch, N, B, dt, nrhs, Bm)
 
     def check_factor():
@@ -291,19 +252,19 @@ def ldl_is_exact(ch, fam, N, B, u, dt, solves=True):
         Fl = lower_of(F, u)
         same(np.tril(Fl, -1), np.tril(L, -1), dt)
         same(np.diag(Fl).copy(), dd, dt)
-        assert other_kept(F, SA, u)
+        assert other_triangle_kept(F, SA, u)
         st = ch.last_sytrf_stats()
         assert st["inertia"] == (int((dd > 0).sum()), int((dd < 0).sum()))
         assert (st["min_abs_d"], st["max_abs_d"], st["max_abs_l"]) == (1.0, 4.0, 1.0)
 
-    assert ch.CHAMELEON_dsytrf_nopiv_Tile(uplo(ch, u), dA) == 0
+    assert ch.CHAMELEON_dsytrf_nopiv_Tile(uplo_code(ch, u), dA) == 0
     check_factor()
-    assert ch.CHAMELEON_dsytrs_nopiv_Tile(uplo(ch, u), dA, dB) == 0
+    assert ch.CHAMELEON_dsytrs_nopiv_Tile(uplo_code(ch, u), dA, dB) == 0
     if solves:
         same(dB.to_lapack(), X, dt)
     dA.from_lapack(SA)
     dB.from_lapack(Bm.astype(npdt(dt)))
-    assert ch.CHAMELEON_dsysv_nopiv_Tile(uplo(ch, u), dA, dB) == 0
+    assert ch.CHAMELEON_dsysv_nopiv_Tile(uplo_code(ch, u), dA, dB) == 0
     check_factor()
     if solves:
         same(dB.to_lapack(), X, dt)
@@ -329,12 +290,12 @@ def test_sygst_on_wide_panel_tiles_in_fp64(cham, fam, N, B, u):
 
 def sygst_is_exact(ch, fam, N, B, u, dt):
     A, L, M = dm.sygst_case(N, N, **fam_kw(fam, B))
-    SA, SB = stored(A, u, dt), stored(L, u, dt, fill=-7.0)
+    SA, SB = stored_as(A, u, dt), stored_as(L, u, dt, fill=-7.0)
     dA, dB = desc(ch, N, B, dt, content=SA), desc(ch, N, B, dt, content=SB)
-    assert ch.CHAMELEON_dsygst_Tile(1, uplo(ch, u), dA, dB) == 0
+    assert ch.CHAMELEON_dsygst_Tile(1, uplo_code(ch, u), dA, dB) == 0
     F = dA.to_lapack()
     same(lower_of(F, u), np.tril(M), dt)
-    assert other_kept(F, SA, u)
+    assert other_triangle_kept(F, SA, u)
     assert np.array_equal(bits(dB.to_lapack()), bits(SB))
     ch.CHAMELEON_Desc_Destroy(dA)
     ch.CHAMELEON_Desc_Destroy(dB)

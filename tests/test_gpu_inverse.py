@@ -6,18 +6,11 @@ import functools
 import numpy as np
 import pytest
 
+from chol_testkit import bits, desc, other, spd_spectral, stored_lower, uplo_code
+
 pytestmark = pytest.mark.gpu
 
 EPS64, EPS32 = 2.0 ** -53, 2.0 ** -24
-
-
-def spd_spectral(n, kappa, seed):
-    """Q diag(logspace(0, -log10 kappa)) Q^T: kappa_2 = kappa exactly (up to rounding)  (as test_gpu_conditioning.py)."""
-    rng = np.random.default_rng(seed)
-    Q, _ = np.linalg.qr(rng.standard_normal((n, n)))
-    lam = np.logspace(0.0, -np.log10(kappa), n)
-    A = (Q * lam) @ Q.T
-    return np.asfortranarray((A + A.T) * 0.5)
 
 
 @functools.lru_cache(maxsize=4)
@@ -29,49 +22,25 @@ def plgsy_problem(N):
     return A, np.asfortranarray(np.linalg.cholesky(A))
 
 
-def desc(ch, N, B, ncols=None, dtype=None):
-    ncols = N if ncols is None else ncols
-    return ch.CHAMELEON_Desc_Create(None, dtype or ch.ChamRealDouble, B, B, B * B, N, ncols, 0, 0, N, ncols, 1, 1)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
-
-
-def uplo_of(ch, u):
-    return ch.ChamLower if u == "L" else ch.ChamUpper
-
-
-def other(N, u, k=1):
-    """indices of the strict triangle a `u` call must leave alone"""
-    return np.triu_indices(N, k) if u == "L" else np.tril_indices(N, -k)
-
-
-def stored(L, u, fill):
-    """the factor L stored in the `u` triangle (U = L^T for Upper), the other strict triangle = fill"""
-    M = np.array(L if u == "L" else L.T, order="F")
-    M[other(L.shape[0], u)] = fill[other(L.shape[0], u)] if isinstance(fill, np.ndarray) else fill
-    return M
-
-
-def run(ch, fn, M, B, u, dtype=None, extra=()):
+def run(ch, fn, M, B, u, dt="d", extra=()):
     """-> (info, the stored matrix after fn(uplo, *extra, A))"""
-    d = desc(ch, M.shape[0], B, dtype=dtype)
+    d = desc(ch, M.shape[0], B, dt)
     d.from_lapack(M)
-    info = fn(uplo_of(ch, u), *extra, d)
+    info = fn(uplo_code(ch, u), *extra, d)
     return info, d.to_lapack()
 
 
-def trtri(ch, M, B, u, dtype=None):
-    return run(ch, ch.CHAMELEON_dtrtri_Tile, M, B, u, dtype, (ch.ChamNonUnit,))
+def trtri(ch, M, B, u, dt="d"):
+    return run(ch, ch.CHAMELEON_dtrtri_Tile, M, B, u, dt, (ch.ChamNonUnit,))
 
 
 def potri(ch, M, B, u):
     return run(ch, ch.CHAMELEON_dpotri_Tile, M, B, u)
 
 
-def lower_of(X, u):
+def lower_of_rowmajor(X, u):
+    """chol_testkit.lower_of in C order for Upper too (tril of the transposed view, not the transposed triu): the
+    residual checks below multiply by it, and a BLAS may sum another layout in another order"""
     return np.tril(X) if u == "L" else np.tril(X.T)
 
 
@@ -100,11 +69,11 @@ TRTRI = [(512, 128, "L"), (512, 128, "U"), (1000, 192, "L"), (2048, 256, "L"), (
 def test_trtri_fp64(cham, N, B, u):
     ch = cham
     A, L = plgsy_problem(N)
-    M = stored(L, u, A)
+    M = stored_lower(L, u, A)
     info, Xs = trtri(ch, M, B, u)
     assert info == 0
     assert np.array_equal(bits(Xs[other(N, u)]), bits(M[other(N, u)]))
-    check_trtri_bound(L, lower_of(Xs, u), EPS64)
+    check_trtri_bound(L, lower_of_rowmajor(Xs, u), EPS64)
 
 
 @pytest.mark.parametrize("u", ["L", "U"])
@@ -113,11 +82,11 @@ def test_trtri_fp32(cham, u):
     N, B = 2048, 256
     _, L = plgsy_problem(N)
     L32 = np.asfortranarray(L.astype(np.float32))
-    M = stored(L32, u, np.float32(0.5))
-    info, Xs = trtri(ch, M, B, u, ch.ChamRealFloat)
+    M = stored_lower(L32, u, np.float32(0.5))
+    info, Xs = trtri(ch, M, B, u, "s")
     assert info == 0 and Xs.dtype == np.float32
     assert np.array_equal(bits(Xs[other(N, u)]), bits(M[other(N, u)]))
-    check_trtri_bound(L32.astype(np.float64), lower_of(Xs, u).astype(np.float64), EPS32)
+    check_trtri_bound(L32.astype(np.float64), lower_of_rowmajor(Xs, u).astype(np.float64), EPS32)
 
 
 @pytest.mark.parametrize("N,B,u", [(1000, 192, "L"), (1024, 256, "U")])
@@ -125,21 +94,21 @@ def test_other_triangle_nan(cham, N, B, u):
     """NaN in the other strict triangle (the other halves of the diagonal tiles included): same inverse, NaN kept"""
     ch = cham
     A, L = plgsy_problem(N)
-    info, X0 = trtri(ch, stored(L, u, A), B, u)
-    M = stored(L, u, np.nan)
+    info, X0 = trtri(ch, stored_lower(L, u, A), B, u)
+    M = stored_lower(L, u, np.nan)
     info2, X1 = trtri(ch, M, B, u)
     assert info == info2 == 0
-    assert np.array_equal(bits(lower_of(X1, u)), bits(lower_of(X0, u)))
+    assert np.array_equal(bits(lower_of_rowmajor(X1, u)), bits(lower_of_rowmajor(X0, u)))
     assert np.array_equal(bits(X1[other(N, u)]), bits(M[other(N, u)]))
     # potri on the same storage
     info3, P = potri(ch, M, B, u)
     assert info3 == 0 and np.array_equal(bits(P[other(N, u)]), bits(M[other(N, u)]))
-    assert not np.isnan(lower_of(P, u)).any()
+    assert not np.isnan(lower_of_rowmajor(P, u)).any()
 
 
 def check_potri(A, P, u, kappa, c=10.0):
     n = A.shape[0]
-    Xl = lower_of(P, u)
+    Xl = lower_of_rowmajor(P, u)
     X = Xl + np.tril(Xl, -1).T
     r = np.linalg.norm(A @ X - np.eye(n)) / (np.linalg.norm(A) * np.linalg.norm(X))
     assert r <= c * n * EPS64, r
@@ -152,7 +121,7 @@ def check_potri(A, P, u, kappa, c=10.0):
 def test_potri_plgsy(cham, N, B, u):
     ch = cham
     A, L = plgsy_problem(N)
-    M = stored(L, u, A)
+    M = stored_lower(L, u, A)
     info, P = potri(ch, M, B, u)
     assert info == 0
     assert np.array_equal(bits(P[other(N, u)]), bits(M[other(N, u)]))
@@ -168,8 +137,8 @@ def test_potri_conditioning(cham, kappa, u):
     A = spd_spectral(N, kappa, 5)
     d = desc(ch, N, B)
     d.from_lapack(A)
-    assert ch.CHAMELEON_dpotrf_Tile(uplo_of(ch, u), d) == 0
-    assert ch.CHAMELEON_dpotri_Tile(uplo_of(ch, u), d) == 0
+    assert ch.CHAMELEON_dpotrf_Tile(uplo_code(ch, u), d) == 0
+    assert ch.CHAMELEON_dpotri_Tile(uplo_code(ch, u), d) == 0
     P = d.to_lapack()
     assert np.array_equal(bits(P[other(N, u)]), bits(A[other(N, u)]))
     check_potri(A, P, u, kappa)
@@ -219,9 +188,9 @@ def test_poinv_is_potrf_then_potri(cham, N, B, u):
     d1, d2 = desc(ch, N, B), desc(ch, N, B)
     d1.from_lapack(A)
     d2.from_lapack(A)
-    assert ch.CHAMELEON_dpoinv_Tile(uplo_of(ch, u), d1) == 0
-    assert ch.CHAMELEON_dpotrf_Tile(uplo_of(ch, u), d2) == 0
-    assert ch.CHAMELEON_dpotri_Tile(uplo_of(ch, u), d2) == 0
+    assert ch.CHAMELEON_dpoinv_Tile(uplo_code(ch, u), d1) == 0
+    assert ch.CHAMELEON_dpotrf_Tile(uplo_code(ch, u), d2) == 0
+    assert ch.CHAMELEON_dpotri_Tile(uplo_code(ch, u), d2) == 0
     assert np.array_equal(bits(d1.to_lapack()), bits(d2.to_lapack()))
 
 
@@ -246,7 +215,7 @@ def test_zero_on_the_diagonal(cham, which, N, B, u, j):
     A, L = plgsy_problem(N)
     L0 = L.copy(order="F")
     L0[j, j] = 0.0
-    M = stored(L0, u, A)
+    M = stored_lower(L0, u, A)
     info, after = (trtri if which == "trtri" else potri)(ch, M, B, u)
     assert info == j + 1
     assert np.array_equal(bits(after), bits(M))
@@ -266,7 +235,7 @@ def test_argument_errors(cham):
         with pytest.raises(ch.CholmiError) as e:
             call(d)
         assert e.value.code == -1
-    rect = desc(ch, N, B, N + B)
+    rect = desc(ch, N, B, cols=N + B)
     with pytest.raises(ch.CholmiError) as e:
         ch.CHAMELEON_dtrtri_Tile(ch.ChamLower, ch.ChamNonUnit, rect)
     assert e.value.code == -3
@@ -289,7 +258,7 @@ def test_deterministic(cham):
     ch = cham
     N, B = 2048, 256
     A, L = plgsy_problem(N)
-    M = stored(L, "L", A)
+    M = stored_lower(L, "L", A)
     _, X1 = trtri(ch, M, B, "L")
     _, X2 = trtri(ch, M, B, "L")
     assert np.array_equal(bits(X1), bits(X2))

@@ -5,16 +5,9 @@ import numpy as np
 import pytest
 import scipy.linalg.lapack as lapack
 
+from chol_testkit import bits, desc, lower_of, pxq_refused, spd_spectral, stored_lower, uplo_code
+
 pytestmark = pytest.mark.gpu
-
-
-def spd_spectral(n, kappa, seed):
-    """Q diag(logspace(0, -log10 kappa)) Q^T: kappa_2 = kappa exactly (up to rounding)  (as test_gpu_conditioning.py)."""
-    rng = np.random.default_rng(seed)
-    Q, _ = np.linalg.qr(rng.standard_normal((n, n)))
-    lam = np.logspace(0.0, -np.log10(kappa), n)
-    A = (Q * lam) @ Q.T
-    return np.asfortranarray((A + A.T) * 0.5)
 
 
 def plgsy_matrix(N):
@@ -23,31 +16,8 @@ def plgsy_matrix(N):
     return orc.plgsy_matrix(N, float(N), 42)
 
 
-def desc(ch, N, B, dtype=None):
-    return ch.CHAMELEON_Desc_Create(None, dtype or ch.ChamRealDouble, B, B, B * B, N, N, 0, 0, N, N, 1, 1)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
-
-
-def uplo_of(ch, u):
-    return ch.ChamLower if u == "L" else ch.ChamUpper
-
-
-def stored(M, u, fill=np.nan):
-    """the lower triangle of M (a factor L, or a symmetric matrix) stored in the `u` triangle (Upper: that of M^T),
-    the other strict triangle = fill"""
-    n = M.shape[0]
-    S = np.array(np.tril(M) if u == "L" else np.triu(M.T), order="F")
-    idx = np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
-    S[idx] = fill
-    return S
-
-
-def upload(ch, S, B, dtype=None):
-    d = desc(ch, S.shape[0], B, dtype)
+def upload(ch, S, B, dt="d"):
+    d = desc(ch, S.shape[0], B, dt)
     d.from_lapack(S)
     return d
 
@@ -74,27 +44,27 @@ def test_lansy(cham, N, B, u, dt):
     npt = np.float64 if dt == "d" else np.float32
     X = rng.standard_normal((N, N))
     Sym = ((X + X.T) * 0.5).astype(npt)
-    S = stored(Sym, u)
-    d = upload(ch, S, B, ch.ChamRealDouble if dt == "d" else ch.ChamRealFloat)
+    S = stored_lower(Sym, u)
+    d = upload(ch, S, B, dt)
     full = Sym.astype(np.float64)
     want = {ch.ChamMaxNorm: np.abs(full).max(), ch.ChamOneNorm: np.linalg.norm(full, 1),
             ch.ChamInfNorm: np.linalg.norm(full, np.inf), ch.ChamFrobeniusNorm: np.linalg.norm(full, "fro")}
     got = {}
     for norm, w in want.items():
-        got[norm] = ch.CHAMELEON_dlansy_Tile(norm, uplo_of(ch, u), d)
+        got[norm] = ch.CHAMELEON_dlansy_Tile(norm, uplo_code(ch, u), d)
         assert abs(got[norm] - w) <= 1e-13 * w, (norm, got[norm], w)
-        assert ch.CHAMELEON_dlansy_Tile(norm, uplo_of(ch, u), d) == got[norm]  # repeat: the same bits
+        assert ch.CHAMELEON_dlansy_Tile(norm, uplo_code(ch, u), d) == got[norm]  # repeat: the same bits
     assert got[ch.ChamMaxNorm] == want[ch.ChamMaxNorm]
     assert np.float64(got[ch.ChamOneNorm]).tobytes() == np.float64(got[ch.ChamInfNorm]).tobytes()
     assert np.array_equal(bits(d.to_lapack()), bits(S))  # A unchanged, NaN half included
 
 
 # ------------------------------------------------------------------------------------------------------------ pocon
-def pocon(ch, Lf, u, B, anorm, dtype=None):
+def pocon(ch, Lf, u, B, anorm, dt="d"):
     """-> (rcond, stats, the stored factor after the call, what was stored)"""
-    S = stored(Lf, u)
-    d = upload(ch, S, B, dtype)
-    r = ch.CHAMELEON_dpocon_Tile(uplo_of(ch, u), d, anorm)
+    S = stored_lower(Lf, u)
+    d = upload(ch, S, B, dt)
+    r = ch.CHAMELEON_dpocon_Tile(uplo_code(ch, u), d, anorm)
     return r, ch.last_pocon_stats(), d.to_lapack(), S
 
 
@@ -143,7 +113,7 @@ def test_pocon_fp32(cham, kappa, u):
     A = spd_spectral(N, kappa, 11)
     Lf = np.asfortranarray(np.linalg.cholesky(A).astype(np.float32))
     anorm = float(np.linalg.norm(A.astype(np.float32).astype(np.float64), 1))
-    r, st, after, S = pocon(ch, Lf, u, B, anorm, ch.ChamRealFloat)
+    r, st, after, S = pocon(ch, Lf, u, B, anorm, "s")
     ref = lapack_rcond(Lf, u, anorm)
     assert abs(r - ref) <= 1e-3 * ref, (r, ref)
     assert np.array_equal(bits(after), bits(S))
@@ -154,14 +124,14 @@ def test_pocon_on_potrf_factor_with_lansy(cham, N, B, u):
     """the whole workflow on the device: lansy of A, potrf, pocon -- against LAPACK on the same factor"""
     ch = cham
     A = plgsy_matrix(N)
-    S = stored(A, u)
+    S = stored_lower(A, u)
     d = upload(ch, S, B)
-    anorm = ch.CHAMELEON_dlansy_Tile(ch.ChamOneNorm, uplo_of(ch, u), d)
+    anorm = ch.CHAMELEON_dlansy_Tile(ch.ChamOneNorm, uplo_code(ch, u), d)
     assert abs(anorm - np.linalg.norm(A, 1)) <= 1e-13 * anorm
-    assert ch.CHAMELEON_dpotrf_Tile(uplo_of(ch, u), d) == 0
+    assert ch.CHAMELEON_dpotrf_Tile(uplo_code(ch, u), d) == 0
     F = d.to_lapack()
-    Lf = np.asfortranarray(np.tril(F) if u == "L" else np.triu(F).T)
-    r = ch.CHAMELEON_dpocon_Tile(uplo_of(ch, u), d, anorm)
+    Lf = np.asfortranarray(lower_of(F, u))
+    r = ch.CHAMELEON_dpocon_Tile(uplo_code(ch, u), d, anorm)
     ref = lapack_rcond(Lf, u, anorm)
     assert abs(r - ref) <= 1e-6 * ref, (r, ref)
 
@@ -189,11 +159,11 @@ def test_pocon_deterministic(cham, u):
     N, B = 2048, 256
     A = spd_spectral(N, 1e6, 3)
     Lf = np.asfortranarray(np.linalg.cholesky(A))
-    S = stored(Lf, u)
+    S = stored_lower(Lf, u)
     d = upload(ch, S, B)
     anorm = float(np.linalg.norm(A, 1))
-    r1 = ch.CHAMELEON_dpocon_Tile(uplo_of(ch, u), d, anorm)
-    r2 = ch.CHAMELEON_dpocon_Tile(uplo_of(ch, u), d, anorm)
+    r1 = ch.CHAMELEON_dpocon_Tile(uplo_code(ch, u), d, anorm)
+    r2 = ch.CHAMELEON_dpocon_Tile(uplo_code(ch, u), d, anorm)
     assert np.float64(r1).tobytes() == np.float64(r2).tobytes()
     assert np.array_equal(bits(d.to_lapack()), bits(S))
 
@@ -203,14 +173,14 @@ def test_pocon_edge_cases(cham):
     N, B = 512, 128
     A = plgsy_matrix(N)
     Lf = np.asfortranarray(np.linalg.cholesky(A))
-    d = upload(ch, stored(Lf, "L"), B)
+    d = upload(ch, stored_lower(Lf, "L"), B)
     assert ch.CHAMELEON_dpocon_Tile(ch.ChamLower, d, 0.0) == 0.0
     assert ch.CHAMELEON_dpocon_Tile(ch.ChamLower, d, float("inf")) == 0.0
     Z = Lf.copy()
     Z[300, 300] = 0.0
     for u in ("L", "U"):
-        dz = upload(ch, stored(Z, u), B)
-        assert ch.CHAMELEON_dpocon_Tile(uplo_of(ch, u), dz, 1.0) == 0.0
+        dz = upload(ch, stored_lower(Z, u), B)
+        assert ch.CHAMELEON_dpocon_Tile(uplo_code(ch, u), dz, 1.0) == 0.0
         assert ch.last_pocon_stats()["applications"] == 0
     for bad, code in ((-1.0, -3), (float("nan"), -3)):
         with pytest.raises(ch.CholmiError) as e:
@@ -232,18 +202,6 @@ def test_pocon_edge_cases(cham):
 
 
 def test_pxq_descriptor_is_not_supported(cham):
-    from dense_linear_app_amd._lib import lib
-
     ch = cham
-    lib().chol_set_transport(None)
-    ch.set_rank(0, 2)
-    try:
-        d = ch.CHAMELEON_Desc_Create(None, ch.ChamRealDouble, 256, 256, 256 * 256, 1024, 1024, 0, 0, 1024, 1024, 1, 2)
-        for call in (lambda: ch.CHAMELEON_dpocon_Tile(ch.ChamLower, d, 1.0),
-                     lambda: ch.CHAMELEON_dlansy_Tile(ch.ChamOneNorm, ch.ChamLower, d)):
-            with pytest.raises(ch.CholmiError) as e:
-                call()
-            assert e.value.code == -104  # CHOL_ERR_NOT_SUPPORTED
-        ch.CHAMELEON_Desc_Destroy(d)
-    finally:
-        ch.set_rank(0, 1)
+    pxq_refused(ch, 1, lambda d: ch.CHAMELEON_dpocon_Tile(ch.ChamLower, d, 1.0),
+                lambda d: ch.CHAMELEON_dlansy_Tile(ch.ChamOneNorm, ch.ChamLower, d))

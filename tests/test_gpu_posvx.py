@@ -6,40 +6,14 @@ import numpy as np
 import pytest
 import scipy.linalg.lapack as lapack
 
+from chol_testkit import bits, desc, other, pxq_refused, stored_sym, uplo_code
+
 pytestmark = pytest.mark.gpu
 
 KX = 40  # spd.hip: POSVX_KX, the widest application of A^{-1} that runs as multi-vector sweeps
 NPT = {"d": np.float64, "s": np.float32}
 EPS = {"d": 2.0 ** -53, "s": 2.0 ** -24}
 C_BERR = 2.0  # berr <= (n + 1) eps C_BERR
-
-
-def dtype_of(ch, dt):
-    return ch.ChamRealDouble if dt == "d" else ch.ChamRealFloat
-
-
-def desc(ch, N, B, ncols, dt="d"):
-    return ch.CHAMELEON_Desc_Create(None, dtype_of(ch, dt), B, B, B * B, N, ncols, 0, 0, N, ncols, 1, 1)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
-
-
-def uplo_of(ch, u):
-    return ch.ChamLower if u == "L" else ch.ChamUpper
-
-
-def other(n, u):
-    return np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
-
-
-def stored(M, u, fill=np.nan):
-    """the `u` triangle of the symmetric M, the other strict triangle = fill"""
-    S = np.array(M, order="F")
-    S[other(M.shape[0], u)] = fill
-    return S
 
 
 def sym_of(S, u):
@@ -62,15 +36,15 @@ def scaled_problem(N, nrhs, dt, seed=7):
 
 def run_posvx(ch, fact, u, A, Bm, B, dt, AF=None, equed="N", S=None, X0=None):
     N, nrhs = Bm.shape
-    dA, dAF, dS = desc(ch, N, B, N, dt), desc(ch, N, B, N, dt), desc(ch, N, B, 1, dt)
-    dB, dX = desc(ch, N, B, nrhs, dt), desc(ch, N, B, nrhs, dt)
-    dA.from_lapack(stored(A, u))
-    dAF.from_lapack(stored(AF, u) if AF is not None else np.full((N, N), np.nan, dtype=NPT[dt]))
+    dA, dAF, dS = desc(ch, N, B, dt), desc(ch, N, B, dt), desc(ch, N, B, dt, 1)
+    dB, dX = desc(ch, N, B, dt, nrhs), desc(ch, N, B, dt, nrhs)
+    dA.from_lapack(stored_sym(A, u))
+    dAF.from_lapack(stored_sym(AF, u) if AF is not None else np.full((N, N), np.nan, dtype=NPT[dt]))
     if S is not None:
         dS.from_lapack(S.reshape(N, 1))
     dB.from_lapack(Bm)
     dX.from_lapack(X0 if X0 is not None else np.zeros((N, nrhs), dtype=NPT[dt]))
-    info, eq, rcond, ferr, berr = ch.CHAMELEON_dposvx_Tile(fact, uplo_of(ch, u), dA, dAF, equed, dS, dB, dX)
+    info, eq, rcond, ferr, berr = ch.CHAMELEON_dposvx_Tile(fact, uplo_code(ch, u), dA, dAF, equed, dS, dB, dX)
     out = dict(info=info, equed=eq, rcond=rcond, ferr=ferr, berr=berr, A=dA.to_lapack(), AF=dAF.to_lapack(),
                S=dS.to_lapack()[:, 0], B=dB.to_lapack(), X=dX.to_lapack(), stats=ch.last_posvx_stats())
     return out
@@ -104,8 +78,8 @@ SHAPES = [(1000, 192), (512, 128)]
 def test_poequ(cham, N, B, dt):
     ch = cham
     A, Bm = scaled_problem(N, 1, dt)
-    dA, dS = desc(ch, N, B, N, dt), desc(ch, N, B, 1, dt)
-    dA.from_lapack(stored(A, "L"))
+    dA, dS = desc(ch, N, B, dt), desc(ch, N, B, dt, 1)
+    dA.from_lapack(stored_sym(A, "L"))
     before = dA.to_lapack()
     info, scond, amax = ch.CHAMELEON_dpoequ_Tile(dA, dS)
     d = np.diag(A)
@@ -121,7 +95,7 @@ def test_poequ(cham, N, B, dt):
     A2 = A.copy()
     A2[N // 2 + 3, N // 2 + 3] = -1.0
     A2[N - 7, N - 7] = 0.0
-    dA.from_lapack(stored(A2, "L"))
+    dA.from_lapack(stored_sym(A2, "L"))
     assert ch.CHAMELEON_dpoequ_Tile(dA, dS)[0] == N // 2 + 4
 
 
@@ -141,12 +115,12 @@ def test_laqsy(cham, u, dt):
         D = 1.0 / np.sqrt(np.diag(A0)) * dg
         A = np.asfortranarray((D[:, None] * A0 * D[None, :]).astype(NPT[dt]))
         A = np.asfortranarray((A + A.T) / 2)
-        dA, dS = desc(ch, N, B, N, dt), desc(ch, N, B, 1, dt)
-        dA.from_lapack(stored(A, u))
+        dA, dS = desc(ch, N, B, dt), desc(ch, N, B, dt, 1)
+        dA.from_lapack(stored_sym(A, u))
         before = dA.to_lapack()
         info, scond, amax = ch.CHAMELEON_dpoequ_Tile(dA, dS)
         assert info == 0 and (scond < 0.1) == scaled, scond
-        equed = ch.CHAMELEON_dlaqsy_Tile(uplo_of(ch, u), dA, dS, scond, amax)
+        equed = ch.CHAMELEON_dlaqsy_Tile(uplo_code(ch, u), dA, dS, scond, amax)
         after = dA.to_lapack()
         a_s, _, eq_ref = fn(A, np.ones((N, 1), dtype=NPT[dt]), fact="E", lower=int(u == "L"))[:3]
         assert equed == ("Y" if scaled else "N") == eq_ref.decode()
@@ -286,15 +260,15 @@ def test_porfs_on_potrs_solution(cham, u, dt):
     A = np.asfortranarray((Xr @ Xr.T / N + 0.05 * np.eye(N)).astype(NPT[dt]))
     A = np.asfortranarray((A + A.T) / 2)
     Bm = np.asfortranarray(rng.standard_normal((N, nrhs)).astype(NPT[dt]))
-    dA, dAF, dB, dX = desc(ch, N, B, N, dt), desc(ch, N, B, N, dt), desc(ch, N, B, nrhs, dt), desc(ch, N, B, nrhs, dt)
-    dA.from_lapack(stored(A, u))
-    dAF.from_lapack(stored(A, u))
+    dA, dAF, dB, dX = desc(ch, N, B, dt), desc(ch, N, B, dt), desc(ch, N, B, dt, nrhs), desc(ch, N, B, dt, nrhs)
+    dA.from_lapack(stored_sym(A, u))
+    dAF.from_lapack(stored_sym(A, u))
     dB.from_lapack(Bm)
-    assert ch.CHAMELEON_dpotrf_Tile(uplo_of(ch, u), dAF) == 0
+    assert ch.CHAMELEON_dpotrf_Tile(uplo_code(ch, u), dAF) == 0
     dX.from_lapack(Bm)
-    assert ch.CHAMELEON_dpotrs_Tile(uplo_of(ch, u), dAF, dX) == 0
+    assert ch.CHAMELEON_dpotrs_Tile(uplo_code(ch, u), dAF, dX) == 0
     before = dA.to_lapack()
-    info, ferr, berr = ch.CHAMELEON_dporfs_Tile(uplo_of(ch, u), dA, dAF, dB, dX)
+    info, ferr, berr = ch.CHAMELEON_dporfs_Tile(uplo_code(ch, u), dA, dAF, dB, dX)
     assert info == 0
     assert np.array_equal(bits(dA.to_lapack()), bits(before))
     check_bounds(dX.to_lapack(), true_solution(A, Bm), ferr, berr, N, dt)
@@ -307,8 +281,8 @@ def test_argument_errors(cham):
 
     ch = cham
     N, B = 256, 128
-    dA, dAF, dS = desc(ch, N, B, N), desc(ch, N, B, N), desc(ch, N, B, 1)
-    dB, dX, dXs = desc(ch, N, B, 2), desc(ch, N, B, 2), desc(ch, N, B, 2, "s")
+    dA, dAF, dS = desc(ch, N, B), desc(ch, N, B), desc(ch, N, B, cols=1)
+    dB, dX, dXs = desc(ch, N, B, cols=2), desc(ch, N, B, cols=2), desc(ch, N, B, "s", 2)
     d = C.c_double()
     e = C.c_int(0)
     f2 = (C.c_double * 2)()
@@ -342,23 +316,10 @@ def test_argument_errors(cham):
 
 
 def test_pxq_descriptor_is_not_supported(cham):
-    from dense_linear_app_amd._lib import lib
-
     ch = cham
-    lib().chol_set_transport(None)
-    ch.set_rank(0, 2)
-    try:
-        mk = lambda n: ch.CHAMELEON_Desc_Create(None, ch.ChamRealDouble, 256, 256, 256 * 256, 1024, n, 0, 0, 1024, n,  # noqa: E731
-                                                1, 2)
-        dA, dAF, dS, dB, dX = mk(1024), mk(1024), mk(1), mk(2), mk(2)
-        for call in (lambda: ch.CHAMELEON_dpoequ_Tile(dA, dS),
-                     lambda: ch.CHAMELEON_dlaqsy_Tile(ch.ChamLower, dA, dS, 0.01, 1.0),
-                     lambda: ch.CHAMELEON_dporfs_Tile(ch.ChamLower, dA, dAF, dB, dX),
-                     lambda: ch.CHAMELEON_dposvx_Tile("E", ch.ChamLower, dA, dAF, "N", dS, dB, dX)):
-            with pytest.raises(ch.CholmiError) as e:
-                call()
-            assert e.value.code == -104  # CHOL_ERR_NOT_SUPPORTED
-        for d in (dA, dAF, dS, dB, dX):
-            ch.CHAMELEON_Desc_Destroy(d)
-    finally:
-        ch.set_rank(0, 1)
+    pxq_refused(
+        ch, (1024, 1024, 1, 2, 2),
+        lambda dA, dAF, dS, dB, dX: ch.CHAMELEON_dpoequ_Tile(dA, dS),
+        lambda dA, dAF, dS, dB, dX: ch.CHAMELEON_dlaqsy_Tile(ch.ChamLower, dA, dS, 0.01, 1.0),
+        lambda dA, dAF, dS, dB, dX: ch.CHAMELEON_dporfs_Tile(ch.ChamLower, dA, dAF, dB, dX),
+        lambda dA, dAF, dS, dB, dX: ch.CHAMELEON_dposvx_Tile("E", ch.ChamLower, dA, dAF, "N", dS, dB, dX))

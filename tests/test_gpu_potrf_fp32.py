@@ -23,6 +23,8 @@ when that tile's whole update is dropped, unless the matrix then fails to factor
 import numpy as np
 import pytest
 
+from chol_testkit import spd_spectral
+
 pytestmark = pytest.mark.gpu
 EPS32 = float(np.finfo(np.float32).eps)
 FWD = {"gram": (6e-6, 1.2e-5), "kappa1e3": (3e-5, 6e-5)}  # (full, strictly lower)
@@ -34,17 +36,14 @@ def spd_gram(n, seed):
     return M @ M.T / n + 0.05 * np.eye(n)
 
 
-def spd_spectral(n, kappa, seed):
-    """Q diag(logspace(0, -log10 kappa)) Q^T: kappa_2 = kappa exactly (up to rounding)."""
-    rng = np.random.default_rng(seed)
-    Q, _ = np.linalg.qr(rng.standard_normal((n, n)))
-    lam = np.logspace(0.0, -np.log10(kappa), n)
-    A = (Q * lam) @ Q.T
-    return (A + A.T) * 0.5
+def spd_spectral_rowmajor(n, kappa, seed):
+    """chol_testkit.spd_spectral in C order, as this file has always rounded it to fp32: the matrix is symmetric bit
+    for bit, so its transposed view is that"""
+    return spd_spectral(n, kappa, seed).T
 
 
 def fp32_input(kind, N, B):
-    A = spd_gram(N, 7 * N + B) if kind == "gram" else spd_spectral(N, 1e3, 11 * N + B)
+    A = spd_gram(N, 7 * N + B) if kind == "gram" else spd_spectral_rowmajor(N, 1e3, 11 * N + B)
     return np.asfortranarray(A.astype(np.float32).astype(np.float64))
 
 

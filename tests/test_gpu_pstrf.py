@@ -8,14 +8,12 @@ import numpy as np
 import pytest
 import scipy.linalg.lapack as lapack
 
+from chol_testkit import UserView, bits, desc, npdt, other_triangle_kept, pxq_refused, stored_lower, uplo_code
+from pstrf_model import gram
+
 pytestmark = pytest.mark.gpu
 
 EPS = {"d": 2.0 ** -53, "s": 2.0 ** -24}
-
-
-def gram(n, r, seed, dtype=np.float64):
-    G = np.random.default_rng(seed).standard_normal((n, r))
-    return np.asfortranarray((G @ G.T).astype(dtype))
 
 
 @functools.lru_cache(maxsize=None)
@@ -26,42 +24,12 @@ def full_rank(n, seed):
     return A, float(ev[-1] / ev[0])
 
 
-def npdt(dt):
-    return np.float64 if dt == "d" else np.float32
-
-
-def chdt(ch, dt):
-    return ch.ChamRealDouble if dt == "d" else ch.ChamRealFloat
-
-
-def uplo_of(ch, u):
-    return ch.ChamLower if u == "L" else ch.ChamUpper
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
-
-
-def stored(M, u, fill=np.nan):
-    """the lower triangle of the symmetric M stored in the `u` triangle, the other strict triangle = fill"""
-    n = M.shape[0]
-    S = np.array(np.tril(M) if u == "L" else np.triu(M.T), order="F")
-    idx = np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
-    S[idx] = fill
-    return S
-
-
-def desc(ch, N, B, dtype):
-    return ch.CHAMELEON_Desc_Create(None, dtype, B, B, B * B, N, N, 0, 0, N, N, 1, 1)
-
-
 def pstrf(ch, A, B, u="L", dt="d", tol=-1.0):
     """-> (info, piv, rank, L as Lower, the stored matrix after the call, what was stored)"""
-    S = stored(A.astype(npdt(dt)), u)
-    d = desc(ch, A.shape[0], B, chdt(ch, dt))
+    S = stored_lower(A.astype(npdt(dt)), u)
+    d = desc(ch, A.shape[0], B, dt)
     d.from_lapack(S)
-    info, piv, rank = ch.CHAMELEON_dpstrf_Tile(uplo_of(ch, u), d, tol)
+    info, piv, rank = ch.CHAMELEON_dpstrf_Tile(uplo_code(ch, u), d, tol)
     F = d.to_lapack()
     ch.CHAMELEON_Desc_Destroy(d)
     L = np.tril(F) if u == "L" else np.triu(F).T
@@ -80,12 +48,6 @@ def residual(A, piv, L, rank):
     P = A[np.ix_(piv - 1, piv - 1)]
     Lr = L.astype(np.float64)[:, :rank]
     return np.linalg.norm(P[:, :rank] - Lr @ Lr[:rank].T) / np.linalg.norm(A)
-
-
-def assert_other_triangle(F, S, u):
-    n = S.shape[0]
-    idx = np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
-    assert np.array_equal(bits(F[idx]), bits(S[idx]))
 
 
 # ------------------------------------------------------------------------------------------------------- full rank
@@ -107,7 +69,7 @@ def test_full_rank(cham, N, B, u, dt):
     if np.array_equal(piv, ref_piv):
         err = np.abs(L.astype(np.float64) - Lref).max() / np.abs(Lref).max()
         assert err <= 10 * kappa * np.sqrt(N) * EPS[dt], (err, kappa)
-    assert_other_triangle(F, S, u)
+    assert other_triangle_kept(F, S, u)
     st = ch.last_pstrf_stats()
     assert st["steps"] == N and st["total_ms"] > 0 and st["steps_ms"] > 0
 
@@ -125,7 +87,7 @@ def test_rank_deficient(cham, r, u):
     assert sorted(piv) == list(range(1, N + 1))
     assert np.array_equal(piv[:rank], ref_piv[:rank])
     assert residual(A, piv, L, rank) <= 30 * N * EPS["d"]  # (the rows of L match piv)
-    assert_other_triangle(F, S, u)
+    assert other_triangle_kept(F, S, u)
     assert ch.last_pstrf_stats()["steps"] == r
 
 
@@ -236,7 +198,7 @@ def test_single_tile_not_a_multiple_of_64(cham):
         assert info == 1 and rank == ref_rank == 60
         assert np.array_equal(piv[:rank], ref_piv[:rank])
         assert residual(A, piv, L, rank) <= 30 * N * EPS["d"]
-        assert_other_triangle(F, S, u)
+        assert other_triangle_kept(F, S, u)
 
 
 def test_argument_errors(cham):
@@ -245,7 +207,7 @@ def test_argument_errors(cham):
 
     ch = cham
     N, B = 256, 128
-    d = desc(ch, N, B, ch.ChamRealDouble)
+    d = desc(ch, N, B, "d")
     d.from_lapack(full_rank(N, 15)[0])
     piv = (C.c_int * N)()
     r = C.c_int()
@@ -265,33 +227,18 @@ def test_argument_errors(cham):
 
 
 def test_pxq_descriptor_is_not_supported(cham):
-    from dense_linear_app_amd._lib import lib
-
     ch = cham
-    lib().chol_set_transport(None)
-    ch.set_rank(0, 2)
-    try:
-        d = ch.CHAMELEON_Desc_Create(None, ch.ChamRealDouble, 256, 256, 256 * 256, 1024, 1024, 0, 0, 1024, 1024, 1, 2)
-        with pytest.raises(ch.CholmiError) as e:
-            ch.CHAMELEON_dpstrf_Tile(ch.ChamLower, d)
-        assert e.value.code == -104  # CHOL_ERR_NOT_SUPPORTED
-        ch.CHAMELEON_Desc_Destroy(d)
-    finally:
-        ch.set_rank(0, 1)
+    pxq_refused(ch, 1, lambda d: ch.CHAMELEON_dpstrf_Tile(ch.ChamLower, d))
 
 
 def test_sub_matrix_view(cham):
     """a tile-aligned view of a device user buffer gives the factor of the whole-matrix descriptor; the user's tiles
     outside the view stay as they were"""
-    import torch
-
     ch = cham
-    mb, lt, oi, oj, vt = 256, 5, 1, 2, 3
-    lm, m = lt * mb, vt * mb
-    user = np.random.default_rng(16).standard_normal(lt * lt * mb * mb)
-    buf = torch.from_numpy(user.copy()).cuda()
+    uv = UserView(ch)
+    mb, m = uv.mb, uv.m
     A = gram(m, 500, 16)
-    v = ch.CHAMELEON_Desc_Create(buf, ch.ChamRealDouble, mb, mb, mb * mb, lm, lm, oi * mb, oj * mb, m, m, 1, 1)
+    v = uv.view_desc()
     v.from_lapack(A)
     info, piv, rank = ch.CHAMELEON_dpstrf_Tile(ch.ChamLower, v)
     Lv = np.tril(v.to_lapack())
@@ -300,12 +247,7 @@ def test_sub_matrix_view(cham):
     assert (info, rank) == (info2, rank2) == (1, 500)
     assert np.array_equal(piv, piv2)
     assert np.array_equal(bits(Lv[:, :rank]), bits(L2[:, :rank]))
-    now = buf.cpu().numpy().reshape(lt * lt, mb * mb)
-    before = user.reshape(lt * lt, mb * mb)
-    for J in range(lt):
-        for I in range(lt):
-            if not (oi <= I < oi + vt and oj <= J < oj + vt):
-                assert np.array_equal(now[I + J * lt], before[I + J * lt]), (I, J)
+    uv.outside_unchanged()
 
 
 def test_large(cham):

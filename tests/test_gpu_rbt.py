@@ -29,6 +29,8 @@ import functools
 import numpy as np
 import pytest
 
+from chol_testkit import (U, UserView, bits, desc, image_matrix, lower_of, npdt, other, other_triangle_kept,
+                          ragged_padding_mask, stored_lower, uplo_code)
 from rbt_model import backward_error, family, random_w, rbt_sym, sysv_rbt_model
 
 pytestmark = pytest.mark.gpu
@@ -36,48 +38,6 @@ pytestmark = pytest.mark.gpu
 BERR_U = 6.23       # 10 x 0.623 u, the model's largest final berr (above)
 MAX_STEPS = 3       # the model's largest step count (1) + 2
 SPD_SOLVE_U = 9.63  # 10 x 0.963 u, the model's largest backward error of sytrs_rbt on the SPD cases (above)
-U = {"d": 2.0 ** -53, "s": 2.0 ** -24}
-
-
-def npdt(dt):
-    return np.float64 if dt == "d" else np.float32
-
-
-def chdt(ch, dt):
-    return ch.ChamRealDouble if dt == "d" else ch.ChamRealFloat
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
-
-
-def stored(M, u, fill=np.nan):
-    """the lower triangle of M stored in the `u` triangle, the other strict one = fill"""
-    n = M.shape[0]
-    S = np.array(np.tril(M) if u == "L" else np.triu(np.tril(M).T), order="F")
-    idx = np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
-    S[idx] = fill
-    return S
-
-
-def lower_of(F, u):
-    return np.tril(F) if u == "L" else np.triu(F).T
-
-
-def other_triangle_kept(F, S, u):
-    n = S.shape[0]
-    idx = np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
-    return np.array_equal(bits(F[idx]), bits(S[idx]))
-
-
-def desc(ch, N, B, dt, ncols=None):
-    nc = N if ncols is None else ncols
-    return ch.CHAMELEON_Desc_Create(None, chdt(ch, dt), B, B, B * B, N, nc, 0, 0, N, nc, 1, 1)
-
-
-def uplo(ch, u):
-    return ch.ChamLower if u == "L" else ch.ChamUpper
 
 
 def wdesc(ch, Wc, B, dt):
@@ -88,10 +48,10 @@ def wdesc(ch, Wc, B, dt):
 
 def apply(ch, A, Wc, B, depth, u="L", dt="d"):
     """-> (the lower triangle of W^T A W from the device, A after the call, A as stored)"""
-    S = stored(A.astype(npdt(dt)), u)
+    S = stored_lower(A.astype(npdt(dt)), u)
     da, dw = desc(ch, A.shape[0], B, dt), wdesc(ch, Wc, B, dt)
     da.from_lapack(S)
-    assert ch.CHAMELEON_drbt_apply_Tile(uplo(ch, u), da, dw, depth) == 0
+    assert ch.CHAMELEON_drbt_apply_Tile(uplo_code(ch, u), da, dw, depth) == 0
     F, W = da.to_lapack(), dw.to_lapack()
     ch.CHAMELEON_Desc_Destroy(da)
     ch.CHAMELEON_Desc_Destroy(dw)
@@ -135,38 +95,21 @@ def test_apply_integer_exact(cham, dt):
     assert np.array_equal(Lg, np.rint(Lg))
 
 
-def raw_image(d):
-    """the descriptor's stored fp64 tile image, padding included (through the HIP runtime this process has loaded)"""
-    import ctypes
-
-    ptr, nbytes = d.local_ptr()
-    path = next(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln)
-    hip = ctypes.CDLL(path)
-    out = np.empty(nbytes // 8, dtype=np.float64)
-    assert hip.hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), ctypes.c_size_t(nbytes), 2) == 0
-    return out
-
-
 def test_repeatable_and_padding(cham):
     """two calls give the same bits; a ragged order keeps the padding of the image bit for bit"""
     ch = cham
     n, B, nt, depth = 1000, 256, 4, 2
-    pad = np.zeros((nt * B, nt * B), dtype=bool)
-    pad[n:, :] = pad[:, n:] = True
+    pad = ragged_padding_mask(n, B, nt)
     A = family("zero_diag", n, 2)
     Wc = random_w(n, depth, 3)
     outs = []
-
-    def image(d):  # as one (nt B) x (nt B) matrix
-        return raw_image(d)[: nt * nt * B * B].reshape(nt, nt, B, B).transpose(1, 3, 0, 2).reshape(nt * B, nt * B)
-
     for _ in range(2):
         da, dw = desc(ch, n, B, "d"), wdesc(ch, Wc, B, "d")
-        da.from_lapack(stored(A, "L"))
-        before = image(da)
+        da.from_lapack(stored_lower(A, "L"))
+        before = image_matrix(da, nt, B, np.float64)
         assert ch.CHAMELEON_drbt_apply_Tile(ch.ChamLower, da, dw, depth) == 0
         outs.append(da.to_lapack())
-        after = image(da)
+        after = image_matrix(da, nt, B, np.float64)
         ch.CHAMELEON_Desc_Destroy(da)
         ch.CHAMELEON_Desc_Destroy(dw)
         assert np.array_equal(bits(after[pad]), bits(before[pad]))
@@ -176,29 +119,20 @@ def test_repeatable_and_padding(cham):
 def test_sub_matrix_view(cham):
     """a tile-aligned view of a device user buffer gives the whole-matrix descriptor's result; the user's tiles outside
     the view stay as they were"""
-    import torch
-
     ch = cham
-    mb, lt, oi, oj, vt, depth = 256, 5, 1, 2, 3, 2
-    lm, m = lt * mb, vt * mb
-    user = np.random.default_rng(16).standard_normal(lt * lt * mb * mb)
-    buf = torch.from_numpy(user.copy()).cuda()
+    uv, depth = UserView(ch), 2
+    mb, m = uv.mb, uv.m
     A = family("saddle", m, 6)
     Wc = random_w(m, depth, 7)
-    v = ch.CHAMELEON_Desc_Create(buf, ch.ChamRealDouble, mb, mb, mb * mb, lm, lm, oi * mb, oj * mb, m, m, 1, 1)
-    v.from_lapack(stored(A, "L"))
+    v = uv.view_desc()
+    v.from_lapack(stored_lower(A, "L"))
     dw = wdesc(ch, Wc, mb, "d")
     assert ch.CHAMELEON_drbt_apply_Tile(ch.ChamLower, v, dw, depth) == 0
     Lv = np.tril(v.to_lapack())
     ch.CHAMELEON_Desc_Destroy(v)
     ch.CHAMELEON_Desc_Destroy(dw)
     assert np.array_equal(bits(Lv), bits(rbt_sym(A, Wc, depth)))
-    now = buf.cpu().numpy().reshape(lt * lt, mb * mb)
-    before = user.reshape(lt * lt, mb * mb)
-    for J in range(lt):
-        for I in range(lt):
-            if not (oi <= I < oi + vt and oj <= J < oj + vt):
-                assert np.array_equal(now[I + J * lt], before[I + J * lt]), (I, J)
+    uv.outside_unchanged()
 
 
 @pytest.mark.parametrize("u", ["L", "U"])
@@ -210,13 +144,13 @@ def test_sytrf_rbt_seed_and_composition(cham, u, dt):
     ch = cham
     n, B, depth = 1024, 256, 2
     A = family("saddle", n, 31).astype(npdt(dt))
-    S = stored(A, u)
+    S = stored_lower(A, u)
 
     def run(seed, Win=None):
         da, dw = desc(ch, n, B, dt), desc(ch, n, B, dt, depth)
         da.from_lapack(S)
         dw.from_lapack(np.asfortranarray(np.full((n, depth), 7.0) if Win is None else Win))
-        info = ch.CHAMELEON_dsytrf_rbt_Tile(uplo(ch, u), da, dw, depth, seed)
+        info = ch.CHAMELEON_dsytrf_rbt_Tile(uplo_code(ch, u), da, dw, depth, seed)
         F, W, st = da.to_lapack(), dw.to_lapack(), ch.last_sytrf_stats()
         ch.CHAMELEON_Desc_Destroy(da)
         ch.CHAMELEON_Desc_Destroy(dw)
@@ -236,9 +170,9 @@ def test_sytrf_rbt_seed_and_composition(cham, u, dt):
     # the composition
     da, dw = desc(ch, n, B, dt), wdesc(ch, W, B, dt)
     da.from_lapack(S)
-    assert ch.CHAMELEON_drbt_apply_Tile(uplo(ch, u), da, dw, depth) == 0
+    assert ch.CHAMELEON_drbt_apply_Tile(uplo_code(ch, u), da, dw, depth) == 0
     assert np.array_equal(bits(lower_of(da.to_lapack(), u)), bits(rbt_sym(A, W, depth)))
-    assert ch.CHAMELEON_dsytrf_nopiv_Tile(uplo(ch, u), da) == 0
+    assert ch.CHAMELEON_dsytrf_nopiv_Tile(uplo_code(ch, u), da) == 0
     assert np.array_equal(bits(da.to_lapack()), bits(F))
     ch.CHAMELEON_Desc_Destroy(da)
     ch.CHAMELEON_Desc_Destroy(dw)
@@ -262,12 +196,12 @@ def test_sytrs_spd(cham, n, B, depth, u, dt):
     b = r.standard_normal((n, 3)).astype(npdt(dt))
     Wc = random_w(n, depth, n + depth, npdt(dt))
     da, dw, db = desc(ch, n, B, dt), wdesc(ch, Wc, B, dt), desc(ch, n, B, dt, 3)
-    da.from_lapack(stored(A, u))
+    da.from_lapack(stored_lower(A, u))
     db.from_lapack(np.asfortranarray(b))
-    assert ch.CHAMELEON_dsytrf_rbt_Tile(uplo(ch, u), da, dw, depth, 0) == 0
+    assert ch.CHAMELEON_dsytrf_rbt_Tile(uplo_code(ch, u), da, dw, depth, 0) == 0
     assert ch.last_sytrf_stats()["inertia"] == (n, 0)
     F0 = da.to_lapack()
-    assert ch.CHAMELEON_dsytrs_rbt_Tile(uplo(ch, u), da, dw, depth, db) == 0
+    assert ch.CHAMELEON_dsytrs_rbt_Tile(uplo_code(ch, u), da, dw, depth, db) == 0
     assert np.array_equal(bits(da.to_lapack()), bits(F0))
     assert np.array_equal(bits(dw.to_lapack()), bits(Wc))
     x = db.to_lapack()
@@ -301,12 +235,12 @@ def test_sysv_families(cham, name, n, B, depth, nrhs, u):
     # (the model itself stays inside the device's bounds on every case; its final berr is rounding noise of the
     # residual and moves with the BLAS that numpy runs on)
     assert m["info"] == 0 and 0 <= m["iter"] <= MAX_STEPS and m["berr"].max() <= BERR_U * U["d"]
-    S = stored(A, u)
+    S = stored_lower(A, u)
     # without the butterflies
     da, db = desc(ch, n, B, "d"), desc(ch, n, B, "d", nrhs)
     da.from_lapack(S)
     db.from_lapack(np.asfortranarray(b))
-    info0 = ch.CHAMELEON_dsysv_nopiv_Tile(uplo(ch, u), da, db)
+    info0 = ch.CHAMELEON_dsysv_nopiv_Tile(uplo_code(ch, u), da, db)
     be_nopiv = np.inf if info0 else backward_error(A, db.to_lapack(), b).max()
     ch.CHAMELEON_Desc_Destroy(da)
     ch.CHAMELEON_Desc_Destroy(db)
@@ -317,7 +251,7 @@ def test_sysv_families(cham, name, n, B, depth, nrhs, u):
     da.from_lapack(S)
     daf.from_lapack(np.asfortranarray(np.full((n, n), -7.0)))
     db.from_lapack(np.asfortranarray(b))
-    info, it, berr = ch.CHAMELEON_dsysv_rbt_Tile(uplo(ch, u), da, daf, dw, depth, 0, db, dx)
+    info, it, berr = ch.CHAMELEON_dsysv_rbt_Tile(uplo_code(ch, u), da, daf, dw, depth, 0, db, dx)
     x, AF = dx.to_lapack(), daf.to_lapack()
     st, rs = ch.last_sytrf_stats(), ch.last_rbt_stats()
     assert np.array_equal(bits(da.to_lapack()), bits(S)) and np.array_equal(bits(db.to_lapack()), bits(b))
@@ -333,8 +267,7 @@ def test_sysv_families(cham, name, n, B, depth, nrhs, u):
     assert max(berr) <= BERR_U * U["d"], max(berr) / U["d"]
     # what numpy measures (the two residuals differ by their own rounding, of the order of u, so both get the bound)
     assert be.max() <= BERR_U * U["d"], be.max() / U["d"]
-    idx = np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
-    assert np.all(AF[idx] == -7.0)  # the other triangle of AF
+    assert np.all(AF[other(n, u)] == -7.0)  # the other triangle of AF
     xr = np.linalg.solve(A, b)
     cond = np.linalg.cond(A, np.inf)
     ferr = (np.abs(x - xr).max(0) / np.abs(xr).max(0)).max()
@@ -415,7 +348,7 @@ def test_order_not_a_multiple_is_refused(cham, n, depth):
     ch = cham
     B = 128
     da, dw = desc(ch, n, B, "d"), desc(ch, n, B, "d", 2)
-    A = stored(family("randsym", n, 1), "L", 0.0)
+    A = stored_lower(family("randsym", n, 1), "L", 0.0)
     da.from_lapack(A)
     for call in (lambda: ch.CHAMELEON_drbt_apply_Tile(ch.ChamLower, da, dw, depth),
                  lambda: ch.CHAMELEON_dsytrf_rbt_Tile(ch.ChamLower, da, dw, depth, 1)):

@@ -37,6 +37,7 @@ import pytest
 import scipy.linalg.lapack as lapack
 
 import refine_model as rm
+from chol_testkit import bits, desc, stored_lower, uplo_code
 
 pytestmark = pytest.mark.gpu
 
@@ -44,19 +45,6 @@ SHAPES = [(1000, 192), (1024, 256)]
 NMAX = 57
 FERR_TOL = {"d": 1e-6, "s": 1e-4}
 RCOND_TOL = {"d": 1e-6, "s": 1e-4}
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
-
-
-def stored(M, u):
-    """the lower triangle of M (symmetric, or a Lower factor) stored in the `u` triangle, the other strict one NaN"""
-    n = M.shape[0]
-    S = np.array(np.tril(M) if u == "L" else np.tril(M).T, order="F")
-    S[np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)] = np.nan
-    return S
 
 
 def scaling(n, dt):
@@ -116,12 +104,10 @@ class Device:
     """the descriptors of one problem on the device: A and AF with the other strict triangle NaN"""
 
     def __init__(self, ch, N, T, u, dt, A, AF, B, X0=None, S=None):
-        self.ch, self.u = ch, ch.ChamLower if u == "L" else ch.ChamUpper
-        cdt = ch.ChamRealDouble if dt == "d" else ch.ChamRealFloat
+        self.ch, self.u = ch, uplo_code(ch, u)
         nrhs = B.shape[1]
-        mk = lambda nc: ch.CHAMELEON_Desc_Create(None, cdt, T, T, T * T, N, nc, 0, 0, N, nc, 1, 1)  # noqa: E731
-        self.dA, self.dAF, self.dS, self.dB, self.dX = mk(N), mk(N), mk(1), mk(nrhs), mk(nrhs)
-        self.A0, self.AF0, self.B0 = stored(A, u), stored(AF, u), np.asfortranarray(B)
+        self.dA, self.dAF, self.dS, self.dB, self.dX = (desc(ch, N, T, dt, nc) for nc in (N, N, 1, nrhs, nrhs))
+        self.A0, self.AF0, self.B0 = stored_lower(A, u), stored_lower(AF, u), np.asfortranarray(B)
         self.dA.from_lapack(self.A0)
         self.dAF.from_lapack(self.AF0)
         self.dB.from_lapack(self.B0)

@@ -9,24 +9,14 @@ import pytest
 import scipy.linalg
 import scipy.linalg.lapack as lapack
 
+from chol_testkit import (UserView, bits, desc, image_matrix, npdt, other_triangle_kept, pxq_refused,
+                          ragged_padding_mask, stored_lower, uplo_code)
+
 pytestmark = pytest.mark.gpu
 
 # max |C - ref| / (max |A| ||inv(L)||_2^2): about 10 x what was measured (the CPU model against scipy: 2-4e-16 in
 # fp64, 1-2e-7 in fp32)
 BOUND = {"d": 4e-15, "s": 2e-6}
-
-
-def npdt(dt):
-    return np.float64 if dt == "d" else np.float32
-
-
-def chdt(ch, dt):
-    return ch.ChamRealDouble if dt == "d" else ch.ChamRealFloat
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
 
 
 @functools.lru_cache(maxsize=None)
@@ -39,28 +29,15 @@ def problem(n, seed):
     return H + H.T, Bm, np.linalg.cholesky(Bm), float(np.linalg.eigvalsh(Bm)[0])
 
 
-def stored(M, u, fill=np.nan):
-    """the lower triangle of M (symmetric, or a Lower factor) stored in the `u` triangle, the other strict one = fill"""
-    n = M.shape[0]
-    S = np.array(np.tril(M) if u == "L" else np.triu(np.tril(M).T), order="F")
-    idx = np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
-    S[idx] = fill
-    return S
-
-
-def desc(ch, N, B, dt):
-    return ch.CHAMELEON_Desc_Create(None, chdt(ch, dt), B, B, B * B, N, N, 0, 0, N, N, 1, 1)
-
-
 def sygst(ch, A, L, B, u="L", dt="d", fill=np.nan, bfill=-7.0):
     """-> (info, C as Lower, A after the call, A as stored, B after the call, B as stored)"""
-    SA = stored(A.astype(npdt(dt)), u, fill)
-    SB = stored(L.astype(npdt(dt)), u, bfill)
+    SA = stored_lower(A.astype(npdt(dt)), u, fill)
+    SB = stored_lower(L.astype(npdt(dt)), u, bfill)
     n = A.shape[0]
     da, db = desc(ch, n, B, dt), desc(ch, n, B, dt)
     da.from_lapack(SA)
     db.from_lapack(SB)
-    info = ch.CHAMELEON_dsygst_Tile(1, ch.ChamLower if u == "L" else ch.ChamUpper, da, db)
+    info = ch.CHAMELEON_dsygst_Tile(1, uplo_code(ch, u), da, db)
     F, FB = da.to_lapack(), db.to_lapack()
     ch.CHAMELEON_Desc_Destroy(da)
     ch.CHAMELEON_Desc_Destroy(db)
@@ -73,12 +50,6 @@ def reference(A, L, dt):
     c, info = fn(A.astype(npdt(dt)), L.astype(npdt(dt)), itype=1, lower=1)
     assert info == 0
     return np.tril(c)
-
-
-def other_triangle_kept(F, S, u):
-    n = S.shape[0]
-    idx = np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
-    return np.array_equal(bits(F[idx]), bits(S[idx]))
 
 
 @pytest.mark.parametrize("n,B", [(1000, 128), (1100, 192), (1536, 256), (2100, 512), (2048, 1024), (300, 512),
@@ -141,40 +112,22 @@ def test_exact_integer(cham, n, B, u, dt):
     assert np.array_equal(C, np.tril(M).astype(npdt(dt)))
 
 
-def raw_image(d):
-    """the descriptor's stored fp64 tile image, padding included (through the HIP runtime this process has loaded)"""
-    import ctypes
-
-    ptr, nbytes = d.local_ptr()
-    path = next(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln)
-    hip = ctypes.CDLL(path)
-    out = np.empty(nbytes // 8, dtype=np.float64)
-    assert hip.hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), ctypes.c_size_t(nbytes), 2) == 0
-    return out
-
-
 def test_repeatable_and_padding(cham):
     """two calls give the same bits; a ragged order keeps the padding of A's image (the identity on the diagonal,
     zeros elsewhere) bit for bit"""
     ch = cham
     n, B, nt = 1000, 256, 4
-    k = n - (nt - 1) * B  # rows / columns k .. B-1 of the last tile row / column are padding
-    pad = np.zeros((nt * B, nt * B), dtype=bool)
-    pad[(nt - 1) * B + k:, :] = pad[:, (nt - 1) * B + k:] = True
+    pad = ragged_padding_mask(n, B, nt)
     A, _, L, _ = problem(n, 5)
     outs = []
-
-    def image(d):  # as one (nt B) x (nt B) matrix
-        return raw_image(d)[: nt * nt * B * B].reshape(nt, nt, B, B).transpose(1, 3, 0, 2).reshape(nt * B, nt * B)
-
     for _ in range(2):
         da, db = desc(ch, n, B, "d"), desc(ch, n, B, "d")
-        da.from_lapack(stored(A, "L"))
-        db.from_lapack(stored(L, "L"))
-        before = image(da)
+        da.from_lapack(stored_lower(A, "L"))
+        db.from_lapack(stored_lower(L, "L"))
+        before = image_matrix(da, nt, B, np.float64)
         assert ch.CHAMELEON_dsygst_Tile(1, ch.ChamLower, da, db) == 0
         outs.append(da.to_lapack())
-        after = image(da)
+        after = image_matrix(da, nt, B, np.float64)
         ch.CHAMELEON_Desc_Destroy(da)
         ch.CHAMELEON_Desc_Destroy(db)
         assert np.array_equal(bits(after[pad]), bits(before[pad]))
@@ -185,30 +138,21 @@ def test_repeatable_and_padding(cham):
 def test_sub_matrix_view(cham):
     """a tile-aligned view of a device user buffer gives the whole-matrix descriptor's result; the user's tiles
     outside the view stay as they were"""
-    import torch
-
     ch = cham
-    mb, lt, oi, oj, vt = 256, 5, 1, 2, 3
-    lm, m = lt * mb, vt * mb
-    user = np.random.default_rng(16).standard_normal(lt * lt * mb * mb)
-    buf = torch.from_numpy(user.copy()).cuda()
+    uv = UserView(ch)
+    mb, m = uv.mb, uv.m
     A, _, L, _ = problem(m, 6)
-    v = ch.CHAMELEON_Desc_Create(buf, ch.ChamRealDouble, mb, mb, mb * mb, lm, lm, oi * mb, oj * mb, m, m, 1, 1)
-    v.from_lapack(stored(A, "L"))
+    v = uv.view_desc()
+    v.from_lapack(stored_lower(A, "L"))
     db = desc(ch, m, mb, "d")
-    db.from_lapack(stored(L, "L"))
+    db.from_lapack(stored_lower(L, "L"))
     assert ch.CHAMELEON_dsygst_Tile(1, ch.ChamLower, v, db) == 0
     Cv = np.tril(v.to_lapack())
     ch.CHAMELEON_Desc_Destroy(v)
     ch.CHAMELEON_Desc_Destroy(db)
     _, C, *_ = sygst(ch, A, L, mb)
     assert np.array_equal(bits(Cv), bits(C))
-    now = buf.cpu().numpy().reshape(lt * lt, mb * mb)
-    before = user.reshape(lt * lt, mb * mb)
-    for J in range(lt):
-        for I in range(lt):
-            if not (oi <= I < oi + vt and oj <= J < oj + vt):
-                assert np.array_equal(now[I + J * lt], before[I + J * lt]), (I, J)
+    uv.outside_unchanged()
 
 
 @pytest.mark.parametrize("u", ["L", "U"])
@@ -253,18 +197,5 @@ def test_argument_errors(cham):
 
 
 def test_pxq_descriptor_is_not_supported(cham):
-    from dense_linear_app_amd._lib import lib
-
     ch = cham
-    lib().chol_set_transport(None)
-    ch.set_rank(0, 2)
-    try:
-        da = ch.CHAMELEON_Desc_Create(None, ch.ChamRealDouble, 256, 256, 256 * 256, 1024, 1024, 0, 0, 1024, 1024, 1, 2)
-        db = ch.CHAMELEON_Desc_Create(None, ch.ChamRealDouble, 256, 256, 256 * 256, 1024, 1024, 0, 0, 1024, 1024, 1, 2)
-        with pytest.raises(ch.CholmiError) as e:
-            ch.CHAMELEON_dsygst_Tile(1, ch.ChamLower, da, db)
-        assert e.value.code == -104  # CHOL_ERR_NOT_SUPPORTED
-        ch.CHAMELEON_Desc_Destroy(da)
-        ch.CHAMELEON_Desc_Destroy(db)
-    finally:
-        ch.set_rank(0, 1)
+    pxq_refused(ch, 2, lambda da, db: ch.CHAMELEON_dsygst_Tile(1, ch.ChamLower, da, db))

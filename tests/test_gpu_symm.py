@@ -21,57 +21,17 @@ numpy's own product in the dtype sits at 0.003-0.016 of it on these inputs and t
 (n = 100), so a failure is a bug.  Columns 0, 7 and 128
 of an nrhs = 300 call equal the same columns of calls with nrhs = 1, 8 and 129 bit for bit, and a repeated call returns
 the same bits."""
-import ctypes
 import functools
 
 import numpy as np
 import pytest
 
 import symm_model as sm
+from chol_testkit import bits, desc, gamma, npdt, put_image, pxq_refused, raw_image, stored_sym
 
 pytestmark = pytest.mark.gpu
 
-U = {"d": 2.0 ** -53, "s": 2.0 ** -24}
 NS = -104  # CHOL_ERR_NOT_SUPPORTED
-
-
-def gamma(k, dt):
-    return k * U[dt] / (1 - k * U[dt])
-
-
-def chdt(ch, dt):
-    return ch.ChamRealDouble if dt == "d" else ch.ChamRealFloat
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
-
-
-def desc(ch, n, tile, dt, cols=None):
-    cols = n if cols is None else cols
-    return ch.CHAMELEON_Desc_Create(None, chdt(ch, dt), tile, tile, tile * tile, n, cols, 0, 0, n, cols, 1, 1)
-
-
-@functools.lru_cache(maxsize=None)
-def _hip():
-    path = next(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln)
-    return ctypes.CDLL(path)
-
-
-def raw_image(d):
-    """the descriptor's stored tile image, padding included (through the HIP runtime this process has loaded)"""
-    ptr, nbytes = d.local_ptr()
-    out = np.empty(nbytes, dtype=np.uint8)
-    assert _hip().hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), ctypes.c_size_t(nbytes), 2) == 0
-    return out
-
-
-def put_image(d, img):
-    ptr, nbytes = d.local_ptr()
-    assert img.nbytes == nbytes
-    assert _hip().hipMemcpy(ctypes.c_void_p(ptr), ctypes.c_void_p(img.ctypes.data), ctypes.c_size_t(nbytes), 1) == 0
-
 
 _PAD = {}
 
@@ -83,9 +43,9 @@ def padding_of(ch, n, tile, dt, cols):
     if key not in _PAD:
         d = desc(ch, n, tile, dt, cols)
         d.from_lapack(np.full((n, cols), 1.0, order="F"))
-        one = raw_image(d).view(sm.npdt(dt))
+        one = raw_image(d).view(npdt(dt))
         d.from_lapack(np.full((n, cols), 2.0, order="F"))
-        two = raw_image(d).view(sm.npdt(dt))
+        two = raw_image(d).view(npdt(dt))
         ch.CHAMELEON_Desc_Destroy(d)
         pad = one == two
         assert (~pad).sum() == n * cols
@@ -101,8 +61,8 @@ class Image:
         n, cols = M.shape
         self.pad = padding_of(ch, n, tile, dt, cols)
         self.d = desc(ch, n, tile, dt, cols)
-        self.d.from_lapack(np.asfortranarray(M, dtype=sm.npdt(dt)))
-        img = raw_image(self.d).view(sm.npdt(dt)).copy()
+        self.d.from_lapack(np.asfortranarray(M, dtype=npdt(dt)))
+        img = raw_image(self.d).view(npdt(dt)).copy()
         img[self.pad] = np.nan
         put_image(self.d, img.view(np.uint8))
         self.before = raw_image(self.d)
@@ -147,7 +107,7 @@ class Sym:
 
 
 def same_bits(got, want, dt, what):
-    want = np.asarray(want).astype(sm.npdt(dt))
+    want = np.asarray(want).astype(npdt(dt))
     assert got.dtype == want.dtype and np.array_equal(bits(got), bits(want)), what
 
 
@@ -160,7 +120,7 @@ def test_exact(cham, n, tile, dt, u):
     A, B, C = sm.exact_problem(n)
     AB = A @ B
     nan = np.full_like(C, np.nan)
-    with Sym(cham, sm.stored(A, u), tile, u, dt) as S:
+    with Sym(cham, stored_sym(A, u), tile, u, dt) as S:
         for nrhs in sm.NRHS:
             for alpha, beta in sm.SCALARS:
                 got = S.symm(alpha, B[:, :nrhs], beta, (nan if beta == 0 else C)[:, :nrhs])
@@ -177,7 +137,7 @@ def test_exact(cham, n, tile, dt, u):
 def random_reference(n, dt):
     """-> the inputs rounded to dt, alpha A B + beta C0 in np.longdouble and |alpha| |A| |B| + |beta| |C0| (read-only)"""
     alpha, beta = sm.RANDOM_SCALARS
-    A, B, C = (a.astype(sm.npdt(dt)) for a in sm.random_problem(n))
+    A, B, C = (a.astype(npdt(dt)) for a in sm.random_problem(n))
     hi = [a.astype(np.longdouble) for a in (A, B, C)]
     ref = np.longdouble(alpha) * (hi[0] @ hi[1]) + np.longdouble(beta) * hi[2]
     scale = abs(alpha) * (np.abs(hi[0]) @ np.abs(hi[1])) + abs(beta) * np.abs(hi[2])
@@ -191,7 +151,7 @@ def test_random_family_and_columns(cham, n, tile, dt, u):
     alpha, beta = sm.RANDOM_SCALARS
     A, B, C, ref, scale = random_reference(n, dt)
     got = {}
-    with Sym(cham, sm.stored(A, u), tile, u, dt) as S:
+    with Sym(cham, stored_sym(A, u), tile, u, dt) as S:
         for nrhs in sm.NRHS:
             got[nrhs] = S.symm(alpha, B[:, :nrhs], beta, C[:, :nrhs])
             err = np.abs(got[nrhs].astype(np.longdouble) - ref[:, :nrhs])
@@ -220,7 +180,7 @@ def test_c_as_a_sub_matrix_view(cham):
     v = ch.CHAMELEON_Desc_Create(buf, ch.ChamRealDouble, mb, mb, mb * mb, lm, lm, oi * mb, oj * mb, n, n, 1, 1)
     v.from_lapack(np.asfortranarray(C))
     held = buf.cpu().numpy().copy()
-    with Sym(ch, sm.stored(A, "L"), mb, "L", "d") as S:
+    with Sym(ch, stored_sym(A, "L"), mb, "L", "d") as S:
         plain = S.symm(-2.0, B, 1.0, C)
         b = Image(ch, B, mb, "d")
         assert ch.CHAMELEON_dsymm_Tile(ch.ChamLeft, ch.ChamLower, -2.0, S.a.d, b.d, 1.0, v) == 0
@@ -296,28 +256,15 @@ def test_argument_errors(cham):
 
 
 def test_pxq_descriptor_is_not_supported(cham):
-    from dense_linear_app_amd._lib import lib
-
     ch = cham
-    lib().chol_set_transport(None)
-    ch.set_rank(0, 2)
-    try:
-        mk = lambda: ch.CHAMELEON_Desc_Create(None, ch.ChamRealDouble, 256, 256, 256 * 256, 1024, 1024, 0, 0, 1024, 1024, 1, 2)
-        da, db, dc = mk(), mk(), mk()
-        with pytest.raises(ch.CholmiError) as e:
-            ch.CHAMELEON_dsymm_Tile(ch.ChamLeft, ch.ChamLower, 1.0, da, db, 0.0, dc)
-        assert e.value.code == NS
-        for d in (da, db, dc):
-            ch.CHAMELEON_Desc_Destroy(d)
-    finally:
-        ch.set_rank(0, 1)
+    pxq_refused(ch, 3, lambda da, db, dc: ch.CHAMELEON_dsymm_Tile(ch.ChamLeft, ch.ChamLower, 1.0, da, db, 0.0, dc))
 
 
 def test_stats_return_what_the_call_did(cham):
     ch = cham
     n, tile = 384, 128
     A, B, C = sm.exact_problem(n)
-    with Sym(ch, sm.stored(A, "L"), tile, "L", "d") as S:
+    with Sym(ch, stored_sym(A, "L"), tile, "L", "d") as S:
         for nrhs, width in ((1, 16), (8, 16), (129, 128), (300, 128)):
             S.symm(1.0, B[:, :nrhs], 0.0, C[:, :nrhs])
             st = ch.last_symm_stats()

@@ -20,42 +20,16 @@ import functools
 import numpy as np
 import pytest
 
-from sytrf_model import growth_scale, inertia, residual, split, sytrf_model, sytrs_model
+from chol_testkit import (U, UserView, bits, desc, image_matrix, npdt, other_triangle_kept, pxq_refused,
+                          ragged_padding_mask, stored_lower, uplo_code)
+from sytrf_model import growth_scale, inertia, quasi_definite, residual, split, sytrf_model, sytrs_model
 
 pytestmark = pytest.mark.gpu
 
 RESID_U = 160.0  # 10 x 16.0 u, the model's largest residual (above)
 SOLVE_U = 14.6   # 10 x 1.46 u, the model's largest backward error (above)
-U = {"d": 2.0 ** -53, "s": 2.0 ** -24}
 
-
-def npdt(dt):
-    return np.float64 if dt == "d" else np.float32
-
-
-def chdt(ch, dt):
-    return ch.ChamRealDouble if dt == "d" else ch.ChamRealFloat
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
-
-
-@functools.lru_cache(maxsize=None)
-def quasi_definite(n, m, seed, perm=False):
-    """[[H, J^T], [J, -C]], H = G G^T / 2n with G n x 2n standard normal, C likewise of order m, J = randn / sqrt(n)"""
-    r = np.random.default_rng(seed)
-    G = r.standard_normal((n, 2 * n))
-    H = G @ G.T / (2 * n)
-    G = r.standard_normal((m, 2 * m))
-    C = G @ G.T / (2 * m)
-    J = r.standard_normal((m, n)) / np.sqrt(n)
-    K = np.block([[H, J.T], [J, -C]])
-    if perm:
-        p = r.permutation(n + m)
-        K = K[np.ix_(p, p)]
-    return K
+quasi_definite = functools.lru_cache(maxsize=None)(quasi_definite)  # (one array per case here: copy before writing)
 
 
 @functools.lru_cache(maxsize=None)
@@ -63,39 +37,15 @@ def model(n, m, seed, perm, B, dt):
     return sytrf_model(quasi_definite(n, m, seed, perm).astype(npdt(dt)), B)
 
 
-def stored(M, u, fill=np.nan):
-    """the lower triangle of M (symmetric, or a Lower factor) stored in the `u` triangle, the other strict one = fill"""
-    n = M.shape[0]
-    S = np.array(np.tril(M) if u == "L" else np.triu(np.tril(M).T), order="F")
-    idx = np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
-    S[idx] = fill
-    return S
-
-
-def desc(ch, N, B, dt, ncols=None):
-    nc = N if ncols is None else ncols
-    return ch.CHAMELEON_Desc_Create(None, chdt(ch, dt), B, B, B * B, N, nc, 0, 0, N, nc, 1, 1)
-
-
-def uplo(ch, u):
-    return ch.ChamLower if u == "L" else ch.ChamUpper
-
-
 def sytrf(ch, K, B, u="L", dt="d", fill=np.nan):
     """-> (info, the factor as Lower storage (D on the diagonal, L below), A after the call, A as stored, stats)"""
-    S = stored(K.astype(npdt(dt)), u, fill)
+    S = stored_lower(K.astype(npdt(dt)), u, fill)
     d = desc(ch, K.shape[0], B, dt)
     d.from_lapack(S)
-    info = ch.CHAMELEON_dsytrf_nopiv_Tile(uplo(ch, u), d)
+    info = ch.CHAMELEON_dsytrf_nopiv_Tile(uplo_code(ch, u), d)
     F = d.to_lapack()
     ch.CHAMELEON_Desc_Destroy(d)
     return info, (np.tril(F) if u == "L" else np.triu(F).T), F, S, ch.last_sytrf_stats()
-
-
-def other_triangle_kept(F, S, u):
-    n = S.shape[0]
-    idx = np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
-    return np.array_equal(bits(F[idx]), bits(S[idx]))
 
 
 def check_factor(Fg, K, Fm, dt, what=""):
@@ -200,16 +150,16 @@ def test_solve(cham, nrhs, u, dt):
     bem = backward_error(K, sytrs_model(Fm, b), b.astype(np.float64))
     for call in ("sytrs", "sysv"):
         da, db = desc(ch, N, B, dt), desc(ch, N, B, dt, nrhs)
-        S = stored(K, u)
+        S = stored_lower(K, u)
         da.from_lapack(S)
         db.from_lapack(np.asfortranarray(b))
         if call == "sytrs":
-            assert ch.CHAMELEON_dsytrf_nopiv_Tile(uplo(ch, u), da) == 0
+            assert ch.CHAMELEON_dsytrf_nopiv_Tile(uplo_code(ch, u), da) == 0
             F0 = da.to_lapack()
-            assert ch.CHAMELEON_dsytrs_nopiv_Tile(uplo(ch, u), da, db) == 0
+            assert ch.CHAMELEON_dsytrs_nopiv_Tile(uplo_code(ch, u), da, db) == 0
             assert np.array_equal(bits(da.to_lapack()), bits(F0))  # A only read
         else:
-            assert ch.CHAMELEON_dsysv_nopiv_Tile(uplo(ch, u), da, db) == 0
+            assert ch.CHAMELEON_dsysv_nopiv_Tile(uplo_code(ch, u), da, db) == 0
         x = db.to_lapack()
         ch.CHAMELEON_Desc_Destroy(da)
         ch.CHAMELEON_Desc_Destroy(db)
@@ -241,10 +191,10 @@ def test_zero_pivot(cham, at, u, dt):
     assert info == at + 2
     N = K.shape[0]
     da, db = desc(ch, N, 128, dt), desc(ch, N, 128, dt, 3)
-    da.from_lapack(stored(K.astype(npdt(dt)), u))
+    da.from_lapack(stored_lower(K.astype(npdt(dt)), u))
     b = np.asfortranarray(np.random.default_rng(4).standard_normal((N, 3)).astype(npdt(dt)))
     db.from_lapack(b)
-    assert ch.CHAMELEON_dsysv_nopiv_Tile(uplo(ch, u), da, db) == at + 2
+    assert ch.CHAMELEON_dsysv_nopiv_Tile(uplo_code(ch, u), da, db) == at + 2
     assert np.array_equal(bits(db.to_lapack()), bits(b))
     ch.CHAMELEON_Desc_Destroy(da)
     ch.CHAMELEON_Desc_Destroy(db)
@@ -280,71 +230,44 @@ def test_non_finite_and_order_one(cham, dt):
     ch.CHAMELEON_Desc_Destroy(db)
 
 
-def raw_image(d):
-    """the descriptor's stored fp64 tile image, padding included (through the HIP runtime this process has loaded)"""
-    import ctypes
-
-    ptr, nbytes = d.local_ptr()
-    path = next(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln)
-    hip = ctypes.CDLL(path)
-    out = np.empty(nbytes // 8, dtype=np.float64)
-    assert hip.hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), ctypes.c_size_t(nbytes), 2) == 0
-    return out
-
-
 def test_repeatable_and_padding(cham):
     """two calls give the same bits; a ragged order keeps the padding of the image (the identity on the diagonal,
     zeros elsewhere) bit for bit"""
     ch = cham
     n, B, nt = 1000, 256, 4
-    k = n - (nt - 1) * B
-    pad = np.zeros((nt * B, nt * B), dtype=bool)
-    pad[(nt - 1) * B + k:, :] = pad[:, (nt - 1) * B + k:] = True
+    pad = ragged_padding_mask(n, B, nt)
     K = quasi_definite(600, 400, 21, True)
     outs = []
-
-    def image(d):  # as one (nt B) x (nt B) matrix
-        return raw_image(d)[: nt * nt * B * B].reshape(nt, nt, B, B).transpose(1, 3, 0, 2).reshape(nt * B, nt * B)
-
     for _ in range(2):
         da = desc(ch, n, B, "d")
-        da.from_lapack(stored(K, "L"))
-        before = image(da)
+        da.from_lapack(stored_lower(K, "L"))
+        before = image_matrix(da, nt, B, np.float64)
         assert ch.CHAMELEON_dsytrf_nopiv_Tile(ch.ChamLower, da) == 0
         outs.append(da.to_lapack())
-        after = image(da)
+        after = image_matrix(da, nt, B, np.float64)
         ch.CHAMELEON_Desc_Destroy(da)
         assert np.array_equal(bits(after[pad]), bits(before[pad]))
         assert np.array_equal(after[n:, n:], np.eye(nt * B - n)) and not np.any(after[n:, :n])
     assert np.array_equal(bits(outs[0]), bits(outs[1]))
-    assert other_triangle_kept(outs[0], stored(K, "L"), "L")
+    assert other_triangle_kept(outs[0], stored_lower(K, "L"), "L")
 
 
 def test_sub_matrix_view(cham):
     """a tile-aligned view of a device user buffer gives the whole-matrix descriptor's result; the user's tiles
     outside the view stay as they were"""
-    import torch
-
     ch = cham
-    mb, lt, oi, oj, vt = 256, 5, 1, 2, 3
-    lm, m = lt * mb, vt * mb
-    user = np.random.default_rng(16).standard_normal(lt * lt * mb * mb)
-    buf = torch.from_numpy(user.copy()).cuda()
+    uv = UserView(ch)
+    mb = uv.mb
     K = quasi_definite(500, 268, 6, True)
-    v = ch.CHAMELEON_Desc_Create(buf, ch.ChamRealDouble, mb, mb, mb * mb, lm, lm, oi * mb, oj * mb, m, m, 1, 1)
-    v.from_lapack(stored(K, "L"))
+    v = uv.view_desc()
+    v.from_lapack(stored_lower(K, "L"))
     assert ch.CHAMELEON_dsytrf_nopiv_Tile(ch.ChamLower, v) == 0
     Fv = np.tril(v.to_lapack())
     ch.CHAMELEON_Desc_Destroy(v)
     _, Fg, *_ = sytrf(ch, K, mb)
     assert np.array_equal(bits(Fv), bits(Fg))
     check_factor(Fv, K, sytrf_model(K, mb)[0], "d", "view")
-    now = buf.cpu().numpy().reshape(lt * lt, mb * mb)
-    before = user.reshape(lt * lt, mb * mb)
-    for J in range(lt):
-        for I in range(lt):
-            if not (oi <= I < oi + vt and oj <= J < oj + vt):
-                assert np.array_equal(now[I + J * lt], before[I + J * lt]), (I, J)
+    uv.outside_unchanged()
 
 
 def test_potrf_still_stops_at_the_first_negative_pivot(cham):
@@ -352,7 +275,7 @@ def test_potrf_still_stops_at_the_first_negative_pivot(cham):
     ch = cham
     n, m, B = 600, 424, 128
     d = desc(ch, n + m, B, "d")
-    d.from_lapack(stored(quasi_definite(n, m, n + m + B), "L", 0.0))
+    d.from_lapack(stored_lower(quasi_definite(n, m, n + m + B), "L", 0.0))
     assert ch.CHAMELEON_dpotrf_Tile(ch.ChamLower, d) == n + 1
     ch.CHAMELEON_Desc_Destroy(d)
     assert sytrf(ch, quasi_definite(n, m, n + m + B), B)[0] == 0  # ... where sytrf_nopiv goes through
@@ -367,7 +290,7 @@ def test_spd_matches_potrf(cham, dt):
     info, Fg, _, _, st = sytrf(ch, H, B, "L", dt)
     assert info == 0 and st["inertia"] == (n, 0)
     d = desc(ch, n, B, dt)
-    d.from_lapack(stored(H.astype(npdt(dt)), "L", 0.0))
+    d.from_lapack(stored_lower(H.astype(npdt(dt)), "L", 0.0))
     assert ch.CHAMELEON_dpotrf_Tile(ch.ChamLower, d) == 0
     Lc = np.tril(d.to_lapack()).astype(np.float64)
     ch.CHAMELEON_Desc_Destroy(d)
@@ -403,19 +326,8 @@ def test_argument_errors(cham):
 
 
 def test_pxq_descriptor_is_not_supported(cham):
-    from dense_linear_app_amd._lib import lib
-
     ch = cham
-    lib().chol_set_transport(None)
-    ch.set_rank(0, 2)
-    try:
-        da = ch.CHAMELEON_Desc_Create(None, ch.ChamRealDouble, 256, 256, 256 * 256, 1024, 1024, 0, 0, 1024, 1024, 1, 2)
-        with pytest.raises(ch.CholmiError) as e:
-            ch.CHAMELEON_dsytrf_nopiv_Tile(ch.ChamLower, da)
-        assert e.value.code == -104  # CHOL_ERR_NOT_SUPPORTED
-        ch.CHAMELEON_Desc_Destroy(da)
-    finally:
-        ch.set_rank(0, 1)
+    pxq_refused(ch, 1, lambda da: ch.CHAMELEON_dsytrf_nopiv_Tile(ch.ChamLower, da))
 
 
 def test_large(cham):

@@ -18,62 +18,19 @@ kappa(L) about 6), with u = 2^-53 / 2^-24 and gamma_k = k u / (1 - k u):
           inputs in fp64 (np.longdouble for fp64): the product bound for any order, with or without fma
   logdet  |value - ref| <= gamma_{n+4} 2 sum |log L_jj|, ref from the stored diagonal in np.longdouble: a log within
           1 ulp and n - 1 additions."""
-import ctypes
 import functools
 
 import numpy as np
 import pytest
 
 import trtrs_model as tm
+from chol_testkit import U, UserView, bits, desc, gamma, npdt, pxq_refused, raw_image, stored_lower, uplo_code
 
 pytestmark = pytest.mark.gpu
 
-U = {"d": 2.0 ** -53, "s": 2.0 ** -24}
-
-
-def gamma(k, dt):
-    return k * U[dt] / (1 - k * U[dt])
-
-
-def npdt(dt):
-    return np.float64 if dt == "d" else np.float32
-
-
-def chdt(ch, dt):
-    return ch.ChamRealDouble if dt == "d" else ch.ChamRealFloat
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32)
-
-
-def stored(M, u, fill=np.nan):
-    """the Lower factor M stored in the `u` triangle, the other strict one = fill"""
-    n = M.shape[0]
-    S = np.array(np.tril(M) if u == "L" else np.tril(M).T, order="F")
-    idx = np.triu_indices(n, 1) if u == "L" else np.tril_indices(n, -1)
-    S[idx] = fill
-    return S
-
-
-def desc(ch, n, B, dt, r=None):
-    r = n if r is None else r
-    return ch.CHAMELEON_Desc_Create(None, chdt(ch, dt), B, B, B * B, n, r, 0, 0, n, r, 1, 1)
-
 
 def codes(ch, u, t):
-    return (ch.ChamLower if u == "L" else ch.ChamUpper), (ch.ChamNoTrans if t == "N" else ch.ChamTrans)
-
-
-def raw_image(d):
-    """the descriptor's stored tile image, padding included (through the HIP runtime this process has loaded)"""
-    ptr, nbytes = d.local_ptr()
-    path = next(ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln)
-    hip = ctypes.CDLL(path)
-    out = np.empty(nbytes, dtype=np.uint8)
-    assert hip.hipMemcpy(ctypes.c_void_p(out.ctypes.data), ctypes.c_void_p(ptr), ctypes.c_size_t(nbytes), 2) == 0
-    return out
+    return uplo_code(ch, u), (ch.ChamNoTrans if t == "N" else ch.ChamTrans)
 
 
 class Factor:
@@ -83,7 +40,7 @@ class Factor:
     def __init__(self, ch, L, B, u, dt):
         self.ch, self.u, self.dt, self.B, self.n = ch, u, dt, B, L.shape[0]
         self.d = desc(ch, self.n, B, dt)
-        self.d.from_lapack(stored(L.astype(npdt(dt)), u))
+        self.d.from_lapack(stored_lower(L.astype(npdt(dt)), u))
         self.before = raw_image(self.d)
 
     def __enter__(self):
@@ -240,7 +197,7 @@ def test_logdet_info(cham):
         for j, v in planted:
             M[j, j] = v
         d = desc(ch, n, B, "d")
-        d.from_lapack(stored(M, "L"))
+        d.from_lapack(stored_lower(M, "L"))
         info, _ = ch.CHAMELEON_dlogdet_Tile(d)
         ch.CHAMELEON_Desc_Destroy(d)
         assert info == min(j for j, _ in planted) + 1
@@ -283,8 +240,8 @@ def test_eigenvectors_of_the_generalized_problem(cham):
     A = H + H.T
     L = np.linalg.cholesky(Bm)
     da, db = desc(ch, n, B, "d"), desc(ch, n, B, "d")
-    da.from_lapack(stored(A, "L", 0.0))
-    db.from_lapack(stored(L, "L"))
+    da.from_lapack(stored_lower(A, "L", 0.0))
+    db.from_lapack(stored_lower(L, "L"))
     assert ch.CHAMELEON_dsygst_Tile(1, ch.ChamLower, da, db) == 0
     C = np.tril(da.to_lapack())
     lam, Yv = np.linalg.eigh(C + np.tril(C, -1).T)
@@ -306,16 +263,12 @@ def test_eigenvectors_of_the_generalized_problem(cham):
 def test_sub_matrix_view(cham):
     """a tile-aligned view of a device user buffer as A gives the whole-matrix descriptor's results bit for bit; the
     user's buffer stays as it was, all of it"""
-    import torch
-
     ch = cham
-    mb, lt, oi, oj, vt = 256, 5, 1, 2, 3
-    lm, m = lt * mb, vt * mb
-    user = np.random.default_rng(16).standard_normal(lt * lt * mb * mb)
-    buf = torch.from_numpy(user.copy()).cuda()
+    uv = UserView(ch)
+    mb, m, buf = uv.mb, uv.m, uv.buf
     L, R = rounded(m, "d")
-    v = ch.CHAMELEON_Desc_Create(buf, ch.ChamRealDouble, mb, mb, mb * mb, lm, lm, oi * mb, oj * mb, m, m, 1, 1)
-    v.from_lapack(stored(L, "L"))
+    v = uv.view_desc()
+    v.from_lapack(stored_lower(L, "L"))
     held = buf.cpu().numpy().copy()
     with Factor(ch, L, mb, "L", "d") as F:
         for nrhs in (3, tm.NARROW + 1):
@@ -408,22 +361,9 @@ def test_argument_errors(cham):
 
 
 def test_pxq_descriptor_is_not_supported(cham):
-    from dense_linear_app_amd._lib import lib
-
     ch = cham
-    lib().chol_set_transport(None)
-    ch.set_rank(0, 2)
-    try:
-        mk = lambda: ch.CHAMELEON_Desc_Create(None, ch.ChamRealDouble, 256, 256, 256 * 256, 1024, 1024, 0, 0, 1024, 1024, 1, 2)
-        da, db = mk(), mk()
-        calls = [lambda: ch.CHAMELEON_dtrtrs_Tile(ch.ChamLower, ch.ChamNoTrans, ch.ChamNonUnit, da, db),
-                 lambda: ch.CHAMELEON_dtrmm_Tile(ch.ChamLeft, ch.ChamLower, ch.ChamNoTrans, ch.ChamNonUnit, 1.0, da, db),
-                 lambda: ch.CHAMELEON_dlogdet_Tile(da)]
-        for fn in calls:
-            with pytest.raises(ch.CholmiError) as e:
-                fn()
-            assert e.value.code == -104  # CHOL_ERR_NOT_SUPPORTED
-        ch.CHAMELEON_Desc_Destroy(da)
-        ch.CHAMELEON_Desc_Destroy(db)
-    finally:
-        ch.set_rank(0, 1)
+    pxq_refused(
+        ch, 2,
+        lambda da, db: ch.CHAMELEON_dtrtrs_Tile(ch.ChamLower, ch.ChamNoTrans, ch.ChamNonUnit, da, db),
+        lambda da, db: ch.CHAMELEON_dtrmm_Tile(ch.ChamLeft, ch.ChamLower, ch.ChamNoTrans, ch.ChamNonUnit, 1.0, da, db),
+        lambda da, db: ch.CHAMELEON_dlogdet_Tile(da))

@@ -3,7 +3,8 @@ wrappers and ABI symbols exist and every entry point refuses to run before chol_
 test_gpu_pocon.py."""
 import pytest
 
-from dense_linear_app_amd import _lib, chameleon as ch
+from chol_testkit import assert_before_init_refused, assert_symbols_exported
+from dense_linear_app_amd import chameleon as ch
 
 SYMBOLS = ["chol_lansy_tile", "chol_pocon_tile", "chol_last_pocon_stats"]
 
@@ -13,15 +14,12 @@ def test_wrappers_exist():
         for p in "ds":
             assert callable(getattr(ch, f"CHAMELEON_{p}{name}_Tile"))
     assert callable(ch.last_pocon_stats)
-    for s in SYMBOLS:
-        assert s in _lib.abi_symbols()
+    assert_symbols_exported(SYMBOLS)
 
 
 @pytest.mark.parametrize("sym", SYMBOLS)
 def test_before_init_is_refused(sym):
-    L = _lib.lib()
     args = {"chol_lansy_tile": (ch.ChamOneNorm, ch.ChamLower, None, None),
             "chol_pocon_tile": (ch.ChamLower, None, 1.0, None),
             "chol_last_pocon_stats": (None,)}[sym]
-    assert getattr(L, sym)(*args) == -101  # CHOL_ERR_NOT_INITIALIZED
-    assert b"before chol_init" in L.chol_last_error()
+    assert_before_init_refused(sym, args)

@@ -5,6 +5,7 @@ import ctypes as C
 
 import pytest
 
+from chol_testkit import assert_before_init_refused, assert_symbols_exported
 from dense_linear_app_amd import _lib, chameleon as ch
 
 SYMBOLS = ["chol_poequ_tile", "chol_laqsy_tile", "chol_porfs_tile", "chol_posvx_tile", "chol_last_posvx_stats"]
@@ -15,13 +16,11 @@ def test_wrappers_exist():
         for p in "ds":
             assert callable(getattr(ch, f"CHAMELEON_{p}{name}_Tile"))
     assert callable(ch.last_posvx_stats)
-    for s in SYMBOLS:
-        assert s in _lib.abi_symbols()
+    assert_symbols_exported(SYMBOLS)
 
 
 @pytest.mark.parametrize("sym", SYMBOLS)
 def test_before_init_is_refused(sym):
-    L = _lib.lib()
     d = C.c_double()
     e = C.c_int(0)
     args = {"chol_poequ_tile": (None, None, C.byref(d), C.byref(d)),
@@ -30,8 +29,7 @@ def test_before_init_is_refused(sym):
             "chol_posvx_tile": (0, ch.ChamLower, None, None, C.byref(e), None, None, None, C.byref(d), C.byref(d),
                                 C.byref(d)),
             "chol_last_posvx_stats": ((C.c_double * 8)(),)}[sym]
-    assert getattr(L, sym)(*args) == -101  # CHOL_ERR_NOT_INITIALIZED
-    assert b"before chol_init" in L.chol_last_error()
+    assert_before_init_refused(sym, args)
 
 
 def test_fact_and_equed_characters():

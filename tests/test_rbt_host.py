@@ -6,6 +6,7 @@ accuracy.  The device numerics are in test_gpu_rbt.py."""
 import numpy as np
 import pytest
 
+from chol_testkit import assert_before_init_refused, assert_symbols_exported
 from dense_linear_app_amd import _lib, chameleon as ch
 from rbt_model import (backward_error, butterfly_dense, family, random_w, rbt_sym, rbt_vec, sysv_rbt_model)
 from sytrf_model import sytrf_model, sytrs_model
@@ -20,19 +21,17 @@ def test_wrappers_exist():
         for r in ("sytrf_rbt", "sytrs_rbt", "sysv_rbt", "rbt_apply"):
             assert callable(getattr(ch, f"CHAMELEON_{p}{r}_Tile"))
     assert callable(ch.last_rbt_stats)
+    assert_symbols_exported(SYMBOLS)
     for s in SYMBOLS:
-        assert s in _lib.abi_symbols()
         assert getattr(_lib.lib(), s).argtypes is not None
 
 
 @pytest.mark.parametrize("sym", SYMBOLS)
 def test_before_init_is_refused(sym):
-    L = _lib.lib()
     args = {"chol_sytrf_rbt_tile": (ch.ChamLower, None, None, 2, 1), "chol_sytrs_rbt_tile": (ch.ChamLower, None, None, 2, None),
             "chol_sysv_rbt_tile": (ch.ChamLower, None, None, None, 2, 1, None, None, None, None),
             "chol_rbt_apply_tile": (ch.ChamLower, None, None, 2), "chol_last_rbt_stats": (None,)}[sym]
-    assert getattr(L, sym)(*args) == -101  # CHOL_ERR_NOT_INITIALIZED
-    assert b"before chol_init" in L.chol_last_error()
+    assert_before_init_refused(sym, args)
 
 
 @pytest.mark.parametrize("n", [8, 60, 256])

@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 import scipy.linalg.lapack as lapack
 
-from dense_linear_app_amd import _lib, chameleon as ch
+from chol_testkit import assert_before_init_refused, assert_symbols_exported
+from dense_linear_app_amd import chameleon as ch
 from sygst_model import sygst_model
 
 SYMBOLS = ["chol_sygst_tile", "chol_last_sygst_stats"]
@@ -17,16 +18,13 @@ def test_wrappers_exist():
     for p in "ds":
         assert callable(getattr(ch, f"CHAMELEON_{p}sygst_Tile"))
     assert callable(ch.last_sygst_stats)
-    for s in SYMBOLS:
-        assert s in _lib.abi_symbols()
+    assert_symbols_exported(SYMBOLS)
 
 
 @pytest.mark.parametrize("sym", SYMBOLS)
 def test_before_init_is_refused(sym):
-    L = _lib.lib()
     args = {"chol_sygst_tile": (1, ch.ChamLower, None, None), "chol_last_sygst_stats": (None,)}[sym]
-    assert getattr(L, sym)(*args) == -101  # CHOL_ERR_NOT_INITIALIZED
-    assert b"before chol_init" in L.chol_last_error()
+    assert_before_init_refused(sym, args)
 
 
 def problem(n, seed, dtype=np.float64):

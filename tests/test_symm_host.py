@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import symm_model as sm
-from dense_linear_app_amd import _lib
+from chol_testkit import assert_before_init_refused, assert_symbols_exported, npdt, stored_sym
 from dense_linear_app_amd import chameleon as ch
 
 SYMBOLS = ["chol_symm_tile", "chol_last_symm_stats"]
@@ -17,18 +17,14 @@ def test_wrappers_exist():
     for p in "ds":
         assert callable(getattr(ch, f"CHAMELEON_{p}symm_Tile"))
     assert callable(ch.last_symm_stats)
-    for s in SYMBOLS:
-        assert s in _lib.abi_symbols()
-        assert hasattr(_lib.lib(), s)
+    assert_symbols_exported(SYMBOLS)
 
 
 @pytest.mark.parametrize("sym", SYMBOLS)
 def test_before_init_is_refused(sym):
-    L = _lib.lib()
     args = {"chol_symm_tile": (ch.ChamLeft, ch.ChamLower, 1.0, None, None, 0.0, None),
             "chol_last_symm_stats": (None,)}[sym]
-    assert getattr(L, sym)(*args) == -101  # CHOL_ERR_NOT_INITIALIZED
-    assert b"before chol_init" in L.chol_last_error()
+    assert_before_init_refused(sym, args)
 
 
 @pytest.mark.parametrize("n,tile", sm.SHAPES)
@@ -53,13 +49,13 @@ def test_the_exact_family_is_exact_in_any_order(n, tile):
 def test_model_reads_one_triangle(u, dt):
     """the model on the stored triangle (NaN in the other) is the dense product, and follows BLAS's rules for the scalars"""
     n, nrhs = 100, 8
-    A, B, C = (a.astype(sm.npdt(dt)) for a in sm.exact_problem(n))
+    A, B, C = (a.astype(npdt(dt)) for a in sm.exact_problem(n))
     B, C = B[:, :nrhs], C[:, :nrhs]
-    S = sm.stored(A, u).astype(sm.npdt(dt))
+    S = stored_sym(A, u).astype(npdt(dt))
     for alpha, beta in sm.SCALARS:
         want = alpha * (A.astype(np.float64) @ B) + beta * C
         got = sm.symm(S, u, alpha, B, beta, np.full_like(C, np.nan) if beta == 0 else C)
-        assert got.dtype == sm.npdt(dt) and np.array_equal(got, want)
+        assert got.dtype == npdt(dt) and np.array_equal(got, want)
     nan = np.full_like(B, np.nan)
     assert np.array_equal(sm.symm(np.full_like(S, np.nan), u, 0.0, nan, -1.0, C), -C)
     assert np.array_equal(sm.symm(np.full_like(S, np.nan), u, 0.0, nan, 0.0, nan), np.zeros_like(C))

@@ -6,8 +6,9 @@ exact on the integer case the GPU test uses.  The device numerics are in test_gp
 import numpy as np
 import pytest
 
-from dense_linear_app_amd import _lib, chameleon as ch
-from sytrf_model import inertia, ldl_unblocked, residual, split, sytrf_model, sytrs_model
+from chol_testkit import assert_before_init_refused, assert_symbols_exported
+from dense_linear_app_amd import chameleon as ch
+from sytrf_model import inertia, ldl_unblocked, quasi_definite, residual, split, sytrf_model, sytrs_model
 
 SYMBOLS = ["chol_sytrf_nopiv_tile", "chol_sytrs_nopiv_tile", "chol_sysv_nopiv_tile", "chol_last_sytrf_stats"]
 
@@ -17,32 +18,14 @@ def test_wrappers_exist():
         for r in ("sytrf", "sytrs", "sysv"):
             assert callable(getattr(ch, f"CHAMELEON_{p}{r}_nopiv_Tile"))
     assert callable(ch.last_sytrf_stats)
-    for s in SYMBOLS:
-        assert s in _lib.abi_symbols()
+    assert_symbols_exported(SYMBOLS)
 
 
 @pytest.mark.parametrize("sym", SYMBOLS)
 def test_before_init_is_refused(sym):
-    L = _lib.lib()
     args = {"chol_sytrf_nopiv_tile": (ch.ChamLower, None), "chol_sytrs_nopiv_tile": (ch.ChamLower, None, None),
             "chol_sysv_nopiv_tile": (ch.ChamLower, None, None), "chol_last_sytrf_stats": (None,)}[sym]
-    assert getattr(L, sym)(*args) == -101  # CHOL_ERR_NOT_INITIALIZED
-    assert b"before chol_init" in L.chol_last_error()
-
-
-def quasi_definite(n, m, seed, perm=False):
-    """[[H, J^T], [J, -C]], H = G G^T / 2n with G n x 2n standard normal, C likewise of order m, J = randn / sqrt(n)"""
-    r = np.random.default_rng(seed)
-    G = r.standard_normal((n, 2 * n))
-    H = G @ G.T / (2 * n)
-    G = r.standard_normal((m, 2 * m))
-    C = G @ G.T / (2 * m)
-    J = r.standard_normal((m, n)) / np.sqrt(n)
-    K = np.block([[H, J.T], [J, -C]])
-    if perm:
-        p = r.permutation(n + m)
-        K = K[np.ix_(p, p)]
-    return K
+    assert_before_init_refused(sym, args)
 
 
 U = {np.float64: 2.0 ** -53, np.float32: 2.0 ** -24}

@@ -12,7 +12,7 @@ import scipy.linalg
 
 import dyadic_model as dm
 import trtrs_model as tm
-from dense_linear_app_amd import _lib
+from chol_testkit import assert_before_init_refused, assert_symbols_exported, npdt
 from dense_linear_app_amd import chameleon as ch
 
 SYMBOLS = ["chol_trtrs_tile", "chol_trmm_tile", "chol_logdet_tile", "chol_last_trtrs_stats"]
@@ -23,19 +23,15 @@ def test_wrappers_exist():
         for r in ("trtrs", "trmm", "logdet"):
             assert callable(getattr(ch, f"CHAMELEON_{p}{r}_Tile"))
     assert callable(ch.last_trtrs_stats)
-    for s in SYMBOLS:
-        assert s in _lib.abi_symbols()
-        assert hasattr(_lib.lib(), s)
+    assert_symbols_exported(SYMBOLS)
 
 
 @pytest.mark.parametrize("sym", SYMBOLS)
 def test_before_init_is_refused(sym):
-    L = _lib.lib()
     args = {"chol_trtrs_tile": (ch.ChamLower, ch.ChamNoTrans, ch.ChamNonUnit, None, None),
             "chol_trmm_tile": (ch.ChamLeft, ch.ChamLower, ch.ChamNoTrans, ch.ChamNonUnit, 1.0, None, None),
             "chol_logdet_tile": (None, None), "chol_last_trtrs_stats": (None,)}[sym]
-    assert getattr(L, sym)(*args) == -101  # CHOL_ERR_NOT_INITIALIZED
-    assert b"before chol_init" in L.chol_last_error()
+    assert_before_init_refused(sym, args)
 
 
 @pytest.mark.parametrize("dt", ["d", "s"])
@@ -43,11 +39,11 @@ def test_before_init_is_refused(sym):
 def test_model_beside_lapack_on_the_random_family(n, B, dt):
     """both reach a componentwise backward error far inside n u (Higham, Accuracy and Stability, Thm 8.5)"""
     L64, B64 = tm.random_problem(n)
-    L, R = L64.astype(tm.npdt(dt)), B64.astype(tm.npdt(dt))
+    L, R = L64.astype(npdt(dt)), B64.astype(npdt(dt))
     u = 2.0 ** -53 if dt == "d" else 2.0 ** -24
     for forward in (True, False):
         M = L if forward else L.T
-        wm = tm.solve_backward_error(M, tm.half_solve(L, R, B, forward, tm.npdt(dt)), R).max() / u
+        wm = tm.solve_backward_error(M, tm.half_solve(L, R, B, forward, npdt(dt)), R).max() / u
         wl = tm.solve_backward_error(M, scipy.linalg.solve_triangular(L, R, lower=True, trans=0 if forward else 1), R).max() / u
         print(f"n={n} B={B} {dt} {'forward' if forward else 'backward'}: model {wm:.2f} u, LAPACK {wl:.2f} u")
         assert wm <= n and wl <= n
@@ -64,10 +60,10 @@ def test_the_emulation_is_exact(fam, n, B, dt):
         # peak is at most 2.8e3 on every case but panel (2100, 512), where it is 2.94e3 forward and 3.84e3 backward.)
         print(f"{fam} n={n} B={B} {'forward' if forward else 'backward'}: product peak {pk:.4g}")
         assert pk <= (3.9e3 if (fam, n) == ("panel", 2100) else 2.8e3) and 16 * 2 * pk < tm.limit("s"), pk
-        Bd = Bm.astype(tm.npdt(dt))
+        Bd = Bm.astype(npdt(dt))
         assert np.array_equal(Bd.astype(np.float64), Bm)
-        got = tm.half_solve(L, Bd, B, forward, tm.npdt(dt), peak)
-        assert got.dtype == tm.npdt(dt) and np.array_equal(got.astype(np.float64), X)
+        got = tm.half_solve(L, Bd, B, forward, npdt(dt), peak)
+        assert got.dtype == npdt(dt) and np.array_equal(got.astype(np.float64), X)
     print(f"{fam} n={n} B={B} {dt}: peak {peak.value:.3g}")
     assert 16 * peak.value < tm.limit(dt), peak.value
 

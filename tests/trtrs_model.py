@@ -29,10 +29,6 @@ EXACT = [(fam, n, B, dt) for fam, n, B, dts in CASES for dt in dts]
 EXACT_IDS = ["-".join(str(x) for x in c) for c in EXACT]
 
 
-def npdt(dt):
-    return np.float64 if dt == "d" else np.float32
-
-
 def limit(dt):
     """16 x peak (four fractional bits) must stay below this"""
     return 2.0 ** 53 if dt == "d" else 2.0 ** 24
