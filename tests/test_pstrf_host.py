@@ -1,12 +1,16 @@
 """CPU-side checks of the pivoted Cholesky factorisation (chol_pstrf_tile / chol_last_pstrf_stats): the Python wrappers
 and ABI symbols exist, both entry points refuse to run before chol_init, and the numpy model of the library's algorithm
 (pstrf_model.py: tile columns, candidates reset per tile column, deferred interchanges, padded rows excluded) picks
-LAPACK's pivots and rank.  The device numerics are in test_gpu_pstrf.py."""
+LAPACK's pivots and rank.  Then the proofs of the exact family (pstrf_model.level_case): on every case and dtype that
+pstrf_model.CASES lists, LAPACK, the model and the closed form agree bit for bit, the stopping rule sits at its edge
+where the GPU tests say it does, and each deliberately wrong variant of the model is told apart -- so every value that
+test_gpu_pstrf.py expects comes from LAPACK and the closed form alone.  The device numerics are in test_gpu_pstrf.py."""
 import numpy as np
 import pytest
 import scipy.linalg.lapack as lapack
 
-from chol_testkit import assert_before_init_refused, assert_symbols_exported
+import pstrf_model as pm
+from chol_testkit import assert_before_init_refused, assert_symbols_exported, bits, npdt
 from dense_linear_app_amd import chameleon as ch
 from pstrf_model import gram, pstrf_model
 
@@ -78,3 +82,126 @@ def test_model_explicit_tol():
     A = gram(n, n, 8) * np.outer(np.logspace(0, -6, n), np.logspace(0, -6, n))
     for tol in (1e-2, 1e-6):
         check_against_lapack(A, B, tol)
+
+
+# ------------------------------------------------------------------------------------------- the exact family
+ALL_EXACT = pm.EXACT + [(*pm.VIEW_CASE[:5], dt) for dt in pm.VIEW_CASE[5]]
+
+
+@pytest.mark.parametrize("n,B,m,t,r,dt", ALL_EXACT, ids=["-".join(str(x) for x in c) for c in ALL_EXACT])
+def test_level_case_is_exact(n, B, m, t, r, dt):
+    A, L0, sigma = pm.case_of((n, B, m, t, r))
+    Ad = A.astype(npdt(dt))
+    assert np.array_equal(Ad.astype(np.float64), A)  # representable
+    assert np.array_equal(A, A.T) and sorted(sigma) == list(range(n))
+    assert m * 4.0 ** -t < 9 / 16  # the order is forced up to ties
+    assert pm.level_bits(L0, t) < (53 if dt == "d" else 24)  # every partial sum of every order is exact
+    piv, rank, info, L = pstrf_model(Ad, B)
+    lpiv, lrank, linfo, LL = pm.lapack_level(n, B, m, t, r, dt)
+    assert (rank, info) == (lrank, linfo)
+    assert np.array_equal(piv[:rank], lpiv[:rank])
+    if dt == "d" or (n, B) != pm.STOP_CASE[:2]:  # (fp32 stops one level early there: test_stop_at_equality)
+        assert rank == (n if r is None else r)
+    for p, F in ((piv, L), (lpiv, LL)):
+        assert sorted(p) == list(range(1, n + 1))
+        E = pm.expected_factor(L0, sigma, p, rank).astype(npdt(dt))
+        assert np.array_equal(bits(F[:, :rank]), bits(E))
+    # the elimination order goes level by level, and within a level by the smallest current position
+    lev = sigma[piv[:rank] - 1] // m
+    assert np.all(np.diff(lev) >= 0)
+
+
+def test_stop_at_equality():
+    """(1024, 256), G = 7: amax = 4^7; in fp32 the default stopping value is 1024 2^-24 2^14 = 1 exactly, the pivots of
+    the last level, so fp32 stops at rank 896 and fp64 finishes; a pivot equal to an explicit tol stops too"""
+    n, B, m, t, r, _ = pm.STOP_CASE
+    A = pm.case_of(pm.STOP_CASE)[0]
+    assert np.diag(A).max() == 4.0 ** 7
+    assert np.float32(n) * np.float32(2.0 ** -24) * np.float32(4.0 ** 7) == np.float32(1.0)
+    for dt, tol, want in (("s", -1.0, (896, 1)), ("d", -1.0, (1024, 0)), ("d", 16.0, (640, 1)), ("d", 15.0, (768, 1)),
+                          ("s", 16.0, (640, 1)), ("s", 15.0, (768, 1))):
+        _, rank, info, _ = pstrf_model(A.astype(npdt(dt)), B, tol)
+        assert (rank, info) == want, (dt, tol)
+        assert pm.lapack_level(n, B, m, t, r, dt, tol)[1:3] == want, (dt, tol)
+
+
+def test_wrong_variants_are_told_apart():
+    # the last of equal candidates: other pivots on (1000, 192)
+    n, B = pm.RAGGED_CASE[:2]
+    A = pm.case_of(pm.RAGGED_CASE)[0]
+    piv = pm.lapack_level(*pm.RAGGED_CASE[:5], "d")[0]
+    assert np.array_equal(pstrf_model(A, B)[0], piv)
+    assert not np.array_equal(pstrf_model(A, B, tie="last")[0], piv)
+    # going on at a pivot equal to the stopping value: another rank on the fp32 (1024, 256)
+    A32 = pm.case_of(pm.STOP_CASE)[0].astype(np.float32)
+    assert pstrf_model(A32, pm.STOP_CASE[1])[1] == 896
+    assert pstrf_model(A32, pm.STOP_CASE[1], stop_at_equal=False)[1] == 1024
+    # candidates from the padding: the padded identity's 1 is above the stopping value once the true rank is used up
+    n, B, _, _, r, _ = pm.RAGGED_DEFICIENT_CASE
+    A = pm.case_of(pm.RAGGED_DEFICIENT_CASE)[0]
+    assert pstrf_model(A, B)[1] == r
+    assert pstrf_model(A, B, exclude_padding=False)[1] > r
+
+
+def nan_plant_expected(case, i, k):
+    """the documented rule (pstrf.hip's header: a NaN candidate ranks first, then stops) on the LAPACK run without the
+    plant -> (rank, piv[:rank]): the NaN at (i, k) of A0 enters row i's candidate when column k is eliminated"""
+    _, _, sigma = pm.case_of(case)
+    piv = pm.lapack_level(*case[:5], "d")[0]
+    rank = int(np.flatnonzero(sigma[piv - 1] == k)[0]) + 1
+    return rank, piv[:rank]
+
+
+@pytest.mark.parametrize("i,k", pm.NAN_PLANTS)
+def test_nan_rule_of_the_model(i, k):
+    """the model, which carries the library's NaN rule, on the planted matrix against the rule evaluated on the
+    unplanted LAPACK run"""
+    case = pm.RAGGED_CASE
+    n, B, m = case[:3]
+    assert i // m > k // m
+    A = pm.nan_planted(case, i, k)
+    piv, rank, info, L = pstrf_model(A, B)
+    want_rank, want_piv = nan_plant_expected(case, i, k)
+    assert (rank, info) == (want_rank, 1) and 0 < rank < n
+    assert np.array_equal(piv[:rank], want_piv)
+    E = pm.nan_expected_factor(case, i, k, piv, rank)
+    assert np.isnan(E).sum() == 1 and np.isnan(E[:, rank - 1]).sum() == 1
+    assert np.array_equal(np.isnan(L[:, :rank]), np.isnan(E))
+    assert np.array_equal(np.nan_to_num(L[:, :rank]), np.nan_to_num(E))
+
+
+def low_rank_pstrf(Lp, tol_n):
+    """the unblocked pivoted factorisation of Lp Lp^T without forming it (Lp n x r, float32): columns from inner
+    products of Lp's rows -> (piv 1-based, rank, L's first rank columns)"""
+    n, r = Lp.shape
+    Lp = Lp.copy()
+    piv = np.arange(1, n + 1)
+    d = (Lp * Lp).sum(axis=1, dtype=np.float32)
+    L = np.zeros((n, r + 1), dtype=np.float32)
+    dstop = np.float32(tol_n) * np.float32(2.0 ** -24) * d.max()
+    for j in range(r + 1):
+        p = j + pm.best(d[j:])
+        if j > 0 and not d[p] > dstop:
+            return piv, j, L[:, :j]
+        for x in (Lp, L, d, piv):
+            x[[j, p]] = x[[p, j]]
+        ljj = np.sqrt(d[j])
+        L[j, j] = ljj
+        L[j + 1:, j] = (Lp[j + 1:] @ Lp[j] - L[j + 1:, :j] @ L[j, :j]) / ljj
+        d[j + 1:] -= L[j + 1:, j] ** 2
+    raise AssertionError("did not stop")
+
+
+def test_chunk_case():
+    """the expected result of test_gpu_pstrf.py: test_more_than_256_chunks, from the factor of the matrix (n x 5)
+    alone: every product and sum is a multiple of 1/4 below 2^5, so the arithmetic is exact"""
+    L0, sigma, want = pm.chunk_factor()
+    n = L0.shape[0]
+    assert n >= 16448 and -(-n // 64) > 256
+    assert sorted(sigma) == list(range(n))
+    assert np.array_equal(np.sort(np.flatnonzero(sigma < 5)) // 64, [1, 125, 255, 256, 257])
+    assert np.array_equal(L0 * 2, np.round(L0 * 2)) and np.abs(L0[5:]).max() == 0.5
+    piv, rank, L = low_rank_pstrf(L0[sigma], n)
+    assert rank == 5
+    assert np.array_equal(piv[:5], want) and np.array_equal(want, [101, 8001, 16384, 16385, 16485])
+    assert np.array_equal(bits(L), bits(pm.expected_factor(L0, sigma, piv, 5).astype(np.float32)))
