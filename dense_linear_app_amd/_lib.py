@@ -75,6 +75,8 @@ def lib() -> C.CDLL:
         "chol_chud_tile": ([i, vp, vp], i),
         "chol_chdd_tile": ([i, vp, vp], i),
         "chol_last_chud_stats": ([C.POINTER(d)], i),
+        "chol_chex_tile": ([i, vp, i, i, i], i),
+        "chol_last_chex_stats": ([C.POINTER(d)], i),
         "chol_trtrs_tile": ([i, i, i, vp, vp], i),
         "chol_trmm_tile": ([i, i, i, i, d, vp, vp], i),
         "chol_logdet_tile": ([vp, C.POINTER(d)], i),

@@ -422,6 +422,23 @@ def last_chud_stats() -> dict:
             "stop_vector": int(v[5])}
 
 
+def CHAMELEON_dchex_Tile(uplo: int, A: Desc, k: int, l: int, job: int) -> int:
+    """LINPACK DCHEX without Z: A, the factor chol_potrf_tile(uplo, .) returned of a matrix M, <- the factor of
+    P^T M P, P the circular shift of the variables k..l (1-based): job 1 moves variable l up to position k, job 2 moves
+    variable k down to position l, in O(n (l - k)) operations.  To delete variable k: job 2 with l = n, then the
+    leading (n-1) x (n-1) view holds the factor without it.  Returns 0, or info > 0: the 1-based index of a zero on the
+    factor's diagonal (A unchanged), or the column at which non-finite data stopped a rotation (A unspecified)."""
+    return check("chol_chex_tile", lib().chol_chex_tile(uplo, A.handle, k, l, job))
+
+
+def last_chex_stats() -> dict:
+    """The last CHAMELEON_dchex_Tile (chol_last_chex_stats): total, data movement, chain (job 2: generators and
+    in-tile appliers; job 1: the coefficient chain) and bulk applier time [ms], the job and l - k."""
+    v = (C.c_double * 8)()
+    check("chol_last_chex_stats", lib().chol_last_chex_stats(v))
+    return {"total_ms": v[0], "move_ms": v[1], "chain_ms": v[2], "bulk_ms": v[3], "job": int(v[4]), "l_minus_k": int(v[5])}
+
+
 def CHAMELEON_dtrtrs_Tile(uplo: int, trans: int, diag: int, A: Desc, B: Desc) -> int:
     """LAPACK DTRTRS: B <- inv(op(T)) B, T the `uplo` triangle of A (the factor chol_potrf_tile(uplo, .) returned), op
     the transpose for ChamTrans; A is only read.  Returns 0, or info > 0: the 1-based index of a zero on the diagonal
@@ -561,6 +578,7 @@ CHAMELEON_spstrf_Tile = CHAMELEON_dpstrf_Tile
 CHAMELEON_ssygst_Tile = CHAMELEON_dsygst_Tile
 CHAMELEON_schud_Tile = CHAMELEON_dchud_Tile
 CHAMELEON_schdd_Tile = CHAMELEON_dchdd_Tile
+CHAMELEON_schex_Tile = CHAMELEON_dchex_Tile
 CHAMELEON_strtrs_Tile = CHAMELEON_dtrtrs_Tile
 CHAMELEON_strmm_Tile = CHAMELEON_dtrmm_Tile
 CHAMELEON_slogdet_Tile = CHAMELEON_dlogdet_Tile

@@ -540,6 +540,44 @@ template <typename T>
 void launch_chud_apply(hipStream_t s, T *Acol, long bs, int e, int mb, long n, int k, long r0, long r1, int c0, int nc,
                        const T *tab, const ChudVecs<T> &V, int rg);
 
+// ---- launchers (chex.hip): chol_chex_tile (LINPACK DCHEX, Lower) on a single-process image; rows and columns 0-based ----
+// the image: tile (I, J) at A + (I + J lmt) bs, ld e, mb used rows and columns a tile, order n
+template <typename T>
+struct ChexMat {
+  T *A;
+  long bs;
+  int lmt, e, mb;
+  long n;
+};
+// the saved copy of a tile column from tile row row0 down, tile after tile
+template <typename T>
+struct ChexStage {
+  const T *p;
+  int row0;
+};
+// w (tile row I, stored row r at w + I e + r) over the rows k0..n-1 <- job 2: the moved variable's old column in the
+// new row order, chud's vector; job 1: what a row carries into its rotations (row k0 is left to launch_chex_coef)
+template <typename T>
+void launch_chex_vec(hipStream_t s, const ChexMat<T> &M, int k0, int l0, int job, T *w);
+// A(i, l0) <- w_i for i >= l0
+template <typename T>
+void launch_chex_setcol(hipStream_t s, const ChexMat<T> &M, int l0, const T *w);
+// the columns c < c1 of tile column J, tile rows [I0, I1), from the copies S0 (of tile column J) and S1 (of J + 1): in
+// a column before k0 the rows k0..l0 permuted; job 2: a column j of k0..l0-1 <- the old column j + 1, its rows above
+// l0 moved up by one, a zero in row l0 (the other columns and rows are left alone)
+template <typename T>
+void launch_chex_move(hipStream_t s, const ChexMat<T> &M, int J, int c1, int I0, int I1, int k0, int l0, int job,
+                      const ChexStage<T> &S0, const ChexStage<T> &S1);
+// job 1: tab[2 (i - k0) ..] <- (cc_i, ss_i) of column i, i = l0-1 down to k0 (chex_rot.h), from row l0 of A; w_k0 <- the
+// last pivot; info[0] <- the 1-based new column of the first rotation whose rho^2 is not positive (else untouched)
+template <typename T>
+void launch_chex_coef(hipStream_t s, const ChexMat<T> &M, int k0, int l0, T *tab, T *w, int *info);
+// job 1: the new columns jlo..jhi (inside tile column J and k0..l0) of every row from tile row J down (nt tile rows),
+// right to left, read from S0 (the copy of tile column J) and S1 (of J - 1, its last column), written to A
+template <typename T>
+void launch_chex_apply(hipStream_t s, const ChexMat<T> &M, int nt, int J, int jlo, int jhi, int k0, int l0,
+                       const ChexStage<T> &S0, const ChexStage<T> &S1, const T *tab, T *w);
+
 // ---- launchers (sytrf.hip): chol_sytrf_nopiv_tile / chol_sytrs_nopiv_tile (A = L D L^T, Lower) on a single-process image ----
 // one diagonal tile (e x e, ld e, e % 128 == 0) <- its factor in place, by 128-block steps: D on the diagonal, the unit
 // lower triangular L below it, the strict upper triangle not touched.  Wt: one tile of scratch; Lc, winv: e / 128 blocks

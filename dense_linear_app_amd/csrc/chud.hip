@@ -24,16 +24,6 @@ __device__ __forceinline__ T *chud_vec(const ChudVecs<T> &V, int t, int I, int r
   return V.p + ((long)(t / V.mb) * V.lmt + I) * V.bs + (long)(t % V.mb) * V.ld + r;
 }
 
-// A workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every global load and store in
-// flight, which would put the latency of the prefetched columns and of the stores behind them on every step of the
-// chain.  Both kernels exchange data between lanes through LDS alone: a lane reads and writes only its own rows of L
-// and V in global memory, and the table is written by one kernel and read by the next.
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
 // Columns c0 .. c0+nc-1 (nc <= 128) of the diagonal tile D (ld e) against the vectors V.g0 .. V.g0+rg-1: the lower
 // triangle of the nc x nc diagonal block and its rows of V (tile row I); tab[(c0 + j) rg + t] <- the rotation of
 // column c0 + j and vector V.g0 + t.  Column j: row j's lane makes the rg pivots one after another (each needs the

@@ -8,6 +8,16 @@
 
 namespace cholmi {
 
+// A workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every global load and store in
+// flight, which would put the latency of the prefetched columns and of the stores behind them on every step of the
+// chain.  The kernels of chud.hip and chex.hip exchange data between lanes through LDS alone: a lane reads and writes
+// only its own rows of L and V in global memory, and a table is written by one kernel and read by the next.
+__device__ __forceinline__ void lds_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
 // what a row needs of the rotation (column j, vector t): the appliers read it as four consecutive values
 template <typename T>
 struct ChudRot {

@@ -1,9 +1,9 @@
 // The routines of libcholmi.so that work from a factor (include/cholmi.h), one section each below: the SPD solve, the
 // mixed-precision solve, the inverse, the condition estimate, the expert solve with error bounds, the pivoted
 // factorisation, the reduction of the generalized symmetric-definite eigenproblem, the L D L^T factorisation without
-// pivoting with its solve, their butterfly-randomised forms, the rank-r update and downdate of a factor, the halves of a
-// factor alone, and the symmetric product from one stored triangle; the entry
-// points come last.  All run on the main
+// pivoting with its solve, their butterfly-randomised forms, the rank-r update and downdate of a factor, the circular
+// shift of a factor's variables, the halves of a factor alone, and the symmetric product from one stored triangle; the
+// entry points come last.  All run on the main
 // stream of the context that api.hip keeps (api_internal.h); this file owns only its scratch and the statistics of the
 // last call of each family.
 #include <hip/hip_runtime.h>
@@ -33,6 +33,7 @@ ScratchPool<8, true> rf;  // poequ / porfs / posvx
 ScratchPool<3> ps;        // pstrf
 ScratchPool<3> sg;        // sygst
 ScratchPool<2> cu;        // chud / chdd
+ScratchPool<4> cx;        // chex
 ScratchPool<4> sy;        // sytrf_nopiv / sytrs_nopiv
 // sytrf_rbt / sysv_rbt.  Not cleared when it grows (a clear on the null stream would race with the main stream's upload
 // of W): every buffer is written before it is read
@@ -55,7 +56,7 @@ struct LastStats {
     return 0;
   }
 };
-LastStats mx_stats, cn_stats, rf_stats, ps_stats, sg_stats, cu_stats, sy_stats, rb_stats, tr_stats, sm_stats;
+LastStats mx_stats, cn_stats, rf_stats, ps_stats, sg_stats, cu_stats, cx_stats, sy_stats, rb_stats, tr_stats, sm_stats;
 
 hipStream_t main_stream() { return main_rank_ctx()->st[ST_MAIN]; }
 
@@ -1404,6 +1405,134 @@ int chud_entry(const char *what, int uplo, chol_desc *A, chol_desc *V, double si
   });
 }
 
+// ---------------------------------------------------------------- circular shift of the variables (LINPACK DCHEX)
+// Lower, rows and columns 0-based: L <- the factor of P^T L L^T P, P the circular shift of the variables k0..l0.  Both
+// jobs move the window (rows >= k0 of the columns k0..l0) by one row and one column along the diagonal and permute the
+// rows k0..l0 of the columns before k0; the rows before k0 and the columns after l0 are not touched.  A lane's source
+// is another lane's destination, so the walk goes tile column by tile column and copies each one (from tile row kt down;
+// before kt: its tile rows kt..lt) into a ring of two buffers before it is written; the kernels read L from the copies.
+//   job 2 (k0 moves down to l0), tile columns ascending: the move (chex.hip: new column j <- old column j + 1, so tile
+//     column J needs the copies of J and J + 1), then chud's generator and appliers with sigma = +1 on the window's
+//     columns of J alone, against the one vector that launch_chex_vec made of the old column k0; at the end the rotated
+//     vector becomes column l0.
+//   job 1 (l0 moves up to k0): the rotations come from row l0 alone (launch_chex_coef, a chain of l0 - k0 pivots);
+//     then tile columns descending, the applier reads the copies of J and J - 1 and writes column J rotated and moved
+//     in one pass; what a row carries from one tile column to the next is in the work vector.
+// One stream, in program order; the phases are timed as sygst's are.
+// *info <- 0, or the 1-based new column of the first rotation whose squared pivot is not positive (or is NaN)
+template <typename T>
+int chex_impl(chol_desc *A, int k0, int l0, int job, int *info) {
+  hipStream_t s = main_stream();
+  double *st = cx_stats.v;  // total, data movement, chain, bulk appliers, job, l - k
+  const long n = A->lm;
+  const int nt = A->nt, mb = A->mb, e = A->mbi, lmt = A->lmt, kt = k0 / mb, lt = l0 / mb;
+  const long bs = A->bsizi;
+  const char *what = "chex_tile";
+  *info = 0;
+  // cx[0], cx[1]: the ring; cx[2]: the work vector (nt e) and the table behind it (job 1: two values a column of the
+  // window; job 2: chud's four a column of a tile); cx[3]: the stop word
+  const size_t tabn = job == 1 ? 2 * (size_t)(l0 - k0) : 4 * (size_t)mb;
+  int rc = cx.ensure_bytes(0, (size_t)(nt - kt) * bs * sizeof(T), what);
+  if (!rc) rc = cx.ensure_bytes(1, (size_t)(nt - kt) * bs * sizeof(T), what);
+  if (!rc) rc = cx.ensure_bytes(2, ((size_t)nt * e + tabn) * sizeof(T), what);
+  if (!rc) rc = cx.ensure_bytes(3, 2 * sizeof(int), what);
+  if (rc) return rc;
+  T *w = cx.as<T>(2), *tab = w + (size_t)nt * e;
+  int *stop = cx.as<int>(3);
+  T *Am = reinterpret_cast<T *>(A->mat);
+  const ChexMat<T> M{Am, bs, lmt, e, mb, n};
+  ChexStage<T> S[2];
+  // tile column X saved into buffer `slot`
+  auto stage = [&](int X, int slot) -> int {
+    const int row0 = std::max(X, kt), cnt = (X < kt ? lt + 1 : nt) - row0;
+    HIPCHECK(hipMemcpyAsync(cx.p[slot], Am + ((long)row0 + (long)X * lmt) * bs, (size_t)cnt * bs * sizeof(T),
+                            hipMemcpyDeviceToDevice, s));
+    S[slot] = ChexStage<T>{cx.as<T>(slot), row0};
+    return 0;
+  };
+  forget_winv(A->mat);  // (A is overwritten)
+  HIPCHECK(hipMemsetAsync(stop, 0, 2 * sizeof(int), s));
+  PhaseMarks pm;
+  enum { P_MOVE = 1, P_CHAIN, P_BULK };
+  if ((rc = pm.mark(0))) return rc;
+  if (job == 2) {
+    const ChudVecs<T> vec{w, (long)e, e, nt, mb, 0};
+    launch_chex_vec<T>(s, M, k0, l0, 2, w);
+    for (int J = 0; J < kt; ++J) {
+      if ((rc = stage(J, 0))) return rc;
+      launch_chex_move<T>(s, M, J, mb, kt, lt + 1, k0, l0, 2, S[0], S[0]);
+    }
+    if ((rc = stage(kt, kt & 1))) return rc;
+    for (int J = kt; J <= lt; ++J) {
+      if (J < lt && (rc = stage(J + 1, (J + 1) & 1))) return rc;
+      const int ca = std::max(k0 - J * mb, 0), cb = std::min(mb, l0 - J * mb);  // the window's columns of J before l0
+      launch_chex_move<T>(s, M, J, cb, J, nt, k0, l0, 2, S[J & 1], S[J < lt ? (J + 1) & 1 : J & 1]);
+      if ((rc = pm.mark(P_MOVE))) return rc;
+      if (cb <= ca) continue;
+      const int nv = (int)std::min<long>(mb, n - (long)J * mb);
+      T *Acol = Am + ((long)J + (long)J * lmt) * bs;
+      for (int c0 = ca; c0 < cb; c0 += MACRO) {
+        const int nc = std::min(MACRO, cb - c0);
+        launch_chud_gen<T>(s, Acol, e, c0, nc, vec, J, 1, T(1), tab, stop, J * mb + c0 + 1);
+        launch_chud_apply<T>(s, Acol, bs, e, mb, n, J, c0 + nc, nv, c0, nc, tab, vec, 1);
+      }
+      if ((rc = pm.mark(P_CHAIN))) return rc;
+      if (J + 1 < nt) {
+        launch_chud_apply<T>(s, Acol, bs, e, mb, n, J, e, (long)(nt - J) * e, ca, cb - ca, tab, vec, 1);
+        if ((rc = pm.mark(P_BULK))) return rc;
+      }
+    }
+    launch_chex_setcol<T>(s, M, l0, w);
+    HIPCHECK(hipGetLastError());
+    if ((rc = pm.mark(P_MOVE))) return rc;
+  } else {
+    launch_chex_coef<T>(s, M, k0, l0, tab, w, stop);
+    if ((rc = pm.mark(P_CHAIN))) return rc;
+    launch_chex_vec<T>(s, M, k0, l0, 1, w);
+    if ((rc = stage(lt, lt & 1))) return rc;
+    for (int J = lt; J >= kt; --J) {
+      if (J > kt && (rc = stage(J - 1, (J - 1) & 1))) return rc;
+      if ((rc = pm.mark(P_MOVE))) return rc;
+      launch_chex_apply<T>(s, M, nt, J, std::max(k0, J * mb), std::min(l0, (J + 1) * mb - 1), k0, l0, S[J & 1],
+                           S[J > kt ? (J - 1) & 1 : J & 1], tab, w);
+      if ((rc = pm.mark(P_BULK))) return rc;
+    }
+    launch_chex_move<T>(s, M, kt, k0 - kt * mb, kt, lt + 1, k0, l0, 1, S[kt & 1], S[kt & 1]);
+    for (int J = 0; J < kt; ++J) {
+      if ((rc = stage(J, 0))) return rc;
+      launch_chex_move<T>(s, M, J, mb, kt, lt + 1, k0, l0, 1, S[0], S[0]);
+    }
+    HIPCHECK(hipGetLastError());
+    if ((rc = pm.mark(P_MOVE))) return rc;
+  }
+  int hstop[2] = {0, 0};
+  HIPCHECK(hipMemcpyAsync(hstop, stop, sizeof hstop, hipMemcpyDeviceToHost, s));
+  if ((rc = pm.sum(st))) return rc;
+  HIPCHECK(hipStreamSynchronize(s));
+  *info = hstop[0];
+  return 0;
+}
+
+// the Lower path, or Upper between two transposes of A's storage (the shift of U^T U's variables is that of L L^T's
+// with L = U^T); a zero on the factor's diagonal returns its index before anything is written
+int chex_run(int uplo, chol_desc *A, int k, int l, int job) {
+  const bool dbl = A->dtype == CHOL_REAL_DOUBLE;
+  cx_stats.clear();
+  cx_stats.v[4] = job;
+  cx_stats.v[5] = l - k;
+  if (A->lm == 0 || k == l) return 0;
+  int info = 0;
+  int rc = dbl ? diag_zero<double>(A, &info, "chex_tile") : diag_zero<float>(A, &info, "chex_tile");
+  if (rc) return rc;
+  if (info) return info;
+  rc = through_lower(uplo == CHOL_UPPER, {A}, [&] {
+    return dbl ? chex_impl<double>(A, k - 1, l - 1, job, &info) : chex_impl<float>(A, k - 1, l - 1, job, &info);
+  });
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(main_stream()));
+  return rc ? rc : info;
+}
+
 // ---------------------------------------------------------------- L D L^T without pivoting (MAGMA dsytrf_nopiv)
 // Lower: A = L D L^T, L unit lower triangular, D diagonal; on return D on the diagonal and L below it.  Right-looking
 // with the tile as the block; tile column k (T: the tiles below k):
@@ -1892,6 +2021,7 @@ void cholmi::spd_release() {
   ps.release();
   sg.release();
   cu.release();
+  cx.release();
   sy.release();
   rb.release();
   tr.release();
@@ -2192,6 +2322,24 @@ int chol_chdd_tile(int uplo, chol_desc_t *A, chol_desc_t *V) {
 }
 
 int chol_last_chud_stats(double *out8) { return cu_stats.read("chud", out8); }
+
+int chol_chex_tile(int uplo, chol_desc_t *A, int k, int l, int job) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "chex_tile before chol_init");
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "chex_tile: uplo");
+  if (!A) return fail(-2, "chex_tile: NULL A");
+  return with_views({{A, true}}, [&]() -> int {
+    int rc = inverse_check("chex_tile", A, 2);
+    if (rc) return rc;
+    const int n = A->lm;
+    if (n > 0 && (k < 1 || k > n)) return fail(-3, "chex_tile: k outside 1..n");
+    if (n > 0 && (l < k || l > n)) return fail(-4, "chex_tile: l outside k..n");
+    if (job != 1 && job != 2) return fail(-5, "chex_tile: job must be 1 (right shift) or 2 (left shift)");
+    std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+    return chex_run(uplo, A, k, l, job);
+  });
+}
+
+int chol_last_chex_stats(double *out8) { return cx_stats.read("chex", out8); }
 
 int chol_trtrs_tile(int uplo, int trans, int diag, chol_desc_t *A, chol_desc_t *B) {
   if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "trtrs_tile before chol_init");

@@ -371,6 +371,41 @@ int chol_chdd_tile(int uplo, chol_desc_t *A, chol_desc_t *V);
  * 0-based index of the vector at which a downdate stopped (-1: none); the rest 0. */
 int chol_last_chud_stats(double *out8);
 
+/* LINPACK DCHEX without Z: A holds the Cholesky factor that chol_potrf_tile(uplo, A) returned, of a matrix M.  On
+ * return it holds the factor of P^T M P, P the circular shift of the variables k..l (1-based, 1 <= k <= l <= n):
+ *   job 1 (right shift): new order 1..k-1, l, k, k+1, .., l-1, l+1..n     (variable l moves up to position k)
+ *   job 2 (left shift):  new order 1..k-1, k+1, .., l, k, l+1..n          (variable k moves down to position l)
+ * O(n (l-k)) operations; only the columns <= l of the rows >= k are touched, one tile column at a time through a
+ * staged copy (two buffers of a tile column each).  To delete variable k: job 2 with l = n, then the leading
+ * (n-1) x (n-1) sub-matrix view holds the factor without it.
+ *
+ * The arithmetic is fixed (Lower form, L the old and L' the new factor; each a b + c one fused multiply-add):
+ *   job 2: chol_chud_tile's rotations of ONE vector, sigma = +1, on the columns k..l-1 alone: the vector is
+ *     v_i = L(i+1,k) (k <= i < l), v_l = L(k,k), v_i = L(i,k) (i > l); column j is the old column j+1 moved up by one
+ *     row, W(i,j) = L(i+1,j+1) (j <= i < l), W(l,j) = 0, W(i,j) = L(i,j+1) (i > l); afterwards L'(i,l) = v_i, i >= l.
+ *   job 1: y = L(l,l); for i = l-1 down to k: x = L(l,i), rho_i = sqrt(x x + y y), cc_i = y / rho_i,
+ *     ss_i = x / rho_i, y = rho_i.  Every other old row r >= k, new row r' = r+1 (r < l) or r (r > l):
+ *     b = L(r,l) (r > l) or +0; for i = min(r,l-1) down to k: a = L(r,i), L'(r',i+1) = cc_i a - (ss_i b),
+ *     b = ss_i a + cc_i b; finally L'(r',k) = b.  L'(k,k) = rho_k.
+ *   both: in the columns before k the rows k..l are permuted, every entry a bit-for-bit copy.
+ * No floating-point atomics and no reductions: a repeated call returns the same bits, and the result does not depend
+ * on the tile size.  Only the `uplo` triangle is read or written; the other strict triangle, the padding, the rows
+ * before k and the columns after l are not written at all.
+ *
+ * chol_chud_tile's descriptor rules for A: device-resident single-process square A (ragged orders and sub-matrix views
+ * included), stored tile edge a multiple of 64, fp64 or fp32 by the dtype; a p x q block-cyclic descriptor returns
+ * CHOL_ERR_NOT_SUPPORTED.  Cached block inverses of the old factor (chol_desc_set_version) are dropped.
+ *
+ * Returns 0 (also for n = 0 or k = l, with nothing written), or j > 0 (1-based):
+ *   - an exact zero at L_jj, found before anything is written: A unchanged;
+ *   - the new column j that the first rotation with a squared pivot <= 0 or NaN would have written (non-finite data
+ *     only).  A is then unspecified.
+ * Argument errors: -1 uplo, -2 A, -3 k (outside 1..n), -4 l (outside k..n), -5 job. */
+int chol_chex_tile(int uplo, chol_desc_t *A, int k, int l, int job);
+/* The last chol_chex_tile: total, data movement (staging copies and plain moves), chain (job 2: chud's generators and
+ * in-tile appliers; job 1: the coefficient chain) and bulk applier time [ms]; job; l - k; the rest 0. */
+int chol_last_chex_stats(double *out8);
+
 /* One half of a Cholesky factor alone: the triangular solve, the triangular product and the log-determinant, on
  * device-resident single-process descriptors with the rules of chol_potrs_tile: A square (ragged orders and
  * sub-matrix views included), stored tile edge a multiple of 64; B n x nrhs with A's dtype, order and tile size, any
