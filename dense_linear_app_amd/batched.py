@@ -1,0 +1,134 @@
+"""Batched Cholesky of small matrices on torch device tensors, in place (include/cholmi.h: chol_potrf_batched,
+chol_potrs_batched, chol_posv_batched): 10^3 .. 10^6 independent SPD matrices of order n <= 64.
+
+    info = potrf_batched(A)            A: (batch, n, n) or (n, n), float64 or float32
+    info = potrs_batched(A, B)         B: (batch, n) or (batch, n, nrhs)   [(n,) or (n, nrhs) with a 2-d A]
+    info = posv_batched(A, B)
+
+Each returns LAPACK's info of every matrix as a numpy int32 array.  The matrices of A are column-major
+(stride(-2) == 1, lda = stride(-1)) or row-major (stride(-1) == 1, lda = stride(-2)); `uplo` always speaks of the
+mathematical matrix, so for a row-major tensor the other code goes to the library.  The matrices of a 3-d B are
+column-major (what torch.empty(batch, nrhs, n).mT gives); a row-major B is refused: nothing is copied or transposed
+behind the caller's back.  Negative statuses raise CholmiError."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from ._lib import check, lib
+from .chameleon import ChamLower, ChamRealDouble, ChamRealFloat, ChamUpper
+
+
+def _dtype_code(t, what):
+    import torch
+
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what} must be a torch tensor")
+    if t.dtype == torch.float64:
+        return ChamRealDouble
+    if t.dtype == torch.float32:
+        return ChamRealFloat
+    raise ValueError(f"{what} must be float64 or float32, not {t.dtype}")
+
+
+def _require_device(*tensors):
+    """(after the layout rules, which need no device)  The library runs on a stream of its own and is synchronous at
+    the boundary: what torch has queued on these tensors finishes first"""
+    import torch
+
+    for t in tensors:
+        if t.device.type != "cuda" or t.device != tensors[0].device:
+            raise ValueError(f"A and B must be device tensors on one device, not on {t.device}")
+    torch.cuda.current_stream(tensors[0].device).synchronize()
+
+
+def _images_of_A(A, uplo):
+    """-> (dtype code, uplo for the library, n, lda, strideA, batch)"""
+    if uplo not in (ChamLower, ChamUpper):
+        raise ValueError("uplo must be ChamLower or ChamUpper")
+    dt = _dtype_code(A, "A")
+    if A.dim() not in (2, 3) or A.shape[-1] != A.shape[-2]:
+        raise ValueError(f"A must be (batch, n, n) or (n, n), not {tuple(A.shape)}")
+    n = A.shape[-1]
+    batch = A.shape[0] if A.dim() == 3 else 1
+    if n <= 1 or A.stride(-2) == 1:  # column-major
+        lda, code = (A.stride(-1) if n > 1 else 1), uplo
+    elif A.stride(-1) == 1:  # row-major: the transposed images, so the other triangle
+        lda, code = A.stride(-2), (ChamUpper if uplo == ChamLower else ChamLower)
+    else:
+        raise ValueError("the matrices of A must be column-major (stride(-2) == 1) or row-major (stride(-1) == 1)")
+    stride = A.stride(0) if A.dim() == 3 and batch > 1 else lda * n
+    if lda < max(1, n) or stride < lda * n:
+        raise ValueError(f"the matrices of A overlap: strides {tuple(A.stride())} for shape {tuple(A.shape)}")
+    return dt, code, n, lda, stride, batch
+
+
+def _images_of_B(A, B, dt, n, batch):
+    """-> (nrhs, ldb, strideB)"""
+    if _dtype_code(B, "B") != dt:
+        raise ValueError("B must have A's dtype")
+    lead = tuple(A.shape[:-2])
+    if B.dim() == A.dim() - 1 and tuple(B.shape) == lead + (n,):
+        nrhs, ldb = 1, max(1, n)
+        if n > 1 and B.stride(-1) != 1:
+            raise ValueError("the vectors of a (batch, n) B must be contiguous (stride(-1) == 1)")
+    elif B.dim() == A.dim() and tuple(B.shape[:-1]) == lead + (n,):
+        nrhs = B.shape[-1]
+        if n > 1 and B.stride(-2) != 1:
+            if B.stride(-1) == 1:
+                raise ValueError("B is row-major: its matrices must be column-major (stride(-2) == 1), which is what "
+                                 "torch.empty(batch, nrhs, n).mT gives; nothing is transposed here")
+            raise ValueError("the matrices of B must be column-major (stride(-2) == 1)")
+        ldb = B.stride(-1) if nrhs > 1 else max(1, n)
+    else:
+        raise ValueError(f"B must be {lead + (n,)} or {lead + (n, 'nrhs')}, not {tuple(B.shape)}")
+    stride = B.stride(0) if A.dim() == 3 and batch > 1 else ldb * nrhs
+    if ldb < max(1, n) or stride < ldb * nrhs:
+        raise ValueError(f"the matrices of B overlap: strides {tuple(B.stride())} for shape {tuple(B.shape)}")
+    return nrhs, ldb, stride
+
+
+def _info(batch):
+    info = np.zeros(batch, dtype=np.int32)
+    return info, info.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def potrf_batched(A, uplo: int = ChamLower) -> np.ndarray:
+    """Every matrix of A <- its Cholesky factor in the `uplo` triangle.  -> info (numpy int32, one per matrix)"""
+    dt, code, n, lda, sa, batch = _images_of_A(A, uplo)
+    _require_device(A)
+    info, pinfo = _info(batch)
+    check("chol_potrf_batched", lib().chol_potrf_batched(code, dt, n, A.data_ptr(), lda, sa, batch, pinfo))
+    return info
+
+
+def _solve(name, A, B, uplo):
+    dt, code, n, lda, sa, batch = _images_of_A(A, uplo)
+    nrhs, ldb, sb = _images_of_B(A, B, dt, n, batch)
+    _require_device(A, B)
+    info, pinfo = _info(batch)
+    check(name, getattr(lib(), name)(code, dt, n, nrhs, A.data_ptr(), lda, sa, B.data_ptr(), ldb, sb, batch, pinfo))
+    return info
+
+
+def potrs_batched(A, B, uplo: int = ChamLower) -> np.ndarray:
+    """B <- inv(A) B from the factors potrf_batched left in A.  info[b] = j: an exact zero at L_jj of matrix b, its B
+    untouched"""
+    return _solve("chol_potrs_batched", A, B, uplo)
+
+
+def posv_batched(A, B, uplo: int = ChamLower) -> np.ndarray:
+    """potrf_batched and potrs_batched in one pass, the same bits.  info[b] > 0: B of that matrix untouched"""
+    return _solve("chol_posv_batched", A, B, uplo)
+
+
+def last_batched_stats() -> dict:
+    """The last batched call (chol_last_batched_stats)"""
+    v = (C.c_double * 8)()
+    check("chol_last_batched_stats", lib().chol_last_batched_stats(v))
+    return {"total_ms": v[0], "kernel_ms": v[1], "batch": int(v[2]), "n": int(v[3]), "per_wavefront": int(v[4]),
+            "workgroups": int(v[5]), "bytes": v[6]}
+
+
+__all__ = ["potrf_batched", "potrs_batched", "posv_batched", "last_batched_stats"]

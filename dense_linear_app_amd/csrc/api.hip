@@ -328,16 +328,6 @@ int ensure_events(size_t n) {
   return 0;
 }
 
-bool is_device_ptr(const void *p) {
-  hipPointerAttribute_t attr;
-  hipError_t e = hipPointerGetAttributes(&attr, p);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();  // plain host memory: not an error for us
-    return false;
-  }
-  return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-}
-
 LocalMat local_mat(const chol_desc *d, void *base) {
   LocalMat L;
   L.base = base;
@@ -620,6 +610,16 @@ namespace cholmi {
 // ---- what spd.hip uses (api_internal.h) ------------------------------------------------------------------------
 bool ctx_inited() { return g.inited; }
 std::recursive_mutex &ctx_mutex() { return g_mu; }
+
+bool is_device_ptr(const void *p) {
+  hipPointerAttribute_t attr;
+  hipError_t e = hipPointerGetAttributes(&attr, p);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();  // plain host memory: not an error for us
+    return false;
+  }
+  return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
+}
 
 int fail(int code, const char *msg) {
   set_error(msg);
@@ -984,6 +984,7 @@ int chol_finalize(void) {
   g.stage.release();
   g.work.release();
   spd_release();
+  batched_release();
   if (g.wc_winv) (void)hipFree(g.wc_winv);
   g.wc_winv = nullptr;
   if (g.d_binfo) (void)hipFree(g.d_binfo);

@@ -1,10 +1,12 @@
-// What api.hip shares with the other host translation unit of the ABI (spd.hip, the routines that work from a factor):
+// What api.hip shares with the other host translation units of the ABI (spd.hip, the routines that work from a factor;
+// batched.hip, the batched small-matrix routines, which use the context, the errors and the scratch pools alone):
 // the context's state, the error reporting, the scratch pools, the view refresh, the descriptor rules, running an Upper
 // call through the Lower path, and a whole-matrix descriptor's trailing update.  Host only: the kernel translation
 // units see cholmi_internal.h alone.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <functional>
 #include <initializer_list>
@@ -21,6 +23,7 @@ namespace cholmi {
 
 bool ctx_inited();
 std::recursive_mutex &ctx_mutex();  // one ABI call at a time on the context
+bool is_device_ptr(const void *p);  // device or managed memory (plain host memory: false)
 
 // record msg as chol_last_error's text and return code; failf: the text formatted as printf does
 int fail(int code, const char *msg);
@@ -118,7 +121,8 @@ inline PanelRef one_panel(const void *base, int first = 0) {
   return pan;
 }
 
-// spd.hip: its scratch, freed by chol_finalize
+// spd.hip, batched.hip: their scratch, freed by chol_finalize
 void spd_release();
+void batched_release();
 
 }  // namespace cholmi

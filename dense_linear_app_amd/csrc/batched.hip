@@ -1,0 +1,373 @@
+// Batched Cholesky of small matrices (include/cholmi.h: chol_potrf_batched, chol_potrs_batched, chol_posv_batched):
+// 10^3 .. 10^6 independent SPD matrices of order n <= 64, column-major images at a fixed stride.  One kernel, three
+// modes (factor, solve, factor + solve in one pass); the entry points follow it.
+//
+// Lane = row.  A sub-group of NP = 8 / 16 / 32 / 64 lanes (the padded order) owns one matrix, 64 / NP matrices share a
+// wavefront; lane i keeps row i of the lower triangle in registers (a[m] = A(i,m), m <= i; every index of a[] is a
+// compile-time constant: the loops over the padded order are unrolled, the actual order only guards them with
+// wave-uniform branches).  The factorisation is right-looking: step j broadcasts the pivot, scales column j, and
+// updates a[m] <- fma(-a[j], L(m,j), a[m]) with L(m,j) broadcast from lane m -- for entry (i,m) that is the chain
+// k = 0 .. m-1 ascending of the header.  A broadcast is v_readlane with a compile-time lane at NP = 64 and a shuffle
+// inside the sub-group below it.  No LDS, no barrier, no atomics on data; a matrix that fails only sets its own flag
+// and keeps its own stores back, so its neighbours in the wavefront see nothing of it.
+// `uplo` only chooses the loads and stores: Lower reads A(i,m) at i + m lda (a wave reads whole columns); Upper holds
+// U = L^T, so lane i reads its row m = 0 .. i at consecutive addresses, with 16-byte loads where the image allows
+// them (base, lda and stride all multiples of 16 bytes) and the chunk lies inside the triangle.
+// The solve keeps the same rows: forward y_j = b_j r_j (r_j = 1 / L(j,j)), b_i <- fma(-L(i,j), y_j, b_i) for i > j;
+// backward, j descending, x_j = (y_j - S_j) r_j with S_j the sum over the sub-group of t_i = L(i,j) x_i (i > j, else
+// +0) by the butterfly t <- t + t[lane ^ off], off = NP/2 .. 1: a fixed tree per padded order, whatever uplo, nrhs or
+// the position in the batch.  One right-hand column at a time, each on its own.
+// (compiled with -ffp-contract=off: only the fma() calls below fuse)
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstdint>
+
+#include "api_internal.h"
+
+using namespace cholmi;
+
+namespace {
+
+enum { MODE_POTRF = 0, MODE_POTRS = 1, MODE_POSV = 2 };
+constexpr int BATCHED_THREADS = 256;  // four wavefronts, nothing shared between them
+constexpr int NO_FAILURE = 0x7f7f7f7f;  // (what hipMemset of 0x7f leaves in the first-failure word)
+
+template <typename T>
+struct BatchedArgs {
+  T *A, *B;
+  long lda, strideA, ldb, strideB;
+  int n, nrhs, batch;
+  int vec;     // A's image allows 16-byte accesses of whole rows (Upper)
+  int *info;   // batch words
+  int *first;  // min over the failing matrices of b + 1
+};
+
+__device__ __forceinline__ float readlane(float x, int l) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l));
+}
+__device__ __forceinline__ double readlane(double x, int l) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), l),
+                          __builtin_amdgcn_readlane(__double2loint(x), l));
+}
+// x of lane `src` of this lane's sub-group (src a compile-time constant after unrolling)
+template <typename T, int NP>
+__device__ __forceinline__ T bcast(T x, int src) {
+  if constexpr (NP == 64) return readlane(x, src);
+  else return __shfl(x, src, NP);
+}
+__device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fma_(double a, double b, double c) { return __builtin_fma(a, b, c); }
+__device__ __forceinline__ float sqrt_(float a) { return __builtin_sqrtf(a); }
+__device__ __forceinline__ double sqrt_(double a) { return __builtin_sqrt(a); }
+
+template <typename T>
+struct Vec16;
+template <>
+struct Vec16<float> {
+  using type = float4;
+};
+template <>
+struct Vec16<double> {
+  using type = double2;
+};
+
+// Row i of the `uplo` triangle into a[] (live: this lane has a row; entries beyond the triangle: +0).  Every a[m] is
+// assigned once, from a value of its own: zeroing the array first and loading under a branch makes the compiler keep
+// a[] as one vector, copied whole at every branch, which spills at NP = 16 and 32.
+template <typename T, int NP, bool UPPER>
+__device__ __forceinline__ void load_rows(T (&a)[NP], const T *Ab, long lda, int n, int i, bool live, bool vec) {
+  if constexpr (!UPPER) {
+#pragma unroll
+    for (int m = 0; m < NP; ++m) {
+      T v = T(0);
+      if (m < n && live && i >= m) v = Ab[i + (long)m * lda];
+      a[m] = v;
+    }
+  } else {
+    constexpr int W = 16 / (int)sizeof(T);
+    using V = typename Vec16<T>::type;
+    const T *row = Ab + (long)i * lda;
+#pragma unroll
+    for (int c = 0; c < NP; c += W) {
+      V v = {};
+      T *e = reinterpret_cast<T *>(&v);
+      if (c < n && live) {
+        if (vec && c + W - 1 <= i) {
+          v = *reinterpret_cast<const V *>(row + c);
+        } else {
+#pragma unroll
+          for (int q = 0; q < W; ++q)
+            if (c + q <= i) e[q] = row[c + q];
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < W; ++q) a[c + q] = e[q];
+    }
+  }
+}
+
+// The columns < cols of row i back into the triangle
+template <typename T, int NP, bool UPPER>
+__device__ __forceinline__ void store_rows(const T (&a)[NP], T *Ab, long lda, int cols, int i, bool live, bool vec) {
+  if constexpr (!UPPER) {
+#pragma unroll
+    for (int m = 0; m < NP; ++m)
+      if (m < cols && live && i >= m) Ab[i + (long)m * lda] = a[m];
+  } else {
+    constexpr int W = 16 / (int)sizeof(T);
+    using V = typename Vec16<T>::type;
+    T *row = Ab + (long)i * lda;
+#pragma unroll
+    for (int c = 0; c < NP; c += W) {
+      if (c < cols && live) {
+        if (vec && c + W - 1 <= i && c + W <= cols) {
+          V v;
+          T *e = reinterpret_cast<T *>(&v);
+#pragma unroll
+          for (int q = 0; q < W; ++q) e[q] = a[c + q];
+          *reinterpret_cast<V *>(row + c) = v;
+        } else {
+#pragma unroll
+          for (int q = 0; q < W; ++q)
+            if (c + q <= i && c + q < cols) row[c + q] = a[c + q];
+        }
+      }
+    }
+  }
+}
+
+// Registers: the row is NP sizeof(T) / 4 VGPRs -- 128 at fp64 and order 64, which with the solve's values stays under
+// 168 (three wavefronts per SIMD).  The launch bound of 256 lanes allows all 512 registers; no kernel takes AGPRs or
+// scratch (DESIGN.md 3m has the table).
+template <typename T, int NP, bool UPPER, int MODE>
+__global__ __launch_bounds__(BATCHED_THREADS) void k_batched(BatchedArgs<T> p) {
+  constexpr int M = 64 / NP;  // matrices per wavefront
+  const int lane = threadIdx.x & 63;
+  const long wave = (long)blockIdx.x * (BATCHED_THREADS / 64) + (threadIdx.x >> 6);
+  if (wave * M >= p.batch) return;  // (a whole wavefront: the shuffles below never see a partly exited one)
+  const int sub = lane / NP, i = lane % NP, n = p.n;
+  const long b = wave * M + sub;
+  const bool live = b < p.batch && i < n;
+  T *Ab = p.A + (live ? b : 0) * p.strideA;
+
+  T a[NP];
+  load_rows<T, NP, UPPER>(a, Ab, p.lda, n, i, live, p.vec != 0);
+
+  int bad = 0;  // LAPACK's info of this lane's matrix: the same in every lane of the sub-group
+  T r = T(0);   // 1 / L(i,i)
+  if constexpr (MODE != MODE_POTRS) {
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      if (j < n) {
+        const T d = bcast<T, NP>(a[j], j);
+        if (!bad && !(d > T(0))) bad = j + 1;
+        const T piv = sqrt_(d), rj = T(1) / piv;
+        a[j] = i == j ? piv : a[j] * rj;
+        if (i == j) r = rj;
+#pragma unroll
+        for (int m = j + 1; m < NP; ++m)
+          if ((m & ~7) < n) a[m] = fma_(-a[j], bcast<T, NP>(a[j], m), a[m]);
+      }
+    }
+    // (a failed matrix: the columns before the failing one are final and stored, the rest stays as it was given)
+    store_rows<T, NP, UPPER>(a, Ab, p.lda, bad ? bad - 1 : n, i, live, p.vec != 0);
+  } else {
+    T d = T(1);
+#pragma unroll
+    for (int k = 0; k < NP; ++k)
+      if (i == k) d = a[k];
+    const unsigned long long z = __ballot(live && d == T(0)) >> (sub * NP) & (NP == 64 ? ~0ull : (1ull << NP) - 1);
+    if (z) bad = __ffsll((long long)z);
+    r = live ? T(1) / d : T(0);
+  }
+  if (live && i == 0) {
+    p.info[b] = bad;
+    if (bad) atomicMin(p.first, (int)(b < INT_MAX ? b + 1 : INT_MAX));
+  }
+
+  if constexpr (MODE != MODE_POTRF) {
+    const bool wr = live && !bad;  // (a failed matrix computes on, in its own lanes, and stores nothing)
+    T *Bb = p.B + (live ? b : 0) * p.strideB + i;
+    for (int c = 0; c < p.nrhs; ++c) {
+      T *at = Bb + (long)c * p.ldb;
+      T v = wr ? *at : T(0);
+#pragma unroll
+      for (int j = 0; j < NP; ++j) {
+        if (j < n) {
+          const T yj = bcast<T, NP>(v * r, j);
+          if (i > j) v = fma_(-a[j], yj, v);
+        }
+      }
+      const T y = v * r;
+      T x = T(0);
+#pragma unroll
+      for (int j = NP - 1; j >= 0; --j) {
+        if (j < n) {
+          T t = i > j ? a[j] * x : T(0);
+#pragma unroll
+          for (int off = NP / 2; off >= 1; off >>= 1) t = t + __shfl_xor(t, off, NP);
+          const T cand = (y - t) * r;
+          if (i == j) x = cand;
+        }
+      }
+      if (wr) *at = x;
+    }
+  }
+}
+
+template <typename T, int NP, bool UPPER>
+void launch_mode(int mode, hipStream_t s, unsigned grid, const BatchedArgs<T> &p) {
+  if (mode == MODE_POTRF) k_batched<T, NP, UPPER, MODE_POTRF><<<grid, BATCHED_THREADS, 0, s>>>(p);
+  else if (mode == MODE_POTRS) k_batched<T, NP, UPPER, MODE_POTRS><<<grid, BATCHED_THREADS, 0, s>>>(p);
+  else k_batched<T, NP, UPPER, MODE_POSV><<<grid, BATCHED_THREADS, 0, s>>>(p);
+}
+template <typename T, int NP>
+void launch_uplo(bool upper, int mode, hipStream_t s, unsigned grid, const BatchedArgs<T> &p) {
+  if (upper) launch_mode<T, NP, true>(mode, s, grid, p);
+  else launch_mode<T, NP, false>(mode, s, grid, p);
+}
+inline int padded_order(int n) { return n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64; }
+template <typename T>
+void launch_batched(bool upper, int mode, hipStream_t s, unsigned grid, const BatchedArgs<T> &p) {
+  switch (padded_order(p.n)) {
+    case 8: return launch_uplo<T, 8>(upper, mode, s, grid, p);
+    case 16: return launch_uplo<T, 16>(upper, mode, s, grid, p);
+    case 32: return launch_uplo<T, 32>(upper, mode, s, grid, p);
+    default: return launch_uplo<T, 64>(upper, mode, s, grid, p);
+  }
+}
+
+// ---------------------------------------------------------------- host
+ScratchPool<1> bt;  // [0]: the first-failure word, then (at 16 bytes) the batch words of info
+hipEvent_t bt_ev[4] = {};
+double bt_stats[8] = {};
+
+// the position of each argument in an entry point's signature (0: it has none)
+struct ArgPos {
+  int uplo, dtype, n, nrhs, A, lda, strideA, B, ldb, strideB, batch;
+};
+constexpr ArgPos POS_POTRF = {1, 2, 3, 0, 4, 5, 6, 0, 0, 0, 7};
+constexpr ArgPos POS_SOLVE = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+
+// bytes from the base to the end of the last element of `batch` images of rows x cols
+inline unsigned long long span_bytes(long long rows, long long cols, long long ld, long long stride, long long batch,
+                                     size_t es) {
+  if (!rows || !cols || !batch) return 0;
+  return ((unsigned long long)(batch - 1) * stride + (unsigned long long)(cols - 1) * ld + rows) * es;
+}
+
+int run_batched(const char *what, int mode, const ArgPos &pos, int uplo, int dtype, int n, int nrhs, void *A, int lda,
+                long long strideA, void *B, int ldb, long long strideB, int batch, int *info) {
+  if (!ctx_inited()) return failf(CHOL_ERR_NOT_INITIALIZED, "%s before chol_init", what);
+  const bool solve = mode != MODE_POTRF;
+  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return failf(-pos.uplo, "%s: uplo", what);
+  if (dtype != CHOL_REAL_DOUBLE && dtype != CHOL_REAL_FLOAT)
+    return failf(-pos.dtype, "%s: dtype must be fp64 or fp32", what);
+  if (n < 0) return failf(-pos.n, "%s: n < 0", what);
+  if (solve && nrhs < 0) return failf(-pos.nrhs, "%s: nrhs < 0", what);
+  if (batch < 0) return failf(-pos.batch, "%s: batch < 0", what);
+  if (n > 64)
+    return failf(CHOL_ERR_NOT_SUPPORTED,
+                 "%s: n > 64; use chol_potrf_batch (tiles that are multiples of 128) or the descriptor routines "
+                 "(chol_potrf_tile, chol_potrs_tile, chol_posv_tile)", what);
+  if (lda < (n > 1 ? n : 1)) return failf(-pos.lda, "%s: lda < max(1, n)", what);
+  if (strideA < (long long)lda * n) return failf(-pos.strideA, "%s: strideA < lda * n", what);
+  if (solve) {
+    if (ldb < (n > 1 ? n : 1)) return failf(-pos.ldb, "%s: ldb < max(1, n)", what);
+    if (strideB < (long long)ldb * nrhs) return failf(-pos.strideB, "%s: strideB < ldb * nrhs", what);
+  }
+  if (n == 0 || batch == 0 || (mode == MODE_POTRS && nrhs == 0)) {
+    for (int b = 0; info && b < batch; ++b) info[b] = 0;
+    return 0;
+  }
+  const bool rhs = solve && nrhs > 0;
+  const size_t es = dtype == CHOL_REAL_DOUBLE ? sizeof(double) : sizeof(float);
+  if (!A || !is_device_ptr(A)) return failf(-pos.A, "%s: A must be a device pointer", what);
+  if (rhs) {
+    if (!B || !is_device_ptr(B)) return failf(-pos.B, "%s: B must be a device pointer", what);
+    const uintptr_t a0 = (uintptr_t)A, b0 = (uintptr_t)B;
+    const uintptr_t a1 = a0 + span_bytes(n, n, lda, strideA, batch, es);
+    const uintptr_t b1 = b0 + span_bytes(n, nrhs, ldb, strideB, batch, es);
+    if (a0 < b1 && b0 < a1) return failf(-pos.B, "%s: the address ranges of A and B overlap", what);
+  }
+
+  return with_views({}, [&]() -> int {
+    hipStream_t s = main_rank_ctx()->st[ST_MAIN];
+    if (int rc = bt.ensure_bytes(0, 16 + (size_t)batch * sizeof(int), what)) return rc;
+    for (hipEvent_t &e : bt_ev)
+      if (!e) HIPCHECK(hipEventCreate(&e));
+    int *first = bt.as<int>(0), *dinfo = first + 4;
+    const int NP = padded_order(n), per_wave = 64 / NP;
+    const long long waves = ((long long)batch + per_wave - 1) / per_wave;
+    const unsigned grid = (unsigned)((waves + BATCHED_THREADS / 64 - 1) / (BATCHED_THREADS / 64));
+    const bool vec = (uintptr_t)A % 16 == 0 && (size_t)lda * es % 16 == 0 && (unsigned long long)strideA * es % 16 == 0;
+
+    // events: the whole call [0] .. [3], the kernel [1] .. [2]
+    HIPCHECK(hipEventRecord(bt_ev[0], s));
+    HIPCHECK(hipMemsetAsync(first, 0x7f, sizeof(int), s));
+    HIPCHECK(hipEventRecord(bt_ev[1], s));
+    const int kmode = rhs ? mode : MODE_POTRF;  // (posv without a right-hand side factors)
+    if (dtype == CHOL_REAL_DOUBLE) {
+      const BatchedArgs<double> p = {(double *)A, (double *)B, lda,   strideA, ldb,   strideB,
+                                     n,           nrhs,        batch, vec,     dinfo, first};
+      launch_batched<double>(uplo == CHOL_UPPER, kmode, s, grid, p);
+    } else {
+      const BatchedArgs<float> p = {(float *)A, (float *)B, lda,   strideA, ldb,   strideB,
+                                    n,          nrhs,       batch, vec,     dinfo, first};
+      launch_batched<float>(uplo == CHOL_UPPER, kmode, s, grid, p);
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipEventRecord(bt_ev[2], s));
+    int head = NO_FAILURE;
+    HIPCHECK(hipMemcpyAsync(&head, first, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (info) HIPCHECK(hipMemcpyAsync(info, dinfo, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipEventRecord(bt_ev[3], s));
+    HIPCHECK(hipStreamSynchronize(s));
+    float total = 0, kern = 0;
+    HIPCHECK(hipEventElapsedTime(&total, bt_ev[0], bt_ev[3]));
+    HIPCHECK(hipEventElapsedTime(&kern, bt_ev[1], bt_ev[2]));
+
+    const double tri = 0.5 * n * (n + 1.0), rhs_el = rhs ? 2.0 * n * nrhs : 0.0;
+    const double el = (mode == MODE_POTRS ? tri : 2.0 * tri) + rhs_el;
+    const double st[8] = {total, kern, (double)batch, (double)n, (double)per_wave, (double)grid, el * es * batch, 0.0};
+    std::copy(st, st + 8, bt_stats);
+    return head == NO_FAILURE ? 0 : head;
+  });
+}
+
+}  // namespace
+
+void cholmi::batched_release() {
+  bt.release();
+  for (hipEvent_t &e : bt_ev) {
+    if (e) (void)hipEventDestroy(e);
+    e = nullptr;
+  }
+}
+
+// ---------------------------------------------------------------- the entry points (C linkage: include/cholmi.h)
+int chol_potrf_batched(int uplo, int dtype, int n, void *A, int lda, long long strideA, int batch, int *info) {
+  return run_batched("potrf_batched", MODE_POTRF, POS_POTRF, uplo, dtype, n, 0, A, lda, strideA, nullptr, 1, 0, batch,
+                     info);
+}
+
+int chol_potrs_batched(int uplo, int dtype, int n, int nrhs, const void *A, int lda, long long strideA, void *B,
+                       int ldb, long long strideB, int batch, int *info) {
+  return run_batched("potrs_batched", MODE_POTRS, POS_SOLVE, uplo, dtype, n, nrhs, const_cast<void *>(A), lda, strideA,
+                     B, ldb, strideB, batch, info);
+}
+
+int chol_posv_batched(int uplo, int dtype, int n, int nrhs, void *A, int lda, long long strideA, void *B, int ldb,
+                      long long strideB, int batch, int *info) {
+  return run_batched("posv_batched", MODE_POSV, POS_SOLVE, uplo, dtype, n, nrhs, A, lda, strideA, B, ldb, strideB,
+                     batch, info);
+}
+
+int chol_last_batched_stats(double *out8) {
+  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "last_batched_stats before chol_init");
+  if (!out8) return fail(-1, "last_batched_stats: NULL");
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  std::copy(bt_stats, bt_stats + 8, out8);
+  return 0;
+}

@@ -406,6 +406,51 @@ int chol_chex_tile(int uplo, chol_desc_t *A, int k, int l, int job);
  * in-tile appliers; job 1: the coefficient chain) and bulk applier time [ms]; job; l - k; the rest 0. */
 int chol_last_chex_stats(double *out8);
 
+/* Batched Cholesky of small matrices: `batch` independent SPD matrices of order 0 <= n <= 64 (10^3 .. 10^6 of them is
+ * the regime), without descriptors.  Matrix b is column-major at A + b strideA elements with leading dimension
+ * lda >= max(1,n), strideA >= lda n; B likewise, n x nrhs, ldb >= max(1,n), strideB >= ldb nrhs.  A and B are device
+ * pointers (a host pointer is an argument error); nothing beyond element alignment is assumed (lda may be odd, the
+ * base may sit one element past a 16-byte boundary); every offset is computed in 64 bits.  fp64 or fp32 by dtype
+ * (CHOL_REAL_DOUBLE / CHOL_REAL_FLOAT), fp32 in single precision throughout; CHOL_LOWER and CHOL_UPPER.  Only the
+ * `uplo` triangle of each matrix is read or written: the other strict triangle, the lda - n rows under each column,
+ * the gap between matrices, and the same places of B come back bit for bit and may hold NaN.  n > 64 returns
+ * CHOL_ERR_NOT_SUPPORTED (chol_potrf_batch takes tiles that are multiples of 128, the descriptor routines any order).
+ * Zero sizes (n, batch; nrhs for potrs) return 0 with nothing written on the device.
+ *
+ * The calls are synchronous and run on the library's main stream.  info: a host array of `batch` ints, or NULL;
+ * info[b] is LAPACK's info of matrix b.  Returns 0 when every info[b] is 0, else b + 1 (1-based) of the first matrix
+ * with info[b] > 0; negative: the position of a bad argument in the signature (lda, ldb or a stride too small, the
+ * address ranges of A and B overlapping (B's position) included) or CHOL_ERR_*.  A failing matrix never disturbs
+ * another one, also not one that shares its wavefront.
+ *
+ * potrf, the arithmetic fixed (uplo only says where L is stored, Upper holds U = L^T; each a b + c one fused
+ * multiply-add, sqrt and the division correctly rounded):
+ *   for j = 0..n-1:  s_i = A(i,j) (i >= j);  for k = 0..j-1 ascending: s_i = fma(-L(i,k), L(j,k), s_i);
+ *     if !(s_j > 0): info = j+1, stop;  L(j,j) = sqrt(s_j);  r_j = 1 / L(j,j);  L(i,j) = s_i r_j (i > j).
+ *   On info = j+1 the columns before j+1 hold the factor's, the rest of the triangle is as it was given.
+ * potrs, B <- inv(L L^T) B from the factor, one column of B at a time and each on its own (r_j = 1 / L(j,j), P = 8,
+ * 16, 32 or 64 the least of them >= n):
+ *   forward   for j = 0..n-1:  y_j = b_j r_j;  b_i = fma(-L(i,j), y_j, b_i) (i > j)
+ *   backward  for j = n-1..0:  t_i = L(i,j) x_i (j < i < n), +0 for the other i < P;
+ *             for off = P/2, P/4, .., 1: t_i = t_i + t_(i xor off) (all i at once);  x_j = (y_j - t_j) r_j
+ *   The order depends on n alone: not on uplo, nrhs, the matrix's place in the batch or its wavefront's other matrices.
+ *   An exact zero on the stored diagonal gives info[b] = j (1-based, the first) and leaves that matrix's B untouched,
+ *   as chol_trtrs_tile does.
+ * posv: potrf then potrs in one pass, the factor never read back from memory; the same bits as the two calls.  With
+ * info[b] > 0 that matrix's B is untouched.
+ *
+ * Argument positions: potrf 1 uplo, 2 dtype, 3 n, 4 A, 5 lda, 6 strideA, 7 batch; potrs and posv 1 uplo, 2 dtype, 3 n,
+ * 4 nrhs, 5 A, 6 lda, 7 strideA, 8 B, 9 ldb, 10 strideB, 11 batch. */
+int chol_potrf_batched(int uplo, int dtype, int n, void *A, int lda, long long strideA, int batch, int *info);
+int chol_potrs_batched(int uplo, int dtype, int n, int nrhs, const void *A, int lda, long long strideA, void *B,
+                       int ldb, long long strideB, int batch, int *info);
+int chol_posv_batched(int uplo, int dtype, int n, int nrhs, void *A, int lda, long long strideA, void *B, int ldb,
+                      long long strideB, int batch, int *info);
+/* The last batched call: total time and kernel time [ms] (the library's own events); batch; n; matrices per wavefront;
+ * workgroups launched; the bytes the algorithm must move (the stored triangles read and written, plus B read and
+ * written); 0. */
+int chol_last_batched_stats(double *out8);
+
 /* One half of a Cholesky factor alone: the triangular solve, the triangular product and the log-determinant, on
  * device-resident single-process descriptors with the rules of chol_potrs_tile: A square (ragged orders and
  * sub-matrix views included), stored tile edge a multiple of 64; B n x nrhs with A's dtype, order and tile size, any
