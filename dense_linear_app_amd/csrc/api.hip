@@ -585,10 +585,7 @@ static int mfma_probe_on(RankCtx *r, int dtype, int waves_per_simd, int iters, d
   double best = 0;
   for (int rep = 0; rep < 4; ++rep) {
     HIPCHECK(hipEventRecord(e0, r->st[ST_MAIN]));
-    if (dtype == CHOL_REAL_DOUBLE)
-      launch_mfma_probe<double>(r->st[ST_MAIN], (double *)buf, blocks, iters);
-    else
-      launch_mfma_probe<float>(r->st[ST_MAIN], (float *)buf, blocks, iters);
+    by_dtype(dtype, [&](auto t) { launch_mfma_probe<decltype(t)>(r->st[ST_MAIN], (decltype(t) *)buf, blocks, iters); });
     HIPCHECK(hipEventRecord(e1, r->st[ST_MAIN]));
     HIPCHECK(hipStreamSynchronize(r->st[ST_MAIN]));
     float ms = 0;
@@ -695,10 +692,9 @@ void forget_winv(const void *ptr) {
 }
 
 void transpose_storage(chol_desc *A) {
-  if (A->dtype == CHOL_REAL_DOUBLE)
-    launch_transpose_inplace<double>(g.r.st[ST_MAIN], (double *)A->mat, A->nt, A->mbi);
-  else
-    launch_transpose_inplace<float>(g.r.st[ST_MAIN], (float *)A->mat, A->nt, A->mbi);
+  by_dtype(A->dtype, [&](auto t) {
+    launch_transpose_inplace<decltype(t)>(g.r.st[ST_MAIN], (decltype(t) *)A->mat, A->nt, A->mbi);
+  });
 }
 
 int through_lower(bool upper, std::initializer_list<chol_desc *> ds, const std::function<int()> &body, bool wait,
@@ -715,19 +711,19 @@ LocalMat whole_local_mat(const chol_desc *d) { return local_mat(d, d->mat); }
 
 // (posvx factors AF inside its own view refresh)
 int potrf_run(int uplo, chol_desc *A) {
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  if (uplo == CHOL_LOWER)
-    return A->dtype == CHOL_REAL_DOUBLE ? potrf_impl<double>(A) : potrf_impl<float>(A);
+  // (under the context lock: every caller is a with_views body)
+  auto lower = [&](bool upper_staged) {
+    return by_dtype(A->dtype, [&](auto t) { return potrf_impl<decltype(t)>(A, upper_staged); });
+  };
+  if (uplo == CHOL_LOWER) return lower(false);
   // ChamUpper: A = U^T U with U = L^T.  Transpose the stored matrix in place (its upper
   // triangle becomes the lower one), factor Lower, transpose back: the upper triangle now
   // holds U and the caller's strict lower triangle is bit-for-bit what it was.
   const bool one = single_tile_square(A);
   if (!one && (A->p * A->q != 1 || !A->on_device || A->mt != A->nt))
     return fail(CHOL_ERR_NOT_SUPPORTED, "potrf_tile(Upper): single-process device-resident square matrices");
-  if (one && !(A->on_device && A->mb % MACRO == 0))
-    return A->dtype == CHOL_REAL_DOUBLE ? potrf_impl<double>(A, true) : potrf_impl<float>(A, true);
-  return through_lower(true, {A},
-                       [&] { return A->dtype == CHOL_REAL_DOUBLE ? potrf_impl<double>(A) : potrf_impl<float>(A); });
+  if (one && !(A->on_device && A->mb % MACRO == 0)) return lower(true);
+  return through_lower(true, {A}, [&] { return lower(false); });
 }
 
 void *DevPool::get(size_t bytes) {
@@ -1102,10 +1098,9 @@ int chol_internal_desc_create(chol_desc_t **desc, void *mat, int dtype, int mb, 
     d->on_device = true;
     if (d->padded && lm == ln) {  // zero everywhere, identity on the diagonal tiles' diagonals
       const LocalMat Lm = local_mat(d, d->mat);
-      if (dtype == CHOL_REAL_DOUBLE)
-        launch_plgsy<double>(g.r.st[ST_MAIN], Lm, d->lnt, d->prow, d->pcol, 0.0, 0ull, 0, 0, 0);
-      else
-        launch_plgsy<float>(g.r.st[ST_MAIN], Lm, d->lnt, d->prow, d->pcol, 0.0, 0ull, 0, 0, 0);
+      by_dtype(dtype, [&](auto t) {
+        launch_plgsy<decltype(t)>(g.r.st[ST_MAIN], Lm, d->lnt, d->prow, d->pcol, 0.0, 0ull, 0, 0, 0);
+      });
       (void)hipStreamSynchronize(g.r.st[ST_MAIN]);
     } else {  // library-owned storage starts at zero (tiles a one-sided dplgsy does not touch)
       (void)hipMemsetAsync(d->mat, 0, bytes, g.r.st[ST_MAIN]);
@@ -1193,7 +1188,7 @@ static int flush_pending_t() {
 namespace {
 int tx_flush_pending() {
   if (!tx.ready || !tx.pend.on) return 0;
-  return tx.pend.dtype == CHOL_REAL_DOUBLE ? flush_pending_t<double>() : flush_pending_t<float>();
+  return by_dtype(tx.pend.dtype, [](auto t) { return flush_pending_t<decltype(t)>(); });
 }
 }  // namespace
 
@@ -1377,8 +1372,9 @@ int chol_potrf_batch(int dtype, int mb, int n, const void *const *a_in, void *co
   if (!a_in || !a_out || !slots) return fail(-4, "potrf_batch: NULL pointer list");
   std::lock_guard<std::recursive_mutex> lk(g_mu);
   const bool defer = (flags & CHOL_BATCH_ASYNC) != 0;
-  const int rc = dtype == CHOL_REAL_DOUBLE ? potrf_batch_impl<double>(dtype, mb, n, a_in, a_out, versions, slots, defer)
-                                           : potrf_batch_impl<float>(dtype, mb, n, a_in, a_out, versions, slots, defer);
+  const int rc = by_dtype(dtype, [&](auto t) {
+    return potrf_batch_impl<decltype(t)>(dtype, mb, n, a_in, a_out, versions, slots, defer);
+  });
   if (rc) return rc;
   if (!(flags & CHOL_BATCH_ASYNC)) return tx_quiesce();
   return 0;
@@ -1412,8 +1408,9 @@ int chol_tile_batch(int op, int dtype, int mb, int n, const void *const *c_in, c
     for (int t = 0; t < n; ++t)
       if (!b[t]) return fail(-7, "tile_batch: NULL b operand of a GEMM task");
   std::lock_guard<std::recursive_mutex> lk(g_mu);
-  const int rc = dtype == CHOL_REAL_DOUBLE ? tile_batch_impl<double>(op, dtype, mb, n, c_in, a, b, c_out, a_versions, flags)
-                                           : tile_batch_impl<float>(op, dtype, mb, n, c_in, a, b, c_out, a_versions, flags);
+  const int rc = by_dtype(dtype, [&](auto t) {
+    return tile_batch_impl<decltype(t)>(op, dtype, mb, n, c_in, a, b, c_out, a_versions, flags);
+  });
   if (rc) return rc;
   if (!(flags & CHOL_BATCH_ASYNC)) return tx_quiesce();
   return 0;
@@ -1560,8 +1557,7 @@ int chol_trsm_tile(int side, int uplo, int trans, int diag, double alpha, chol_d
     return fail(CHOL_ERR_NOT_SUPPORTED, "trsm_tile: only (Right, Lower, Trans, NonUnit)");
   if (!single_tile_square(A) || !single_tile_square(B) || A->mb != B->mb || A->dtype != B->dtype)
     return fail(CHOL_ERR_NOT_SUPPORTED, "trsm_tile: needs two 1-tile descriptors of equal size and type");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  return A->dtype == CHOL_REAL_DOUBLE ? trsm_impl<double>(alpha, A, B) : trsm_impl<float>(alpha, A, B);
+  return by_dtype(A->dtype, [&](auto t) { return trsm_impl<decltype(t)>(alpha, A, B); });
   });
 }
 
@@ -1577,9 +1573,7 @@ int chol_syrk_tile(int uplo, int trans, double alpha, chol_desc_t *A, double bet
     return fail(CHOL_ERR_NOT_SUPPORTED, "syrk_tile: only (Lower, NoTrans)");
   if (!single_tile_square(A) || !single_tile_square(C) || A->mb != C->mb || A->dtype != C->dtype)
     return fail(CHOL_ERR_NOT_SUPPORTED, "syrk_tile: needs two 1-tile descriptors of equal size and type");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  return A->dtype == CHOL_REAL_DOUBLE ? gemm_impl<double>(alpha, A, A, beta, C, true)
-                                      : gemm_impl<float>(alpha, A, A, beta, C, true);
+  return by_dtype(A->dtype, [&](auto t) { return gemm_impl<decltype(t)>(alpha, A, A, beta, C, true); });
   });
 }
 
@@ -1597,9 +1591,7 @@ int chol_gemm_tile(int transA, int transB, double alpha, chol_desc_t *A, chol_de
   if (!single_tile_square(A) || !single_tile_square(B) || !single_tile_square(C) || A->mb != C->mb ||
       B->mb != C->mb || A->dtype != C->dtype || B->dtype != C->dtype)
     return fail(CHOL_ERR_NOT_SUPPORTED, "gemm_tile: needs three 1-tile descriptors of equal size and type");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  return A->dtype == CHOL_REAL_DOUBLE ? gemm_impl<double>(alpha, A, B, beta, C, false)
-                                      : gemm_impl<float>(alpha, A, B, beta, C, false);
+  return by_dtype(A->dtype, [&](auto t) { return gemm_impl<decltype(t)>(alpha, A, B, beta, C, false); });
   });
 }
 
@@ -1613,12 +1605,10 @@ int chol_plgsy_tile(double bump, int uplo, chol_desc_t *A, unsigned long long se
   if (!A->on_device) return fail(CHOL_ERR_NOT_SUPPORTED, "plgsy_tile: descriptor must be device-resident");
   if (A->mt == 1 && A->nt == 1 && (A->m != A->mb || A->n != A->nb) && !A->padded)
     return fail(CHOL_ERR_NOT_SUPPORTED, "plgsy_tile: partial single tile");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
   const LocalMat L = local_mat(A, A->mat);
-  if (A->dtype == CHOL_REAL_DOUBLE)
-    launch_plgsy<double>(g.r.st[ST_MAIN], L, A->lnt, A->prow, A->pcol, bump, seed, A->mb, (long)A->lm, side);
-  else
-    launch_plgsy<float>(g.r.st[ST_MAIN], L, A->lnt, A->prow, A->pcol, bump, seed, A->mb, (long)A->lm, side);
+  by_dtype(A->dtype, [&](auto t) {
+    launch_plgsy<decltype(t)>(g.r.st[ST_MAIN], L, A->lnt, A->prow, A->pcol, bump, seed, A->mb, (long)A->lm, side);
+  });
   HIPCHECK(hipStreamSynchronize(g.r.st[ST_MAIN]));
   return 0;
   });
@@ -1634,12 +1624,11 @@ int chol_lacpy_tile(int uplo, chol_desc_t *A, chol_desc_t *B) {
   rc = resident_whole("lacpy_tile", B);
   if (rc) return rc;
   if (!same_geometry(A, B)) return fail(-3, "lacpy_tile: descriptors differ in shape, tiling or type");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
   const int side = uplo == CHOL_LOWER ? 1 : uplo == CHOL_UPPER ? 2 : 0;
-  if (A->dtype == CHOL_REAL_DOUBLE)
-    launch_lacpy<double>(g.r.st[ST_MAIN], geo_of(A), side, (const double *)A->mat, (double *)B->mat);
-  else
-    launch_lacpy<float>(g.r.st[ST_MAIN], geo_of(A), side, (const float *)A->mat, (float *)B->mat);
+  by_dtype(A->dtype, [&](auto t) {
+    using T = decltype(t);
+    launch_lacpy<T>(g.r.st[ST_MAIN], geo_of(A), side, (const T *)A->mat, (T *)B->mat);
+  });
   HIPCHECK(hipStreamSynchronize(g.r.st[ST_MAIN]));
   return 0;
   });
@@ -1654,11 +1643,10 @@ int chol_geadd_tile(int trans, double alpha, chol_desc_t *A, double beta, chol_d
   rc = resident_whole("geadd_tile", B);
   if (rc) return rc;
   if (!same_geometry(A, B)) return fail(-5, "geadd_tile: descriptors differ in shape, tiling or type");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
-  if (A->dtype == CHOL_REAL_DOUBLE)
-    launch_geadd<double>(g.r.st[ST_MAIN], geo_of(A), alpha, (const double *)A->mat, beta, (double *)B->mat);
-  else
-    launch_geadd<float>(g.r.st[ST_MAIN], geo_of(A), alpha, (const float *)A->mat, beta, (float *)B->mat);
+  by_dtype(A->dtype, [&](auto t) {
+    using T = decltype(t);
+    launch_geadd<T>(g.r.st[ST_MAIN], geo_of(A), alpha, (const T *)A->mat, beta, (T *)B->mat);
+  });
   HIPCHECK(hipStreamSynchronize(g.r.st[ST_MAIN]));
   return 0;
   });
@@ -1678,15 +1666,11 @@ int chol_lange_tile(int norm, chol_desc_t *A, double *value) {
   }
   int rc = resident_whole("lange_tile", A);
   if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
   const TileGeo ge = geo_of(A);
   int rcw = g.work.ensure_bytes(0, (size_t)(std::max(ge.m, ge.n) + 2) * sizeof(double), "lange_tile");
   if (rcw) return rcw;
   double *work = g.work.as<double>(0);
-  if (A->dtype == CHOL_REAL_DOUBLE)
-    launch_lange<double>(g.r.st[ST_MAIN], ge, kind, (const double *)A->mat, work);
-  else
-    launch_lange<float>(g.r.st[ST_MAIN], ge, kind, (const float *)A->mat, work);
+  by_dtype(A->dtype, [&](auto t) { launch_lange<decltype(t)>(g.r.st[ST_MAIN], ge, kind, (const decltype(t) *)A->mat, work); });
   double v = 0;
   hipError_t e = hipMemcpyAsync(&v, work, sizeof(double), hipMemcpyDeviceToHost, g.r.st[ST_MAIN]);
   if (e == hipSuccess) e = hipStreamSynchronize(g.r.st[ST_MAIN]);
@@ -1704,7 +1688,6 @@ int chol_lauum_tile(int uplo, chol_desc_t *A) {
   if (rc) return rc;
   if (A->mt != A->nt || A->lm != A->ln) return fail(-2, "lauum_tile: matrix is not square");
   if (A->mbi % 64) return fail(CHOL_ERR_NOT_SUPPORTED, "lauum_tile: stored tile edge must be a multiple of 64");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
   const size_t bytes = (size_t)A->mt * A->nt * A->bsizi * A->esize;
   void *tmp = nullptr;
   if (hipMalloc(&tmp, bytes) != hipSuccess) {
@@ -1716,13 +1699,11 @@ int chol_lauum_tile(int uplo, chol_desc_t *A) {
   ge.mbu = ge.mbs;
   ge.m = (long)ge.lmt * ge.mbs;
   ge.n = (long)ge.lnt * ge.mbs;
-  if (A->dtype == CHOL_REAL_DOUBLE) {
-    launch_lauum_lower<double>(g.r.st[ST_MAIN], (const double *)A->mat, (double *)tmp, A->nt, A->mbi);
-    launch_lacpy<double>(g.r.st[ST_MAIN], ge, 1, (const double *)tmp, (double *)A->mat);
-  } else {
-    launch_lauum_lower<float>(g.r.st[ST_MAIN], (const float *)A->mat, (float *)tmp, A->nt, A->mbi);
-    launch_lacpy<float>(g.r.st[ST_MAIN], ge, 1, (const float *)tmp, (float *)A->mat);
-  }
+  by_dtype(A->dtype, [&](auto t) {
+    using T = decltype(t);
+    launch_lauum_lower<T>(g.r.st[ST_MAIN], (const T *)A->mat, (T *)tmp, A->nt, A->mbi);
+    launch_lacpy<T>(g.r.st[ST_MAIN], ge, 1, (const T *)tmp, (T *)A->mat);
+  });
   hipError_t e = hipStreamSynchronize(g.r.st[ST_MAIN]);
   (void)hipFree(tmp);
   if (e != hipSuccess) return fail_hip(e, "lauum_tile", __FILE__, __LINE__);
@@ -1801,7 +1782,6 @@ static int residual_common(chol_desc_t *L, double bump, unsigned long long seed,
   if (!L || (!rel_fro && !rel_inf)) return fail(-1, "residual: NULL");
   if (L->p * L->q != 1 || !L->on_device || L->mt != L->nt || L->mb != L->nb || L->mbi % MACRO)
     return fail(CHOL_ERR_NOT_SUPPORTED, "residual: single-process device-resident square tiled matrix only");
-  std::lock_guard<std::recursive_mutex> lk(g_mu);
   const long n = L->lm;
   double *rows = nullptr;
   if (rel_inf) {
@@ -1809,12 +1789,10 @@ static int residual_common(chol_desc_t *L, double bump, unsigned long long seed,
     HIPCHECK(hipMemsetAsync(rows, 0, 2 * (size_t)n * sizeof(double), g.r.st[ST_MAIN]));
   }
   HIPCHECK(hipMemsetAsync(g.d_acc, 0, 2 * sizeof(double), g.r.st[ST_MAIN]));
-  if (L->dtype == CHOL_REAL_DOUBLE)
-    launch_residual<double>(g.r.st[ST_MAIN], reinterpret_cast<const double *>(L->mat), L->nt, L->mbi, bump, seed,
-                            g.d_acc, L->mb, n, rows);
-  else
-    launch_residual<float>(g.r.st[ST_MAIN], reinterpret_cast<const float *>(L->mat), L->nt, L->mbi, bump, seed,
-                           g.d_acc, L->mb, n, rows);
+  by_dtype(L->dtype, [&](auto t) {
+    launch_residual<decltype(t)>(g.r.st[ST_MAIN], reinterpret_cast<const decltype(t) *>(L->mat), L->nt, L->mbi, bump,
+                                 seed, g.d_acc, L->mb, n, rows);
+  });
   double h[2];
   HIPCHECK(hipMemcpyAsync(h, g.d_acc, sizeof h, hipMemcpyDeviceToHost, g.r.st[ST_MAIN]));
   HIPCHECK(hipStreamSynchronize(g.r.st[ST_MAIN]));
@@ -1872,10 +1850,9 @@ int chol_bench_update(chol_desc_t *d, int k, int ablate, int reps, double *ms, d
   float best = 1e30f;
   for (int r = 0; r <= reps; ++r) {
     HIPCHECK(hipEventRecord(g.r.events[0], g.r.st[ST_MAIN]));
-    if (d->dtype == CHOL_REAL_DOUBLE)
-      launch_trail_update<double>(g.r.st[ST_MAIN], C, d->d_list, rr.off, rr.na, rr.offb, rr.nb, pan);
-    else
-      launch_trail_update<float>(g.r.st[ST_MAIN], C, d->d_list, rr.off, rr.na, rr.offb, rr.nb, pan);
+    by_dtype(d->dtype, [&](auto t) {
+      launch_trail_update<decltype(t)>(g.r.st[ST_MAIN], C, d->d_list, rr.off, rr.na, rr.offb, rr.nb, pan);
+    });
     HIPCHECK(hipEventRecord(g.r.events[1], g.r.st[ST_MAIN]));
     HIPCHECK(hipStreamSynchronize(g.r.st[ST_MAIN]));
     float t = 0;

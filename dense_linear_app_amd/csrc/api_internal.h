@@ -1,7 +1,7 @@
 // What api.hip shares with the other host translation units of the ABI (spd.hip, the routines that work from a factor;
 // batched.hip, the batched small-matrix routines, which use the context, the errors and the scratch pools alone):
-// the context's state, the error reporting, the scratch pools, the view refresh, the descriptor rules, running an Upper
-// call through the Lower path, and a whole-matrix descriptor's trailing update.  Host only: the kernel translation
+// the context's state, the error reporting, the dispatch on the element type, the scratch pools, the view refresh, the
+// descriptor rules, running an Upper call through the Lower path, and a whole-matrix descriptor's trailing update.  Host only: the kernel translation
 // units see cholmi_internal.h alone.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -39,6 +39,13 @@ int scratch_failed(const char *what);
 
 inline int roundup(int x, int m) { return (x + m - 1) / m * m; }
 
+// f(T{}) for the element type T of `dtype` (CHOL_REAL_DOUBLE, else float): the call site is a generic lambda that
+// names the type as decltype of its parameter
+template <typename F>
+auto by_dtype(int dtype, F &&f) {
+  return dtype == CHOL_REAL_DOUBLE ? f(double{}) : f(float{});
+}
+
 // N device buffers, each grown on demand (in whole MiB) and kept until release(); Zero: a buffer is cleared when it
 // grows.  One pool per set of buffers that are live together: two pools never share memory.
 template <int N, bool Zero = false>
@@ -74,10 +81,10 @@ struct ScratchPool {
   }
 };
 
-// One entry point's body between the refresh of its views' images and their write-back, all under the context
-// lock (recursive: the bodies take it again); a failed refresh returns before the body runs, a failed write-back
-// is reported unless the body already failed.  The write-back also follows a body that returned info > 0
-// (a partly factored matrix, as LAPACK leaves it).
+// One entry point's body between the refresh of its views' images and their write-back; a failed refresh returns
+// before the body runs, a failed write-back is reported unless the body already failed.  The write-back also follows
+// a body that returned info > 0 (a partly factored matrix, as LAPACK leaves it).  The body runs under the context
+// lock, so bodies, and what only they call, do not take it again.
 struct ViewArg {
   chol_desc *d;
   bool write_back;
@@ -95,7 +102,7 @@ TileGeo geo_of(const chol_desc *d);
 // that factors, inverts or solves with a tile checks this before any launch writes winv
 bool winv_fits(const chol_desc *d);
 #define CHECK_WINV(d, what) \
-  if (!winv_fits(d)) return fail(CHOL_ERR_NOT_SUPPORTED, what ": tile size above 4096")
+  if (!winv_fits(d)) return failf(CHOL_ERR_NOT_SUPPORTED, "%s: tile size above 4096", what)
 void forget_winv(const void *ptr);  // (a tile that is overwritten: its cached block inverses are stale)
 
 // chol_potrf_tile after its argument checks, on the descriptor's image as it stands

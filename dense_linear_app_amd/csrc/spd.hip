@@ -3,9 +3,11 @@
 // factorisation, the reduction of the generalized symmetric-definite eigenproblem, the L D L^T factorisation without
 // pivoting with its solve, their butterfly-randomised forms, the rank-r update and downdate of a factor, the circular
 // shift of a factor's variables, the halves of a factor alone, and the symmetric product from one stored triangle; the
-// entry points come last.  All run on the main
-// stream of the context that api.hip keeps (api_internal.h); this file owns only its scratch and the statistics of the
-// last call of each family.
+// entry points come last.  All run on the main stream of the context that api.hip keeps (api_internal.h), inside a
+// with_views body and so under the context lock; this file owns only its scratch and the statistics of the last call
+// of each family.  What the routines repeat is said once: the element type by by_dtype (api_internal.h), a timed
+// stretch by timed(), the look for a zero pivot and the Lower path with its launch check by lower_run(), an entry
+// point's name and its first refusals by Entry.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -44,6 +46,7 @@ ScratchPool<4> rb;
 ScratchPool<4, true> tr;
 
 // The statistics of a family's last call: written by the routine under the context lock, read by chol_last_*_stats
+// (which is no with_views body and takes the lock itself)
 struct LastStats {
   double v[8] = {};
   void clear() { std::fill(v, v + 8, 0.0); }
@@ -59,6 +62,20 @@ struct LastStats {
 LastStats mx_stats, cn_stats, rf_stats, ps_stats, sg_stats, cu_stats, cx_stats, sy_stats, rb_stats, tr_stats, sm_stats;
 
 hipStream_t main_stream() { return main_rank_ctx()->st[ST_MAIN]; }
+
+// An entry point's name, its refusals "<what>: <why>", and what the entry points begin with: the refusal before
+// chol_init, then (given an uplo) the uplo rule at argument position pos.  Where another argument's rule stands
+// between the two, the entry point calls begin() and uplo_at() apart; each check stays on its side of with_views
+struct Entry {
+  const char *what;
+  int bad(int code, const char *why) const { return failf(code, "%s: %s", what, why); }
+  int begin() const { return ctx_inited() ? 0 : failf(CHOL_ERR_NOT_INITIALIZED, "%s before chol_init", what); }
+  int uplo_at(int uplo, int pos) const { return uplo == CHOL_LOWER || uplo == CHOL_UPPER ? 0 : bad(-pos, "uplo"); }
+  int begin(int uplo, int pos = 1) const {
+    const int rc = begin();
+    return rc ? rc : uplo_at(uplo, pos);
+  }
+};
 
 // one of the trailing updates (launch_trail_update, launch_syr2k_update, launch_ldl_update) on the tiles of d's columns
 // [jlo, jhi), from the given panels
@@ -97,6 +114,16 @@ struct EventTimer {
     return add(acc);
   }
 };
+
+// body() between the two events of a timer of its own, the time added to *acc; a body that returns non-zero (an
+// error, or an info it found before it wrote anything) returns before the timer is stopped
+template <typename Body>
+int timed(double *acc, const Body &body) {
+  EventTimer tt;
+  if (int rc = tt.start()) return rc;
+  if (int rc = body()) return rc;
+  return tt.stop(acc);
+}
 
 // ---------------------------------------------------------------- solve with the factor
 // X <- A^{-1} B for A = L L^T already factored (CHAMELEON_dpotrs_Tile(ChamLower, A, B)).
@@ -439,12 +466,14 @@ int inverse_check(const char *what, chol_desc *A, int apos) {
 }
 
 // the first exact zero on the diagonal (1-based), or 0; read before anything is written (what: the calling routine)
-template <typename T>
 int diag_zero(const chol_desc *A, int *info, const char *what) {
   hipStream_t s = main_stream();
   if (int rc = iv.ensure_bytes(3, sizeof(int), what)) return rc;
   int *first = iv.as<int>(3);
-  launch_diag_zero<T>(s, reinterpret_cast<const T *>(A->mat), (long)(A->lmt + 1) * A->bsizi, A->mbi, A->mb, A->lm, first);
+  by_dtype(A->dtype, [&](auto t) {
+    using T = decltype(t);
+    launch_diag_zero<T>(s, reinterpret_cast<const T *>(A->mat), (long)(A->lmt + 1) * A->bsizi, A->mbi, A->mb, A->lm, first);
+  });
   HIPCHECK(hipGetLastError());
   int v = 0;
   HIPCHECK(hipMemcpyAsync(&v, first, sizeof v, hipMemcpyDeviceToHost, s));
@@ -453,17 +482,29 @@ int diag_zero(const chol_desc *A, int *info, const char *what) {
   return 0;
 }
 
-int inverse_run(int uplo, chol_desc *A, bool potri) {
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
-  const bool dbl = A->dtype == CHOL_REAL_DOUBLE;
+// The look for a zero pivot and the Lower path that sygst, chud, chex and sytrf share: an exact zero on `scan`'s
+// diagonal returns its 1-based index before anything is written (scan null: no look); then body() on the Lower
+// orientation of `ds` (through_lower), the launch check and the wait for the main stream -> the body's status
+int lower_run(const char *what, const chol_desc *scan, int uplo, std::initializer_list<chol_desc *> ds,
+              const std::function<int()> &body) {
   int info = 0;
-  const char *what = potri ? "potri_tile" : "trtri_tile";
-  int rc = dbl ? diag_zero<double>(A, &info, what) : diag_zero<float>(A, &info, what);
-  if (rc) return rc;
+  if (scan)
+    if (int rc = diag_zero(scan, &info, what)) return rc;
+  if (info) return info;
+  const int rc = through_lower(uplo == CHOL_UPPER, ds, body);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(main_stream()));
+  return rc;
+}
+
+// (not lower_run: inverse_impl ends with its own wait, and no launch check follows the second transpose)
+int inverse_run(int uplo, chol_desc *A, bool potri) {
+  int info = 0;
+  if (int rc = diag_zero(A, &info, potri ? "potri_tile" : "trtri_tile")) return rc;
   if (info) return info;  // (LAPACK: A is unchanged)
   // ChamUpper: U = L^T; inv(U) = inv(L)^T and inv(U^T U) = inv(L L^T) -- the Lower path on the transposed storage
   return through_lower(uplo == CHOL_UPPER, {A},
-                       [&] { return dbl ? inverse_impl<double>(A, potri) : inverse_impl<float>(A, potri); });
+                       [&] { return by_dtype(A->dtype, [&](auto t) { return inverse_impl<decltype(t)>(A, potri); }); });
 }
 
 // ---------------------------------------------------------------- condition estimate (LAPACK DLANSY / DPOCON)
@@ -599,7 +640,7 @@ int pocon_impl(chol_desc *A, int upper, double anorm, double *rcond, bool staged
   int rc = tt.start();
   if (rc) return rc;
   int info = 0;
-  rc = diag_zero<T>(A, &info, "pocon_tile");
+  rc = diag_zero(A, &info, "pocon_tile");
   if (rc) return rc;
   if (info) return 0;  // a zero on the factor's diagonal: rcond = 0, no sweep
   // scratch: the diagonal tiles, their 128-block inverses, the products' Y blocks (stage_factor_diag), the vectors,
@@ -1184,10 +1225,12 @@ int pstrf_impl(chol_desc *A, int *piv, int *rank, double tol) {
 void pstrf_flip(chol_desc *A) {
   if (A->mbi % 64 == 0) return transpose_storage(A);
   const PsGeo g{A->lm, A->mb, A->mbi, A->lmt, (long)A->bsizi};
-  if (A->dtype == CHOL_REAL_DOUBLE) launch_pstrf_transpose<double>(main_stream(), g, (double *)A->mat);
-  else launch_pstrf_transpose<float>(main_stream(), g, (float *)A->mat);
+  by_dtype(A->dtype, [&](auto t) { launch_pstrf_transpose<decltype(t)>(main_stream(), g, (decltype(t) *)A->mat); });
 }
 
+// (not lower_run: no look for a zero pivot, its own flip, and the launch check follows the Upper path alone.  The two
+// arms are written out: called through by_dtype, pstrf_impl is inlined otherwise and the library's dynamic symbols
+// lose the weak std::vector<int>::push_back they have had)
 int pstrf_run(int uplo, chol_desc *A, int *piv, int *rank, double tol) {
   const bool up = uplo == CHOL_UPPER;
   const int rc = through_lower(up, {A}, [&] {
@@ -1296,16 +1339,8 @@ int sygst_impl(chol_desc *A, chol_desc *B) {
 // the Lower path, or Upper between transposes of both storages (U^T U = L L^T with L = U^T, and inv(U^T) A inv(U) is
 // the Lower result); a zero on B's diagonal returns its index before anything is written
 int sygst_run(int uplo, chol_desc *A, chol_desc *B) {
-  const bool dbl = A->dtype == CHOL_REAL_DOUBLE;
-  int info = 0;
-  int rc = dbl ? diag_zero<double>(B, &info, "sygst_tile") : diag_zero<float>(B, &info, "sygst_tile");
-  if (rc) return rc;
-  if (info) return info;
-  rc = through_lower(uplo == CHOL_UPPER, {A, B},
-                     [&] { return dbl ? sygst_impl<double>(A, B) : sygst_impl<float>(A, B); });
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipStreamSynchronize(main_stream()));
-  return rc;
+  return lower_run("sygst_tile", B, uplo, {A, B},
+                   [&] { return by_dtype(A->dtype, [&](auto t) { return sygst_impl<decltype(t)>(A, B); }); });
 }
 
 // ---------------------------------------------------------------- rank-r update / downdate (LINPACK DCHUD / DCHDD)
@@ -1373,25 +1408,20 @@ int chud_impl(chol_desc *A, chol_desc *V, T sigma, int *info) {
 // the Lower path, or Upper between two transposes of A's storage (U^T U + sigma V V^T = L L^T + sigma V V^T with
 // L = U^T); a zero on the factor's diagonal returns its index before anything is written
 int chud_run(int uplo, chol_desc *A, chol_desc *V, double sigma, const char *what) {
-  const bool dbl = A->dtype == CHOL_REAL_DOUBLE;
   int info = 0;
-  int rc = dbl ? diag_zero<double>(A, &info, what) : diag_zero<float>(A, &info, what);
-  if (rc) return rc;
-  if (info) return info;
-  rc = through_lower(uplo == CHOL_UPPER, {A}, [&] {
-    return dbl ? chud_impl<double>(A, V, sigma, &info) : chud_impl<float>(A, V, (float)sigma, &info);
+  const int rc = lower_run(what, A, uplo, {A}, [&] {
+    return by_dtype(A->dtype, [&](auto t) { return chud_impl<decltype(t)>(A, V, (decltype(t))sigma, &info); });
   });
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipStreamSynchronize(main_stream()));
   return rc ? rc : info;
 }
 
-// chol_chud_tile / chol_chdd_tile after the initialisation check
-int chud_entry(const char *what, int uplo, chol_desc *A, chol_desc *V, double sigma) {
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return failf(-1, "%s: uplo", what);
-  if (!A) return failf(-2, "%s: NULL A", what);
-  if (!V) return failf(-3, "%s: NULL V", what);
-  if (A == V || (A->mat && A->mat == V->mat)) return failf(-3, "%s: V aliases A", what);
+// chol_chud_tile / chol_chdd_tile
+int chud_entry(const Entry &e, int uplo, chol_desc *A, chol_desc *V, double sigma) {
+  const char *what = e.what;
+  if (int rc = e.begin(uplo)) return rc;
+  if (!A) return e.bad(-2, "NULL A");
+  if (!V) return e.bad(-3, "NULL V");
+  if (A == V || (A->mat && A->mat == V->mat)) return e.bad(-3, "V aliases A");
   // (V is workspace: the image of a view of V is not written back)
   return with_views({{A, true}, {V, false}}, [&]() -> int {
     int rc = inverse_check(what, A, 2);
@@ -1400,7 +1430,6 @@ int chud_entry(const char *what, int uplo, chol_desc *A, chol_desc *V, double si
     // (A's rows, not same_rows: a one-tile A of order mb keeps its tile edge, an n x r image of it is padded to 128)
     if (V->lm != A->lm || V->mb != A->mb || V->dtype != A->dtype)
       return failf(-3, "%s: V must have A's dtype, order and tile size", what);
-    std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
     return chud_run(uplo, A, V, sigma, what);
   });
 }
@@ -1516,20 +1545,14 @@ int chex_impl(chol_desc *A, int k0, int l0, int job, int *info) {
 // the Lower path, or Upper between two transposes of A's storage (the shift of U^T U's variables is that of L L^T's
 // with L = U^T); a zero on the factor's diagonal returns its index before anything is written
 int chex_run(int uplo, chol_desc *A, int k, int l, int job) {
-  const bool dbl = A->dtype == CHOL_REAL_DOUBLE;
   cx_stats.clear();
   cx_stats.v[4] = job;
   cx_stats.v[5] = l - k;
   if (A->lm == 0 || k == l) return 0;
   int info = 0;
-  int rc = dbl ? diag_zero<double>(A, &info, "chex_tile") : diag_zero<float>(A, &info, "chex_tile");
-  if (rc) return rc;
-  if (info) return info;
-  rc = through_lower(uplo == CHOL_UPPER, {A}, [&] {
-    return dbl ? chex_impl<double>(A, k - 1, l - 1, job, &info) : chex_impl<float>(A, k - 1, l - 1, job, &info);
+  const int rc = lower_run("chex_tile", A, uplo, {A}, [&] {
+    return by_dtype(A->dtype, [&](auto t) { return chex_impl<decltype(t)>(A, k - 1, l - 1, job, &info); });
   });
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipStreamSynchronize(main_stream()));
   return rc ? rc : info;
 }
 
@@ -1607,11 +1630,9 @@ int sytrf_impl(chol_desc *A, int *info) {
 int sytrf_run(int uplo, chol_desc *A) {
   if (A->mbi % MACRO) return fail(CHOL_ERR_NOT_SUPPORTED, "sytrf_nopiv_tile: stored tile edge must be a multiple of 128");
   int info = 0;
-  const int rc = through_lower(uplo == CHOL_UPPER, {A}, [&] {
-    return A->dtype == CHOL_REAL_DOUBLE ? sytrf_impl<double>(A, &info) : sytrf_impl<float>(A, &info);
+  const int rc = lower_run("sytrf_nopiv_tile", /*scan=*/nullptr, uplo, {A}, [&] {
+    return by_dtype(A->dtype, [&](auto t) { return sytrf_impl<decltype(t)>(A, &info); });
   });
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipStreamSynchronize(main_stream()));
   return rc ? rc : info;
 }
 
@@ -1621,7 +1642,7 @@ template <typename T>
 int sytrs_impl(int upper, chol_desc *A, chol_desc *B, bool diag_checked = false) {
   int info = 0;
   // (sytrs_rbt has looked before its butterflies wrote B)
-  int rc = diag_checked ? 0 : diag_zero<T>(A, &info, "sytrs_nopiv_tile");
+  int rc = diag_checked ? 0 : diag_zero(A, &info, "sytrs_nopiv_tile");
   if (rc) return rc;
   if (info) return info;
   const int nt = A->nt, e = A->mbi;
@@ -1675,13 +1696,13 @@ void rbt_transform(chol_desc *A, const chol_desc *W, int depth) {
 // X <- W^T X (the smallest butterflies first) or W X (the full-order butterfly first)
 template <typename T>
 int rbt_vectors(chol_desc *X, const chol_desc *W, int depth, bool trans, double *st) {
-  EventTimer tv;
-  if (int rc = tv.start()) return rc;
-  for (int x = 0; x < depth; ++x)
-    launch_rbt_vec<T>(main_stream(), geo_of(X), reinterpret_cast<T *>(X->mat), geo_of(W), reinterpret_cast<const T *>(W->mat),
-                      trans ? depth - 1 - x : x, trans);
-  HIPCHECK(hipGetLastError());
-  return tv.stop(&st[RB_VEC]);
+  return timed(&st[RB_VEC], [&]() -> int {
+    for (int x = 0; x < depth; ++x)
+      launch_rbt_vec<T>(main_stream(), geo_of(X), reinterpret_cast<T *>(X->mat), geo_of(W),
+                        reinterpret_cast<const T *>(W->mat), trans ? depth - 1 - x : x, trans);
+    HIPCHECK(hipGetLastError());
+    return 0;
+  });
 }
 
 // W filled (seed != 0), A <- W^T A W on the `uplo` triangle, then sytrf_impl on it -> *info.  Upper: one transpose of
@@ -1714,7 +1735,7 @@ int sytrs_rbt_impl(int upper, chol_desc *A, const chol_desc *W, int depth, chol_
                    bool diag_checked = false) {
   int info = 0;
   // (the refinement steps solve with the factor the first solve saw)
-  int rc = diag_checked ? 0 : diag_zero<T>(A, &info, "sytrs_rbt_tile");
+  int rc = diag_checked ? 0 : diag_zero(A, &info, "sytrs_rbt_tile");
   if (rc) return rc;
   if (info) return info;
   if ((rc = rbt_vectors<T>(B, W, depth, true, st))) return rc;
@@ -2029,25 +2050,25 @@ void cholmi::spd_release() {
 
 // ---------------------------------------------------------------- the entry points (C linkage: include/cholmi.h)
 int chol_potrs_tile(int uplo, chol_desc_t *A, chol_desc_t *B) {
+  const Entry e{"potrs_tile"};
   return with_views({{A, false}, {B, true}}, [&]() -> int {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "potrs_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "potrs_tile: uplo");
-  int rc = resident_whole("potrs_tile", A);
+  int rc = e.begin(uplo);
+  if (!rc) rc = resident_whole(e.what, A);
+  if (!rc) rc = resident_whole(e.what, B);
   if (rc) return rc;
-  rc = resident_whole("potrs_tile", B);
-  if (rc) return rc;
-  if (A->mt != A->nt || A->lm != A->ln) return fail(-2, "potrs_tile: A is not square");
-  if (!same_rows(A, B)) return fail(-3, "potrs_tile: B must have A's order, tile size and type");
-  if (A->mbi % 64) return fail(CHOL_ERR_NOT_SUPPORTED, "potrs_tile: stored tile edge must be a multiple of 64");
-  CHECK_WINV(A, "potrs_tile");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  if (A->mt != A->nt || A->lm != A->ln) return e.bad(-2, "A is not square");
+  if (!same_rows(A, B)) return e.bad(-3, "B must have A's order, tile size and type");
+  if (A->mbi % 64) return e.bad(CHOL_ERR_NOT_SUPPORTED, "stored tile edge must be a multiple of 64");
+  CHECK_WINV(A, e.what);
   const int up = uplo == CHOL_UPPER;
-  rc = A->dtype == CHOL_REAL_DOUBLE ? potrs_uplo<double>(up, A, B) : potrs_uplo<float>(up, A, B);
+  rc = by_dtype(A->dtype, [&](auto t) { return potrs_uplo<decltype(t)>(up, A, B); });
   if (up) HIPCHECK(hipStreamSynchronize(main_stream()));
   return rc;
   });
 }
 
+// The composite entry points (posv, poinv, sysv_nopiv, and dsposv's fallback) keep every check of their own: the
+// routines they call repeat none of them with the same text, since each text begins with its routine's name
 int chol_posv_tile(int uplo, chol_desc_t *A, chol_desc_t *B) {
   if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "posv_tile: uplo");
   const int info = chol_potrf_tile(uplo, A);
@@ -2056,27 +2077,25 @@ int chol_posv_tile(int uplo, chol_desc_t *A, chol_desc_t *B) {
 }
 
 int chol_dsposv_tile(int uplo, chol_desc_t *A, chol_desc_t *B, chol_desc_t *X, int *iter) {
+  const Entry e{"dsposv_tile"};
   return with_views({{A, false}, {B, false}, {X, false}}, [&]() -> int {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "dsposv_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "dsposv_tile: uplo");
-  int rc = resident_whole("dsposv_tile", A);
+  int rc = e.begin(uplo);
+  if (!rc) rc = resident_whole(e.what, A);
   if (rc) return rc;
-  if (A->dtype != CHOL_REAL_DOUBLE) return fail(-2, "dsposv_tile: A must be fp64");
-  if (A->mt != A->nt || A->lm != A->ln) return fail(-2, "dsposv_tile: A is not square");
-  if (!B) return fail(-3, "dsposv_tile: B is NULL");
-  if ((rc = resident_whole("dsposv_tile", B))) return rc;
-  if (!same_rows(A, B) || B->mat == A->mat)
-    return fail(-3, "dsposv_tile: B must be fp64 with A's order and tile size");
-  if (!X) return fail(-4, "dsposv_tile: X is NULL");
-  if ((rc = resident_whole("dsposv_tile", X))) return rc;
-  if (!same_geometry(B, X)) return fail(-4, "dsposv_tile: X must have B's shape, tile size and type");
-  if (X->mat == A->mat || X->mat == B->mat) return fail(-4, "dsposv_tile: X aliases A or B");
-  if (!iter) return fail(-5, "dsposv_tile: iter is NULL");
+  if (A->dtype != CHOL_REAL_DOUBLE) return e.bad(-2, "A must be fp64");
+  if (A->mt != A->nt || A->lm != A->ln) return e.bad(-2, "A is not square");
+  if (!B) return e.bad(-3, "B is NULL");
+  if ((rc = resident_whole(e.what, B))) return rc;
+  if (!same_rows(A, B) || B->mat == A->mat) return e.bad(-3, "B must be fp64 with A's order and tile size");
+  if (!X) return e.bad(-4, "X is NULL");
+  if ((rc = resident_whole(e.what, X))) return rc;
+  if (!same_geometry(B, X)) return e.bad(-4, "X must have B's shape, tile size and type");
+  if (X->mat == A->mat || X->mat == B->mat) return e.bad(-4, "X aliases A or B");
+  if (!iter) return e.bad(-5, "iter is NULL");
   if (A->user_mat || B->user_mat || X->user_mat)
-    return fail(CHOL_ERR_NOT_SUPPORTED, "dsposv_tile: sub-matrix views over a user buffer");
-  if (A->mbi % MACRO) return fail(CHOL_ERR_NOT_SUPPORTED, "dsposv_tile: stored tile edge must be a multiple of 128");
-  CHECK_WINV(A, "dsposv_tile");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+    return e.bad(CHOL_ERR_NOT_SUPPORTED, "sub-matrix views over a user buffer");
+  if (A->mbi % MACRO) return e.bad(CHOL_ERR_NOT_SUPPORTED, "stored tile edge must be a multiple of 128");
+  CHECK_WINV(A, e.what);
   rc = dsposv_mixed(uplo, A, B, X, iter);
   if (rc < 0) return rc;
   if (*iter >= 0) return 0;
@@ -2092,32 +2111,31 @@ int chol_dsposv_tile(int uplo, chol_desc_t *A, chol_desc_t *B, chol_desc_t *X, i
 int chol_last_dsposv_stats(double *out8) { return mx_stats.read("dsposv", out8); }
 
 int chol_trtri_tile(int uplo, int diag, chol_desc_t *A) {
+  const Entry e{"trtri_tile"};
   return with_views({{A, true}}, [&]() -> int {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "trtri_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "trtri_tile: uplo");
-  if (diag != CHOL_NONUNIT && diag != CHOL_UNIT) return fail(-2, "trtri_tile: diag");
-  if (diag == CHOL_UNIT)
-    return fail(CHOL_ERR_NOT_SUPPORTED, "trtri_tile: ChamUnit (a Cholesky factor has no unit diagonal)");
-  int rc = inverse_check("trtri_tile", A, 3);
+  int rc = e.begin(uplo);
   if (rc) return rc;
+  if (diag != CHOL_NONUNIT && diag != CHOL_UNIT) return e.bad(-2, "diag");
+  if (diag == CHOL_UNIT)
+    return e.bad(CHOL_ERR_NOT_SUPPORTED, "ChamUnit (a Cholesky factor has no unit diagonal)");
+  if ((rc = inverse_check(e.what, A, 3))) return rc;
   return inverse_run(uplo, A, false);
   });
 }
 
 int chol_potri_tile(int uplo, chol_desc_t *A) {
+  const Entry e{"potri_tile"};
   return with_views({{A, true}}, [&]() -> int {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "potri_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "potri_tile: uplo");
-  int rc = inverse_check("potri_tile", A, 2);
-  if (rc) return rc;
-  return inverse_run(uplo, A, true);
+  int rc = e.begin(uplo);
+  if (!rc) rc = inverse_check(e.what, A, 2);
+  return rc ? rc : inverse_run(uplo, A, true);
   });
 }
 
 int chol_poinv_tile(int uplo, chol_desc_t *A) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "poinv_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "poinv_tile: uplo");
-  int rc = inverse_check("poinv_tile", A, 2);  // (before the factorisation writes anything)
+  const Entry e{"poinv_tile"};
+  int rc = e.begin(uplo);
+  if (!rc) rc = inverse_check(e.what, A, 2);  // (before the factorisation writes anything)
   if (rc) return rc;
   const int info = chol_potrf_tile(uplo, A);
   if (info != 0) return info;  // > 0: not positive definite, A as potrf leaves it
@@ -2125,164 +2143,151 @@ int chol_poinv_tile(int uplo, chol_desc_t *A) {
 }
 
 int chol_lansy_tile(int norm, int uplo, chol_desc_t *A, double *value) {
+  const Entry e{"lansy_tile"};
   return with_views({{A, false}}, [&]() -> int {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "lansy_tile before chol_init");
+  int rc = e.begin();
+  if (rc) return rc;
   int kind;
   switch (norm) {
     case CHOL_MAX_NORM: kind = 0; break;
     case CHOL_ONE_NORM:
     case CHOL_INF_NORM: kind = 1; break;  // (symmetric: one value for both)
     case CHOL_FROBENIUS_NORM: kind = 2; break;
-    default: return fail(-1, "lansy_tile: norm");
+    default: return e.bad(-1, "norm");
   }
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-2, "lansy_tile: uplo");
-  int rc = inverse_check("lansy_tile", A, 3);
-  if (rc) return rc;
-  if (!value) return fail(-4, "lansy_tile: NULL value");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  if ((rc = e.uplo_at(uplo, 2))) return rc;
+  if ((rc = inverse_check(e.what, A, 3))) return rc;
+  if (!value) return e.bad(-4, "NULL value");
   const int up = uplo == CHOL_UPPER;
   double v[3];
-  rc = A->dtype == CHOL_REAL_DOUBLE ? lansy_impl<double>(A, up, "lansy_tile", v) : lansy_impl<float>(A, up, "lansy_tile", v);
-  if (rc) return rc;
+  if ((rc = by_dtype(A->dtype, [&](auto t) { return lansy_impl<decltype(t)>(A, up, e.what, v); }))) return rc;
   *value = kind == 2 ? std::sqrt(v[2]) : v[kind];
   return 0;
   });
 }
 
 int chol_pocon_tile(int uplo, chol_desc_t *A, double anorm, double *rcond) {
+  const Entry e{"pocon_tile"};
   return with_views({{A, false}}, [&]() -> int {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "pocon_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "pocon_tile: uplo");
-  int rc = inverse_check("pocon_tile", A, 2);
+  int rc = e.begin(uplo);
+  if (!rc) rc = inverse_check(e.what, A, 2);
   if (rc) return rc;
-  if (!(anorm >= 0)) return fail(-3, "pocon_tile: anorm is negative or NaN");
-  if (!rcond) return fail(-4, "pocon_tile: NULL rcond");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  if (!(anorm >= 0)) return e.bad(-3, "anorm is negative or NaN");
+  if (!rcond) return e.bad(-4, "NULL rcond");
   const int up = uplo == CHOL_UPPER;
-  return A->dtype == CHOL_REAL_DOUBLE ? pocon_impl<double>(A, up, anorm, rcond) : pocon_impl<float>(A, up, anorm, rcond);
+  return by_dtype(A->dtype, [&](auto t) { return pocon_impl<decltype(t)>(A, up, anorm, rcond); });
   });
 }
 
 int chol_last_pocon_stats(double *out4) { return cn_stats.read("pocon", out4, 4); }
 
 int chol_poequ_tile(chol_desc_t *A, chol_desc_t *S, double *scond, double *amax) {
+  const Entry e{"poequ_tile"};
   return with_views({{A, false}, {S, true}}, [&]() -> int {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "poequ_tile before chol_init");
-  int rc = square_check("poequ_tile", A, 1);
+  int rc = e.begin();
+  if (!rc) rc = square_check(e.what, A, 1);
+  if (!rc) rc = rhs_check(e.what, A, S, 2, "S");
   if (rc) return rc;
-  if ((rc = rhs_check("poequ_tile", A, S, 2, "S"))) return rc;
-  if (S->ln != 1 || S->mat == A->mat) return fail(-2, "poequ_tile: S must be an n x 1 descriptor of its own");
-  if (!scond) return fail(-3, "poequ_tile: NULL scond");
-  if (!amax) return fail(-4, "poequ_tile: NULL amax");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  if (S->ln != 1 || S->mat == A->mat) return e.bad(-2, "S must be an n x 1 descriptor of its own");
+  if (!scond) return e.bad(-3, "NULL scond");
+  if (!amax) return e.bad(-4, "NULL amax");
   int info = 0;
-  rc = A->dtype == CHOL_REAL_DOUBLE ? poequ_impl<double>(A, S, scond, amax, &info)
-                                    : poequ_impl<float>(A, S, scond, amax, &info);
+  rc = by_dtype(A->dtype, [&](auto t) { return poequ_impl<decltype(t)>(A, S, scond, amax, &info); });
   return rc ? rc : info;
   });
 }
 
 int chol_laqsy_tile(int uplo, chol_desc_t *A, chol_desc_t *S, double scond, double amax, int *equed) {
+  const Entry e{"laqsy_tile"};
   return with_views({{A, true}, {S, false}}, [&]() -> int {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "laqsy_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "laqsy_tile: uplo");
-  int rc = square_check("laqsy_tile", A, 2);
+  int rc = e.begin(uplo);
+  if (!rc) rc = square_check(e.what, A, 2);
+  if (!rc) rc = rhs_check(e.what, A, S, 3, "S");
   if (rc) return rc;
-  if ((rc = rhs_check("laqsy_tile", A, S, 3, "S"))) return rc;
-  if (S->ln != 1 || S->mat == A->mat) return fail(-3, "laqsy_tile: S must be an n x 1 descriptor of its own");
-  if (!(scond >= 0)) return fail(-4, "laqsy_tile: scond is negative or NaN");
-  if (!(amax >= 0)) return fail(-5, "laqsy_tile: amax is negative or NaN");
-  if (!equed) return fail(-6, "laqsy_tile: NULL equed");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  if (S->ln != 1 || S->mat == A->mat) return e.bad(-3, "S must be an n x 1 descriptor of its own");
+  if (!(scond >= 0)) return e.bad(-4, "scond is negative or NaN");
+  if (!(amax >= 0)) return e.bad(-5, "amax is negative or NaN");
+  if (!equed) return e.bad(-6, "NULL equed");
   const int up = uplo == CHOL_UPPER;
-  return A->dtype == CHOL_REAL_DOUBLE ? laqsy_impl<double>(up, A, S, scond, amax, equed)
-                                      : laqsy_impl<float>(up, A, S, scond, amax, equed);
+  return by_dtype(A->dtype, [&](auto t) { return laqsy_impl<decltype(t)>(up, A, S, scond, amax, equed); });
   });
 }
 
 int chol_porfs_tile(int uplo, chol_desc_t *A, chol_desc_t *AF, chol_desc_t *B, chol_desc_t *X, double *ferr,
                     double *berr) {
+  const Entry e{"porfs_tile"};
   return with_views({{A, false}, {AF, false}, {B, false}, {X, true}}, [&]() -> int {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "porfs_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "porfs_tile: uplo");
-  int rc = porfs_args("porfs_tile", A, AF, B, X, 2, 4, 5);
+  int rc = e.begin(uplo);
+  if (!rc) rc = porfs_args(e.what, A, AF, B, X, 2, 4, 5);
   if (rc) return rc;
-  if (!ferr) return fail(-6, "porfs_tile: NULL ferr");
-  if (!berr) return fail(-7, "porfs_tile: NULL berr");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  if (!ferr) return e.bad(-6, "NULL ferr");
+  if (!berr) return e.bad(-7, "NULL berr");
   const int up = uplo == CHOL_UPPER;
   rf_stats.clear();
-  EventTimer tt;
-  if ((rc = tt.start())) return rc;
-  if (A->dtype == CHOL_REAL_DOUBLE) {
-    if (!(rc = stage_factor_diag<double>(AF, up, "porfs_tile")))
-      rc = porfs_impl<double>(up, A, AF, B, X, ferr, berr, rf_stats.v);
-  } else {
-    if (!(rc = stage_factor_diag<float>(AF, up, "porfs_tile")))
-      rc = porfs_impl<float>(up, A, AF, B, X, ferr, berr, rf_stats.v);
-  }
-  if (rc) return rc;
-  return tt.stop(&rf_stats.v[0]);
+  return timed(&rf_stats.v[0], [&] {
+    return by_dtype(A->dtype, [&](auto t) {
+      using T = decltype(t);
+      const int r = stage_factor_diag<T>(AF, up, e.what);
+      return r ? r : porfs_impl<T>(up, A, AF, B, X, ferr, berr, rf_stats.v);
+    });
+  });
   });
 }
 
 int chol_posvx_tile(int fact, int uplo, chol_desc_t *A, chol_desc_t *AF, int *equed, chol_desc_t *S, chol_desc_t *B,
                     chol_desc_t *X, double *rcond, double *ferr, double *berr) {
+  const Entry e{"posvx_tile"};
   return with_views({{A, true}, {AF, true}, {S, true}, {B, true}, {X, true}}, [&]() -> int {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "posvx_tile before chol_init");
-  if (fact != CHOL_FACT_NONE && fact != CHOL_FACT_EQUILIBRATE && fact != CHOL_FACT_FACTORED)
-    return fail(-1, "posvx_tile: fact");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-2, "posvx_tile: uplo");
-  int rc = porfs_args("posvx_tile", A, AF, B, X, 3, 7, 8);
+  int rc = e.begin();
   if (rc) return rc;
-  if (!equed) return fail(-5, "posvx_tile: NULL equed");
-  if (fact == CHOL_FACT_FACTORED && *equed != 0 && *equed != 1) return fail(-5, "posvx_tile: equed must be 0 or 1");
+  if (fact != CHOL_FACT_NONE && fact != CHOL_FACT_EQUILIBRATE && fact != CHOL_FACT_FACTORED) return e.bad(-1, "fact");
+  if ((rc = e.uplo_at(uplo, 2))) return rc;
+  if ((rc = porfs_args(e.what, A, AF, B, X, 3, 7, 8))) return rc;
+  if (!equed) return e.bad(-5, "NULL equed");
+  if (fact == CHOL_FACT_FACTORED && *equed != 0 && *equed != 1) return e.bad(-5, "equed must be 0 or 1");
   const bool need_s = fact == CHOL_FACT_EQUILIBRATE || (fact == CHOL_FACT_FACTORED && *equed == 1);
   if (need_s || S) {
-    if ((rc = rhs_check("posvx_tile", A, S, 6, "S"))) return rc;
+    if ((rc = rhs_check(e.what, A, S, 6, "S"))) return rc;
     if (S->ln != 1 || S->mat == A->mat || S->mat == AF->mat || S->mat == B->mat || S->mat == X->mat)
-      return fail(-6, "posvx_tile: S must be an n x 1 descriptor of its own");
+      return e.bad(-6, "S must be an n x 1 descriptor of its own");
   }
-  if (!rcond) return fail(-9, "posvx_tile: NULL rcond");
-  if (!ferr) return fail(-10, "posvx_tile: NULL ferr");
-  if (!berr) return fail(-11, "posvx_tile: NULL berr");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  if (!rcond) return e.bad(-9, "NULL rcond");
+  if (!ferr) return e.bad(-10, "NULL ferr");
+  if (!berr) return e.bad(-11, "NULL berr");
   const int up = uplo == CHOL_UPPER;
-  return A->dtype == CHOL_REAL_DOUBLE ? posvx_impl<double>(fact, up, A, AF, equed, S, B, X, rcond, ferr, berr)
-                                      : posvx_impl<float>(fact, up, A, AF, equed, S, B, X, rcond, ferr, berr);
+  return by_dtype(A->dtype, [&](auto t) {
+    return posvx_impl<decltype(t)>(fact, up, A, AF, equed, S, B, X, rcond, ferr, berr);
+  });
   });
 }
 
 int chol_bench_refine(int uplo, chol_desc_t *A, chol_desc_t *AF, chol_desc_t *X, int path, int reps, double *ms) {
+  const Entry e{"bench_refine"};
   return with_views({{A, false}, {AF, false}, {X, false}}, [&]() -> int {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "bench_refine before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "bench_refine: uplo");
-  int rc = square_check("bench_refine", A, 2);
+  int rc = e.begin(uplo);
+  if (!rc) rc = square_check(e.what, A, 2);
+  if (!rc) rc = square_check(e.what, AF, 3);
+  if (!rc) rc = rhs_check(e.what, A, X, 4, "X");
   if (rc) return rc;
-  if ((rc = square_check("bench_refine", AF, 3))) return rc;
-  if ((rc = rhs_check("bench_refine", A, X, 4, "X"))) return rc;
-  if (path < 0 || path > 2 || reps < 1 || !ms) return fail(-5, "bench_refine: path, reps or ms");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  if (path < 0 || path > 2 || reps < 1 || !ms) return e.bad(-5, "path, reps or ms");
   const int up = uplo == CHOL_UPPER;
-  return A->dtype == CHOL_REAL_DOUBLE ? bench_refine_impl<double>(up, A, AF, X, path, reps, ms)
-                                      : bench_refine_impl<float>(up, A, AF, X, path, reps, ms);
+  return by_dtype(A->dtype, [&](auto t) { return bench_refine_impl<decltype(t)>(up, A, AF, X, path, reps, ms); });
   });
 }
 
 int chol_last_posvx_stats(double *out8) { return rf_stats.read("posvx", out8); }
 
 int chol_pstrf_tile(int uplo, chol_desc_t *A, int *piv, int *rank, double tol) {
+  const Entry e{"pstrf_tile"};
   return with_views({{A, true}}, [&]() -> int {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "pstrf_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "pstrf_tile: uplo");
-  if (!A) return fail(-2, "pstrf_tile: NULL descriptor");
-  int rc = resident_whole("pstrf_tile", A);
+  int rc = e.begin(uplo);
   if (rc) return rc;
-  if (A->mt != A->nt || A->lm != A->ln) return fail(-2, "pstrf_tile: A is not square");
-  if (!piv) return fail(-3, "pstrf_tile: NULL piv");
-  if (!rank) return fail(-4, "pstrf_tile: NULL rank");
-  if (std::isnan(tol)) return fail(-5, "pstrf_tile: tol is NaN");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  if (!A) return e.bad(-2, "NULL descriptor");
+  if ((rc = resident_whole(e.what, A))) return rc;
+  if (A->mt != A->nt || A->lm != A->ln) return e.bad(-2, "A is not square");
+  if (!piv) return e.bad(-3, "NULL piv");
+  if (!rank) return e.bad(-4, "NULL rank");
+  if (std::isnan(tol)) return e.bad(-5, "tol is NaN");
   return pstrf_run(uplo, A, piv, rank, tol);
   });
 }
@@ -2290,21 +2295,21 @@ int chol_pstrf_tile(int uplo, chol_desc_t *A, int *piv, int *rank, double tol) {
 int chol_last_pstrf_stats(double *out8) { return ps_stats.read("pstrf", out8); }
 
 int chol_sygst_tile(int itype, int uplo, chol_desc_t *A, chol_desc_t *B) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "sygst_tile before chol_init");
-  if (itype < 1 || itype > 3) return fail(-1, "sygst_tile: itype");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-2, "sygst_tile: uplo");
-  if (!A) return fail(-3, "sygst_tile: NULL A");
-  if (!B) return fail(-4, "sygst_tile: NULL B");
-  if (A == B || (A->mat && A->mat == B->mat)) return fail(-4, "sygst_tile: B aliases A");
+  const Entry e{"sygst_tile"};
+  int rc = e.begin();
+  if (rc) return rc;
+  if (itype < 1 || itype > 3) return e.bad(-1, "itype");
+  if ((rc = e.uplo_at(uplo, 2))) return rc;
+  if (!A) return e.bad(-3, "NULL A");
+  if (!B) return e.bad(-4, "NULL B");
+  if (A == B || (A->mat && A->mat == B->mat)) return e.bad(-4, "B aliases A");
   return with_views({{A, true}, {B, false}}, [&]() -> int {
-  int rc = inverse_check("sygst_tile", A, 3);
+  int rc = inverse_check(e.what, A, 3);
+  if (!rc) rc = inverse_check(e.what, B, 4);
   if (rc) return rc;
-  rc = inverse_check("sygst_tile", B, 4);
-  if (rc) return rc;
-  if (!same_geometry(A, B)) return fail(-4, "sygst_tile: B's dtype or geometry differs from A's");
-  if (itype != 1) return fail(CHOL_ERR_NOT_SUPPORTED, "sygst_tile: itype 2 and 3 (C = L^T A L)");
-  CHECK_WINV(A, "sygst_tile");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  if (!same_geometry(A, B)) return e.bad(-4, "B's dtype or geometry differs from A's");
+  if (itype != 1) return e.bad(CHOL_ERR_NOT_SUPPORTED, "itype 2 and 3 (C = L^T A L)");
+  CHECK_WINV(A, e.what);
   return sygst_run(uplo, A, B);
   });
 }
@@ -2312,29 +2317,25 @@ int chol_sygst_tile(int itype, int uplo, chol_desc_t *A, chol_desc_t *B) {
 int chol_last_sygst_stats(double *out8) { return sg_stats.read("sygst", out8); }
 
 int chol_chud_tile(int uplo, chol_desc_t *A, chol_desc_t *V) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "chud_tile before chol_init");
-  return chud_entry("chud_tile", uplo, A, V, 1.0);
+  return chud_entry(Entry{"chud_tile"}, uplo, A, V, 1.0);
 }
 
 int chol_chdd_tile(int uplo, chol_desc_t *A, chol_desc_t *V) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "chdd_tile before chol_init");
-  return chud_entry("chdd_tile", uplo, A, V, -1.0);
+  return chud_entry(Entry{"chdd_tile"}, uplo, A, V, -1.0);
 }
 
 int chol_last_chud_stats(double *out8) { return cu_stats.read("chud", out8); }
 
 int chol_chex_tile(int uplo, chol_desc_t *A, int k, int l, int job) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "chex_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "chex_tile: uplo");
-  if (!A) return fail(-2, "chex_tile: NULL A");
+  const Entry e{"chex_tile"};
+  if (int rc = e.begin(uplo)) return rc;
+  if (!A) return e.bad(-2, "NULL A");
   return with_views({{A, true}}, [&]() -> int {
-    int rc = inverse_check("chex_tile", A, 2);
-    if (rc) return rc;
+    if (int rc = inverse_check(e.what, A, 2)) return rc;
     const int n = A->lm;
-    if (n > 0 && (k < 1 || k > n)) return fail(-3, "chex_tile: k outside 1..n");
-    if (n > 0 && (l < k || l > n)) return fail(-4, "chex_tile: l outside k..n");
-    if (job != 1 && job != 2) return fail(-5, "chex_tile: job must be 1 (right shift) or 2 (left shift)");
-    std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+    if (n > 0 && (k < 1 || k > n)) return e.bad(-3, "k outside 1..n");
+    if (n > 0 && (l < k || l > n)) return e.bad(-4, "l outside k..n");
+    if (job != 1 && job != 2) return e.bad(-5, "job must be 1 (right shift) or 2 (left shift)");
     return chex_run(uplo, A, k, l, job);
   });
 }
@@ -2342,101 +2343,88 @@ int chol_chex_tile(int uplo, chol_desc_t *A, int k, int l, int job) {
 int chol_last_chex_stats(double *out8) { return cx_stats.read("chex", out8); }
 
 int chol_trtrs_tile(int uplo, int trans, int diag, chol_desc_t *A, chol_desc_t *B) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "trtrs_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "trtrs_tile: uplo");
-  if (trans != CHOL_NOTRANS && trans != CHOL_TRANS) return fail(-2, "trtrs_tile: trans");
-  if (diag != CHOL_NONUNIT && diag != CHOL_UNIT) return fail(-3, "trtrs_tile: diag");
-  if (!A) return fail(-4, "trtrs_tile: NULL A");
-  if (!B) return fail(-5, "trtrs_tile: NULL B");
-  if (A == B || (A->mat && A->mat == B->mat)) return fail(-5, "trtrs_tile: B aliases A");
+  const Entry e{"trtrs_tile"};
+  if (int rc = e.begin(uplo)) return rc;
+  if (trans != CHOL_NOTRANS && trans != CHOL_TRANS) return e.bad(-2, "trans");
+  if (diag != CHOL_NONUNIT && diag != CHOL_UNIT) return e.bad(-3, "diag");
+  if (!A) return e.bad(-4, "NULL A");
+  if (!B) return e.bad(-5, "NULL B");
+  if (A == B || (A->mat && A->mat == B->mat)) return e.bad(-5, "B aliases A");
   return with_views({{A, false}, {B, true}}, [&]() -> int {
-  int rc = half_args("trtrs_tile", A, 4, B, 5);
-  if (rc) return rc;
+  if (int rc = half_args(e.what, A, 4, B, 5)) return rc;
   if (diag == CHOL_UNIT)
-    return fail(CHOL_ERR_NOT_SUPPORTED, "trtrs_tile: ChamUnit (a Cholesky factor has no unit diagonal)");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
-  const bool dbl = A->dtype == CHOL_REAL_DOUBLE;
+    return e.bad(CHOL_ERR_NOT_SUPPORTED, "ChamUnit (a Cholesky factor has no unit diagonal)");
   const int up = uplo == CHOL_UPPER, tr_ = trans == CHOL_TRANS;
   tr_stats.clear();
-  EventTimer tt;
-  if ((rc = tt.start())) return rc;
-  int info = 0;
-  rc = dbl ? diag_zero<double>(A, &info, "trtrs_tile") : diag_zero<float>(A, &info, "trtrs_tile");
-  if (rc) return rc;
-  if (info) return info;  // (LAPACK: B is unchanged)
-  rc = dbl ? trtrs_impl<double>(up, tr_, A, B, tr_stats.v) : trtrs_impl<float>(up, tr_, A, B, tr_stats.v);
-  if (rc) return rc;
-  return tt.stop(&tr_stats.v[0]);
+  // (not lower_run: the Lower path is inside trtrs_impl, around its wide sweep alone, and the time is taken around both)
+  return timed(&tr_stats.v[0], [&]() -> int {
+    int info = 0;
+    if (int rc = diag_zero(A, &info, e.what)) return rc;
+    if (info) return info;  // (LAPACK: B is unchanged)
+    return by_dtype(A->dtype, [&](auto t) { return trtrs_impl<decltype(t)>(up, tr_, A, B, tr_stats.v); });
+  });
   });
 }
 
 int chol_trmm_tile(int side, int uplo, int trans, int diag, double alpha, chol_desc_t *A, chol_desc_t *B) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "trmm_tile before chol_init");
-  if (side != CHOL_LEFT && side != CHOL_RIGHT) return fail(-1, "trmm_tile: side");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-2, "trmm_tile: uplo");
-  if (trans != CHOL_NOTRANS && trans != CHOL_TRANS) return fail(-3, "trmm_tile: trans");
-  if (diag != CHOL_NONUNIT && diag != CHOL_UNIT) return fail(-4, "trmm_tile: diag");
-  if (!A) return fail(-6, "trmm_tile: NULL A");
-  if (!B) return fail(-7, "trmm_tile: NULL B");
-  if (A == B || (A->mat && A->mat == B->mat)) return fail(-7, "trmm_tile: B aliases A");
+  const Entry e{"trmm_tile"};
+  if (int rc = e.begin()) return rc;
+  if (side != CHOL_LEFT && side != CHOL_RIGHT) return e.bad(-1, "side");
+  if (int rc = e.uplo_at(uplo, 2)) return rc;
+  if (trans != CHOL_NOTRANS && trans != CHOL_TRANS) return e.bad(-3, "trans");
+  if (diag != CHOL_NONUNIT && diag != CHOL_UNIT) return e.bad(-4, "diag");
+  if (!A) return e.bad(-6, "NULL A");
+  if (!B) return e.bad(-7, "NULL B");
+  if (A == B || (A->mat && A->mat == B->mat)) return e.bad(-7, "B aliases A");
   return with_views({{A, false}, {B, true}}, [&]() -> int {
-  int rc = half_args("trmm_tile", A, 6, B, 7);
-  if (rc) return rc;
-  if (side == CHOL_RIGHT) return fail(CHOL_ERR_NOT_SUPPORTED, "trmm_tile: ChamRight");
+  if (int rc = half_args(e.what, A, 6, B, 7)) return rc;
+  if (side == CHOL_RIGHT) return e.bad(CHOL_ERR_NOT_SUPPORTED, "ChamRight");
   if (diag == CHOL_UNIT)
-    return fail(CHOL_ERR_NOT_SUPPORTED, "trmm_tile: ChamUnit (a Cholesky factor has no unit diagonal)");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+    return e.bad(CHOL_ERR_NOT_SUPPORTED, "ChamUnit (a Cholesky factor has no unit diagonal)");
   const int up = uplo == CHOL_UPPER, tr_ = trans == CHOL_TRANS;
   tr_stats.clear();
-  EventTimer tt;
-  if ((rc = tt.start())) return rc;
-  rc = A->dtype == CHOL_REAL_DOUBLE ? trmm_impl<double>(up, tr_, alpha, A, B, tr_stats.v)
-                                    : trmm_impl<float>(up, tr_, alpha, A, B, tr_stats.v);
-  if (rc) return rc;
-  return tt.stop(&tr_stats.v[0]);
+  return timed(&tr_stats.v[0], [&] {
+    return by_dtype(A->dtype, [&](auto t) { return trmm_impl<decltype(t)>(up, tr_, alpha, A, B, tr_stats.v); });
+  });
   });
 }
 
 int chol_symm_tile(int side, int uplo, double alpha, chol_desc_t *A, chol_desc_t *B, double beta, chol_desc_t *C) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "symm_tile before chol_init");
-  if (side != CHOL_LEFT && side != CHOL_RIGHT) return fail(-1, "symm_tile: side");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-2, "symm_tile: uplo");
-  if (!A) return fail(-4, "symm_tile: NULL A");
-  if (!B) return fail(-5, "symm_tile: NULL B");
-  if (!C) return fail(-7, "symm_tile: NULL C");
-  if (C == A || C == B || (C->mat && (C->mat == A->mat || C->mat == B->mat)))
-    return fail(-7, "symm_tile: C aliases A or B");
+  const Entry e{"symm_tile"};
+  if (int rc = e.begin()) return rc;
+  if (side != CHOL_LEFT && side != CHOL_RIGHT) return e.bad(-1, "side");
+  if (int rc = e.uplo_at(uplo, 2)) return rc;
+  if (!A) return e.bad(-4, "NULL A");
+  if (!B) return e.bad(-5, "NULL B");
+  if (!C) return e.bad(-7, "NULL C");
+  if (C == A || C == B || (C->mat && (C->mat == A->mat || C->mat == B->mat))) return e.bad(-7, "C aliases A or B");
   return with_views({{A, false}, {B, false}, {C, true}}, [&]() -> int {
-  int rc = inverse_check("symm_tile", A, 4);
+  int rc = inverse_check(e.what, A, 4);
+  if (!rc) rc = symm_operand(A, B, 5, "B");
+  if (!rc) rc = symm_operand(A, C, 7, "C");
   if (rc) return rc;
-  if ((rc = symm_operand(A, B, 5, "B"))) return rc;
-  if ((rc = symm_operand(A, C, 7, "C"))) return rc;
-  if (C->ln != B->ln || C->mbi != B->mbi) return fail(-7, "symm_tile: C must have B's width");
-  if (side == CHOL_RIGHT) return fail(CHOL_ERR_NOT_SUPPORTED, "symm_tile: ChamRight");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  if (C->ln != B->ln || C->mbi != B->mbi) return e.bad(-7, "C must have B's width");
+  if (side == CHOL_RIGHT) return e.bad(CHOL_ERR_NOT_SUPPORTED, "ChamRight");
   sm_stats.clear();
-  EventTimer tt;
-  if ((rc = tt.start())) return rc;
   const int up = uplo == CHOL_UPPER;
-  rc = A->dtype == CHOL_REAL_DOUBLE ? symm_impl<double>(up, alpha, A, B, beta, C, sm_stats.v)
-                                    : symm_impl<float>(up, alpha, A, B, beta, C, sm_stats.v);
-  if (rc) return rc;
-  return tt.stop(&sm_stats.v[0]);
+  return timed(&sm_stats.v[0], [&] {
+    return by_dtype(A->dtype, [&](auto t) { return symm_impl<decltype(t)>(up, alpha, A, B, beta, C, sm_stats.v); });
+  });
   });
 }
 
 int chol_last_symm_stats(double *out8) { return sm_stats.read("symm", out8); }
 
 int chol_logdet_tile(chol_desc_t *A, double *logdet) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "logdet_tile before chol_init");
-  if (!A) return fail(-1, "logdet_tile: NULL A");
+  const Entry e{"logdet_tile"};
+  if (int rc = e.begin()) return rc;
+  if (!A) return e.bad(-1, "NULL A");
   return with_views({{A, false}}, [&]() -> int {
-  int rc = inverse_check("logdet_tile", A, 1);
+  int rc = inverse_check(e.what, A, 1);
   if (rc) return rc;
-  if (!logdet) return fail(-2, "logdet_tile: NULL logdet");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  if (!logdet) return e.bad(-2, "NULL logdet");
   int info = 0;
-  rc = A->dtype == CHOL_REAL_DOUBLE ? logdet_impl<double>(A, logdet, &info) : logdet_impl<float>(A, logdet, &info);
+  rc = by_dtype(A->dtype, [&](auto t) { return logdet_impl<decltype(t)>(A, logdet, &info); });
   return rc ? rc : info;
   });
 }
@@ -2444,49 +2432,45 @@ int chol_logdet_tile(chol_desc_t *A, double *logdet) {
 int chol_last_trtrs_stats(double *out8) { return tr_stats.read("trtrs", out8); }
 
 int chol_debug_half_limits(int trtrs_cols, int trmm_cols) {
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());  // (no with_views body)
   trtrs_kx = trtrs_cols < 0 ? TRTRS_KX : trtrs_cols;
   trmm_kx = trmm_cols < 0 ? TRMM_KX : trmm_cols;
   return 0;
 }
 
 int chol_sytrf_nopiv_tile(int uplo, chol_desc_t *A) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "sytrf_nopiv_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "sytrf_nopiv_tile: uplo");
-  if (!A) return fail(-2, "sytrf_nopiv_tile: NULL A");
+  const Entry e{"sytrf_nopiv_tile"};
+  if (int rc = e.begin(uplo)) return rc;
+  if (!A) return e.bad(-2, "NULL A");
   return with_views({{A, true}}, [&]() -> int {
-  int rc = inverse_check("sytrf_nopiv_tile", A, 2);
-  if (rc) return rc;
-  CHECK_WINV(A, "sytrf_nopiv_tile");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  if (int rc = inverse_check(e.what, A, 2)) return rc;
+  CHECK_WINV(A, e.what);
   return sytrf_run(uplo, A);
   });
 }
 
 int chol_sytrs_nopiv_tile(int uplo, chol_desc_t *A, chol_desc_t *B) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "sytrs_nopiv_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "sytrs_nopiv_tile: uplo");
-  if (!A) return fail(-2, "sytrs_nopiv_tile: NULL A");
-  if (!B) return fail(-3, "sytrs_nopiv_tile: NULL B");
-  if (A == B || (A->mat && A->mat == B->mat)) return fail(-3, "sytrs_nopiv_tile: B aliases A");
+  const Entry e{"sytrs_nopiv_tile"};
+  if (int rc = e.begin(uplo)) return rc;
+  if (!A) return e.bad(-2, "NULL A");
+  if (!B) return e.bad(-3, "NULL B");
+  if (A == B || (A->mat && A->mat == B->mat)) return e.bad(-3, "B aliases A");
   return with_views({{A, false}, {B, true}}, [&]() -> int {
-  int rc = inverse_check("sytrs_nopiv_tile", A, 2);
+  int rc = inverse_check(e.what, A, 2);
+  if (!rc) rc = resident_whole(e.what, B);
   if (rc) return rc;
-  rc = resident_whole("sytrs_nopiv_tile", B);
-  if (rc) return rc;
-  if (!same_rows(A, B)) return fail(-3, "sytrs_nopiv_tile: B must have A's order, tile size and type");
-  CHECK_WINV(A, "sytrs_nopiv_tile");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+  if (!same_rows(A, B)) return e.bad(-3, "B must have A's order, tile size and type");
+  CHECK_WINV(A, e.what);
   const int up = uplo == CHOL_UPPER;
-  return A->dtype == CHOL_REAL_DOUBLE ? sytrs_impl<double>(up, A, B) : sytrs_impl<float>(up, A, B);
+  return by_dtype(A->dtype, [&](auto t) { return sytrs_impl<decltype(t)>(up, A, B); });
   });
 }
 
 int chol_sysv_nopiv_tile(int uplo, chol_desc_t *A, chol_desc_t *B) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "sysv_nopiv_tile before chol_init");
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "sysv_nopiv_tile: uplo");
-  if (!A) return fail(-2, "sysv_nopiv_tile: NULL A");
-  if (!B) return fail(-3, "sysv_nopiv_tile: NULL B");
+  const Entry e{"sysv_nopiv_tile"};
+  if (int rc = e.begin(uplo)) return rc;
+  if (!A) return e.bad(-2, "NULL A");
+  if (!B) return e.bad(-3, "NULL B");
   const int info = chol_sytrf_nopiv_tile(uplo, A);
   if (info != 0) return info;  // > 0: a zero or non-finite pivot, B untouched
   return chol_sytrs_nopiv_tile(uplo, A, B);
@@ -2495,18 +2479,16 @@ int chol_sysv_nopiv_tile(int uplo, chol_desc_t *A, chol_desc_t *B) {
 int chol_last_sytrf_stats(double *out8) { return sy_stats.read("sytrf", out8); }
 
 int chol_rbt_apply_tile(int uplo, chol_desc_t *A, chol_desc_t *W, int depth) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "rbt_apply_tile before chol_init");
+  const Entry e{"rbt_apply_tile"};
+  if (int rc = e.begin()) return rc;
   return with_views({{A, true}, {W, false}}, [&]() -> int {
-  int rc = rbt_args("rbt_apply_tile", uplo, A, 2, W, 3, depth, 4);
+  int rc = rbt_args(e.what, uplo, A, 2, W, 3, depth, 4);
   if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
   if (A->lm == 0) return 0;
   forget_winv(A->mat);  // (A is overwritten)
+  // (not lower_run: a failed wait after the second transpose returns before the launch check)
   rc = through_lower(uplo == CHOL_UPPER, {A}, [&] {
-    if (A->dtype == CHOL_REAL_DOUBLE)
-      rbt_transform<double>(A, W, depth);
-    else
-      rbt_transform<float>(A, W, depth);
+    by_dtype(A->dtype, [&](auto t) { rbt_transform<decltype(t)>(A, W, depth); });
     return 0;
   });
   if (rc) return rc;
@@ -2517,73 +2499,68 @@ int chol_rbt_apply_tile(int uplo, chol_desc_t *A, chol_desc_t *W, int depth) {
 }
 
 int chol_sytrf_rbt_tile(int uplo, chol_desc_t *A, chol_desc_t *W, int depth, unsigned long long seed) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "sytrf_rbt_tile before chol_init");
+  const Entry e{"sytrf_rbt_tile"};
+  if (int rc = e.begin()) return rc;
   return with_views({{A, true}, {W, true}}, [&]() -> int {
-  int rc = rbt_args("sytrf_rbt_tile", uplo, A, 2, W, 3, depth, 4);
+  int rc = rbt_args(e.what, uplo, A, 2, W, 3, depth, 4);
   if (rc) return rc;
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
   rb_stats.clear();
-  if (A->lm == 0) return 0;
-  EventTimer tt;
-  if ((rc = tt.start())) return rc;
-  int info = 0;
-  rc = A->dtype == CHOL_REAL_DOUBLE ? sytrf_rbt_impl<double>(uplo, A, W, depth, seed, &info, rb_stats.v)
-                                    : sytrf_rbt_impl<float>(uplo, A, W, depth, seed, &info, rb_stats.v);
-  if (rc) return rc;
-  if ((rc = tt.stop(&rb_stats.v[RB_TOTAL]))) return rc;
-  return info;
+  if (A->lm == 0) return 0;  // (after the clear, before the timer starts)
+  int info = 0;  // (a positive info is returned with the timer stopped)
+  rc = timed(&rb_stats.v[RB_TOTAL], [&] {
+    return by_dtype(A->dtype, [&](auto t) {
+      return sytrf_rbt_impl<decltype(t)>(uplo, A, W, depth, seed, &info, rb_stats.v);
+    });
+  });
+  return rc ? rc : info;
   });
 }
 
 int chol_sytrs_rbt_tile(int uplo, chol_desc_t *A, chol_desc_t *W, int depth, chol_desc_t *B) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "sytrs_rbt_tile before chol_init");
+  const Entry e{"sytrs_rbt_tile"};
+  if (int rc = e.begin()) return rc;
   return with_views({{A, false}, {W, false}, {B, true}}, [&]() -> int {
-  int rc = rbt_args("sytrs_rbt_tile", uplo, A, 2, W, 3, depth, 4);
+  int rc = rbt_args(e.what, uplo, A, 2, W, 3, depth, 4);
   if (rc) return rc;
-  if (!B) return fail(-5, "sytrs_rbt_tile: NULL B");
-  if ((rc = resident_whole("sytrs_rbt_tile", B))) return rc;
+  if (!B) return e.bad(-5, "NULL B");
+  if ((rc = resident_whole(e.what, B))) return rc;
   if (!same_rows(A, B) || B == A || B == W || B->mat == A->mat || B->mat == W->mat)
-    return fail(-5, "sytrs_rbt_tile: B must be a descriptor of its own with A's order, tile size and type");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+    return e.bad(-5, "B must be a descriptor of its own with A's order, tile size and type");
   rb_stats.clear();
   if (A->lm == 0) return 0;
-  EventTimer tt;
-  if ((rc = tt.start())) return rc;
   const int up = uplo == CHOL_UPPER;
-  rc = A->dtype == CHOL_REAL_DOUBLE ? sytrs_rbt_impl<double>(up, A, W, depth, B, rb_stats.v)
-                                    : sytrs_rbt_impl<float>(up, A, W, depth, B, rb_stats.v);
-  if (rc) return rc;
-  return tt.stop(&rb_stats.v[RB_TOTAL]);
+  return timed(&rb_stats.v[RB_TOTAL], [&] {
+    return by_dtype(A->dtype, [&](auto t) { return sytrs_rbt_impl<decltype(t)>(up, A, W, depth, B, rb_stats.v); });
+  });
   });
 }
 
 int chol_sysv_rbt_tile(int uplo, chol_desc_t *A, chol_desc_t *AF, chol_desc_t *W, int depth, unsigned long long seed,
                        chol_desc_t *B, chol_desc_t *X, int *iter, double *berr) {
-  if (!ctx_inited()) return fail(CHOL_ERR_NOT_INITIALIZED, "sysv_rbt_tile before chol_init");
+  const Entry e{"sysv_rbt_tile"};
+  if (int rc = e.begin()) return rc;
   return with_views({{A, false}, {AF, true}, {W, true}, {B, false}, {X, true}}, [&]() -> int {
-  const char *what = "sysv_rbt_tile";
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return fail(-1, "sysv_rbt_tile: uplo");
-  if (!A) return fail(-2, "sysv_rbt_tile: NULL A");
-  int rc = inverse_check(what, A, 2);
+  int rc = e.uplo_at(uplo, 1);
   if (rc) return rc;
-  if (!AF) return fail(-3, "sysv_rbt_tile: NULL AF");
-  if ((rc = resident_whole(what, AF))) return rc;
+  if (!A) return e.bad(-2, "NULL A");
+  if ((rc = inverse_check(e.what, A, 2))) return rc;
+  if (!AF) return e.bad(-3, "NULL AF");
+  if ((rc = resident_whole(e.what, AF))) return rc;
   if (!same_geometry(A, AF) || AF == A || AF->mat == A->mat)
-    return fail(-3, "sysv_rbt_tile: AF must be a descriptor of its own with A's geometry and type");
-  if ((rc = rbt_args(what, uplo, AF, 3, W, 4, depth, 5))) return rc;
-  if (W->mat == A->mat) return fail(-4, "sysv_rbt_tile: W aliases A");
-  if (!B) return fail(-7, "sysv_rbt_tile: NULL B");
-  if ((rc = resident_whole(what, B))) return rc;
+    return e.bad(-3, "AF must be a descriptor of its own with A's geometry and type");
+  if ((rc = rbt_args(e.what, uplo, AF, 3, W, 4, depth, 5))) return rc;
+  if (W->mat == A->mat) return e.bad(-4, "W aliases A");
+  if (!B) return e.bad(-7, "NULL B");
+  if ((rc = resident_whole(e.what, B))) return rc;
   if (!same_rows(A, B) || B->mat == A->mat || B->mat == AF->mat || B->mat == W->mat)
-    return fail(-7, "sysv_rbt_tile: B must be a descriptor of its own with A's order, tile size and type");
-  if (!X) return fail(-8, "sysv_rbt_tile: NULL X");
-  if ((rc = resident_whole(what, X))) return rc;
+    return e.bad(-7, "B must be a descriptor of its own with A's order, tile size and type");
+  if (!X) return e.bad(-8, "NULL X");
+  if ((rc = resident_whole(e.what, X))) return rc;
   if (!same_geometry(B, X) || X == B || X->mat == B->mat || X->mat == A->mat || X->mat == AF->mat || X->mat == W->mat)
-    return fail(-8, "sysv_rbt_tile: X must be a descriptor of its own with B's shape, tile size and type");
-  if (!iter) return fail(-9, "sysv_rbt_tile: NULL iter");
+    return e.bad(-8, "X must be a descriptor of its own with B's shape, tile size and type");
+  if (!iter) return e.bad(-9, "NULL iter");
   if (A->dtype != CHOL_REAL_DOUBLE)
-    return fail(CHOL_ERR_NOT_SUPPORTED, "sysv_rbt_tile: fp32 (the residual pass is fp64: use sytrf_rbt / sytrs_rbt)");
-  std::lock_guard<std::recursive_mutex> lk(ctx_mutex());
+    return e.bad(CHOL_ERR_NOT_SUPPORTED, "fp32 (the residual pass is fp64: use sytrf_rbt / sytrs_rbt)");
   rb_stats.clear();
   *iter = 0;
   if (A->lm == 0 || B->ln == 0) return 0;

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Do two builds of libcholmi.so return the same bits from the routines that work on 128 x 128 blocks of a stored triangle?
+"""Do two builds of libcholmi.so return the same bits from the routines that work from a factor or a stored triangle?
 python scripts/bits_vs_parent.py OTHER/libcholmi.so
 
 Runs the same calls in two fresh child processes, one per library (the other build through LIBCHOLMI_PATH, this tree's
@@ -7,7 +7,10 @@ as usual), and prints the SHA-256 of every output, identical / DIFFERENT per lin
 line differs.  OTHER is typically a build of the parent commit (see scripts/compare_codeobj.py).  The calls: lansy
 (max, one, Frobenius), pocon (rcond and the number of applications), trtrs and trmm for both transposes at nrhs 1, 3,
 8, 9, porfs (X, ferr, berr) and posvx 'E' at nrhs 1 and 3, and in fp64 dsposv (X, iter) at nrhs 1 and 7 and sysv_rbt
-(X, iter); Lower and Upper, fp64 and fp32, on plgsy matrices factored by the library itself.  The shapes (N, tile) are
+(X, iter); and, for the host scaffolding these share with the other routines of spd.hip: potrs, trtri and potri, pstrf
+(piv, rank and the factor), sygst, chud and chdd (r = 1 and 3), chex (both jobs), sytrf_nopiv and sytrs_nopiv,
+sytrf_rbt, sytrs_rbt and rbt_apply, symm and logdet.  Lower and Upper, fp64 and fp32, on plgsy matrices factored by the
+library itself.  The shapes (N, tile) are
 the smallest that reach every mask of the block kernels: (512, 64) a stored edge of 64, one block per tile of which 64
 rows are valid; (192, 192) one tile; (768, 192) a padded image, blocks of 128 + 64; (1000, 192) a ragged last tile;
 (1024, 256) two full blocks per tile.  A call that raises in both builds alike is listed as refused and not counted: at
@@ -68,6 +71,61 @@ def child():
                     return f"{sha(rc)} applications {ch.last_pocon_stats()['applications']}"
 
                 emit(f"{tag} pocon", pocon)
+                factor = dAF.to_lapack()
+
+                def on_copy(M, call, *more):
+                    """the matrix the call leaves in a copy of M, with its info and what `more` returns"""
+                    d = image(M)
+                    info = call(d)
+                    return f"{sha(d.to_lapack(), *[m(d) for m in more])} info {info}"
+
+                def potrs():
+                    dX = image(rhs[3])
+                    info = ch.CHAMELEON_dpotrs_Tile(uc, dAF, dX)
+                    return f"{sha(dX.to_lapack())} info {info}"
+
+                def pstrf():
+                    d = image(A0)
+                    info, piv, rank = ch.CHAMELEON_dpstrf_Tile(uc, d)
+                    return f"{sha(d.to_lapack(), piv, rank)} info {info}"
+
+                def ldl():
+                    d, dB = image(A0), image(rhs[3])
+                    info = ch.CHAMELEON_dsytrf_nopiv_Tile(uc, d)
+                    info2 = ch.CHAMELEON_dsytrs_nopiv_Tile(uc, d, dB)
+                    return f"{sha(d.to_lapack(), dB.to_lapack())} info {info} {info2}"
+
+                def rbt():
+                    d, dW, dB, dT = image(A0), desc(2), image(rhs[3]), image(A0)
+                    info = ch.CHAMELEON_dsytrf_rbt_Tile(uc, d, dW, 2, 1)
+                    info2 = ch.CHAMELEON_dsytrs_rbt_Tile(uc, d, dW, 2, dB)
+                    ch.CHAMELEON_drbt_apply_Tile(uc, dT, dW, 2)
+                    return f"{sha(d.to_lapack(), dW.to_lapack(), dB.to_lapack(), dT.to_lapack())} info {info} {info2}"
+
+                def symm():
+                    dB, dC = image(rhs[3]), image(rhs[3][::-1])
+                    ch.CHAMELEON_dsymm_Tile(ch.ChamLeft, uc, 1.25, dA, dB, 0.5, dC)
+                    return sha(dC.to_lapack())
+
+                def logdet():
+                    info, v = ch.CHAMELEON_dlogdet_Tile(dAF)
+                    return f"{sha(v)} info {info}"
+
+                emit(f"{tag} potrs nrhs 3", potrs)
+                emit(f"{tag} trtri", lambda: on_copy(factor, lambda d: ch.CHAMELEON_dtrtri_Tile(uc, ch.ChamNonUnit, d)))
+                emit(f"{tag} potri", lambda: on_copy(factor, lambda d: ch.CHAMELEON_dpotri_Tile(uc, d)))
+                emit(f"{tag} pstrf", pstrf)
+                emit(f"{tag} sygst", lambda: on_copy(A0 + np.diag(np.arange(N) % 7.0),
+                                                     lambda d: ch.CHAMELEON_dsygst_Tile(1, uc, d, dAF)))
+                for r in (1, 3):
+                    for nm, fn in (("chud", ch.CHAMELEON_dchud_Tile), ("chdd", ch.CHAMELEON_dchdd_Tile)):
+                        emit(f"{tag} {nm} r {r}", lambda: on_copy(factor, lambda d: fn(uc, d, image(rhs[r] / 4))))
+                for job in (1, 2):
+                    emit(f"{tag} chex job {job}", lambda: on_copy(factor, lambda d: ch.CHAMELEON_dchex_Tile(uc, d, 3, N - 2, job)))
+                emit(f"{tag} sytrf_nopiv sytrs_nopiv", ldl)
+                emit(f"{tag} sytrf_rbt sytrs_rbt rbt_apply", rbt)
+                emit(f"{tag} symm nrhs 3", symm)
+                emit(f"{tag} logdet", logdet)
                 for tn, tc in (("N", ch.ChamNoTrans), ("T", ch.ChamTrans)):
                     for k in (1, 3, 8, 9):
                         def trtrs():
