@@ -1804,8 +1804,8 @@ static int residual_common(chol_desc_t *L, double bump, unsigned long long seed,
     if (e != hipSuccess) return fail_hip(e, "residual row sums", __FILE__, __LINE__);
     double rmax = 0, amax = 0;
     for (long r = 0; r < n; ++r) {
-      rmax = std::max(rmax, hr[r]);
-      amax = std::max(amax, hr[n + r]);
+      rmax = nan_max(rmax, hr[r]);
+      amax = nan_max(amax, hr[n + r]);
     }
     *rel_inf = rmax / (amax > 0 ? amax : 1.0);  // V6:84
   }

@@ -273,6 +273,11 @@ void launch_pad_identity(hipStream_t s, T *dst, int n, int ldp);
 template <typename T>
 void launch_transpose_inplace(hipStream_t s, T *M, int nt, int mb);
 
+// The maximum that LAPACK's norms take (DLANGE, DLANSY: `IF (VALUE < TEMP .OR. DISNAN(TEMP))`): a NaN on either side
+// gives a NaN, where fmax and std::max drop it.  Every max of the norms and of the residual's row sums goes through
+// it, so a NaN in the matrix is a NaN in the verdict.
+__host__ __device__ inline double nan_max(double a, double b) { return (a > b || a != a) ? a : b; }
+
 // ---- launchers (verify_ops.hip): the driver's validation block, v6_test.c:51, 74-85 ----
 // Geometry of a single-process stored tile image: lmt x lnt tiles of mbs x mbs elements, of
 // which the caller's tile is the leading mbu x mbu part; the matrix is m x n.

@@ -59,21 +59,23 @@ __global__ __launch_bounds__(256) void k_lansy_blocks(TileGeo g, int upper, cons
     load_pair<T>(b.S, g.mbs, r, c, b.vr, b.vc, b.tri, t0, t1);
     const double a0 = fabs((double)t0), a1 = fabs((double)t1);
     // the row sums take the stored half with the diagonal, the column sums the strict half
-    const double ca0 = (diag && r == c) ? 0.0 : a0, ca1 = (diag && r + 1 == c) ? 0.0 : a1;
+    const bool d0 = diag && r == c, d1 = diag && r + 1 == c;
+    const double ca0 = d0 ? 0.0 : a0, ca1 = d1 ? 0.0 : a1;
+    const double da0 = d0 ? a0 : 0.0, da1 = d1 ? a1 : 0.0;  // (selected, not a0 - ca0: Inf - Inf would be a NaN)
     racc0 += a0;
     racc1 += a1;
     const double s = wave_sum<double>(ca0 + ca1);
     if (lane == k) cres = s;
-    amax = fmax(amax, fmax(a0, a1));
+    amax = nan_max(amax, nan_max(a0, a1));
     sqs = fma(ca1, ca1, fma(ca0, ca0, sqs));                   // strict entries: twice (the other triangle)
-    sqd = fma(a1 - ca1, a1 - ca1, fma(a0 - ca0, a0 - ca0, sqd));  // the diagonal: once
+    sqd = fma(da1, da1, fma(da0, da0, sqd));                   // the diagonal: once
   }
   srow[w][r] = racc0;
   srow[w][r + 1] = racc1;
   // max: order-independent; sum of squares: a fixed tree
   double m = amax;
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+  for (int o = 32; o > 0; o >>= 1) m = nan_max(m, __shfl_xor(m, o, 64));
   const double wsq = wave_sum<double>(2.0 * sqs + sqd);
   if (lane == 0) {
     sred[0][w] = m;
@@ -85,7 +87,7 @@ __global__ __launch_bounds__(256) void k_lansy_blocks(TileGeo g, int upper, cons
   if (tid < CB) prow[tid] = ((srow[0][tid] + srow[1][tid]) + srow[2][tid]) + srow[3][tid];
   if (lane < 32) pcol[w * 32 + lane] = cres;
   if (tid == 0) {
-    const double bm = fmax(fmax(sred[0][0], sred[0][1]), fmax(sred[0][2], sred[0][3]));
+    const double bm = nan_max(nan_max(sred[0][0], sred[0][1]), nan_max(sred[0][2], sred[0][3]));
     atomicMax(res, (unsigned long long)__double_as_longlong(bm));
     ssq[pair] = ((sred[1][0] + sred[1][1]) + sred[1][2]) + sred[1][3];
   }

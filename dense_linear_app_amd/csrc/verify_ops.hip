@@ -116,12 +116,12 @@ __global__ __launch_bounds__(256) void k_colstats(TileGeo g, const T *__restrict
     for (long ii = lane; ii < rows; ii += 64) {
       const double v = fabs((double)p[ii]);
       s += v;
-      mx = fmax(mx, v);
+      mx = nan_max(mx, v);
       ss += v * v;
     }
     for (int o = 32; o > 0; o >>= 1) {
       s += __shfl_down(s, o, 64);
-      mx = fmax(mx, __shfl_down(mx, o, 64));
+      mx = nan_max(mx, __shfl_down(mx, o, 64));
       ss += __shfl_down(ss, o, 64);
     }
     if (lane == 0) {
@@ -134,8 +134,8 @@ __global__ __launch_bounds__(256) void k_colstats(TileGeo g, const T *__restrict
 
 __global__ __launch_bounds__(256) void k_vecmax(const double *v, long n, double *out) {
   double mx = 0.0;
-  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < n; q += (long)gridDim.x * 256) mx = fmax(mx, v[q]);
-  for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_down(mx, o, 64));
+  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < n; q += (long)gridDim.x * 256) mx = nan_max(mx, v[q]);
+  for (int o = 32; o > 0; o >>= 1) mx = nan_max(mx, __shfl_down(mx, o, 64));
   if ((threadIdx.x & 63) == 0) atomic_max_nonneg(out, mx);
 }
 

@@ -189,7 +189,9 @@ int chol_plgsy_tile(double bump, int uplo, chol_desc_t *A, unsigned long long se
  *   CHAMELEON_dlange_Tile(norm, A)               V6:74, 85   *value <- the norm
  *   CHAMELEON_dlauum_Tile(ChamLower, A)          V6:80       tril(A) <- tril(L^T L), L = tril(A)
  *   CHAMELEON_dgeadd_Tile(ChamNoTrans, a, A, b, B) V6:83     B <- a A + b B
- * (s-precision by descriptor dtype).  dlauum takes a scratch copy of the matrix. */
+ * (s-precision by descriptor dtype).  dlauum takes a scratch copy of the matrix.
+ * dlange follows LAPACK DLANGE on non-finite entries, in all four norms: a NaN anywhere inside the m x n matrix
+ * gives NaN; otherwise a +-Inf gives +Inf.  The stored padding outside the matrix is never read. */
 int chol_lacpy_tile(int uplo, chol_desc_t *A, chol_desc_t *B);
 int chol_lange_tile(int norm, chol_desc_t *A, double *value);
 int chol_lauum_tile(int uplo, chol_desc_t *A);
@@ -244,7 +246,9 @@ int chol_poinv_tile(int uplo, chol_desc_t *A);
  * CHAMELEON_dlansy_Tile(norm, uplo, A) -- LAPACK DLANSY: *value <- the norm of the symmetric matrix whose `uplo`
  * triangle A stores.  CHOL_MAX_NORM, CHOL_ONE_NORM, CHOL_INF_NORM (equal to ONE, bit for bit) or
  * CHOL_FROBENIUS_NORM (the sum of squares in fp64, off-diagonal entries twice, then its square root, as
- * chol_lange_tile).  Sums run in a fixed order: a repeated call returns the same bits. */
+ * chol_lange_tile).  Sums run in a fixed order: a repeated call returns the same bits.  Non-finite entries as in
+ * chol_lange_tile: a NaN inside the `uplo` triangle gives NaN in every norm, otherwise a +-Inf gives +Inf; the other
+ * triangle is never read. */
 int chol_lansy_tile(int norm, int uplo, chol_desc_t *A, double *value);
 /* LAPACK DPOCON: A holds the factor of chol_potrf_tile(uplo, .); anorm = ||A_original||_1 (chol_lansy_tile).
  * *rcond <- 1 / (anorm * est(||A^{-1}||_1)), est from LAPACK DLACN2 (Higham's estimator, at most 11 applications of
@@ -609,9 +613,11 @@ int chol_tile_upload(chol_desc_t *desc, int I, int J, const void *host_tile);
 int chol_tile_download(chol_desc_t *desc, int I, int J, void *host_tile);
 
 /* ||tril(L) tril(L)^T - A||_F / ||A||_F with A regenerated by the plgsy rule
- * (the check V6:72-87 intended).  L = factored descriptor. */
+ * (the check V6:72-87 intended).  L = factored descriptor.  Only tril(L) is read.  A NaN in tril(L) gives NaN
+ * and a +-Inf there a non-finite value, never a finite number: the verdict cannot hide a non-finite factor. */
 int chol_residual_plgsy(chol_desc_t *L, double bump, unsigned long long seed, double *rel);
-/* The quantity v6_test.c:72-86 prints, computed correctly: ||A - L L^T||_inf / ||A||_inf. */
+/* The quantity v6_test.c:72-86 prints, computed correctly: ||A - L L^T||_inf / ||A||_inf, over the full symmetric
+ * matrices.  Non-finite entries of tril(L) as in chol_residual_plgsy (the maximum over the row sums keeps a NaN). */
 int chol_residual_plgsy_inf(chol_desc_t *L, double bump, unsigned long long seed, double *rel_inf);
 
 /* ---- client-side host helpers (pure host code, usable without a GPU) ------ */
