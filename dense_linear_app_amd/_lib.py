@@ -80,6 +80,8 @@ def lib() -> C.CDLL:
         "chol_potrf_batched": ([i, i, i, vp, i, C.c_longlong, i, C.POINTER(i)], i),
         "chol_potrs_batched": ([i, i, i, i, vp, i, C.c_longlong, vp, i, C.c_longlong, i, C.POINTER(i)], i),
         "chol_posv_batched": ([i, i, i, i, vp, i, C.c_longlong, vp, i, C.c_longlong, i, C.POINTER(i)], i),
+        "chol_chud_batched": ([i, i, i, i, vp, i, C.c_longlong, vp, i, C.c_longlong, i, C.POINTER(i)], i),
+        "chol_chdd_batched": ([i, i, i, i, vp, i, C.c_longlong, vp, i, C.c_longlong, i, C.POINTER(i)], i),
         "chol_last_batched_stats": ([C.POINTER(d)], i),
         "chol_trtrs_tile": ([i, i, i, vp, vp], i),
         "chol_trmm_tile": ([i, i, i, i, d, vp, vp], i),

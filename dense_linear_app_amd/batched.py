@@ -1,14 +1,17 @@
 """Batched Cholesky of small matrices on torch device tensors, in place (include/cholmi.h: chol_potrf_batched,
-chol_potrs_batched, chol_posv_batched): 10^3 .. 10^6 independent SPD matrices of order n <= 64.
+chol_potrs_batched, chol_posv_batched, chol_chud_batched, chol_chdd_batched): 10^3 .. 10^6 independent SPD matrices of
+order n <= 64.
 
     info = potrf_batched(A)            A: (batch, n, n) or (n, n), float64 or float32
     info = potrs_batched(A, B)         B: (batch, n) or (batch, n, nrhs)   [(n,) or (n, nrhs) with a 2-d A]
     info = posv_batched(A, B)
+    info = chud_batched(A, V)          V: (batch, n) or (batch, n, r), only read: the factors of L L^T + V V^T
+    info = chdd_batched(A, V)                                                     the factors of L L^T - V V^T
 
 Each returns LAPACK's info of every matrix as a numpy int32 array.  The matrices of A are column-major
 (stride(-2) == 1, lda = stride(-1)) or row-major (stride(-1) == 1, lda = stride(-2)); `uplo` always speaks of the
-mathematical matrix, so for a row-major tensor the other code goes to the library.  The matrices of a 3-d B are
-column-major (what torch.empty(batch, nrhs, n).mT gives); a row-major B is refused: nothing is copied or transposed
+mathematical matrix, so for a row-major tensor the other code goes to the library.  The matrices of a 3-d B or V are
+column-major (what torch.empty(batch, nrhs, n).mT gives); a row-major one is refused: nothing is copied or transposed
 behind the caller's back.  Negative statuses raise CholmiError."""
 from __future__ import annotations
 
@@ -64,28 +67,28 @@ def _images_of_A(A, uplo):
     return dt, code, n, lda, stride, batch
 
 
-def _images_of_B(A, B, dt, n, batch):
-    """-> (nrhs, ldb, strideB)"""
-    if _dtype_code(B, "B") != dt:
-        raise ValueError("B must have A's dtype")
+def _images_of_B(A, B, dt, n, batch, name="B"):
+    """-> (nrhs, ldb, strideB); name: what the messages call it (the vectors V of chud_batched follow B's rules)"""
+    if _dtype_code(B, name) != dt:
+        raise ValueError(f"{name} must have A's dtype")
     lead = tuple(A.shape[:-2])
     if B.dim() == A.dim() - 1 and tuple(B.shape) == lead + (n,):
         nrhs, ldb = 1, max(1, n)
         if n > 1 and B.stride(-1) != 1:
-            raise ValueError("the vectors of a (batch, n) B must be contiguous (stride(-1) == 1)")
+            raise ValueError(f"the vectors of a (batch, n) {name} must be contiguous (stride(-1) == 1)")
     elif B.dim() == A.dim() and tuple(B.shape[:-1]) == lead + (n,):
         nrhs = B.shape[-1]
         if n > 1 and B.stride(-2) != 1:
             if B.stride(-1) == 1:
-                raise ValueError("B is row-major: its matrices must be column-major (stride(-2) == 1), which is what "
-                                 "torch.empty(batch, nrhs, n).mT gives; nothing is transposed here")
-            raise ValueError("the matrices of B must be column-major (stride(-2) == 1)")
+                raise ValueError(f"{name} is row-major: its matrices must be column-major (stride(-2) == 1), which is "
+                                 "what torch.empty(batch, nrhs, n).mT gives; nothing is transposed here")
+            raise ValueError(f"the matrices of {name} must be column-major (stride(-2) == 1)")
         ldb = B.stride(-1) if nrhs > 1 else max(1, n)
     else:
-        raise ValueError(f"B must be {lead + (n,)} or {lead + (n, 'nrhs')}, not {tuple(B.shape)}")
+        raise ValueError(f"{name} must be {lead + (n,)} or {lead + (n, 'nrhs')}, not {tuple(B.shape)}")
     stride = B.stride(0) if A.dim() == 3 and batch > 1 else ldb * nrhs
     if ldb < max(1, n) or stride < ldb * nrhs:
-        raise ValueError(f"the matrices of B overlap: strides {tuple(B.stride())} for shape {tuple(B.shape)}")
+        raise ValueError(f"the matrices of {name} overlap: strides {tuple(B.stride())} for shape {tuple(B.shape)}")
     return nrhs, ldb, stride
 
 
@@ -123,6 +126,34 @@ def posv_batched(A, B, uplo: int = ChamLower) -> np.ndarray:
     return _solve("chol_posv_batched", A, B, uplo)
 
 
+def _update(name, A, V, uplo):
+    dt, code, n, lda, sa, batch = _images_of_A(A, uplo)
+    r, ldv, sv = _images_of_B(A, V, dt, n, batch, "V")
+    _require_device(A, V)
+    info, pinfo = _info(batch)
+    check(name, getattr(lib(), name)(code, dt, n, r, A.data_ptr(), lda, sa, V.data_ptr(), ldv, sv, batch, pinfo))
+    return info
+
+
+def chud_batched(A, V, uplo: int = ChamLower) -> np.ndarray:
+    """The factors potrf_batched left in A <- the factors of L L^T + V V^T (LINPACK DCHUD, MATLAB cholupdate, for the
+    r columns of V at once; the bits of r calls with one column each).  V is only read.  -> info; info[b] = j > 0: an
+    exact zero at L_jj, or a NaN / Inf reached column j; that matrix's A is untouched.
+
+    LINPACK's Z and RHO (a recursive least-squares step: the row x with the observation y joins) need no argument of
+    their own: border the matrix with the right-hand side, M = [[A, b], [b^T, c]] of order n + 1 <= 64, factor it,
+    and update with the vector (x, y).  The last row of the bordered factor is (z^T, rho): L z = b solves the
+    triangular half of the normal equations and rho^2 is the residual sum of squares."""
+    return _update("chol_chud_batched", A, V, uplo)
+
+
+def chdd_batched(A, V, uplo: int = ChamLower) -> np.ndarray:
+    """The factors of L L^T - V V^T (LINPACK DCHDD).  info[b] = j > 0: the leading minor of order j of matrix b's
+    L L^T - V V^T is not positive definite (or an exact zero at L_jj): that matrix's A is untouched, bit for bit, and
+    the others are updated as if it were not there.  The bordered form of chud_batched gives Z and RHO here too."""
+    return _update("chol_chdd_batched", A, V, uplo)
+
+
 def last_batched_stats() -> dict:
     """The last batched call (chol_last_batched_stats)"""
     v = (C.c_double * 8)()
@@ -131,4 +162,4 @@ def last_batched_stats() -> dict:
             "workgroups": int(v[5]), "bytes": v[6]}
 
 
-__all__ = ["potrf_batched", "potrs_batched", "posv_batched", "last_batched_stats"]
+__all__ = ["potrf_batched", "potrs_batched", "posv_batched", "chud_batched", "chdd_batched", "last_batched_stats"]

@@ -17,6 +17,9 @@
 // backward, j descending, x_j = (y_j - S_j) r_j with S_j the sum over the sub-group of t_i = L(i,j) x_i (i > j, else
 // +0) by the butterfly t <- t + t[lane ^ off], off = NP/2 .. 1: a fixed tree per padded order, whatever uplo, nrhs or
 // the position in the batch.  One right-hand column at a time, each on its own.
+// The rank-r update and downdate of such factors (chol_chud_batched, chol_chdd_batched) is a second kernel on the same
+// rows, k_chud_rows: the rotated vector is one more register per lane, a rotation two broadcasts and one chud_apply
+// (chud_rot.h, the arithmetic of chol_chud_tile), vectors outer and columns inner, one store after the last vector.
 // (compiled with -ffp-contract=off: only the fma() calls below fuse)
 #include <hip/hip_runtime.h>
 
@@ -24,12 +27,13 @@
 #include <cstdint>
 
 #include "api_internal.h"
+#include "chud_rot.h"
 
 using namespace cholmi;
 
 namespace {
 
-enum { MODE_POTRF = 0, MODE_POTRS = 1, MODE_POSV = 2 };
+enum { MODE_POTRF = 0, MODE_POTRS = 1, MODE_POSV = 2, MODE_CHUD = 3, MODE_CHDD = 4 };  // (k_batched has the first three)
 constexpr int BATCHED_THREADS = 256;  // four wavefronts, nothing shared between them
 constexpr int NO_FAILURE = 0x7f7f7f7f;  // (what hipMemset of 0x7f leaves in the first-failure word)
 
@@ -238,6 +242,98 @@ void launch_batched(bool upper, int mode, hipStream_t s, unsigned grid, const Ba
   }
 }
 
+// ---------------------------------------------------------------- rank-r update and downdate
+template <typename T>
+struct ChudRowsArgs {
+  T *A;
+  const T *V;
+  long lda, strideA, ldv, strideV;
+  int n, r, batch;
+  int vec;    // as BatchedArgs
+  T sigma;    // +1 update, -1 downdate
+  int *info;  // batch words
+  int *first;
+};
+
+// The factor of L L^T + sigma V V^T in the rows k_batched keeps.  Vector t: lane i holds v = V(i,t); column j takes
+// L_jj and v_j from lane j, every lane makes the pivot for itself (it is the same in the whole sub-group), lanes 0, 1
+// and 2 of the sub-group divide one of the three quotients each and broadcast it (one division per column instead of
+// three: 0.66 to 0.85 of the time at r >= 4), lane j keeps rr and the lanes below apply the rotation.
+// The lanes i < j apply it too, to registers nobody reads again (a[j] beyond the triangle, a v_i whose column is
+// past), which saves the selects.
+// Running the vectors outside gives the bits and the info of the header's order (columns outer): the rotation of
+// (j, t) needs column j after the vectors before t and vector t after the columns before j, in either order; a
+// rotation that cannot be made is the identity (chud_pivot), so the columns before the first such column -- the
+// header's info, the least over the vectors -- are the same in both orders, and nothing of that matrix is stored.
+// Registers: the row, v, the pivot's and the rotation's values: fp64 at order 64 stays under 168.
+template <typename T, int NP, bool UPPER>
+__global__ __launch_bounds__(BATCHED_THREADS) void k_chud_rows(ChudRowsArgs<T> p) {
+  constexpr int M = 64 / NP;
+  const int lane = threadIdx.x & 63;
+  const long wave = (long)blockIdx.x * (BATCHED_THREADS / 64) + (threadIdx.x >> 6);
+  if (wave * M >= p.batch) return;
+  const int sub = lane / NP, i = lane % NP, n = p.n;
+  const long b = wave * M + sub;
+  const bool live = b < p.batch && i < n;
+  T *Ab = p.A + (live ? b : 0) * p.strideA;
+  const T *Vb = p.V + (live ? b : 0) * p.strideV + i;
+
+  T a[NP];
+  load_rows<T, NP, UPPER>(a, Ab, p.lda, n, i, live, p.vec != 0);
+
+  T d = T(1);
+#pragma unroll
+  for (int k = 0; k < NP; ++k)
+    if (i == k) d = a[k];
+  const unsigned long long z = __ballot(live && d == T(0)) >> (sub * NP) & (NP == 64 ? ~0ull : (1ull << NP) - 1);
+  const int zero = z ? __ffsll((long long)z) : 0;  // an exact zero on the diagonal comes before everything else
+  int stop = NP + 1;  // the first column (1-based) at which some vector's rotation cannot be made
+
+  for (int t = 0; t < p.r; ++t) {
+    T v = live ? Vb[(long)t * p.ldv] : T(0);
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      if (j < n) {
+        const T ljj = bcast<T, NP>(a[j], j);
+        T vj = bcast<T, NP>(v, j), rr;
+        if (!chud_pivot<T>(ljj, vj, p.sigma, rr) && j + 1 < stop) stop = j + 1;
+        ChudRot<T> rot;
+        const T q = chud_quotient<T>(i, ljj, vj, rr);  // (lanes 0, 1, 2: c, s, ci; the others divide for nothing)
+        rot.c = bcast<T, NP>(q, 0);
+        rot.s = bcast<T, NP>(q, 1);
+        rot.ci = bcast<T, NP>(q, 2);
+        rot.ss = p.sigma * rot.s;
+        T l = a[j];
+        chud_apply<T>(l, v, rot);
+        a[j] = i == j ? rr : l;
+      }
+    }
+  }
+
+  const int bad = zero ? zero : stop <= NP ? stop : 0;
+  // (a failed matrix has computed on, in its own lanes, and stores nothing)
+  store_rows<T, NP, UPPER>(a, Ab, p.lda, n, i, live && !bad, p.vec != 0);
+  if (live && i == 0) {
+    p.info[b] = bad;
+    if (bad) atomicMin(p.first, (int)(b < INT_MAX ? b + 1 : INT_MAX));
+  }
+}
+
+template <typename T, int NP>
+void launch_chud_uplo(bool upper, hipStream_t s, unsigned grid, const ChudRowsArgs<T> &p) {
+  if (upper) k_chud_rows<T, NP, true><<<grid, BATCHED_THREADS, 0, s>>>(p);
+  else k_chud_rows<T, NP, false><<<grid, BATCHED_THREADS, 0, s>>>(p);
+}
+template <typename T>
+void launch_chud_rows(bool upper, hipStream_t s, unsigned grid, const ChudRowsArgs<T> &p) {
+  switch (padded_order(p.n)) {
+    case 8: return launch_chud_uplo<T, 8>(upper, s, grid, p);
+    case 16: return launch_chud_uplo<T, 16>(upper, s, grid, p);
+    case 32: return launch_chud_uplo<T, 32>(upper, s, grid, p);
+    default: return launch_chud_uplo<T, 64>(upper, s, grid, p);
+  }
+}
+
 // ---------------------------------------------------------------- host
 ScratchPool<1> bt;  // [0]: the first-failure word, then (at 16 bytes) the batch words of info
 hipEvent_t bt_ev[4] = {};
@@ -257,16 +353,22 @@ inline unsigned long long span_bytes(long long rows, long long cols, long long l
   return ((unsigned long long)(batch - 1) * stride + (unsigned long long)(cols - 1) * ld + rows) * es;
 }
 
+// The five entry points.  MODE_CHUD / MODE_CHDD: B is the n x nrhs block of vectors V (only read), nrhs is r.
 int run_batched(const char *what, int mode, const ArgPos &pos, int uplo, int dtype, int n, int nrhs, void *A, int lda,
                 long long strideA, void *B, int ldb, long long strideB, int batch, int *info) {
   if (!ctx_inited()) return failf(CHOL_ERR_NOT_INITIALIZED, "%s before chol_init", what);
-  const bool solve = mode != MODE_POTRF;
+  const bool solve = mode != MODE_POTRF, chud = mode == MODE_CHUD || mode == MODE_CHDD;
+  const char *bn = chud ? "V" : "B", *ldn = chud ? "ldv" : "ldb", *cn = chud ? "r" : "nrhs";
   if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return failf(-pos.uplo, "%s: uplo", what);
   if (dtype != CHOL_REAL_DOUBLE && dtype != CHOL_REAL_FLOAT)
     return failf(-pos.dtype, "%s: dtype must be fp64 or fp32", what);
   if (n < 0) return failf(-pos.n, "%s: n < 0", what);
-  if (solve && nrhs < 0) return failf(-pos.nrhs, "%s: nrhs < 0", what);
+  if (solve && nrhs < 0) return failf(-pos.nrhs, "%s: %s < 0", what, cn);
   if (batch < 0) return failf(-pos.batch, "%s: batch < 0", what);
+  if (n > 64 && chud)
+    return failf(CHOL_ERR_NOT_SUPPORTED,
+                 "%s: n > 64; use the descriptor routines (chol_chud_tile, chol_chdd_tile), which take any order",
+                 what);
   if (n > 64)
     return failf(CHOL_ERR_NOT_SUPPORTED,
                  "%s: n > 64; use chol_potrf_batch (tiles that are multiples of 128) or the descriptor routines "
@@ -274,10 +376,10 @@ int run_batched(const char *what, int mode, const ArgPos &pos, int uplo, int dty
   if (lda < (n > 1 ? n : 1)) return failf(-pos.lda, "%s: lda < max(1, n)", what);
   if (strideA < (long long)lda * n) return failf(-pos.strideA, "%s: strideA < lda * n", what);
   if (solve) {
-    if (ldb < (n > 1 ? n : 1)) return failf(-pos.ldb, "%s: ldb < max(1, n)", what);
-    if (strideB < (long long)ldb * nrhs) return failf(-pos.strideB, "%s: strideB < ldb * nrhs", what);
+    if (ldb < (n > 1 ? n : 1)) return failf(-pos.ldb, "%s: %s < max(1, n)", what, ldn);
+    if (strideB < (long long)ldb * nrhs) return failf(-pos.strideB, "%s: stride%s < %s * %s", what, bn, ldn, cn);
   }
-  if (n == 0 || batch == 0 || (mode == MODE_POTRS && nrhs == 0)) {
+  if (n == 0 || batch == 0 || ((mode == MODE_POTRS || chud) && nrhs == 0)) {
     for (int b = 0; info && b < batch; ++b) info[b] = 0;
     return 0;
   }
@@ -285,11 +387,11 @@ int run_batched(const char *what, int mode, const ArgPos &pos, int uplo, int dty
   const size_t es = dtype == CHOL_REAL_DOUBLE ? sizeof(double) : sizeof(float);
   if (!A || !is_device_ptr(A)) return failf(-pos.A, "%s: A must be a device pointer", what);
   if (rhs) {
-    if (!B || !is_device_ptr(B)) return failf(-pos.B, "%s: B must be a device pointer", what);
+    if (!B || !is_device_ptr(B)) return failf(-pos.B, "%s: %s must be a device pointer", what, bn);
     const uintptr_t a0 = (uintptr_t)A, b0 = (uintptr_t)B;
     const uintptr_t a1 = a0 + span_bytes(n, n, lda, strideA, batch, es);
     const uintptr_t b1 = b0 + span_bytes(n, nrhs, ldb, strideB, batch, es);
-    if (a0 < b1 && b0 < a1) return failf(-pos.B, "%s: the address ranges of A and B overlap", what);
+    if (a0 < b1 && b0 < a1) return failf(-pos.B, "%s: the address ranges of A and %s overlap", what, bn);
   }
 
   return with_views({}, [&]() -> int {
@@ -308,7 +410,18 @@ int run_batched(const char *what, int mode, const ArgPos &pos, int uplo, int dty
     HIPCHECK(hipMemsetAsync(first, 0x7f, sizeof(int), s));
     HIPCHECK(hipEventRecord(bt_ev[1], s));
     const int kmode = rhs ? mode : MODE_POTRF;  // (posv without a right-hand side factors)
-    if (dtype == CHOL_REAL_DOUBLE) {
+    if (chud) {
+      const double sigma = mode == MODE_CHUD ? 1.0 : -1.0;
+      if (dtype == CHOL_REAL_DOUBLE) {
+        const ChudRowsArgs<double> p = {(double *)A, (const double *)B, lda, strideA, ldb,   strideB, n,
+                                        nrhs,        batch,             vec, sigma,   dinfo, first};
+        launch_chud_rows<double>(uplo == CHOL_UPPER, s, grid, p);
+      } else {
+        const ChudRowsArgs<float> p = {(float *)A, (const float *)B, lda, strideA,      ldb,   strideB, n,
+                                       nrhs,       batch,            vec, (float)sigma, dinfo, first};
+        launch_chud_rows<float>(uplo == CHOL_UPPER, s, grid, p);
+      }
+    } else if (dtype == CHOL_REAL_DOUBLE) {
       const BatchedArgs<double> p = {(double *)A, (double *)B, lda,   strideA, ldb,   strideB,
                                      n,           nrhs,        batch, vec,     dinfo, first};
       launch_batched<double>(uplo == CHOL_UPPER, kmode, s, grid, p);
@@ -328,7 +441,7 @@ int run_batched(const char *what, int mode, const ArgPos &pos, int uplo, int dty
     HIPCHECK(hipEventElapsedTime(&total, bt_ev[0], bt_ev[3]));
     HIPCHECK(hipEventElapsedTime(&kern, bt_ev[1], bt_ev[2]));
 
-    const double tri = 0.5 * n * (n + 1.0), rhs_el = rhs ? 2.0 * n * nrhs : 0.0;
+    const double tri = 0.5 * n * (n + 1.0), rhs_el = chud ? 1.0 * n * nrhs : rhs ? 2.0 * n * nrhs : 0.0;  // (V: read)
     const double el = (mode == MODE_POTRS ? tri : 2.0 * tri) + rhs_el;
     const double st[8] = {total, kern, (double)batch, (double)n, (double)per_wave, (double)grid, el * es * batch, 0.0};
     std::copy(st, st + 8, bt_stats);
@@ -362,6 +475,18 @@ int chol_posv_batched(int uplo, int dtype, int n, int nrhs, void *A, int lda, lo
                       long long strideB, int batch, int *info) {
   return run_batched("posv_batched", MODE_POSV, POS_SOLVE, uplo, dtype, n, nrhs, A, lda, strideA, B, ldb, strideB,
                      batch, info);
+}
+
+int chol_chud_batched(int uplo, int dtype, int n, int r, void *A, int lda, long long strideA, const void *V, int ldv,
+                      long long strideV, int batch, int *info) {
+  return run_batched("chud_batched", MODE_CHUD, POS_SOLVE, uplo, dtype, n, r, A, lda, strideA, const_cast<void *>(V),
+                     ldv, strideV, batch, info);
+}
+
+int chol_chdd_batched(int uplo, int dtype, int n, int r, void *A, int lda, long long strideA, const void *V, int ldv,
+                      long long strideV, int batch, int *info) {
+  return run_batched("chdd_batched", MODE_CHDD, POS_SOLVE, uplo, dtype, n, r, A, lda, strideA, const_cast<void *>(V),
+                     ldv, strideV, batch, info);
 }
 
 int chol_last_batched_stats(double *out8) {

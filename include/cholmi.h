@@ -450,9 +450,41 @@ int chol_potrs_batched(int uplo, int dtype, int n, int nrhs, const void *A, int 
                        int ldb, long long strideB, int batch, int *info);
 int chol_posv_batched(int uplo, int dtype, int n, int nrhs, void *A, int lda, long long strideA, void *B, int ldb,
                       long long strideB, int batch, int *info);
+/* The rank-r update and downdate of such factors (LINPACK DCHUD / DCHDD without Z and RHO, for r vectors): matrix b's
+ * `uplo` triangle, as chol_potrf_batched(uplo, ..) left it, becomes the factor of L L^T + V V^T (chol_chud_batched) or
+ * of L L^T - V V^T (chol_chdd_batched), V its n x r block of vectors.  The storage rules of chol_potrs_batched with V
+ * in B's place: column-major at V + b strideV, ldv >= max(1,n), strideV >= ldv r; device pointers, fp64 or fp32, Lower
+ * and Upper, element alignment alone, 64-bit offsets, 0 <= n <= 64 (n > 64: CHOL_ERR_NOT_SUPPORTED; chol_chud_tile and
+ * chol_chdd_tile take any order).  Zero sizes (n, r, batch) return 0 with nothing written on the device.
+ *
+ * The arithmetic is chol_chud_tile's block above, each a b + c one fused multiply-add; for every matrix with info 0
+ * the bits are those chol_chud_tile / chol_chdd_tile return for the same L and V.  They depend neither on uplo, the
+ * layout, the matrix's place in the batch or its wavefront's other matrices, nor on how the vectors are grouped into
+ * calls: r vectors in one call give the bits of r calls with one vector each.
+ *
+ * V IS ONLY READ (unlike the tile routine's workspace) and comes back bit for bit.  Only the `uplo` triangle of A is
+ * read or written; the other strict triangle, the lda - n rows under a column, the gaps between the matrices and V's
+ * padding come back bit for bit and may hold NaN.
+ *
+ * info[b] (a host array of `batch` ints, or NULL): 0; or j (1-based) of the first exact zero L_jj, found before any
+ * rotation and ahead of everything else; or the first column j, columns outer and vectors inner, at which some vector
+ * gives d2 <= 0 or NaN (a NaN or Inf in V or on the diagonal ends here): the leading minor of order j of
+ * L L^T - V V^T is not positive definite.  Whenever info[b] > 0 matrix b's A IS UNTOUCHED, bit for bit (stronger than
+ * the tile routine), and no other matrix is disturbed.  Returns 0, or b + 1 of the first matrix with info[b] > 0;
+ * negative: the position of a bad argument (a host pointer, lda, ldv or a stride too small, the address ranges of A
+ * and V overlapping (V's position) included) or CHOL_ERR_*.
+ *
+ * Z and RHO of LINPACK (a recursive least-squares step): border the matrix with the right-hand side,
+ * [A b; b^T c], order n + 1 <= 64, and update its factor with (x, y): the last row of the factor is z^T and rho.
+ *
+ * Argument positions: 1 uplo, 2 dtype, 3 n, 4 r, 5 A, 6 lda, 7 strideA, 8 V, 9 ldv, 10 strideV, 11 batch. */
+int chol_chud_batched(int uplo, int dtype, int n, int r, void *A, int lda, long long strideA, const void *V, int ldv,
+                      long long strideV, int batch, int *info);
+int chol_chdd_batched(int uplo, int dtype, int n, int r, void *A, int lda, long long strideA, const void *V, int ldv,
+                      long long strideV, int batch, int *info);
 /* The last batched call: total time and kernel time [ms] (the library's own events); batch; n; matrices per wavefront;
  * workgroups launched; the bytes the algorithm must move (the stored triangles read and written, plus B read and
- * written); 0. */
+ * written; chud and chdd: the triangles read and written, plus V read); 0. */
 int chol_last_batched_stats(double *out8);
 
 /* One half of a Cholesky factor alone: the triangular solve, the triangular product and the log-determinant, on
