@@ -3,16 +3,23 @@
 reference's metric, v6_test.c:60) on N MI355X of one node.
 
   python bench.py --gpus 1 --steps K --warmup W            (default: N=65536, tile=1024, fp64)
+  python bench.py --full ...                               (the plain run plus every side measurement, see below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 ... bench.py --gpus 8 ...
   python bench.py --gpus 8 ...      (no launcher: this process starts and supervises the 8 ranks itself and
                                      never touches a GPU; see launch_ranks)
 
 A step is one factorisation of a freshly generated matrix that is already resident in HBM
 in tile layout; every step is timed in its own synchronised bracket and the K brackets are
-summed, generation happens between them.  The residual of the last step's factor is computed
-(untimed) and printed in the line; --dump-outputs DIR writes a fixed sample of it (bench.py: dump_factor).
+summed, generation happens between them.  --dump-outputs DIR writes a fixed sample of the last
+step's factor (bench.py: dump_factor).
 The matrix is the same for every GPU count (counter-based generator), so the N-GPU runs
 factor the SAME problem: strong scaling.  Rank 0 prints one JSON line.
+
+A plain run does what the headline figure needs and no more: set-up, warm-up, the K timed steps, the dump if asked
+for, the line.  --full adds, after the timed steps and outside every bracket, what else the benchmark measures and
+checks: the residual of the last step's factor, the roofline of the update kernel (MFMA probe, HBM traffic from two
+child runs under rocprofv3 --pmc), one step without the library's event brackets, the task-API leg, the CPU baseline
+and, on several GPUs, one profiled step per rank.  The --no-* switches take single legs out of a --full run.
 """
 from __future__ import annotations
 
@@ -43,6 +50,11 @@ def parse():
     ap.add_argument("--tile", type=int, default=1024)
     ap.add_argument("--dtype", choices=["f64", "f32"], default="f64")
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: residual of the last factor, roofline of the update kernel (MFMA "
+                         "probe, live HBM traffic), one un-bracketed step, the task-API leg, the CPU baseline, a profiled "
+                         "step per rank on several GPUs; all after the timed steps. The --no-* switches and the --cpu-* / "
+                         "--worker-path-* sizes below apply to a --full run only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     # the CPU baseline is quoted at N=16384, tile=512 (config 2's shape): ~1.5 s of oracle +
     # ~2 s of vendor LAPACK on 16 cores; --cpu-extra-N adds a second, larger sample to the line
@@ -50,7 +62,7 @@ def parse():
     ap.add_argument("--cpu-tile", type=int, default=512)
     ap.add_argument("--cpu-extra-N", type=int, default=20480)
     ap.add_argument("--no-check", action="store_true",
-                    help="skip the (untimed) residual of the last step's factor; by default it is in the line")
+                    help="--full: skip the (untimed) residual of the last step's factor")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="roofline.traffic from the committed PMC pass instead of two child runs under rocprofv3 --pmc")
     ap.add_argument("--no-worker-path", action="store_true",
@@ -175,7 +187,7 @@ def live_pmc_traffic(a, budget_s: float = 150.0):
             out = os.path.join(tmp, ctr)
             cmd = [rocprof, "--pmc", ctr, "--output-format", "csv", "-d", out, "--", sys.executable, os.path.abspath(__file__),
                    "--N", str(a.N), "--tile", str(a.tile), "--dtype", a.dtype, "--seed", str(a.seed), "--steps", "1", "--warmup", "0",
-                   "--no-cpu-baseline", "--no-worker-path", "--no-check", "--no-live-traffic"]
+                   "--full", "--no-cpu-baseline", "--no-worker-path", "--no-check", "--no-live-traffic"]
             env = dict(os.environ, TMPDIR="/tmp")
             p = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=left)
             if p.returncode != 0:
@@ -268,7 +280,8 @@ def run_single(a) -> dict:
     N, B = a.N, a.tile
     dt = ch.ChamRealDouble if a.dtype == "f64" else ch.ChamRealFloat
     d = ch.CHAMELEON_Desc_Create(None, dt, B, B, B * B, N, N, 0, 0, N, N, 1, 1)
-    probe = ch.mfma_probe(dt, 4)  # the register-only MFMA stream this chip sustains right now (TFLOP/s)
+    # --full: the register-only MFMA stream this chip sustains right now (TFLOP/s)
+    probe = ch.mfma_probe(dt, 4) if a.full else None
     kernel = ch.update_kernel_name(dt)
     ch.set_profiling(False)
     for w in range(a.warmup):
@@ -295,22 +308,24 @@ def run_single(a) -> dict:
         upd_launches += st["update_launches"]
     ch.set_profiling(False)
     dump = dump_factor(d, a.seed, a.dump_outputs) if a.dump_outputs else None  # (before the step below overwrites it)
-    # one step more, outside the K timed ones, WITHOUT the library's brackets: what the event records and the closing
-    # waits of the profiled steps cost (they add no dependency; this puts the number on record)
-    ch.CHAMELEON_dplgsy_Tile(float(N), ch.ChamLower, d, a.seed)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    info = ch.CHAMELEON_dpotrf_Tile(ch.ChamLower, d)
-    torch.cuda.synchronize()
-    unprofiled = time.perf_counter() - t0
-    assert info == 0, info
-    # the factor the last step left in HBM (same matrix, same schedule as the timed ones), checked (untimed)
-    res = ch.residual_plgsy(d, float(N), a.seed) if not a.no_check else None
+    unprofiled = res = None
+    if a.full:
+        # one step more, outside the K timed ones, WITHOUT the library's brackets: what the event records and the closing
+        # waits of the profiled steps cost (they add no dependency; this puts the number on record)
+        ch.CHAMELEON_dplgsy_Tile(float(N), ch.ChamLower, d, a.seed)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        info = ch.CHAMELEON_dpotrf_Tile(ch.ChamLower, d)
+        torch.cuda.synchronize()
+        unprofiled = (time.perf_counter() - t0) * 1e3
+        assert info == 0, info
+        # the factor the last step left in HBM (same matrix, same schedule as the timed ones), checked (untimed)
+        res = ch.residual_plgsy(d, float(N), a.seed) if not a.no_check else None
     ch.CHAMELEON_Desc_Destroy(d)
     return {"elapsed": elapsed, "upd_ms": upd_ms, "upd_flops": upd_flops, "upd_launches": upd_launches,
-            "regimes": ch.last_potrf_regimes(),  # of the last (un-bracketed) step: the schedule the timed steps ran too
+            "regimes": ch.last_potrf_regimes(),  # of the last step (a timed one, or --full's un-bracketed one): one schedule
             "residual": res, "probe": probe, "kernel": kernel, "calibration": ch.calibration(),
-            "counters": bool(lib_counters()), "unprofiled_ms": unprofiled * 1e3, "dump": dump}
+            "counters": bool(lib_counters()), "unprofiled_ms": unprofiled, "dump": dump}
 
 
 def run_multi(a) -> dict:
@@ -433,47 +448,48 @@ def run_multi(a) -> dict:
         if rank == 0:
             dump = dump_factor(full, a.seed, a.dump_outputs)
             ch.CHAMELEON_Desc_Destroy(full)
-    # one more step, untimed, with the library's HIP-event brackets on: every rank's own update-kernel time and the
-    # device time of its whole schedule, so that a scaling curve explains itself (update alone vs what the rank waited)
-    ch.set_profiling(True)
-    eng.generate(float(a.N), a.seed)
-    torch.cuda.synchronize()
-    dist.barrier()
-    info = factor()
-    torch.cuda.synchronize()
-    ch.set_profiling(False)
-    assert info == 0, info
-    st = ch.last_potrf_stats()
-    mine = torch.tensor([st["update_ms"], st["total_ms"], float(st["update_launches"]), st["update_flops"]], dtype=torch.float64)
-    per_rank = [torch.zeros_like(mine) for _ in range(world)]
-    dist.all_gather(per_rank, mine)
-    stats["rank_update_ms"] = [round(float(x[0]), 3) for x in per_rank]
-    stats["rank_device_ms"] = [round(float(x[1]), 3) for x in per_rank]
-    stats["rank_update_launches"] = [int(x[2]) for x in per_rank]
-    stats["rank_update_tflops"] = [round(float(x[3]) / (float(x[0]) * 1e-3) / 1e12, 2) if float(x[0]) > 0 else None for x in per_rank]
+    res = None
+    if a.full:
+        # one more step, untimed, with the library's HIP-event brackets on: every rank's own update-kernel time and the
+        # device time of its whole schedule, so that a scaling curve explains itself (update alone vs what the rank waited)
+        ch.set_profiling(True)
+        eng.generate(float(a.N), a.seed)
+        torch.cuda.synchronize()
+        dist.barrier()
+        info = factor()
+        torch.cuda.synchronize()
+        ch.set_profiling(False)
+        assert info == 0, info
+        st = ch.last_potrf_stats()
+        mine = torch.tensor([st["update_ms"], st["total_ms"], float(st["update_launches"]), st["update_flops"]], dtype=torch.float64)
+        per_rank = [torch.zeros_like(mine) for _ in range(world)]
+        dist.all_gather(per_rank, mine)
+        stats["rank_update_ms"] = [round(float(x[0]), 3) for x in per_rank]
+        stats["rank_device_ms"] = [round(float(x[1]), 3) for x in per_rank]
+        stats["rank_update_launches"] = [int(x[2]) for x in per_rank]
+        stats["rank_update_tflops"] = [round(float(x[3]) / (float(x[0]) * 1e-3) / 1e12, 2) if float(x[0]) > 0 else None for x in per_rank]
+        beat("profiled")
+        # device time of each rank's own schedule in the last step (HIP events on its streams): max and min over ranks --
+        # their spread is the block-cyclic imbalance plus what each rank waited for tiles
+        dev = torch.tensor([ch.last_potrf_stats()["total_ms"]], dtype=torch.float64)
+        dmax, dmin = dev.clone(), dev.clone()
+        dist.all_reduce(dmax, op=dist.ReduceOp.MAX)
+        dist.all_reduce(dmin, op=dist.ReduceOp.MIN)
+        stats["device_ms_max"], stats["device_ms_min"] = round(float(dmax.item()), 3), round(float(dmin.item()), 3)
+        # the factor of the last timed step, gathered on rank 0 and checked (untimed) against the regenerated matrix
+        if not a.no_check:
+            full = None
+            if rank == 0:
+                dt = ch.ChamRealDouble if a.dtype == "f64" else ch.ChamRealFloat
+                full = ch.CHAMELEON_Desc_Create(None, dt, a.tile, a.tile, a.tile * a.tile, a.N, a.N, 0, 0, a.N, a.N, 1, 1)
+            dd.gather_lower(eng.desc, full, 0)
+            if rank == 0:
+                res = ch.residual_plgsy(full, float(a.N), a.seed)
+                ch.CHAMELEON_Desc_Destroy(full)
     stats["calibration"] = ch.calibration()
     stats["counters"] = bool(lib_counters())
     stats["regimes_rank0"] = ch.last_potrf_regimes()
     stats["grid_probe"] = grid_probe
-    beat("profiled")
-    # device time of each rank's own schedule in the last step (HIP events on its streams): max and min over ranks --
-    # their spread is the block-cyclic imbalance plus what each rank waited for tiles
-    dev = torch.tensor([ch.last_potrf_stats()["total_ms"]], dtype=torch.float64)
-    dmax, dmin = dev.clone(), dev.clone()
-    dist.all_reduce(dmax, op=dist.ReduceOp.MAX)
-    dist.all_reduce(dmin, op=dist.ReduceOp.MIN)
-    stats["device_ms_max"], stats["device_ms_min"] = round(float(dmax.item()), 3), round(float(dmin.item()), 3)
-    # the factor of the last timed step, gathered on rank 0 and checked (untimed) against the regenerated matrix
-    res = None
-    if not a.no_check:
-        full = None
-        if rank == 0:
-            dt = ch.ChamRealDouble if a.dtype == "f64" else ch.ChamRealFloat
-            full = ch.CHAMELEON_Desc_Create(None, dt, a.tile, a.tile, a.tile * a.tile, a.N, a.N, 0, 0, a.N, a.N, 1, 1)
-        dd.gather_lower(eng.desc, full, 0)
-        if rank == 0:
-            res = ch.residual_plgsy(full, float(a.N), a.seed)
-            ch.CHAMELEON_Desc_Destroy(full)
     out = {"elapsed": float(t.item()), "rank": rank, "grid": f"{P}x{Q}", "residual": res, "dist": stats,
            "backend": backend, "fallback": fallback, "dump": dump}
     dist.barrier()
@@ -615,7 +631,7 @@ def main() -> int:
         "pct_of_mfma_peak": round(100.0 * tflops / (peak * a.gpus), 2),
     }
     if a.gpus == 1:
-        if r["upd_ms"] > 0:
+        if a.full and r["upd_ms"] > 0:
             ach = r["upd_flops"] / (r["upd_ms"] * 1e-3) / 1e12
             # no accounting may ever put the kernel above what the matrix cores sustain (the probe, +2 % for clock jitter)
             assert ach <= 1.02 * max(r["probe"], peak), (ach, r["probe"], peak)
@@ -643,6 +659,9 @@ def main() -> int:
                 # overlap twice (profiles/r02_bench_union_busy.txt: sum / union = 1.24, union = brackets)
                 "time_base": "union of concurrent launches",
             }
+            # one extra step without the library's HIP-event brackets, beside the mean of the K bracketed ones
+            line["unprofiled_ms"] = round(r["unprofiled_ms"], 3)
+        if r["upd_ms"] > 0:
             c = r["calibration"]
             line["config"]["schedule_calibration"] = {"mfma_probe_tflops": [round(c[0], 2), round(c[2], 2)],
                                                       "diag_step_us": [round(c[1], 1), round(c[3], 1)],
@@ -652,14 +671,12 @@ def main() -> int:
             # which regime the walker picked for how many of the waves (it picks from the calibration above: two boxes may
             # run two schedules -- this ties the number to the one it ran)
             line["config"]["schedule_regimes"] = r["regimes"]
-            # one extra step without the library's HIP-event brackets, beside the mean of the K bracketed ones
-            line["unprofiled_ms"] = round(r["unprofiled_ms"], 3)
-        if not a.no_worker_path:
+        if a.full and not a.no_worker_path:
             try:
                 line["worker_path"] = worker_path(a.worker_path_N, a.worker_path_tile)
             except Exception as e:  # the side leg never breaks the bench line
                 line["worker_path"] = {"error": str(e)[:200]}
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(a.cpu_N, a.cpu_tile, a.seed)
             if a.cpu_extra_N and a.cpu_extra_N != a.cpu_N:
                 line["cpu_baseline"]["extra"] = cpu_baseline(a.cpu_extra_N, a.cpu_tile, a.seed, vendor=False)
@@ -669,13 +686,14 @@ def main() -> int:
         line["outputs"] = r["dump"]
     if r.get("dist"):
         line["config"]["exchange"] = {"backend": r["backend"], "fallback": r.get("fallback"), "host_issue_us_per_wave": round(r["dist"]["issue_us_per_wave"], 1),
-                                      "sends_per_rank0": r["dist"]["sends"], "bytes_sent_rank0": r["dist"]["bytes_sent"],
-                                      "rank_device_ms_last_step": [r["dist"]["device_ms_min"], r["dist"]["device_ms_max"]],
-                                      # from one extra (untimed) step with the library's HIP-event brackets on, rank by rank:
-                                      # the update kernel's time (union of its launches), its rate, the rank's whole schedule
-                                      "rank_update_ms": r["dist"]["rank_update_ms"], "rank_update_tflops": r["dist"]["rank_update_tflops"],
-                                      "rank_update_launches": r["dist"]["rank_update_launches"],
-                                      "rank_device_ms_profiled_step": r["dist"]["rank_device_ms"]}
+                                      "sends_per_rank0": r["dist"]["sends"], "bytes_sent_rank0": r["dist"]["bytes_sent"]}
+        if a.full:
+            # from one extra (untimed) step with the library's HIP-event brackets on, rank by rank:
+            # the update kernel's time (union of its launches), its rate, the rank's whole schedule
+            line["config"]["exchange"].update({"rank_device_ms_last_step": [r["dist"]["device_ms_min"], r["dist"]["device_ms_max"]],
+                                               "rank_update_ms": r["dist"]["rank_update_ms"], "rank_update_tflops": r["dist"]["rank_update_tflops"],
+                                               "rank_update_launches": r["dist"]["rank_update_launches"],
+                                               "rank_device_ms_profiled_step": r["dist"]["rank_device_ms"]})
         c = r["dist"]["calibration"]
         line["config"]["schedule_calibration"] = {"mfma_probe_tflops": [round(c[0], 2), round(c[2], 2)],
                                                   "diag_step_us": [round(c[1], 1), round(c[3], 1)],

@@ -38,8 +38,9 @@ def test_self_launch_without_a_gpu_reports_the_failed_rank():
 
 @pytest.mark.gpu
 def test_self_launched_two_ranks_on_one_gpu_over_gloo():
-    """Two ranks sharing cuda:0, tiles moved by gloo: the line of a 2 x 1 run, parsed."""
-    rc, line, _, err = _bench(["--gpus", "2", "--N", "8192", "--tile", "512", "--steps", "1", "--warmup", "1"],
+    """Two ranks sharing cuda:0, tiles moved by gloo: the line of a 2 x 1 run, parsed (--full: the residual and the
+    profiled step's rank-by-rank figures are side measurements)."""
+    rc, line, _, err = _bench(["--gpus", "2", "--N", "8192", "--tile", "512", "--steps", "1", "--warmup", "1", "--full"],
                               {"CHOLMI_DIST_BACKEND": "gloo"}, 900)
     assert rc == 0, err[-3000:]
     assert line["n_gpus"] == 2 and line["value"] > 0 and line["launcher"] == "self"
