@@ -1,16 +1,20 @@
 """Batched Cholesky of small matrices on torch device tensors, in place (include/cholmi.h: chol_potrf_batched,
-chol_potrs_batched, chol_posv_batched, chol_chud_batched, chol_chdd_batched): 10^3 .. 10^6 independent SPD matrices of
-order n <= 64.
+chol_potrs_batched, chol_posv_batched, chol_chud_batched, chol_chdd_batched, chol_trtrs_batched, chol_trmm_batched,
+chol_logdet_batched): 10^3 .. 10^6 independent SPD matrices of order n <= 64.
 
     info = potrf_batched(A)            A: (batch, n, n) or (n, n), float64 or float32
     info = potrs_batched(A, B)         B: (batch, n) or (batch, n, nrhs)   [(n,) or (n, nrhs) with a 2-d A]
     info = posv_batched(A, B)
     info = chud_batched(A, V)          V: (batch, n) or (batch, n, r), only read: the factors of L L^T + V V^T
     info = chdd_batched(A, V)                                                     the factors of L L^T - V V^T
+    info = trtrs_batched(A, B, uplo, trans)     B <- inv(op(T)) B, T the `uplo` triangle of A (a factor), only read
+    trmm_batched(A, B, uplo, trans, alpha)      B <- alpha op(T) B
+    logdet, info = logdet_batched(A)            log det(L L^T) from the diagonal: a float64 tensor on A's device
 
-Each returns LAPACK's info of every matrix as a numpy int32 array.  The matrices of A are column-major
+Each info is LAPACK's info of every matrix as a numpy int32 array.  The matrices of A are column-major
 (stride(-2) == 1, lda = stride(-1)) or row-major (stride(-1) == 1, lda = stride(-2)); `uplo` always speaks of the
-mathematical matrix, so for a row-major tensor the other code goes to the library.  The matrices of a 3-d B or V are
+mathematical matrix, so for a row-major tensor the other code goes to the library (and the other `trans` as well: a
+row-major tensor is the column-major image of the transpose).  The matrices of a 3-d B or V are
 column-major (what torch.empty(batch, nrhs, n).mT gives); a row-major one is refused: nothing is copied or transposed
 behind the caller's back.  Negative statuses raise CholmiError."""
 from __future__ import annotations
@@ -20,7 +24,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import check, lib
-from .chameleon import ChamLower, ChamRealDouble, ChamRealFloat, ChamUpper
+from .chameleon import ChamLower, ChamNoTrans, ChamRealDouble, ChamRealFloat, ChamTrans, ChamUpper
 
 
 def _dtype_code(t, what):
@@ -154,6 +158,54 @@ def chdd_batched(A, V, uplo: int = ChamLower) -> np.ndarray:
     return _update("chol_chdd_batched", A, V, uplo)
 
 
+def _half_of_A(A, uplo, trans):
+    """-> (dtype code, uplo and trans for the library, n, lda, strideA, batch).  `uplo` and `trans` speak of the
+    mathematical matrix; a row-major tensor is the column-major image of its transpose, so there BOTH codes flip"""
+    if trans not in (ChamNoTrans, ChamTrans):
+        raise ValueError("trans must be ChamNoTrans or ChamTrans")
+    dt, code, n, lda, sa, batch = _images_of_A(A, uplo)
+    if code != uplo:
+        trans = ChamTrans if trans == ChamNoTrans else ChamNoTrans
+    return dt, code, trans, n, lda, sa, batch
+
+
+def trtrs_batched(A, B, uplo: int = ChamLower, trans: int = ChamNoTrans) -> np.ndarray:
+    """B <- inv(op(T)) B, T the `uplo` triangle of every matrix of A (what potrf_batched left), op(T) = T or T^T; A is
+    only read.  (Lower, NoTrans) then (Lower, Trans) on the same B returns the bits of potrs_batched.  -> info;
+    info[b] = j: an exact zero at T_jj of matrix b, its B untouched"""
+    dt, code, tr, n, lda, sa, batch = _half_of_A(A, uplo, trans)
+    nrhs, ldb, sb = _images_of_B(A, B, dt, n, batch)
+    _require_device(A, B)
+    info, pinfo = _info(batch)
+    check("chol_trtrs_batched", lib().chol_trtrs_batched(code, tr, dt, n, nrhs, A.data_ptr(), lda, sa, B.data_ptr(),
+                                                         ldb, sb, batch, pinfo))
+    return info
+
+
+def trmm_batched(A, B, uplo: int = ChamLower, trans: int = ChamNoTrans, alpha: float = 1.0) -> None:
+    """B <- alpha op(T) B (a sample x = L z, or L^T z); A is only read.  alpha == 0: B <- +0 with neither A nor B
+    read.  A zero on the diagonal is no failure: there is no info"""
+    dt, code, tr, n, lda, sa, batch = _half_of_A(A, uplo, trans)
+    nrhs, ldb, sb = _images_of_B(A, B, dt, n, batch)
+    _require_device(A, B)
+    check("chol_trmm_batched", lib().chol_trmm_batched(code, tr, dt, n, nrhs, float(alpha), A.data_ptr(), lda, sa,
+                                                       B.data_ptr(), ldb, sb, batch))
+
+
+def logdet_batched(A):
+    """-> (logdet, info): log det(L L^T) = 2 sum log L_jj of every factor in A as a float64 tensor on A's device
+    (for both dtypes), and info (numpy int32); info[b] = j: the first L_jj <= 0 or NaN, logdet[b] is NaN then.  Only
+    the diagonal is read"""
+    import torch
+
+    dt, _, n, lda, sa, batch = _images_of_A(A, ChamLower)
+    _require_device(A)
+    out = torch.empty(batch, dtype=torch.float64, device=A.device)
+    info, pinfo = _info(batch)
+    check("chol_logdet_batched", lib().chol_logdet_batched(dt, n, A.data_ptr(), lda, sa, batch, out.data_ptr(), pinfo))
+    return out, info
+
+
 def last_batched_stats() -> dict:
     """The last batched call (chol_last_batched_stats)"""
     v = (C.c_double * 8)()
@@ -162,4 +214,5 @@ def last_batched_stats() -> dict:
             "workgroups": int(v[5]), "bytes": v[6]}
 
 
-__all__ = ["potrf_batched", "potrs_batched", "posv_batched", "chud_batched", "chdd_batched", "last_batched_stats"]
+__all__ = ["potrf_batched", "potrs_batched", "posv_batched", "chud_batched", "chdd_batched", "trtrs_batched",
+           "trmm_batched", "logdet_batched", "last_batched_stats"]

@@ -20,6 +20,9 @@
 // The rank-r update and downdate of such factors (chol_chud_batched, chol_chdd_batched) is a second kernel on the same
 // rows, k_chud_rows: the rotated vector is one more register per lane, a rotation two broadcasts and one chud_apply
 // (chud_rot.h, the arithmetic of chol_chud_tile), vectors outer and columns inner, one store after the last vector.
+// One half of such a factor alone (chol_trtrs_batched, chol_trmm_batched, chol_logdet_batched) is a third family on the
+// same rows, k_half_rows: the forward or the backward sweep of the solve on its own, the two products with L and L^T,
+// and a small kernel that reads the diagonal alone for the log-determinant.
 // (compiled with -ffp-contract=off: only the fma() calls below fuse)
 #include <hip/hip_runtime.h>
 
@@ -334,6 +337,171 @@ void launch_chud_rows(bool upper, hipStream_t s, unsigned grid, const ChudRowsAr
   }
 }
 
+// ---------------------------------------------------------------- one half of the factor: trtrs, trmm, logdet
+enum { HALF_SOLVE_FWD = 0, HALF_SOLVE_BWD = 1, HALF_MUL_FWD = 2, HALF_MUL_BWD = 3 };
+
+template <typename T>
+struct HalfArgs {
+  const T *A;
+  T *B;
+  long lda, strideA, ldb, strideB;
+  int n, nrhs, batch;
+  int vec;     // as BatchedArgs
+  T alpha;     // (the products)
+  int *info;   // batch words (the solves)
+  int *first;
+};
+
+// One sweep with the lower factor L in the rows k_batched keeps (UPPER: the image holds U = L^T; which of op(T) is the
+// forward and which the backward half the host decides).  The solves are the two halves of k_batched's MODE_POTRS,
+// statement for statement, so forward then backward returns its bits.  The products: forward x_i = sum over k <= i of
+// L(i,k) z_k, z_k broadcast from lane k, k ascending; backward x_j = sum over i >= j of L(i,j) z_i by the backward
+// solve's butterfly.  Both select the terms of the triangle instead of multiplying by the +0 that load_rows left
+// beyond it: a NaN in z_k reaches only the rows that depend on it.
+// Registers: the row and four or five values, the budget of MODE_POTRS (DESIGN.md 3o has the table).
+template <typename T, int NP, bool UPPER, int OP>
+__global__ __launch_bounds__(BATCHED_THREADS) void k_half_rows(HalfArgs<T> p) {
+  constexpr int M = 64 / NP;
+  constexpr bool SOLVE = OP == HALF_SOLVE_FWD || OP == HALF_SOLVE_BWD;
+  const int lane = threadIdx.x & 63;
+  const long wave = (long)blockIdx.x * (BATCHED_THREADS / 64) + (threadIdx.x >> 6);
+  if (wave * M >= p.batch) return;
+  const int sub = lane / NP, i = lane % NP, n = p.n;
+  const long b = wave * M + sub;
+  const bool live = b < p.batch && i < n;
+  const T *Ab = p.A + (live ? b : 0) * p.strideA;
+
+  T a[NP];
+  load_rows<T, NP, UPPER>(a, Ab, p.lda, n, i, live, p.vec != 0);
+
+  int bad = 0;
+  T r = T(0);  // 1 / L(i,i)
+  if constexpr (SOLVE) {
+    T d = T(1);
+#pragma unroll
+    for (int k = 0; k < NP; ++k)
+      if (i == k) d = a[k];
+    const unsigned long long z = __ballot(live && d == T(0)) >> (sub * NP) & (NP == 64 ? ~0ull : (1ull << NP) - 1);
+    if (z) bad = __ffsll((long long)z);
+    r = live ? T(1) / d : T(0);
+    if (live && i == 0) {
+      p.info[b] = bad;
+      if (bad) atomicMin(p.first, (int)(b < INT_MAX ? b + 1 : INT_MAX));
+    }
+  }
+
+  const bool wr = live && !bad;  // (a failed matrix computes on, in its own lanes, and stores nothing)
+  T *Bb = p.B + (live ? b : 0) * p.strideB + i;
+  for (int c = 0; c < p.nrhs; ++c) {
+    T *at = Bb + (long)c * p.ldb;
+    T v = wr ? *at : T(0);
+    T x = T(0);
+    if constexpr (OP == HALF_SOLVE_FWD) {
+#pragma unroll
+      for (int j = 0; j < NP; ++j) {
+        if (j < n) {
+          const T yj = bcast<T, NP>(v * r, j);
+          if (i > j) v = fma_(-a[j], yj, v);
+        }
+      }
+      x = v * r;
+    } else if constexpr (OP == HALF_SOLVE_BWD) {
+#pragma unroll
+      for (int j = NP - 1; j >= 0; --j) {
+        if (j < n) {
+          T t = i > j ? a[j] * x : T(0);
+#pragma unroll
+          for (int off = NP / 2; off >= 1; off >>= 1) t = t + __shfl_xor(t, off, NP);
+          const T cand = (v - t) * r;
+          if (i == j) x = cand;
+        }
+      }
+    } else if constexpr (OP == HALF_MUL_FWD) {
+      T s = T(0);
+#pragma unroll
+      for (int k = 0; k < NP; ++k) {
+        if (k < n) {
+          const T zk = bcast<T, NP>(v, k);
+          if (i >= k) s = fma_(a[k], zk, s);
+        }
+      }
+      x = p.alpha * s;
+    } else {
+#pragma unroll
+      for (int j = NP - 1; j >= 0; --j) {
+        if (j < n) {
+          T t = i >= j ? a[j] * v : T(0);  // (+0 in the lanes from n on: a[j] and v are +0 there)
+#pragma unroll
+          for (int off = NP / 2; off >= 1; off >>= 1) t = t + __shfl_xor(t, off, NP);
+          if (i == j) x = p.alpha * t;
+        }
+      }
+    }
+    if (wr) *at = x;
+  }
+}
+
+template <typename T, int NP, bool UPPER>
+void launch_half_op(int op, hipStream_t s, unsigned grid, const HalfArgs<T> &p) {
+  if (op == HALF_SOLVE_FWD) k_half_rows<T, NP, UPPER, HALF_SOLVE_FWD><<<grid, BATCHED_THREADS, 0, s>>>(p);
+  else if (op == HALF_SOLVE_BWD) k_half_rows<T, NP, UPPER, HALF_SOLVE_BWD><<<grid, BATCHED_THREADS, 0, s>>>(p);
+  else if (op == HALF_MUL_FWD) k_half_rows<T, NP, UPPER, HALF_MUL_FWD><<<grid, BATCHED_THREADS, 0, s>>>(p);
+  else k_half_rows<T, NP, UPPER, HALF_MUL_BWD><<<grid, BATCHED_THREADS, 0, s>>>(p);
+}
+template <typename T, int NP>
+void launch_half_uplo(bool upper, int op, hipStream_t s, unsigned grid, const HalfArgs<T> &p) {
+  if (upper) launch_half_op<T, NP, true>(op, s, grid, p);
+  else launch_half_op<T, NP, false>(op, s, grid, p);
+}
+template <typename T>
+void launch_half_rows(bool upper, int op, hipStream_t s, unsigned grid, const HalfArgs<T> &p) {
+  switch (padded_order(p.n)) {
+    case 8: return launch_half_uplo<T, 8>(upper, op, s, grid, p);
+    case 16: return launch_half_uplo<T, 16>(upper, op, s, grid, p);
+    case 32: return launch_half_uplo<T, 32>(upper, op, s, grid, p);
+    default: return launch_half_uplo<T, 64>(upper, op, s, grid, p);
+  }
+}
+
+// trmm with alpha == 0: B <- +0 in the lanes of k_half_rows, neither A nor B read (NP: the padded order)
+template <typename T>
+__global__ __launch_bounds__(BATCHED_THREADS) void k_zero_rows(T *B, long ldb, long strideB, int n, int nrhs,
+                                                               int batch, int NP) {
+  const int lane = threadIdx.x & 63;
+  const long wave = (long)blockIdx.x * (BATCHED_THREADS / 64) + (threadIdx.x >> 6);
+  const int i = lane % NP;
+  const long b = wave * (64 / NP) + lane / NP;
+  if (b >= batch || i >= n) return;
+  T *Bb = B + b * strideB + i;
+  for (int c = 0; c < nrhs; ++c) Bb[(long)c * ldb] = T(0);
+}
+
+// logdet[b] = 2 (((log d_0 + log d_1) + log d_2) + ..): the sub-groups of k_half_rows with lane = j, which loads d_j
+// alone and takes its logarithm in fp64; the chain then runs in every lane of the sub-group, log d_j shuffled from
+// lane j.  The first d_j <= 0 or NaN is info and makes the value NaN.
+template <typename T>
+__global__ __launch_bounds__(BATCHED_THREADS) void k_diag_logdet(const T *A, long lda, long strideA, int n, int batch,
+                                                            int NP, double *out, int *info, int *first) {
+  const int lane = threadIdx.x & 63;
+  const long wave = (long)blockIdx.x * (BATCHED_THREADS / 64) + (threadIdx.x >> 6);
+  const int M = 64 / NP;
+  if (wave * M >= batch) return;  // (a whole wavefront)
+  const int sub = lane / NP, j = lane % NP;
+  const long b = wave * M + sub;
+  const bool live = b < batch && j < n;
+  const double d = live ? (double)A[b * strideA + j * (lda + 1)] : 1.0;
+  const unsigned long long z = __ballot(live && !(d > 0.0)) >> (sub * NP) & (NP == 64 ? ~0ull : (1ull << NP) - 1);
+  const int bad = z ? __ffsll((long long)z) : 0;
+  const double lg = log(d);
+  double s = 0.0;
+  for (int k = 0; k < n; ++k) s = s + __shfl(lg, k, NP);
+  if (live && j == 0) {
+    out[b] = bad ? __builtin_nan("") : 2.0 * s;
+    info[b] = bad;
+    if (bad) atomicMin(first, (int)(b < INT_MAX ? b + 1 : INT_MAX));
+  }
+}
+
 // ---------------------------------------------------------------- host
 ScratchPool<1> bt;  // [0]: the first-failure word, then (at 16 bytes) the batch words of info
 hipEvent_t bt_ev[4] = {};
@@ -341,10 +509,26 @@ double bt_stats[8] = {};
 
 // the position of each argument in an entry point's signature (0: it has none)
 struct ArgPos {
-  int uplo, dtype, n, nrhs, A, lda, strideA, B, ldb, strideB, batch;
+  int uplo, dtype, n, nrhs, A, lda, strideA, B, ldb, strideB, batch, trans;
 };
-constexpr ArgPos POS_POTRF = {1, 2, 3, 0, 4, 5, 6, 0, 0, 0, 7};
-constexpr ArgPos POS_SOLVE = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+constexpr ArgPos POS_POTRF = {1, 2, 3, 0, 4, 5, 6, 0, 0, 0, 7, 0};
+constexpr ArgPos POS_SOLVE = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 0};
+constexpr ArgPos POS_TRTRS = {1, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 2};
+constexpr ArgPos POS_TRMM = {1, 3, 4, 5, 7, 8, 9, 10, 11, 12, 13, 2};  // (6: alpha)
+constexpr ArgPos POS_LOGDET = {0, 1, 2, 0, 3, 4, 5, 0, 0, 0, 6, 0};    // (7: logdet)
+
+// what the messages call B and its arguments, and where n > 64 sends the caller
+struct ArgNames {
+  const char *B, *ldb, *nrhs, *beyond;
+};
+constexpr ArgNames NAMES_POTRF = {"B", "ldb", "nrhs",
+                                  "use chol_potrf_batch (tiles that are multiples of 128) or the descriptor routines "
+                                  "(chol_potrf_tile, chol_potrs_tile, chol_posv_tile)"};
+constexpr ArgNames NAMES_CHUD = {"V", "ldv", "r",
+                                 "use the descriptor routines (chol_chud_tile, chol_chdd_tile), which take any order"};
+constexpr ArgNames NAMES_HALF = {"B", "ldb", "nrhs",
+                                 "use the descriptor routines (chol_trtrs_tile, chol_trmm_tile, chol_logdet_tile), "
+                                 "which take any order"};
 
 // bytes from the base to the end of the last element of `batch` images of rows x cols
 inline unsigned long long span_bytes(long long rows, long long cols, long long ld, long long stride, long long batch,
@@ -353,47 +537,55 @@ inline unsigned long long span_bytes(long long rows, long long cols, long long l
   return ((unsigned long long)(batch - 1) * stride + (unsigned long long)(cols - 1) * ld + rows) * es;
 }
 
-// The five entry points.  MODE_CHUD / MODE_CHDD: B is the n x nrhs block of vectors V (only read), nrhs is r.
-int run_batched(const char *what, int mode, const ArgPos &pos, int uplo, int dtype, int n, int nrhs, void *A, int lda,
-                long long strideA, void *B, int ldb, long long strideB, int batch, int *info) {
+// The argument rules that every entry point shares, in the order of the checks (pos.B == 0: the routine has no B;
+// empty_rhs: nrhs == 0 leaves nothing to do).  -> negative: the error; 1: a zero size, info zeroed, nothing to do;
+// 0: go on.
+int check_images(const char *what, const ArgPos &pos, const ArgNames &nm, int uplo, int trans, int dtype, int n,
+                 int nrhs, const void *A, int lda, long long strideA, const void *B, int ldb, long long strideB,
+                 int batch, bool empty_rhs, int *info) {
   if (!ctx_inited()) return failf(CHOL_ERR_NOT_INITIALIZED, "%s before chol_init", what);
-  const bool solve = mode != MODE_POTRF, chud = mode == MODE_CHUD || mode == MODE_CHDD;
-  const char *bn = chud ? "V" : "B", *ldn = chud ? "ldv" : "ldb", *cn = chud ? "r" : "nrhs";
-  if (uplo != CHOL_LOWER && uplo != CHOL_UPPER) return failf(-pos.uplo, "%s: uplo", what);
+  if (pos.uplo && uplo != CHOL_LOWER && uplo != CHOL_UPPER) return failf(-pos.uplo, "%s: uplo", what);
+  if (pos.trans && trans != CHOL_NOTRANS && trans != CHOL_TRANS)
+    return failf(-pos.trans, "%s: trans must be CHOL_NOTRANS or CHOL_TRANS", what);
   if (dtype != CHOL_REAL_DOUBLE && dtype != CHOL_REAL_FLOAT)
     return failf(-pos.dtype, "%s: dtype must be fp64 or fp32", what);
   if (n < 0) return failf(-pos.n, "%s: n < 0", what);
-  if (solve && nrhs < 0) return failf(-pos.nrhs, "%s: %s < 0", what, cn);
+  if (pos.B && nrhs < 0) return failf(-pos.nrhs, "%s: %s < 0", what, nm.nrhs);
   if (batch < 0) return failf(-pos.batch, "%s: batch < 0", what);
-  if (n > 64 && chud)
-    return failf(CHOL_ERR_NOT_SUPPORTED,
-                 "%s: n > 64; use the descriptor routines (chol_chud_tile, chol_chdd_tile), which take any order",
-                 what);
-  if (n > 64)
-    return failf(CHOL_ERR_NOT_SUPPORTED,
-                 "%s: n > 64; use chol_potrf_batch (tiles that are multiples of 128) or the descriptor routines "
-                 "(chol_potrf_tile, chol_potrs_tile, chol_posv_tile)", what);
+  if (n > 64) return failf(CHOL_ERR_NOT_SUPPORTED, "%s: n > 64; %s", what, nm.beyond);
   if (lda < (n > 1 ? n : 1)) return failf(-pos.lda, "%s: lda < max(1, n)", what);
   if (strideA < (long long)lda * n) return failf(-pos.strideA, "%s: strideA < lda * n", what);
-  if (solve) {
-    if (ldb < (n > 1 ? n : 1)) return failf(-pos.ldb, "%s: %s < max(1, n)", what, ldn);
-    if (strideB < (long long)ldb * nrhs) return failf(-pos.strideB, "%s: stride%s < %s * %s", what, bn, ldn, cn);
+  if (pos.B) {
+    if (ldb < (n > 1 ? n : 1)) return failf(-pos.ldb, "%s: %s < max(1, n)", what, nm.ldb);
+    if (strideB < (long long)ldb * nrhs)
+      return failf(-pos.strideB, "%s: stride%s < %s * %s", what, nm.B, nm.ldb, nm.nrhs);
   }
-  if (n == 0 || batch == 0 || ((mode == MODE_POTRS || chud) && nrhs == 0)) {
+  if (n == 0 || batch == 0 || (empty_rhs && nrhs == 0)) {
     for (int b = 0; info && b < batch; ++b) info[b] = 0;
-    return 0;
+    return 1;
   }
-  const bool rhs = solve && nrhs > 0;
   const size_t es = dtype == CHOL_REAL_DOUBLE ? sizeof(double) : sizeof(float);
   if (!A || !is_device_ptr(A)) return failf(-pos.A, "%s: A must be a device pointer", what);
-  if (rhs) {
-    if (!B || !is_device_ptr(B)) return failf(-pos.B, "%s: %s must be a device pointer", what, bn);
+  if (pos.B && nrhs > 0) {
+    if (!B || !is_device_ptr(B)) return failf(-pos.B, "%s: %s must be a device pointer", what, nm.B);
     const uintptr_t a0 = (uintptr_t)A, b0 = (uintptr_t)B;
     const uintptr_t a1 = a0 + span_bytes(n, n, lda, strideA, batch, es);
     const uintptr_t b1 = b0 + span_bytes(n, nrhs, ldb, strideB, batch, es);
-    if (a0 < b1 && b0 < a1) return failf(-pos.B, "%s: the address ranges of A and %s overlap", what, bn);
+    if (a0 < b1 && b0 < a1) return failf(-pos.B, "%s: the address ranges of A and %s overlap", what, nm.B);
   }
+  return 0;
+}
 
+// A's image allows 16-byte accesses of whole rows
+inline bool rows_vec(const void *A, int lda, long long strideA, size_t es) {
+  return (uintptr_t)A % 16 == 0 && (size_t)lda * es % 16 == 0 && (unsigned long long)strideA * es % 16 == 0;
+}
+
+// One call on the main stream between the library's events: the first-failure word reset, launch(s, grid, dinfo,
+// first) for `batch` matrices in sub-groups of the padded order of n, the word and info back, the statistics.
+// -> 0, or b + 1 of the first failing matrix
+int run_timed(const char *what, int n, int batch, int *info, double bytes,
+              const std::function<void(hipStream_t, unsigned, int *, int *)> &launch) {
   return with_views({}, [&]() -> int {
     hipStream_t s = main_rank_ctx()->st[ST_MAIN];
     if (int rc = bt.ensure_bytes(0, 16 + (size_t)batch * sizeof(int), what)) return rc;
@@ -403,12 +595,42 @@ int run_batched(const char *what, int mode, const ArgPos &pos, int uplo, int dty
     const int NP = padded_order(n), per_wave = 64 / NP;
     const long long waves = ((long long)batch + per_wave - 1) / per_wave;
     const unsigned grid = (unsigned)((waves + BATCHED_THREADS / 64 - 1) / (BATCHED_THREADS / 64));
-    const bool vec = (uintptr_t)A % 16 == 0 && (size_t)lda * es % 16 == 0 && (unsigned long long)strideA * es % 16 == 0;
 
     // events: the whole call [0] .. [3], the kernel [1] .. [2]
     HIPCHECK(hipEventRecord(bt_ev[0], s));
     HIPCHECK(hipMemsetAsync(first, 0x7f, sizeof(int), s));
     HIPCHECK(hipEventRecord(bt_ev[1], s));
+    launch(s, grid, dinfo, first);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipEventRecord(bt_ev[2], s));
+    int head = NO_FAILURE;
+    HIPCHECK(hipMemcpyAsync(&head, first, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (info) HIPCHECK(hipMemcpyAsync(info, dinfo, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipEventRecord(bt_ev[3], s));
+    HIPCHECK(hipStreamSynchronize(s));
+    float total = 0, kern = 0;
+    HIPCHECK(hipEventElapsedTime(&total, bt_ev[0], bt_ev[3]));
+    HIPCHECK(hipEventElapsedTime(&kern, bt_ev[1], bt_ev[2]));
+    const double st[8] = {total, kern, (double)batch, (double)n, (double)per_wave, (double)grid, bytes, 0.0};
+    std::copy(st, st + 8, bt_stats);
+    return head == NO_FAILURE ? 0 : head;
+  });
+}
+
+// potrf, potrs, posv, chud and chdd.  MODE_CHUD / MODE_CHDD: B is the n x nrhs block of vectors V (only read), nrhs
+// is r.
+int run_batched(const char *what, int mode, const ArgPos &pos, int uplo, int dtype, int n, int nrhs, void *A, int lda,
+                long long strideA, void *B, int ldb, long long strideB, int batch, int *info) {
+  const bool chud = mode == MODE_CHUD || mode == MODE_CHDD;
+  if (int rc = check_images(what, pos, chud ? NAMES_CHUD : NAMES_POTRF, uplo, 0, dtype, n, nrhs, A, lda, strideA, B,
+                            ldb, strideB, batch, mode == MODE_POTRS || chud, info))
+    return rc < 0 ? rc : 0;
+  const bool rhs = mode != MODE_POTRF && nrhs > 0;
+  const size_t es = dtype == CHOL_REAL_DOUBLE ? sizeof(double) : sizeof(float);
+  const bool vec = rows_vec(A, lda, strideA, es);
+  const double tri = 0.5 * n * (n + 1.0), rhs_el = chud ? 1.0 * n * nrhs : rhs ? 2.0 * n * nrhs : 0.0;  // (V: read)
+  const double el = (mode == MODE_POTRS ? tri : 2.0 * tri) + rhs_el;
+  return run_timed(what, n, batch, info, el * es * batch, [&](hipStream_t s, unsigned grid, int *dinfo, int *first) {
     const int kmode = rhs ? mode : MODE_POTRF;  // (posv without a right-hand side factors)
     if (chud) {
       const double sigma = mode == MODE_CHUD ? 1.0 : -1.0;
@@ -430,22 +652,65 @@ int run_batched(const char *what, int mode, const ArgPos &pos, int uplo, int dty
                                     n,          nrhs,       batch, vec,     dinfo, first};
       launch_batched<float>(uplo == CHOL_UPPER, kmode, s, grid, p);
     }
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipEventRecord(bt_ev[2], s));
-    int head = NO_FAILURE;
-    HIPCHECK(hipMemcpyAsync(&head, first, sizeof(int), hipMemcpyDeviceToHost, s));
-    if (info) HIPCHECK(hipMemcpyAsync(info, dinfo, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipEventRecord(bt_ev[3], s));
-    HIPCHECK(hipStreamSynchronize(s));
-    float total = 0, kern = 0;
-    HIPCHECK(hipEventElapsedTime(&total, bt_ev[0], bt_ev[3]));
-    HIPCHECK(hipEventElapsedTime(&kern, bt_ev[1], bt_ev[2]));
+  });
+}
 
-    const double tri = 0.5 * n * (n + 1.0), rhs_el = chud ? 1.0 * n * nrhs : rhs ? 2.0 * n * nrhs : 0.0;  // (V: read)
-    const double el = (mode == MODE_POTRS ? tri : 2.0 * tri) + rhs_el;
-    const double st[8] = {total, kern, (double)batch, (double)n, (double)per_wave, (double)grid, el * es * batch, 0.0};
-    std::copy(st, st + 8, bt_stats);
-    return head == NO_FAILURE ? 0 : head;
+// trtrs (solve) and trmm.  The forward half is L, the backward half L^T, L the lower factor however it is stored:
+// (Lower, NoTrans) and (Upper, Trans) are forward.
+int run_half(const char *what, bool solve, const ArgPos &pos, int uplo, int trans, int dtype, int n, int nrhs,
+             double alpha, const void *A, int lda, long long strideA, void *B, int ldb, long long strideB, int batch,
+             int *info) {
+  if (int rc = check_images(what, pos, NAMES_HALF, uplo, trans, dtype, n, nrhs, A, lda, strideA, B, ldb, strideB,
+                            batch, true, info))
+    return rc < 0 ? rc : 0;
+  const size_t es = dtype == CHOL_REAL_DOUBLE ? sizeof(double) : sizeof(float);
+  const bool forward = (uplo == CHOL_LOWER) == (trans == CHOL_NOTRANS);
+  const int op = solve ? (forward ? HALF_SOLVE_FWD : HALF_SOLVE_BWD) : (forward ? HALF_MUL_FWD : HALF_MUL_BWD);
+  const bool zero = !solve && (dtype == CHOL_REAL_DOUBLE ? alpha == 0.0 : (float)alpha == 0.0f);
+  const double el = zero ? 1.0 * n * nrhs : 0.5 * n * (n + 1.0) + 2.0 * n * nrhs;  // (alpha == 0: B written)
+  return run_timed(what, n, batch, info, el * es * batch, [&](hipStream_t s, unsigned grid, int *dinfo, int *first) {
+    const int NP = padded_order(n);
+    const bool vec = rows_vec(A, lda, strideA, es);
+    if (dtype == CHOL_REAL_DOUBLE) {
+      const HalfArgs<double> p = {(const double *)A, (double *)B, lda, strideA, ldb,   strideB, n,
+                                  nrhs,              batch,       vec, alpha,   dinfo, first};
+      if (zero) k_zero_rows<double><<<grid, BATCHED_THREADS, 0, s>>>(p.B, ldb, strideB, n, nrhs, batch, NP);
+      else launch_half_rows<double>(uplo == CHOL_UPPER, op, s, grid, p);
+    } else {
+      const HalfArgs<float> p = {(const float *)A, (float *)B, lda, strideA,      ldb,   strideB, n,
+                                 nrhs,             batch,      vec, (float)alpha, dinfo, first};
+      if (zero) k_zero_rows<float><<<grid, BATCHED_THREADS, 0, s>>>(p.B, ldb, strideB, n, nrhs, batch, NP);
+      else launch_half_rows<float>(uplo == CHOL_UPPER, op, s, grid, p);
+    }
+  });
+}
+
+// logdet: the diagonal alone, the values to a device array
+int run_logdet(int dtype, int n, const void *A, int lda, long long strideA, int batch, double *logdet, int *info) {
+  const char *what = "logdet_batched";
+  const int rc = check_images(what, POS_LOGDET, NAMES_HALF, 0, 0, dtype, n, 0, A, lda, strideA, nullptr, 1, 0, batch,
+                              false, info);
+  if (rc < 0) return rc;
+  if (batch == 0) return 0;
+  if (!logdet || !is_device_ptr(logdet)) return failf(-7, "%s: logdet must be a device pointer", what);
+  if (rc) {  // n = 0: the determinant of the empty matrix is 1
+    return with_views({}, [&]() -> int {
+      hipStream_t s = main_rank_ctx()->st[ST_MAIN];
+      HIPCHECK(hipMemsetAsync(logdet, 0, (size_t)batch * sizeof(double), s));
+      HIPCHECK(hipStreamSynchronize(s));
+      return 0;
+    });
+  }
+  const size_t es = dtype == CHOL_REAL_DOUBLE ? sizeof(double) : sizeof(float);
+  const double bytes = (1.0 * n * es + sizeof(double)) * batch;
+  return run_timed(what, n, batch, info, bytes, [&](hipStream_t s, unsigned grid, int *dinfo, int *first) {
+    const int NP = padded_order(n);
+    if (dtype == CHOL_REAL_DOUBLE)
+      k_diag_logdet<double>
+          <<<grid, BATCHED_THREADS, 0, s>>>((const double *)A, lda, strideA, n, batch, NP, logdet, dinfo, first);
+    else
+      k_diag_logdet<float>
+          <<<grid, BATCHED_THREADS, 0, s>>>((const float *)A, lda, strideA, n, batch, NP, logdet, dinfo, first);
   });
 }
 
@@ -487,6 +752,23 @@ int chol_chdd_batched(int uplo, int dtype, int n, int r, void *A, int lda, long 
                       long long strideV, int batch, int *info) {
   return run_batched("chdd_batched", MODE_CHDD, POS_SOLVE, uplo, dtype, n, r, A, lda, strideA, const_cast<void *>(V),
                      ldv, strideV, batch, info);
+}
+
+int chol_trtrs_batched(int uplo, int trans, int dtype, int n, int nrhs, const void *A, int lda, long long strideA,
+                       void *B, int ldb, long long strideB, int batch, int *info) {
+  return run_half("trtrs_batched", true, POS_TRTRS, uplo, trans, dtype, n, nrhs, 1.0, A, lda, strideA, B, ldb, strideB,
+                  batch, info);
+}
+
+int chol_trmm_batched(int uplo, int trans, int dtype, int n, int nrhs, double alpha, const void *A, int lda,
+                      long long strideA, void *B, int ldb, long long strideB, int batch) {
+  return run_half("trmm_batched", false, POS_TRMM, uplo, trans, dtype, n, nrhs, alpha, A, lda, strideA, B, ldb,
+                  strideB, batch, nullptr);
+}
+
+int chol_logdet_batched(int dtype, int n, const void *A, int lda, long long strideA, int batch, double *logdet,
+                        int *info) {
+  return run_logdet(dtype, n, A, lda, strideA, batch, logdet, info);
 }
 
 int chol_last_batched_stats(double *out8) {

@@ -482,9 +482,58 @@ int chol_chud_batched(int uplo, int dtype, int n, int r, void *A, int lda, long 
                       long long strideV, int batch, int *info);
 int chol_chdd_batched(int uplo, int dtype, int n, int r, void *A, int lda, long long strideA, const void *V, int ldv,
                       long long strideV, int batch, int *info);
+/* One half of such a factor alone (what chol_trtrs_tile, chol_trmm_tile and chol_logdet_tile are to the tiled side):
+ * B <- inv(op(T)) B (chol_trtrs_batched), B <- alpha op(T) B (chol_trmm_batched) and log det(L L^T)
+ * (chol_logdet_batched).  The storage rules are chol_potrs_batched's: column-major images at a fixed stride,
+ * lda >= max(1,n), strideA >= lda n, B likewise (n x nrhs, ldb >= max(1,n), strideB >= ldb nrhs); device pointers
+ * only; element alignment alone; 64-bit offsets; 0 <= n <= 64 (n > 64: CHOL_ERR_NOT_SUPPORTED; chol_trtrs_tile,
+ * chol_trmm_tile and chol_logdet_tile take any order); fp64 or fp32 by dtype, fp32 in single precision throughout;
+ * zero sizes (n, nrhs, batch) return 0 with nothing written on the device (but see logdet for n = 0); overlapping
+ * address ranges of A and B are an argument error at B's position; synchronous, on the library's main stream.
+ *
+ * T is the `uplo` triangle of each image, op(T) = T (CHOL_NOTRANS) or T^T (CHOL_TRANS): all four combinations.  uplo
+ * only chooses the loads: L below is the lower factor however it is stored (Upper holds U = L^T), so (Lower, NoTrans)
+ * and (Upper, Trans) are the FORWARD half, op(T) = L, and (Lower, Trans) and (Upper, NoTrans) the BACKWARD half,
+ * op(T) = L^T.  A IS ONLY READ: the whole buffer comes back bit for bit; the other strict triangle, the lda - n rows
+ * under a column and the gaps may hold NaN and none of it reaches B.  Of B only the n x nrhs entries are written.
+ *
+ * The arithmetic, fixed (each a b + c one fused multiply-add; r_j = 1 / L(j,j); P = 8, 16, 32 or 64, the least of them
+ * >= n; one column of B at a time and each on its own):
+ *   trtrs forward   for j = 0..n-1:  y_j = b_j r_j;  b_i = fma(-L(i,j), y_j, b_i) (i > j)
+ *   trtrs backward  for j = n-1..0:  t_i = L(i,j) x_i (j < i < n), +0 for the other i < P;
+ *                   for off = P/2, P/4, .., 1: t_i = t_i + t_(i xor off) (all i at once);  x_j = (b_j - t_j) r_j
+ *     These are the two halves of chol_potrs_batched: the forward call followed by the backward call on the same B
+ *     returns its bits.  An exact zero on the stored diagonal gives info[b] = j (1-based, the first): that matrix's B
+ *     is untouched and no other matrix is disturbed, also not one that shares its wavefront.  info is a host array of
+ *     `batch` ints or NULL; the return value is 0, or b + 1 of the first such matrix.
+ *   trmm forward    s_i = +0;  for k = 0..i ascending: s_i = fma(L(i,k), z_k, s_i);  B(i) = alpha s_i
+ *   trmm backward   for j = n-1..0:  t_i = L(i,j) z_i (j <= i < n), +0 for the other i < P;  the same butterfly;
+ *                   B(j) = alpha t_j
+ *     The terms outside the triangle are left out, not multiplied by a stored zero: a NaN in z_k reaches the rows
+ *     i >= k (forward) or i <= k (backward) and no other.  alpha is rounded to the dtype; with alpha == 0 neither A nor
+ *     B is read and B <- +0, as BLAS does (a NaN in B does not survive).  A zero on the diagonal is no failure: trmm
+ *     has no info and returns 0.
+ *   logdet          only the diagonal is read, so there is no uplo.  `logdet` is a DEVICE array of `batch` doubles
+ *     for both dtypes (a host pointer is an argument error):
+ *     logdet[b] = 2 (((log d_0 + log d_1) + log d_2) + ..), d_j = L(j,j) converted to fp64, the device's fp64 log, a
+ *     plain ascending chain.  info[b] = j (1-based) for the first d_j <= 0 or NaN, and logdet[b] is then NaN; the
+ *     return value is 0, or b + 1 of the first such matrix.  n = 0 gives logdet[b] = 0 (the one write of a zero size).
+ * For every routine the bits depend on n and that matrix's data alone: not on uplo, the layout, nrhs, the matrix's
+ * place in the batch, its wavefront's other matrices, or whether the call is repeated.
+ *
+ * Argument positions: trtrs 1 uplo, 2 trans, 3 dtype, 4 n, 5 nrhs, 6 A, 7 lda, 8 strideA, 9 B, 10 ldb, 11 strideB,
+ * 12 batch; trmm 1 uplo, 2 trans, 3 dtype, 4 n, 5 nrhs, 6 alpha, 7 A, 8 lda, 9 strideA, 10 B, 11 ldb, 12 strideB,
+ * 13 batch; logdet 1 dtype, 2 n, 3 A, 4 lda, 5 strideA, 6 batch, 7 logdet. */
+int chol_trtrs_batched(int uplo, int trans, int dtype, int n, int nrhs, const void *A, int lda, long long strideA,
+                       void *B, int ldb, long long strideB, int batch, int *info);
+int chol_trmm_batched(int uplo, int trans, int dtype, int n, int nrhs, double alpha, const void *A, int lda,
+                      long long strideA, void *B, int ldb, long long strideB, int batch);
+int chol_logdet_batched(int dtype, int n, const void *A, int lda, long long strideA, int batch, double *logdet,
+                        int *info);
 /* The last batched call: total time and kernel time [ms] (the library's own events); batch; n; matrices per wavefront;
  * workgroups launched; the bytes the algorithm must move (the stored triangles read and written, plus B read and
- * written; chud and chdd: the triangles read and written, plus V read); 0. */
+ * written; chud and chdd: the triangles read and written, plus V read; trtrs and trmm: the triangle read, plus B read
+ * and written -- B written alone with alpha == 0; logdet: n diagonal elements read and 8 bytes written); 0. */
 int chol_last_batched_stats(double *out8);
 
 /* One half of a Cholesky factor alone: the triangular solve, the triangular product and the log-determinant, on
