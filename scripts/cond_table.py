@@ -2,6 +2,8 @@
 """Measured accuracy of the GPU tile operations against the CPU oracle as a function of the
 condition number (the table of DESIGN.md section 6).  Run on the GPU box:
     python scripts/cond_table.py > gpurun_out/cond_table.txt
+With one argument, d or s.  d (the default): fp64.  s: fp32 -- the same constructions rounded to fp32 at the fp32 rows' parameters, eps of fp32, the
+oracle's fp32 routines beside the GPU's, the forward differences against the fp64 oracle on the rounded input.
 Columns: componentwise backward error of POTRF and TRSM in units of B*eps (GPU | oracle), i.e.
 max |L L^T - A| / (B eps |L||L^T|) and max |X L^T - A| / (B eps (|X||L^T| + |A|)); forward difference
 GPU vs oracle relative to max|ref|, and that difference divided by (B eps kappa)."""
@@ -17,67 +19,82 @@ from dense_linear_app_amd import chameleon as ch  # noqa: E402
 from oracle import oracle as orc  # noqa: E402  (checker)
 import test_gpu_conditioning as tc  # noqa: E402
 
-EPS = np.finfo(float).eps
+DT = sys.argv[1] if len(sys.argv) > 1 else "d"
+assert DT in ("d", "s"), "usage: cond_table.py [d|s]"
+EPS = tc.eps_of(DT)
+wide, rounded = tc.wide, (lambda A: tc.rounded(A, DT))
+CH_DT = tc.chdt(ch, DT)
+potrf, trsm = tc.op(ch, DT, "potrf"), tc.op(ch, DT, "trsm")
+orc_potrf, orc_trsm = (orc.dpotrf, orc.dtrsm) if DT == "d" else (orc.spotrf, orc.strsm)
+KAPPAS = {"d": (1e2, 1e6, 1e10), "s": (1e1, 1e2, 1e4)}[DT]
+KAPPA_128 = {"d": 1e13, "s": 1e5}[DT]
+DECADES = {"d": (13, 26), "s": (6, 9)}[DT]
+KLS = {"d": (1e3, 1e8, 1e12), "s": (1e1, 1e3, 1e5)}[DT]
+WHOLE = {"d": ((2048, 512, 1e2), (2048, 512, 1e8), (2048, 512, 1e11), (4096, 1024, 1e10)),
+         "s": ((2048, 512, 1e1), (2048, 512, 1e2), (2048, 512, 1e3), (4096, 1024, 1e2))}[DT]
 
 
 def bw_potrf(L, A, B):
-    L = np.tril(L)
+    L, A = np.tril(wide(L)), wide(A)
     return float((np.abs(np.tril(L @ L.T - A)) / (B * EPS * (np.abs(L) @ np.abs(L).T) + 1e-300)).max())
 
 
 def bw_trsm(X, L, A, B):
-    L = np.tril(L)
+    X, L, A = wide(X), np.tril(wide(L)), wide(A)
     return float((np.abs(X @ L.T - A) / (B * EPS * (np.abs(X) @ np.abs(L).T + np.abs(A)) + 1e-300)).max())
 
 
 def main():
     ch.CHAMELEON_Init(1, 1)
     print("kind       B    kappa2(A)  kinf(L)   potrf_bw gpu|orc   trsm_bw gpu|orc   |dL|/|L|   /(B eps k)  |dX|/|X|   /(B eps kL)")
-    cases = [("spectral", B, k) for B in (128, 512, 1024) for k in (1e2, 1e6, 1e10)] + [("spectral", 128, 1e13)]
-    cases += [("graded", B, k) for B in (128, 512) for k in (13, 26)]
+    cases = [("spectral", B, k) for B in (128, 512, 1024) for k in KAPPAS] + [("spectral", 128, KAPPA_128)]
+    cases += [("graded", B, k) for B in (128, 512) for k in DECADES]
     for kind, B, k in cases:
         if kind == "spectral":
             A = tc.spd_spectral(2 * B, k, seed=B + int(np.log10(k)))
         else:
             A, _, _ = tc.spd_graded(2 * B, k, seed=B + int(k))
+        A = rounded(A)
         Akk, A10 = np.asfortranarray(A[:B, :B]), np.asfortranarray(A[B:, :B])
         L = Akk.copy(order="F")
-        info = ch.CHAMELEON_dpotrf_Tile(ch.ChamLower, tc.desc1(ch, L))
-        Lref, iref = orc.dpotrf(Akk)
+        info = potrf(ch.ChamLower, tc.desc1(ch, L))
+        Lorc, iref = orc_potrf(Akk)
+        Lref = orc.dpotrf(wide(Akk))[0]  # (fp64: Lorc itself)
         X = A10.copy(order="F")
-        ch.CHAMELEON_dtrsm_Tile(ch.ChamRight, ch.ChamLower, ch.ChamTrans, ch.ChamNonUnit, 1.0, tc.desc1(ch, L), tc.desc1(ch, X))
+        trsm(ch.ChamRight, ch.ChamLower, ch.ChamTrans, ch.ChamNonUnit, 1.0, tc.desc1(ch, L), tc.desc1(ch, X))
         Lt = np.asfortranarray(np.tril(L))
-        Xref = orc.dtrsm(Lt, A10)
-        kA, kL = np.linalg.cond(Akk), np.linalg.cond(Lt, np.inf)
-        dL = np.abs(np.tril(L) - np.tril(Lref)).max() / np.abs(Lref).max()
+        Xorc, Xref = orc_trsm(Lt, A10), orc.dtrsm(wide(Lt), wide(A10))
+        kA, kL = np.linalg.cond(wide(Akk)), np.linalg.cond(wide(Lt), np.inf)
+        dL = np.abs(np.tril(wide(L)) - np.tril(Lref)).max() / np.abs(Lref).max()
         dX = np.abs(X - Xref).max() / np.abs(Xref).max()
-        print(f"{kind:9s} {B:5d} {kA:10.2e} {kL:9.2e}  {bw_potrf(L, Akk, B):7.3f} | {bw_potrf(Lref, Akk, B):5.3f}   "
-              f"{bw_trsm(X, Lt, A10, B):7.3f} | {bw_trsm(Xref, Lt, A10, B):5.3f}  {dL:9.2e} {dL / (B * EPS * kA):9.2e}  {dX:9.2e} {dX / (B * EPS * kL):9.2e}"
+        print(f"{kind:9s} {B:5d} {kA:10.2e} {kL:9.2e}  {bw_potrf(L, Akk, B):7.3f} | {bw_potrf(Lorc, Akk, B):5.3f}   "
+              f"{bw_trsm(X, Lt, A10, B):7.3f} | {bw_trsm(Xorc, Lt, A10, B):5.3f}  {dL:9.2e} {dL / (B * EPS * kA):9.2e}  {dX:9.2e} {dX / (B * EPS * kL):9.2e}"
               f"  info {info}/{iref}", flush=True)
     # general triangular factor (TRSM alone)
-    for kl in (1e3, 1e8, 1e12):
+    for kl in KLS:
         B = 256
-        rng = np.random.default_rng(int(np.log10(kl)))
-        U, _ = np.linalg.qr(rng.standard_normal((B, B)))
-        V, _ = np.linalg.qr(rng.standard_normal((B, B)))
-        _, R = np.linalg.qr(((U * np.logspace(0, -np.log10(kl), B)) @ V.T).T)
-        Lt = np.asfortranarray(np.tril(R.T))
-        A = np.asfortranarray(rng.uniform(-1, 1, (B, B)))
+        Lm, A = tc.cc.triangular_input(DT, kl, B)
+        Lt = np.asfortranarray(np.tril(np.nan_to_num(Lm)))
         X = A.copy(order="F")
-        ch.CHAMELEON_dtrsm_Tile(ch.ChamRight, ch.ChamLower, ch.ChamTrans, ch.ChamNonUnit, 1.0, tc.desc1(ch, Lt.copy(order="F")), tc.desc1(ch, X))
-        Xref = orc.dtrsm(Lt, A)
-        kL = np.linalg.cond(Lt, np.inf)
+        trsm(ch.ChamRight, ch.ChamLower, ch.ChamTrans, ch.ChamNonUnit, 1.0, tc.desc1(ch, Lt.copy(order="F")), tc.desc1(ch, X))
+        Xorc, Xref = orc_trsm(Lt, A), orc.dtrsm(wide(Lt), wide(A))
+        kL = np.linalg.cond(wide(Lt), np.inf)
         dX = np.abs(X - Xref).max() / np.abs(Xref).max()
-        print(f"triangular {B:4d} {'-':>10s} {kL:9.2e}  {'-':>7s} | {'-':>5s}   {bw_trsm(X, Lt, A, B):7.3f} | {bw_trsm(Xref, Lt, A, B):5.3f}  "
+        print(f"triangular {B:4d} {'-':>10s} {kL:9.2e}  {'-':>7s} | {'-':>5s}   {bw_trsm(X, Lt, A, B):7.3f} | {bw_trsm(Xorc, Lt, A, B):5.3f}  "
               f"{'-':>9s} {'-':>9s}  {dX:9.2e} {dX / (B * EPS * kL):9.2e}", flush=True)
     # whole matrix
-    for N, B, k in ((2048, 512, 1e2), (2048, 512, 1e8), (2048, 512, 1e11), (4096, 1024, 1e10)):
-        A = tc.spd_spectral(N, k, seed=N + int(np.log10(k)))
-        d = ch.CHAMELEON_Desc_Create(None, ch.ChamRealDouble, B, B, B * B, N, N, 0, 0, N, N, 1, 1)
+    for N, B, k in WHOLE:
+        A = rounded(tc.spd_spectral(N, k, seed=N + int(np.log10(k))))
+        d = ch.CHAMELEON_Desc_Create(None, CH_DT, B, B, B * B, N, N, 0, 0, N, N, 1, 1)
         d.from_lapack(A)
-        info = ch.CHAMELEON_dpotrf_Tile(ch.ChamLower, d)
-        L = np.tril(d.to_lapack())
-        Lref, iref = orc.cholesky_lower(A, B)
+        info = potrf(ch.ChamLower, d)
+        L = np.tril(wide(d.to_lapack()))
+        if DT == "d":
+            Lref, iref = orc.cholesky_lower(A, B)
+        else:
+            Lref, iref = orc.spotrf(A)
+            Lref = np.tril(wide(Lref))
+        A = wide(A)
         nA = np.linalg.norm(A)
         print(f"whole N={N} B={B} kappa={k:.0e}: residual_F gpu {np.linalg.norm(L @ L.T - A) / nA:.2e} | oracle {np.linalg.norm(Lref @ Lref.T - A) / nA:.2e}; "
               f"componentwise/(N eps) gpu {bw_potrf(L, A, N):.3f} | oracle {bw_potrf(Lref, A, N):.3f}; max|dL|/max|L| {np.abs(L - Lref).max() / np.abs(Lref).max():.2e}; info {info}/{iref}", flush=True)

@@ -1,7 +1,7 @@
 """What the tests of the routines share: the dtype and code maps, the bit view, the triangle helpers and the two ways of
 storing a matrix in one triangle, the descriptor constructor, access to a descriptor's stored image on the device, and
 the scaffolds of the tests that every routine repeats (a P x Q descriptor is refused, a sub-matrix view of a user
-buffer, the padding of a ragged image, the checks without a GPU).  A plain module, imported like the *_model.py files:
+buffer, the padding of a ragged image, the checks without a GPU, a case list run in a fresh child process).  A plain module, imported like the *_model.py files:
 no fixtures, no hooks.  It needs numpy alone to import; ctypes, torch and the library are touched inside the helpers
 that use them, so the modules that import it still import on a machine without a GPU.
 
@@ -185,6 +185,31 @@ def assert_before_init_refused(sym, args):
     L = _lib.lib()
     assert getattr(L, sym)(*args) == -101  # CHOL_ERR_NOT_INITIALIZED
     assert b"before chol_init" in L.chol_last_error()
+
+
+# ---------------------------------------------------------------- child processes
+def run_child(script, args, env, timeout, what):
+    """`script args` in one fresh python process under the environment switches `env` (the library reads them once, at
+    chol_init) with a time limit of its own -> the records of its "CASE <json>" lines.  A child that hangs or is killed by
+    a signal (a GPU fault or abort, not a wrong number) ends the whole session: nothing more is started on that GPU"""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import pytest
+
+    try:
+        r = subprocess.run([sys.executable, os.path.abspath(script), *args], env=dict(os.environ, **env),
+                           capture_output=True, text=True, timeout=timeout)
+    except subprocess.TimeoutExpired as e:
+        pytest.exit(f"the child of {what} hung: nothing more is started on this GPU ({e.stdout})", returncode=3)
+    print(r.stdout)
+    if r.returncode < 0 or r.returncode in (134, 139):
+        pytest.exit(f"the child of {what} died ({r.returncode}): nothing more is started on this GPU\n"
+                    f"{r.stdout}\n{r.stderr[-2000:]}", returncode=3)
+    assert r.returncode == 0, (r.stdout, r.stderr[-2000:])
+    return [json.loads(ln[5:]) for ln in r.stdout.splitlines() if ln.startswith("CASE ")]
 
 
 # ---------------------------------------------------------------- matrices

@@ -225,8 +225,10 @@ def chol_unblocked(T, peak):
     return 0
 
 
-def potrf_blocked(A, dtype, nb=NB):
-    """-> (L, peak): right-looking Cholesky of the lower triangle of A in nb-blocks"""
+def potrf_blocked_info(A, dtype, nb=NB):
+    """-> (info, M, peak): right-looking Cholesky of the lower triangle of A in nb-blocks, stopped at the first pivot that
+    is not > 0 (info = its column + 1, LAPACK's).  M: the working image as it then stands -- the factor's columns before
+    that pivot, the pivot itself at M[info - 1, info - 1], the Schur complement behind it; info = 0: the factor"""
     dtype = np.dtype(dtype)
     n = A.shape[0]
     M = padded(A, dtype, nb)
@@ -236,14 +238,23 @@ def potrf_blocked(A, dtype, nb=NB):
     for k in range(0, N, nb):
         d, t = slice(k, k + nb), slice(k + nb, N)
         Tk = np.tril(M[d, d])
-        assert chol_unblocked(Tk, peak) == 0
+        info = chol_unblocked(Tk, peak)
         M[d, d] = Tk
+        if info:
+            return k + info, np.tril(M[:n, :n]), peak.value
         if k + nb < N:
             W = inv_lower(Tk, peak)
             M[t, d] = peak.mm(M[t, d], W.T)
             M[t, t] = np.tril(peak.mm(M[t, d], M[t, d].T, M[t, t]))
             peak.see(M[t, :])
-    return np.tril(M[:n, :n]), peak.value
+    return 0, np.tril(M[:n, :n]), peak.value
+
+
+def potrf_blocked(A, dtype, nb=NB):
+    """-> (L, peak): right-looking Cholesky of the lower triangle of A in nb-blocks"""
+    info, L, peak = potrf_blocked_info(A, dtype, nb)
+    assert info == 0
+    return L, peak
 
 
 def ldl_blocked(A, dtype, nb=NB):

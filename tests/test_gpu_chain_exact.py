@@ -18,14 +18,13 @@ single-tile POTRF and TRSM (alpha != 1 takes the throughput form on one tile; B 
 wave-level task path."""
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 import dyadic_model as dm
-from chol_testkit import bits, chdt, desc, npdt, stored_lower
+from chol_testkit import bits, chdt, desc, npdt, run_child, stored_lower
 
 pytestmark = pytest.mark.gpu
 
@@ -200,17 +199,7 @@ def test_potrf_is_exact_in_every_form_of_the_chain(name, env, regime):
     128-blocks (and two ragged orders on such tiles), mirror and mod3 on nbm = 2, 4 and the two ragged orders (CASES),
     fp64 and fp32, in one child per setting: info = 0, tril(F) == L with zero mismatches, the NaN-filled strict upper
     triangle untouched, and -- where the setting forces a regime -- the library's count says that it ran"""
-    try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "cases", inputs_file()], env=dict(os.environ, **env),
-                           capture_output=True, text=True, timeout=300)
-    except subprocess.TimeoutExpired as e:
-        pytest.exit(f"the child of setting {name} hung: nothing more is started on this GPU ({e.stdout})", returncode=3)
-    print(r.stdout)
-    if r.returncode < 0 or r.returncode in (134, 139):  # killed by a signal: a GPU fault or abort, not a wrong number
-        pytest.exit(f"the child of setting {name} died ({r.returncode}): nothing more is started on this GPU\n"
-                    f"{r.stdout}\n{r.stderr[-2000:]}", returncode=3)
-    assert r.returncode == 0, (r.stdout, r.stderr[-2000:])
-    cases = [json.loads(ln[5:]) for ln in r.stdout.splitlines() if ln.startswith("CASE ")]
+    cases = run_child(__file__, ["cases", inputs_file()], env, 300, f"setting {name}")
     assert [(c["family"], c["N"], c["B"], c["dt"]) for c in cases] == [(fam, N, B, dt) for fam, N, B in CASES for dt in "ds"]
     bad = [c for c in cases if c["info"] != 0 or c["mismatches"] or c["upper_touched"]]
     assert not bad, bad
@@ -242,17 +231,7 @@ def test_intile_update_leaves_a_finite_upper_triangle_alone(fused):
     is -7, one tile of 2 and of 4 blocks (one and three in-tile steps), the parity and the panel family (whose in-tile
     update touches every entry of the diagonal blocks' lower triangles), fp64 and fp32, the solve and the update of a step
     in one launch and in two: L exact, and not one bit above the diagonal changed"""
-    try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "finite-fill"],
-                           env=dict(os.environ, CHOLMI_INTILE_FUSED=fused), capture_output=True, text=True, timeout=120)
-    except subprocess.TimeoutExpired as e:
-        pytest.exit(f"the finite-fill child hung: nothing more is started on this GPU ({e.stdout})", returncode=3)
-    print(r.stdout)
-    if r.returncode < 0 or r.returncode in (134, 139):
-        pytest.exit(f"the finite-fill child died ({r.returncode}): nothing more is started on this GPU\n"
-                    f"{r.stdout}\n{r.stderr[-2000:]}", returncode=3)
-    assert r.returncode == 0, (r.stdout, r.stderr[-2000:])
-    cases = [json.loads(ln[5:]) for ln in r.stdout.splitlines() if ln.startswith("CASE ")]
+    cases = run_child(__file__, ["finite-fill"], {"CHOLMI_INTILE_FUSED": fused}, 120, "the finite fill")
     assert [(c["family"], c["B"], c["dt"]) for c in cases] == [(fam, B, dt) for fam, B in FILL_CASES for dt in "ds"]
     bad = [c for c in cases if c["info"] != 0 or c["mismatches"] or c["upper_touched"]]
     assert not bad, bad
