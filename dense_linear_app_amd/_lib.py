@@ -85,6 +85,10 @@ def lib() -> C.CDLL:
         "chol_trtrs_batched": ([i, i, i, i, i, vp, i, C.c_longlong, vp, i, C.c_longlong, i, C.POINTER(i)], i),
         "chol_trmm_batched": ([i, i, i, i, i, d, vp, i, C.c_longlong, vp, i, C.c_longlong, i], i),
         "chol_logdet_batched": ([i, i, vp, i, C.c_longlong, i, vp, C.POINTER(i)], i),
+        "chol_trtri_batched": ([i, i, i, vp, i, C.c_longlong, i, C.POINTER(i)], i),
+        "chol_potri_batched": ([i, i, i, vp, i, C.c_longlong, i, C.POINTER(i)], i),
+        "chol_poinv_batched": ([i, i, i, vp, i, C.c_longlong, i, C.POINTER(i)], i),
+        "chol_invdiag_batched": ([i, i, i, vp, i, C.c_longlong, vp, C.c_longlong, i, C.POINTER(i)], i),
         "chol_last_batched_stats": ([C.POINTER(d)], i),
         "chol_trtrs_tile": ([i, i, i, vp, vp], i),
         "chol_trmm_tile": ([i, i, i, i, d, vp, vp], i),

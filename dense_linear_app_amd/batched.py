@@ -1,6 +1,7 @@
 """Batched Cholesky of small matrices on torch device tensors, in place (include/cholmi.h: chol_potrf_batched,
 chol_potrs_batched, chol_posv_batched, chol_chud_batched, chol_chdd_batched, chol_trtrs_batched, chol_trmm_batched,
-chol_logdet_batched): 10^3 .. 10^6 independent SPD matrices of order n <= 64.
+chol_logdet_batched, chol_trtri_batched, chol_potri_batched, chol_poinv_batched, chol_invdiag_batched): 10^3 .. 10^6
+independent SPD matrices of order n <= 64.
 
     info = potrf_batched(A)            A: (batch, n, n) or (n, n), float64 or float32
     info = potrs_batched(A, B)         B: (batch, n) or (batch, n, nrhs)   [(n,) or (n, nrhs) with a 2-d A]
@@ -10,6 +11,10 @@ chol_logdet_batched): 10^3 .. 10^6 independent SPD matrices of order n <= 64.
     info = trtrs_batched(A, B, uplo, trans)     B <- inv(op(T)) B, T the `uplo` triangle of A (a factor), only read
     trmm_batched(A, B, uplo, trans, alpha)      B <- alpha op(T) B
     logdet, info = logdet_batched(A)            log det(L L^T) from the diagonal: a float64 tensor on A's device
+    info = trtri_batched(A, uplo)               the stored triangle T <- inv(T)
+    info = potri_batched(A, uplo)               the factor's triangle <- that of inv(L L^T)
+    info = poinv_batched(A, uplo)               potrf_batched then potri_batched in one pass
+    D, info = invdiag_batched(A, uplo)          diag(inv(L L^T)): a new (batch, n) tensor of A's dtype; A only read
 
 Each info is LAPACK's info of every matrix as a numpy int32 array.  The matrices of A are column-major
 (stride(-2) == 1, lda = stride(-1)) or row-major (stride(-1) == 1, lda = stride(-2)); `uplo` always speaks of the
@@ -206,6 +211,49 @@ def logdet_batched(A):
     return out, info
 
 
+def _inverse(name, A, uplo):
+    dt, code, n, lda, sa, batch = _images_of_A(A, uplo)
+    _require_device(A)
+    info, pinfo = _info(batch)
+    check(name, getattr(lib(), name)(code, dt, n, A.data_ptr(), lda, sa, batch, pinfo))
+    return info
+
+
+def trtri_batched(A, uplo: int = ChamLower) -> np.ndarray:
+    """The `uplo` triangle T of every matrix of A (what potrf_batched left) <- inv(T), in place: Lower gives
+    W = inv(L), Upper inv(U) = W^T.  For a finite factor the bits of the lower triangle of trtrs_batched(A, I).
+    -> info; info[b] = j: an exact zero at T_jj of matrix b, its A untouched"""
+    return _inverse("chol_trtri_batched", A, uplo)
+
+
+def potri_batched(A, uplo: int = ChamLower) -> np.ndarray:
+    """The factor in the `uplo` triangle of every matrix of A <- the `uplo` triangle of inv(L L^T) (the covariance of
+    a normal-equations estimate, a block-Jacobi block).  -> info; info[b] = j: an exact zero at L_jj of matrix b, its
+    A untouched"""
+    return _inverse("chol_potri_batched", A, uplo)
+
+
+def poinv_batched(A, uplo: int = ChamLower) -> np.ndarray:
+    """The `uplo` triangle of every SPD matrix of A <- that of its inverse: potrf_batched and potri_batched in one
+    pass, the same bits.  -> potrf_batched's info; a failing matrix is left as potrf_batched leaves it"""
+    return _inverse("chol_poinv_batched", A, uplo)
+
+
+def invdiag_batched(A, uplo: int = ChamLower):
+    """-> (D, info): the diagonal of inv(L L^T) of every factor in A (the marginal variances of a local Gaussian
+    process) as a new contiguous (batch, n) tensor of A's dtype on A's device, the bits of the diagonal potri_batched
+    would write; A is only read.  info[b] = j: an exact zero at L_jj of matrix b, D[b] is then not written"""
+    import torch
+
+    dt, code, n, lda, sa, batch = _images_of_A(A, uplo)
+    _require_device(A)
+    D = torch.empty((batch, n), dtype=A.dtype, device=A.device)
+    info, pinfo = _info(batch)
+    check("chol_invdiag_batched", lib().chol_invdiag_batched(code, dt, n, A.data_ptr(), lda, sa, D.data_ptr(), n,
+                                                             batch, pinfo))
+    return D, info
+
+
 def last_batched_stats() -> dict:
     """The last batched call (chol_last_batched_stats)"""
     v = (C.c_double * 8)()
@@ -215,4 +263,5 @@ def last_batched_stats() -> dict:
 
 
 __all__ = ["potrf_batched", "potrs_batched", "posv_batched", "chud_batched", "chdd_batched", "trtrs_batched",
-           "trmm_batched", "logdet_batched", "last_batched_stats"]
+           "trmm_batched", "logdet_batched", "trtri_batched", "potri_batched", "poinv_batched", "invdiag_batched",
+           "last_batched_stats"]

@@ -23,6 +23,9 @@
 // One half of such a factor alone (chol_trtrs_batched, chol_trmm_batched, chol_logdet_batched) is a third family on the
 // same rows, k_half_rows: the forward or the backward sweep of the solve on its own, the two products with L and L^T,
 // and a small kernel that reads the diagonal alone for the log-determinant.
+// The explicit inverses (chol_trtri_batched, chol_potri_batched, chol_poinv_batched, chol_invdiag_batched) are a fourth
+// family on the same rows, k_inv_rows: inv(L) and then inv(L)^T inv(L) built in place in the one register array, by
+// broadcasts alone.
 // (compiled with -ffp-contract=off: only the fma() calls below fuse)
 #include <hip/hip_runtime.h>
 
@@ -142,6 +145,42 @@ __device__ __forceinline__ void store_rows(const T (&a)[NP], T *Ab, long lda, in
       }
     }
   }
+}
+
+// The right-looking factorisation of the rows in a[] for k_inv_rows: the loop of k_batched below, statement for
+// statement (k_batched keeps its own copy: called from there, this function changes its register allocation, to 106
+// from 56 VGPRs at fp64 and order 16).  -> LAPACK's info of this lane's matrix, the same in every lane of the
+// sub-group; r: 1 / L(i,i)
+template <typename T, int NP>
+__device__ __forceinline__ int factor_rows(T (&a)[NP], int n, int i, T &r) {
+  int bad = 0;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    if (j < n) {
+      const T d = bcast<T, NP>(a[j], j);
+      if (!bad && !(d > T(0))) bad = j + 1;
+      const T piv = sqrt_(d), rj = T(1) / piv;
+      a[j] = i == j ? piv : a[j] * rj;
+      if (i == j) r = rj;
+#pragma unroll
+      for (int m = j + 1; m < NP; ++m)
+        if ((m & ~7) < n) a[m] = fma_(-a[j], bcast<T, NP>(a[j], m), a[m]);
+    }
+  }
+  return bad;
+}
+
+// The first exact zero on the diagonal of the factor in a[] (1-based, 0: none), the same in every lane of the
+// sub-group; r: 1 / L(i,i) (+0 in a lane without a row).  (k_batched's and k_half_rows' check, for k_inv_rows)
+template <typename T, int NP>
+__device__ __forceinline__ int diagonal_of_rows(const T (&a)[NP], int sub, int i, bool live, T &r) {
+  T d = T(1);
+#pragma unroll
+  for (int k = 0; k < NP; ++k)
+    if (i == k) d = a[k];
+  const unsigned long long z = __ballot(live && d == T(0)) >> (sub * NP) & (NP == 64 ? ~0ull : (1ull << NP) - 1);
+  r = live ? T(1) / d : T(0);
+  return z ? __ffsll((long long)z) : 0;
 }
 
 // Registers: the row is NP sizeof(T) / 4 VGPRs -- 128 at fp64 and order 64, which with the solve's values stays under
@@ -502,6 +541,175 @@ __global__ __launch_bounds__(BATCHED_THREADS) void k_diag_logdet(const T *A, lon
   }
 }
 
+// ---------------------------------------------------------------- the inverses: trtri, potri, poinv, invdiag
+enum { INV_TRTRI = 0, INV_POTRI = 1, INV_POINV = 2, INV_DIAG = 3 };
+
+template <typename T>
+struct InvArgs {
+  T *A;
+  T *D;  // (invdiag: n elements per matrix; A is only read then)
+  long lda, strideA, strideD;
+  int n, batch;
+  int vec;    // as BatchedArgs
+  int *info;  // batch words
+  int *first;
+};
+
+// Column i of W = inv(L) from lane i, whose t[k] = W(k,i), k >= i, into the `uplo` triangle: Lower stores the column
+// as it is (a run of consecutive addresses per lane, in 16-byte pieces where the image allows them and the piece lies
+// inside the triangle: load_rows<UPPER> mirrored), Upper stores it as row i of inv(U) = W^T (a wave writes whole
+// columns)
+template <typename T, int NP, bool UPPER>
+__device__ __forceinline__ void store_cols(const T (&t)[NP], T *Ab, long lda, int n, int i, bool live, bool vec) {
+  if constexpr (UPPER) {
+#pragma unroll
+    for (int k = 0; k < NP; ++k)
+      if (k < n && live && k >= i) Ab[i + (long)k * lda] = t[k];
+  } else {
+    constexpr int W = 16 / (int)sizeof(T);
+    using V = typename Vec16<T>::type;
+    T *col = Ab + (long)i * lda;
+#pragma unroll
+    for (int c = 0; c < NP; c += W) {
+      if (c < n && live) {
+        if (vec && c >= i && c + W <= n) {
+          V v;
+          T *e = reinterpret_cast<T *>(&v);
+#pragma unroll
+          for (int q = 0; q < W; ++q) e[q] = t[c + q];
+          *reinterpret_cast<V *>(col + c) = v;
+        } else {
+#pragma unroll
+          for (int q = 0; q < W; ++q)
+            if (c + q >= i && c + q < n) col[c + q] = t[c + q];
+        }
+      }
+    }
+  }
+}
+
+// The inverses in the rows k_batched keeps, in ONE register array.  Lane i loads row i of L into t[m], m <= i, with +0
+// beyond the triangle; column i of W = inv(L) needs the slots k >= i, the complement but for the diagonal, whose
+// L(i,i) lives on as r = 1 / L(i,i).  So the column is built in place, right-looking (the header's chain, which is the
+// forward sweep of k_half_rows applied to e_i and started at step i): t[i] = 1, and at step j the lanes i <= j make
+// y = t[j] r_j final and update t[k] <- fma(-L(k,j), y, t[k]), k > j, with L(k,j) = t[j] of lane k, which lane k
+// (k > j: not yet started) still holds.  The lanes i > j are left alone by a select, not by a product with the +0 they
+// hold: their slots are L's, and a NaN or Inf in column j of L must not reach the columns of W after j.
+// The product X = W^T W is built in place as well: row i of X needs the slots m <= i, which hold L (dead by now) and
+// are set to +0, the diagonal slot too (W(i,i) is r).  Step k, ascending, adds W(k,i) W(k,m) to t[m] for m <= k in
+// the lanes i <= k, W(k,m) = t[k] of lane m; slot k is written last in its step, after every lane has read it.  The
+// slots m > i of a lane receive sums that belong to nothing; they are dead (column entries of the steps before) and
+// never stored.  The diagonal of X alone (invdiag) needs no broadcast: x_i = sum over k >= i of W(k,i)^2.
+// No reduction anywhere: n^2 / 2 broadcasts per phase.  Registers: one row, as k_batched (DESIGN.md 3p has the table).
+template <typename T, int NP, bool UPPER, int MODE>
+__global__ __launch_bounds__(BATCHED_THREADS) void k_inv_rows(InvArgs<T> p) {
+  constexpr int M = 64 / NP;
+  const int lane = threadIdx.x & 63;
+  const long wave = (long)blockIdx.x * (BATCHED_THREADS / 64) + (threadIdx.x >> 6);
+  if (wave * M >= p.batch) return;  // (a whole wavefront)
+  const int sub = lane / NP, i = lane % NP, n = p.n;
+  const long b = wave * M + sub;
+  const bool live = b < p.batch && i < n;
+  T *Ab = p.A + (live ? b : 0) * p.strideA;
+
+  T t[NP];
+  load_rows<T, NP, UPPER>(t, Ab, p.lda, n, i, live, p.vec != 0);
+
+  int bad;
+  T r = T(0);  // 1 / L(i,i)
+  if constexpr (MODE == INV_POINV) {
+    bad = factor_rows<T, NP>(t, n, i, r);
+    // (a failed matrix is left as potrf leaves it; the others keep the factor in registers)
+    store_rows<T, NP, UPPER>(t, Ab, p.lda, bad - 1, i, live && bad, p.vec != 0);
+  } else {
+    bad = diagonal_of_rows<T, NP>(t, sub, i, live, r);
+  }
+  if (live && i == 0) {
+    p.info[b] = bad;
+    if (bad) atomicMin(p.first, (int)(b < INT_MAX ? b + 1 : INT_MAX));
+  }
+  const bool wr = live && !bad;  // (a failed matrix computes on, in its own lanes, and stores nothing more)
+
+  // W = inv(L): t[k] = W(k,i), k >= i, from e_i (factor_rows leaves its updates beyond the triangle, not +0)
+#pragma unroll
+  for (int k = 0; k < NP; ++k) t[k] = i == k ? T(1) : i < k ? T(0) : t[k];
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    if (j < n) {
+      const bool on = i <= j;
+      const T lj = t[j];  // (the lanes k > j: L(k,j))
+      const T y = lj * bcast<T, NP>(r, j);
+      t[j] = on ? y : lj;
+#pragma unroll
+      for (int k = j + 1; k < NP; ++k) {
+        if ((k & ~7) < n) {
+          const T u = fma_(-bcast<T, NP>(lj, k), y, t[k]);
+          t[k] = on ? u : t[k];
+        }
+      }
+    }
+  }
+  if constexpr (MODE == INV_TRTRI) {
+    store_cols<T, NP, UPPER>(t, Ab, p.lda, n, i, wr, p.vec != 0);
+    return;
+  }
+
+  if constexpr (MODE == INV_DIAG) {
+    T s = T(0);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+      if (k < n) {
+        const T u = fma_(t[k], t[k], s);
+        s = i <= k ? u : s;
+      }
+    }
+    if (wr) p.D[b * p.strideD + i] = s;
+    return;
+  }
+
+  // X = W^T W: t[m] = X(i,m), m <= i
+#pragma unroll
+  for (int m = 0; m < NP; ++m) t[m] = i >= m ? T(0) : t[m];
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    if (k < n) {
+      const bool on = i <= k;
+      const T wk = t[k];                // (the lanes m < k: W(k,m))
+      const T ck = i == k ? r : wk;     // W(k,i)
+#pragma unroll
+      for (int m = 0; m < k; ++m) {
+        const T u = fma_(ck, bcast<T, NP>(wk, m), t[m]);
+        t[m] = on ? u : t[m];
+      }
+      const T u = fma_(ck, bcast<T, NP>(r, k), wk);  // (lane k: r r + 0)
+      t[k] = on ? u : wk;
+    }
+  }
+  store_rows<T, NP, UPPER>(t, Ab, p.lda, n, i, wr, p.vec != 0);
+}
+
+template <typename T, int NP, bool UPPER>
+void launch_inv_mode(int mode, hipStream_t s, unsigned grid, const InvArgs<T> &p) {
+  if (mode == INV_TRTRI) k_inv_rows<T, NP, UPPER, INV_TRTRI><<<grid, BATCHED_THREADS, 0, s>>>(p);
+  else if (mode == INV_POTRI) k_inv_rows<T, NP, UPPER, INV_POTRI><<<grid, BATCHED_THREADS, 0, s>>>(p);
+  else if (mode == INV_POINV) k_inv_rows<T, NP, UPPER, INV_POINV><<<grid, BATCHED_THREADS, 0, s>>>(p);
+  else k_inv_rows<T, NP, UPPER, INV_DIAG><<<grid, BATCHED_THREADS, 0, s>>>(p);
+}
+template <typename T, int NP>
+void launch_inv_uplo(bool upper, int mode, hipStream_t s, unsigned grid, const InvArgs<T> &p) {
+  if (upper) launch_inv_mode<T, NP, true>(mode, s, grid, p);
+  else launch_inv_mode<T, NP, false>(mode, s, grid, p);
+}
+template <typename T>
+void launch_inv_rows(bool upper, int mode, hipStream_t s, unsigned grid, const InvArgs<T> &p) {
+  switch (padded_order(p.n)) {
+    case 8: return launch_inv_uplo<T, 8>(upper, mode, s, grid, p);
+    case 16: return launch_inv_uplo<T, 16>(upper, mode, s, grid, p);
+    case 32: return launch_inv_uplo<T, 32>(upper, mode, s, grid, p);
+    default: return launch_inv_uplo<T, 64>(upper, mode, s, grid, p);
+  }
+}
+
 // ---------------------------------------------------------------- host
 ScratchPool<1> bt;  // [0]: the first-failure word, then (at 16 bytes) the batch words of info
 hipEvent_t bt_ev[4] = {};
@@ -516,6 +724,7 @@ constexpr ArgPos POS_SOLVE = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 0};
 constexpr ArgPos POS_TRTRS = {1, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 2};
 constexpr ArgPos POS_TRMM = {1, 3, 4, 5, 7, 8, 9, 10, 11, 12, 13, 2};  // (6: alpha)
 constexpr ArgPos POS_LOGDET = {0, 1, 2, 0, 3, 4, 5, 0, 0, 0, 6, 0};    // (7: logdet)
+constexpr ArgPos POS_INVDIAG = {1, 2, 3, 0, 4, 5, 6, 7, 0, 8, 9, 0};   // (D: an n x 1 image in B's place)
 
 // what the messages call B and its arguments, and where n > 64 sends the caller
 struct ArgNames {
@@ -529,6 +738,9 @@ constexpr ArgNames NAMES_CHUD = {"V", "ldv", "r",
 constexpr ArgNames NAMES_HALF = {"B", "ldb", "nrhs",
                                  "use the descriptor routines (chol_trtrs_tile, chol_trmm_tile, chol_logdet_tile), "
                                  "which take any order"};
+constexpr ArgNames NAMES_INV = {"D", "n", "1",
+                                "use the descriptor routines (chol_trtri_tile, chol_potri_tile, chol_poinv_tile), "
+                                "which take any order"};
 
 // bytes from the base to the end of the last element of `batch` images of rows x cols
 inline unsigned long long span_bytes(long long rows, long long cols, long long ld, long long stride, long long batch,
@@ -714,6 +926,27 @@ int run_logdet(int dtype, int n, const void *A, int lda, long long strideA, int 
   });
 }
 
+// trtri, potri, poinv (D == nullptr, pos = POS_POTRF) and invdiag (D: n elements per matrix at strideD, A only read)
+int run_inv(const char *what, int mode, const ArgPos &pos, int uplo, int dtype, int n, void *A, int lda,
+            long long strideA, void *D, long long strideD, int batch, int *info) {
+  // (D is checked as an n x 1 image of leading dimension max(1, n): strideD >= n, also for n = 0)
+  if (int rc = check_images(what, pos, NAMES_INV, uplo, 0, dtype, n, n ? 1 : 0, A, lda, strideA, D, n > 1 ? n : 1,
+                            strideD, batch, false, info))
+    return rc < 0 ? rc : 0;
+  const size_t es = dtype == CHOL_REAL_DOUBLE ? sizeof(double) : sizeof(float);
+  const bool vec = rows_vec(A, lda, strideA, es);
+  const double tri = 0.5 * n * (n + 1.0), el = mode == INV_DIAG ? tri + n : 2.0 * tri;
+  return run_timed(what, n, batch, info, el * es * batch, [&](hipStream_t s, unsigned grid, int *dinfo, int *first) {
+    if (dtype == CHOL_REAL_DOUBLE) {
+      const InvArgs<double> p = {(double *)A, (double *)D, lda, strideA, strideD, n, batch, vec, dinfo, first};
+      launch_inv_rows<double>(uplo == CHOL_UPPER, mode, s, grid, p);
+    } else {
+      const InvArgs<float> p = {(float *)A, (float *)D, lda, strideA, strideD, n, batch, vec, dinfo, first};
+      launch_inv_rows<float>(uplo == CHOL_UPPER, mode, s, grid, p);
+    }
+  });
+}
+
 }  // namespace
 
 void cholmi::batched_release() {
@@ -769,6 +1002,24 @@ int chol_trmm_batched(int uplo, int trans, int dtype, int n, int nrhs, double al
 int chol_logdet_batched(int dtype, int n, const void *A, int lda, long long strideA, int batch, double *logdet,
                         int *info) {
   return run_logdet(dtype, n, A, lda, strideA, batch, logdet, info);
+}
+
+int chol_trtri_batched(int uplo, int dtype, int n, void *A, int lda, long long strideA, int batch, int *info) {
+  return run_inv("trtri_batched", INV_TRTRI, POS_POTRF, uplo, dtype, n, A, lda, strideA, nullptr, 0, batch, info);
+}
+
+int chol_potri_batched(int uplo, int dtype, int n, void *A, int lda, long long strideA, int batch, int *info) {
+  return run_inv("potri_batched", INV_POTRI, POS_POTRF, uplo, dtype, n, A, lda, strideA, nullptr, 0, batch, info);
+}
+
+int chol_poinv_batched(int uplo, int dtype, int n, void *A, int lda, long long strideA, int batch, int *info) {
+  return run_inv("poinv_batched", INV_POINV, POS_POTRF, uplo, dtype, n, A, lda, strideA, nullptr, 0, batch, info);
+}
+
+int chol_invdiag_batched(int uplo, int dtype, int n, const void *A, int lda, long long strideA, void *D,
+                         long long strideD, int batch, int *info) {
+  return run_inv("invdiag_batched", INV_DIAG, POS_INVDIAG, uplo, dtype, n, const_cast<void *>(A), lda, strideA, D,
+                 strideD, batch, info);
 }
 
 int chol_last_batched_stats(double *out8) {

@@ -530,10 +530,54 @@ int chol_trmm_batched(int uplo, int trans, int dtype, int n, int nrhs, double al
                       long long strideA, void *B, int ldb, long long strideB, int batch);
 int chol_logdet_batched(int dtype, int n, const void *A, int lda, long long strideA, int batch, double *logdet,
                         int *info);
+/* The explicit inverses of such factors (what chol_trtri_tile, chol_potri_tile and chol_poinv_tile are to the tiled
+ * side), in place: the stored triangle T becomes inv(T) (chol_trtri_batched), the triangle of inv(L L^T)
+ * (chol_potri_batched), or the `uplo` triangle of an SPD matrix becomes that of its inverse (chol_poinv_batched);
+ * chol_invdiag_batched returns the diagonal of inv(L L^T) alone (marginal variances, leave-one-out residuals).  The
+ * storage and argument rules are chol_potrf_batched's: column-major images at a fixed stride, lda >= max(1,n),
+ * strideA >= lda n; device pointers only; element alignment alone; 64-bit offsets; 0 <= n <= 64 (n > 64:
+ * CHOL_ERR_NOT_SUPPORTED; chol_trtri_tile, chol_potri_tile and chol_poinv_tile take any order); fp64 or fp32 by dtype,
+ * fp32 in single precision throughout; Lower and Upper; zero sizes (n, batch) return 0 with nothing written on the
+ * device; synchronous, on the library's main stream.  Only the `uplo` triangle is read or written: the other strict
+ * triangle, the lda - n rows under a column and the gaps come back bit for bit and may hold NaN.
+ * invdiag: A IS ONLY READ; D + b strideD receives the n diagonal entries of matrix b's inverse in A's dtype,
+ * strideD >= n, a device pointer; the address ranges of A and D overlapping are an argument error at D's position.
+ *
+ * The arithmetic, fixed (L the lower factor however it is stored, Upper holds U = L^T; r_j = 1 / L(j,j); each a b + c
+ * one fused multiply-add; W = inv(L)):
+ *   trtri  column c of W on its own:  b_c = 1, b_i = +0 (i > c);
+ *          for j = c..n-1 ascending:  W(j,c) = b_j r_j;  b_i = fma(-L(i,j), W(j,c), b_i) (i > j)
+ *          Lower receives W, Upper inv(U) = W^T.  This is the forward sweep of chol_trtrs_batched applied to e_c and
+ *          started at step c: for a finite factor the bits are those of the lower triangle of trtrs_batched(F, I).
+ *   potri  X(i,m), i >= m:  s = +0;  for k = i..n-1 ascending:  s = fma(W(k,i), W(k,m), s)
+ *          X = W^T W = inv(L L^T); Lower receives its lower triangle, Upper the upper one (the same bits, mirrored).
+ *   poinv  potrf (the chain of chol_potrf_batched) then potri in one pass, the factor never stored: the bits of the
+ *          two calls.
+ *   invdiag  D(i) = X(i,i) of potri, bit for bit.
+ *   The terms outside an entry's sum are left out, not multiplied by a stored zero: a NaN at L(p,q) reaches exactly
+ *   the entries W(k,c) with c <= q and k >= p, and of X the entries X(i,m) with m <= q; every other entry keeps its
+ *   bits.  The order depends on n and that matrix's data alone: not on uplo, the layout, the matrix's place in the
+ *   batch, its wavefront's other matrices, or whether the call is repeated.
+ *
+ * info (a host array of `batch` ints, or NULL).  trtri, potri, invdiag: info[b] = j (1-based) is the first exact zero
+ * on the stored diagonal; that matrix's A (invdiag: D) is then untouched, as chol_trtri_tile and chol_trtrs_batched
+ * leave it.  poinv: potrf's info, and that matrix is left as chol_potrf_batched leaves it (the columns before the
+ * failing one hold the factor's, the rest is as it was given).  A failing matrix never disturbs another one, also not
+ * one that shares its wavefront.  Returns 0, or b + 1 of the first matrix with info[b] > 0; negative: the position of
+ * a bad argument or CHOL_ERR_*.
+ *
+ * Argument positions: trtri, potri and poinv 1 uplo, 2 dtype, 3 n, 4 A, 5 lda, 6 strideA, 7 batch; invdiag 1 uplo,
+ * 2 dtype, 3 n, 4 A, 5 lda, 6 strideA, 7 D, 8 strideD, 9 batch. */
+int chol_trtri_batched(int uplo, int dtype, int n, void *A, int lda, long long strideA, int batch, int *info);
+int chol_potri_batched(int uplo, int dtype, int n, void *A, int lda, long long strideA, int batch, int *info);
+int chol_poinv_batched(int uplo, int dtype, int n, void *A, int lda, long long strideA, int batch, int *info);
+int chol_invdiag_batched(int uplo, int dtype, int n, const void *A, int lda, long long strideA, void *D,
+                         long long strideD, int batch, int *info);
 /* The last batched call: total time and kernel time [ms] (the library's own events); batch; n; matrices per wavefront;
  * workgroups launched; the bytes the algorithm must move (the stored triangles read and written, plus B read and
  * written; chud and chdd: the triangles read and written, plus V read; trtrs and trmm: the triangle read, plus B read
- * and written -- B written alone with alpha == 0; logdet: n diagonal elements read and 8 bytes written); 0. */
+ * and written -- B written alone with alpha == 0; logdet: n diagonal elements read and 8 bytes written; trtri, potri
+ * and poinv: the triangles read and written; invdiag: the triangles read and n elements written); 0. */
 int chol_last_batched_stats(double *out8);
 
 /* One half of a Cholesky factor alone: the triangular solve, the triangular product and the log-determinant, on
